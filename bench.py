@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- leaf hashes/s and Merkle-root wall time on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--leaves-log2 26] [--maxlen 127]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--leaves-log2 26] [--maxlen 127] [--dump-outputs DIR] [--full]
 
 One "step" = one pass of the hot path (map -> reduce -> gather -> combine) over the whole
 synthetic workload, with the packed batches already resident in HBM.  The workload is
@@ -18,15 +18,25 @@ processes spawned before anything touches the GPU.  Fewer than N GPUs, or RCCL u
 run FAILS; it never reports a smaller N or another transport as if it were the requested one.
 
 Prints ONE JSON line on rank 0 (see the driver contract): `value` is whole-job leaf hashes/s;
-`roofline` prices the dominant kernel (map) against HBM (the spec'd bound), `roofline_reduce`
-the reduction, `valu_roofline` carries the bound the path actually sits under -- VALU issue: the
-shader clock each kernel HOLDS, measured in-kernel in this run, and the dual-issue floor of its
-instruction stream (static counts of the loaded library);
+`ms_per_step` the wall time of one timed step; `roofline` prices the dominant kernel (map) against
+HBM (the spec'd bound), `roofline_reduce` the reduction, both from the HIP events of the timed
+steps; `valu_roofline` the static VALU counts of the loaded library against the same steps;
 `root_matches_golden` checks the timed path's root (and every rank's sub-root) against
 tests/golden/big_roots.json, which holds what the reference's own CPU path printed for these
-streams; `cpu_baseline` is that CPU path (oracle/_ref, built from the reference sources) timed
-on the SAME 2^26-string stream on this box's host cores (one core: the path is serial; ~80 s); `long_strings` is the map
-kernel on `rndm 42 2^21 4096` (BASELINE configs[4]'s shape, one 4.3 GB batch).
+streams.
+
+A plain run does only that: set up, settle, warm up, time the K steps, print the line.  With
+--dump-outputs DIR it also writes what the last timed step computed: DIR/root.npy (the 8 words
+of the root, float64) and DIR/sub_roots.npy (every rank's sub-tree root, [ranks, 8] float64).
+
+--full adds the measurements that take runs of their own (each can be left out with its --no-*
+option): `valu_roofline` gains the shader clock each kernel HOLDS, measured in-kernel in a child
+process; `cpu_baseline` is the reference's CPU path (oracle/_ref, built from the reference sources)
+timed on the SAME 2^26-string stream on this box's host cores (one core: the path is serial; ~80 s);
+`reference_shapes`, `two_stream_overlap`, `pipeline_pcie_inclusive` and `from_file_on_stdin` run the
+same stream in other shapes and schedules; `long_strings` is the map kernel on `rndm 42 2^21 4096`
+(BASELINE configs[4]'s shape, one 4.3 GB batch), `config5_full` configs[4] at full size; N > 1
+adds the `vkmr hip:all` one-process check.
 """
 import argparse
 import ctypes as C
@@ -60,6 +70,11 @@ def parse():
     p.add_argument("--batch-log2", type=int, default=None,
                    help="strings per map launch (default: leaves-log2, the GPU's whole share as ONE packed batch -- 4.4 GB, well inside "
                         "the format's 2^32 words; the reference's Vulkan-sized batches hold <= 2^23, which costs 3 %% in launch tails)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed as DIR/root.npy and DIR/sub_roots.npy (the digest words, float64)")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements (clock leg, CPU baseline, other shapes and schedules, long strings, "
+                        "configs[4] at full size, the hip:all check); the --no-* options below leave single ones out")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--cpu-sample-log2", type=int, default=None,
                    help="give the CPU baseline only the first 2^k strings of the stream (default: the whole stream, about 80 s for 2^26)")
@@ -160,8 +175,10 @@ def cpu_baseline(seed, maxlen, sample_log2, full_log2):
                            C.c_void_p(leaves.ctypes.data), C.c_int(1))
     L.oracle_root_inplace(C.c_void_p(leaves.ctypes.data), C.c_size_t(n), C.c_void_p(root.ctypes.data))
     dt = time.perf_counter() - t0
+    from vk_merkle_roots_amd.engine import digest_hex
     return {"value": n / dt, "unit": "leaf hashes/s", "cores": 1, "kind": "port",
-            "sample": sample.replace("via stdin", "packed") + " (hash + tree only)", "host_cores": os.cpu_count(), "seconds": dt, "leaves": n}
+            "sample": sample.replace("via stdin", "packed") + " (hash + tree only)", "host_cores": os.cpu_count(), "seconds": dt, "leaves": n,
+            "root": digest_hex(root)}
 
 
 # ---- secondary measurements (N = 1 only, outside the timed region) ---------------------------------
@@ -519,6 +536,17 @@ def check_against_golden(golden, seed, world, root_hex, sub_roots):
     return root_ok, subs_ok
 
 
+def dump_outputs(path, root_hex, sub_roots):
+    """--dump-outputs: the root and the sub-tree roots of the last timed step as float64 arrays of their digest words
+    (H[0..7]; every uint32 is exact in float64)."""
+    os.makedirs(path, exist_ok=True)
+
+    def words(h):
+        return np.frombuffer(bytes.fromhex(h), dtype=">u4").astype(np.float64)
+    np.save(os.path.join(path, "root.npy"), words(root_hex))
+    np.save(os.path.join(path, "sub_roots.npy"), np.stack([words(h) for h in sub_roots]))
+
+
 def golden_big_roots(leaves_log2, maxlen):
     path = os.path.join(ROOT, "tests", "golden", "big_roots.json")
     try:
@@ -753,6 +781,8 @@ def main():
         root_hex = digest_hex(final)
         sub_roots = ([digest_hex(r) for r in dev.download(d_all, 32 * world).reshape(-1, 8)] if comm is not None or a.rehearse_gloo
                      else [digest_hex(dev.download(d_sub, 32))])
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, root_hex, sub_roots)
         # the timed path's own result against what the reference CPU path printed for these streams
         golden = golden_big_roots(a.leaves_log2, a.maxlen) if a.seed == 42 else None
         root_ok, subs_ok = check_against_golden(golden, a.seed, world, root_hex, sub_roots)
@@ -804,7 +834,7 @@ def main():
             "gather_ms": gather_ms,
             "setup": {"generate_s": t_gen, "h2d_pageable_s": t_h2d},
         }
-        if world == 1 and not a.no_pipeline and not a.levels_variant and nbatches == 1 and nslices == 1 and a.leaves_log2 > 23:
+        if a.full and world == 1 and not a.no_pipeline and not a.levels_variant and nbatches == 1 and nslices == 1 and a.leaves_log2 > 23:
             # the same step in the reference's shapes -- map launches of 2^23 strings (its batch, Batches.h:131-134), each its
             # OWN packed batch (own data words: the launch picks its fetch mode from them, as a real 2^23-string batch would),
             # slices of 2^23 digests (its slice, SHA-256vk.cpp:23) reduced by one batched call, roots combined on the device
@@ -839,7 +869,7 @@ def main():
             d_s8.free()
             dev.map_async(d_batches[0][0], d_batches[0][1], d_batches[0][2], bstr, d_digests)   # kernel_info reports the main shape again
             dev.sync()
-        if world == 1 and not a.no_pipeline and not a.levels_variant and nbatches == 1 and nslices == 1:
+        if a.full and world == 1 and not a.no_pipeline and not a.levels_variant and nbatches == 1 and nslices == 1:
             ts = two_stream_rate(dev, vk, d_batches[0], bstr, n, slice_height)
             out["two_stream_overlap"] = {"leaf_hashes_per_s": ts["leaf_hashes_per_s"], "ms_per_step": ts["ms_per_step"], "what": ts["what"],
                                          "roots_match": all(digest_hex(r) == root_hex for r in ts["roots"])}
@@ -848,7 +878,7 @@ def main():
                 b_[0].free()
                 b_[2].free()
             d_digests.free()
-        if world == 1 and not a.no_pipeline and not a.levels_variant:
+        if a.full and world == 1 and not a.no_pipeline and not a.levels_variant:
             pl_bstr = min(n, 1 << 23)   # the stream processor's shape: batches small enough for copies to hide behind kernels
             pl = pipeline_rate(vk, batch, pl_bstr, slice_log2 if nslices > 1 else min(slice_log2, 23), device=local_rank)
             out["pipeline_pcie_inclusive"] = {"leaf_hashes_per_s": pl["leaf_hashes_per_s"], "ms": pl["ms"], "h2d_GBps": pl["h2d_GBps"],
@@ -857,7 +887,7 @@ def main():
                                               "what": "libvkmr_pipeline.so: strings staged in the C++ stream processor's pinned batches, then its own "
                                                       "schedule -- per batch H2D on the copy stream and the map kernel behind it, slices of 2^23 to "
                                                       "Reductions as they fill, combine on the device (Mappings::Map / Reductions of `vkmr hip:0`)"}
-        if world == 1 and not a.no_pipeline and not a.levels_variant:
+        if a.full and world == 1 and not a.no_pipeline and not a.levels_variant:
             try:
                 ff = from_file_rate(a.seed, n, a.maxlen, local_rank)
             except Exception as e:   # no room for the stream in the temporary directory, a time-out ...: the leg is reported as failed, the line is still printed
@@ -865,9 +895,9 @@ def main():
             if "root_hex" in ff:
                 ff["root_matches"] = ff.pop("root_hex") == root_hex and ff["items"] == n
             out["from_file_on_stdin"] = ff
-        if world == 1 and not a.no_long_strings:
+        if a.full and world == 1 and not a.no_long_strings:
             out["long_strings"] = long_strings_rate(dev, vk, a.seed)
-        if world == 1 and not a.no_config5 and not a.no_long_strings and a.leaves_log2 >= 24:
+        if a.full and world == 1 and not a.no_config5 and not a.no_long_strings and a.leaves_log2 >= 24:
             try:
                 out["config5_full"] = config5_full(dev, vk, a.seed)
             except Exception as e:   # out of host or device memory on an unusual box: the leg is reported as failed, the line is still printed
@@ -904,8 +934,8 @@ def main():
             return cb
 
         if world == 1:
-            out["valu_roofline"] = valu_roofline_block(None if a.no_clock_leg else clock_leg(a.seed, a.maxlen, a.leaves_log2))
-            if not a.no_cpu_baseline:
+            out["valu_roofline"] = valu_roofline_block(None if (not a.full or a.no_clock_leg) else clock_leg(a.seed, a.maxlen, a.leaves_log2))
+            if a.full and not a.no_cpu_baseline:
                 out["cpu_baseline"] = cpu_baseline_block()
     # Every rank leaves the data path together BEFORE rank 0 runs its one-process probe: the other ranks must not sit in
     # a barrier under the watchdog while rank 0 spends up to two minutes in child processes, and must not tear their
@@ -924,11 +954,11 @@ def main():
             enter("clock leg")
             for buf in [b_[0] for b_ in d_batches] + [b_[2] for b_ in d_batches] + [d_digests]:
                 buf.free()
-            out["valu_roofline"] = valu_roofline_block(None if (a.no_clock_leg or collective != "nccl") else clock_leg(a.seed, a.maxlen, a.leaves_log2))
-            if not a.no_cpu_baseline:
+            out["valu_roofline"] = valu_roofline_block(None if (not a.full or a.no_clock_leg or collective != "nccl") else clock_leg(a.seed, a.maxlen, a.leaves_log2))
+            if a.full and not a.no_cpu_baseline:
                 enter("cpu baseline")
                 out["cpu_baseline"] = cpu_baseline_block()
-        if world > 1 and collective == "nccl":
+        if a.full and world > 1 and collective == "nccl":
             enter("hip:all probe")
             out["hip_all_one_process_check"] = hip_all_check(timeout_s=60)
         os.write(result_fd, (json.dumps(out) + "\n").encode())

@@ -1,4 +1,5 @@
 import ctypes as C
+import hashlib
 import json
 import os
 import subprocess
@@ -12,6 +13,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden", "vectors.json")
+REF_CHECKS = os.path.join(ROOT, "tests", "golden", "ref_checks.json")
 ORACLE_DIR = os.path.join(ROOT, "oracle")
 REF_DIR = os.path.join(ORACLE_DIR, "_ref")
 
@@ -33,9 +35,33 @@ def golden_pattern(n, salt):
     return bytes(out)
 
 
+def ref_check_inputs():
+    """The messages and the string lists test_oracle.py::test_oracle_vs_compiled_reference hashes (the reference's outputs
+    for them are recorded in tests/golden/ref_checks.json by tests/golden/make_ref_checks.py)."""
+    rng = np.random.default_rng(11)
+    msgs = [rng.integers(0, 256, size=n, dtype=np.uint8).tobytes() for n in list(range(0, 200, 3)) + [1000, 5000]]
+    trees = [[rng.integers(0, 256, size=int(rng.integers(1, 200)), dtype=np.uint8).tobytes() for _ in range(n)]
+             for n in [1, 2, 3, 5, 8, 13, 64, 77, 256, 301]]
+    return msgs, trees
+
+
+def strings_sha256(strs):
+    """sha256 over the strings, each preceded by its length: pins a list of inputs in a fixture."""
+    h = hashlib.sha256()
+    for s in strs:
+        h.update(len(s).to_bytes(8, "little") + s)
+    return h.hexdigest()
+
+
 @pytest.fixture(scope="session")
 def golden():
     with open(GOLDEN) as f:
+        return json.load(f)
+
+
+@pytest.fixture(scope="session")
+def ref_checks():
+    with open(REF_CHECKS) as f:
         return json.load(f)
 
 
@@ -121,14 +147,13 @@ def oracle():
 
 @pytest.fixture(scope="session")
 def ref_lib():
-    """The reference's own CPU path compiled into oracle/_ref (built where /root/reference
-    exists; travels prebuilt to the GPU box).  Skips when absent."""
+    """The reference's own CPU path compiled into oracle/_ref (oracle/Makefile `ref`, where the reference sources are
+    present), or None where it is absent: the tests then use what it returned, recorded in tests/golden/."""
     so = os.path.join(REF_DIR, "libvkmr_ref.so")
     if not os.path.exists(so):
-        if os.path.isdir("/root/reference/src/vkmr"):
-            subprocess.check_call(["make", "-C", ORACLE_DIR, "ref"], stdout=subprocess.DEVNULL)
-        else:
-            pytest.skip("oracle/_ref not built and /root/reference absent")
+        subprocess.check_call(["make", "-C", ORACLE_DIR, "ref"], stdout=subprocess.DEVNULL)
+    if not os.path.exists(so):
+        return None
     L = C.CDLL(so)
     L.ref_sha256d.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p]
     L.ref_sha256.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p]

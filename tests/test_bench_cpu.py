@@ -60,10 +60,11 @@ def test_bench_line_contract_and_root(fake_lib, oracle, extra):
 
 
 @pytest.mark.parametrize("n", [2, 3])
-def test_bench_spawns_its_ranks_and_combines_in_rank_order(fake_lib, oracle, n):
+def test_bench_spawns_its_ranks_and_combines_in_rank_order(fake_lib, oracle, n, tmp_path):
     """`python bench.py --gpus N --rehearse-gloo`: the script starts the N ranks itself (no launcher), rank r hashes
-    rndm 42+r, the sub-roots are gathered in rank order and combined with the duplicate-last rule."""
-    r = run_bench(fake_lib, "--gpus", str(n), "--rehearse-gloo", "--leaves-log2", "12", "--steps", "2", "--warmup", "1")
+    rndm 42+r, the sub-roots are gathered in rank order and combined with the duplicate-last rule; --dump-outputs holds both."""
+    out = tmp_path / "outputs"
+    r = run_bench(fake_lib, "--gpus", str(n), "--rehearse-gloo", "--leaves-log2", "12", "--steps", "2", "--warmup", "1", "--dump-outputs", str(out))
     assert r.returncode == 0, r.stderr[-1500:].decode()
     lines = r.stdout.decode().strip().splitlines()
     assert len(lines) == 1
@@ -73,6 +74,8 @@ def test_bench_spawns_its_ranks_and_combines_in_rank_order(fake_lib, oracle, n):
     assert d["sub_roots"] == [oracle.hex(s) for s in subs]
     assert d["root"] == oracle.hex(oracle.root(subs))
     assert d["value"] > 0 and d["config"]["leaves_total"] == n << 12
+    assert (np.load(out / "sub_roots.npy") == subs.astype(np.float64)).all()
+    assert (np.load(out / "root.npy") == oracle.root(subs).astype(np.float64)).all()
 
 
 def _leaves(oracle, seed, n):
@@ -86,13 +89,41 @@ def test_bench_secondary_blocks_agree_with_the_timed_root(fake_lib, oracle):
     digest buffers) are separate drivings of the same ABI: each must reproduce the timed path's root."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["VKMR_HIP_LIB"] = fake_lib
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--leaves-log2", "12", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-                        "--no-long-strings"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=600)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--leaves-log2", "12", "--steps", "2", "--warmup", "1", "--full",
+                        "--no-cpu-baseline", "--no-long-strings"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-1500:].decode()
     d = json.loads(r.stdout.decode().strip().splitlines()[-1])
     assert d["root"] == oracle.hex(oracle_root(oracle, 42, 1 << 12))
     assert d["pipeline_pcie_inclusive"]["root_matches"] is True
     assert d["two_stream_overlap"]["roots_match"] is True
+
+
+SECONDARY = {"reference_shapes", "two_stream_overlap", "pipeline_pcie_inclusive", "from_file_on_stdin", "long_strings", "config5_full", "cpu_baseline",
+             "hip_all_one_process_check"}
+
+
+def test_a_plain_run_times_the_headline_only_and_dumps_its_last_step(fake_lib, oracle, tmp_path):
+    """Without --full the line carries the headline and what the timed steps' own events give, and none of the secondary
+    legs runs (not even the clock leg); --dump-outputs DIR holds the last timed step's root and sub-roots as float64 words."""
+    out = tmp_path / "outputs"
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    env["VKMR_HIP_LIB"] = fake_lib
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--leaves-log2", "12", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(out)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=600)
+    assert r.returncode == 0, r.stderr[-1500:].decode()
+    lines = r.stdout.decode().strip().splitlines()
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    for k in REQUIRED + ["roofline_reduce"]:
+        assert k in d, k
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["unit"] == "leaf hashes/s" and d["higher_is_better"] is True and d["dtype"] == "u32"
+    assert not SECONDARY & set(d), SECONDARY & set(d)
+    assert d["valu_roofline"]["clock"] is None
+    want = oracle_root(oracle, 42, 1 << 12)
+    assert d["root"] == oracle.hex(want)
+    root, subs = np.load(out / "root.npy"), np.load(out / "sub_roots.npy")
+    assert root.dtype == np.float64 and root.shape == (8,) and subs.dtype == np.float64 and subs.shape == (1, 8)
+    assert (root == want.astype(np.float64)).all() and (subs[0] == root).all()
 
 
 def test_an_n_rank_line_is_as_complete_as_the_one_rank_line(fake_lib, oracle):
@@ -102,7 +133,7 @@ def test_an_n_rank_line_is_as_complete_as_the_one_rank_line(fake_lib, oracle):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["VKMR_HIP_LIB"] = fake_lib
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--rehearse-gloo", "--leaves-log2", "10", "--steps", "1", "--warmup", "1",
-                        "--no-pipeline", "--no-long-strings"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=900)
+                        "--full", "--no-pipeline", "--no-long-strings"], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=900)
     assert r.returncode == 0, r.stderr[-1500:].decode()
     lines = r.stdout.decode().strip().splitlines()
     assert len(lines) == 1

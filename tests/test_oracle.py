@@ -1,15 +1,14 @@
 """The oracle (oracle/sha256d_oracle.c) pinned against the reference: golden vectors
 recorded from the reference's own CPU path (tests/golden/vectors.json), the compiled
-reference itself (oracle/_ref, when present) and an independent hashlib model."""
+reference itself (its recorded outputs, and oracle/_ref where present) and an independent hashlib model."""
 import ctypes as C
 import hashlib
 import os
 import subprocess
 
 import numpy as np
-import pytest
 
-from conftest import REF_DIR, golden_pattern
+from conftest import REF_DIR, golden_pattern, ref_check_inputs, strings_sha256
 
 
 def d256(b):
@@ -120,32 +119,45 @@ def test_g3_stream_packed_mt(oracle, golden):
     assert oracle.hex(oracle.root(leaves, threads=8)) == g["root"]
 
 
-def test_oracle_vs_compiled_reference(oracle, ref_lib):
-    """Leaf by leaf and root by root against the reference's own code (oracle/_ref)."""
-    rng = np.random.default_rng(11)
-    for n in list(range(0, 200, 3)) + [1000, 5000]:
-        msg = rng.integers(0, 256, size=n, dtype=np.uint8).tobytes()
-        out = C.create_string_buffer(32)
-        ref_lib.ref_sha256d(msg, n, out)
-        assert oracle.hex(oracle.leaf(msg)) == out.raw.hex(), n
-    for n in [1, 2, 3, 5, 8, 13, 64, 77, 256, 301]:
-        strs = [rng.integers(0, 256, size=int(rng.integers(1, 200)), dtype=np.uint8).tobytes() for _ in range(n)]
-        blob = b"".join(strs)
-        offs = np.zeros(n + 1, dtype=np.uint64)
-        offs[1:] = np.cumsum([len(s) for s in strs])
-        hexbuf = C.create_string_buffer(65)
-        ref_lib.ref_root(blob, offs.ctypes.data, n, hexbuf)
+def test_oracle_vs_compiled_reference(oracle, ref_lib, ref_checks):
+    """Leaf by leaf and root by root against the reference's own code: what it returned for these inputs
+    (tests/golden/ref_checks.json) and, where oracle/_ref is built, the compiled reference itself."""
+    msgs, trees = ref_check_inputs()
+    assert len(msgs) == len(ref_checks["leaves"]) and len(trees) == len(ref_checks["trees"])
+    for msg, rec in zip(msgs, ref_checks["leaves"]):
+        n = len(msg)
+        assert (n, hashlib.sha256(msg).hexdigest()) == (rec["len"], rec["input_sha256"]), "input differs from the recorded one"
+        got = oracle.hex(oracle.leaf(msg))
+        assert got == rec["sha256d"], n
+        if ref_lib is not None:
+            out = C.create_string_buffer(32)
+            ref_lib.ref_sha256d(msg, n, out)
+            assert got == out.raw.hex(), n
+    for strs, rec in zip(trees, ref_checks["trees"]):
+        n = len(strs)
+        assert (n, strings_sha256(strs)) == (rec["count"], rec["input_sha256"]), "input differs from the recorded one"
         leaves = np.stack([oracle.leaf(s) for s in strs])
-        assert oracle.hex(oracle.root(leaves)) == hexbuf.value.decode(), n
+        got = oracle.hex(oracle.root(leaves))
+        assert got == rec["root"], n
+        if ref_lib is not None:
+            blob = b"".join(strs)
+            offs = np.zeros(n + 1, dtype=np.uint64)
+            offs[1:] = np.cumsum([len(s) for s in strs])
+            hexbuf = C.create_string_buffer(65)
+            ref_lib.ref_root(blob, offs.ctypes.data, n, hexbuf)
+            assert got == hexbuf.value.decode(), n
 
 
-def test_reference_driver_matches_golden(golden):
-    exe = os.path.join(REF_DIR, "vkmr_cpu_ref")
-    if not os.path.exists(exe):
-        pytest.skip("oracle/_ref not built")
+def test_reference_driver_matches_golden(golden, ref_checks):
+    """The golden root of a stream is the one the reference's stdin driver prints: its recorded line
+    (tests/golden/ref_checks.json) and, where oracle/_ref is built, the driver itself."""
     s = golden["streams"]["L2_empty_lines"]
-    out = subprocess.run([exe], input=bytes.fromhex(s["stream_hex"]), stdout=subprocess.PIPE, stderr=subprocess.DEVNULL).stdout.decode()
-    assert f"CPU: computed root (of {s['items']} item(s), {s['bytes']} byte(s)) => {s['root']} in " in out
+    want = f"CPU: computed root (of {s['items']} item(s), {s['bytes']} byte(s)) => {s['root']} in "
+    assert ref_checks["driver"]["L2_empty_lines"] == want
+    exe = os.path.join(REF_DIR, "vkmr_cpu_ref")
+    if os.path.exists(exe):
+        out = subprocess.run([exe], input=bytes.fromhex(s["stream_hex"]), stdout=subprocess.PIPE, stderr=subprocess.DEVNULL).stdout.decode()
+        assert want in out
 
 
 def test_big_roots_fixture_is_consistent(oracle):

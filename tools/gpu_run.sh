@@ -7,7 +7,7 @@
 #   clock <log2> [variant] tools/kernel_clock.py on the stamped library (product twin, or the experiments twin with a variant)
 #   suite                  the GPU test suite + smoke
 #   bench [args]           one bench line
-#   measure                PMC passes -> profiles/pmc_latest.json, rocprofv3 kernel stats of the bench command, the bench line
+#   measure                PMC passes -> profiles/pmc_latest.json, rocprofv3 kernel stats of the bench command, the full bench line (--full)
 #   e2e [log2...]          `vkmr hip:0 < file` of 2^k strings (default 25 26): printed time and process wall, N runs each, the distribution
 #   frontend               VKMR_TIMING=1 phases, a pipe, hip-api stats and copy/kernel overlap of `vkmr hip:0`
 #   rehearsals             soaks against the oracle; torchrun --nproc 2 (gloo rehearsal; plain N=2 must fail on one GPU); --force-dist (RCCL, one rank)
@@ -55,7 +55,7 @@ measure)
   cp gpurun_out/pmc_$ROUND/summary.txt $OUT/pmc_summary.txt
   ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $GRAFT_REPO_ROOT/gpurun_out/prof_$ROUND -- python3 $GRAFT_REPO_ROOT/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-pipeline --no-clock-leg > $GRAFT_REPO_ROOT/$OUT/prof_bench.json 2> $GRAFT_REPO_ROOT/$OUT/prof_bench.err )
   find gpurun_out/prof_$ROUND -name "*kernel_stats.csv" -exec cp {} $OUT/kernel_stats.csv \;
-  timeout -k 10 600 python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
+  timeout -k 10 600 python bench.py --steps 20 --warmup 5 --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc=$?"
   ;;
 e2e)
   [ $# -eq 0 ] && set -- 25 26
@@ -98,7 +98,7 @@ print('process wall %.3f s; printed %s ms;' % (w, line.rsplit(' in ',1)[1]), ' |
 rehearsals)
   timeout -k 10 300 python3 tests/soak/soak_abi.py ${SOAK_ABI:-150} > $OUT/soak_abi.txt 2>&1; tail -2 $OUT/soak_abi.txt
   timeout -k 10 400 python3 tests/soak/soak_frontend.py ${SOAK_FRONTEND:-200} > $OUT/soak_frontend.txt 2>&1; tail -3 $OUT/soak_frontend.txt
-  timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --rehearse-gloo --steps 3 --warmup 1 --no-config5 --no-long-strings --cpu-sample-log2 20 > $OUT/bench_torchrun_gloo2.json 2> $OUT/bench_torchrun_gloo2.err; echo "torchrun rehearsal rc=$?"; python3 -c "
+  timeout -k 10 400 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 bench.py --gpus 2 --rehearse-gloo --steps 3 --warmup 1 --full --no-config5 --no-long-strings --cpu-sample-log2 20 > $OUT/bench_torchrun_gloo2.json 2> $OUT/bench_torchrun_gloo2.err; echo "torchrun rehearsal rc=$?"; python3 -c "
 import json
 d=json.loads(open('$OUT/bench_torchrun_gloo2.json').read().splitlines()[-1]); print({k:d.get(k) for k in ('n_gpus','ms_per_step','root_matches_golden','sub_roots_match_golden')}, d['config']['collective'], 'cpu_baseline' in d, 'valu_roofline' in d)"
   timeout -k 10 200 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29534 bench.py --gpus 2 --steps 2 > $OUT/bench_torchrun_2.json 2> $OUT/bench_torchrun_2.err; echo "torchrun N=2 on one GPU rc=$? (must be non-zero)"; wc -c $OUT/bench_torchrun_2.json
