@@ -236,6 +236,50 @@ VKMR_API vkmr_status vkmr_hip_reduce_levels_async(int dev, vkmr_stream s,
 VKMR_API size_t vkmr_hip_reduce_levels_scratch_bytes(uint64_t count);
 
 /*
+ * STORED TREE (the reference's proof "to do", README.md:118-120, for any number of leaves): every level of the tree
+ * vkmr_hip_reduce_async(count, height) computes, kept in HBM.  Level 0 is digests_dev itself (not copied); tree_dev
+ * holds levels 1..height back to back: level l has n_l = ceil(count / 2^l) cells and starts at cell
+ * sum over 1 <= j < l of n_j.  Node j of level l = SHA-256d(L[l-1][2j] || L[l-1][min(2j+1, n_{l-1}-1)]) (duplicate-last
+ * rule, also after the count has collapsed to one: the last-slice rule), so the last cell of tree_dev is the root that
+ * vkmr_hip_reduce_async writes.  Same height contract as every reduce; height == 0 (count == 1) writes nothing (the root
+ * is the leaf) and tree_dev may then be NULL.  One launch of the levels kernel per level: about the cost of
+ * vkmr_hip_reduce_levels_async.
+ *   tree_dev  vkmr_hip_tree_bytes(count, height) bytes of device memory
+ * vkmr_hip_tree_bytes returns 0 for count == 0 or height > 63.
+ */
+VKMR_API size_t vkmr_hip_tree_bytes(uint64_t count, uint32_t height);
+VKMR_API vkmr_status vkmr_hip_reduce_tree_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev,
+                                                uint64_t count, uint32_t height, vkmr_digest* tree_dev);
+
+/*
+ * PROOFS FROM THE STORED TREE (README.md:118-120): a gather, no hash.  digests_dev and tree_dev as written by
+ * vkmr_hip_reduce_tree_async(count, height); indices_dev: k leaf indices in DEVICE memory (k any value up to 2^32 - 1).
+ * siblings_dev[q * height + l] (k * height cells, indexed in 64 bits) = L[l][s] with p = indices[q] >> l, s = p ^ 1, or
+ * s = p where p ^ 1 >= n_l -- exactly vkmr_hip_proof_async's siblings and the layout of vkmr_hip_reduce_proofs_async.
+ * The host cannot check indices that live on the device: an index >= count gets `height` all-zero cells.
+ * k == 0 does nothing; height == 0 writes nothing.
+ */
+VKMR_API vkmr_status vkmr_hip_tree_proofs_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev,
+                                                const vkmr_digest* tree_dev, uint64_t count, uint32_t height,
+                                                const uint64_t* indices_dev, uint32_t k, vkmr_digest* siblings_dev);
+
+/*
+ * BATCH VERIFICATION (the reference has no counterpart: it neither writes nor checks proofs).  One lane per proof: leaf
+ * leaves_dev[q] is folded with siblings_dev[q * height + l], l = 0..height-1, as vkmr_host_cpu_fold_proof does (bit l of
+ * indices_dev[q] set: node = SHA-256d(sibling || node), else SHA-256d(node || sibling)).  ok_dev[q] = 1 when
+ * indices_dev[q] < 2^height and the fold equals roots_dev[nroots == 1 ? 0 : q], else 0.
+ *   height 1..63; nroots 1 (every proof against one root) or k (a root per proof); all buffers in device memory.
+ * A proof shows membership AT A POSITION, not the number of leaves: under the duplicate-last rule the last node of an
+ * odd level is its own sibling, so a tree over an odd number n of leaves and one over n + 1 leaves whose last leaf
+ * repeats the n-th have the same root (the known ambiguity of Bitcoin-style trees).  Callers that need the count commit to it elsewhere.
+ * k == 0 does nothing.
+ */
+VKMR_API vkmr_status vkmr_hip_verify_proofs_async(int dev, vkmr_stream s, const vkmr_digest* leaves_dev,
+                                                  const uint64_t* indices_dev, const vkmr_digest* siblings_dev,
+                                                  uint32_t k, uint32_t height, const vkmr_digest* roots_dev,
+                                                  uint32_t nroots, uint32_t* ok_dev);
+
+/*
  * COMBINE: duplicate-last Merkle root over n >= 1 slice roots given in slice order, always
  * at least one level -- the rule of CpuSha256D::Root that the reference applies to the slice
  * roots on the CPU (CpuSha256DforReductions, src/vkmr/Reductions.cpp:56-69, :703-712).  Here

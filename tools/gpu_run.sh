@@ -14,6 +14,8 @@
 #   cumask                 tools/cu_mask_probe.py: where CU-mask bits land, map/reduce on half the CUs with and without neighbours
 #   issue <set>            tools/issue_patterns (python3 tools/gen_issue_patterns.py <set> and a build beforehand)
 #   proofs                 tools/proof_timing.py: a slice reduced with and without proofs written in the pass
+#   treeproofs [args]      tools/tree_proofs_timing.py: stored tree, proof gather, batch verify (one JSON line), then the same run under
+#                          rocprofv3 --kernel-trace --stats for the kernel times; stops at the first failing step
 cd ${GRAFT_REPO_ROOT:-.}
 ROUND=${ROUND:-r04}
 OUT=gpurun_out/$ROUND
@@ -111,6 +113,15 @@ issue)
   ;;
 proofs)
   for k in "26 8" "26 1" "26 16" "23 16"; do set -- $k; timeout -k 10 300 python3 tools/proof_timing.py --log2 $1 --proofs $2; done > $OUT/proof_timing.txt 2>&1; cat $OUT/proof_timing.txt
+  ;;
+treeproofs)
+  timeout -k 10 400 python3 tools/tree_proofs_timing.py "$@" > $OUT/tree_proofs_timing.json 2> $OUT/tree_proofs_timing.err && echo "tree_proofs_timing ok" &&
+  cat $OUT/tree_proofs_timing.json &&
+  repo=$(pwd) &&
+  ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $repo/$OUT/prof_tree -- python3 $repo/tools/tree_proofs_timing.py "$@" > $repo/$OUT/tree_proofs_prof.json 2> $repo/$OUT/tree_proofs_prof.err ) &&
+  find $OUT/prof_tree -name "*kernel_stats.csv" -exec cp {} $OUT/tree_proofs_kernel_stats.csv \; &&
+  cat $OUT/tree_proofs_kernel_stats.csv
+  echo "treeproofs rc=$?"
   ;;
 cumask)
   hipcc --offload-arch=gfx950 -O2 -shared -fPIC -o tools/libwhere.so tools/where.hip

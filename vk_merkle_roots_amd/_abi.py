@@ -59,6 +59,12 @@ SIGNATURES = {
                                                C.c_void_p]),
     "vkmr_hip_reduce_levels_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p]),
     "vkmr_hip_reduce_levels_scratch_bytes": (C.c_size_t, [C.c_uint64]),
+    "vkmr_hip_tree_bytes": (C.c_size_t, [C.c_uint64, C.c_uint32]),
+    "vkmr_hip_reduce_tree_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
+    "vkmr_hip_tree_proofs_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32,
+                                             C.c_void_p]),
+    "vkmr_hip_verify_proofs_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                               C.c_uint32, C.c_void_p]),
     "vkmr_hip_combine_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "vkmr_hip_comm_init_all": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
     "vkmr_hip_comm_create_id": (C.c_int, [C.c_void_p]),
@@ -111,8 +117,10 @@ class VkmrError(RuntimeError):
         self.status = status
 
 
-def _bind(lib, table):
+def _bind(lib, table, strict=True):
     for name, (res, args) in table.items():
+        if not strict and not hasattr(lib, name):
+            continue                     # an alternative build that predates this entry point: calling it raises AttributeError
         fn = getattr(lib, name)          # AttributeError when a declared symbol is not exported
         fn.restype = res
         fn.argtypes = args
@@ -135,7 +143,7 @@ def lib():
     if _lib is None:
         path = os.environ.get("VKMR_HIP_LIB", HIP_LIB)      # alternative build of the SAME extension, for A/B timing
         if path != HIP_LIB and os.path.exists(path):
-            _lib = _bind(C.CDLL(path, mode=C.RTLD_GLOBAL), SIGNATURES)
+            _lib = _bind(C.CDLL(path, mode=C.RTLD_GLOBAL), SIGNATURES, strict=False)
             return _lib
         if not os.path.exists(HIP_LIB):
             raise RuntimeError(f"{HIP_LIB} is missing: run `python -m vk_merkle_roots_amd.build` "

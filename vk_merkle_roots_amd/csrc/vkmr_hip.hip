@@ -4,7 +4,9 @@
 //   map_kernel.hpp      map_kernel             SHA-256d of every packed string      (SHA-256.comp:177-304)
 //   reduce_kernels.hpp  reduce_pass_kernel     streaming sub-tree collapse per wave (SHA-256.comp:325-391)
 //                       reduce_collapse_kernel / reduce_tail_kernel   the latency-bound top, __shfl_down
-//                       reduce_level_kernel    one level per launch, cross-check    (SHA-256.comp:393-434)
+//                       reduce_level_kernel    one level per launch, cross-check    (SHA-256.comp:393-434); builds the stored tree
+//   tree_kernels.hpp    tree_proofs_kernel     proofs gathered from the stored tree (README.md:118-120)
+//                       verify_proofs_kernel   batch proof verification, one lane per proof (no reference counterpart)
 //   sha256d_device.hpp  the SHA-256 round / compression building blocks
 //   meta_kernels.hpp    sizes_*_kernel         metadata entries from 16-bit sizes   (Batches.cpp:64-121)
 //
@@ -31,6 +33,7 @@ using vkmr_dev::Node;
 #endif
 #include "reduce_kernels.hpp"
 #include "reduce_plan.hpp"
+#include "tree_kernels.hpp"
 
 // ============================================================================
 // C ABI
@@ -707,6 +710,27 @@ size_t vkmr_hip_reduce_levels_scratch_bytes(uint64_t count)
     return (size_t)(ceil_shift(count, 1) + ceil_shift(count, 2) + 2) * sizeof(vkmr_digest);
 }
 
+// Level lv + 1 from level lv, lv = 0..height-1, one reduce_level_kernel launch each; dst(lv) is where level lv + 1 goes.
+// Shared by the levels cross-check (ping-pong scratch, root last) and the stored tree (every level kept).
+extern "C++" {   // a template inside the C block
+template <class Dst>
+static vkmr_status levels_launch(hipStream_t stream, const Node* in, uint64_t count, uint32_t height, Dst dst, const char* too_large)
+{
+    uint64_t n = count;
+    for (uint32_t lv = 0; lv < height; ++lv) {
+        const uint64_t pairs = ceil_shift(n, 1);
+        Node* out = dst(lv);
+        const uint64_t grid = (pairs + 255) / 256;
+        if (grid > 0x7fffffffull) return fail(VKMR_ERR_INVALID, too_large);
+        hipLaunchKernelGGL(reduce_level_kernel, dim3((uint32_t)grid), dim3(256), 0, stream, in, n, out);
+        VKMR_TRY(hipGetLastError());
+        in = out;
+        n = pairs;
+    }
+    return VKMR_OK;
+}
+}
+
 vkmr_status vkmr_hip_reduce_levels_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t count,
                                          uint32_t height, void* scratch_dev, vkmr_digest* root_dev)
 {
@@ -715,21 +739,88 @@ vkmr_status vkmr_hip_reduce_levels_async(int dev, vkmr_stream s, const vkmr_dige
     if (!height_ok(count, height))
         return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_levels_async: height does not reduce count to one node");
     VKMR_TRY(hipSetDevice(dev));
-    const Node* in = reinterpret_cast<const Node*>(digests_dev);
     Node* bufA = reinterpret_cast<Node*>(scratch_dev);
     Node* bufB = bufA + ceil_shift(count, 1);
-    uint64_t n = count;
-    for (uint32_t lv = 0; lv < height; ++lv) {
-        const uint64_t pairs = ceil_shift(n, 1);
-        Node* out = (lv + 1 == height) ? reinterpret_cast<Node*>(root_dev) : ((lv & 1) ? bufB : bufA);
-        const uint64_t grid = (pairs + 255) / 256;
-        if (grid > 0x7fffffffull) return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_levels_async: slice too large");
-        hipLaunchKernelGGL(reduce_level_kernel, dim3((uint32_t)grid), dim3(256), 0, S(s), in, n, out);
-        VKMR_TRY(hipGetLastError());
-        in = out;
-        n = pairs;
-    }
+    Node* root = reinterpret_cast<Node*>(root_dev);
+    const vkmr_status st = levels_launch(S(s), reinterpret_cast<const Node*>(digests_dev), count, height,
+                                         [=](uint32_t lv) { return (lv + 1 == height) ? root : ((lv & 1) ? bufB : bufA); },
+                                         "vkmr_hip_reduce_levels_async: slice too large");
+    if (st != VKMR_OK) return st;
     if (height == 0) VKMR_TRY(hipMemcpyAsync(root_dev, digests_dev, sizeof(vkmr_digest), hipMemcpyDeviceToDevice, S(s)));
+    return VKMR_OK;
+}
+
+// ---- stored tree: build, gather proofs, verify (tree_kernels.hpp) -------------------------------------------------------
+
+// Start cell of every level 1..height inside the tree buffer (off[0] = 0, unused); returns the buffer's cell count.
+static uint64_t tree_levels(uint64_t count, uint32_t height, TreeLevels* lv)
+{
+    uint64_t cells = 0;
+    if (lv) lv->off[0] = 0;
+    for (uint32_t l = 1; l <= height && l < VKMR_TREE_MAX_LEVELS; ++l) {
+        if (lv) lv->off[l] = cells;
+        cells += ceil_shift(count, l);
+    }
+    return cells;
+}
+
+size_t vkmr_hip_tree_bytes(uint64_t count, uint32_t height)
+{
+    if (count == 0 || height > 63) return 0;
+    return (size_t)tree_levels(count, height, nullptr) * sizeof(vkmr_digest);
+}
+
+vkmr_status vkmr_hip_reduce_tree_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t count, uint32_t height,
+                                       vkmr_digest* tree_dev)
+{
+    if (!digests_dev || (!tree_dev && height > 0)) return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_tree_async: null pointer");
+    if (!height_ok(count, height))
+        return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_tree_async: height does not reduce count to one node");
+    if (height == 0) return VKMR_OK;   // one leaf, no level: the root is the leaf
+    TreeLevels lv;
+    tree_levels(count, height, &lv);
+    VKMR_TRY(hipSetDevice(dev));
+    Node* tree = reinterpret_cast<Node*>(tree_dev);
+    return levels_launch(S(s), reinterpret_cast<const Node*>(digests_dev), count, height, [&](uint32_t l) { return tree + lv.off[l + 1]; },
+                         "vkmr_hip_reduce_tree_async: slice too large");
+}
+
+vkmr_status vkmr_hip_tree_proofs_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* tree_dev, uint64_t count,
+                                       uint32_t height, const uint64_t* indices_dev, uint32_t k, vkmr_digest* siblings_dev)
+{
+    if (k == 0) return VKMR_OK;
+    if (!digests_dev || (!tree_dev && height > 0) || !indices_dev || !siblings_dev)
+        return fail(VKMR_ERR_INVALID, "vkmr_hip_tree_proofs_async: null pointer");
+    if (!height_ok(count, height))
+        return fail(VKMR_ERR_INVALID, "vkmr_hip_tree_proofs_async: height does not reduce count to one node");
+    if (height == 0) return VKMR_OK;   // no level, no sibling
+    TreeLevels lv;
+    tree_levels(count, height, &lv);
+    const uint64_t total = (uint64_t)k * height;
+    const uint64_t grid = (total + 255) / 256;
+    if (grid > 0x7fffffffull) return fail(VKMR_ERR_INVALID, "vkmr_hip_tree_proofs_async: too many proofs in one call");
+    VKMR_TRY(hipSetDevice(dev));
+    hipLaunchKernelGGL(tree_proofs_kernel, dim3((uint32_t)grid), dim3(256), 0, S(s), reinterpret_cast<const Node*>(digests_dev),
+                       reinterpret_cast<const Node*>(tree_dev), lv, count, height, indices_dev, total, reinterpret_cast<Node*>(siblings_dev));
+    VKMR_TRY(hipGetLastError());
+    return VKMR_OK;
+}
+
+vkmr_status vkmr_hip_verify_proofs_async(int dev, vkmr_stream s, const vkmr_digest* leaves_dev, const uint64_t* indices_dev,
+                                         const vkmr_digest* siblings_dev, uint32_t k, uint32_t height, const vkmr_digest* roots_dev,
+                                         uint32_t nroots, uint32_t* ok_dev)
+{
+    if (k == 0) return VKMR_OK;
+    if (!leaves_dev || !indices_dev || !siblings_dev || !roots_dev || !ok_dev)
+        return fail(VKMR_ERR_INVALID, "vkmr_hip_verify_proofs_async: null pointer");
+    if (height == 0 || height > 63) return fail(VKMR_ERR_INVALID, "vkmr_hip_verify_proofs_async: height must be 1..63");
+    if (nroots != 1 && nroots != k) return fail(VKMR_ERR_INVALID, "vkmr_hip_verify_proofs_async: nroots must be 1 or k");
+    VKMR_TRY(hipSetDevice(dev));
+    const uint32_t grid = (uint32_t)(((uint64_t)k + 255) / 256);
+    hipLaunchKernelGGL(verify_proofs_kernel, dim3(grid), dim3(256), 0, S(s), reinterpret_cast<const Node*>(leaves_dev), indices_dev,
+                       reinterpret_cast<const Node*>(siblings_dev), k, height, reinterpret_cast<const Node*>(roots_dev),
+                       (uint32_t)(nroots == 1 ? 0u : 1u), ok_dev);
+    VKMR_TRY(hipGetLastError());
     return VKMR_OK;
 }
 

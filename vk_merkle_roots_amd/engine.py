@@ -237,6 +237,50 @@ class HipDevice:
             b.free()
         return sib, root
 
+    # -- stored tree: build, gather proofs, verify -----------------------------------
+    def tree_bytes(self, count, height):
+        return self.lib.vkmr_hip_tree_bytes(count, height)
+
+    def reduce_tree_async(self, digests_buf, count, height, tree_buf, stream=None):
+        check(self.lib.vkmr_hip_reduce_tree_async(self.index, stream or self.stream, digests_buf.ptr, count, height,
+                                                  tree_buf.ptr if tree_buf else None), "vkmr_hip_reduce_tree_async")
+
+    def tree_proofs_async(self, digests_buf, tree_buf, count, height, indices_buf, k, siblings_buf, stream=None):
+        check(self.lib.vkmr_hip_tree_proofs_async(self.index, stream or self.stream, digests_buf.ptr, tree_buf.ptr if tree_buf else None,
+                                                  count, height, indices_buf.ptr, k, siblings_buf.ptr), "vkmr_hip_tree_proofs_async")
+
+    def verify_proofs_async(self, leaves_buf, indices_buf, siblings_buf, k, height, roots_buf, nroots, ok_buf, stream=None):
+        check(self.lib.vkmr_hip_verify_proofs_async(self.index, stream or self.stream, leaves_buf.ptr, indices_buf.ptr, siblings_buf.ptr, k,
+                                                    height, roots_buf.ptr, nroots, ok_buf.ptr), "vkmr_hip_verify_proofs_async")
+
+    def build_tree(self, digests_buf, count, height=None):
+        """Every level of the tree over `count` digests in `digests_buf` (which stays level 0 and must outlive the tree),
+        kept on the device: a MerkleTree."""
+        height = tree_height(count) if height is None else height
+        tree_buf = self.alloc(self.tree_bytes(count, height)) if height else None
+        self.reduce_tree_async(digests_buf, count, height, tree_buf)
+        return MerkleTree(self, digests_buf, count, height, tree_buf)
+
+    def verify_proofs(self, leaves, indices, siblings, roots):
+        """bool [k]: proof q (leaf [8], index, siblings [height, 8]) folds to roots[0] (roots [8] or [1, 8]) or roots[q]
+        (roots [k, 8]), its index inside the tree.  Host arrays in, verified on the device."""
+        leaves = np.ascontiguousarray(leaves, dtype=np.uint32).reshape(-1, 8)
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        k = int(idx.shape[0])
+        siblings = np.ascontiguousarray(siblings, dtype=np.uint32).reshape(k, -1, 8)
+        roots = np.ascontiguousarray(roots, dtype=np.uint32).reshape(-1, 8)
+        if leaves.shape[0] != k or roots.shape[0] not in (1, k):
+            raise ValueError("verify_proofs: one leaf per index, and one root or one per proof")
+        if k == 0:
+            return np.zeros(0, dtype=bool)
+        bufs = [self.upload(a) for a in (leaves, idx, siblings, roots)]
+        d_ok = self.alloc(4 * k)
+        self.verify_proofs_async(bufs[0], bufs[1], bufs[2], k, siblings.shape[1], bufs[3], roots.shape[0], d_ok)
+        ok = self.download(d_ok, 4 * k)
+        for b in bufs + [d_ok]:
+            b.free()
+        return ok == 1
+
     def reduce_scratch(self, count, levels_variant=False):
         fn = self.lib.vkmr_hip_reduce_levels_scratch_bytes if levels_variant else self.lib.vkmr_hip_reduce_scratch_bytes
         return self.alloc(fn(count))
@@ -284,6 +328,80 @@ class HipDevice:
         for b in (d_in, d_scratch, d_root):
             b.free()
         return root
+
+
+class MerkleTree:
+    """Every level of a duplicate-last tree, resident on the device (vkmr_hip_reduce_tree_async): level 0 is the digests
+    buffer it was built from, levels 1..height one buffer laid out as include/vkmr_hip.h describes."""
+
+    def __init__(self, dev, digests_buf, count, height, tree_buf, owned=()):
+        self.dev, self.digests, self.count, self.height, self.tree = dev, digests_buf, int(count), int(height), tree_buf
+        self._owned = list(owned)
+
+    def level_size(self, l):
+        return -(-self.count >> l)
+
+    def level_offset(self, l):
+        """Start cell of level l >= 1 inside the tree buffer."""
+        return sum(self.level_size(j) for j in range(1, l))
+
+    def level(self, l):
+        """[n_l, 8] uint32: the cells of level l (0 = the leaves, height = the root)."""
+        if not 0 <= l <= self.height:
+            raise IndexError(f"level {l} of a tree of height {self.height}")
+        n = self.level_size(l)
+        if l == 0:
+            return self.dev.download(self.digests, 32 * n).reshape(n, 8)
+        return self.dev.download(self.tree, 32 * n, offset=32 * self.level_offset(l)).reshape(n, 8)
+
+    def root(self):
+        """[8] uint32; equals what reduce_async(count, height) writes."""
+        if self.height == 0:
+            return self.dev.download(self.digests, 32)
+        return self.dev.download(self.tree, 32, offset=self.dev.tree_bytes(self.count, self.height) - 32)
+
+    def proofs_async(self, indices_buf, k, siblings_buf, stream=None):
+        """Siblings of k leaves whose indices are in device memory, written to siblings_buf [k, height] on the device."""
+        self.dev.tree_proofs_async(self.digests, self.tree, self.count, self.height, indices_buf, k, siblings_buf, stream=stream)
+
+    def proofs(self, indices):
+        """[k, height, 8] uint32: the proofs of leaves `indices` (a host array); an index >= count gets zero cells."""
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        k = int(idx.shape[0])
+        if k == 0 or self.height == 0:
+            return np.zeros((k, self.height, 8), dtype=np.uint32)
+        d_idx = self.dev.upload(idx)
+        d_sib = self.dev.alloc(32 * k * self.height)
+        self.proofs_async(d_idx, k, d_sib)
+        out = self.dev.download(d_sib, 32 * k * self.height).reshape(k, self.height, 8)
+        d_idx.free()
+        d_sib.free()
+        return out
+
+    def free(self):
+        if self.tree:
+            self.tree.free()
+            self.tree = None
+        for b in self._owned:
+            b.free()
+        self._owned = []
+
+
+def merkle_tree_packed(dev, batch, height=None):
+    """The strings of `batch` mapped to leaf digests and the whole tree over them built, all on the device (a MerkleTree
+    that owns its leaves)."""
+    if batch.count == 0:
+        raise ValueError("merkle_tree_packed: empty batch")
+    d_data = dev.upload(batch.data if batch.words else np.zeros(1, np.uint32))
+    d_meta = dev.upload(batch.meta)
+    d_leaves = dev.alloc(32 * batch.count)
+    dev.map_async(d_data, batch.words, d_meta, batch.count, d_leaves)
+    tree = dev.build_tree(d_leaves, batch.count, height)
+    tree._owned.append(d_leaves)
+    dev.sync()
+    d_data.free()
+    d_meta.free()
+    return tree
 
 
 def digest_hex(words):
