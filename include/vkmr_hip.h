@@ -280,6 +280,25 @@ VKMR_API vkmr_status vkmr_hip_verify_proofs_async(int dev, vkmr_stream s, const 
                                                   uint32_t nroots, uint32_t* ok_dev);
 
 /*
+ * UPDATE LEAVES OF THE STORED TREE (the reference has no counterpart: its trees are rebuilt).  digests_dev and tree_dev
+ * as written by vkmr_hip_reduce_tree_async(count, height); level 0 is the caller's digests buffer and this call writes
+ * into it.  indices_dev[0..k) and leaves_dev[0..k) in DEVICE memory: the indices strictly increasing and < count (the
+ * host cannot check them; the device does, see status_dev).  On success digests_dev[indices[q]] = leaves[q] for every q,
+ * and every ancestor of those leaves is hashed again by the rule of the stored tree (duplicate-last, also after the
+ * count has collapsed to one), so every cell equals what a fresh vkmr_hip_reduce_tree_async over the updated leaves
+ * writes.  No other cell is written.  Work: sum over l = 1..height of |unique(indices >> l)| node hashes, one launch
+ * per level.
+ *   status_dev  one uint32_t in device memory, always written: 0 when the update was applied; bit 0 set if an index
+ *               was >= count, bit 1 if the indices were not strictly increasing (out of order or repeated).  When it
+ *               is nonzero NOTHING in the leaves or the tree has changed.
+ * k == 0 does nothing whatever the other arguments; height == 0 (count == 1) writes only the leaf, and tree_dev may then
+ * be NULL.  Stream-ordered: a proof gather or verify enqueued after it on the same stream sees the new tree.
+ */
+VKMR_API vkmr_status vkmr_hip_tree_update_async(int dev, vkmr_stream s, vkmr_digest* digests_dev, vkmr_digest* tree_dev,
+                                                uint64_t count, uint32_t height, const uint64_t* indices_dev,
+                                                const vkmr_digest* leaves_dev, uint32_t k, uint32_t* status_dev);
+
+/*
  * COMBINE: duplicate-last Merkle root over n >= 1 slice roots given in slice order, always
  * at least one level -- the rule of CpuSha256D::Root that the reference applies to the slice
  * roots on the CPU (CpuSha256DforReductions, src/vkmr/Reductions.cpp:56-69, :703-712).  Here

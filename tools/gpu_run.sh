@@ -16,6 +16,8 @@
 #   proofs                 tools/proof_timing.py: a slice reduced with and without proofs written in the pass
 #   treeproofs [args]      tools/tree_proofs_timing.py: stored tree, proof gather, batch verify (one JSON line), then the same run under
 #                          rocprofv3 --kernel-trace --stats for the kernel times; stops at the first failing step
+#   treeupdate [args]      tools/tree_update_timing.py: leaf updates of a stored tree against a rebuild (one JSON line), then the same
+#                          run under rocprofv3 --kernel-trace --stats for the kernel times; stops at the first failing step
 cd ${GRAFT_REPO_ROOT:-.}
 ROUND=${ROUND:-r04}
 OUT=gpurun_out/$ROUND
@@ -122,6 +124,15 @@ treeproofs)
   find $OUT/prof_tree -name "*kernel_stats.csv" -exec cp {} $OUT/tree_proofs_kernel_stats.csv \; &&
   cat $OUT/tree_proofs_kernel_stats.csv
   echo "treeproofs rc=$?"
+  ;;
+treeupdate)
+  timeout -k 10 400 python3 tools/tree_update_timing.py "$@" > $OUT/tree_update_timing.json 2> $OUT/tree_update_timing.err && echo "tree_update_timing ok" &&
+  cat $OUT/tree_update_timing.json &&
+  repo=$(pwd) &&
+  ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $repo/$OUT/prof_update -- python3 $repo/tools/tree_update_timing.py "$@" > $repo/$OUT/tree_update_prof.json 2> $repo/$OUT/tree_update_prof.err ) &&
+  find $OUT/prof_update -name "*kernel_stats.csv" -exec cp {} $OUT/tree_update_kernel_stats.csv \; &&
+  cat $OUT/tree_update_kernel_stats.csv
+  echo "treeupdate rc=$?"
   ;;
 cumask)
   hipcc --offload-arch=gfx950 -O2 -shared -fPIC -o tools/libwhere.so tools/where.hip

@@ -1,5 +1,6 @@
-// tree_kernels.hpp -- the stored tree's proof gather and the batch verifier (include/vkmr_hip.h: vkmr_hip_tree_proofs_async,
-// vkmr_hip_verify_proofs_async).  The tree itself is built by reduce_level_kernel (reduce_kernels.hpp), one launch per level.
+// tree_kernels.hpp -- the stored tree's proof gather, the batch verifier and the leaf update (include/vkmr_hip.h:
+// vkmr_hip_tree_proofs_async, vkmr_hip_verify_proofs_async, vkmr_hip_tree_update_async).  The tree itself is built by
+// reduce_level_kernel (reduce_kernels.hpp), one launch per level.
 //
 // Layout (vkmr_hip_reduce_tree_async): level 0 is the caller's digests; levels 1..height lie back to back in one buffer,
 // level l (n_l = ceil(count / 2^l) cells) starting at cell off[l] = sum of n_j over 1 <= j < l.
@@ -67,4 +68,53 @@ __global__ __launch_bounds__(256) void verify_proofs_kernel(const Node* __restri
 #pragma unroll
     for (int w = 0; w < 8; ++w) diff |= cur.w[w] ^ root.w[w];
     ok[q] = diff == 0u ? 1u : 0u;
+}
+
+// ---- leaf updates (vkmr_hip_tree_update_async) --------------------------------------------------------------------------
+// Three launches on one stream, every lane one update entry q < k: the check ORs the contract's violations into *status
+// (zeroed by the host), and the two writers read *status first and write nothing when it is nonzero, so a rejected batch
+// leaves the leaves and the tree as they were.
+
+// No hash: bit 0 when index_q >= count, bit 1 when index_{q-1} >= index_q (out of order or repeated).
+__global__ __launch_bounds__(256) void tree_update_check_kernel(const uint64_t* __restrict__ indices, uint32_t k, uint64_t count,
+                                                                uint32_t* __restrict__ status)
+{
+    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= k) return;
+    const uint64_t index = indices[q];
+    uint32_t bits = index >= count ? 1u : 0u;
+    if (q > 0 && indices[q - 1] >= index) bits |= 2u;
+    if (bits) atomicOr(status, bits);
+}
+
+// No hash: digests[index_q] = leaves[q].
+__global__ __launch_bounds__(256) void tree_update_leaves_kernel(Node* __restrict__ digests, const uint64_t* __restrict__ indices,
+                                                                 const Node* __restrict__ leaves, uint32_t k, const uint32_t* __restrict__ status)
+{
+    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= k || *status != 0u) return;
+    const Node v = vkmr_dev::load_node(leaves + q);
+    uint32_t o[8];
+#pragma unroll
+    for (int w = 0; w < 8; ++w) o[w] = v.w[w];
+    vkmr_dev::store_node(digests + indices[q], o);
+}
+
+// One level l >= 1 per launch: in = level l - 1 (n_in cells), out = level l.  Lane q hashes parent p = index_q >> l when it
+// is the first lane of its run (the indices are sorted, so lanes with the same parent are adjacent): each dirty node is
+// hashed exactly once, distinct lanes write distinct cells and read only the level below.  reduce_level_kernel's body with
+// a different index; its one hash_pair is the kernel's only hash block.  The check ran first: index_q < count, so p < n_l.
+__global__ __launch_bounds__(256) void tree_update_level_kernel(const Node* __restrict__ in, uint64_t n_in, Node* __restrict__ out,
+                                                                const uint64_t* __restrict__ indices, uint32_t k, uint32_t l,
+                                                                const uint32_t* __restrict__ status)
+{
+    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= k || *status != 0u) return;
+    const uint64_t p = indices[q] >> l;
+    if (q > 0 && (indices[q - 1] >> l) == p) return;
+    const Node a = vkmr_dev::load_node(in + 2 * p);
+    const Node b = vkmr_dev::load_node(in + ((2 * p + 1 < n_in) ? 2 * p + 1 : 2 * p));
+    uint32_t o[8];
+    vkmr_dev::hash_pair(a.w, b.w, o);
+    vkmr_dev::store_node(out + p, o);
 }

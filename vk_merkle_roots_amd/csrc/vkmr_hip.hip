@@ -7,6 +7,7 @@
 //                       reduce_level_kernel    one level per launch, cross-check    (SHA-256.comp:393-434); builds the stored tree
 //   tree_kernels.hpp    tree_proofs_kernel     proofs gathered from the stored tree (README.md:118-120)
 //                       verify_proofs_kernel   batch proof verification, one lane per proof (no reference counterpart)
+//                       tree_update_*_kernel   leaf updates: check, store the leaves, rehash the dirty nodes level by level
 //   sha256d_device.hpp  the SHA-256 round / compression building blocks
 //   meta_kernels.hpp    sizes_*_kernel         metadata entries from 16-bit sizes   (Batches.cpp:64-121)
 //
@@ -821,6 +822,36 @@ vkmr_status vkmr_hip_verify_proofs_async(int dev, vkmr_stream s, const vkmr_dige
                        reinterpret_cast<const Node*>(siblings_dev), k, height, reinterpret_cast<const Node*>(roots_dev),
                        (uint32_t)(nroots == 1 ? 0u : 1u), ok_dev);
     VKMR_TRY(hipGetLastError());
+    return VKMR_OK;
+}
+
+vkmr_status vkmr_hip_tree_update_async(int dev, vkmr_stream s, vkmr_digest* digests_dev, vkmr_digest* tree_dev, uint64_t count,
+                                       uint32_t height, const uint64_t* indices_dev, const vkmr_digest* leaves_dev, uint32_t k,
+                                       uint32_t* status_dev)
+{
+    if (k == 0) return VKMR_OK;
+    if (!digests_dev || (!tree_dev && height > 0) || !indices_dev || !leaves_dev || !status_dev)
+        return fail(VKMR_ERR_INVALID, "vkmr_hip_tree_update_async: null pointer");
+    if (!height_ok(count, height))
+        return fail(VKMR_ERR_INVALID, "vkmr_hip_tree_update_async: height does not reduce count to one node");
+    TreeLevels lv;
+    tree_levels(count, height, &lv);
+    const uint32_t grid = (uint32_t)(((uint64_t)k + 255) / 256);
+    Node* digests = reinterpret_cast<Node*>(digests_dev);
+    Node* tree = reinterpret_cast<Node*>(tree_dev);
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_TRY(hipMemsetAsync(status_dev, 0, sizeof(uint32_t), S(s)));
+    hipLaunchKernelGGL(tree_update_check_kernel, dim3(grid), dim3(256), 0, S(s), indices_dev, k, count, status_dev);
+    VKMR_TRY(hipGetLastError());
+    hipLaunchKernelGGL(tree_update_leaves_kernel, dim3(grid), dim3(256), 0, S(s), digests, indices_dev,
+                       reinterpret_cast<const Node*>(leaves_dev), k, (const uint32_t*)status_dev);
+    VKMR_TRY(hipGetLastError());
+    for (uint32_t l = 1; l <= height; ++l) {   // level l from level l - 1, which the previous launch finished
+        const Node* in = (l == 1) ? digests : tree + lv.off[l - 1];
+        hipLaunchKernelGGL(tree_update_level_kernel, dim3(grid), dim3(256), 0, S(s), in, ceil_shift(count, l - 1), tree + lv.off[l],
+                           indices_dev, k, l, (const uint32_t*)status_dev);
+        VKMR_TRY(hipGetLastError());
+    }
     return VKMR_OK;
 }
 

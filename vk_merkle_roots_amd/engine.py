@@ -253,6 +253,11 @@ class HipDevice:
         check(self.lib.vkmr_hip_verify_proofs_async(self.index, stream or self.stream, leaves_buf.ptr, indices_buf.ptr, siblings_buf.ptr, k,
                                                     height, roots_buf.ptr, nroots, ok_buf.ptr), "vkmr_hip_verify_proofs_async")
 
+    def tree_update_async(self, digests_buf, tree_buf, count, height, indices_buf, leaves_buf, k, status_buf, stream=None):
+        check(self.lib.vkmr_hip_tree_update_async(self.index, stream or self.stream, digests_buf.ptr, tree_buf.ptr if tree_buf else None,
+                                                  count, height, indices_buf.ptr, leaves_buf.ptr, k, status_buf.ptr),
+              "vkmr_hip_tree_update_async")
+
     def build_tree(self, digests_buf, count, height=None):
         """Every level of the tree over `count` digests in `digests_buf` (which stays level 0 and must outlive the tree),
         kept on the device: a MerkleTree."""
@@ -377,6 +382,79 @@ class MerkleTree:
         d_idx.free()
         d_sib.free()
         return out
+
+    def update_async(self, indices_buf, leaves_buf, k, status_buf, stream=None):
+        """Leaves indices[q] = leaves[q], q < k, and every ancestor rehashed, on the device: indices [k] uint64 strictly
+        increasing and < count, leaves [k, 8], status one uint32 (0: applied; bit 0: an index >= count, bit 1: not strictly
+        increasing; nonzero: nothing changed).  All in device memory; ordered on `stream` like the proof gather."""
+        self.dev.tree_update_async(self.digests, self.tree, self.count, self.height, indices_buf, leaves_buf, k, status_buf, stream=stream)
+
+    def _update_order(self, indices):
+        """(sorted unique uint64 indices, positions in `indices` they come from): the last occurrence of a repeated index
+        wins.  IndexError for an index < 0 or >= count; no device call."""
+        raw = np.asarray(indices).reshape(-1)
+        if raw.dtype.kind == "O":            # Python ints numpy could not fit in one integer type
+            vals = [int(x) for x in raw]
+            if any(v < 0 or v >= self.count for v in vals):
+                raise IndexError(f"update: index outside [0, {self.count})")
+            idx = np.array(vals, dtype=np.uint64)
+        elif raw.size and raw.dtype.kind not in "iu":
+            raise ValueError("update: indices must be integers")
+        else:
+            if raw.dtype.kind == "i" and (raw < 0).any():
+                raise IndexError("update: negative index")
+            idx = raw.astype(np.uint64)
+            if (idx >= np.uint64(self.count)).any():
+                raise IndexError(f"update: index outside [0, {self.count})")
+        order = np.argsort(idx, kind="stable")
+        s = idx[order]
+        last = np.ones(s.shape[0], dtype=bool)
+        last[:-1] = s[1:] != s[:-1]        # a stable sort keeps repeats in call order: the last of each run is the last occurrence
+        return s[last], order[last]
+
+    def _apply(self, d_idx, d_leaves, k):
+        d_status = self.dev.alloc(4)
+        self.update_async(d_idx, d_leaves, k, d_status)
+        status = int(self.dev.download(d_status, 4)[0])
+        d_status.free()
+        if status:
+            raise RuntimeError(f"MerkleTree.update: the device refused sorted in-range indices (status {status})")
+
+    def update(self, indices, leaves):
+        """Set leaf indices[q] to leaves[q] ([k, 8] uint32; host arrays) and rehash every ancestor, on the device; a repeated
+        index takes its last value.  A tree built over a caller's digests buffer updates that buffer (it is level 0).
+        IndexError for an index < 0 or >= count, ValueError when leaves is not [k, 8], both before any device call."""
+        lv = np.asarray(leaves)
+        k = int(np.asarray(indices).size)
+        if lv.shape != (k, 8):
+            raise ValueError(f"update: leaves must be [{k}, 8], not {list(lv.shape)}")
+        idx, pos = self._update_order(indices)
+        if idx.shape[0] == 0:
+            return
+        lv = np.ascontiguousarray(lv[pos], dtype=np.uint32)
+        d_idx, d_leaves = self.dev.upload(idx), self.dev.upload(lv)
+        self._apply(d_idx, d_leaves, idx.shape[0])
+        d_idx.free()
+        d_leaves.free()
+
+    def update_packed(self, indices, batch):
+        """Set leaf indices[q] to the digest of string q of `batch` (batch.count == len(indices)): the strings are mapped on
+        the device and the tree updated there, no digest goes through the host.  Same index rules as update()."""
+        k = int(np.asarray(indices).size)
+        if batch.count != k:
+            raise ValueError(f"update_packed: {batch.count} strings for {k} indices")
+        idx, pos = self._update_order(indices)
+        if idx.shape[0] == 0:
+            return
+        meta = np.ascontiguousarray(batch.meta[pos])      # map's entries are independent: the strings in sorted-index order
+        d_data = self.dev.upload(batch.data if batch.words else np.zeros(1, np.uint32))
+        d_meta = self.dev.upload(meta)
+        d_idx = self.dev.upload(idx)
+        d_leaves = self.dev.alloc(32 * idx.shape[0])
+        self.dev.map_async(d_data, batch.words, d_meta, idx.shape[0], d_leaves)
+        self._apply(d_idx, d_leaves, idx.shape[0])
+        for b in (d_data, d_meta, d_idx, d_leaves):
+            b.free()
 
     def free(self):
         if self.tree:
