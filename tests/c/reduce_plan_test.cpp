@@ -3,9 +3,14 @@
 // for a short last slice and for the sibling sub-trees of a proof, and checks that the scratch
 // cells written never exceed what the size functions promise.  Built and run by
 // tests/test_reduce_plan.py (no GPU).
+//
+// `reduce_plan_test --steps n nslices height [n nslices height ...]` prints instead, for each triple, a line
+// `# n nslices height` and then one line `kind levels n_out` per launch of reduce_launch (kind: B = bulk pass,
+// C = collapse, T = tail): the schedule itself, for tests/reduce_cases.py, which must not carry a copy of it.
 #include <cstdio>
 #include <cstdint>
 #include <cstdlib>
+#include <cstring>
 
 #include "reduce_plan.hpp"
 
@@ -51,8 +56,34 @@ static void check(uint64_t n, uint32_t nslices, uint64_t budget_count)
     }
 }
 
-int main()
+// The launches of reduce_launch(nslices slices of n nodes, height levels), as vkmr_hip.hip walks next_step.
+static int print_steps(uint64_t n, uint32_t nslices, uint32_t height)
 {
+    printf("# %llu %u %u\n", (unsigned long long)n, nslices, height);
+    if (n == 0 || nslices == 0 || height > 63 || ceil_shift(n, height) != 1) { printf("invalid\n"); return 1; }
+    uint32_t left = height;
+    for (;;) {
+        const Step st = next_step(n, left, nslices);
+        printf("%c %u %llu\n", st.kind == STEP_BULK ? 'B' : st.kind == STEP_COLLAPSE ? 'C' : 'T', st.levels, (unsigned long long)st.n_out);
+        if (st.kind == STEP_TAIL) return 0;
+        if (st.levels == 0 || st.levels > left || st.n_out >= n) { printf("invalid\n"); return 1; }
+        n = st.n_out;
+        left -= st.levels;
+    }
+}
+
+int main(int argc, char** argv)
+{
+    if (argc > 1) {
+        if (strcmp(argv[1], "--steps") != 0 || argc < 5 || (argc - 2) % 3 != 0) {
+            fprintf(stderr, "usage: %s [--steps n nslices height [n nslices height ...]]\n", argv[0]);
+            return 2;
+        }
+        int rc = 0;
+        for (int i = 2; i + 2 < argc; i += 3)
+            rc |= print_steps(strtoull(argv[i], nullptr, 10), (uint32_t)strtoul(argv[i + 1], nullptr, 10), (uint32_t)strtoul(argv[i + 2], nullptr, 10));
+        return rc;
+    }
     uint64_t x = 88172645463325252ull;
     auto rnd = [&]() { x ^= x << 13; x ^= x >> 7; x ^= x << 17; return x; };
 

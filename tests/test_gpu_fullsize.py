@@ -36,7 +36,6 @@ def test_config3_2p26_leaves(gpu, oracle):
     assert (got == want_leaves).all()
     del got
     want_root = oracle.hex(oracle.root(want_leaves, threads=64))
-    del want_leaves
     # ... and what the reference's own CPU path printed for this stream (tests/golden/big_roots.json)
     import json
     import os
@@ -63,13 +62,16 @@ def test_config3_2p26_leaves(gpu, oracle):
     gpu.reduce_async(d_r64, 64, 6, d_top, d_final)
     assert digest_hex(gpu.download(d_final, 32)) == want_root
 
-    # (4) ragged: drop the last 12345 leaves -> last slice short, reduced to capacity height
+    # (4) ragged: drop the last 12345 leaves -> last slice short, reduced to capacity height; both ways the oracle's root
     m = n - 12345
+    want_ragged = oracle.hex(oracle.root(want_leaves[:m], threads=64))
+    del want_leaves
     gpu.reduce_slices_async(d_digests, 8, 1 << 23, m - 7 * (1 << 23), 23, d_scratch, d_roots)
     gpu.reduce_async(d_roots, 8, 3, d_top, d_final)
     ragged_sliced = digest_hex(gpu.download(d_final, 32))
     gpu.reduce_async(d_digests, m, tree_height(m), d_s1, d_final)
     assert digest_hex(gpu.download(d_final, 32)) == ragged_sliced
+    assert ragged_sliced == want_ragged
 
 
 def test_config5_long_strings(gpu, oracle):

@@ -395,6 +395,7 @@ def test_proofs_written_during_the_reduction_equal_the_recomputed_ones(gpu, orac
     cases as the test above and on sizes that go through every kernel of the schedule (bulk passes, collapses, tail, levels
     above a lone node), with the same root as the plain reduction."""
     import vk_merkle_roots_amd as vk
+    from vk_merkle_roots_amd.engine import tree_height
     h = vk.host_lib()
     rng = np.random.default_rng(13)
     cases = [(1, 1), (2, 1), (3, 2), (5, 3), (8, 3), (9, 4), (100, 7), (129, 8), (1000, 10), (1000, 14), (4097, 13), (70001, 17), (300000, 19),
@@ -403,6 +404,11 @@ def test_proofs_written_during_the_reduction_equal_the_recomputed_ones(gpu, orac
         leaves = rng.integers(0, 2**32, size=(n, 8), dtype=np.uint32)
         d_in = gpu.upload(leaves)
         want_root = gpu.reduce_digests(leaves, height)
+        # ... which is the oracle's: the threaded root, and the lone node hashed with itself for every level above it
+        oracle_root = oracle.root(leaves, threads=8)
+        for _ in range(height - tree_height(n)):
+            oracle_root = oracle.node(oracle_root, oracle_root)
+        assert (want_root == oracle_root).all(), (n, height)
         fixed = sorted({0, n - 1, n // 2, (n * 2) // 3, max(0, n - 2)})
         for K in (1, 8, 16):
             idx = (fixed + [int(x) for x in rng.integers(0, n, size=16)])[:K] if K > 1 else [fixed[-1]]
