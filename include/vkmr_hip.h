@@ -299,6 +299,55 @@ VKMR_API vkmr_status vkmr_hip_tree_update_async(int dev, vkmr_stream s, vkmr_dig
                                                 const vkmr_digest* leaves_dev, uint32_t k, uint32_t* status_dev);
 
 /*
+ * MULTIPROOF FROM THE STORED TREE (the reference has no counterpart): ONE proof for k leaves of one tree -- the proved
+ * leaves, their positions and the nodes that cannot be recomputed from them, each once -- instead of k independent proofs
+ * whose paths merge on the way up.  digests_dev and tree_dev as written by vkmr_hip_reduce_tree_async(count, height);
+ * indices_dev[0..k) in DEVICE memory, strictly increasing and < count (the rule of vkmr_hip_tree_update_async; the device
+ * checks it).  Let A_0 = the indices and A_{l+1} = unique(A_l >> 1).  For l = 0..height-1 in this order, and inside a level
+ * for p in A_l ascending: nothing when p ^ 1 is in A_l (the verifier computes that node itself), else ONE node, L[l][p ^ 1],
+ * or L[l][p] where p ^ 1 >= n_l (the cell vkmr_hip_tree_proofs_async puts there).  nodes_dev receives these M = sum of m_l
+ * cells in that order.  m_l <= min(k, n_{l+1}): vkmr_hip_multiproof_max_nodes returns the bound
+ * sum over l < height of min(k, ceil(count / 2^(l+1))) cells (0 for count == 0 or height > 63).  For k == 1 the multiproof is
+ * the single proof: M == height, the cells of vkmr_hip_tree_proofs_async.  A gather, no hash.
+ *   scratch_dev     vkmr_hip_multiproof_scratch_bytes(k, height) bytes of device memory, 16-byte aligned (0 for k == 0 or
+ *                   height > 63; one size serves the gather and the verifier below)
+ *   nodes_capacity  cells nodes_dev can hold; nodes_dev may be NULL when it is 0
+ *   info_dev        2 + height uint64_t in device memory.  info_dev[0] = status, always written: 0 done; bit 0 an index
+ *                   >= count, bit 1 indices not strictly increasing (both as vkmr_hip_tree_update_async defines them; then
+ *                   nothing else of the caller's is written: info_dev[1..] keep what they held and must not be read);
+ *                   bit 2 M > nodes_capacity (then info_dev[1] and the counts are written and valid and no node is, so the
+ *                   caller can allocate and call again).  info_dev[1] = M, info_dev[2 + l] = m_l.
+ * k == 0 does nothing whatever the other arguments; height == 0 (count == 1) writes the status and M = 0, and tree_dev,
+ * scratch_dev and nodes_dev may then be NULL.  Stream-ordered like the other tree calls: a multiproof gathered after an
+ * update on the same stream proves the new tree.
+ */
+VKMR_API size_t vkmr_hip_multiproof_max_nodes(uint64_t count, uint32_t height, uint32_t k);
+VKMR_API size_t vkmr_hip_multiproof_scratch_bytes(uint32_t k, uint32_t height);
+VKMR_API vkmr_status vkmr_hip_tree_multiproof_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev,
+                                                    const vkmr_digest* tree_dev, uint64_t count, uint32_t height,
+                                                    const uint64_t* indices_dev, uint32_t k, void* scratch_dev,
+                                                    vkmr_digest* nodes_dev, uint64_t nodes_capacity, uint64_t* info_dev);
+
+/*
+ * MULTIPROOF VERIFICATION: one root, one answer.  leaves_dev[0..k) are the proved leaves, indices_dev[0..k) their
+ * positions, nodes_dev[0..m) the multiproof in the order above; never `count`: whether p ^ 1 is in A_l follows from the
+ * indices alone, and a duplicated last node arrives as an ordinary node of the proof.  cur_0[p] = the leaf of p.  For each
+ * level, for each P in A_{l+1} ascending: of the children 2P and 2P + 1, those in A_l come from cur_l and a missing one is
+ * the next unread node; cur_{l+1}[P] = SHA-256d(left || right).  ok_dev[0] = 1 iff the indices are strictly increasing and
+ * < 2^height, exactly m nodes are consumed and cur_height[0] equals root_dev[0]; else 0.  Work: sum over l = 1..height of
+ * |A_l| node hashes, one launch per level.  The leaves are not overwritten.
+ *   height 1..63; scratch_dev: vkmr_hip_multiproof_scratch_bytes(k, height) bytes, 16-byte aligned; nodes_dev may be NULL
+ *   when m == 0; all buffers in device memory.
+ * As with vkmr_hip_verify_proofs_async, this shows membership AT POSITIONS, not the number of leaves: the known ambiguity
+ * of duplicate-last trees is unchanged.  k == 0 does nothing.  vkmr_host_cpu_verify_multiproof (libvkmr_host.so) applies the
+ * same rule on the CPU, for a receiver without a GPU.
+ */
+VKMR_API vkmr_status vkmr_hip_verify_multiproof_async(int dev, vkmr_stream s, const vkmr_digest* leaves_dev,
+                                                      const uint64_t* indices_dev, uint32_t k, uint32_t height,
+                                                      const vkmr_digest* nodes_dev, uint64_t m, const vkmr_digest* root_dev,
+                                                      void* scratch_dev, uint32_t* ok_dev);
+
+/*
  * COMBINE: duplicate-last Merkle root over n >= 1 slice roots given in slice order, always
  * at least one level -- the rule of CpuSha256D::Root that the reference applies to the slice
  * roots on the CPU (CpuSha256DforReductions, src/vkmr/Reductions.cpp:56-69, :703-712).  Here

@@ -67,6 +67,12 @@ SIGNATURES = {
                                                C.c_uint32, C.c_void_p]),
     "vkmr_hip_tree_update_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
                                              C.c_uint32, C.c_void_p]),
+    "vkmr_hip_multiproof_max_nodes": (C.c_size_t, [C.c_uint64, C.c_uint32, C.c_uint32]),
+    "vkmr_hip_multiproof_scratch_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "vkmr_hip_tree_multiproof_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32,
+                                                 C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "vkmr_hip_verify_multiproof_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
+                                                   C.c_void_p, C.c_void_p, C.c_void_p]),
     "vkmr_hip_combine_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "vkmr_hip_comm_init_all": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
     "vkmr_hip_comm_create_id": (C.c_int, [C.c_void_p]),
@@ -86,6 +92,7 @@ HOST_SIGNATURES = {
     "vkmr_host_cpu_reduce": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p]),
     "vkmr_host_cpu_combine": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p]),
     "vkmr_host_cpu_fold_proof": (None, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "vkmr_host_cpu_verify_multiproof": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]),
     "vkmr_host_rndm_pack": (C.c_int64, [C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p,
                                         C.POINTER(C.c_uint64)]),
     "vkmr_host_rndm_open": (C.c_void_p, [C.c_uint32]),

@@ -74,4 +74,43 @@ __attribute__((visibility("default"))) void vkmr_host_cpu_fold_proof(const vkmr_
     std::memcpy(root->data, cur, 32);
 }
 
+// Multiproof verification on the CPU, by the rule of vkmr_hip_verify_multiproof_async: 1 when the indices are strictly
+// increasing and < 2^height, the fold of leaves and nodes consumes exactly m nodes and ends in `root`; else 0.
+__attribute__((visibility("default"))) int vkmr_host_cpu_verify_multiproof(const vkmr_digest* leaves, const uint64_t* indices, uint32_t k,
+                                                                            uint32_t height, const vkmr_digest* nodes, uint64_t m,
+                                                                            const vkmr_digest* root)
+{
+    if (!leaves || !indices || !root || k == 0 || height > 63 || (!nodes && m > 0)) return 0;
+    for (uint32_t q = 0; q < k; ++q)
+        if ((indices[q] >> height) != 0 || (q > 0 && indices[q - 1] >= indices[q])) return 0;
+    std::vector<uint64_t> pos(indices, indices + k);
+    std::vector<vkmr_digest> cur(leaves, leaves + k);
+    uint64_t used = 0;
+    for (uint32_t l = 0; l < height; ++l) {
+        size_t out = 0;
+        for (size_t i = 0; i < pos.size();) {   // pos is strictly increasing: the children of one parent are adjacent
+            const uint64_t p = pos[i];
+            const bool both = !(p & 1ull) && i + 1 < pos.size() && pos[i + 1] == p + 1;
+            const vkmr_digest* other;
+            if (both) {
+                other = &cur[i + 1];
+            } else {
+                if (used >= m) return 0;
+                other = &nodes[used++];
+            }
+            vkmr_digest h;
+            if (p & 1ull)
+                vkmr::cpu_sha256d_pair(other->data, cur[i].data, h.data);
+            else
+                vkmr::cpu_sha256d_pair(cur[i].data, other->data, h.data);
+            i += both ? 2 : 1;
+            pos[out] = p >> 1;          // out <= i: written behind what is still to be read
+            cur[out++] = h;
+        }
+        pos.resize(out);
+        cur.resize(out);
+    }
+    return used == m && pos.size() == 1 && pos[0] == 0 && std::memcmp(cur[0].data, root->data, 32) == 0 ? 1 : 0;
+}
+
 }  // extern "C"

@@ -118,3 +118,180 @@ __global__ __launch_bounds__(256) void tree_update_level_kernel(const Node* __re
     vkmr_dev::hash_pair(a.w, b.w, o);
     vkmr_dev::store_node(out + p, o);
 }
+
+// ---- multiproofs (vkmr_hip_tree_multiproof_async, vkmr_hip_verify_multiproof_async) -------------------------------------
+// One proof for k leaves of one tree: per level l, for every node p of A_l = unique(indices >> l) whose sibling p ^ 1 is not
+// in A_l, the sibling's cell (the node's own where it has none), in level-major, ascending-p order.  Who emits follows from
+// the sorted indices alone: entry q "owns" the cell of (l, p = index_q >> l) when p is odd and q is the first lane of p's run
+// (p - 1 is in A_l iff the lane before has it), or p is even and q is the last lane of the run (p + 1 iff the lane after).
+// The gather and the verifier share the ranking of those flags:
+//   masks        one lane per entry, a loop over the levels: the flags of 64 entries as one ballot word, mask[l * W + (q >> 6)]
+//   block_sums   one lane per word: set bits per block of 256 words
+//   block_starts one workgroup: exclusive prefix over the (level, block) sums in 64 bits; M, the per-level counts, the bound
+//   word_starts  one lane per word: cells emitted before the word
+// so that the cell of (l, q) has rank word_start + popcount(mask below q's bit): two loads, and no flag is computed twice.
+// Header (uint64 words): [0] status (its low 32 bits are what tree_update_check_kernel ORs into), [1] M, [2 + l] m_l.  The
+// gather's header is the caller's info_dev, the verifier's lies in its scratch.
+
+#define VKMR_MP_HEADER_WORDS (2 + VKMR_TREE_MAX_LEVELS)   // status, M, up to 64 level counts
+#define VKMR_MP_BLOCK_WORDS 256                           // ballot words per block of the prefix sum: 16384 entries
+
+__global__ __launch_bounds__(256) void multiproof_masks_kernel(const uint64_t* __restrict__ indices, uint32_t k, uint32_t height, uint64_t words,
+                                                               uint64_t* __restrict__ mask)
+{
+    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const bool in = q < k;                       // the lanes past k vote 0: every lane of the wavefront reaches the ballots
+    const uint64_t index = in ? indices[q] : 0ull;
+    const bool has_prev = in && q > 0, has_next = in && q + 1 < k;
+    const uint64_t prev = has_prev ? indices[q - 1] : 0ull;
+    const uint64_t next = has_next ? indices[q + 1] : 0ull;
+    const uint64_t w = q >> 6;
+    for (uint32_t l = 0; l < height; ++l) {      // wave-uniform trip count
+        const uint64_t p = index >> l;
+        const bool emit_odd = !has_prev || (prev >> l) + 1ull < p;    // first of the run, and p - 1 is not there
+        const bool emit_even = !has_next || (next >> l) > p + 1ull;   // last of the run, and p + 1 is not there
+        const uint64_t m = __ballot(in && ((p & 1ull) ? emit_odd : emit_even));
+        if ((threadIdx.x & 63u) == 0u && w < words) mask[(uint64_t)l * words + w] = m;
+    }
+}
+
+__global__ __launch_bounds__(VKMR_MP_BLOCK_WORDS) void multiproof_block_sums_kernel(const uint64_t* __restrict__ mask, uint64_t words, uint64_t blocks,
+                                                                                    uint64_t* __restrict__ block)
+{
+    __shared__ uint32_t s_wave[VKMR_MP_BLOCK_WORDS / 64];
+    const uint64_t w = (uint64_t)blockIdx.x * VKMR_MP_BLOCK_WORDS + threadIdx.x;
+    const uint32_t v = w < words ? (uint32_t)__popcll(mask[(uint64_t)blockIdx.y * words + w]) : 0u;
+    uint32_t total;
+    (void)vkmr_sizes::block_exclusive(v, s_wave, &total);
+    if (threadIdx.x == 0) block[(uint64_t)blockIdx.y * blocks + blockIdx.x] = total;
+}
+
+// One workgroup.  block[] becomes its exclusive prefix; hdr[1] = M, hdr[2 + l] = m_l.  Status bit 2 when M > limit (the
+// gather: the node buffer is too small) or, with `exact`, when M != limit (the verifier: not exactly m nodes would be
+// consumed).  A status that the index check has set ends the call here: nothing else is written.
+__global__ __launch_bounds__(256) void multiproof_block_starts_kernel(uint64_t* __restrict__ block, uint64_t blocks, uint32_t height, uint64_t limit,
+                                                                      uint32_t exact, uint64_t* __restrict__ hdr)
+{
+    __shared__ uint32_t s_wave[256 / 64];
+    __shared__ uint64_t s_level[VKMR_TREE_MAX_LEVELS + 1];
+    if (hdr[0] != 0ull) return;                  // the same word in every lane
+    const uint64_t n = blocks * height;
+    uint64_t carry = 0;
+    for (uint64_t base = 0; base < n; base += 256) {   // wave-uniform trip count
+        const uint64_t i = base + threadIdx.x;
+        const uint32_t v = i < n ? (uint32_t)block[i] : 0u;   // a block holds at most 16384 cells, a round 2^22
+        uint32_t total;
+        const uint64_t start = carry + vkmr_sizes::block_exclusive(v, s_wave, &total);
+        if (i < n) {
+            block[i] = start;
+            if (i % blocks == 0) s_level[i / blocks] = start;
+        }
+        carry += total;
+        __syncthreads();   // s_wave is reused by the next round
+    }
+    if (threadIdx.x == 0) {
+        s_level[height] = carry;
+        hdr[1] = carry;
+        if (exact ? carry != limit : carry > limit) hdr[0] = 4ull;
+    }
+    __syncthreads();
+    if (threadIdx.x < height) hdr[2 + threadIdx.x] = s_level[threadIdx.x + 1] - s_level[threadIdx.x];
+}
+
+__global__ __launch_bounds__(VKMR_MP_BLOCK_WORDS) void multiproof_word_starts_kernel(const uint64_t* __restrict__ mask, uint64_t words, uint64_t blocks,
+                                                                                     const uint64_t* __restrict__ block, const uint64_t* __restrict__ hdr,
+                                                                                     uint64_t* __restrict__ word_start)
+{
+    __shared__ uint32_t s_wave[VKMR_MP_BLOCK_WORDS / 64];
+    if (hdr[0] != 0ull) return;                  // the same word in every lane
+    const uint64_t w = (uint64_t)blockIdx.x * VKMR_MP_BLOCK_WORDS + threadIdx.x;
+    const uint32_t v = w < words ? (uint32_t)__popcll(mask[(uint64_t)blockIdx.y * words + w]) : 0u;
+    uint32_t total;
+    const uint32_t ex = vkmr_sizes::block_exclusive(v, s_wave, &total);
+    if (w < words) word_start[(uint64_t)blockIdx.y * words + w] = block[(uint64_t)blockIdx.y * blocks + blockIdx.x] + ex;
+}
+
+// Rank of the cell that entry j owns at level l (its flag is set: the callers know).
+__device__ __forceinline__ uint64_t multiproof_rank(const uint64_t* __restrict__ mask, const uint64_t* __restrict__ word_start, uint64_t words, uint32_t l,
+                                                    uint64_t j)
+{
+    const uint64_t at = (uint64_t)l * words + (j >> 6);
+    return word_start[at] + (uint64_t)__popcll(mask[at] & ((1ull << (j & 63ull)) - 1ull));
+}
+
+// Gather, one lane per (level, entry): blockIdx.y = l.  A lane whose flag is set loads the sibling cell as tree_proofs_kernel
+// does and stores it at its rank; a wavefront's ranks are consecutive, so its stores lie back to back.  No hash.
+__global__ __launch_bounds__(256) void tree_multiproof_gather_kernel(const Node* __restrict__ digests, const Node* __restrict__ tree, TreeLevels lv, uint64_t count,
+                                                                     const uint64_t* __restrict__ indices, uint32_t k, uint64_t words,
+                                                                     const uint64_t* __restrict__ mask, const uint64_t* __restrict__ word_start,
+                                                                     const uint64_t* __restrict__ hdr, Node* __restrict__ nodes)
+{
+    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= k || hdr[0] != 0ull) return;
+    const uint32_t l = blockIdx.y;
+    const uint64_t at = (uint64_t)l * words + (q >> 6);
+    const uint64_t m = mask[at];
+    const uint64_t bit = 1ull << (q & 63ull);
+    if (!(m & bit)) return;
+    const uint64_t rank = word_start[at] + (uint64_t)__popcll(m & (bit - 1ull));   // < M <= the buffer's capacity: the status is 0
+    const uint64_t n = ((count - 1) >> l) + 1;     // cells of level l; the check ran: index < count, so p < n
+    const uint64_t p = indices[q] >> l;
+    const uint64_t s = ((p ^ 1ull) < n) ? (p ^ 1ull) : p;
+    const Node v = vkmr_dev::load_node((l == 0) ? digests + s : tree + lv.off[l] + s);
+    uint32_t o[8];
+#pragma unroll
+    for (int w = 0; w < 8; ++w) o[w] = v.w[w];
+    vkmr_dev::store_node(nodes + rank, o);
+}
+
+// Verifier, one launch per level l = 0..height-1 (level l + 1 from level l), one lane per entry.  The value of node p of
+// level l lives in cell[first lane of p's run], and end[that lane] is the first lane behind the run (level 0: the leaves,
+// and q + 1).  The first lane of parent P's run hashes P: an even child p is its own cell, and the run that starts at end[q]
+// is p + 1 when it has the same parent; an odd child at the head of P's run has no left sibling among the entries.  The
+// missing child is the proof's node at the rank of the entry that owns it (the last lane of an even p's run, the first of an
+// odd p's): the order the gather emits in.  A lane writes only its own cell and end, which no other lane of the launch reads
+// (the lane at end[q] lies inside P's run, not at its head), so the levels run in place.  One hash_pair: the only hash block.
+__global__ __launch_bounds__(256) void verify_multiproof_level_kernel(const Node* __restrict__ in, Node* __restrict__ cell, uint32_t* __restrict__ end,
+                                                                      const uint64_t* __restrict__ indices, uint32_t k, uint32_t l, uint64_t words,
+                                                                      const uint64_t* __restrict__ mask, const uint64_t* __restrict__ word_start,
+                                                                      const Node* __restrict__ nodes, const uint64_t* __restrict__ hdr)
+{
+    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= k || hdr[0] != 0ull) return;
+    const uint64_t p = indices[q] >> l;
+    const uint64_t P = p >> 1;
+    if (q > 0 && (indices[q - 1] >> l) >> 1 == P) return;   // not the head of P's run
+    const uint64_t e = (l == 0) ? q + 1 : (uint64_t)end[q];
+    const bool right = p & 1ull;
+    const Node* other;
+    uint64_t e2 = e;
+    if (right) {
+        other = nodes + multiproof_rank(mask, word_start, words, l, q);
+    } else if (e < k && (indices[e] >> l) >> 1 == P) {
+        other = in + e;
+        e2 = (l == 0) ? e + 1 : (uint64_t)end[e];
+    } else {
+        other = nodes + multiproof_rank(mask, word_start, words, l, e - 1);
+    }
+    // the operand order is chosen on the pointers: selecting between the loaded nodes word by word went through scratch
+    const Node x = vkmr_dev::load_node(right ? other : in + q), y = vkmr_dev::load_node(right ? in + q : other);
+    uint32_t o[8];
+    vkmr_dev::hash_pair(x.w, y.w, o);
+    vkmr_dev::store_node(cell + q, o);
+    end[q] = (uint32_t)e2;
+}
+
+// ok = 1 when the checks passed (status 0: indices strictly increasing and < 2^height, exactly m nodes consumed) and the
+// value of node 0 of level `height` (cell 0) equals the root.
+__global__ void verify_multiproof_finish_kernel(const Node* __restrict__ cell, const Node* __restrict__ root, const uint64_t* __restrict__ hdr,
+                                                uint32_t* __restrict__ ok)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    uint32_t diff = hdr[0] != 0ull ? 1u : 0u;
+    if (!diff) {                                  // the cells are only written when the status is 0
+        const Node c = vkmr_dev::load_node(cell), r = vkmr_dev::load_node(root);
+#pragma unroll
+        for (int w = 0; w < 8; ++w) diff |= c.w[w] ^ r.w[w];
+    }
+    ok[0] = diff == 0u ? 1u : 0u;
+}

@@ -8,6 +8,8 @@
 //   tree_kernels.hpp    tree_proofs_kernel     proofs gathered from the stored tree (README.md:118-120)
 //                       verify_proofs_kernel   batch proof verification, one lane per proof (no reference counterpart)
 //                       tree_update_*_kernel   leaf updates: check, store the leaves, rehash the dirty nodes level by level
+//                       multiproof_*_kernel, tree_multiproof_gather_kernel, verify_multiproof_*_kernel   one proof for k leaves:
+//                                              rank the nodes to emit, gather them; fold leaves and nodes level by level
 //   sha256d_device.hpp  the SHA-256 round / compression building blocks
 //   meta_kernels.hpp    sizes_*_kernel         metadata entries from 16-bit sizes   (Batches.cpp:64-121)
 //
@@ -852,6 +854,127 @@ vkmr_status vkmr_hip_tree_update_async(int dev, vkmr_stream s, vkmr_digest* dige
                            indices_dev, k, l, (const uint32_t*)status_dev);
         VKMR_TRY(hipGetLastError());
     }
+    return VKMR_OK;
+}
+
+// ---- multiproofs: one proof for k leaves of one stored tree (tree_kernels.hpp) ----------------------------------------------
+
+size_t vkmr_hip_multiproof_max_nodes(uint64_t count, uint32_t height, uint32_t k)
+{
+    if (count == 0 || height > 63) return 0;
+    uint64_t cells = 0;
+    for (uint32_t l = 0; l < height; ++l) {   // at most one node per pair of level l
+        const uint64_t pairs = ceil_shift(count, l + 1);
+        cells += pairs < k ? pairs : k;
+    }
+    return (size_t)cells;
+}
+
+// Where the parts of scratch_dev lie.  The cells come first (16-byte loads); the gather uses mask, word_start and block only.
+struct MultiproofLayout {
+    uint64_t words, blocks;   // ballot words per level, blocks of VKMR_MP_BLOCK_WORDS words per level
+    size_t cell, mask, word_start, block, hdr, end, bytes;
+};
+
+static MultiproofLayout multiproof_layout(uint32_t k, uint32_t height)
+{
+    MultiproofLayout L;
+    L.words = ((uint64_t)k + 63) / 64;
+    L.blocks = (L.words + VKMR_MP_BLOCK_WORDS - 1) / VKMR_MP_BLOCK_WORDS;
+    size_t at = 0;
+    L.cell = at;       at += (size_t)k * sizeof(vkmr_digest);
+    L.mask = at;       at += (size_t)(L.words * height) * sizeof(uint64_t);
+    L.word_start = at; at += (size_t)(L.words * height) * sizeof(uint64_t);
+    L.block = at;      at += (size_t)(L.blocks * height) * sizeof(uint64_t);
+    L.hdr = at;        at += VKMR_MP_HEADER_WORDS * sizeof(uint64_t);
+    L.end = at;        at += (size_t)k * sizeof(uint32_t);
+    L.bytes = at;
+    return L;
+}
+
+size_t vkmr_hip_multiproof_scratch_bytes(uint32_t k, uint32_t height)
+{
+    if (k == 0 || height > 63) return 0;
+    return multiproof_layout(k, height).bytes;
+}
+
+// The launches both calls share: the index check into hdr[0], then the ranking of the emit flags (masks, block sums, block
+// starts, word starts).  `count` is the bound of the index check; limit / exact as multiproof_block_starts_kernel takes them.
+static vkmr_status multiproof_rank_launch(hipStream_t stream, const uint64_t* indices_dev, uint32_t k, uint64_t count, uint32_t height,
+                                          const MultiproofLayout& L, char* scratch, uint64_t* hdr, uint64_t limit, uint32_t exact)
+{
+    const uint32_t grid = (uint32_t)(((uint64_t)k + 255) / 256);
+    VKMR_TRY(hipMemsetAsync(hdr, 0, (height == 0 ? 2 : 1) * sizeof(uint64_t), stream));
+    hipLaunchKernelGGL(tree_update_check_kernel, dim3(grid), dim3(256), 0, stream, indices_dev, k, count, reinterpret_cast<uint32_t*>(hdr));
+    VKMR_TRY(hipGetLastError());
+    if (height == 0) return VKMR_OK;
+    uint64_t* mask = reinterpret_cast<uint64_t*>(scratch + L.mask);
+    uint64_t* word_start = reinterpret_cast<uint64_t*>(scratch + L.word_start);
+    uint64_t* block = reinterpret_cast<uint64_t*>(scratch + L.block);
+    const dim3 wgrid((uint32_t)L.blocks, height);
+    hipLaunchKernelGGL(multiproof_masks_kernel, dim3(grid), dim3(256), 0, stream, indices_dev, k, height, L.words, mask);
+    VKMR_TRY(hipGetLastError());
+    hipLaunchKernelGGL(multiproof_block_sums_kernel, wgrid, dim3(VKMR_MP_BLOCK_WORDS), 0, stream, (const uint64_t*)mask, L.words, L.blocks, block);
+    VKMR_TRY(hipGetLastError());
+    hipLaunchKernelGGL(multiproof_block_starts_kernel, dim3(1), dim3(256), 0, stream, block, L.blocks, height, limit, exact, hdr);
+    VKMR_TRY(hipGetLastError());
+    hipLaunchKernelGGL(multiproof_word_starts_kernel, wgrid, dim3(VKMR_MP_BLOCK_WORDS), 0, stream, (const uint64_t*)mask, L.words, L.blocks,
+                       (const uint64_t*)block, (const uint64_t*)hdr, word_start);
+    VKMR_TRY(hipGetLastError());
+    return VKMR_OK;
+}
+
+vkmr_status vkmr_hip_tree_multiproof_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* tree_dev, uint64_t count,
+                                           uint32_t height, const uint64_t* indices_dev, uint32_t k, void* scratch_dev, vkmr_digest* nodes_dev,
+                                           uint64_t nodes_capacity, uint64_t* info_dev)
+{
+    if (k == 0) return VKMR_OK;
+    if (!digests_dev || !indices_dev || !info_dev || (height > 0 && (!tree_dev || !scratch_dev)) || (!nodes_dev && nodes_capacity > 0))
+        return fail(VKMR_ERR_INVALID, "vkmr_hip_tree_multiproof_async: null pointer");
+    if (!height_ok(count, height))
+        return fail(VKMR_ERR_INVALID, "vkmr_hip_tree_multiproof_async: height does not reduce count to one node");
+    TreeLevels lv;
+    tree_levels(count, height, &lv);
+    const MultiproofLayout L = multiproof_layout(k, height);
+    char* scratch = static_cast<char*>(scratch_dev);
+    VKMR_TRY(hipSetDevice(dev));
+    const vkmr_status st = multiproof_rank_launch(S(s), indices_dev, k, count, height, L, scratch, info_dev, nodes_capacity, 0u);
+    if (st != VKMR_OK || height == 0) return st;
+    hipLaunchKernelGGL(tree_multiproof_gather_kernel, dim3((uint32_t)(((uint64_t)k + 255) / 256), height), dim3(256), 0, S(s),
+                       reinterpret_cast<const Node*>(digests_dev), reinterpret_cast<const Node*>(tree_dev), lv, count, indices_dev, k, L.words,
+                       reinterpret_cast<const uint64_t*>(scratch + L.mask), reinterpret_cast<const uint64_t*>(scratch + L.word_start),
+                       (const uint64_t*)info_dev, reinterpret_cast<Node*>(nodes_dev));
+    VKMR_TRY(hipGetLastError());
+    return VKMR_OK;
+}
+
+vkmr_status vkmr_hip_verify_multiproof_async(int dev, vkmr_stream s, const vkmr_digest* leaves_dev, const uint64_t* indices_dev, uint32_t k,
+                                             uint32_t height, const vkmr_digest* nodes_dev, uint64_t m, const vkmr_digest* root_dev,
+                                             void* scratch_dev, uint32_t* ok_dev)
+{
+    if (k == 0) return VKMR_OK;
+    if (!leaves_dev || !indices_dev || !root_dev || !scratch_dev || !ok_dev || (!nodes_dev && m > 0))
+        return fail(VKMR_ERR_INVALID, "vkmr_hip_verify_multiproof_async: null pointer");
+    if (height == 0 || height > 63) return fail(VKMR_ERR_INVALID, "vkmr_hip_verify_multiproof_async: height must be 1..63");
+    const MultiproofLayout L = multiproof_layout(k, height);
+    char* scratch = static_cast<char*>(scratch_dev);
+    uint64_t* hdr = reinterpret_cast<uint64_t*>(scratch + L.hdr);
+    Node* cell = reinterpret_cast<Node*>(scratch + L.cell);
+    VKMR_TRY(hipSetDevice(dev));
+    // the index check with 2^height as the bound: bit 0 an index outside the tree, bit 1 not strictly increasing; exact: M == m
+    const vkmr_status st = multiproof_rank_launch(S(s), indices_dev, k, 1ull << height, height, L, scratch, hdr, m, 1u);
+    if (st != VKMR_OK) return st;
+    const uint32_t grid = (uint32_t)(((uint64_t)k + 255) / 256);
+    for (uint32_t l = 0; l < height; ++l) {   // level l + 1 from level l, which the previous launch finished
+        hipLaunchKernelGGL(verify_multiproof_level_kernel, dim3(grid), dim3(256), 0, S(s), l == 0 ? reinterpret_cast<const Node*>(leaves_dev) : cell,
+                           cell, reinterpret_cast<uint32_t*>(scratch + L.end), indices_dev, k, l, L.words,
+                           reinterpret_cast<const uint64_t*>(scratch + L.mask), reinterpret_cast<const uint64_t*>(scratch + L.word_start),
+                           reinterpret_cast<const Node*>(nodes_dev), (const uint64_t*)hdr);
+        VKMR_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(verify_multiproof_finish_kernel, dim3(1), dim3(64), 0, S(s), (const Node*)cell, reinterpret_cast<const Node*>(root_dev),
+                       (const uint64_t*)hdr, ok_dev);
+    VKMR_TRY(hipGetLastError());
     return VKMR_OK;
 }
 

@@ -258,6 +258,38 @@ class HipDevice:
                                                   count, height, indices_buf.ptr, leaves_buf.ptr, k, status_buf.ptr),
               "vkmr_hip_tree_update_async")
 
+    def tree_multiproof_async(self, digests_buf, tree_buf, count, height, indices_buf, k, scratch_buf, nodes_buf, nodes_capacity, info_buf,
+                              stream=None):
+        check(self.lib.vkmr_hip_tree_multiproof_async(self.index, stream or self.stream, digests_buf.ptr, tree_buf.ptr if tree_buf else None,
+                                                      count, height, indices_buf.ptr, k, scratch_buf.ptr if scratch_buf else None,
+                                                      nodes_buf.ptr if nodes_buf else None, nodes_capacity, info_buf.ptr),
+              "vkmr_hip_tree_multiproof_async")
+
+    def verify_multiproof_async(self, leaves_buf, indices_buf, k, height, nodes_buf, m, root_buf, scratch_buf, ok_buf, stream=None):
+        check(self.lib.vkmr_hip_verify_multiproof_async(self.index, stream or self.stream, leaves_buf.ptr, indices_buf.ptr, k, height,
+                                                        nodes_buf.ptr if nodes_buf else None, m, root_buf.ptr, scratch_buf.ptr, ok_buf.ptr),
+              "vkmr_hip_verify_multiproof_async")
+
+    def verify_multiproof(self, leaves, indices, nodes, root, height):
+        """bool: the multiproof `nodes` ([M, 8]) proves leaves ([k, 8]) at `indices` ([k], strictly increasing) under `root`
+        in a tree of `height` levels (1..63).  Host arrays in, verified on the device; no leaf proves nothing: False."""
+        leaves = np.ascontiguousarray(leaves, dtype=np.uint32).reshape(-1, 8)
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        nodes = np.ascontiguousarray(nodes, dtype=np.uint32).reshape(-1, 8)
+        root = np.ascontiguousarray(root, dtype=np.uint32).reshape(8)
+        k, m = int(idx.shape[0]), int(nodes.shape[0])
+        if leaves.shape[0] != k:
+            raise ValueError("verify_multiproof: one leaf per index")
+        if k == 0:
+            return False
+        bufs = [self.upload(a) for a in (leaves, idx, nodes, root)]
+        d_scr, d_ok = self.alloc(self.lib.vkmr_hip_multiproof_scratch_bytes(k, height)), self.alloc(4)
+        self.verify_multiproof_async(bufs[0], bufs[1], k, height, bufs[2] if m else None, m, bufs[3], d_scr, d_ok)
+        ok = int(self.download(d_ok, 4)[0])
+        for b in bufs + [d_scr, d_ok]:
+            b.free()
+        return ok == 1
+
     def build_tree(self, digests_buf, count, height=None):
         """Every level of the tree over `count` digests in `digests_buf` (which stays level 0 and must outlive the tree),
         kept on the device: a MerkleTree."""
@@ -335,6 +367,15 @@ class HipDevice:
         return root
 
 
+class Multiproof:
+    """One proof for several leaves of one tree (vkmr_hip_tree_multiproof_async): `indices` uint64 [k] sorted and unique,
+    `nodes` uint32 [M, 8] in level-major order, `level_counts` uint64 [height] (nodes per level), `height`.  With the leaves
+    at `indices` and the root it is what HipDevice.verify_multiproof and vkmr_host_cpu_verify_multiproof take."""
+
+    def __init__(self, indices, nodes, level_counts, height):
+        self.indices, self.nodes, self.level_counts, self.height = indices, nodes, level_counts, int(height)
+
+
 class MerkleTree:
     """Every level of a duplicate-last tree, resident on the device (vkmr_hip_reduce_tree_async): level 0 is the digests
     buffer it was built from, levels 1..height one buffer laid out as include/vkmr_hip.h describes."""
@@ -383,29 +424,61 @@ class MerkleTree:
         d_sib.free()
         return out
 
+    def multiproof_async(self, indices_buf, k, scratch_buf, nodes_buf, nodes_capacity, info_buf, stream=None):
+        """ONE proof for the k leaves whose strictly increasing indices are in device memory, written to nodes_buf
+        (nodes_capacity cells); info_buf: 2 + height uint64 (status, M, the per-level counts).  include/vkmr_hip.h."""
+        self.dev.tree_multiproof_async(self.digests, self.tree, self.count, self.height, indices_buf, k, scratch_buf, nodes_buf, nodes_capacity,
+                                       info_buf, stream=stream)
+
+    def multiproof(self, indices):
+        """A Multiproof of leaves `indices` (a host array; sorted and deduplicated here).  IndexError for an index < 0 or
+        >= count, ValueError for indices that are not integers or for none at all, before any device call."""
+        idx, _ = self._update_order(indices, "multiproof")
+        k = int(idx.shape[0])
+        if k == 0:
+            raise ValueError("multiproof: no index")
+        lib = self.dev.lib
+        cap = lib.vkmr_hip_multiproof_max_nodes(self.count, self.height, k)
+        d_idx = self.dev.upload(idx)
+        d_scr = self.dev.alloc(lib.vkmr_hip_multiproof_scratch_bytes(k, self.height)) if self.height else None
+        d_nodes = self.dev.alloc(32 * cap) if cap else None
+        d_info = self.dev.alloc(8 * (2 + self.height))
+        self.multiproof_async(d_idx, k, d_scr, d_nodes, cap, d_info)
+        status = int(self.dev.download(d_info, 8, dtype=np.uint64)[0])
+        if status == 0:                       # M and the counts are only written then (or with bit 2)
+            info = self.dev.download(d_info, 8 * (2 + self.height), dtype=np.uint64)
+            m = int(info[1])
+            nodes = self.dev.download(d_nodes, 32 * m).reshape(m, 8) if m else np.zeros((0, 8), dtype=np.uint32)
+        for b in (d_idx, d_scr, d_nodes, d_info):
+            if b:
+                b.free()
+        if status:
+            raise RuntimeError(f"MerkleTree.multiproof: the device refused sorted in-range indices (status {status})")
+        return Multiproof(idx, nodes, info[2:].copy(), self.height)
+
     def update_async(self, indices_buf, leaves_buf, k, status_buf, stream=None):
         """Leaves indices[q] = leaves[q], q < k, and every ancestor rehashed, on the device: indices [k] uint64 strictly
         increasing and < count, leaves [k, 8], status one uint32 (0: applied; bit 0: an index >= count, bit 1: not strictly
         increasing; nonzero: nothing changed).  All in device memory; ordered on `stream` like the proof gather."""
         self.dev.tree_update_async(self.digests, self.tree, self.count, self.height, indices_buf, leaves_buf, k, status_buf, stream=stream)
 
-    def _update_order(self, indices):
+    def _update_order(self, indices, what="update"):
         """(sorted unique uint64 indices, positions in `indices` they come from): the last occurrence of a repeated index
         wins.  IndexError for an index < 0 or >= count; no device call."""
         raw = np.asarray(indices).reshape(-1)
         if raw.dtype.kind == "O":            # Python ints numpy could not fit in one integer type
             vals = [int(x) for x in raw]
             if any(v < 0 or v >= self.count for v in vals):
-                raise IndexError(f"update: index outside [0, {self.count})")
+                raise IndexError(f"{what}: index outside [0, {self.count})")
             idx = np.array(vals, dtype=np.uint64)
         elif raw.size and raw.dtype.kind not in "iu":
-            raise ValueError("update: indices must be integers")
+            raise ValueError(f"{what}: indices must be integers")
         else:
             if raw.dtype.kind == "i" and (raw < 0).any():
-                raise IndexError("update: negative index")
+                raise IndexError(f"{what}: negative index")
             idx = raw.astype(np.uint64)
             if (idx >= np.uint64(self.count)).any():
-                raise IndexError(f"update: index outside [0, {self.count})")
+                raise IndexError(f"{what}: index outside [0, {self.count})")
         order = np.argsort(idx, kind="stable")
         s = idx[order]
         last = np.ones(s.shape[0], dtype=bool)
