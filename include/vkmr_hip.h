@@ -348,6 +348,33 @@ VKMR_API vkmr_status vkmr_hip_verify_multiproof_async(int dev, vkmr_stream s, co
                                                       void* scratch_dev, uint32_t* ok_dev);
 
 /*
+ * FOREST (the reference has no counterpart: it reduces one stream to one root): the roots of `ntrees` independent trees of
+ * unequal size in ONE call -- the blocks of a chain, the files of an index, the accounts of a state.  digests_dev holds
+ * `total` cells, the leaves of all trees back to back; offsets_dev is ntrees + 1 uint64_t in DEVICE memory and tree t is
+ * cells [offsets[t], offsets[t+1]), c_t of them.  roots_dev[t] receives what vkmr_hip_reduce_async(c_t, h_t) writes with
+ * h_t = max(1, ceil(log2 c_t)): the single-slice rule (duplicate-last at every level, a lone leaf hashed with itself once).
+ * An empty tree (c_t == 0) gets an all-zero cell and is not an error.
+ *   max_count    the caller's upper bound on every c_t (at least 1; a value above `total` is treated as `total`).  It
+ *                fixes the number of levels, and so the launches, without the host reading the offsets: one launch per
+ *                level, max(1, ceil(log2 max_count)) of them, one lane per node of the whole forest at that level.  The
+ *                launch sequence depends on (total, ntrees, max_count) only and never grows with ntrees.
+ *   status_dev   one uint32_t in device memory, always written: 0 when done.  The host cannot check offsets that live on
+ *                the device; the device does, before any root is written: bit 0 set if the offsets decrease somewhere or
+ *                offsets[ntrees] > total, bit 1 if some c_t > max_count.  When it is nonzero NO cell of roots_dev is
+ *                written (the rule of vkmr_hip_tree_update_async).
+ *   scratch_dev  vkmr_hip_forest_scratch_bytes(total, ntrees) bytes of device memory, 16-byte aligned:
+ *                32 * ((total >> 1) + (total >> 2) + 2 * ntrees), an upper bound for EVERY forest of at most `total`
+ *                leaves in at most `ntrees` trees; 0 for ntrees == 0.
+ * ntrees == 0 does nothing whatever the other arguments.  total == 0 with ntrees > 0 is allowed (every tree empty) and
+ * digests_dev may then be NULL.  Stream-ordered: no allocation, no host synchronisation, no host read of device data.
+ * vkmr_host_cpu_forest_roots (libvkmr_host.so) applies the same rule on the CPU, for a receiver without a GPU.
+ */
+VKMR_API size_t vkmr_hip_forest_scratch_bytes(uint64_t total, uint32_t ntrees);
+VKMR_API vkmr_status vkmr_hip_reduce_forest_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t total,
+                                                  const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count,
+                                                  void* scratch_dev, vkmr_digest* roots_dev, uint32_t* status_dev);
+
+/*
  * COMBINE: duplicate-last Merkle root over n >= 1 slice roots given in slice order, always
  * at least one level -- the rule of CpuSha256D::Root that the reference applies to the slice
  * roots on the CPU (CpuSha256DforReductions, src/vkmr/Reductions.cpp:56-69, :703-712).  Here

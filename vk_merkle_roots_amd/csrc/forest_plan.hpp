@@ -1,0 +1,54 @@
+// forest_plan.hpp -- where the nodes of a forest lie, level by level, and the scratch budget of its reduction
+// (vkmr_hip_reduce_forest_async).  Plain integer arithmetic, no HIP types: shared by the kernels (forest_kernels.hpp), the
+// C ABI (vkmr_hip.hip) and the CPU-side sweep in tests/c/forest_plan_test.cpp, which checks that no two trees' cells
+// overlap and that no launch writes past what vkmr_hip_forest_scratch_bytes() promises.
+//
+// A forest is `ntrees` trees whose leaves lie back to back: tree t is cells [offsets[t], offsets[t+1]) of the leaves,
+// c_t of them.  Level 0 is the caller's buffer.  Level l >= 1 of tree t (ceil(c_t / 2^l) nodes) starts at cell
+//     pos_l(t) = (offsets[t] >> l) + t
+// of that level's buffer.  No prefix sum is needed to find it, and consecutive trees never overlap:
+//     pos_l(t+1) - pos_l(t) = ((offsets[t] + c_t) >> l) - (offsets[t] >> l) + 1 >= (c_t >> l) + 1 >= ceil(c_t / 2^l).
+// pos_l is strictly increasing in t, so the tree a cell belongs to is found by binary search over the offsets alone.
+// The last tree ends at or before (offsets[ntrees] >> l) + 1 + (ntrees - 1) <= (total >> l) + ntrees: the cells of level l.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define VKMR_FOREST_FN __host__ __device__ __forceinline__
+#else
+#define VKMR_FOREST_FN inline
+#endif
+
+namespace vkmr_forest {
+
+// Levels of the tree over c >= 1 leaves: max(1, ceil(log2 c)) -- a lone leaf is hashed with itself once (the single-slice
+// rule of vkmr_hip_reduce_async).
+VKMR_FOREST_FN uint32_t height(uint64_t c) { return c <= 2 ? 1u : 64u - (uint32_t)__builtin_clzll(c - 1); }
+
+// Nodes of level l of a tree over c leaves: ceil(c / 2^l), and 0 for an empty tree.
+VKMR_FOREST_FN uint64_t level_count(uint64_t c, uint32_t l) { return c == 0 ? 0 : ((c - 1) >> l) + 1; }
+
+// First cell of tree t's level l: in the caller's leaves for l == 0, in the level's own buffer otherwise.
+VKMR_FOREST_FN uint64_t pos(uint64_t offset, uint32_t t, uint32_t l) { return l == 0 ? offset : (offset >> l) + t; }
+
+// Cells of the buffer of level l >= 1 (one lane per cell in the launch that forms it).
+VKMR_FOREST_FN uint64_t level_cells(uint64_t total, uint32_t ntrees, uint32_t l) { return (l >= 64 ? 0 : total >> l) + ntrees; }
+
+// Launches: one per level up to the height of the largest tree the caller allows (max_count above total counts as total).
+inline uint32_t launches(uint64_t total, uint64_t max_count)
+{
+    const uint64_t m = max_count < total ? max_count : total;
+    return m <= 1 ? 1u : height(m);
+}
+
+// Two ping-pong buffers: odd levels in A = [0, level_cells(1)), even levels in B behind it (every later level is no
+// larger than the one two below it).  A tree's last level goes to roots_dev, not to scratch, so the last launch writes none.
+inline uint64_t level_base(uint64_t total, uint32_t ntrees, uint32_t l) { return (l & 1u) ? 0 : level_cells(total, ntrees, 1); }
+
+// The scratch budget in cells: (total >> 1) + (total >> 2) + 2 * ntrees, and nothing for no tree.  Monotone in both.
+inline uint64_t scratch_cells(uint64_t total, uint32_t ntrees)
+{
+    return ntrees == 0 ? 0 : level_cells(total, ntrees, 1) + level_cells(total, ntrees, 2);
+}
+
+}  // namespace vkmr_forest

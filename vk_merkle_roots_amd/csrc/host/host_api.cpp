@@ -113,4 +113,28 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_verify_multiproof(const
     return used == m && pos.size() == 1 && pos[0] == 0 && std::memcmp(cur[0].data, root->data, 32) == 0 ? 1 : 0;
 }
 
+// Roots of a forest on the CPU, by the rule of vkmr_hip_reduce_forest_async: tree t is digests[offsets[t] .. offsets[t+1]),
+// reduced through max(1, ceil(log2 c_t)) levels (vkmr_host_cpu_reduce); an empty tree gets an all-zero root.  Nonzero when
+// the offsets decrease somewhere (nothing is written then) or a pointer is missing.
+__attribute__((visibility("default"))) int vkmr_host_cpu_forest_roots(const vkmr_digest* digests, const uint64_t* offsets, uint32_t ntrees,
+                                                                       vkmr_digest* roots)
+{
+    if (ntrees == 0) return 0;
+    if (!offsets || !roots) return -1;
+    for (uint32_t t = 0; t < ntrees; ++t)
+        if (offsets[t + 1] < offsets[t]) return 1;
+    if (!digests && offsets[ntrees] > offsets[0]) return -1;
+    for (uint32_t t = 0; t < ntrees; ++t) {
+        const uint64_t c = offsets[t + 1] - offsets[t];
+        if (c == 0) {
+            std::memset(roots[t].data, 0, 32);
+            continue;
+        }
+        uint32_t height = 1;
+        while (((c - 1) >> height) != 0) ++height;
+        if (vkmr_host_cpu_reduce(digests + offsets[t], c, height, &roots[t]) != 0) return -1;
+    }
+    return 0;
+}
+
 }  // extern "C"

@@ -10,6 +10,8 @@
 //                       tree_update_*_kernel   leaf updates: check, store the leaves, rehash the dirty nodes level by level
 //                       multiproof_*_kernel, tree_multiproof_gather_kernel, verify_multiproof_*_kernel   one proof for k leaves:
 //                                              rank the nodes to emit, gather them; fold leaves and nodes level by level
+//   forest_kernels.hpp  forest_check_kernel, forest_level_kernel   roots of many trees of unequal size: one lane per node of the
+//                                              whole forest, level by level (no reference counterpart)
 //   sha256d_device.hpp  the SHA-256 round / compression building blocks
 //   meta_kernels.hpp    sizes_*_kernel         metadata entries from 16-bit sizes   (Batches.cpp:64-121)
 //
@@ -37,6 +39,7 @@ using vkmr_dev::Node;
 #include "reduce_kernels.hpp"
 #include "reduce_plan.hpp"
 #include "tree_kernels.hpp"
+#include "forest_kernels.hpp"
 
 // ============================================================================
 // C ABI
@@ -975,6 +978,45 @@ vkmr_status vkmr_hip_verify_multiproof_async(int dev, vkmr_stream s, const vkmr_
     hipLaunchKernelGGL(verify_multiproof_finish_kernel, dim3(1), dim3(64), 0, S(s), (const Node*)cell, reinterpret_cast<const Node*>(root_dev),
                        (const uint64_t*)hdr, ok_dev);
     VKMR_TRY(hipGetLastError());
+    return VKMR_OK;
+}
+
+// ---- forest: the roots of many trees of unequal size (forest_kernels.hpp, forest_plan.hpp) ---------------------------------
+
+size_t vkmr_hip_forest_scratch_bytes(uint64_t total, uint32_t ntrees)
+{
+    // two ping-pong level buffers: ((total >> 1) + ntrees) + ((total >> 2) + ntrees) cells -- vkmr_forest::scratch_cells
+    return (size_t)vkmr_forest::scratch_cells(total, ntrees) * sizeof(vkmr_digest);
+}
+
+vkmr_status vkmr_hip_reduce_forest_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t total, const uint64_t* offsets_dev,
+                                         uint32_t ntrees, uint64_t max_count, void* scratch_dev, vkmr_digest* roots_dev, uint32_t* status_dev)
+{
+    if (ntrees == 0) return VKMR_OK;
+    if ((!digests_dev && total > 0) || !offsets_dev || !scratch_dev || !roots_dev || !status_dev)
+        return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_forest_async: null pointer");
+    if (max_count == 0) return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_forest_async: max_count must be at least 1");
+    if (reinterpret_cast<uintptr_t>(scratch_dev) & 15u) return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_forest_async: scratch must be 16-byte aligned");
+    if (total > (1ull << 58)) return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_forest_async: forest too large");
+    if (max_count > total) max_count = total;
+    const uint32_t levels = vkmr_forest::launches(total, max_count);
+    if ((vkmr_forest::level_cells(total, ntrees, 1) + 255) / 256 > 0x7fffffffull)
+        return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_forest_async: forest too large");
+    const Node* digests = reinterpret_cast<const Node*>(digests_dev);
+    Node* scratch = reinterpret_cast<Node*>(scratch_dev);
+    Node* roots = reinterpret_cast<Node*>(roots_dev);
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_TRY(hipMemsetAsync(status_dev, 0, sizeof(uint32_t), S(s)));
+    hipLaunchKernelGGL(forest_check_kernel, dim3((uint32_t)(((uint64_t)ntrees + 255) / 256)), dim3(256), 0, S(s), offsets_dev, ntrees, total, max_count,
+                       status_dev);
+    VKMR_TRY(hipGetLastError());
+    for (uint32_t l = 1; l <= levels; ++l) {   // level l from level l - 1, which the previous launch finished
+        const Node* in = (l == 1) ? digests : scratch + vkmr_forest::level_base(total, ntrees, l - 1);
+        const uint64_t cells = vkmr_forest::level_cells(total, ntrees, l);
+        hipLaunchKernelGGL(forest_level_kernel, dim3((uint32_t)((cells + 255) / 256)), dim3(256), 0, S(s), in, offsets_dev, ntrees, l, cells,
+                           scratch + vkmr_forest::level_base(total, ntrees, l), roots, (const uint32_t*)status_dev);
+        VKMR_TRY(hipGetLastError());
+    }
     return VKMR_OK;
 }
 

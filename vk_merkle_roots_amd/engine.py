@@ -318,6 +318,48 @@ class HipDevice:
             b.free()
         return ok == 1
 
+    # -- forest: the roots of many trees of unequal size in one call ----------------------
+    def reduce_forest_async(self, digests_buf, total, offsets_buf, ntrees, max_count, scratch_buf, roots_buf, status_buf, stream=None):
+        check(self.lib.vkmr_hip_reduce_forest_async(self.index, stream or self.stream, digests_buf.ptr if digests_buf else None, total,
+                                                    offsets_buf.ptr if offsets_buf else None, ntrees, max_count,
+                                                    scratch_buf.ptr if scratch_buf else None, roots_buf.ptr if roots_buf else None,
+                                                    status_buf.ptr if status_buf else None), "vkmr_hip_reduce_forest_async")
+
+    def _forest_of_buffer(self, d_leaves, total, counts, max_count, what):
+        """[ntrees, 8] uint32: the roots of the trees of `counts` leaves each over the `total` cells of d_leaves."""
+        offsets, ntrees = forest_offsets(counts)
+        if int(offsets[-1]) != total:
+            raise ValueError(f"{what}: the counts add up to {int(offsets[-1])}, not to the {total} leaves")
+        if ntrees == 0:
+            return np.zeros((0, 8), dtype=np.uint32)
+        if max_count is None:
+            max_count = max(1, int(np.diff(offsets).max()))
+        d_off = self.upload(offsets)
+        d_scr = self.alloc(self.lib.vkmr_hip_forest_scratch_bytes(total, ntrees))
+        d_roots, d_status = self.alloc(32 * ntrees), self.alloc(4)
+        self.reduce_forest_async(d_leaves, total, d_off, ntrees, max_count, d_scr, d_roots, d_status)
+        status = int(self.download(d_status, 4)[0])
+        roots = self.download(d_roots, 32 * ntrees).reshape(ntrees, 8) if status == 0 else None
+        for b in (d_off, d_scr, d_roots, d_status):
+            b.free()
+        if status:
+            raise ValueError(f"{what}: the device refused the forest (status {status}: {forest_status_text(status)})")
+        return roots
+
+    def forest_roots(self, digests, counts, max_count=None):
+        """[ntrees, 8] uint32: the root of every tree of a forest (vkmr_hip_reduce_forest_async).  `digests` [total, 8] holds the
+        leaves of all trees back to back, tree t the next counts[t] of them; an empty tree gets an all-zero root.  max_count:
+        an upper bound on every count (the largest count when None).  ValueError when the counts do not add up to the
+        leaves, or when the device refuses the forest (a count above max_count)."""
+        digests = np.ascontiguousarray(digests, dtype=np.uint32).reshape(-1, 8)
+        total = int(digests.shape[0])
+        d_in = self.upload(digests) if total else None
+        try:
+            return self._forest_of_buffer(d_in, total, counts, max_count, "forest_roots")
+        finally:
+            if d_in:
+                d_in.free()
+
     def reduce_scratch(self, count, levels_variant=False):
         fn = self.lib.vkmr_hip_reduce_levels_scratch_bytes if levels_variant else self.lib.vkmr_hip_reduce_scratch_bytes
         return self.alloc(fn(count))
@@ -553,6 +595,50 @@ def merkle_tree_packed(dev, batch, height=None):
     d_data.free()
     d_meta.free()
     return tree
+
+
+def forest_offsets(counts):
+    """(offsets uint64 [ntrees + 1], ntrees) of trees of `counts` leaves laid back to back from cell 0."""
+    raw = np.asarray(counts).reshape(-1)
+    if raw.size and raw.dtype.kind not in "iu":
+        raise ValueError("forest: counts must be integers")
+    if raw.size and raw.dtype.kind == "i" and (raw < 0).any():
+        raise ValueError("forest: negative count")
+    offsets = np.zeros(raw.size + 1, dtype=np.uint64)
+    np.cumsum(raw.astype(np.uint64), out=offsets[1:])
+    return offsets, int(raw.size)
+
+
+def forest_status_text(status):
+    """The bits of vkmr_hip_reduce_forest_async's status word, named."""
+    names = []
+    if status & 1:
+        names.append("bit 0: the offsets decrease or end past the leaves")
+    if status & 2:
+        names.append("bit 1: a tree holds more than max_count leaves")
+    if status & ~3:
+        names.append("unknown bits")
+    return "; ".join(names) if names else "ok"
+
+
+def merkle_roots_packed_forest(dev, batch, counts, max_count=None):
+    """One root per block from a stream of strings: `batch` is mapped to leaf digests ONCE and ONE forest call reduces tree t
+    over the next counts[t] of them.  [ntrees, 8] uint32 (digest_hex gives the canonical text); no digest goes through
+    the host."""
+    offsets, _ = forest_offsets(counts)
+    if int(offsets[-1]) != batch.count:
+        raise ValueError(f"merkle_roots_packed_forest: the counts add up to {int(offsets[-1])}, not to the {batch.count} strings")
+    if batch.count == 0:
+        return dev._forest_of_buffer(None, 0, counts, max_count, "merkle_roots_packed_forest")
+    d_data = dev.upload(batch.data if batch.words else np.zeros(1, np.uint32))
+    d_meta = dev.upload(batch.meta)
+    d_leaves = dev.alloc(32 * batch.count)
+    dev.map_async(d_data, batch.words, d_meta, batch.count, d_leaves)
+    try:
+        return dev._forest_of_buffer(d_leaves, batch.count, counts, max_count, "merkle_roots_packed_forest")
+    finally:
+        for b in (d_data, d_meta, d_leaves):
+            b.free()
 
 
 def digest_hex(words):
