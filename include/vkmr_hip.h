@@ -375,6 +375,61 @@ VKMR_API vkmr_status vkmr_hip_reduce_forest_async(int dev, vkmr_stream s, const 
                                                   void* scratch_dev, vkmr_digest* roots_dev, uint32_t* status_dev);
 
 /*
+ * STORED FOREST: vkmr_hip_reduce_forest_async with every level kept in HBM, so that the forest can hand out proofs.  Same
+ * contract, same device-side checks and same launches (the status word zeroed, the check, one launch per level); there is
+ * no scratch argument.  With H = max(1, ceil(log2 min(max_count, total))) levels and cells(l) = (total >> l) + ntrees:
+ * level 0 is digests_dev itself (not copied); level l = 1..H has a buffer of cells(l) cells that starts at cell
+ * sum over 1 <= j < l of cells(j) of forest_dev, and node j of tree t's level l is cell (offsets[t] >> l) + t + j of it, for
+ * l < h_t.  Level h_t of tree t is its root and goes to roots_dev[t] as in vkmr_hip_reduce_forest_async (an empty tree: an
+ * all-zero cell).  Cells of a level buffer that are not a node of some tree at that level are unspecified; nothing reads
+ * them.  A nonzero status writes no root, and the forest is then not to be used.
+ *   forest_dev  vkmr_hip_forest_tree_bytes(total, ntrees, max_count) bytes of device memory, 16-byte aligned:
+ *               32 * sum over l = 1..H of cells(l); 0 for ntrees == 0 or max_count == 0.
+ * ntrees == 0 does nothing whatever the other arguments.
+ */
+VKMR_API size_t vkmr_hip_forest_tree_bytes(uint64_t total, uint32_t ntrees, uint64_t max_count);
+VKMR_API vkmr_status vkmr_hip_reduce_forest_tree_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t total,
+                                                       const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count,
+                                                       vkmr_digest* forest_dev, vkmr_digest* roots_dev, uint32_t* status_dev);
+
+/*
+ * PROOFS FROM THE STORED FOREST ("is leaf i in tree t?"): a gather, no hash.  digests_dev and forest_dev as written by
+ * vkmr_hip_reduce_forest_tree_async; the call TRUSTS that offsets_dev, total, ntrees and max_count are those of that build
+ * and that the build reported status 0 -- it checks no offset again and follows them into the forest.  Query q is leaf
+ * indices_dev[q] (its index inside its tree) of tree trees_dev[q]; both arrays live in DEVICE memory, in any order, repeats
+ * allowed.  With H as above, the stride of a forest's proofs:
+ *   heights_dev[q]           = h_t = max(1, ceil(log2 c_t))
+ *   siblings_dev[q * H + l]  for l < h_t: the cell vkmr_hip_tree_proofs_async gives for a tree built over tree t's leaves
+ *                            alone, L_t[l][p ^ 1] with p = index >> l, or L_t[l][p] where p ^ 1 >= n_l; all-zero for l >= h_t
+ * (k * H cells, indexed in 64 bits).  The host cannot check queries that live on the device: trees[q] >= ntrees or
+ * indices[q] >= c_t (so every query into an empty tree) gets height 0 and H all-zero cells, the rule of
+ * vkmr_hip_tree_proofs_async for a bad index.  k == 0 does nothing.
+ * vkmr_host_cpu_forest_proofs (libvkmr_host.so) applies the same rule on the CPU, for a sender without a GPU.
+ */
+VKMR_API vkmr_status vkmr_hip_forest_proofs_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev,
+                                                  const vkmr_digest* forest_dev, uint64_t total, const uint64_t* offsets_dev,
+                                                  uint32_t ntrees, uint64_t max_count, const uint32_t* trees_dev,
+                                                  const uint64_t* indices_dev, uint32_t k, vkmr_digest* siblings_dev,
+                                                  uint32_t* heights_dev);
+
+/*
+ * BATCH VERIFICATION OF FOREST PROOFS: vkmr_hip_verify_proofs_async for proofs of unequal height against the roots of a
+ * forest.  One lane per proof.  ok_dev[q] = 1 iff 1 <= heights_dev[q] <= stride, indices_dev[q] < 2^heights_dev[q],
+ * trees_dev[q] < ntrees, and leaves_dev[q] folded with siblings_dev[q * stride + l], l = 0..heights_dev[q]-1, as
+ * vkmr_host_cpu_fold_proof does equals roots_dev[trees_dev[q]]; else 0.  Cells at l >= heights_dev[q] are never read.
+ *   stride 1..63 (the H of vkmr_hip_forest_proofs_async, or any layout with at least the tallest proof's cells per proof);
+ *   roots_dev: ntrees cells; all buffers in device memory.
+ * The counts and the offsets of the forest are not arguments: a proof shows membership AT A POSITION of the tree whose root
+ * it names, not the number of leaves, as stated at vkmr_hip_verify_proofs_async.  A wavefront works until its tallest proof
+ * is folded.  k == 0 does nothing.
+ */
+VKMR_API vkmr_status vkmr_hip_verify_forest_proofs_async(int dev, vkmr_stream s, const vkmr_digest* leaves_dev,
+                                                         const uint32_t* trees_dev, const uint64_t* indices_dev,
+                                                         const vkmr_digest* siblings_dev, const uint32_t* heights_dev,
+                                                         uint32_t k, uint32_t stride, const vkmr_digest* roots_dev,
+                                                         uint32_t ntrees, uint32_t* ok_dev);
+
+/*
  * COMBINE: duplicate-last Merkle root over n >= 1 slice roots given in slice order, always
  * at least one level -- the rule of CpuSha256D::Root that the reference applies to the slice
  * roots on the CPU (CpuSha256DforReductions, src/vkmr/Reductions.cpp:56-69, :703-712).  Here

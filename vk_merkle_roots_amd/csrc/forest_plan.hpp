@@ -51,4 +51,19 @@ inline uint64_t scratch_cells(uint64_t total, uint32_t ntrees)
     return ntrees == 0 ? 0 : level_cells(total, ntrees, 1) + level_cells(total, ntrees, 2);
 }
 
+// ---- stored forest (vkmr_hip_reduce_forest_tree_async): the same positions, one buffer per level instead of two that
+// alternate.  Level l >= 1 keeps its level_cells(l) cells behind those of levels 1 .. l - 1; level 0 stays the caller's
+// leaves.  `levels` = launches(total, max_count) is also the stride of a forest's proofs.
+
+// First cell of level l's buffer inside the stored forest: the cells of levels 1 .. l - 1.
+inline uint64_t stored_level_base(uint64_t total, uint32_t ntrees, uint32_t l)
+{
+    uint64_t cells = 0;
+    for (uint32_t j = 1; j < l; ++j) cells += level_cells(total, ntrees, j);
+    return cells;
+}
+
+// Cells of the stored forest: levels 1 .. `levels`.
+inline uint64_t stored_cells(uint64_t total, uint32_t ntrees, uint32_t levels) { return stored_level_base(total, ntrees, levels + 1); }
+
 }  // namespace vkmr_forest

@@ -1,5 +1,6 @@
 // host_api.cpp -- C entry points over the host-side C++ for bindings and tests
 // (libvkmr_host.so): the "CPU" backend on packed batches and on slice roots.
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <vector>
@@ -133,6 +134,65 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_forest_roots(const vkmr
         uint32_t height = 1;
         while (((c - 1) >> height) != 0) ++height;
         if (vkmr_host_cpu_reduce(digests + offsets[t], c, height, &roots[t]) != 0) return -1;
+    }
+    return 0;
+}
+
+// Proofs from a forest on the CPU, by the rule of vkmr_hip_forest_proofs_async: query q is leaf indices[q] of tree trees[q]
+// (tree t: digests[offsets[t] .. offsets[t+1])); heights[q] = h_t = max(1, ceil(log2 c_t)) and siblings[q * stride + l] is
+// L_t[l][p ^ 1] with p = index >> l, or L_t[l][p] where p ^ 1 is past the level's end, for l < h_t and all-zero behind.  A
+// tree >= ntrees or an index >= c_t gets height 0 and `stride` zero cells.  Nonzero, and nothing written, when the offsets
+// decrease somewhere (1), when `stride` is below the largest h_t a query needs (2) or a pointer is missing (-1).  A tree's
+// levels are formed once, however many queries ask for it.  The proofs verify through vkmr_host_cpu_fold_proof.
+__attribute__((visibility("default"))) int vkmr_host_cpu_forest_proofs(const vkmr_digest* digests, const uint64_t* offsets, uint32_t ntrees,
+                                                                        const uint32_t* trees, const uint64_t* indices, uint32_t k, uint32_t stride,
+                                                                        vkmr_digest* siblings, uint32_t* heights)
+{
+    if (k == 0) return 0;
+    if (!trees || !indices || !heights || (!siblings && stride > 0) || (!offsets && ntrees > 0)) return -1;
+    for (uint32_t t = 0; t < ntrees; ++t)
+        if (offsets[t + 1] < offsets[t]) return 1;
+    if (ntrees > 0 && !digests && offsets[ntrees] > offsets[0]) return -1;
+    auto count_of = [&](uint32_t q) -> uint64_t {      // c_t of a query that names a leaf, else 0
+        if (trees[q] >= ntrees) return 0;
+        const uint64_t c = offsets[trees[q] + 1] - offsets[trees[q]];
+        return indices[q] < c ? c : 0;
+    };
+    auto height_of = [](uint64_t c) {
+        uint32_t h = 1;
+        while (((c - 1) >> h) != 0) ++h;
+        return h;
+    };
+    std::vector<uint32_t> order;                       // the queries that name a leaf, by tree
+    for (uint32_t q = 0; q < k; ++q) {
+        const uint64_t c = count_of(q);
+        if (c == 0) continue;
+        if (height_of(c) > stride) return 2;
+        order.push_back(q);
+    }
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return trees[x] < trees[y]; });
+    std::memset(heights, 0, sizeof(uint32_t) * (size_t)k);
+    if (stride > 0) std::memset(siblings, 0, sizeof(vkmr_digest) * (size_t)k * stride);
+    std::vector<std::vector<vkmr_digest>> levels;      // levels[l] of the tree the queries at hand ask for, l < h_t
+    for (size_t i = 0; i < order.size(); ++i) {
+        const uint32_t q = order[i], t = trees[q];
+        const uint64_t c = offsets[t + 1] - offsets[t];
+        const uint32_t h = height_of(c);
+        if (i == 0 || trees[order[i - 1]] != t) {
+            levels.assign(h, {});
+            levels[0].assign(digests + offsets[t], digests + offsets[t + 1]);
+            for (uint32_t l = 1; l < h; ++l) {
+                const std::vector<vkmr_digest>& in = levels[l - 1];
+                levels[l].resize((in.size() + 1) / 2);
+                for (size_t j = 0; j < levels[l].size(); ++j)
+                    vkmr::cpu_sha256d_pair(in[2 * j].data, in[2 * j + 1 < in.size() ? 2 * j + 1 : 2 * j].data, levels[l][j].data);
+            }
+        }
+        heights[q] = h;
+        for (uint32_t l = 0; l < h; ++l) {
+            const uint64_t p = indices[q] >> l;
+            siblings[(size_t)q * stride + l] = levels[l][(p ^ 1ull) < levels[l].size() ? (p ^ 1ull) : p];
+        }
     }
     return 0;
 }

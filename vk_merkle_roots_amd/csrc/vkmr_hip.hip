@@ -11,7 +11,9 @@
 //                       multiproof_*_kernel, tree_multiproof_gather_kernel, verify_multiproof_*_kernel   one proof for k leaves:
 //                                              rank the nodes to emit, gather them; fold leaves and nodes level by level
 //   forest_kernels.hpp  forest_check_kernel, forest_level_kernel   roots of many trees of unequal size: one lane per node of the
-//                                              whole forest, level by level (no reference counterpart)
+//                                              whole forest, level by level (no reference counterpart); builds the stored forest
+//   forest_tree_kernels.hpp  forest_proofs_kernel          proofs gathered from the stored forest, one lane per (query, level)
+//                            verify_forest_proofs_kernel   batch verification of proofs of unequal height, one lane per proof
 //   sha256d_device.hpp  the SHA-256 round / compression building blocks
 //   meta_kernels.hpp    sizes_*_kernel         metadata entries from 16-bit sizes   (Batches.cpp:64-121)
 //
@@ -40,6 +42,7 @@ using vkmr_dev::Node;
 #include "reduce_plan.hpp"
 #include "tree_kernels.hpp"
 #include "forest_kernels.hpp"
+#include "forest_tree_kernels.hpp"
 
 // ============================================================================
 // C ABI
@@ -989,21 +992,27 @@ size_t vkmr_hip_forest_scratch_bytes(uint64_t total, uint32_t ntrees)
     return (size_t)vkmr_forest::scratch_cells(total, ntrees) * sizeof(vkmr_digest);
 }
 
-vkmr_status vkmr_hip_reduce_forest_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t total, const uint64_t* offsets_dev,
-                                         uint32_t ntrees, uint64_t max_count, void* scratch_dev, vkmr_digest* roots_dev, uint32_t* status_dev)
+// The launches of both forest builds: the status word zeroed, the check, then level l from level l - 1 for l = 1 .. levels.
+// level(l) is where level l >= 1 is kept: one of two alternating buffers (the roots alone are wanted) or a buffer of its own
+// (the stored forest).
+extern "C++" {   // a template inside the C block
+template <class LevelBuffer>
+static vkmr_status forest_launch(const char* who, int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t total, const uint64_t* offsets_dev,
+                                 uint32_t ntrees, uint64_t max_count, const void* buffer_dev, vkmr_digest* roots_dev, uint32_t* status_dev,
+                                 LevelBuffer level)
 {
-    if (ntrees == 0) return VKMR_OK;
-    if ((!digests_dev && total > 0) || !offsets_dev || !scratch_dev || !roots_dev || !status_dev)
-        return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_forest_async: null pointer");
-    if (max_count == 0) return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_forest_async: max_count must be at least 1");
-    if (reinterpret_cast<uintptr_t>(scratch_dev) & 15u) return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_forest_async: scratch must be 16-byte aligned");
-    if (total > (1ull << 58)) return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_forest_async: forest too large");
+    auto refuse = [who](const char* why) {
+        char what[128];
+        snprintf(what, sizeof what, "%s: %s", who, why);
+        return fail(VKMR_ERR_INVALID, what);
+    };
+    if ((!digests_dev && total > 0) || !offsets_dev || !buffer_dev || !roots_dev || !status_dev) return refuse("null pointer");
+    if (max_count == 0) return refuse("max_count must be at least 1");
+    if (reinterpret_cast<uintptr_t>(buffer_dev) & 15u) return refuse("the level buffer must be 16-byte aligned");
+    if (total > (1ull << 58) || (vkmr_forest::level_cells(total, ntrees, 1) + 255) / 256 > 0x7fffffffull) return refuse("forest too large");
     if (max_count > total) max_count = total;
     const uint32_t levels = vkmr_forest::launches(total, max_count);
-    if ((vkmr_forest::level_cells(total, ntrees, 1) + 255) / 256 > 0x7fffffffull)
-        return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_forest_async: forest too large");
     const Node* digests = reinterpret_cast<const Node*>(digests_dev);
-    Node* scratch = reinterpret_cast<Node*>(scratch_dev);
     Node* roots = reinterpret_cast<Node*>(roots_dev);
     VKMR_TRY(hipSetDevice(dev));
     VKMR_TRY(hipMemsetAsync(status_dev, 0, sizeof(uint32_t), S(s)));
@@ -1011,12 +1020,79 @@ vkmr_status vkmr_hip_reduce_forest_async(int dev, vkmr_stream s, const vkmr_dige
                        status_dev);
     VKMR_TRY(hipGetLastError());
     for (uint32_t l = 1; l <= levels; ++l) {   // level l from level l - 1, which the previous launch finished
-        const Node* in = (l == 1) ? digests : scratch + vkmr_forest::level_base(total, ntrees, l - 1);
+        const Node* in = (l == 1) ? digests : level(l - 1);
         const uint64_t cells = vkmr_forest::level_cells(total, ntrees, l);
-        hipLaunchKernelGGL(forest_level_kernel, dim3((uint32_t)((cells + 255) / 256)), dim3(256), 0, S(s), in, offsets_dev, ntrees, l, cells,
-                           scratch + vkmr_forest::level_base(total, ntrees, l), roots, (const uint32_t*)status_dev);
+        hipLaunchKernelGGL(forest_level_kernel, dim3((uint32_t)((cells + 255) / 256)), dim3(256), 0, S(s), in, offsets_dev, ntrees, l, cells, level(l),
+                           roots, (const uint32_t*)status_dev);
         VKMR_TRY(hipGetLastError());
     }
+    return VKMR_OK;
+}
+}  // extern "C++"
+
+vkmr_status vkmr_hip_reduce_forest_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t total, const uint64_t* offsets_dev,
+                                         uint32_t ntrees, uint64_t max_count, void* scratch_dev, vkmr_digest* roots_dev, uint32_t* status_dev)
+{
+    if (ntrees == 0) return VKMR_OK;
+    Node* scratch = reinterpret_cast<Node*>(scratch_dev);
+    return forest_launch("vkmr_hip_reduce_forest_async", dev, s, digests_dev, total, offsets_dev, ntrees, max_count, scratch_dev, roots_dev, status_dev,
+                         [&](uint32_t l) { return scratch + vkmr_forest::level_base(total, ntrees, l); });
+}
+
+// ---- stored forest: every level kept, proofs gathered from it, proofs of unequal height verified (forest_tree_kernels.hpp) ----
+
+size_t vkmr_hip_forest_tree_bytes(uint64_t total, uint32_t ntrees, uint64_t max_count)
+{
+    if (ntrees == 0 || max_count == 0) return 0;
+    return (size_t)vkmr_forest::stored_cells(total, ntrees, vkmr_forest::launches(total, max_count)) * sizeof(vkmr_digest);
+}
+
+vkmr_status vkmr_hip_reduce_forest_tree_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t total, const uint64_t* offsets_dev,
+                                              uint32_t ntrees, uint64_t max_count, vkmr_digest* forest_dev, vkmr_digest* roots_dev,
+                                              uint32_t* status_dev)
+{
+    if (ntrees == 0) return VKMR_OK;
+    Node* forest = reinterpret_cast<Node*>(forest_dev);
+    return forest_launch("vkmr_hip_reduce_forest_tree_async", dev, s, digests_dev, total, offsets_dev, ntrees, max_count, forest_dev, roots_dev,
+                         status_dev, [&](uint32_t l) { return forest + vkmr_forest::stored_level_base(total, ntrees, l); });
+}
+
+vkmr_status vkmr_hip_forest_proofs_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* forest_dev, uint64_t total,
+                                         const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count, const uint32_t* trees_dev,
+                                         const uint64_t* indices_dev, uint32_t k, vkmr_digest* siblings_dev, uint32_t* heights_dev)
+{
+    if (k == 0) return VKMR_OK;
+    if ((!digests_dev && total > 0) || !forest_dev || !offsets_dev || !trees_dev || !indices_dev || !siblings_dev || !heights_dev)
+        return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_proofs_async: null pointer");
+    if (max_count == 0) return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_proofs_async: max_count must be at least 1");
+    if (total > (1ull << 58)) return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_proofs_async: forest too large");
+    const uint32_t H = vkmr_forest::launches(total, max_count);   // <= 58
+    ForestLevels lv;
+    for (uint32_t l = 0; l < VKMR_TREE_MAX_LEVELS; ++l) lv.base[l] = (l >= 1 && l <= H) ? vkmr_forest::stored_level_base(total, ntrees, l) : 0;
+    const uint64_t cells = (uint64_t)k * H;
+    const uint64_t grid = (cells + 255) / 256;
+    if (grid > 0x7fffffffull) return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_proofs_async: too many proofs in one call");
+    VKMR_TRY(hipSetDevice(dev));
+    hipLaunchKernelGGL(forest_proofs_kernel, dim3((uint32_t)grid), dim3(256), 0, S(s), reinterpret_cast<const Node*>(digests_dev),
+                       reinterpret_cast<const Node*>(forest_dev), lv, offsets_dev, ntrees, H, trees_dev, indices_dev, cells,
+                       reinterpret_cast<Node*>(siblings_dev), heights_dev);
+    VKMR_TRY(hipGetLastError());
+    return VKMR_OK;
+}
+
+vkmr_status vkmr_hip_verify_forest_proofs_async(int dev, vkmr_stream s, const vkmr_digest* leaves_dev, const uint32_t* trees_dev,
+                                                const uint64_t* indices_dev, const vkmr_digest* siblings_dev, const uint32_t* heights_dev,
+                                                uint32_t k, uint32_t stride, const vkmr_digest* roots_dev, uint32_t ntrees, uint32_t* ok_dev)
+{
+    if (k == 0) return VKMR_OK;
+    if (!leaves_dev || !trees_dev || !indices_dev || !siblings_dev || !heights_dev || !roots_dev || !ok_dev)
+        return fail(VKMR_ERR_INVALID, "vkmr_hip_verify_forest_proofs_async: null pointer");
+    if (stride == 0 || stride > 63) return fail(VKMR_ERR_INVALID, "vkmr_hip_verify_forest_proofs_async: stride must be 1..63");
+    VKMR_TRY(hipSetDevice(dev));
+    const uint32_t grid = (uint32_t)(((uint64_t)k + 255) / 256);
+    hipLaunchKernelGGL(verify_forest_proofs_kernel, dim3(grid), dim3(256), 0, S(s), reinterpret_cast<const Node*>(leaves_dev), trees_dev, indices_dev,
+                       reinterpret_cast<const Node*>(siblings_dev), heights_dev, k, stride, reinterpret_cast<const Node*>(roots_dev), ntrees, ok_dev);
+    VKMR_TRY(hipGetLastError());
     return VKMR_OK;
 }
 

@@ -360,6 +360,89 @@ class HipDevice:
             if d_in:
                 d_in.free()
 
+    # -- stored forest: every level kept, proofs gathered from it, proofs of unequal height verified --
+    def forest_tree_bytes(self, total, ntrees, max_count):
+        return self.lib.vkmr_hip_forest_tree_bytes(total, ntrees, max_count)
+
+    def reduce_forest_tree_async(self, digests_buf, total, offsets_buf, ntrees, max_count, forest_buf, roots_buf, status_buf, stream=None):
+        check(self.lib.vkmr_hip_reduce_forest_tree_async(self.index, stream or self.stream, digests_buf.ptr if digests_buf else None, total,
+                                                         offsets_buf.ptr if offsets_buf else None, ntrees, max_count,
+                                                         forest_buf.ptr if forest_buf else None, roots_buf.ptr if roots_buf else None,
+                                                         status_buf.ptr if status_buf else None), "vkmr_hip_reduce_forest_tree_async")
+
+    def forest_proofs_async(self, digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, trees_buf, indices_buf, k, siblings_buf,
+                            heights_buf, stream=None):
+        check(self.lib.vkmr_hip_forest_proofs_async(self.index, stream or self.stream, digests_buf.ptr if digests_buf else None, forest_buf.ptr,
+                                                    total, offsets_buf.ptr, ntrees, max_count, trees_buf.ptr, indices_buf.ptr, k, siblings_buf.ptr,
+                                                    heights_buf.ptr), "vkmr_hip_forest_proofs_async")
+
+    def verify_forest_proofs_async(self, leaves_buf, trees_buf, indices_buf, siblings_buf, heights_buf, k, stride, roots_buf, ntrees, ok_buf,
+                                   stream=None):
+        check(self.lib.vkmr_hip_verify_forest_proofs_async(self.index, stream or self.stream, leaves_buf.ptr, trees_buf.ptr, indices_buf.ptr,
+                                                           siblings_buf.ptr, heights_buf.ptr, k, stride, roots_buf.ptr, ntrees, ok_buf.ptr),
+              "vkmr_hip_verify_forest_proofs_async")
+
+    def _build_forest_of_buffer(self, d_leaves, total, counts, max_count, what, owned=()):
+        """A MerkleForest of the trees of `counts` leaves each over the `total` cells of d_leaves (its level 0)."""
+        offsets, ntrees = forest_offsets(counts)
+        if int(offsets[-1]) != total:
+            raise ValueError(f"{what}: the counts add up to {int(offsets[-1])}, not to the {total} leaves")
+        if ntrees == 0:
+            raise ValueError(f"{what}: no tree")
+        if max_count is None:
+            max_count = max(1, int(np.diff(offsets).max()))
+        d_off = self.upload(offsets)
+        d_forest = self.alloc(self.forest_tree_bytes(total, ntrees, max_count))
+        d_roots, d_status = self.alloc(32 * ntrees), self.alloc(4)
+        self.reduce_forest_tree_async(d_leaves, total, d_off, ntrees, max_count, d_forest, d_roots, d_status)
+        status = int(self.download(d_status, 4)[0])
+        d_status.free()
+        if status:
+            for b in (d_off, d_forest, d_roots):
+                b.free()
+            raise ValueError(f"{what}: the device refused the forest (status {status}: {forest_status_text(status)})")
+        return MerkleForest(self, d_leaves, total, np.diff(offsets), d_off, max_count, d_forest, d_roots, owned=owned)
+
+    def build_forest(self, digests, counts, max_count=None):
+        """Every level of every tree of a forest, kept on the device: a MerkleForest (vkmr_hip_reduce_forest_tree_async).
+        `digests` [total, 8] (a host array) holds the leaves of all trees back to back, tree t the next counts[t] of them;
+        max_count: an upper bound on every count (the largest count when None).  ValueError when the counts do not add up to
+        the leaves, for no tree at all, or when the device refuses the forest (a count above max_count)."""
+        digests = np.ascontiguousarray(digests, dtype=np.uint32).reshape(-1, 8)
+        total = int(digests.shape[0])
+        d_in = self.upload(digests) if total else None
+        try:
+            return self._build_forest_of_buffer(d_in, total, counts, max_count, "build_forest", owned=[d_in] if d_in else [])
+        except Exception:
+            if d_in:
+                d_in.free()
+            raise
+
+    def verify_forest_proofs(self, leaves, trees, indices, siblings, heights, roots):
+        """bool [k]: proof q (leaf [8], tree, index, siblings [stride, 8] of which the first heights[q] count) folds to
+        roots[trees[q]] (roots [ntrees, 8]), with 1 <= heights[q] <= stride, its index below 2^heights[q] and its tree below
+        ntrees (vkmr_hip_verify_forest_proofs_async).  Host arrays in, verified on the device."""
+        leaves = np.ascontiguousarray(leaves, dtype=np.uint32).reshape(-1, 8)
+        trees = np.ascontiguousarray(trees, dtype=np.uint32).reshape(-1)
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        heights = np.ascontiguousarray(heights, dtype=np.uint32).reshape(-1)
+        k = int(idx.shape[0])
+        siblings = np.ascontiguousarray(siblings, dtype=np.uint32).reshape(k, -1, 8)
+        roots = np.ascontiguousarray(roots, dtype=np.uint32).reshape(-1, 8)
+        if leaves.shape[0] != k or trees.shape[0] != k or heights.shape[0] != k:
+            raise ValueError("verify_forest_proofs: one leaf, one tree and one height per index")
+        if k == 0:
+            return np.zeros(0, dtype=bool)
+        if roots.shape[0] == 0:
+            raise ValueError("verify_forest_proofs: no root")
+        bufs = [self.upload(a) for a in (leaves, trees, idx, siblings, heights, roots)]
+        d_ok = self.alloc(4 * k)
+        self.verify_forest_proofs_async(bufs[0], bufs[1], bufs[2], bufs[3], bufs[4], k, siblings.shape[1], bufs[5], roots.shape[0], d_ok)
+        ok = self.download(d_ok, 4 * k)
+        for b in bufs + [d_ok]:
+            b.free()
+        return ok == 1
+
     def reduce_scratch(self, count, levels_variant=False):
         fn = self.lib.vkmr_hip_reduce_levels_scratch_bytes if levels_variant else self.lib.vkmr_hip_reduce_scratch_bytes
         return self.alloc(fn(count))
@@ -578,6 +661,78 @@ class MerkleTree:
         for b in self._owned:
             b.free()
         self._owned = []
+
+
+class MerkleForest:
+    """Every level of every tree of a forest, resident on the device (vkmr_hip_reduce_forest_tree_async): level 0 is the
+    leaves buffer it was built from, levels 1..`levels` one buffer laid out as include/vkmr_hip.h describes, the roots a
+    buffer of their own.  `levels` is also the stride of its proofs."""
+
+    def __init__(self, dev, digests_buf, total, counts, offsets_buf, max_count, forest_buf, roots_buf, owned=()):
+        self.dev, self.digests, self.total, self.offsets, self.max_count = dev, digests_buf, int(total), offsets_buf, int(max_count)
+        self.counts = np.asarray(counts, dtype=np.uint64)
+        self.ntrees = int(self.counts.shape[0])
+        self.levels = tree_height(min(self.max_count, self.total)) if self.total else 1
+        self.forest, self.roots_buf = forest_buf, roots_buf
+        self._owned = list(owned)
+
+    def roots(self):
+        """[ntrees, 8] uint32: what forest_roots gives for the same leaves (an all-zero root for an empty tree)."""
+        return self.dev.download(self.roots_buf, 32 * self.ntrees).reshape(self.ntrees, 8)
+
+    def proofs_async(self, trees_buf, indices_buf, k, siblings_buf, heights_buf, stream=None):
+        """Proofs of k (tree, index) queries in device memory, written to siblings_buf [k, levels] and heights_buf [k]."""
+        self.dev.forest_proofs_async(self.digests, self.forest, self.total, self.offsets, self.ntrees, self.max_count, trees_buf, indices_buf, k,
+                                     siblings_buf, heights_buf, stream=stream)
+
+    def proofs(self, trees, indices):
+        """(siblings [k, levels, 8] uint32, heights [k] uint32) of leaves `indices` of trees `trees` (host arrays): the
+        first heights[q] cells of proof q count, the rest are zero; a tree >= ntrees or an index >= its tree's count gets
+        height 0 and zero cells."""
+        trees = np.ascontiguousarray(trees, dtype=np.uint32).reshape(-1)
+        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        k = int(idx.shape[0])
+        if trees.shape[0] != k:
+            raise ValueError("proofs: one tree per index")
+        if k == 0:
+            return np.zeros((0, self.levels, 8), dtype=np.uint32), np.zeros(0, dtype=np.uint32)
+        d_trees, d_idx = self.dev.upload(trees), self.dev.upload(idx)
+        d_sib, d_h = self.dev.alloc(32 * k * self.levels), self.dev.alloc(4 * k)
+        self.proofs_async(d_trees, d_idx, k, d_sib, d_h)
+        sib = self.dev.download(d_sib, 32 * k * self.levels).reshape(k, self.levels, 8)
+        heights = self.dev.download(d_h, 4 * k)
+        for b in (d_trees, d_idx, d_sib, d_h):
+            b.free()
+        return sib, heights
+
+    def free(self):
+        for b in [self.forest, self.roots_buf, self.offsets] + self._owned:
+            if b:
+                b.free()
+        self.forest = self.roots_buf = self.offsets = None
+        self._owned = []
+
+
+def merkle_forest_packed(dev, batch, counts, max_count=None):
+    """The strings of `batch` mapped to leaf digests ONCE and the stored forest built over them, tree t over the next
+    counts[t] of them, all on the device (a MerkleForest that owns its leaves)."""
+    offsets, _ = forest_offsets(counts)
+    if int(offsets[-1]) != batch.count:
+        raise ValueError(f"merkle_forest_packed: the counts add up to {int(offsets[-1])}, not to the {batch.count} strings")
+    if batch.count == 0:
+        return dev._build_forest_of_buffer(None, 0, counts, max_count, "merkle_forest_packed")
+    d_data = dev.upload(batch.data if batch.words else np.zeros(1, np.uint32))
+    d_meta = dev.upload(batch.meta)
+    d_leaves = dev.alloc(32 * batch.count)
+    dev.map_async(d_data, batch.words, d_meta, batch.count, d_leaves)
+    try:
+        return dev._build_forest_of_buffer(d_leaves, batch.count, counts, max_count, "merkle_forest_packed", owned=[d_leaves])
+    except Exception:
+        d_leaves.free()
+        raise
+    finally:                    # the build has read its status back: the map is done
+        d_data.free()
+        d_meta.free()
 
 
 def merkle_tree_packed(dev, batch, height=None):
