@@ -4,11 +4,11 @@ the GPU tests (tests/test_gpu_forest.py), and the helpers both use.  A plain mod
 A case is a list of tree sizes; the leaves of all trees lie back to back from cell 0."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import merkle_model
+from merkle_model import ROOT  # noqa: F401
 
 
 def _edges():
@@ -69,23 +69,13 @@ def host_cpu_roots(leaves, offsets):
 
 def build_plan_exe(directory):
     """tests/c/forest_plan_test.cpp compiled into `directory`; its path."""
-    exe = os.path.join(str(directory), "forest_plan_test")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "vk_merkle_roots_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "c", "forest_plan_test.cpp"), "-o", exe])
-    return exe
+    return merkle_model.build_plan_exe(directory, "forest_plan_test")
 
 
 def plan_replay(exe, directory, forests):
     """For each (first_offset, slack, max_count, counts): (launches, scratch cells written, scratch cells budgeted) as the plan
     header gives them; the C test has checked overlap, bounds and the last level on the way."""
-    path = os.path.join(str(directory), "forests.txt")
-    with open(path, "w") as f:
-        for first, slack, max_count, counts in forests:
-            f.write(" ".join(str(int(x)) for x in [first, slack, max_count] + list(counts)) + "\n")
-    r = subprocess.run([exe, path], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=300)
-    text = r.stdout.decode()
-    assert r.returncode == 0 and "FAIL" not in text and f"ok: {len(forests)} forests" in text, text[-2000:]
-    return [tuple(int(x) for x in line.split()) for line in text.splitlines()[: len(forests)]]
+    return merkle_model.forests_replay(exe, directory, forests, "forests.txt")
 
 
 def ceil_log2(n):

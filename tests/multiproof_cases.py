@@ -6,35 +6,11 @@ Tree: level l has n_l = ceil(count / 2^l) nodes, node j of level l + 1 = SHA-256
 also above the point where the count has collapsed to one.  A_0 = the proved indices, A_{l+1} = unique(A_l >> 1).  For
 l = 0 .. height - 1 and p in A_l ascending: nothing when p ^ 1 is in A_l, else ONE node, L[l][p ^ 1], or L[l][p] where
 p ^ 1 >= n_l.  The verifier needs no count: which children are known follows from the indices alone."""
-import hashlib
-
 import numpy as np
 
+from merkle_model import cpu_levels, node, random_leaves, tree_height  # noqa: F401  (the tests reach them through this module)
+
 COUNTS = [1, 2, 3, 5, 8, 9, 127, 128, 129, 1000]
-
-
-def node(l, r):
-    """SHA-256d(l || r) of word-valued digests."""
-    b = np.concatenate([l, r]).astype(">u4").tobytes()
-    return np.frombuffer(hashlib.sha256(hashlib.sha256(b).digest()).digest(), dtype=">u4").astype(np.uint32)
-
-
-def tree_height(count):
-    return max(1, int(count - 1).bit_length())
-
-
-def cpu_levels(leaves, height):
-    """Every level of the tree over `leaves` ([count, 8] uint32)."""
-    levels = [np.asarray(leaves, dtype=np.uint32)]
-    for _ in range(height):
-        cur = levels[-1]
-        n = cur.shape[0]
-        levels.append(np.stack([node(cur[2 * p], cur[min(2 * p + 1, n - 1)]) for p in range((n + 1) // 2)]))
-    return levels
-
-
-def random_leaves(rng, n):
-    return rng.integers(0, 2**32, size=(n, 8), dtype=np.uint32)
 
 
 def emitted_positions(count, height, indices):

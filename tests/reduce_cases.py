@@ -13,21 +13,15 @@ from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def tree_height(count):
-    return max(1, int(count - 1).bit_length())
+import merkle_model
+from merkle_model import ROOT, tree_height  # noqa: F401
 
 
 # ---- the schedule, asked of the header ------------------------------------------------------------------------------
 
 def build_plan_exe(directory):
     """tests/c/reduce_plan_test.cpp compiled into `directory` (as tests/test_reduce_plan.py does); its path."""
-    exe = os.path.join(str(directory), "reduce_plan_test")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-Wall", "-I", os.path.join(ROOT, "vk_merkle_roots_amd", "csrc"),
-                           os.path.join(ROOT, "tests", "c", "reduce_plan_test.cpp"), "-o", exe])
-    return exe
+    return merkle_model.build_plan_exe(directory, "reduce_plan_test")
 
 
 def schedules(exe, triples):

@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import forest_cases as fc
+from merkle_model import random_counts
 
 pytestmark = pytest.mark.gpu
 
@@ -78,25 +79,6 @@ def test_equal_trees_match_reduce_slices_and_a_ragged_last_tree(gpu, k):
     assert (roots[-1] == gpu.reduce_digests(leaves[(nslices - 1) * cap:])).all()
     for b in (d_leaves, d_scr, d_roots):
         b.free()
-
-
-def random_counts(rng, budget):
-    """Tree sizes of one random forest of at most `budget` leaves: a mix of shapes, empty trees included."""
-    ntrees = int(rng.integers(1, 33))
-    kind = int(rng.integers(0, 4))
-    if kind == 0:
-        counts = rng.integers(0, 20, size=ntrees)
-    elif kind == 1:
-        counts = rng.integers(1, 5000, size=ntrees)
-    elif kind == 2:
-        counts = (1 << rng.integers(0, 15, size=ntrees)) + rng.integers(-1, 2, size=ntrees)
-    else:
-        counts = rng.integers(1, 200, size=ntrees)
-        counts[int(rng.integers(0, ntrees))] = int(rng.integers(1, budget // 2))
-    counts = [int(c) for c in counts]
-    while sum(counts) > budget:
-        counts.pop()
-    return counts
 
 
 @pytest.mark.parametrize("seed", range(50))

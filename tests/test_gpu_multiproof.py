@@ -5,16 +5,10 @@ import numpy as np
 import pytest
 
 import multiproof_cases as mc
+from merkle_model import At
 from test_gpu_tree_proofs import proof_indices
 
 pytestmark = pytest.mark.gpu
-
-
-class At:
-    """A device pointer inside another buffer, for the wrappers that read `.ptr`."""
-
-    def __init__(self, buf, offset):
-        self.ptr = buf.at(offset)
 
 
 def index_sets(count, rng):

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import reduce_cases as rc
+from merkle_model import sibling_index
 from test_gpu_parity import _guarded_scratch
 from test_gpu_tree_proofs import cpu_fold, cpu_levels
 
@@ -159,8 +160,7 @@ def test_proofs_written_in_the_pass_at_ragged_edges(gpu, big, plan_exe, m):
         assert len(edge) >= 3      # n - 1, n - 2 and the walk's first leaf at the least
         for q, index in edge:
             for l in range(m + 1):
-                p = index >> l
-                s = p ^ 1 if (p ^ 1) < -(-n >> l) else p
+                s = sibling_index(index >> l, -(-n >> l))
                 assert (sib[q][l] == levels[l][s - (w0 >> l)]).all(), what + (index, l)
 
 

@@ -1,7 +1,6 @@
 """Stored trees on the GPU: every level (vkmr_hip_reduce_tree_async), proofs gathered from it for any number of leaves
 (vkmr_hip_tree_proofs_async) and their batch verification (vkmr_hip_verify_proofs_async), against hashlib, the other
 proof entry points, vkmr_host_cpu_fold_proof, the golden roots and the proofs the `vkmr` front end prints."""
-import hashlib
 import json
 import os
 
@@ -9,41 +8,14 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from merkle_model import cpu_levels, host_fold as cpu_fold, node, random_leaves  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-def node(l, r):
-    """SHA-256d(l || r) of word-valued digests, with hashlib."""
-    b = np.concatenate([l, r]).astype(">u4").tobytes()
-    return np.frombuffer(hashlib.sha256(hashlib.sha256(b).digest()).digest(), dtype=">u4").astype(np.uint32)
-
-
-def cpu_levels(leaves, height):
-    """Every level of the duplicate-last tree, the unpaired last node hashed with itself (also once it is alone)."""
-    levels = [np.asarray(leaves, dtype=np.uint32)]
-    for _ in range(height):
-        cur = levels[-1]
-        n = cur.shape[0]
-        levels.append(np.stack([node(cur[2 * p], cur[min(2 * p + 1, n - 1)]) for p in range((n + 1) // 2)]))
-    return levels
-
-
-def cpu_fold(leaf, index, siblings, height):
-    import vk_merkle_roots_amd as vk
-    out = np.zeros(8, dtype=np.uint32)
-    vk.host_lib().vkmr_host_cpu_fold_proof(np.ascontiguousarray(leaf, dtype=np.uint32).ctypes.data, int(index),
-                                           np.ascontiguousarray(siblings, dtype=np.uint32).ctypes.data, height, out.ctypes.data)
-    return out
 
 
 def cpu_verify(leaf, index, siblings, height, root):
     """The reference rule of vkmr_hip_verify_proofs_async: the fold of vkmr_host_cpu_fold_proof, and index < 2^height."""
     return int(index) < (1 << height) and bool((cpu_fold(leaf, index, siblings, height) == root).all())
-
-
-def random_leaves(rng, n):
-    return rng.integers(0, 2**32, size=(n, 8), dtype=np.uint32)
 
 
 @pytest.mark.parametrize("count", [1, 2, 3, 5, 8, 9, 127, 128, 129, 1000, 4097, 65537])

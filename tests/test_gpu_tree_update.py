@@ -1,32 +1,12 @@
 """Leaf updates of a stored tree on the GPU (vkmr_hip_tree_update_async, MerkleTree.update / update_async / update_packed):
 every level after an update against hashlib and a fresh build, the device-side index checks, and proofs gathered and verified
 on the same stream after an update."""
-import hashlib
-
 import numpy as np
 import pytest
 
+from merkle_model import At, cpu_levels, node, random_leaves  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-
-
-def node(l, r):
-    """SHA-256d(l || r) of word-valued digests, with hashlib."""
-    b = np.concatenate([l, r]).astype(">u4").tobytes()
-    return np.frombuffer(hashlib.sha256(hashlib.sha256(b).digest()).digest(), dtype=">u4").astype(np.uint32)
-
-
-def cpu_levels(leaves, height):
-    """Every level of the duplicate-last tree, the unpaired last node hashed with itself (also once it is alone)."""
-    levels = [np.asarray(leaves, dtype=np.uint32)]
-    for _ in range(height):
-        cur = levels[-1]
-        n = cur.shape[0]
-        levels.append(np.stack([node(cur[2 * p], cur[min(2 * p + 1, n - 1)]) for p in range((n + 1) // 2)]))
-    return levels
-
-
-def random_leaves(rng, n):
-    return rng.integers(0, 2**32, size=(n, 8), dtype=np.uint32)
 
 
 def all_levels(tree):
@@ -37,13 +17,6 @@ def assert_levels_equal(tree, want, what):
     for l in range(tree.height + 1):
         got = tree.level(l)
         assert got.shape == want[l].shape and (got == want[l]).all(), (what, l)
-
-
-class At:
-    """A device pointer inside another buffer, for the wrappers that read `.ptr`."""
-
-    def __init__(self, buf, offset):
-        self.ptr = buf.at(offset)
 
 
 def update_sets(count, rng):

@@ -73,10 +73,7 @@ __global__ __launch_bounds__(256) void forest_level_kernel(const Node* __restric
     // is its last, h_t, when it has one node
     const uint64_t n_in = vkmr_forest::level_count(c, l - 1u), n_out = vkmr_forest::level_count(c, l);
     if ((l > 1u && n_in == 1ull) || j >= n_out) return;   // the tree is done, or the padding behind its nodes
-    const Node* src = in + vkmr_forest::pos(o, t, l - 1u);
-    const Node a = vkmr_dev::load_node(src + 2 * j);
-    const Node b = vkmr_dev::load_node(src + ((2 * j + 1 < n_in) ? 2 * j + 1 : 2 * j));
     uint32_t x[8];
-    vkmr_dev::hash_pair(a.w, b.w, x);
+    vkmr_dev::hash_parent(in + vkmr_forest::pos(o, t, l - 1u), n_in, j, x);
     vkmr_dev::store_node(n_out == 1ull ? roots + t : out + p, x);
 }

@@ -13,19 +13,13 @@
 #pragma once
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define VKMR_FOREST_FN __host__ __device__ __forceinline__
-#else
-#define VKMR_FOREST_FN inline
-#endif
+#include "merkle_math.hpp"
+#define VKMR_FOREST_FN VKMR_MATH_FN
 
 namespace vkmr_forest {
 
-// Levels of the tree over c >= 1 leaves: max(1, ceil(log2 c)) -- a lone leaf is hashed with itself once (the single-slice
-// rule of vkmr_hip_reduce_async).
-VKMR_FOREST_FN uint32_t height(uint64_t c) { return c <= 2 ? 1u : 64u - (uint32_t)__builtin_clzll(c - 1); }
-
-// Nodes of level l of a tree over c leaves: ceil(c / 2^l), and 0 for an empty tree.
+// Levels of the tree over c >= 1 leaves, and the nodes of its level l (0 for an empty tree): merkle_math.hpp.
+using vkmr_math::height;
 VKMR_FOREST_FN uint64_t level_count(uint64_t c, uint32_t l) { return c == 0 ? 0 : ((c - 1) >> l) + 1; }
 
 // First cell of tree t's level l: in the caller's leaves for l == 0, in the level's own buffer otherwise.

@@ -40,7 +40,7 @@ __global__ __launch_bounds__(256) void forest_proofs_kernel(const Node* __restri
             if (l < h) {
                 const uint64_t n = vkmr_forest::level_count(c, l);
                 const uint64_t p = index >> l;
-                const uint64_t s = ((p ^ 1ull) < n) ? (p ^ 1ull) : p;
+                const uint64_t s = vkmr_math::sibling(p, n);
                 const Node* cell = (l == 0) ? digests + off + s : forest + lv.base[l] + vkmr_forest::pos(off, t, l) + s;
                 const Node v = vkmr_dev::load_node(cell);
 #pragma unroll

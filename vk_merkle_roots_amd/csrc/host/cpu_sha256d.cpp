@@ -3,6 +3,7 @@
 
 #include <cstring>
 
+#include "../merkle_math.hpp"
 #include "util.hpp"
 
 namespace vkmr {
@@ -105,10 +106,8 @@ void cpu_merkle_root_inplace(uint32_t* nodes, size_t n)
     do {
         const size_t pairs = (n + 1) / 2;
         for (size_t p = 0; p < pairs; ++p) {
-            const uint32_t* l = nodes + 16 * p;
-            const uint32_t* r = (2 * p + 1 < n) ? l + 8 : l;
             uint32_t h[8];
-            cpu_sha256d_pair(l, r, h);
+            cpu_sha256d_pair(nodes + 16 * p, nodes + 8 * vkmr_math::right_child(p, n), h);
             std::memcpy(nodes + 8 * p, h, 32);
         }
         n = pairs;

@@ -5,6 +5,7 @@
 #include <cstring>
 #include <vector>
 
+#include "../merkle_math.hpp"
 #include "cpu_sha256d.hpp"
 #include "vkmr_hip.h"
 
@@ -30,10 +31,8 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_reduce(const vkmr_diges
     for (uint32_t lv = 0; lv < height; ++lv) {
         const uint64_t pairs = (n + 1) / 2;
         for (uint64_t p = 0; p < pairs; ++p) {
-            const uint32_t* l = nodes.data() + 16 * p;
-            const uint32_t* r = (2 * p + 1 < n) ? l + 8 : l;
             uint32_t h[8];
-            vkmr::cpu_sha256d_pair(l, r, h);
+            vkmr::cpu_sha256d_pair(nodes.data() + 16 * p, nodes.data() + 8 * vkmr_math::right_child(p, n), h);
             std::memcpy(nodes.data() + 8 * p, h, 32);
         }
         n = pairs;
@@ -131,9 +130,7 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_forest_roots(const vkmr
             std::memset(roots[t].data, 0, 32);
             continue;
         }
-        uint32_t height = 1;
-        while (((c - 1) >> height) != 0) ++height;
-        if (vkmr_host_cpu_reduce(digests + offsets[t], c, height, &roots[t]) != 0) return -1;
+        if (vkmr_host_cpu_reduce(digests + offsets[t], c, vkmr_math::height(c), &roots[t]) != 0) return -1;
     }
     return 0;
 }
@@ -158,16 +155,11 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_forest_proofs(const vkm
         const uint64_t c = offsets[trees[q] + 1] - offsets[trees[q]];
         return indices[q] < c ? c : 0;
     };
-    auto height_of = [](uint64_t c) {
-        uint32_t h = 1;
-        while (((c - 1) >> h) != 0) ++h;
-        return h;
-    };
     std::vector<uint32_t> order;                       // the queries that name a leaf, by tree
     for (uint32_t q = 0; q < k; ++q) {
         const uint64_t c = count_of(q);
         if (c == 0) continue;
-        if (height_of(c) > stride) return 2;
+        if (vkmr_math::height(c) > stride) return 2;
         order.push_back(q);
     }
     std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return trees[x] < trees[y]; });
@@ -177,7 +169,7 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_forest_proofs(const vkm
     for (size_t i = 0; i < order.size(); ++i) {
         const uint32_t q = order[i], t = trees[q];
         const uint64_t c = offsets[t + 1] - offsets[t];
-        const uint32_t h = height_of(c);
+        const uint32_t h = vkmr_math::height(c);
         if (i == 0 || trees[order[i - 1]] != t) {
             levels.assign(h, {});
             levels[0].assign(digests + offsets[t], digests + offsets[t + 1]);
@@ -185,13 +177,12 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_forest_proofs(const vkm
                 const std::vector<vkmr_digest>& in = levels[l - 1];
                 levels[l].resize((in.size() + 1) / 2);
                 for (size_t j = 0; j < levels[l].size(); ++j)
-                    vkmr::cpu_sha256d_pair(in[2 * j].data, in[2 * j + 1 < in.size() ? 2 * j + 1 : 2 * j].data, levels[l][j].data);
+                    vkmr::cpu_sha256d_pair(in[2 * j].data, in[vkmr_math::right_child(j, in.size())].data, levels[l][j].data);
             }
         }
         heights[q] = h;
         for (uint32_t l = 0; l < h; ++l) {
-            const uint64_t p = indices[q] >> l;
-            siblings[(size_t)q * stride + l] = levels[l][(p ^ 1ull) < levels[l].size() ? (p ^ 1ull) : p];
+            siblings[(size_t)q * stride + l] = levels[l][vkmr_math::sibling(indices[q] >> l, levels[l].size())];
         }
     }
     return 0;

@@ -15,8 +15,6 @@ using vkmr_dev::Node;
 // REDUCE
 // ============================================================================
 
-__device__ __forceinline__ uint64_t level_count(uint64_t n, unsigned k) { return (n + ((1ull << k) - 1ull)) >> k; }
-
 // Each wave walks 2^m chunks of 128 consecutive nodes.  A chunk gives 64 level-1
 // nodes (one per lane).  Two such results of equal level merge into 64 nodes of
 // the next level: lanes 0..31 hash pairs of the earlier (pending) result, lanes
@@ -121,7 +119,7 @@ __device__ __forceinline__ void reduce_pass_body(const Node* __restrict__ in0, c
             const uint64_t first = base0 + 128ull * ((uint64_t)c + 1ull - (1ull << k));
             if (first < n_in) {   // wave-uniform: otherwise nothing below is a real node
                 const uint64_t j = (first >> (k + 1)) + lane;
-                const uint64_t ck = level_count(n_in, k);
+                const uint64_t ck = vkmr_math::ceil_shift(n_in, k);
                 uint32_t l[8], r[8];
                 if (k == 0) {
                     if (2 * j < ck) {
@@ -130,7 +128,7 @@ __device__ __forceinline__ void reduce_pass_body(const Node* __restrict__ in0, c
                         // load - wait - branch - load; by then the line has left L1 and often L2:
                         // 1.5x the algorithmic HBM reads, profiles/r02_reduce_fetch.txt.)  An odd count
                         // pairs the last node with itself: it is simply read twice.
-                        const uint64_t jb = (2 * j + 1 < ck) ? 2 * j + 1 : 2 * j;
+                        const uint64_t jb = vkmr_math::right_child(j, ck);
                         const Node a = vkmr_dev::load_node(in + 2 * j);
                         const Node b = vkmr_dev::load_node(in + jb);
 #pragma unroll
@@ -175,7 +173,7 @@ __device__ __forceinline__ void reduce_pass_body(const Node* __restrict__ in0, c
         }
     }
     const uint64_t jo = (base0 >> (m + 1)) + lane;
-    if (jo < level_count(n_in, m + 1)) vkmr_dev::store_node(out + jo, X);
+    if (jo < vkmr_math::ceil_shift(n_in, m + 1)) vkmr_dev::store_node(out + jo, X);
 #ifdef VKMR_STAMPS
     {
         unsigned long long t_end = __builtin_amdgcn_s_memtime();
@@ -215,7 +213,7 @@ __device__ __forceinline__ void shuffle_collapse(uint32_t (&X)[8], uint64_t idx0
                                                  uint32_t& done, uint32_t levels, uint32_t steps, const ProofArgs& pa, uint32_t level0, bool mine)
 {
     for (uint32_t t = 0; t < steps && done < levels; ++t) {
-        const uint64_t cnt = level_count(n_in, done);   // nodes alive at the current level
+        const uint64_t cnt = vkmr_math::ceil_shift(n_in, done);   // nodes alive at the current level
         const uint64_t me = idx0 >> t;                   // this lane's node index at that level
         uint32_t r[8];
 #pragma unroll
@@ -250,7 +248,7 @@ __device__ __forceinline__ void reduce_tail_body(const Node* __restrict__ in0, c
     }
     if (2 * lane < n_in) {
         const Node a = vkmr_dev::load_node(in + 2 * lane);
-        const Node b = vkmr_dev::load_node(in + ((2 * lane + 1 < n_in) ? 2 * lane + 1 : 2 * lane));
+        const Node b = vkmr_dev::load_node(in + ((2 * lane + 1 < n_in) ? 2 * lane + 1 : 2 * lane));   // right_child in 32 bits: one wavefront, n_in <= 128
         if (PROOFS && blockIdx.y == 0) note_siblings<PROOFS>(pa, level0, 0ull, 0u, lane, true, a.w, b.w);
         vkmr_dev::hash_pair(a.w, b.w, X);
     }
@@ -302,14 +300,14 @@ __device__ __forceinline__ void reduce_collapse_body(const Node* __restrict__ in
     uint32_t X[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (2 * j < n_in) {
         const Node a = vkmr_dev::load_node(in + 2 * j);
-        const Node b = vkmr_dev::load_node(in + ((2 * j + 1 < n_in) ? 2 * j + 1 : 2 * j));
+        const Node b = vkmr_dev::load_node(in + vkmr_math::right_child(j, n_in));
         if (PROOFS && mine) note_siblings<PROOFS>(pa, level0, j0, 0u, lane, true, a.w, b.w);
         vkmr_dev::hash_pair(a.w, b.w, X);
     }
     uint32_t done = 1;
     shuffle_collapse<PROOFS>(X, j, lane, n_in, done, levels, 6, pa, level0, mine);
     const uint64_t jo = j >> (levels - 1u);
-    if ((lane & ((1u << (levels - 1u)) - 1u)) == 0u && jo < level_count(n_in, levels)) vkmr_dev::store_node(out + jo, X);
+    if ((lane & ((1u << (levels - 1u)) - 1u)) == 0u && jo < vkmr_math::ceil_shift(n_in, levels)) vkmr_dev::store_node(out + jo, X);
 }
 
 __global__ __launch_bounds__(VKMR_COLLAPSE_WAVES * 64) void reduce_collapse_kernel(const Node* __restrict__ in0, SliceGeom geom, uint32_t levels,
@@ -334,7 +332,7 @@ __global__ __launch_bounds__(256) void reduce_level_kernel(const Node* __restric
     const uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (2 * p >= n_in) return;
     const Node a = vkmr_dev::load_node(in + 2 * p);
-    const Node b = vkmr_dev::load_node(in + ((2 * p + 1 < n_in) ? 2 * p + 1 : 2 * p));
+    const Node b = vkmr_dev::load_node(in + vkmr_math::right_child(p, n_in));
     uint32_t o[8];
     vkmr_dev::hash_pair(a.w, b.w, o);
     vkmr_dev::store_node(out + p, o);

@@ -8,6 +8,8 @@
 #pragma once
 #include <stdint.h>
 
+#include "merkle_math.hpp"
+
 #ifndef VKMR_PASS_WAVES
 #define VKMR_PASS_WAVES 4   // waves per workgroup in reduce_pass_kernel (2: 6 % slower, 8: the same -- profiles/r02_reduce_pass_shape.txt)
 #endif
@@ -26,7 +28,8 @@
 
 namespace vkmr_plan {
 
-inline uint64_t ceil_shift(uint64_t n, unsigned k) { return k >= 64 ? (n ? 1 : 0) : (n >> k) + ((n & ((1ull << k) - 1ull)) ? 1ull : 0ull); }
+// any k; n <= 2^63 as in merkle_math.hpp (above that the sum wraps: the result is too small, never 1 where the true value is not)
+inline uint64_t ceil_shift(uint64_t n, unsigned k) { return k >= 64 ? (n ? 1 : 0) : vkmr_math::ceil_shift(n, k); }
 
 // Levels a bulk pass collapses for n input nodes per slice: the largest m+1 (m <= MAXM)
 // that still leaves enough wavefronts (over all slices of the launch) to fill 256 CUs.

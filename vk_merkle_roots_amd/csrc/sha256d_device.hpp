@@ -18,6 +18,8 @@
 #include <stdint.h>
 #include <utility>
 
+#include "merkle_math.hpp"
+
 namespace vkmr_dev {
 
 struct Node { uint32_t w[8]; };   // word VALUES H[0..7] (VkSha256Result, SHA-256defs.h:47-49)
@@ -160,6 +162,24 @@ __device__ __forceinline__ void store_node(Node* p, const uint32_t (&h)[8])
     uint4* q = reinterpret_cast<uint4*>(p);
     q[0] = make_uint4(h[0], h[1], h[2], h[3]);
     q[1] = make_uint4(h[4], h[5], h[6], h[7]);
+}
+
+__device__ __forceinline__ void store_node(Node* p, const Node& n) { store_node(p, n.w); }
+
+// Parent j of a level of n cells (2 j < n): both loads issue back to back; right_child reads the last node twice at the ragged edge.
+__device__ __forceinline__ void hash_parent(const Node* level, uint64_t n, uint64_t j, uint32_t (&out)[8])
+{
+    const Node a = load_node(level + 2 * j), b = load_node(level + vkmr_math::right_child(j, n));
+    hash_pair(a.w, b.w, out);
+}
+
+// Zero when the two nodes are equal.
+__device__ __forceinline__ uint32_t node_diff(const Node& a, const Node& b)
+{
+    uint32_t diff = 0u;
+#pragma unroll
+    for (int w = 0; w < 8; ++w) diff |= a.w[w] ^ b.w[w];
+    return diff;
 }
 
 }  // namespace vkmr_dev

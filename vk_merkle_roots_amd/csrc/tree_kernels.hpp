@@ -26,8 +26,7 @@ __global__ __launch_bounds__(256) void tree_proofs_kernel(const Node* __restrict
     uint32_t o[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (index < count) {
         const uint64_t n = ((count - 1) >> l) + 1;     // cells of level l
-        const uint64_t p = index >> l;
-        const uint64_t s = ((p ^ 1ull) < n) ? (p ^ 1ull) : p;
+        const uint64_t s = vkmr_math::sibling(index >> l, n);
         const Node* cell = (l == 0) ? digests + s : tree + lv.off[l] + s;
         const Node v = vkmr_dev::load_node(cell);
 #pragma unroll
@@ -93,11 +92,7 @@ __global__ __launch_bounds__(256) void tree_update_leaves_kernel(Node* __restric
 {
     const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (q >= k || *status != 0u) return;
-    const Node v = vkmr_dev::load_node(leaves + q);
-    uint32_t o[8];
-#pragma unroll
-    for (int w = 0; w < 8; ++w) o[w] = v.w[w];
-    vkmr_dev::store_node(digests + indices[q], o);
+    vkmr_dev::store_node(digests + indices[q], vkmr_dev::load_node(leaves + q));
 }
 
 // One level l >= 1 per launch: in = level l - 1 (n_in cells), out = level l.  Lane q hashes parent p = index_q >> l when it
@@ -112,10 +107,8 @@ __global__ __launch_bounds__(256) void tree_update_level_kernel(const Node* __re
     if (q >= k || *status != 0u) return;
     const uint64_t p = indices[q] >> l;
     if (q > 0 && (indices[q - 1] >> l) == p) return;
-    const Node a = vkmr_dev::load_node(in + 2 * p);
-    const Node b = vkmr_dev::load_node(in + ((2 * p + 1 < n_in) ? 2 * p + 1 : 2 * p));
     uint32_t o[8];
-    vkmr_dev::hash_pair(a.w, b.w, o);
+    vkmr_dev::hash_parent(in, n_in, p, o);
     vkmr_dev::store_node(out + p, o);
 }
 
@@ -235,8 +228,7 @@ __global__ __launch_bounds__(256) void tree_multiproof_gather_kernel(const Node*
     if (!(m & bit)) return;
     const uint64_t rank = word_start[at] + (uint64_t)__popcll(m & (bit - 1ull));   // < M <= the buffer's capacity: the status is 0
     const uint64_t n = ((count - 1) >> l) + 1;     // cells of level l; the check ran: index < count, so p < n
-    const uint64_t p = indices[q] >> l;
-    const uint64_t s = ((p ^ 1ull) < n) ? (p ^ 1ull) : p;
+    const uint64_t s = vkmr_math::sibling(indices[q] >> l, n);
     const Node v = vkmr_dev::load_node((l == 0) ? digests + s : tree + lv.off[l] + s);
     uint32_t o[8];
 #pragma unroll
@@ -288,10 +280,6 @@ __global__ void verify_multiproof_finish_kernel(const Node* __restrict__ cell, c
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
     uint32_t diff = hdr[0] != 0ull ? 1u : 0u;
-    if (!diff) {                                  // the cells are only written when the status is 0
-        const Node c = vkmr_dev::load_node(cell), r = vkmr_dev::load_node(root);
-#pragma unroll
-        for (int w = 0; w < 8; ++w) diff |= c.w[w] ^ r.w[w];
-    }
+    if (!diff) diff = vkmr_dev::node_diff(vkmr_dev::load_node(cell), vkmr_dev::load_node(root));   // the cells are only written when the status is 0
     ok[0] = diff == 0u ? 1u : 0u;
 }

@@ -14,7 +14,8 @@
 //                                              whole forest, level by level (no reference counterpart); builds the stored forest
 //   forest_tree_kernels.hpp  forest_proofs_kernel          proofs gathered from the stored forest, one lane per (query, level)
 //                            verify_forest_proofs_kernel   batch verification of proofs of unequal height, one lane per proof
-//   sha256d_device.hpp  the SHA-256 round / compression building blocks
+//   sha256d_device.hpp  the SHA-256 round / compression building blocks, and the tree's: hash_parent, node_diff, store_node
+//   merkle_math.hpp     the integer rules, no HIP types (ceil_shift, height, right_child, sibling): shared with host/ and tests/c
 //   meta_kernels.hpp    sizes_*_kernel         metadata entries from 16-bit sizes   (Batches.cpp:64-121)
 //
 // Host side: plain launches on the caller's stream; no allocation, no sync inside
@@ -76,6 +77,14 @@ static vkmr_status from_hip(hipError_t e, const char* what)
 
 static inline hipStream_t S(vkmr_stream s) { return reinterpret_cast<hipStream_t>(s); }
 static inline hipEvent_t E(vkmr_event e) { return reinterpret_cast<hipEvent_t>(e); }
+// The ABI's digests (and raw scratch) as the kernels' nodes.
+static inline const Node* nodes(const vkmr_digest* d) { return reinterpret_cast<const Node*>(d); }
+static inline Node* nodes(vkmr_digest* d) { return reinterpret_cast<Node*>(d); }
+static inline Node* nodes(void* p) { return static_cast<Node*>(p); }
+// One lane per item in workgroups of 256: the workgroups, the grid (x for the items, y as given), and the most a launch takes.
+static inline uint64_t groups_of(uint64_t items) { return (items + 255) / 256; }
+static inline dim3 grid_of(uint64_t items, uint32_t y = 1) { return dim3((uint32_t)groups_of(items), y); }
+static inline bool grid_too_large(uint64_t groups) { return groups > 0x7fffffffull; }
 
 extern "C" {
 
@@ -356,7 +365,7 @@ vkmr_status vkmr_hip_map_async(int dev, vkmr_stream s, const uint32_t* data_dev,
         return fail(VKMR_ERR_INVALID, "vkmr_hip_map_async: null pointer");
     VKMR_TRY(hipSetDevice(dev));
     const uint64_t avg_words = (data_words + count - 1) / count;
-    Node* out = reinterpret_cast<Node*>(out_dev);
+    Node* out = nodes(out_dev);
 #ifdef VKMR_EXPERIMENTS
     if (vkmr_map_experiment(S(s), data_dev, data_words, meta_dev, count, out, avg_words)) {
         g_last_map_mode = MAP_EXPERIMENT;
@@ -580,7 +589,7 @@ static vkmr_status reduce_launch(hipStream_t stream, const Node* digests, uint32
             const uint32_t m = st.levels - 1u;
             const uint64_t waves = ceil_shift(n, 7 + m);
             const uint64_t grid = (waves + VKMR_PASS_WAVES - 1) / VKMR_PASS_WAVES;
-            if (grid > 0x7fffffffull) return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_async: slice too large");
+            if (grid_too_large(grid)) return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_async: slice too large");
             if (prove) hipLaunchKernelGGL(reduce_pass_proofs_kernel, dim3((uint32_t)grid, nslices), dim3(VKMR_PASS_WAVES * 64), 0, stream, in, g, out, m, *proofs, level0);
             else hipLaunchKernelGGL(reduce_pass_kernel, dim3((uint32_t)grid, nslices), dim3(VKMR_PASS_WAVES * 64), 0, stream, in, g, out, m);
         } else {
@@ -606,8 +615,7 @@ vkmr_status vkmr_hip_reduce_async(int dev, vkmr_stream s, const vkmr_digest* dig
         return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_async: height does not reduce count to one node");
     if (count > VKMR_TAIL_MAX && !scratch_dev) return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_async: null scratch");
     VKMR_TRY(hipSetDevice(dev));
-    return reduce_launch(S(s), reinterpret_cast<const Node*>(digests_dev), 1, count, count, height,
-                         reinterpret_cast<Node*>(scratch_dev), reinterpret_cast<Node*>(root_dev));
+    return reduce_launch(S(s), nodes(digests_dev), 1, count, count, height, nodes(scratch_dev), nodes(root_dev));
 }
 
 // ---- proof ----------------------------------------------------------------------
@@ -620,26 +628,24 @@ vkmr_status vkmr_hip_proof_async(int dev, vkmr_stream s, const vkmr_digest* dige
     if (index >= count) return fail(VKMR_ERR_INVALID, "vkmr_hip_proof_async: index out of range");
     if (count > VKMR_TAIL_MAX && !scratch_dev) return fail(VKMR_ERR_INVALID, "vkmr_hip_proof_async: null scratch");
     VKMR_TRY(hipSetDevice(dev));
-    const Node* leaves = reinterpret_cast<const Node*>(digests_dev);
-    Node* sib = reinterpret_cast<Node*>(siblings_dev);
+    const Node* leaves = nodes(digests_dev);
+    Node* sib = nodes(siblings_dev);
     for (uint32_t l = 0; l < height; ++l) {
-        // level l has cl nodes; the path node is p, its partner q (or p itself at the ragged right edge)
+        // level l has cl nodes; q is the partner of the path node (or the path node itself at the ragged right edge)
         const uint64_t cl = (l >= 64) ? 1 : ceil_shift(count, l);
-        const uint64_t p = (l >= 64) ? 0 : (index >> l);
-        uint64_t q = p ^ 1ull;
-        if (q >= cl) q = p;
+        const uint64_t q = vkmr_math::sibling((l >= 64) ? 0 : (index >> l), cl);
         // node q of level l = root of the sub-tree over leaves [q * 2^l, min((q + 1) * 2^l, count)), l levels
         const uint64_t lo = (l >= 64) ? 0 : (q << l);
         uint64_t n = (l >= 63) ? count - lo : ((count - lo < (1ull << l)) ? count - lo : (1ull << l));
         if (l == 0) {
             VKMR_TRY(hipMemcpyAsync(sib, leaves + lo, sizeof(Node), hipMemcpyDeviceToDevice, S(s)));
         } else {
-            const vkmr_status st = reduce_launch(S(s), leaves + lo, 1, n, n, l, reinterpret_cast<Node*>(scratch_dev), sib + l);
+            const vkmr_status st = reduce_launch(S(s), leaves + lo, 1, n, n, l, nodes(scratch_dev), sib + l);
             if (st != VKMR_OK) return st;
         }
     }
     if (root_dev)
-        return reduce_launch(S(s), leaves, 1, count, count, height, reinterpret_cast<Node*>(scratch_dev), reinterpret_cast<Node*>(root_dev));
+        return reduce_launch(S(s), leaves, 1, count, count, height, nodes(scratch_dev), nodes(root_dev));
     return VKMR_OK;
 }
 
@@ -657,7 +663,7 @@ vkmr_status vkmr_hip_reduce_proofs_async(int dev, vkmr_stream s, const vkmr_dige
     ProofArgs pa;
     pa.k = k;
     pa.height = height;
-    pa.sib = reinterpret_cast<Node*>(siblings_dev);
+    pa.sib = nodes(siblings_dev);
     for (uint32_t q = 0; q < VKMR_MAX_PROOFS; ++q) pa.index[q] = 0;
     for (uint32_t q = 0; q < k; ++q) {
         if (indices[q] >= count) return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_proofs_async: index out of range");
@@ -665,11 +671,9 @@ vkmr_status vkmr_hip_reduce_proofs_async(int dev, vkmr_stream s, const vkmr_dige
     }
     VKMR_TRY(hipSetDevice(dev));
     if (height == 0) {   // one node, no level: the root is the node (reduce_tail_kernel), no sibling exists
-        return reduce_launch(S(s), reinterpret_cast<const Node*>(digests_dev), 1, count, count, height, reinterpret_cast<Node*>(scratch_dev),
-                             reinterpret_cast<Node*>(root_dev));
+        return reduce_launch(S(s), nodes(digests_dev), 1, count, count, height, nodes(scratch_dev), nodes(root_dev));
     }
-    return reduce_launch(S(s), reinterpret_cast<const Node*>(digests_dev), 1, count, count, height, reinterpret_cast<Node*>(scratch_dev),
-                         reinterpret_cast<Node*>(root_dev), &pa);
+    return reduce_launch(S(s), nodes(digests_dev), 1, count, count, height, nodes(scratch_dev), nodes(root_dev), &pa);
 }
 
 vkmr_status vkmr_hip_reduce_slices_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint32_t nslices,
@@ -686,14 +690,14 @@ vkmr_status vkmr_hip_reduce_slices_async(int dev, vkmr_stream s, const vkmr_dige
     // grid.y carries the slice index: at most 32768 slices per launch sequence; longer runs go in
     // chunks on the same stream (the scratch is reused, the stream serialises them)
     const uint32_t chunk = 32768u;
-    const Node* digests = reinterpret_cast<const Node*>(digests_dev);
-    Node* roots = reinterpret_cast<Node*>(roots_dev);
+    const Node* digests = nodes(digests_dev);
+    Node* roots = nodes(roots_dev);
     for (uint32_t first = 0; first < nslices; first += chunk) {
         const uint32_t n = (nslices - first < chunk) ? nslices - first : chunk;
         const bool has_last = (first + n == nslices);
         const uint64_t n_full = (nslices == 1) ? count_last : capacity;
         const vkmr_status st = reduce_launch(S(s), digests + (uint64_t)first * capacity, n, n_full, has_last ? count_last : capacity, height,
-                                             reinterpret_cast<Node*>(scratch_dev), roots + first);
+                                             nodes(scratch_dev), roots + first);
         if (st != VKMR_OK) return st;
     }
     return VKMR_OK;
@@ -729,9 +733,8 @@ static vkmr_status levels_launch(hipStream_t stream, const Node* in, uint64_t co
     for (uint32_t lv = 0; lv < height; ++lv) {
         const uint64_t pairs = ceil_shift(n, 1);
         Node* out = dst(lv);
-        const uint64_t grid = (pairs + 255) / 256;
-        if (grid > 0x7fffffffull) return fail(VKMR_ERR_INVALID, too_large);
-        hipLaunchKernelGGL(reduce_level_kernel, dim3((uint32_t)grid), dim3(256), 0, stream, in, n, out);
+        if (grid_too_large(groups_of(pairs))) return fail(VKMR_ERR_INVALID, too_large);
+        hipLaunchKernelGGL(reduce_level_kernel, grid_of(pairs), dim3(256), 0, stream, in, n, out);
         VKMR_TRY(hipGetLastError());
         in = out;
         n = pairs;
@@ -748,10 +751,10 @@ vkmr_status vkmr_hip_reduce_levels_async(int dev, vkmr_stream s, const vkmr_dige
     if (!height_ok(count, height))
         return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_levels_async: height does not reduce count to one node");
     VKMR_TRY(hipSetDevice(dev));
-    Node* bufA = reinterpret_cast<Node*>(scratch_dev);
+    Node* bufA = nodes(scratch_dev);
     Node* bufB = bufA + ceil_shift(count, 1);
-    Node* root = reinterpret_cast<Node*>(root_dev);
-    const vkmr_status st = levels_launch(S(s), reinterpret_cast<const Node*>(digests_dev), count, height,
+    Node* root = nodes(root_dev);
+    const vkmr_status st = levels_launch(S(s), nodes(digests_dev), count, height,
                                          [=](uint32_t lv) { return (lv + 1 == height) ? root : ((lv & 1) ? bufB : bufA); },
                                          "vkmr_hip_reduce_levels_async: slice too large");
     if (st != VKMR_OK) return st;
@@ -789,8 +792,8 @@ vkmr_status vkmr_hip_reduce_tree_async(int dev, vkmr_stream s, const vkmr_digest
     TreeLevels lv;
     tree_levels(count, height, &lv);
     VKMR_TRY(hipSetDevice(dev));
-    Node* tree = reinterpret_cast<Node*>(tree_dev);
-    return levels_launch(S(s), reinterpret_cast<const Node*>(digests_dev), count, height, [&](uint32_t l) { return tree + lv.off[l + 1]; },
+    Node* tree = nodes(tree_dev);
+    return levels_launch(S(s), nodes(digests_dev), count, height, [&](uint32_t l) { return tree + lv.off[l + 1]; },
                          "vkmr_hip_reduce_tree_async: slice too large");
 }
 
@@ -806,11 +809,10 @@ vkmr_status vkmr_hip_tree_proofs_async(int dev, vkmr_stream s, const vkmr_digest
     TreeLevels lv;
     tree_levels(count, height, &lv);
     const uint64_t total = (uint64_t)k * height;
-    const uint64_t grid = (total + 255) / 256;
-    if (grid > 0x7fffffffull) return fail(VKMR_ERR_INVALID, "vkmr_hip_tree_proofs_async: too many proofs in one call");
+    if (grid_too_large(groups_of(total))) return fail(VKMR_ERR_INVALID, "vkmr_hip_tree_proofs_async: too many proofs in one call");
     VKMR_TRY(hipSetDevice(dev));
-    hipLaunchKernelGGL(tree_proofs_kernel, dim3((uint32_t)grid), dim3(256), 0, S(s), reinterpret_cast<const Node*>(digests_dev),
-                       reinterpret_cast<const Node*>(tree_dev), lv, count, height, indices_dev, total, reinterpret_cast<Node*>(siblings_dev));
+    hipLaunchKernelGGL(tree_proofs_kernel, grid_of(total), dim3(256), 0, S(s), nodes(digests_dev),
+                       nodes(tree_dev), lv, count, height, indices_dev, total, nodes(siblings_dev));
     VKMR_TRY(hipGetLastError());
     return VKMR_OK;
 }
@@ -825,10 +827,8 @@ vkmr_status vkmr_hip_verify_proofs_async(int dev, vkmr_stream s, const vkmr_dige
     if (height == 0 || height > 63) return fail(VKMR_ERR_INVALID, "vkmr_hip_verify_proofs_async: height must be 1..63");
     if (nroots != 1 && nroots != k) return fail(VKMR_ERR_INVALID, "vkmr_hip_verify_proofs_async: nroots must be 1 or k");
     VKMR_TRY(hipSetDevice(dev));
-    const uint32_t grid = (uint32_t)(((uint64_t)k + 255) / 256);
-    hipLaunchKernelGGL(verify_proofs_kernel, dim3(grid), dim3(256), 0, S(s), reinterpret_cast<const Node*>(leaves_dev), indices_dev,
-                       reinterpret_cast<const Node*>(siblings_dev), k, height, reinterpret_cast<const Node*>(roots_dev),
-                       (uint32_t)(nroots == 1 ? 0u : 1u), ok_dev);
+    hipLaunchKernelGGL(verify_proofs_kernel, grid_of(k), dim3(256), 0, S(s), nodes(leaves_dev), indices_dev, nodes(siblings_dev), k, height,
+                       nodes(roots_dev), (uint32_t)(nroots == 1 ? 0u : 1u), ok_dev);
     VKMR_TRY(hipGetLastError());
     return VKMR_OK;
 }
@@ -844,19 +844,18 @@ vkmr_status vkmr_hip_tree_update_async(int dev, vkmr_stream s, vkmr_digest* dige
         return fail(VKMR_ERR_INVALID, "vkmr_hip_tree_update_async: height does not reduce count to one node");
     TreeLevels lv;
     tree_levels(count, height, &lv);
-    const uint32_t grid = (uint32_t)(((uint64_t)k + 255) / 256);
-    Node* digests = reinterpret_cast<Node*>(digests_dev);
-    Node* tree = reinterpret_cast<Node*>(tree_dev);
+    const dim3 grid = grid_of(k);
+    Node* digests = nodes(digests_dev);
+    Node* tree = nodes(tree_dev);
     VKMR_TRY(hipSetDevice(dev));
     VKMR_TRY(hipMemsetAsync(status_dev, 0, sizeof(uint32_t), S(s)));
-    hipLaunchKernelGGL(tree_update_check_kernel, dim3(grid), dim3(256), 0, S(s), indices_dev, k, count, status_dev);
+    hipLaunchKernelGGL(tree_update_check_kernel, grid, dim3(256), 0, S(s), indices_dev, k, count, status_dev);
     VKMR_TRY(hipGetLastError());
-    hipLaunchKernelGGL(tree_update_leaves_kernel, dim3(grid), dim3(256), 0, S(s), digests, indices_dev,
-                       reinterpret_cast<const Node*>(leaves_dev), k, (const uint32_t*)status_dev);
+    hipLaunchKernelGGL(tree_update_leaves_kernel, grid, dim3(256), 0, S(s), digests, indices_dev, nodes(leaves_dev), k, (const uint32_t*)status_dev);
     VKMR_TRY(hipGetLastError());
     for (uint32_t l = 1; l <= height; ++l) {   // level l from level l - 1, which the previous launch finished
         const Node* in = (l == 1) ? digests : tree + lv.off[l - 1];
-        hipLaunchKernelGGL(tree_update_level_kernel, dim3(grid), dim3(256), 0, S(s), in, ceil_shift(count, l - 1), tree + lv.off[l],
+        hipLaunchKernelGGL(tree_update_level_kernel, grid, dim3(256), 0, S(s), in, ceil_shift(count, l - 1), tree + lv.off[l],
                            indices_dev, k, l, (const uint32_t*)status_dev);
         VKMR_TRY(hipGetLastError());
     }
@@ -909,16 +908,16 @@ size_t vkmr_hip_multiproof_scratch_bytes(uint32_t k, uint32_t height)
 static vkmr_status multiproof_rank_launch(hipStream_t stream, const uint64_t* indices_dev, uint32_t k, uint64_t count, uint32_t height,
                                           const MultiproofLayout& L, char* scratch, uint64_t* hdr, uint64_t limit, uint32_t exact)
 {
-    const uint32_t grid = (uint32_t)(((uint64_t)k + 255) / 256);
+    const dim3 grid = grid_of(k);
     VKMR_TRY(hipMemsetAsync(hdr, 0, (height == 0 ? 2 : 1) * sizeof(uint64_t), stream));
-    hipLaunchKernelGGL(tree_update_check_kernel, dim3(grid), dim3(256), 0, stream, indices_dev, k, count, reinterpret_cast<uint32_t*>(hdr));
+    hipLaunchKernelGGL(tree_update_check_kernel, grid, dim3(256), 0, stream, indices_dev, k, count, reinterpret_cast<uint32_t*>(hdr));
     VKMR_TRY(hipGetLastError());
     if (height == 0) return VKMR_OK;
     uint64_t* mask = reinterpret_cast<uint64_t*>(scratch + L.mask);
     uint64_t* word_start = reinterpret_cast<uint64_t*>(scratch + L.word_start);
     uint64_t* block = reinterpret_cast<uint64_t*>(scratch + L.block);
     const dim3 wgrid((uint32_t)L.blocks, height);
-    hipLaunchKernelGGL(multiproof_masks_kernel, dim3(grid), dim3(256), 0, stream, indices_dev, k, height, L.words, mask);
+    hipLaunchKernelGGL(multiproof_masks_kernel, grid, dim3(256), 0, stream, indices_dev, k, height, L.words, mask);
     VKMR_TRY(hipGetLastError());
     hipLaunchKernelGGL(multiproof_block_sums_kernel, wgrid, dim3(VKMR_MP_BLOCK_WORDS), 0, stream, (const uint64_t*)mask, L.words, L.blocks, block);
     VKMR_TRY(hipGetLastError());
@@ -946,10 +945,9 @@ vkmr_status vkmr_hip_tree_multiproof_async(int dev, vkmr_stream s, const vkmr_di
     VKMR_TRY(hipSetDevice(dev));
     const vkmr_status st = multiproof_rank_launch(S(s), indices_dev, k, count, height, L, scratch, info_dev, nodes_capacity, 0u);
     if (st != VKMR_OK || height == 0) return st;
-    hipLaunchKernelGGL(tree_multiproof_gather_kernel, dim3((uint32_t)(((uint64_t)k + 255) / 256), height), dim3(256), 0, S(s),
-                       reinterpret_cast<const Node*>(digests_dev), reinterpret_cast<const Node*>(tree_dev), lv, count, indices_dev, k, L.words,
-                       reinterpret_cast<const uint64_t*>(scratch + L.mask), reinterpret_cast<const uint64_t*>(scratch + L.word_start),
-                       (const uint64_t*)info_dev, reinterpret_cast<Node*>(nodes_dev));
+    hipLaunchKernelGGL(tree_multiproof_gather_kernel, grid_of(k, height), dim3(256), 0, S(s), nodes(digests_dev), nodes(tree_dev), lv, count,
+                       indices_dev, k, L.words, reinterpret_cast<const uint64_t*>(scratch + L.mask),
+                       reinterpret_cast<const uint64_t*>(scratch + L.word_start), (const uint64_t*)info_dev, nodes(nodes_dev));
     VKMR_TRY(hipGetLastError());
     return VKMR_OK;
 }
@@ -965,21 +963,20 @@ vkmr_status vkmr_hip_verify_multiproof_async(int dev, vkmr_stream s, const vkmr_
     const MultiproofLayout L = multiproof_layout(k, height);
     char* scratch = static_cast<char*>(scratch_dev);
     uint64_t* hdr = reinterpret_cast<uint64_t*>(scratch + L.hdr);
-    Node* cell = reinterpret_cast<Node*>(scratch + L.cell);
+    Node* cell = nodes(scratch + L.cell);
     VKMR_TRY(hipSetDevice(dev));
     // the index check with 2^height as the bound: bit 0 an index outside the tree, bit 1 not strictly increasing; exact: M == m
     const vkmr_status st = multiproof_rank_launch(S(s), indices_dev, k, 1ull << height, height, L, scratch, hdr, m, 1u);
     if (st != VKMR_OK) return st;
-    const uint32_t grid = (uint32_t)(((uint64_t)k + 255) / 256);
+    const dim3 grid = grid_of(k);
     for (uint32_t l = 0; l < height; ++l) {   // level l + 1 from level l, which the previous launch finished
-        hipLaunchKernelGGL(verify_multiproof_level_kernel, dim3(grid), dim3(256), 0, S(s), l == 0 ? reinterpret_cast<const Node*>(leaves_dev) : cell,
+        hipLaunchKernelGGL(verify_multiproof_level_kernel, grid, dim3(256), 0, S(s), l == 0 ? nodes(leaves_dev) : cell,
                            cell, reinterpret_cast<uint32_t*>(scratch + L.end), indices_dev, k, l, L.words,
                            reinterpret_cast<const uint64_t*>(scratch + L.mask), reinterpret_cast<const uint64_t*>(scratch + L.word_start),
-                           reinterpret_cast<const Node*>(nodes_dev), (const uint64_t*)hdr);
+                           nodes(nodes_dev), (const uint64_t*)hdr);
         VKMR_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(verify_multiproof_finish_kernel, dim3(1), dim3(64), 0, S(s), (const Node*)cell, reinterpret_cast<const Node*>(root_dev),
-                       (const uint64_t*)hdr, ok_dev);
+    hipLaunchKernelGGL(verify_multiproof_finish_kernel, dim3(1), dim3(64), 0, S(s), (const Node*)cell, nodes(root_dev), (const uint64_t*)hdr, ok_dev);
     VKMR_TRY(hipGetLastError());
     return VKMR_OK;
 }
@@ -1009,20 +1006,19 @@ static vkmr_status forest_launch(const char* who, int dev, vkmr_stream s, const 
     if ((!digests_dev && total > 0) || !offsets_dev || !buffer_dev || !roots_dev || !status_dev) return refuse("null pointer");
     if (max_count == 0) return refuse("max_count must be at least 1");
     if (reinterpret_cast<uintptr_t>(buffer_dev) & 15u) return refuse("the level buffer must be 16-byte aligned");
-    if (total > (1ull << 58) || (vkmr_forest::level_cells(total, ntrees, 1) + 255) / 256 > 0x7fffffffull) return refuse("forest too large");
+    if (total > (1ull << 58) || grid_too_large(groups_of(vkmr_forest::level_cells(total, ntrees, 1)))) return refuse("forest too large");
     if (max_count > total) max_count = total;
     const uint32_t levels = vkmr_forest::launches(total, max_count);
-    const Node* digests = reinterpret_cast<const Node*>(digests_dev);
-    Node* roots = reinterpret_cast<Node*>(roots_dev);
+    const Node* digests = nodes(digests_dev);
+    Node* roots = nodes(roots_dev);
     VKMR_TRY(hipSetDevice(dev));
     VKMR_TRY(hipMemsetAsync(status_dev, 0, sizeof(uint32_t), S(s)));
-    hipLaunchKernelGGL(forest_check_kernel, dim3((uint32_t)(((uint64_t)ntrees + 255) / 256)), dim3(256), 0, S(s), offsets_dev, ntrees, total, max_count,
-                       status_dev);
+    hipLaunchKernelGGL(forest_check_kernel, grid_of(ntrees), dim3(256), 0, S(s), offsets_dev, ntrees, total, max_count, status_dev);
     VKMR_TRY(hipGetLastError());
     for (uint32_t l = 1; l <= levels; ++l) {   // level l from level l - 1, which the previous launch finished
         const Node* in = (l == 1) ? digests : level(l - 1);
         const uint64_t cells = vkmr_forest::level_cells(total, ntrees, l);
-        hipLaunchKernelGGL(forest_level_kernel, dim3((uint32_t)((cells + 255) / 256)), dim3(256), 0, S(s), in, offsets_dev, ntrees, l, cells, level(l),
+        hipLaunchKernelGGL(forest_level_kernel, grid_of(cells), dim3(256), 0, S(s), in, offsets_dev, ntrees, l, cells, level(l),
                            roots, (const uint32_t*)status_dev);
         VKMR_TRY(hipGetLastError());
     }
@@ -1034,7 +1030,7 @@ vkmr_status vkmr_hip_reduce_forest_async(int dev, vkmr_stream s, const vkmr_dige
                                          uint32_t ntrees, uint64_t max_count, void* scratch_dev, vkmr_digest* roots_dev, uint32_t* status_dev)
 {
     if (ntrees == 0) return VKMR_OK;
-    Node* scratch = reinterpret_cast<Node*>(scratch_dev);
+    Node* scratch = nodes(scratch_dev);
     return forest_launch("vkmr_hip_reduce_forest_async", dev, s, digests_dev, total, offsets_dev, ntrees, max_count, scratch_dev, roots_dev, status_dev,
                          [&](uint32_t l) { return scratch + vkmr_forest::level_base(total, ntrees, l); });
 }
@@ -1052,7 +1048,7 @@ vkmr_status vkmr_hip_reduce_forest_tree_async(int dev, vkmr_stream s, const vkmr
                                               uint32_t* status_dev)
 {
     if (ntrees == 0) return VKMR_OK;
-    Node* forest = reinterpret_cast<Node*>(forest_dev);
+    Node* forest = nodes(forest_dev);
     return forest_launch("vkmr_hip_reduce_forest_tree_async", dev, s, digests_dev, total, offsets_dev, ntrees, max_count, forest_dev, roots_dev,
                          status_dev, [&](uint32_t l) { return forest + vkmr_forest::stored_level_base(total, ntrees, l); });
 }
@@ -1070,12 +1066,10 @@ vkmr_status vkmr_hip_forest_proofs_async(int dev, vkmr_stream s, const vkmr_dige
     ForestLevels lv;
     for (uint32_t l = 0; l < VKMR_TREE_MAX_LEVELS; ++l) lv.base[l] = (l >= 1 && l <= H) ? vkmr_forest::stored_level_base(total, ntrees, l) : 0;
     const uint64_t cells = (uint64_t)k * H;
-    const uint64_t grid = (cells + 255) / 256;
-    if (grid > 0x7fffffffull) return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_proofs_async: too many proofs in one call");
+    if (grid_too_large(groups_of(cells))) return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_proofs_async: too many proofs in one call");
     VKMR_TRY(hipSetDevice(dev));
-    hipLaunchKernelGGL(forest_proofs_kernel, dim3((uint32_t)grid), dim3(256), 0, S(s), reinterpret_cast<const Node*>(digests_dev),
-                       reinterpret_cast<const Node*>(forest_dev), lv, offsets_dev, ntrees, H, trees_dev, indices_dev, cells,
-                       reinterpret_cast<Node*>(siblings_dev), heights_dev);
+    hipLaunchKernelGGL(forest_proofs_kernel, grid_of(cells), dim3(256), 0, S(s), nodes(digests_dev), nodes(forest_dev), lv, offsets_dev, ntrees, H,
+                       trees_dev, indices_dev, cells, nodes(siblings_dev), heights_dev);
     VKMR_TRY(hipGetLastError());
     return VKMR_OK;
 }
@@ -1089,27 +1083,20 @@ vkmr_status vkmr_hip_verify_forest_proofs_async(int dev, vkmr_stream s, const vk
         return fail(VKMR_ERR_INVALID, "vkmr_hip_verify_forest_proofs_async: null pointer");
     if (stride == 0 || stride > 63) return fail(VKMR_ERR_INVALID, "vkmr_hip_verify_forest_proofs_async: stride must be 1..63");
     VKMR_TRY(hipSetDevice(dev));
-    const uint32_t grid = (uint32_t)(((uint64_t)k + 255) / 256);
-    hipLaunchKernelGGL(verify_forest_proofs_kernel, dim3(grid), dim3(256), 0, S(s), reinterpret_cast<const Node*>(leaves_dev), trees_dev, indices_dev,
-                       reinterpret_cast<const Node*>(siblings_dev), heights_dev, k, stride, reinterpret_cast<const Node*>(roots_dev), ntrees, ok_dev);
+    const dim3 grid = grid_of(k);
+    hipLaunchKernelGGL(verify_forest_proofs_kernel, grid, dim3(256), 0, S(s), nodes(leaves_dev), trees_dev, indices_dev,
+                       nodes(siblings_dev), heights_dev, k, stride, nodes(roots_dev), ntrees, ok_dev);
     VKMR_TRY(hipGetLastError());
     return VKMR_OK;
 }
 
 // ---- combine --------------------------------------------------------------------
 
-static uint32_t combine_height(uint64_t n)
-{
-    uint32_t height = 1;   // at least one level: CpuSha256D::Root's do-while (SHA-256plus.cpp:515-547)
-    while (ceil_shift(n, height) > 1) ++height;
-    return height;
-}
-
 vkmr_status vkmr_hip_combine_async(int dev, vkmr_stream s, const vkmr_digest* roots_dev, uint32_t n, void* scratch_dev,
                                    vkmr_digest* root_dev)
 {
     if (!roots_dev || !root_dev || n == 0) return fail(VKMR_ERR_INVALID, "vkmr_hip_combine_async: bad argument");
-    return vkmr_hip_reduce_async(dev, s, roots_dev, n, combine_height(n), scratch_dev, root_dev);
+    return vkmr_hip_reduce_async(dev, s, roots_dev, n, vkmr_math::height(n), scratch_dev, root_dev);   // at least one level
 }
 
 void vkmr_hip_digest_hex(const vkmr_digest* d, char* hex)

@@ -121,6 +121,60 @@ class DeviceBuffer:
             pass
 
 
+class BufferScope:
+    """The temporary device buffers of one `with dev.scope() as tmp:` block, freed on every way out of it, an exception
+    included.  release() takes out the ones the block hands on to their new owner."""
+
+    def __init__(self, dev):
+        self.dev, self.bufs = dev, []
+
+    def keep(self, buf):
+        if buf:
+            self.bufs.append(buf)
+        return buf
+
+    def alloc(self, nbytes):
+        return self.keep(self.dev.alloc(nbytes))
+
+    def upload(self, arr):
+        return self.keep(self.dev.upload(arr))
+
+    def release(self, *bufs):
+        self.bufs = [b for b in self.bufs if not any(b is x for x in bufs)]
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        for b in self.bufs:
+            b.free()
+        self.bufs = []
+
+
+def _host(arr, dtype, *shape):
+    """A host array as the device calls take it: contiguous, of `dtype`, reshaped."""
+    return np.ascontiguousarray(arr, dtype=dtype).reshape(*shape)
+
+
+def _as_uint64(values, what, noun, plural, below=None, range_error=IndexError):
+    """`values` as a flat uint64 array.  ValueError when they are not integers, `range_error` for a negative one or, with
+    `below`, for one outside [0, below); no device call."""
+    raw = np.asarray(values).reshape(-1)
+    if raw.dtype.kind == "O" and below is not None:            # Python ints numpy could not fit in one integer type
+        vals = [int(x) for x in raw]
+        if any(v < 0 or v >= below for v in vals):
+            raise range_error(f"{what}: {noun} outside [0, {below})")
+        return np.array(vals, dtype=np.uint64)
+    if raw.size and raw.dtype.kind not in "iu":
+        raise ValueError(f"{what}: {plural} must be integers")
+    if raw.dtype.kind == "i" and (raw < 0).any():
+        raise range_error(f"{what}: negative {noun}")
+    out = raw.astype(np.uint64)
+    if below is not None and (out >= np.uint64(below)).any():
+        raise range_error(f"{what}: {noun} outside [0, {below})")
+    return out
+
+
 class HipDevice:
     """One GPU + one stream.  Every method is one or two ABI calls."""
 
@@ -143,6 +197,10 @@ class HipDevice:
 
     def alloc(self, nbytes):
         return DeviceBuffer(self, nbytes)
+
+    def scope(self):
+        """`with dev.scope() as tmp:` -- tmp.alloc / tmp.upload / tmp.keep give buffers that are freed when the block ends."""
+        return BufferScope(self)
 
     def upload(self, arr, stream=None):
         arr = np.ascontiguousarray(arr)
@@ -197,6 +255,18 @@ class HipDevice:
                                           meta_buf.at(8 * meta_offset), count, out_buf.at(32 * out_offset_digests)),
               "vkmr_hip_map_async")
 
+    def map_packed(self, tmp, batch, out_buf=None, out_offset_digests=0, meta=None):
+        """The strings of `batch` (those of `meta`, rows of batch.meta, when given) mapped to leaf digests in device memory:
+        into out_buf from digest out_offset_digests on, or into a new buffer, which is returned.  Enqueued, not waited for:
+        the uploaded strings, and a new buffer, belong to the scope `tmp`, which must outlive the map (end it behind a sync
+        or a download; tmp.release() a new buffer that is handed on)."""
+        meta = batch.meta if meta is None else meta
+        d_data = tmp.upload(batch.data if batch.words else np.zeros(1, np.uint32))
+        d_meta = tmp.upload(meta)
+        out = out_buf or tmp.alloc(32 * int(meta.shape[0]))
+        self.map_async(d_data, batch.words, d_meta, int(meta.shape[0]), out, out_offset_digests=out_offset_digests)
+        return out
+
     def reduce_async(self, digests_buf, count, height, scratch_buf, root_buf, root_index=0, levels_variant=False, stream=None):
         fn = self.lib.vkmr_hip_reduce_levels_async if levels_variant else self.lib.vkmr_hip_reduce_async
         check(fn(self.index, stream or self.stream, digests_buf.ptr, count, height, scratch_buf.ptr if scratch_buf else None,
@@ -210,32 +280,24 @@ class HipDevice:
 
     def proof(self, digests_buf, count, height, index):
         """(siblings [height, 8], root [8]) of leaf `index` in the tree reduce_async(count, height) computes."""
-        d_sib = self.alloc(32 * max(height, 1))
-        d_root = self.alloc(32)
-        d_scratch = self.reduce_scratch(count)
-        check(self.lib.vkmr_hip_proof_async(self.index, self.stream, digests_buf.ptr, count, height, index, d_scratch.ptr, d_sib.ptr,
-                                            d_root.ptr), "vkmr_hip_proof_async")
-        sib = self.download(d_sib, 32 * height).reshape(-1, 8) if height else np.zeros((0, 8), np.uint32)
-        root = self.download(d_root, 32)
-        for b in (d_sib, d_root, d_scratch):
-            b.free()
-        return sib, root
+        with self.scope() as tmp:
+            d_sib, d_root, d_scratch = tmp.alloc(32 * max(height, 1)), tmp.alloc(32), tmp.keep(self.reduce_scratch(count))
+            check(self.lib.vkmr_hip_proof_async(self.index, self.stream, digests_buf.ptr, count, height, index, d_scratch.ptr, d_sib.ptr,
+                                                d_root.ptr), "vkmr_hip_proof_async")
+            sib = self.download(d_sib, 32 * height).reshape(-1, 8) if height else np.zeros((0, 8), np.uint32)
+            return sib, self.download(d_root, 32)
 
     def reduce_with_proofs(self, digests_buf, count, height, indices):
         """(siblings [k, height, 8], root [8]): the reduction that writes the proofs of leaves `indices` while it runs
         (vkmr_hip_reduce_proofs_async; k <= 16)."""
         idx = np.ascontiguousarray(indices, dtype=np.uint64)
         k = int(idx.shape[0])
-        d_sib = self.alloc(32 * max(height, 1) * max(k, 1))
-        d_root = self.alloc(32)
-        d_scratch = self.reduce_scratch(count)
-        check(self.lib.vkmr_hip_reduce_proofs_async(self.index, self.stream, digests_buf.ptr, count, height, d_scratch.ptr, d_root.ptr,
-                                                    idx.ctypes.data if k else None, k, d_sib.ptr), "vkmr_hip_reduce_proofs_async")
-        sib = self.download(d_sib, 32 * height * k).reshape(k, height, 8) if height and k else np.zeros((k, height, 8), np.uint32)
-        root = self.download(d_root, 32)
-        for b in (d_sib, d_root, d_scratch):
-            b.free()
-        return sib, root
+        with self.scope() as tmp:
+            d_sib, d_root, d_scratch = tmp.alloc(32 * max(height, 1) * max(k, 1)), tmp.alloc(32), tmp.keep(self.reduce_scratch(count))
+            check(self.lib.vkmr_hip_reduce_proofs_async(self.index, self.stream, digests_buf.ptr, count, height, d_scratch.ptr, d_root.ptr,
+                                                        idx.ctypes.data if k else None, k, d_sib.ptr), "vkmr_hip_reduce_proofs_async")
+            sib = self.download(d_sib, 32 * height * k).reshape(k, height, 8) if height and k else np.zeros((k, height, 8), np.uint32)
+            return sib, self.download(d_root, 32)
 
     # -- stored tree: build, gather proofs, verify -----------------------------------
     def tree_bytes(self, count, height):
@@ -273,22 +335,17 @@ class HipDevice:
     def verify_multiproof(self, leaves, indices, nodes, root, height):
         """bool: the multiproof `nodes` ([M, 8]) proves leaves ([k, 8]) at `indices` ([k], strictly increasing) under `root`
         in a tree of `height` levels (1..63).  Host arrays in, verified on the device; no leaf proves nothing: False."""
-        leaves = np.ascontiguousarray(leaves, dtype=np.uint32).reshape(-1, 8)
-        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
-        nodes = np.ascontiguousarray(nodes, dtype=np.uint32).reshape(-1, 8)
-        root = np.ascontiguousarray(root, dtype=np.uint32).reshape(8)
+        leaves, idx, nodes, root = _host(leaves, np.uint32, -1, 8), _host(indices, np.uint64, -1), _host(nodes, np.uint32, -1, 8), _host(root, np.uint32, 8)
         k, m = int(idx.shape[0]), int(nodes.shape[0])
         if leaves.shape[0] != k:
             raise ValueError("verify_multiproof: one leaf per index")
         if k == 0:
             return False
-        bufs = [self.upload(a) for a in (leaves, idx, nodes, root)]
-        d_scr, d_ok = self.alloc(self.lib.vkmr_hip_multiproof_scratch_bytes(k, height)), self.alloc(4)
-        self.verify_multiproof_async(bufs[0], bufs[1], k, height, bufs[2] if m else None, m, bufs[3], d_scr, d_ok)
-        ok = int(self.download(d_ok, 4)[0])
-        for b in bufs + [d_scr, d_ok]:
-            b.free()
-        return ok == 1
+        with self.scope() as tmp:
+            d_leaves, d_idx, d_nodes, d_root = (tmp.upload(a) for a in (leaves, idx, nodes, root))
+            d_scr, d_ok = tmp.alloc(self.lib.vkmr_hip_multiproof_scratch_bytes(k, height)), tmp.alloc(4)
+            self.verify_multiproof_async(d_leaves, d_idx, k, height, d_nodes if m else None, m, d_root, d_scr, d_ok)
+            return int(self.download(d_ok, 4)[0]) == 1
 
     def build_tree(self, digests_buf, count, height=None):
         """Every level of the tree over `count` digests in `digests_buf` (which stays level 0 and must outlive the tree),
@@ -301,22 +358,18 @@ class HipDevice:
     def verify_proofs(self, leaves, indices, siblings, roots):
         """bool [k]: proof q (leaf [8], index, siblings [height, 8]) folds to roots[0] (roots [8] or [1, 8]) or roots[q]
         (roots [k, 8]), its index inside the tree.  Host arrays in, verified on the device."""
-        leaves = np.ascontiguousarray(leaves, dtype=np.uint32).reshape(-1, 8)
-        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        leaves, idx, roots = _host(leaves, np.uint32, -1, 8), _host(indices, np.uint64, -1), _host(roots, np.uint32, -1, 8)
         k = int(idx.shape[0])
-        siblings = np.ascontiguousarray(siblings, dtype=np.uint32).reshape(k, -1, 8)
-        roots = np.ascontiguousarray(roots, dtype=np.uint32).reshape(-1, 8)
+        siblings = _host(siblings, np.uint32, k, -1, 8)
         if leaves.shape[0] != k or roots.shape[0] not in (1, k):
             raise ValueError("verify_proofs: one leaf per index, and one root or one per proof")
         if k == 0:
             return np.zeros(0, dtype=bool)
-        bufs = [self.upload(a) for a in (leaves, idx, siblings, roots)]
-        d_ok = self.alloc(4 * k)
-        self.verify_proofs_async(bufs[0], bufs[1], bufs[2], k, siblings.shape[1], bufs[3], roots.shape[0], d_ok)
-        ok = self.download(d_ok, 4 * k)
-        for b in bufs + [d_ok]:
-            b.free()
-        return ok == 1
+        with self.scope() as tmp:
+            d_leaves, d_idx, d_sib, d_roots = (tmp.upload(a) for a in (leaves, idx, siblings, roots))
+            d_ok = tmp.alloc(4 * k)
+            self.verify_proofs_async(d_leaves, d_idx, d_sib, k, siblings.shape[1], d_roots, roots.shape[0], d_ok)
+            return self.download(d_ok, 4 * k) == 1
 
     # -- forest: the roots of many trees of unequal size in one call ----------------------
     def reduce_forest_async(self, digests_buf, total, offsets_buf, ntrees, max_count, scratch_buf, roots_buf, status_buf, stream=None):
@@ -325,40 +378,42 @@ class HipDevice:
                                                     scratch_buf.ptr if scratch_buf else None, roots_buf.ptr if roots_buf else None,
                                                     status_buf.ptr if status_buf else None), "vkmr_hip_reduce_forest_async")
 
-    def _forest_of_buffer(self, d_leaves, total, counts, max_count, what):
-        """[ntrees, 8] uint32: the roots of the trees of `counts` leaves each over the `total` cells of d_leaves."""
-        offsets, ntrees = forest_offsets(counts)
-        if int(offsets[-1]) != total:
-            raise ValueError(f"{what}: the counts add up to {int(offsets[-1])}, not to the {total} leaves")
-        if ntrees == 0:
-            return np.zeros((0, 8), dtype=np.uint32)
+    def _reduce_forest(self, tmp, d_leaves, total, offsets, ntrees, max_count, what, stored):
+        """One forest call over checked offsets (ntrees >= 1), its buffers in the scope `tmp`: the roots alone, or with
+        `stored` every level kept.  (max_count, offsets buffer, level buffer, roots buffer); ValueError when the device
+        refuses the forest."""
         if max_count is None:
             max_count = max(1, int(np.diff(offsets).max()))
-        d_off = self.upload(offsets)
-        d_scr = self.alloc(self.lib.vkmr_hip_forest_scratch_bytes(total, ntrees))
-        d_roots, d_status = self.alloc(32 * ntrees), self.alloc(4)
-        self.reduce_forest_async(d_leaves, total, d_off, ntrees, max_count, d_scr, d_roots, d_status)
+        d_off, d_roots, d_status = tmp.upload(offsets), tmp.alloc(32 * ntrees), tmp.alloc(4)
+        if stored:
+            d_levels = tmp.alloc(self.forest_tree_bytes(total, ntrees, max_count))
+            self.reduce_forest_tree_async(d_leaves, total, d_off, ntrees, max_count, d_levels, d_roots, d_status)
+        else:
+            d_levels = tmp.alloc(self.lib.vkmr_hip_forest_scratch_bytes(total, ntrees))
+            self.reduce_forest_async(d_leaves, total, d_off, ntrees, max_count, d_levels, d_roots, d_status)
         status = int(self.download(d_status, 4)[0])
-        roots = self.download(d_roots, 32 * ntrees).reshape(ntrees, 8) if status == 0 else None
-        for b in (d_off, d_scr, d_roots, d_status):
-            b.free()
         if status:
             raise ValueError(f"{what}: the device refused the forest (status {status}: {forest_status_text(status)})")
-        return roots
+        return max_count, d_off, d_levels, d_roots
+
+    def _forest_of_buffer(self, d_leaves, total, counts, max_count, what):
+        """[ntrees, 8] uint32: the roots of the trees of `counts` leaves each over the `total` cells of d_leaves."""
+        offsets, ntrees = _checked_offsets(counts, total, what)
+        if ntrees == 0:
+            return np.zeros((0, 8), dtype=np.uint32)
+        with self.scope() as tmp:
+            d_roots = self._reduce_forest(tmp, d_leaves, total, offsets, ntrees, max_count, what, stored=False)[3]
+            return self.download(d_roots, 32 * ntrees).reshape(ntrees, 8)
 
     def forest_roots(self, digests, counts, max_count=None):
         """[ntrees, 8] uint32: the root of every tree of a forest (vkmr_hip_reduce_forest_async).  `digests` [total, 8] holds the
         leaves of all trees back to back, tree t the next counts[t] of them; an empty tree gets an all-zero root.  max_count:
         an upper bound on every count (the largest count when None).  ValueError when the counts do not add up to the
         leaves, or when the device refuses the forest (a count above max_count)."""
-        digests = np.ascontiguousarray(digests, dtype=np.uint32).reshape(-1, 8)
+        digests = _host(digests, np.uint32, -1, 8)
         total = int(digests.shape[0])
-        d_in = self.upload(digests) if total else None
-        try:
-            return self._forest_of_buffer(d_in, total, counts, max_count, "forest_roots")
-        finally:
-            if d_in:
-                d_in.free()
+        with self.scope() as tmp:
+            return self._forest_of_buffer(tmp.upload(digests) if total else None, total, counts, max_count, "forest_roots")
 
     # -- stored forest: every level kept, proofs gathered from it, proofs of unequal height verified --
     def forest_tree_bytes(self, total, ntrees, max_count):
@@ -384,23 +439,12 @@ class HipDevice:
 
     def _build_forest_of_buffer(self, d_leaves, total, counts, max_count, what, owned=()):
         """A MerkleForest of the trees of `counts` leaves each over the `total` cells of d_leaves (its level 0)."""
-        offsets, ntrees = forest_offsets(counts)
-        if int(offsets[-1]) != total:
-            raise ValueError(f"{what}: the counts add up to {int(offsets[-1])}, not to the {total} leaves")
+        offsets, ntrees = _checked_offsets(counts, total, what)
         if ntrees == 0:
             raise ValueError(f"{what}: no tree")
-        if max_count is None:
-            max_count = max(1, int(np.diff(offsets).max()))
-        d_off = self.upload(offsets)
-        d_forest = self.alloc(self.forest_tree_bytes(total, ntrees, max_count))
-        d_roots, d_status = self.alloc(32 * ntrees), self.alloc(4)
-        self.reduce_forest_tree_async(d_leaves, total, d_off, ntrees, max_count, d_forest, d_roots, d_status)
-        status = int(self.download(d_status, 4)[0])
-        d_status.free()
-        if status:
-            for b in (d_off, d_forest, d_roots):
-                b.free()
-            raise ValueError(f"{what}: the device refused the forest (status {status}: {forest_status_text(status)})")
+        with self.scope() as tmp:
+            max_count, d_off, d_forest, d_roots = self._reduce_forest(tmp, d_leaves, total, offsets, ntrees, max_count, what, stored=True)
+            tmp.release(d_off, d_forest, d_roots)      # the forest's from here on
         return MerkleForest(self, d_leaves, total, np.diff(offsets), d_off, max_count, d_forest, d_roots, owned=owned)
 
     def build_forest(self, digests, counts, max_count=None):
@@ -408,40 +452,33 @@ class HipDevice:
         `digests` [total, 8] (a host array) holds the leaves of all trees back to back, tree t the next counts[t] of them;
         max_count: an upper bound on every count (the largest count when None).  ValueError when the counts do not add up to
         the leaves, for no tree at all, or when the device refuses the forest (a count above max_count)."""
-        digests = np.ascontiguousarray(digests, dtype=np.uint32).reshape(-1, 8)
+        digests = _host(digests, np.uint32, -1, 8)
         total = int(digests.shape[0])
-        d_in = self.upload(digests) if total else None
-        try:
-            return self._build_forest_of_buffer(d_in, total, counts, max_count, "build_forest", owned=[d_in] if d_in else [])
-        except Exception:
-            if d_in:
-                d_in.free()
-            raise
+        with self.scope() as tmp:
+            d_in = tmp.upload(digests) if total else None
+            forest = self._build_forest_of_buffer(d_in, total, counts, max_count, "build_forest", owned=[d_in] if d_in else [])
+            tmp.release(d_in)
+        return forest
 
     def verify_forest_proofs(self, leaves, trees, indices, siblings, heights, roots):
         """bool [k]: proof q (leaf [8], tree, index, siblings [stride, 8] of which the first heights[q] count) folds to
         roots[trees[q]] (roots [ntrees, 8]), with 1 <= heights[q] <= stride, its index below 2^heights[q] and its tree below
         ntrees (vkmr_hip_verify_forest_proofs_async).  Host arrays in, verified on the device."""
-        leaves = np.ascontiguousarray(leaves, dtype=np.uint32).reshape(-1, 8)
-        trees = np.ascontiguousarray(trees, dtype=np.uint32).reshape(-1)
-        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
-        heights = np.ascontiguousarray(heights, dtype=np.uint32).reshape(-1)
+        leaves, trees, idx = _host(leaves, np.uint32, -1, 8), _host(trees, np.uint32, -1), _host(indices, np.uint64, -1)
+        heights, roots = _host(heights, np.uint32, -1), _host(roots, np.uint32, -1, 8)
         k = int(idx.shape[0])
-        siblings = np.ascontiguousarray(siblings, dtype=np.uint32).reshape(k, -1, 8)
-        roots = np.ascontiguousarray(roots, dtype=np.uint32).reshape(-1, 8)
+        siblings = _host(siblings, np.uint32, k, -1, 8)
         if leaves.shape[0] != k or trees.shape[0] != k or heights.shape[0] != k:
             raise ValueError("verify_forest_proofs: one leaf, one tree and one height per index")
         if k == 0:
             return np.zeros(0, dtype=bool)
         if roots.shape[0] == 0:
             raise ValueError("verify_forest_proofs: no root")
-        bufs = [self.upload(a) for a in (leaves, trees, idx, siblings, heights, roots)]
-        d_ok = self.alloc(4 * k)
-        self.verify_forest_proofs_async(bufs[0], bufs[1], bufs[2], bufs[3], bufs[4], k, siblings.shape[1], bufs[5], roots.shape[0], d_ok)
-        ok = self.download(d_ok, 4 * k)
-        for b in bufs + [d_ok]:
-            b.free()
-        return ok == 1
+        with self.scope() as tmp:
+            d_leaves, d_trees, d_idx, d_sib, d_h, d_roots = (tmp.upload(a) for a in (leaves, trees, idx, siblings, heights, roots))
+            d_ok = tmp.alloc(4 * k)
+            self.verify_forest_proofs_async(d_leaves, d_trees, d_idx, d_sib, d_h, k, siblings.shape[1], d_roots, roots.shape[0], d_ok)
+            return self.download(d_ok, 4 * k) == 1
 
     def reduce_scratch(self, count, levels_variant=False):
         fn = self.lib.vkmr_hip_reduce_levels_scratch_bytes if levels_variant else self.lib.vkmr_hip_reduce_scratch_bytes
@@ -453,43 +490,30 @@ class HipDevice:
 
     def combine(self, roots):
         """Root ([8] uint32) over slice roots given as a host array, in slice order."""
-        roots = np.ascontiguousarray(roots, dtype=np.uint32).reshape(-1, 8)
-        d_in, d_root = self.upload(roots), self.alloc(32)
-        d_scratch = self.reduce_scratch(roots.shape[0])
-        self.combine_async(d_in, roots.shape[0], d_scratch, d_root)
-        out = self.download(d_root, 32)
-        for b in (d_in, d_root, d_scratch):
-            b.free()
-        return out
+        roots = _host(roots, np.uint32, -1, 8)
+        with self.scope() as tmp:
+            d_in, d_root, d_scratch = tmp.upload(roots), tmp.alloc(32), tmp.keep(self.reduce_scratch(roots.shape[0]))
+            self.combine_async(d_in, roots.shape[0], d_scratch, d_root)
+            return self.download(d_root, 32)
 
     # -- conveniences used by tests ------------------------------------------------
     def leaf_digests(self, batch):
         """Digests of every string of `batch` as a [count, 8] uint32 array."""
         if batch.count == 0:
             return np.zeros((0, 8), dtype=np.uint32)
-        d_data = self.upload(batch.data if batch.words else np.zeros(1, np.uint32))
-        d_meta = self.upload(batch.meta)
-        d_out = self.alloc(32 * batch.count)
-        self.map_async(d_data, batch.words, d_meta, batch.count, d_out)
-        out = self.download(d_out, 32 * batch.count).reshape(-1, 8)
-        for b in (d_data, d_meta, d_out):
-            b.free()
-        return out
+        with self.scope() as tmp:
+            return self.download(self.map_packed(tmp, batch), 32 * batch.count).reshape(-1, 8)
 
     def reduce_digests(self, digests, height=None, levels_variant=False):
         """Sub-tree root ([8] uint32) of a [count, 8] uint32 array of digests."""
-        digests = np.ascontiguousarray(digests, dtype=np.uint32).reshape(-1, 8)
+        digests = _host(digests, np.uint32, -1, 8)
         count = digests.shape[0]
         if height is None:
             height = tree_height(count)
-        d_in = self.upload(digests)
-        d_scratch = self.reduce_scratch(count, levels_variant)
-        d_root = self.alloc(32)
-        self.reduce_async(d_in, count, height, d_scratch, d_root, levels_variant=levels_variant)
-        root = self.download(d_root, 32)
-        for b in (d_in, d_scratch, d_root):
-            b.free()
-        return root
+        with self.scope() as tmp:
+            d_in, d_scratch, d_root = tmp.upload(digests), tmp.keep(self.reduce_scratch(count, levels_variant)), tmp.alloc(32)
+            self.reduce_async(d_in, count, height, d_scratch, d_root, levels_variant=levels_variant)
+            return self.download(d_root, 32)
 
 
 class Multiproof:
@@ -537,17 +561,14 @@ class MerkleTree:
 
     def proofs(self, indices):
         """[k, height, 8] uint32: the proofs of leaves `indices` (a host array); an index >= count gets zero cells."""
-        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        idx = _host(indices, np.uint64, -1)
         k = int(idx.shape[0])
         if k == 0 or self.height == 0:
             return np.zeros((k, self.height, 8), dtype=np.uint32)
-        d_idx = self.dev.upload(idx)
-        d_sib = self.dev.alloc(32 * k * self.height)
-        self.proofs_async(d_idx, k, d_sib)
-        out = self.dev.download(d_sib, 32 * k * self.height).reshape(k, self.height, 8)
-        d_idx.free()
-        d_sib.free()
-        return out
+        with self.dev.scope() as tmp:
+            d_idx, d_sib = tmp.upload(idx), tmp.alloc(32 * k * self.height)
+            self.proofs_async(d_idx, k, d_sib)
+            return self.dev.download(d_sib, 32 * k * self.height).reshape(k, self.height, 8)
 
     def multiproof_async(self, indices_buf, k, scratch_buf, nodes_buf, nodes_capacity, info_buf, stream=None):
         """ONE proof for the k leaves whose strictly increasing indices are in device memory, written to nodes_buf
@@ -564,21 +585,18 @@ class MerkleTree:
             raise ValueError("multiproof: no index")
         lib = self.dev.lib
         cap = lib.vkmr_hip_multiproof_max_nodes(self.count, self.height, k)
-        d_idx = self.dev.upload(idx)
-        d_scr = self.dev.alloc(lib.vkmr_hip_multiproof_scratch_bytes(k, self.height)) if self.height else None
-        d_nodes = self.dev.alloc(32 * cap) if cap else None
-        d_info = self.dev.alloc(8 * (2 + self.height))
-        self.multiproof_async(d_idx, k, d_scr, d_nodes, cap, d_info)
-        status = int(self.dev.download(d_info, 8, dtype=np.uint64)[0])
-        if status == 0:                       # M and the counts are only written then (or with bit 2)
+        with self.dev.scope() as tmp:
+            d_idx = tmp.upload(idx)
+            d_scr = tmp.alloc(lib.vkmr_hip_multiproof_scratch_bytes(k, self.height)) if self.height else None
+            d_nodes = tmp.alloc(32 * cap) if cap else None
+            d_info = tmp.alloc(8 * (2 + self.height))
+            self.multiproof_async(d_idx, k, d_scr, d_nodes, cap, d_info)
+            status = int(self.dev.download(d_info, 8, dtype=np.uint64)[0])
+            if status:                            # M and the counts are only written without one (or with bit 2)
+                raise RuntimeError(f"MerkleTree.multiproof: the device refused sorted in-range indices (status {status})")
             info = self.dev.download(d_info, 8 * (2 + self.height), dtype=np.uint64)
             m = int(info[1])
             nodes = self.dev.download(d_nodes, 32 * m).reshape(m, 8) if m else np.zeros((0, 8), dtype=np.uint32)
-        for b in (d_idx, d_scr, d_nodes, d_info):
-            if b:
-                b.free()
-        if status:
-            raise RuntimeError(f"MerkleTree.multiproof: the device refused sorted in-range indices (status {status})")
         return Multiproof(idx, nodes, info[2:].copy(), self.height)
 
     def update_async(self, indices_buf, leaves_buf, k, status_buf, stream=None):
@@ -590,31 +608,18 @@ class MerkleTree:
     def _update_order(self, indices, what="update"):
         """(sorted unique uint64 indices, positions in `indices` they come from): the last occurrence of a repeated index
         wins.  IndexError for an index < 0 or >= count; no device call."""
-        raw = np.asarray(indices).reshape(-1)
-        if raw.dtype.kind == "O":            # Python ints numpy could not fit in one integer type
-            vals = [int(x) for x in raw]
-            if any(v < 0 or v >= self.count for v in vals):
-                raise IndexError(f"{what}: index outside [0, {self.count})")
-            idx = np.array(vals, dtype=np.uint64)
-        elif raw.size and raw.dtype.kind not in "iu":
-            raise ValueError(f"{what}: indices must be integers")
-        else:
-            if raw.dtype.kind == "i" and (raw < 0).any():
-                raise IndexError(f"{what}: negative index")
-            idx = raw.astype(np.uint64)
-            if (idx >= np.uint64(self.count)).any():
-                raise IndexError(f"{what}: index outside [0, {self.count})")
+        idx = _as_uint64(indices, what, "index", "indices", below=self.count)
         order = np.argsort(idx, kind="stable")
         s = idx[order]
         last = np.ones(s.shape[0], dtype=bool)
         last[:-1] = s[1:] != s[:-1]        # a stable sort keeps repeats in call order: the last of each run is the last occurrence
         return s[last], order[last]
 
-    def _apply(self, d_idx, d_leaves, k):
-        d_status = self.dev.alloc(4)
-        self.update_async(d_idx, d_leaves, k, d_status)
+    def _apply(self, tmp, idx, d_leaves):
+        """The update of leaves idx (sorted, unique, in range) to the digests in d_leaves; its buffers in the scope `tmp`."""
+        d_idx, d_status = tmp.upload(idx), tmp.alloc(4)
+        self.update_async(d_idx, d_leaves, idx.shape[0], d_status)
         status = int(self.dev.download(d_status, 4)[0])
-        d_status.free()
         if status:
             raise RuntimeError(f"MerkleTree.update: the device refused sorted in-range indices (status {status})")
 
@@ -627,13 +632,9 @@ class MerkleTree:
         if lv.shape != (k, 8):
             raise ValueError(f"update: leaves must be [{k}, 8], not {list(lv.shape)}")
         idx, pos = self._update_order(indices)
-        if idx.shape[0] == 0:
-            return
-        lv = np.ascontiguousarray(lv[pos], dtype=np.uint32)
-        d_idx, d_leaves = self.dev.upload(idx), self.dev.upload(lv)
-        self._apply(d_idx, d_leaves, idx.shape[0])
-        d_idx.free()
-        d_leaves.free()
+        with self.dev.scope() as tmp:
+            if idx.shape[0]:
+                self._apply(tmp, idx, tmp.upload(np.ascontiguousarray(lv[pos], dtype=np.uint32)))
 
     def update_packed(self, indices, batch):
         """Set leaf indices[q] to the digest of string q of `batch` (batch.count == len(indices)): the strings are mapped on
@@ -642,17 +643,9 @@ class MerkleTree:
         if batch.count != k:
             raise ValueError(f"update_packed: {batch.count} strings for {k} indices")
         idx, pos = self._update_order(indices)
-        if idx.shape[0] == 0:
-            return
-        meta = np.ascontiguousarray(batch.meta[pos])      # map's entries are independent: the strings in sorted-index order
-        d_data = self.dev.upload(batch.data if batch.words else np.zeros(1, np.uint32))
-        d_meta = self.dev.upload(meta)
-        d_idx = self.dev.upload(idx)
-        d_leaves = self.dev.alloc(32 * idx.shape[0])
-        self.dev.map_async(d_data, batch.words, d_meta, idx.shape[0], d_leaves)
-        self._apply(d_idx, d_leaves, idx.shape[0])
-        for b in (d_data, d_meta, d_idx, d_leaves):
-            b.free()
+        with self.dev.scope() as tmp:
+            if idx.shape[0]:      # map's entries are independent: the strings in sorted-index order
+                self._apply(tmp, idx, self.dev.map_packed(tmp, batch, meta=np.ascontiguousarray(batch.meta[pos])))
 
     def free(self):
         if self.tree:
@@ -689,21 +682,17 @@ class MerkleForest:
         """(siblings [k, levels, 8] uint32, heights [k] uint32) of leaves `indices` of trees `trees` (host arrays): the
         first heights[q] cells of proof q count, the rest are zero; a tree >= ntrees or an index >= its tree's count gets
         height 0 and zero cells."""
-        trees = np.ascontiguousarray(trees, dtype=np.uint32).reshape(-1)
-        idx = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        trees, idx = _host(trees, np.uint32, -1), _host(indices, np.uint64, -1)
         k = int(idx.shape[0])
         if trees.shape[0] != k:
             raise ValueError("proofs: one tree per index")
         if k == 0:
             return np.zeros((0, self.levels, 8), dtype=np.uint32), np.zeros(0, dtype=np.uint32)
-        d_trees, d_idx = self.dev.upload(trees), self.dev.upload(idx)
-        d_sib, d_h = self.dev.alloc(32 * k * self.levels), self.dev.alloc(4 * k)
-        self.proofs_async(d_trees, d_idx, k, d_sib, d_h)
-        sib = self.dev.download(d_sib, 32 * k * self.levels).reshape(k, self.levels, 8)
-        heights = self.dev.download(d_h, 4 * k)
-        for b in (d_trees, d_idx, d_sib, d_h):
-            b.free()
-        return sib, heights
+        with self.dev.scope() as tmp:
+            d_trees, d_idx = tmp.upload(trees), tmp.upload(idx)
+            d_sib, d_h = tmp.alloc(32 * k * self.levels), tmp.alloc(4 * k)
+            self.proofs_async(d_trees, d_idx, k, d_sib, d_h)
+            return self.dev.download(d_sib, 32 * k * self.levels).reshape(k, self.levels, 8), self.dev.download(d_h, 4 * k)
 
     def free(self):
         for b in [self.forest, self.roots_buf, self.offsets] + self._owned:
@@ -713,55 +702,34 @@ class MerkleForest:
         self._owned = []
 
 
-def merkle_forest_packed(dev, batch, counts, max_count=None):
-    """The strings of `batch` mapped to leaf digests ONCE and the stored forest built over them, tree t over the next
-    counts[t] of them, all on the device (a MerkleForest that owns its leaves)."""
-    offsets, _ = forest_offsets(counts)
-    if int(offsets[-1]) != batch.count:
-        raise ValueError(f"merkle_forest_packed: the counts add up to {int(offsets[-1])}, not to the {batch.count} strings")
-    if batch.count == 0:
-        return dev._build_forest_of_buffer(None, 0, counts, max_count, "merkle_forest_packed")
-    d_data = dev.upload(batch.data if batch.words else np.zeros(1, np.uint32))
-    d_meta = dev.upload(batch.meta)
-    d_leaves = dev.alloc(32 * batch.count)
-    dev.map_async(d_data, batch.words, d_meta, batch.count, d_leaves)
-    try:
-        return dev._build_forest_of_buffer(d_leaves, batch.count, counts, max_count, "merkle_forest_packed", owned=[d_leaves])
-    except Exception:
-        d_leaves.free()
-        raise
-    finally:                    # the build has read its status back: the map is done
-        d_data.free()
-        d_meta.free()
-
-
 def merkle_tree_packed(dev, batch, height=None):
     """The strings of `batch` mapped to leaf digests and the whole tree over them built, all on the device (a MerkleTree
     that owns its leaves)."""
     if batch.count == 0:
         raise ValueError("merkle_tree_packed: empty batch")
-    d_data = dev.upload(batch.data if batch.words else np.zeros(1, np.uint32))
-    d_meta = dev.upload(batch.meta)
-    d_leaves = dev.alloc(32 * batch.count)
-    dev.map_async(d_data, batch.words, d_meta, batch.count, d_leaves)
-    tree = dev.build_tree(d_leaves, batch.count, height)
-    tree._owned.append(d_leaves)
-    dev.sync()
-    d_data.free()
-    d_meta.free()
+    with dev.scope() as tmp:
+        d_leaves = dev.map_packed(tmp, batch)
+        tree = dev.build_tree(d_leaves, batch.count, height)
+        dev.sync()
+        tree._owned.append(d_leaves)
+        tmp.release(d_leaves)
     return tree
 
 
 def forest_offsets(counts):
     """(offsets uint64 [ntrees + 1], ntrees) of trees of `counts` leaves laid back to back from cell 0."""
-    raw = np.asarray(counts).reshape(-1)
-    if raw.size and raw.dtype.kind not in "iu":
-        raise ValueError("forest: counts must be integers")
-    if raw.size and raw.dtype.kind == "i" and (raw < 0).any():
-        raise ValueError("forest: negative count")
+    raw = _as_uint64(counts, "forest", "count", "counts", range_error=ValueError)
     offsets = np.zeros(raw.size + 1, dtype=np.uint64)
-    np.cumsum(raw.astype(np.uint64), out=offsets[1:])
+    np.cumsum(raw, out=offsets[1:])
     return offsets, int(raw.size)
+
+
+def _checked_offsets(counts, total, what, cells="leaves"):
+    """forest_offsets(counts); ValueError when they do not add up to the `total` leaves (or strings) at hand."""
+    offsets, ntrees = forest_offsets(counts)
+    if int(offsets[-1]) != total:
+        raise ValueError(f"{what}: the counts add up to {int(offsets[-1])}, not to the {total} {cells}")
+    return offsets, ntrees
 
 
 def forest_status_text(status):
@@ -776,24 +744,30 @@ def forest_status_text(status):
     return "; ".join(names) if names else "ok"
 
 
+def _forest_packed(dev, batch, counts, max_count, what, stored):
+    """`batch` mapped to leaf digests ONCE and one forest call over them: the roots, or with `stored` a MerkleForest that
+    owns its leaves."""
+    _checked_offsets(counts, batch.count, what, "strings")
+    with dev.scope() as tmp:
+        d_leaves = dev.map_packed(tmp, batch) if batch.count else None
+        if not stored:
+            return dev._forest_of_buffer(d_leaves, batch.count, counts, max_count, what)
+        forest = dev._build_forest_of_buffer(d_leaves, batch.count, counts, max_count, what, owned=[d_leaves] if d_leaves else [])
+        tmp.release(d_leaves)
+    return forest
+
+
+def merkle_forest_packed(dev, batch, counts, max_count=None):
+    """The strings of `batch` mapped to leaf digests ONCE and the stored forest built over them, tree t over the next
+    counts[t] of them, all on the device (a MerkleForest that owns its leaves)."""
+    return _forest_packed(dev, batch, counts, max_count, "merkle_forest_packed", stored=True)
+
+
 def merkle_roots_packed_forest(dev, batch, counts, max_count=None):
     """One root per block from a stream of strings: `batch` is mapped to leaf digests ONCE and ONE forest call reduces tree t
     over the next counts[t] of them.  [ntrees, 8] uint32 (digest_hex gives the canonical text); no digest goes through
     the host."""
-    offsets, _ = forest_offsets(counts)
-    if int(offsets[-1]) != batch.count:
-        raise ValueError(f"merkle_roots_packed_forest: the counts add up to {int(offsets[-1])}, not to the {batch.count} strings")
-    if batch.count == 0:
-        return dev._forest_of_buffer(None, 0, counts, max_count, "merkle_roots_packed_forest")
-    d_data = dev.upload(batch.data if batch.words else np.zeros(1, np.uint32))
-    d_meta = dev.upload(batch.meta)
-    d_leaves = dev.alloc(32 * batch.count)
-    dev.map_async(d_data, batch.words, d_meta, batch.count, d_leaves)
-    try:
-        return dev._forest_of_buffer(d_leaves, batch.count, counts, max_count, "merkle_roots_packed_forest")
-    finally:
-        for b in (d_data, d_meta, d_leaves):
-            b.free()
+    return _forest_packed(dev, batch, counts, max_count, "merkle_roots_packed_forest", stored=False)
 
 
 def digest_hex(words):
@@ -809,29 +783,22 @@ def merkle_root_packed_batched(dev, batch, slice_capacity, batch_strings=None):
         return ""
     nslices = (n + slice_capacity - 1) // slice_capacity
     batch_strings = batch_strings or n
-    d_slices = dev.alloc(32 * nslices * slice_capacity)
-    for b0 in range(0, n, batch_strings):
-        b1 = min(n, b0 + batch_strings)
-        sub = batch.slice(b0, b1)
-        d_data = dev.upload(sub.data if sub.words else np.zeros(1, np.uint32))
-        d_meta = dev.upload(sub.meta)
-        dev.map_async(d_data, sub.words, d_meta, sub.count, d_slices, out_offset_digests=b0)
-        dev.sync()
-        d_data.free()
-        d_meta.free()
-    count_last = n - (nslices - 1) * slice_capacity
-    height = int(math.log2(slice_capacity)) if nslices > 1 else tree_height(n)
-    d_scratch = dev.alloc(dev.lib.vkmr_hip_reduce_slices_scratch_bytes(slice_capacity, nslices))
-    d_roots = dev.alloc(32 * nslices)
-    dev.reduce_slices_async(d_slices, nslices, slice_capacity, count_last, height, d_scratch, d_roots)
-    if nslices > 1:
-        d_top = dev.reduce_scratch(nslices)
-        d_final = dev.alloc(32)
-        dev.reduce_async(d_roots, nslices, tree_height(nslices), d_top, d_final)
-        root = dev.download(d_final, 32)
-    else:
-        root = dev.download(d_roots, 32)
-    return digest_hex(root)
+    with dev.scope() as tmp:
+        d_slices = tmp.alloc(32 * nslices * slice_capacity)
+        for b0 in range(0, n, batch_strings):
+            with dev.scope() as up:
+                dev.map_packed(up, batch.slice(b0, min(n, b0 + batch_strings)), d_slices, out_offset_digests=b0)
+                dev.sync()
+        count_last = n - (nslices - 1) * slice_capacity
+        height = int(math.log2(slice_capacity)) if nslices > 1 else tree_height(n)
+        d_scratch = tmp.alloc(dev.lib.vkmr_hip_reduce_slices_scratch_bytes(slice_capacity, nslices))
+        d_roots = tmp.alloc(32 * nslices)
+        dev.reduce_slices_async(d_slices, nslices, slice_capacity, count_last, height, d_scratch, d_roots)
+        if nslices > 1:
+            d_top, d_final = tmp.keep(dev.reduce_scratch(nslices)), tmp.alloc(32)
+            dev.reduce_async(d_roots, nslices, tree_height(nslices), d_top, d_final)
+            return digest_hex(dev.download(d_final, 32))
+        return digest_hex(dev.download(d_roots, 32))
 
 
 def merkle_root_packed(dev, batch, slice_capacity=None, batch_strings=None, levels_variant=False):
@@ -849,26 +816,20 @@ def merkle_root_packed(dev, batch, slice_capacity=None, batch_strings=None, leve
     batch_strings = batch_strings or n
     nslices = (n + slice_capacity - 1) // slice_capacity
     cap_height = int(math.log2(slice_capacity))
-    d_roots = dev.alloc(32 * nslices)
-    for s in range(nslices):
-        lo, hi = s * slice_capacity, min(n, (s + 1) * slice_capacity)
-        d_slice = dev.alloc(32 * (hi - lo))
-        for b0 in range(lo, hi, batch_strings):
-            b1 = min(hi, b0 + batch_strings)
-            sub = batch.slice(b0, b1)
-            d_data = dev.upload(sub.data if sub.words else np.zeros(1, np.uint32))
-            d_meta = dev.upload(sub.meta)
-            dev.map_async(d_data, sub.words, d_meta, sub.count, d_slice, out_offset_digests=b0 - lo)
-            dev.sync()
-            d_data.free()
-            d_meta.free()
-        height = cap_height if nslices > 1 else tree_height(hi - lo)
-        d_scratch = dev.reduce_scratch(hi - lo, levels_variant)
-        dev.reduce_async(d_slice, hi - lo, height, d_scratch, d_roots, root_index=s, levels_variant=levels_variant)
-        dev.sync()
-        d_scratch.free()
-        d_slice.free()
-    roots = dev.download(d_roots, 32 * nslices).reshape(-1, 8)
-    d_roots.free()
+    with dev.scope() as run:
+        d_roots = run.alloc(32 * nslices)
+        for s in range(nslices):
+            lo, hi = s * slice_capacity, min(n, (s + 1) * slice_capacity)
+            with dev.scope() as tmp:
+                d_slice = tmp.alloc(32 * (hi - lo))
+                for b0 in range(lo, hi, batch_strings):
+                    with dev.scope() as up:
+                        dev.map_packed(up, batch.slice(b0, min(hi, b0 + batch_strings)), d_slice, out_offset_digests=b0 - lo)
+                        dev.sync()
+                height = cap_height if nslices > 1 else tree_height(hi - lo)
+                d_scratch = tmp.keep(dev.reduce_scratch(hi - lo, levels_variant))
+                dev.reduce_async(d_slice, hi - lo, height, d_scratch, d_roots, root_index=s, levels_variant=levels_variant)
+                dev.sync()
+        roots = dev.download(d_roots, 32 * nslices).reshape(-1, 8)
     root = roots[0] if nslices == 1 else dev.combine(roots)
     return digest_hex(root)
