@@ -11,6 +11,7 @@
 //   VKMR_FAKE_FAIL_EVENT=i     the i-th event completion (1-based, over all events) reports a device error
 //   VKMR_FAKE_FAIL_REDUCE=i    the i-th vkmr_hip_reduce_async call fails at dispatch
 //   VKMR_FAKE_NO_HASH=1        map and reduce write nothing (host-side timing of the pipeline only; roots are garbage)
+//   VKMR_FAKE_COUNT_CALLS=1    at exit, one "fake: calls ..." line on stderr: how often the resource and stream calls were made
 // "Device" memory is host memory and every *_async call completes at once; hashing is done with the product's
 // own "CPU" backend functions (csrc/host/cpu_sha256d.cpp), never with the oracle.  Scratch buffers are checked
 // against the schedule of the real library (csrc/reduce_plan.hpp): a reduction whose scratch is smaller than
@@ -68,6 +69,29 @@ size_t room_at(const void* p)
 }
 
 bool dev_ok(int dev) { return dev >= 0 && dev < n_devices(); }
+
+// VKMR_FAKE_COUNT_CALLS=1: how often each of these was called -- alloc / create when they succeeded, free / destroy of
+// anything but a null handle (that releases nothing), the stream calls as they come (the double's own nested calls too)
+#define VKMR_COUNTED(X) X(device_alloc) X(device_free) X(host_alloc) X(host_free) X(event_create) X(event_destroy) X(stream_create) X(stream_destroy) \
+    X(memcpy_h2d_async) X(memcpy_d2h_async) X(map_async) X(reduce_async) X(reduce_proofs_async) X(combine_async) X(metadata_from_sizes_async)
+#define X(name) c_##name,
+enum Counted { VKMR_COUNTED(X) c_end };
+#undef X
+std::atomic<unsigned long> g_calls[c_end];
+void report_calls()
+{
+#define X(name) " " #name "=%lu"
+    fprintf(stderr, "fake: calls" VKMR_COUNTED(X) "\n"
+#undef X
+#define X(name) , g_calls[c_##name].load()
+            VKMR_COUNTED(X));
+#undef X
+}
+void called(Counted which)
+{
+    static const bool on = env_long("VKMR_FAKE_COUNT_CALLS", 0) != 0 && atexit(report_calls) == 0;
+    if (on) ++g_calls[which];
+}
 
 struct Event { int polls_left = 0; bool recorded = false; bool failed = false; double at_ms = 0.0; };
 long g_completions = 0, g_reduces = 0;
@@ -132,9 +156,15 @@ vkmr_status vkmr_hip_host_alloc(size_t bytes, void** out)
 {
     if (!out || bytes == 0) return fail(VKMR_ERR_INVALID, "host_alloc");
     *out = calloc(1, bytes);
+    if (*out) called(c_host_alloc);
     return *out ? VKMR_OK : fail(VKMR_ERR_OOM, "host_alloc");
 }
-vkmr_status vkmr_hip_host_free(void* p) { free(p); return VKMR_OK; }
+vkmr_status vkmr_hip_host_free(void* p)
+{
+    if (p) called(c_host_free);
+    free(p);
+    return VKMR_OK;
+}
 
 vkmr_status vkmr_hip_device_alloc(int dev, size_t bytes, void** out)
 {
@@ -148,6 +178,7 @@ vkmr_status vkmr_hip_device_alloc(int dev, size_t bytes, void** out)
     g_allocs[p] = {dev, bytes};
     g_used[(size_t)dev] += bytes;
     *out = p;
+    called(c_device_alloc);
     return VKMR_OK;
 }
 vkmr_status vkmr_hip_device_free(int dev, void* p)
@@ -160,6 +191,7 @@ vkmr_status vkmr_hip_device_free(int dev, void* p)
     g_used[(size_t)it->second.dev] -= it->second.bytes;
     g_allocs.erase(it);
     free(p);
+    called(c_device_free);
     return VKMR_OK;
 }
 
@@ -171,6 +203,7 @@ vkmr_status vkmr_hip_memset_async(int, vkmr_stream, void* dst, int v, size_t n)
 }
 vkmr_status vkmr_hip_memcpy_h2d_async(int, vkmr_stream, void* dst, const void* src, size_t n)
 {
+    called(c_memcpy_h2d_async);
     if (!dst || !src) return fail(VKMR_ERR_INVALID, "h2d: null");
     if (room_at(dst) < n) return fail(VKMR_ERR_INVALID, "h2d: destination outside device memory");
     memcpy(dst, src, n);
@@ -178,6 +211,7 @@ vkmr_status vkmr_hip_memcpy_h2d_async(int, vkmr_stream, void* dst, const void* s
 }
 vkmr_status vkmr_hip_memcpy_d2h_async(int, vkmr_stream, void* dst, const void* src, size_t n)
 {
+    called(c_memcpy_d2h_async);
     if (!dst || !src) return fail(VKMR_ERR_INVALID, "d2h: null");
     if (room_at(src) < n) return fail(VKMR_ERR_INVALID, "d2h: source outside device memory");
     memcpy(dst, src, n);
@@ -198,6 +232,7 @@ size_t vkmr_hip_sizes_scratch_bytes(uint32_t count) { return ((size_t)count / 40
 vkmr_status vkmr_hip_metadata_from_sizes_async(int dev, vkmr_stream, const uint16_t* sizes, uint32_t count, uint32_t first_word, void* scratch,
                                                vkmr_metadata* meta)
 {
+    called(c_metadata_from_sizes_async);
     if (!dev_ok(dev) || (count && (!sizes || !scratch || !meta))) return fail(VKMR_ERR_INVALID, "metadata_from_sizes");
     if (count && (room_at(sizes) < (size_t)count * 2 || room_at(meta) < (size_t)count * sizeof(vkmr_metadata) || room_at(scratch) < vkmr_hip_sizes_scratch_bytes(count)))
         return fail(VKMR_ERR_INVALID, "metadata_from_sizes: outside device memory");
@@ -249,18 +284,30 @@ vkmr_status vkmr_hip_stream_create(int dev, vkmr_stream* out)
 {
     if (!out || !dev_ok(dev)) return fail(VKMR_ERR_INVALID, "stream_create");
     *out = reinterpret_cast<vkmr_stream>(new int(dev));
+    called(c_stream_create);
     return VKMR_OK;
 }
-vkmr_status vkmr_hip_stream_destroy(int, vkmr_stream s) { delete reinterpret_cast<int*>(s); return VKMR_OK; }
+vkmr_status vkmr_hip_stream_destroy(int, vkmr_stream s)
+{
+    if (s) called(c_stream_destroy);
+    delete reinterpret_cast<int*>(s);
+    return VKMR_OK;
+}
 vkmr_status vkmr_hip_stream_sync(int, vkmr_stream) { return VKMR_OK; }
 
 vkmr_status vkmr_hip_event_create(int dev, vkmr_event* out)
 {
     if (!out || !dev_ok(dev)) return fail(VKMR_ERR_INVALID, "event_create");
     *out = reinterpret_cast<vkmr_event>(new Event);
+    called(c_event_create);
     return VKMR_OK;
 }
-vkmr_status vkmr_hip_event_destroy(int, vkmr_event e) { delete reinterpret_cast<Event*>(e); return VKMR_OK; }
+vkmr_status vkmr_hip_event_destroy(int, vkmr_event e)
+{
+    if (e) called(c_event_destroy);
+    delete reinterpret_cast<Event*>(e);
+    return VKMR_OK;
+}
 vkmr_status vkmr_hip_event_record(int, vkmr_event e, vkmr_stream)
 {
     if (!e) return fail(VKMR_ERR_INVALID, "event_record");
@@ -309,6 +356,7 @@ vkmr_status vkmr_hip_event_elapsed_ms(int, vkmr_event b, vkmr_event e, float* ms
 vkmr_status vkmr_hip_map_async(int dev, vkmr_stream, const uint32_t* data, uint64_t data_words, const vkmr_metadata* meta, uint32_t count,
                                vkmr_digest* out)
 {
+    called(c_map_async);
     if (count == 0) return VKMR_OK;
     if (!dev_ok(dev) || !meta || !out) return fail(VKMR_ERR_INVALID, "map: bad argument");
     if (room_at(meta) < (size_t)count * 8 || room_at(out) < (size_t)count * 32 || (data_words && room_at(data) < data_words * 4))
@@ -334,6 +382,7 @@ size_t vkmr_hip_reduce_scratch_bytes(uint64_t count) { return (size_t)vkmr_plan:
 vkmr_status vkmr_hip_reduce_async(int dev, vkmr_stream, const vkmr_digest* digests, uint64_t count, uint32_t height, void* scratch,
                                   vkmr_digest* root)
 {
+    called(c_reduce_async);
     if (!dev_ok(dev) || !digests || !root || count == 0 || height > 63 || vkmr_plan::ceil_shift(count, height) != 1)
         return fail(VKMR_ERR_INVALID, "reduce: bad argument");
     {
@@ -349,6 +398,7 @@ vkmr_status vkmr_hip_reduce_async(int dev, vkmr_stream, const vkmr_digest* diges
 
 vkmr_status vkmr_hip_combine_async(int dev, vkmr_stream s, const vkmr_digest* roots, uint32_t n, void* scratch, vkmr_digest* root)
 {
+    called(c_combine_async);
     if (!roots || !root || n == 0) return fail(VKMR_ERR_INVALID, "combine: bad argument");
     uint32_t height = 1;
     while (vkmr_plan::ceil_shift(n, height) > 1) ++height;
@@ -457,6 +507,7 @@ vkmr_status vkmr_hip_proof_async(int dev, vkmr_stream, const vkmr_digest* digest
 vkmr_status vkmr_hip_reduce_proofs_async(int dev, vkmr_stream s, const vkmr_digest* digests, uint64_t count, uint32_t height, void* scratch,
                                          vkmr_digest* root, const uint64_t* indices, uint32_t k, vkmr_digest* siblings)
 {
+    called(c_reduce_proofs_async);
     if (k == 0) return vkmr_hip_reduce_async(dev, s, digests, count, height, scratch, root);
     if (!indices || !siblings || k > 16) return fail(VKMR_ERR_INVALID, "reduce_proofs: bad argument");
     if (room_at(siblings) < (size_t)k * height * 32) return fail(VKMR_ERR_INVALID, "reduce_proofs: siblings are not device memory (or too small)");

@@ -304,6 +304,52 @@ def test_hip_all_combine_failure_is_loud(fake_vkmr, native, golden):
     assert b"Failed to combine the slice roots" in r.stderr
 
 
+COUNTED = {"VKMR_SLICE_LOG2": 8, "VKMR_BATCH_BYTES": 16384, "VKMR_MAX_INFLIGHT": 2, "VKMR_FAKE_COUNT_CALLS": 1}
+BACKENDS = [("hip:0", {}), ("hip:all", {"VKMR_FAKE_DEVICES": 3})]
+_counted_streams = {}
+
+
+def counted_calls(fake_vkmr, native, backend, strings, **knobs):
+    """`rndm 7 <strings> 60` through the front end on the double; the counters of its "fake: calls" line, and the result line."""
+    if strings not in _counted_streams:
+        _counted_streams[strings] = stream_of(native, {"generator": "rndm 7 %d 60" % strings})
+    r, out, m = run(fake_vkmr, backend, _counted_streams[strings], **dict(COUNTED, **knobs))
+    lines = [l for l in r.stderr.decode().splitlines() if l.startswith("fake: calls ")]
+    assert r.returncode == 0 and len(lines) == 1, r.stderr[-500:]
+    return {k: int(v) for k, v in (f.split("=") for f in lines[0].split()[2:])}, m
+
+
+@pytest.mark.parametrize("backend,devices", BACKENDS)
+@pytest.mark.parametrize("injected,has_root", [
+    ({}, True), ({"VKMR_FAKE_FAIL_EVENT": 1}, False), ({"VKMR_FAKE_FAIL_EVENT": 2}, False), ({"VKMR_FAKE_FAIL_EVENT": 5}, False),
+    ({"VKMR_FAKE_FAIL_REDUCE": 1}, False), ({"VKMR_FAKE_HBM_BYTES": 400000}, True), ({"VKMR_FAKE_HBM_BYTES": 260000}, True),
+    ({"VKMR_FAKE_HBM_BYTES": 160000}, False), ({"VKMR_PROOF_INDEX": 777}, True)])
+def test_every_hip_resource_is_released_exactly_once(fake_vkmr, native, backend, devices, injected, has_root):
+    """Every device buffer, pinned buffer, event and stream of the front end has one owner (csrc/host/hip_handles.hpp): when
+    the process ends, as many were freed as were allocated -- on a clean run, with a failing event, a failing dispatch,
+    device memory that runs out on the way (the first two sizes) or at the start (the third), and with a proof asked for.
+    (LeakSanitizer sees the double's malloc behind a leak; a double free of a pooled event or stream only shows here.)"""
+    calls, m = counted_calls(fake_vkmr, native, backend, 20000, **dict(devices, **injected))
+    for made, released in (("device_alloc", "device_free"), ("host_alloc", "host_free"), ("event_create", "event_destroy"), ("stream_create", "stream_destroy")):
+        assert calls[made] == calls[released] and calls[made] > 0, (made, calls)
+    assert bool(m and m["root"]) == has_root, (m, calls)
+
+
+@pytest.mark.parametrize("backend,devices", BACKENDS)
+def test_a_longer_stream_allocates_nothing_more(fake_vkmr, native, backend, devices):
+    """The pools hold: twice the strings -- twice the batches, mappings and reductions -- and not one more device buffer,
+    pinned buffer or event (hipMalloc / hipFree synchronise the device, pinning a batch is 10-15 ms).  Events complete at
+    once and one thread packs, so that the counts do not depend on timing; all three were equal at both lengths before
+    the handles too (profiles/host_handles_calls.txt)."""
+    knobs = dict(devices, VKMR_FAKE_EVENT_POLLS=0, VKMR_PACK_THREADS=1)
+    short, m1 = counted_calls(fake_vkmr, native, backend, 20000, **knobs)
+    long_, m2 = counted_calls(fake_vkmr, native, backend, 40000, **knobs)
+    assert m1 and m2 and m1["root"] and m2["root"] and int(m2["items"]) == 2 * int(m1["items"]) == 40000
+    assert long_["map_async"] > short["map_async"] and long_["reduce_async"] > short["reduce_async"], (short, long_)
+    for made in ("device_alloc", "host_alloc", "event_create"):
+        assert long_[made] == short[made], (made, short, long_)
+
+
 def test_parallel_packer_in_the_pipeline_under_tsan(native, golden, tmp_path):
     """The fork-join packer feeding the stream processor (mapped file, spans cut at line ends, parts packed at their
     prefix offsets into the pinned batch) under ThreadSanitizer, end to end through the fake ABI."""

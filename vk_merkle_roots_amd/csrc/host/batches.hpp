@@ -23,12 +23,24 @@
 #include <thread>
 #include <vector>
 
+#include "hip_handles.hpp"
 #include "stream_pack.hpp"
 #include "vkmr_hip.h"
 
 namespace vkmr {
 
 class Batches;
+
+// What a batch is made of; owned by the batch while it is out, by its pool's free list otherwise.
+struct BatchBuffers {
+    PinnedMem data, meta, sizes;                  // pinned host: `words` words, `count` entries, `count` 16-bit sizes
+    DeviceMem ddata, dmeta, dsizes, dscratch;     // HBM: their landing zones, vkmr_hip_sizes_scratch_bytes(count)
+    // device-split pools only (experiments build; empty otherwise): the raw text of a batch, vkmr_hip_split_scratch_bytes,
+    // the splitter's three result words and their pinned copy
+    DeviceMem dtext, dsplit, dresult;
+    PinnedMem hresult;
+    size_t words = 0, count = 0;
+};
 
 class Batch {
     friend class Batches;
@@ -44,15 +56,15 @@ public:
     Batch& operator=(const Batch&) = delete;
     ~Batch() { Release(); }
 
-    explicit operator bool() const { return m_data != nullptr && m_meta != nullptr; }
+    explicit operator bool() const { return m_buf.data && m_buf.meta; }
 
     size_type Count() const { return m_count; }          // strings in the batch
     size_type Size() const { return m_bytes; }           // payload bytes
     size_type Words() const { return m_words; }          // packed words used
     bool Empty() const { return !(*this) || m_count == 0; }
-    size_type RoomWords() const { return m_cap_words - m_words; }     // packed words still free
-    size_type CapacityWords() const { return m_cap_words; }
-    size_type CapacityCount() const { return m_cap_count; }
+    size_type RoomWords() const { return m_buf.words - m_words; }     // packed words still free
+    size_type CapacityWords() const { return m_buf.words; }
+    size_type CapacityCount() const { return m_buf.count; }
     number_type Number() const { return m_number; }
     int Device() const { return m_dev; }
 
@@ -80,49 +92,42 @@ public:
     void Pop(size_t count);
 
     // host (pinned) and device views, for Mappings
-    const uint32_t* HostData() const { return m_data; }
-    const vkmr_metadata* HostMeta() const { return m_meta; }
-    uint32_t* DeviceData() const { return m_ddata; }
-    vkmr_metadata* DeviceMeta() const { return m_dmeta; }
+    const uint32_t* HostData() const { return Data(); }
+    const vkmr_metadata* HostMeta() const { return Meta(); }
+    uint32_t* DeviceData() const { return m_buf.ddata.as<uint32_t>(); }
+    vkmr_metadata* DeviceMeta() const { return m_buf.dmeta.as<vkmr_metadata>(); }
     // the 16-bit sizes: usable in place of the metadata when no string reaches 65 536 bytes
-    bool SizesSuffice() const { return m_sizes != nullptr && m_longest < 0xFFFFu; }
-    const uint16_t* HostSizes() const { return m_sizes; }
-    uint16_t* DeviceSizes() const { return m_dsizes; }
-    void* DeviceSizesScratch() const { return m_dscratch; }
+    bool SizesSuffice() const { return m_buf.sizes && m_longest < 0xFFFFu; }
+    const uint16_t* HostSizes() const { return Sizes(); }
+    uint16_t* DeviceSizes() const { return m_buf.dsizes.as<uint16_t>(); }
+    void* DeviceSizesScratch() const { return m_buf.dscratch.get(); }
     // Device-side splitting (pools made with `device_split`): the batch holds raw text instead of packed strings.  The text
     // (whole lines, ending in '\n') is written to TextArea() -- the pinned data buffer taken as bytes -- and SetText says how
     // long it is and what it holds; the device turns it into the packed layout in its own copy of the batch
     // (vkmr_hip_split_text_async) and reports what it found in HostSplitResult() for the owner to check.
-    bool CanHoldText() const { return m_dtext != nullptr; }
-    uint8_t* TextArea() const { return reinterpret_cast<uint8_t*>(m_data); }
-    size_t TextCapacity() const { return m_cap_words * 4; }
+    bool CanHoldText() const { return (bool)m_buf.dtext; }
+    uint8_t* TextArea() const { return m_buf.data.as<uint8_t>(); }
+    size_t TextCapacity() const { return m_buf.words * 4; }
     void SetText(size_t text_bytes, size_t strings, size_t payload_bytes);
     size_t TextBytes() const { return m_text_bytes; }
-    uint8_t* DeviceText() const { return m_dtext; }
-    void* DeviceSplitScratch() const { return m_dsplit; }
-    uint32_t* DeviceSplitResult() const { return m_dresult; }
-    uint32_t* HostSplitResult() const { return m_hresult; }
+    uint8_t* DeviceText() const { return m_buf.dtext.as<uint8_t>(); }
+    void* DeviceSplitScratch() const { return m_buf.dsplit.get(); }
+    uint32_t* DeviceSplitResult() const { return m_buf.dresult.as<uint32_t>(); }
+    uint32_t* HostSplitResult() const { return m_buf.hresult.as<uint32_t>(); }
 
 private:
     void Release();
 
+    uint32_t* Data() const { return m_buf.data.as<uint32_t>(); }
+    vkmr_metadata* Meta() const { return m_buf.meta.as<vkmr_metadata>(); }
+    uint16_t* Sizes() const { return m_buf.sizes.as<uint16_t>(); }
+
     Batches* m_owner = nullptr;
     int m_dev = -1;
-    uint32_t* m_data = nullptr;        // pinned host, data_words capacity
-    vkmr_metadata* m_meta = nullptr;   // pinned host, meta capacity
-    uint32_t* m_ddata = nullptr;       // HBM
-    vkmr_metadata* m_dmeta = nullptr;  // HBM
-    uint16_t* m_sizes = nullptr;       // pinned host, meta capacity
-    uint16_t* m_dsizes = nullptr;      // HBM
-    void* m_dscratch = nullptr;        // HBM, vkmr_hip_sizes_scratch_bytes(meta capacity)
-    uint8_t* m_dtext = nullptr;        // HBM: the raw text of a device-split batch (pools with device_split only)
-    void* m_dsplit = nullptr;          // HBM: vkmr_hip_split_scratch_bytes
-    uint32_t* m_dresult = nullptr;     // HBM: the splitter's three result words
-    uint32_t* m_hresult = nullptr;     // pinned host: their copy
+    BatchBuffers m_buf;                // its capacities are the batch's
     size_t m_text_bytes = 0;           // > 0: the batch holds that much raw text, not packed strings
     size_t m_longest = 0;              // longest string appended so far
     void NoteSizes(size_t first, size_t count);   // sizes[first, first + count) <- meta, m_longest
-    size_t m_cap_words = 0, m_cap_count = 0;
     size_t m_count = 0, m_words = 0, m_bytes = 0;
     number_type m_number = 0xFFFFFFFFu;
 };
@@ -186,9 +191,7 @@ public:
     void Reshape(size_t data_bytes, size_t meta_count);
 
 private:
-    struct Buffers { uint32_t* data; vkmr_metadata* meta; uint32_t* ddata; vkmr_metadata* dmeta; size_t words, count; uint16_t* sizes; uint16_t* dsizes; void* dscratch;
-                     uint8_t* dtext; void* dsplit; uint32_t* dresult; uint32_t* hresult; };
-    void Free(Buffers& b);
+    typedef BatchBuffers Buffers;
     bool Allocate(size_t words, size_t count, Buffers* out);
     void JoinPrefetch();
     int m_dev;

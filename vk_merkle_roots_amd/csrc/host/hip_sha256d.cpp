@@ -161,11 +161,11 @@ HipSha256D::Instance::Instance(const std::string& name, std::vector<int> devices
     const size_t warm_bytes = (size_t)1 << 20;   // a copy the engine treats like a batch's: after a 256-byte one the first batch still took 8-19 ms to submit,
                                                  // after 64 KiB and more 0.01 ms (profiles/r03_frontend_warm_copy.txt)
     auto set_up = [failed, warm_bytes](PerDevice* p) {
-        if (vkmr_hip_stream_create(p->dev, &p->map_stream) != VKMR_OK || vkmr_hip_warm_up(p->dev, p->map_stream, VKMR_WARM_KERNELS, 0) != VKMR_OK)
+        if (StreamHandle::Create(p->dev, &p->map_stream) != VKMR_OK || vkmr_hip_warm_up(p->dev, p->map_stream.get(), VKMR_WARM_KERNELS, 0) != VKMR_OK)
             return failed("map stream");
-        if (vkmr_hip_stream_create(p->dev, &p->copy_stream) != VKMR_OK || vkmr_hip_warm_up(p->dev, p->copy_stream, VKMR_WARM_COPY | VKMR_WARM_KERNELS, warm_bytes) != VKMR_OK)
+        if (StreamHandle::Create(p->dev, &p->copy_stream) != VKMR_OK || vkmr_hip_warm_up(p->dev, p->copy_stream.get(), VKMR_WARM_COPY | VKMR_WARM_KERNELS, warm_bytes) != VKMR_OK)
             return failed("copy stream");
-        p->reduce_stream = p->map_stream;
+        p->reduce_stream = p->map_stream.get();
     };
     for (int d : m_device_ids) {   // what the devices have free now, before this instance takes any of it (ChooseSliceLog2)
         size_t f = 0, t = 0;
@@ -285,18 +285,14 @@ HipSha256D::Instance::~Instance()
     // staged batches and their slice views first: each holds a raw pointer to its pool (Batch::Release -> Batches::Recycle),
     // and the pools go below (a failed StagePacked / RootOfStaged leaves them here)
     m_staged.clear();
-    // ops next (they hold batches and slices), then the pools and streams
+    // ops next (they hold batches and slices), then the pools and streams: each device's batches, then its streams
+    // (the order of PerDevice's members)
     m_pool.reset();
     m_mappings.reset();
     m_reductions.reset();
     m_batch = Batch();
     m_slices = Slices();
-    for (auto& pd : m_devs) {
-        pd.batches.reset();
-        vkmr_hip_stream_destroy(pd.dev, pd.map_stream);
-        vkmr_hip_stream_destroy(pd.dev, pd.copy_stream);
-        if (pd.reduce_stream != pd.map_stream) vkmr_hip_stream_destroy(pd.dev, pd.reduce_stream);
-    }
+    m_devs.clear();
 }
 
 HipSha256D::Instance::PerDevice& HipSha256D::Instance::Dev(int dev)
@@ -394,7 +390,7 @@ bool HipSha256D::Instance::MapCurrent()
             next.batches->Prefetch(m_cfg.max_inflight + 1);
         }
     }
-    return m_mappings->Map(std::move(m_batch), slice.Sub(), pd.map_stream, pd.copy_stream) == VKMR_OK;
+    return m_mappings->Map(std::move(m_batch), slice.Sub(), pd.map_stream.get(), pd.copy_stream.get()) == VKMR_OK;
 }
 
 bool HipSha256D::Instance::StartSliceAndBatch()
@@ -416,6 +412,17 @@ bool HipSha256D::Instance::StartSliceAndBatch()
     return NewBatch(m_slices.Current().Device());
 }
 
+bool HipSha256D::Instance::NextSliceIfFull(bool stage)
+{
+    if (m_slices.Current()) {
+        if (m_slices.Current().Available() != 0) return true;
+        // the slice is fully reserved: send off what is batched and open the next slice
+        if (stage) StageCurrent();
+        else if (!MapCurrent()) return (m_ok = false);
+    }
+    return StartSliceAndBatch();
+}
+
 bool HipSha256D::Instance::Add(const char* bytes, size_t size)
 {
     if (!m_ok || !EnsureGeometry(nullptr, 0)) return false;
@@ -428,13 +435,7 @@ bool HipSha256D::Instance::Add(const char* bytes, size_t size)
     // A failed allocation refuses this string but keeps what was added: the caller stops
     // reading and Root() still covers the earlier strings (reference: Add returns false,
     // the partial root is printed, src/vkmr/Vkmr.cpp:44-55, SHA-256vk.cpp:396-399).
-    if (!m_slices.Current()) {
-        if (!StartSliceAndBatch()) return false;
-    } else if (m_slices.Current().Available() == 0) {
-        // the slice is fully reserved: send off what is batched and open the next slice
-        if (!MapCurrent()) return (m_ok = false);
-        if (!StartSliceAndBatch()) return false;
-    }
+    if (!NextSliceIfFull(false)) return false;
     if (!m_batch.Push(bytes, size)) {
         // batch full: map it and continue in a fresh one on the same device
         const int dev = m_slices.Current().Device();
@@ -522,12 +523,7 @@ bool HipSha256D::Instance::AddLines(const char* buf, size_t len, bool final, Tal
             if (m_mappings->InFlight()) Account(m_mappings->Update());
         }
         if (!m_ok || !m_reductions->Ok()) return (m_ok = false);   // a mapping or reduction failed on the device: stop reading
-        if (!m_slices.Current()) {
-            if (!StartSliceAndBatch()) return false;
-        } else if (m_slices.Current().Available() == 0) {
-            if (!MapCurrent()) return (m_ok = false);
-            if (!StartSliceAndBatch()) return false;
-        }
+        if (!NextSliceIfFull(false)) return false;
         if (!m_batch.Empty() && len - pos >= (1u << 20)) {
             // A large span is waiting.  A batch that is full but for a sliver goes out as it is (topping it up line by line
             // would be done on this thread while the packer's other threads wait); so does a batch that holds a good part of
@@ -606,28 +602,25 @@ bool HipSha256D::Instance::GrowBatchesFor(int dev, size_t string_bytes)
     return true;
 }
 
+void HipSha256D::Instance::StageCurrent()
+{
+    Slice& slice = m_slices.Current();
+    if (m_batch.Empty() || !slice) return;
+    Staged st;
+    st.dev = slice.Device();
+    st.sub = slice.Sub();
+    st.batch = std::move(m_batch);
+    m_staged.push_back(std::move(st));
+}
+
 bool HipSha256D::Instance::StagePacked(const uint32_t* data, const vkmr_metadata* meta, size_t count)
 {
     if (!m_ok || !EnsureGeometry(nullptr, 0)) return false;
-    auto stage_current = [&] {
-        Slice& slice = m_slices.Current();
-        if (m_batch.Empty() || !slice) return;
-        Staged st;
-        st.dev = slice.Device();
-        st.sub = slice.Sub();
-        st.batch = std::move(m_batch);
-        m_staged.push_back(std::move(st));
-    };
     // a failure gives up what was staged: the batches go back to their pools while the pools are alive
     auto give_up = [&] { m_staged.clear(); return false; };
     size_t pos = 0;
     while (pos < count) {
-        if (!m_slices.Current()) {
-            if (!StartSliceAndBatch()) return give_up();
-        } else if (m_slices.Current().Available() == 0) {
-            stage_current();
-            if (!StartSliceAndBatch()) return give_up();
-        }
+        if (!NextSliceIfFull(true)) return give_up();
         Slice& slice = m_slices.Current();
         const size_t took = m_batch.PushPacked(data, meta + pos, count - pos, slice.Available());
         slice.Reserve(took);
@@ -640,7 +633,7 @@ bool HipSha256D::Instance::StagePacked(const uint32_t* data, const vkmr_metadata
                 std::cerr << "A packed string does not fit an empty batch." << std::endl;
                 return give_up();
             }
-            stage_current();
+            StageCurrent();
             if (!NewBatch(dev)) { m_ok = false; return give_up(); }
         }
     }
@@ -650,22 +643,13 @@ bool HipSha256D::Instance::StagePacked(const uint32_t* data, const vkmr_metadata
 ISha256D::out_type HipSha256D::Instance::RootOfStaged()
 {
     if (!m_ok || !m_geometry) return "";
-    {   // the residual batch joins the staged ones
-        Slice& slice = m_slices.Current();
-        if (!m_batch.Empty() && slice) {
-            Staged st;
-            st.dev = slice.Device();
-            st.sub = slice.Sub();
-            st.batch = std::move(m_batch);
-            m_staged.push_back(std::move(st));
-        }
-    }
+    StageCurrent();   // the residual batch joins the staged ones
     for (auto& st : m_staged) {
         m_reductions->Update();
         if (m_mappings->InFlight()) Account(m_mappings->Update());
         if (m_mappings->InFlight() >= m_cfg.max_inflight) Account(m_mappings->WaitUntilAtMost(m_cfg.max_inflight - 1));
         PerDevice& pd = Dev(st.dev);
-        if (!m_ok || m_mappings->Map(std::move(st.batch), std::move(st.sub), pd.map_stream, pd.copy_stream) != VKMR_OK) {
+        if (!m_ok || m_mappings->Map(std::move(st.batch), std::move(st.sub), pd.map_stream.get(), pd.copy_stream.get()) != VKMR_OK) {
             m_staged.clear();   // nothing staged outlives the failure (the pools it points into go with the instance)
             return "";
         }

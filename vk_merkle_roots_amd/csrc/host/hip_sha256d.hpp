@@ -100,7 +100,8 @@ public:
 private:
     struct PerDevice {
         int dev;
-        vkmr_stream map_stream = nullptr, copy_stream = nullptr, reduce_stream = nullptr;   // reduce_stream is the map stream (see the constructor)
+        StreamHandle map_stream, copy_stream;   // declared before the batches: those go first, then the streams (~Instance)
+        vkmr_stream reduce_stream = nullptr;    // borrowed: the map stream (see the constructor)
         std::unique_ptr<Batches> batches;
         bool prefetched = false;   // the pipeline's batches have been requested from the helper thread
     };
@@ -114,6 +115,8 @@ private:
     bool EnsureGeometry(const char* first_span, size_t len);   // slices and reductions exist from the first string on
     uint32_t ChooseSliceLog2(const char* first_span, size_t len, std::string* why) const;
     bool MapCurrent();                                   // dispatches m_batch into the current slice's pending reservations
+    void StageCurrent();                                 // holds it back in m_staged instead (StagePacked)
+    bool NextSliceIfFull(bool stage);                    // no slice yet, or fully reserved: m_batch mapped (or staged), the next slice opened
     void Account(std::vector<Slice>&& retired);          // retired sub-slices -> fill counts -> reductions
     bool StartSliceAndBatch();
     bool NewBatch(int dev);                              // m_batch <- a batch of `dev`, waiting for one to retire if need be

@@ -12,39 +12,31 @@
 namespace vkmr {
 namespace {
 
+// The events of one mapping; recycled through MappingsImpl::m_spare.
+struct Events {
+    EventHandle begin, copied, done;
+};
+
 struct Mapping {
     Batch batch;
     Slice sub;
-    vkmr_event begin = nullptr, copied = nullptr, done = nullptr;
+    Events ev;
     int dev = -1;
 };
 
 class MappingsImpl : public Mappings {
 public:
     MappingsImpl(bool verbose, bool send_sizes) : m_verbose(verbose), m_send_sizes(send_sizes) {}
-    ~MappingsImpl() override
-    {
-        WaitFor();
-        for (auto& e : m_spare) vkmr_hip_event_destroy(e.first, e.second);
-    }
+    ~MappingsImpl() override { WaitFor(); }
 
     HipResult Map(Batch&& batch, slice_type&& sub, vkmr_stream stream, vkmr_stream copy_stream) override
     {
         if (batch.Empty() || !sub) return VKMR_OK;   // nothing to do
         Mapping m;
         m.dev = sub.Device();
-        m.begin = Event(m.dev);
-        m.copied = Event(m.dev);
-        m.done = Event(m.dev);
-        auto give_back = [&] {
-            for (vkmr_event e : {m.begin, m.copied, m.done})
-                if (e) m_spare.emplace_back(m.dev, e);   // keep the events for the next mapping
-        };
-        if (!m.begin || !m.copied || !m.done) {
-            give_back();
-            return VKMR_ERR_HIP;
-        }
-        HipResult r = vkmr_hip_event_record(m.dev, m.begin, copy_stream);
+        if (!TakeEvents(m.dev, &m.ev)) return VKMR_ERR_HIP;
+        const vkmr_event begin = m.ev.begin.get(), copied = m.ev.copied.get(), done = m.ev.done.get();
+        HipResult r = vkmr_hip_event_record(m.dev, begin, copy_stream);
 #ifdef VKMR_EXPERIMENTS
         if (batch.TextBytes() > 0) {
             // (experiments build) raw text: it crosses as it is, the device splits it into the packed layout in the batch's
@@ -74,18 +66,18 @@ public:
             }
         }
         if (r == VKMR_OK && copy_stream != stream) {
-            r = vkmr_hip_event_record(m.dev, m.copied, copy_stream);
-            if (r == VKMR_OK) r = vkmr_hip_stream_wait_event(m.dev, stream, m.copied);
+            r = vkmr_hip_event_record(m.dev, copied, copy_stream);
+            if (r == VKMR_OK) r = vkmr_hip_stream_wait_event(m.dev, stream, copied);
         }
         if (r == VKMR_OK) {
             timing::Scope ts(timing::MAP_LAUNCH);
             r = vkmr_hip_map_async(m.dev, stream, batch.DeviceData(), batch.Words(), batch.DeviceMeta(),
                                    (uint32_t)batch.Count(), sub.Cells());
         }
-        if (r == VKMR_OK) r = vkmr_hip_event_record(m.dev, m.done, stream);
+        if (r == VKMR_OK) r = vkmr_hip_event_record(m.dev, done, stream);
         if (r != VKMR_OK) {
             std::cerr << "Failed to dispatch a mapping: " << vkmr_hip_last_error() << std::endl;
-            give_back();
+            m_spare.push_back(std::move(m.ev));   // keep the events for the next mapping
             return r;
         }
         m.batch = std::move(batch);
@@ -101,17 +93,20 @@ public:
     bool Failed() const override { return m_failed; }
 
 private:
-    vkmr_event Event(int dev)
+    // The three events of a mapping on `dev`: a spare trio of that device, or new ones.  false: one could not be created.
+    bool TakeEvents(int dev, Events* out)
     {
         for (size_t i = 0; i < m_spare.size(); ++i)
-            if (m_spare[i].first == dev) {
-                vkmr_event e = m_spare[i].second;
+            if (m_spare[i].begin.device() == dev) {
+                *out = std::move(m_spare[i]);
                 m_spare.erase(m_spare.begin() + i);
-                return e;
+                return true;
             }
-        vkmr_event e = nullptr;
-        if (vkmr_hip_event_create(dev, &e) != VKMR_OK) return nullptr;
-        return e;
+        Events ev;
+        const bool ok = EventHandle::Create(dev, &ev.begin) == VKMR_OK && EventHandle::Create(dev, &ev.copied) == VKMR_OK &&
+                        EventHandle::Create(dev, &ev.done) == VKMR_OK;
+        if (ok) *out = std::move(ev);
+        return ok;
     }
 
     // Retires finished mappings, oldest first.  With `block`, waits for the oldest
@@ -120,46 +115,36 @@ private:
     {
         std::vector<slice_type> out;
         for (auto it = m_inflight.begin(); it != m_inflight.end();) {
-            HipResult st = vkmr_hip_event_query(it->dev, it->done);
-            if (st == VKMR_NOT_READY && block && m_inflight.size() > keep) st = vkmr_hip_event_wait(it->dev, it->done);
+            HipResult st = vkmr_hip_event_query(it->dev, it->ev.done.get());
+            if (st == VKMR_NOT_READY && block && m_inflight.size() > keep) st = vkmr_hip_event_wait(it->dev, it->ev.done.get());
             if (st == VKMR_NOT_READY) {
                 ++it;
                 continue;
             }
-            if (st < 0) {   // the device reported an error: these digests do not exist
+            bool failed = st < 0;
+            if (failed) {   // the device reported an error: these digests do not exist
                 std::cerr << "Mapping for slice #" << it->sub.Number() << " failed: " << vkmr_hip_last_error() << std::endl;
-                m_failed = true;
-                m_spare.emplace_back(it->dev, it->begin);
-                m_spare.emplace_back(it->dev, it->copied);
-                m_spare.emplace_back(it->dev, it->done);
-                it = m_inflight.erase(it);
-                continue;
-            }
-            if (it->batch.TextBytes() > 0) {   // the device's splitter and the host's count must agree, and the strings must have fitted
+            } else if (it->batch.TextBytes() > 0) {   // the device's splitter and the host's count must agree, and the strings must have fitted
                 const uint32_t* found = it->batch.HostSplitResult();
-                if (found[0] != it->batch.Count() || found[2] != 0u || found[1] > it->batch.Words()) {
+                failed = found[0] != it->batch.Count() || found[2] != 0u || found[1] > it->batch.Words();
+                if (failed)
                     std::cerr << "Mapping for slice #" << it->sub.Number() << " failed: the device split the text into " << found[0] << " string(s) in " << found[1]
                               << " word(s)" << (found[2] ? ", more than the batch holds" : "") << "; the host counted " << it->batch.Count() << " in at most "
                               << it->batch.Words() << "." << std::endl;
-                    m_failed = true;
-                    m_spare.emplace_back(it->dev, it->begin);
-                    m_spare.emplace_back(it->dev, it->copied);
-                    m_spare.emplace_back(it->dev, it->done);
-                    it = m_inflight.erase(it);
-                    continue;
+            }
+            if (failed) {
+                m_failed = true;
+            } else {
+                if (m_verbose) {
+                    float ms = 0.f;
+                    vkmr_hip_event_elapsed_ms(it->dev, it->ev.begin.get(), it->ev.done.get(), &ms);
+                    std::cout << "Mapping for slice #" << it->sub.Number() << " (" << it->sub.Reserved() << " item(s); "
+                              << it->batch.Size() << " byte(s)) finished in " << ms << "ms." << std::endl;
                 }
+                out.push_back(std::move(it->sub));
             }
-            if (m_verbose) {
-                float ms = 0.f;
-                vkmr_hip_event_elapsed_ms(it->dev, it->begin, it->done, &ms);
-                std::cout << "Mapping for slice #" << it->sub.Number() << " (" << it->sub.Reserved() << " item(s); "
-                          << it->batch.Size() << " byte(s)) finished in " << ms << "ms." << std::endl;
-            }
-            m_spare.emplace_back(it->dev, it->begin);
-            m_spare.emplace_back(it->dev, it->copied);
-            m_spare.emplace_back(it->dev, it->done);
-            out.push_back(std::move(it->sub));
-            it = m_inflight.erase(it);   // the batch goes back to its pool here
+            m_spare.push_back(std::move(it->ev));   // keep the events for the next mapping
+            it = m_inflight.erase(it);              // the batch goes back to its pool here
         }
         return out;
     }
@@ -168,7 +153,7 @@ private:
     bool m_send_sizes;   // describe a batch to the device by its 16-bit sizes when they suffice (HipConfig::send_sizes)
     bool m_failed = false;
     std::vector<Mapping> m_inflight;
-    std::vector<std::pair<int, vkmr_event>> m_spare;
+    std::vector<Events> m_spare;
 };
 
 }  // namespace

@@ -14,9 +14,6 @@
 
 namespace vkmr {
 
-// Status of the last failed ABI call, in the role VkResult has in the reference.
-typedef vkmr_status HipResult;
-
 // Maps input batches into (sub-)slices of device memory.
 class Mappings {
 public:

@@ -16,8 +16,8 @@ namespace {
 
 // What one reduction in flight needs besides its slice; recycled through PerDevice::spare.
 struct Resources {
-    void* scratch = nullptr;
-    vkmr_event begin = nullptr, done = nullptr;
+    DeviceMem scratch;
+    EventHandle begin, done;
 };
 
 struct Reduction {
@@ -30,8 +30,10 @@ struct Reduction {
 struct PerDevice {
     int dev = -1;
     vkmr_stream stream = nullptr;        // the stream of this device's reductions (as given to Reduce)
-    vkmr_digest* roots_dev = nullptr;    // HBM: root of the device's j-th slice at [j]
-    vkmr_digest* roots_host = nullptr;   // pinned mirror
+    DeviceMem roots_dev;                 // HBM: root of the device's j-th slice at [j]
+    PinnedMem roots_host;                // pinned mirror
+    vkmr_digest* RootsDev() const { return roots_dev.as<vkmr_digest>(); }
+    vkmr_digest* RootsHost() const { return roots_host.as<vkmr_digest>(); }
     uint32_t roots_cap = 0, roots_used = 0;
     std::vector<Resources> spare;
 };
@@ -42,9 +44,8 @@ public:
         : m_capacity(capacity), m_scratch_bytes(vkmr_hip_reduce_scratch_bytes(capacity)), m_verbose(verbose)
     {
         for (int d : devices) {
-            PerDevice pd;
-            pd.dev = d;
-            m_devs.push_back(pd);
+            m_devs.emplace_back();
+            m_devs.back().dev = d;
         }
         // What every device needs for its first reduction is taken now, before slices and batches fill HBM:
         // the root array and one scratch + event set.  Later reductions re-use that set (or wait for it), so
@@ -58,25 +59,18 @@ public:
                 m_failed = true;
                 break;
             }
-            m_devs[di].spare.push_back(r);
+            m_devs[di].spare.push_back(std::move(r));
         }
     }
 
     ~ReductionsImpl() override
     {
         for (auto& r : m_inflight) {
-            vkmr_hip_event_wait(m_devs[r.device_index].dev, r.res.done);
-            m_devs[r.device_index].spare.push_back(r.res);
+            vkmr_hip_event_wait(m_devs[r.device_index].dev, r.res.done.get());
+            m_devs[r.device_index].spare.push_back(std::move(r.res));
         }
         m_inflight.clear();   // slices go back to their pool
-        for (auto& d : m_devs) {
-            for (auto& res : d.spare) FreeResources(d.dev, res);
-            vkmr_hip_device_free(d.dev, d.roots_dev);
-            vkmr_hip_host_free(d.roots_host);
-        }
         if (m_comm) vkmr_hip_comm_destroy(m_comm);
-        for (auto& pd : m_proof_dev) vkmr_hip_device_free(pd.first, pd.second);
-        vkmr_hip_host_free(m_proof_host);
     }
 
     HipResult Reduce(slice_type&& slice, uint32_t height, vkmr_stream stream) override
@@ -148,7 +142,7 @@ public:
         }
         if (m_dispatched == 1) {   // Reductions.cpp:692-701
             FinishProof(nullptr, 0);
-            return digest_words_to_hex(m_devs[0].roots_host[0].data);
+            return digest_words_to_hex(m_devs[0].RootsHost()[0].data);
         }
         vkmr_digest top;
         if (Combine(&top) != VKMR_OK) {
@@ -159,14 +153,6 @@ public:
     }
 
 private:
-    void FreeResources(int dev, Resources& r)
-    {
-        vkmr_hip_device_free(dev, r.scratch);
-        vkmr_hip_event_destroy(dev, r.begin);
-        vkmr_hip_event_destroy(dev, r.done);
-        r = Resources();
-    }
-
     // Scratch + events for one more reduction on device `di`: recycled, freshly allocated, or --
     // when HBM has no room -- taken over from the oldest reduction once it has retired.
     HipResult Acquire(size_t di, Resources* out)
@@ -174,7 +160,7 @@ private:
         PerDevice& d = m_devs[di];
         for (;;) {
             if (!d.spare.empty()) {
-                *out = d.spare.back();
+                *out = std::move(d.spare.back());
                 d.spare.pop_back();
                 return VKMR_OK;
             }
@@ -185,12 +171,7 @@ private:
                 WaitOne();
                 continue;
             }
-            Resources r;
-            const HipResult st = NewResources(d.dev, &r);
-            if (st == VKMR_OK) {
-                *out = r;
-                return VKMR_OK;
-            }
+            const HipResult st = NewResources(d.dev, out);
             if (st != VKMR_ERR_OOM || !WaitOne()) return st;   // with a set reserved per device, there is always one to wait for
         }
     }
@@ -198,15 +179,12 @@ private:
     HipResult NewResources(int dev, Resources* out)
     {
         Resources r;
-        HipResult st = vkmr_hip_device_alloc(dev, m_scratch_bytes, &r.scratch);
-        if (st == VKMR_OK) st = vkmr_hip_event_create(dev, &r.begin);
-        if (st == VKMR_OK) st = vkmr_hip_event_create(dev, &r.done);
-        if (st != VKMR_OK) {
-            FreeResources(dev, r);
-            return st;
-        }
+        HipResult st = DeviceMem::Alloc(dev, m_scratch_bytes, &r.scratch);
+        if (st == VKMR_OK) st = EventHandle::Create(dev, &r.begin);
+        if (st == VKMR_OK) st = EventHandle::Create(dev, &r.done);
+        if (st != VKMR_OK) return st;
         ++m_allocations;
-        *out = r;
+        *out = std::move(r);
         return VKMR_OK;
     }
 
@@ -218,23 +196,19 @@ private:
         if (slot < d.roots_cap) return VKMR_OK;
         uint32_t cap = d.roots_cap ? d.roots_cap : 4096u;
         while (cap <= slot) cap *= 2u;
-        void *nd = nullptr, *nh = nullptr;
-        HipResult st = vkmr_hip_device_alloc(d.dev, (size_t)cap * sizeof(vkmr_digest), &nd);
-        if (st == VKMR_OK) st = vkmr_hip_host_alloc((size_t)cap * sizeof(vkmr_digest), &nh);
-        if (st != VKMR_OK) {
-            vkmr_hip_device_free(d.dev, nd);
-            return st;
-        }
+        DeviceMem nd;
+        PinnedMem nh;
+        HipResult st = DeviceMem::Alloc(d.dev, (size_t)cap * sizeof(vkmr_digest), &nd);
+        if (st == VKMR_OK) st = PinnedMem::Alloc((size_t)cap * sizeof(vkmr_digest), &nh);
+        if (st != VKMR_OK) return st;
         if (d.roots_cap) {
             while (std::any_of(m_inflight.begin(), m_inflight.end(), [&](const Reduction& r) { return r.device_index == di; })) WaitOne();
-            std::memcpy(nh, d.roots_host, (size_t)d.roots_cap * sizeof(vkmr_digest));
-            st = vkmr_hip_memcpy_h2d_async(d.dev, d.stream, nd, nh, (size_t)d.roots_cap * sizeof(vkmr_digest));
+            std::memcpy(nh.get(), d.roots_host.get(), (size_t)d.roots_cap * sizeof(vkmr_digest));
+            st = vkmr_hip_memcpy_h2d_async(d.dev, d.stream, nd.get(), nh.get(), (size_t)d.roots_cap * sizeof(vkmr_digest));
             if (st == VKMR_OK) st = vkmr_hip_stream_sync(d.dev, d.stream);
-            vkmr_hip_device_free(d.dev, d.roots_dev);
-            vkmr_hip_host_free(d.roots_host);
         }
-        d.roots_dev = static_cast<vkmr_digest*>(nd);
-        d.roots_host = static_cast<vkmr_digest*>(nh);
+        std::swap(d.roots_dev, nd);   // the old arrays are freed on the way out
+        std::swap(d.roots_host, nh);
         d.roots_cap = cap;
         return st;
     }
@@ -258,23 +232,19 @@ private:
             offsets.push_back(r.offset);
         }
         if (here.empty()) return vkmr_hip_reduce_async(d.dev, stream, slice.Cells(), slice.Count(), height, scratch, root_dev);
-        void* sib = nullptr;
-        HipResult st = vkmr_hip_device_alloc(d.dev, (here.size() * (size_t)height + 1) * sizeof(vkmr_digest), &sib);
-        if (st == VKMR_OK) m_proof_dev.push_back(std::make_pair(d.dev, sib));
-        if (st == VKMR_OK && !m_proof_host) {
-            void* h = nullptr;
-            st = vkmr_hip_host_alloc(kMaxProofs * kProofRecord * sizeof(vkmr_digest), &h);   // per proof one record: the leaf + its siblings inside the slice (those above arrive in Combine's own buffer)
-            m_proof_host = static_cast<vkmr_digest*>(h);
-        }
+        m_proof_dev.emplace_back();   // kept until the object goes: the copies below are asynchronous
+        HipResult st = DeviceMem::Alloc(d.dev, (here.size() * (size_t)height + 1) * sizeof(vkmr_digest), &m_proof_dev.back());
+        vkmr_digest* const sib = m_proof_dev.back().as<vkmr_digest>();
+        if (st == VKMR_OK && !m_proof_host)   // per proof one record: the leaf + its siblings inside the slice (those above arrive in Combine's own buffer)
+            st = PinnedMem::Alloc(kMaxProofs * kProofRecord * sizeof(vkmr_digest), &m_proof_host);
+        vkmr_digest* const proof_host = m_proof_host.as<vkmr_digest>();
         if (st == VKMR_OK)
-            st = vkmr_hip_reduce_proofs_async(d.dev, stream, slice.Cells(), slice.Count(), height, scratch, root_dev, offsets.data(), (uint32_t)offsets.size(),
-                                              static_cast<vkmr_digest*>(sib));
+            st = vkmr_hip_reduce_proofs_async(d.dev, stream, slice.Cells(), slice.Count(), height, scratch, root_dev, offsets.data(), (uint32_t)offsets.size(), sib);
         for (size_t q = 0; q < here.size() && st == VKMR_OK; ++q) {
             ProofReq& r = *here[q];
-            st = vkmr_hip_memcpy_d2h_async(d.dev, stream, m_proof_host + r.host_at, slice.Cells() + r.offset, sizeof(vkmr_digest));
+            st = vkmr_hip_memcpy_d2h_async(d.dev, stream, proof_host + r.host_at, slice.Cells() + r.offset, sizeof(vkmr_digest));
             if (st == VKMR_OK && height)
-                st = vkmr_hip_memcpy_d2h_async(d.dev, stream, m_proof_host + r.host_at + 1, static_cast<vkmr_digest*>(sib) + q * (size_t)height,
-                                               (size_t)height * sizeof(vkmr_digest));
+                st = vkmr_hip_memcpy_d2h_async(d.dev, stream, proof_host + r.host_at + 1, sib + q * (size_t)height, (size_t)height * sizeof(vkmr_digest));
             r.dispatched = (st == VKMR_OK);
         }
         return st;
@@ -303,12 +273,12 @@ private:
         HipResult st = EnsureRoots(di, r.slot);
         if (st == VKMR_OK) st = Acquire(di, &r.res);
         if (st != VKMR_OK) return st;
-        st = vkmr_hip_event_record(d.dev, r.res.begin, stream);
-        if (st == VKMR_OK) st = ReduceAndProve(d, slice, height, r.res.scratch, stream, d.roots_dev + r.slot);
-        if (st == VKMR_OK) st = vkmr_hip_memcpy_d2h_async(d.dev, stream, d.roots_host + r.slot, d.roots_dev + r.slot, sizeof(vkmr_digest));
-        if (st == VKMR_OK) st = vkmr_hip_event_record(d.dev, r.res.done, stream);
+        st = vkmr_hip_event_record(d.dev, r.res.begin.get(), stream);
+        if (st == VKMR_OK) st = ReduceAndProve(d, slice, height, r.res.scratch.get(), stream, d.RootsDev() + r.slot);
+        if (st == VKMR_OK) st = vkmr_hip_memcpy_d2h_async(d.dev, stream, d.RootsHost() + r.slot, d.RootsDev() + r.slot, sizeof(vkmr_digest));
+        if (st == VKMR_OK) st = vkmr_hip_event_record(d.dev, r.res.done.get(), stream);
         if (st != VKMR_OK) {
-            d.spare.push_back(r.res);
+            d.spare.push_back(std::move(r.res));
             return st;
         }
         if (r.slot + 1 > d.roots_used) d.roots_used = r.slot + 1;
@@ -324,8 +294,8 @@ private:
     {
         for (auto it = m_inflight.begin(); it != m_inflight.end();) {
             PerDevice& d = m_devs[it->device_index];
-            HipResult st = vkmr_hip_event_query(d.dev, it->res.done);
-            if (st == VKMR_NOT_READY && block && m_inflight.size() > keep) st = vkmr_hip_event_wait(d.dev, it->res.done);
+            HipResult st = vkmr_hip_event_query(d.dev, it->res.done.get());
+            if (st == VKMR_NOT_READY && block && m_inflight.size() > keep) st = vkmr_hip_event_wait(d.dev, it->res.done.get());
             if (st == VKMR_NOT_READY) {
                 ++it;
                 continue;
@@ -337,12 +307,12 @@ private:
                 ++m_retired;
                 if (m_verbose) {
                     float ms = 0.f;
-                    vkmr_hip_event_elapsed_ms(d.dev, it->res.begin, it->res.done, &ms);
+                    vkmr_hip_event_elapsed_ms(d.dev, it->res.begin.get(), it->res.done.get(), &ms);
                     std::cout << "Reduction #" << it->slice.Number() << " finished in " << ms << "ms." << std::endl;
-                    std::cout << "#" << it->slice.Number() << ":" << digest_words_to_hex(d.roots_host[it->slot].data) << std::endl;
+                    std::cout << "#" << it->slice.Number() << ":" << digest_words_to_hex(d.RootsHost()[it->slot].data) << std::endl;
                 }
             }
-            d.spare.push_back(it->res);
+            d.spare.push_back(std::move(it->res));
             it = m_inflight.erase(it);   // the slice's memory returns to its pool here
         }
     }
@@ -352,11 +322,12 @@ private:
     void FinishProof(const vkmr_digest* upper, uint32_t upper_levels)
     {
         if (!m_proof_host || m_failed) return;
+        const vkmr_digest* const proof_host = m_proof_host.as<vkmr_digest>();
         size_t nth = 0;
         for (ProofReq& r : m_proofs) {
             if (!r.dispatched) continue;
-            r.leaf_digest = m_proof_host[r.host_at];
-            r.path.assign(m_proof_host + r.host_at + 1, m_proof_host + r.host_at + 1 + r.slice_levels);
+            r.leaf_digest = proof_host[r.host_at];
+            r.path.assign(proof_host + r.host_at + 1, proof_host + r.host_at + 1 + r.slice_levels);
             for (uint32_t l = 0; l < upper_levels; ++l) r.path.push_back(upper[nth * upper_levels + l]);
             r.done = true;
             ++nth;
@@ -366,13 +337,24 @@ private:
     // Root over all slice roots, in slice order, on the first device.
     HipResult Combine(vkmr_digest* top)
     {
+        std::vector<StreamHandle> own(m_devs.size());   // of the devices that got no slice: lent to PerDevice::stream meanwhile
+        const HipResult st = CombineOn(top, own);
+        for (size_t i = 0; i < own.size(); ++i)
+            if (own[i]) m_devs[i].stream = nullptr;
+        return st;
+    }
+
+    // Its temporaries are released when it returns, at the first failure too.
+    HipResult CombineOn(vkmr_digest* top, std::vector<StreamHandle>& own_streams)
+    {
         const uint32_t total = m_dispatched;
         const size_t ndev = m_devs.size();
         PerDevice& d0 = m_devs[0];
-        void *ordered = nullptr, *scratch = nullptr, *final_dev = nullptr, *final_host = nullptr;
-        std::vector<void*> gathered(ndev, nullptr);
+        DeviceMem ordered, scratch, final_dev, up_sib;
+        PinnedMem final_host, upper_host;
+        std::vector<DeviceMem> gathered(ndev);
         HipResult st = VKMR_OK;
-        const vkmr_digest* roots = d0.roots_dev;
+        const vkmr_digest* roots = d0.RootsDev();
         if (ndev > 1) {
             // ONE all-gather of the per-device root arrays over RCCL, then slice order on device 0
             uint32_t per_rank = 0;
@@ -383,73 +365,56 @@ private:
             if (!m_comm) {
                 std::vector<int> ids;
                 for (const auto& d : m_devs) ids.push_back(d.dev);
-                st = vkmr_hip_comm_init_all(ids.data(), (int)ids.size(), &m_comm);
+                if ((st = vkmr_hip_comm_init_all(ids.data(), (int)ids.size(), &m_comm)) != VKMR_OK) return st;
             }
-            for (size_t i = 0; i < ndev && st == VKMR_OK; ++i) {
+            for (size_t i = 0; i < ndev; ++i) {
                 PerDevice& d = m_devs[i];
                 if (!d.stream) {   // a device that got no slice still takes part in the collective
-                    st = vkmr_hip_stream_create(d.dev, &d.stream);
-                    m_own_streams.push_back(i);
+                    if ((st = StreamHandle::Create(d.dev, &own_streams[i])) != VKMR_OK) return st;
+                    d.stream = own_streams[i].get();
                 }
-                if (st == VKMR_OK) st = EnsureRoots(i, per_rank - 1);   // every rank sends per_rank cells
-                if (st == VKMR_OK) st = vkmr_hip_device_alloc(d.dev, ndev * (size_t)per_rank * sizeof(vkmr_digest), &gathered[i]);
+                if ((st = EnsureRoots(i, per_rank - 1)) != VKMR_OK) return st;   // every rank sends per_rank cells
+                if ((st = DeviceMem::Alloc(d.dev, ndev * (size_t)per_rank * sizeof(vkmr_digest), &gathered[i])) != VKMR_OK) return st;
                 streams.push_back(d.stream);
-                mine.push_back(d.roots_dev);
-                all.push_back(static_cast<vkmr_digest*>(gathered[i]));
+                mine.push_back(d.RootsDev());
+                all.push_back(gathered[i].as<vkmr_digest>());
             }
-            if (st == VKMR_OK) st = vkmr_hip_gather_roots_async(m_comm, streams.data(), mine.data(), per_rank, all.data());
-            if (st == VKMR_OK) st = vkmr_hip_device_alloc(d0.dev, (size_t)total * sizeof(vkmr_digest), &ordered);
-            if (st == VKMR_OK)
-                st = vkmr_hip_roots_in_slice_order_async(d0.dev, d0.stream, all[0], (uint32_t)ndev, per_rank, total, static_cast<vkmr_digest*>(ordered));
-            roots = static_cast<const vkmr_digest*>(ordered);
+            if ((st = vkmr_hip_gather_roots_async(m_comm, streams.data(), mine.data(), per_rank, all.data())) != VKMR_OK) return st;
+            if ((st = DeviceMem::Alloc(d0.dev, (size_t)total * sizeof(vkmr_digest), &ordered)) != VKMR_OK) return st;
+            st = vkmr_hip_roots_in_slice_order_async(d0.dev, d0.stream, all[0], (uint32_t)ndev, per_rank, total, ordered.as<vkmr_digest>());
+            if (st != VKMR_OK) return st;
+            roots = ordered.as<vkmr_digest>();
         }
-        if (st == VKMR_OK) st = vkmr_hip_device_alloc(d0.dev, vkmr_hip_reduce_scratch_bytes(total), &scratch);
-        if (st == VKMR_OK) st = vkmr_hip_device_alloc(d0.dev, sizeof(vkmr_digest), &final_dev);
-        if (st == VKMR_OK) st = vkmr_hip_host_alloc(sizeof(vkmr_digest), &final_host);
+        if ((st = DeviceMem::Alloc(d0.dev, vkmr_hip_reduce_scratch_bytes(total), &scratch)) != VKMR_OK) return st;
+        if ((st = DeviceMem::Alloc(d0.dev, sizeof(vkmr_digest), &final_dev)) != VKMR_OK) return st;
+        if ((st = PinnedMem::Alloc(sizeof(vkmr_digest), &final_host)) != VKMR_OK) return st;
         // the proofs' upper parts: the paths of the leaves' slices among the slice roots -- written by the combine itself
         // (same tree, same launches)
-        void* up_sib = nullptr;
         uint32_t up_levels = 0;
         std::vector<uint64_t> positions;
         for (const ProofReq& r : m_proofs)
             if (r.dispatched) positions.push_back((uint64_t)r.slice_number - 1);
-        vkmr_digest* upper_host = nullptr;
-        if (st == VKMR_OK && !positions.empty()) {
+        if (!positions.empty()) {
             up_levels = 1;
             while (((uint64_t)total + ((1ull << up_levels) - 1ull)) >> up_levels > 1) ++up_levels;
-            st = vkmr_hip_device_alloc(d0.dev, positions.size() * (size_t)up_levels * sizeof(vkmr_digest), &up_sib);
-            if (st == VKMR_OK)
-                st = vkmr_hip_reduce_proofs_async(d0.dev, d0.stream, roots, total, up_levels, scratch, static_cast<vkmr_digest*>(final_dev), positions.data(),
-                                                  (uint32_t)positions.size(), static_cast<vkmr_digest*>(up_sib));
-            if (st == VKMR_OK) {
-                void* h = nullptr;
-                st = vkmr_hip_host_alloc(positions.size() * (size_t)up_levels * sizeof(vkmr_digest), &h);
-                upper_host = static_cast<vkmr_digest*>(h);
-            }
-            if (st == VKMR_OK)
-                st = vkmr_hip_memcpy_d2h_async(d0.dev, d0.stream, upper_host, up_sib, positions.size() * (size_t)up_levels * sizeof(vkmr_digest));
-        } else if (st == VKMR_OK) {
-            st = vkmr_hip_combine_async(d0.dev, d0.stream, roots, total, scratch, static_cast<vkmr_digest*>(final_dev));
+            const size_t up_bytes = positions.size() * (size_t)up_levels * sizeof(vkmr_digest);
+            if ((st = DeviceMem::Alloc(d0.dev, up_bytes, &up_sib)) != VKMR_OK) return st;
+            st = vkmr_hip_reduce_proofs_async(d0.dev, d0.stream, roots, total, up_levels, scratch.get(), final_dev.as<vkmr_digest>(), positions.data(),
+                                              (uint32_t)positions.size(), up_sib.as<vkmr_digest>());
+            if (st != VKMR_OK) return st;
+            if ((st = PinnedMem::Alloc(up_bytes, &upper_host)) != VKMR_OK) return st;
+            st = vkmr_hip_memcpy_d2h_async(d0.dev, d0.stream, upper_host.get(), up_sib.get(), up_bytes);
+        } else {
+            st = vkmr_hip_combine_async(d0.dev, d0.stream, roots, total, scratch.get(), final_dev.as<vkmr_digest>());
         }
-        if (st == VKMR_OK) st = vkmr_hip_memcpy_d2h_async(d0.dev, d0.stream, final_host, final_dev, sizeof(vkmr_digest));
-        if (st == VKMR_OK) st = vkmr_hip_stream_sync(d0.dev, d0.stream);
-        for (size_t i = 1; i < ndev && st == VKMR_OK; ++i)   // the other ranks' side of the gather
-            if (m_devs[i].stream && gathered[i]) st = vkmr_hip_stream_sync(m_devs[i].dev, m_devs[i].stream);
-        if (st == VKMR_OK) std::memcpy(top, final_host, sizeof(vkmr_digest));
-        if (st == VKMR_OK) FinishProof(upper_host, up_levels);
-        vkmr_hip_host_free(upper_host);
-        vkmr_hip_device_free(d0.dev, up_sib);
-        for (size_t i = 0; i < ndev; ++i) vkmr_hip_device_free(m_devs[i].dev, gathered[i]);
-        vkmr_hip_device_free(d0.dev, ordered);
-        vkmr_hip_device_free(d0.dev, scratch);
-        vkmr_hip_device_free(d0.dev, final_dev);
-        vkmr_hip_host_free(final_host);
-        for (size_t i : m_own_streams) {
-            vkmr_hip_stream_destroy(m_devs[i].dev, m_devs[i].stream);
-            m_devs[i].stream = nullptr;
-        }
-        m_own_streams.clear();
-        return st;
+        if (st != VKMR_OK) return st;
+        if ((st = vkmr_hip_memcpy_d2h_async(d0.dev, d0.stream, final_host.get(), final_dev.get(), sizeof(vkmr_digest))) != VKMR_OK) return st;
+        if ((st = vkmr_hip_stream_sync(d0.dev, d0.stream)) != VKMR_OK) return st;
+        for (size_t i = 1; i < ndev; ++i)   // the other ranks' side of the gather
+            if (m_devs[i].stream && gathered[i] && (st = vkmr_hip_stream_sync(m_devs[i].dev, m_devs[i].stream)) != VKMR_OK) return st;
+        std::memcpy(top, final_host.get(), sizeof(vkmr_digest));
+        FinishProof(upper_host.as<vkmr_digest>(), up_levels);
+        return VKMR_OK;
     }
 
     size_t m_capacity, m_scratch_bytes, m_allocations = 0;
@@ -458,7 +423,6 @@ private:
     uint32_t m_dispatched = 0, m_retired = 0, m_last_number = 0;
     std::vector<PerDevice> m_devs;
     std::vector<Reduction> m_inflight;
-    std::vector<size_t> m_own_streams;
     vkmr_comm m_comm = nullptr;
     // the requested Merkle proofs
     static constexpr size_t kMaxProofs = 16;      // what one reduction writes in its pass (vkmr_hip_reduce_proofs_async)
@@ -472,8 +436,8 @@ private:
         std::vector<vkmr_digest> path;
     };
     std::vector<ProofReq> m_proofs;
-    vkmr_digest* m_proof_host = nullptr;          // pinned: per proof the leaf digest and the siblings inside its slice
-    std::vector<std::pair<int, void*>> m_proof_dev;   // device sibling arrays (device, pointer), freed with the object
+    PinnedMem m_proof_host;                       // pinned: per proof the leaf digest and the siblings inside its slice
+    std::vector<DeviceMem> m_proof_dev;           // device sibling arrays, freed with the object
 };
 
 }  // namespace

@@ -5,17 +5,11 @@
 
 namespace vkmr {
 
-SlicePool::~SlicePool()
-{
-    for (auto& d : m_devs)
-        for (vkmr_digest* p : d.free) vkmr_hip_device_free(d.dev, p);
-}
-
 SlicePool::PerDevice& SlicePool::Dev(int dev)
 {
     for (auto& d : m_devs)
         if (d.dev == dev) return d;
-    m_devs.push_back({dev, 0, {}});
+    m_devs.push_back(PerDevice{dev, 0, {}});
     return m_devs.back();
 }
 
@@ -26,41 +20,41 @@ size_t SlicePool::Resident(int dev) const
     return 0;
 }
 
-vkmr_digest* SlicePool::Acquire(int dev, bool* budget_hit)
+DeviceMem SlicePool::Acquire(int dev, bool* budget_hit)
 {
     PerDevice& d = Dev(dev);
+    DeviceMem p;
     if (budget_hit) *budget_hit = false;
     if (!d.free.empty()) {
-        vkmr_digest* p = d.free.back();
+        p = std::move(d.free.back());
         d.free.pop_back();
         ++d.resident;
         return p;
     }
     if (m_budget && d.resident >= m_budget) {
         if (budget_hit) *budget_hit = true;
-        return nullptr;
+        return p;
     }
-    void* p = nullptr;
     std::cout << "Looking for " << m_capacity * sizeof(vkmr_digest) << " bytes of sliced memory.." << std::endl;
-    if (vkmr_hip_device_alloc(dev, m_capacity * sizeof(vkmr_digest), &p) != VKMR_OK) return nullptr;
+    if (DeviceMem::Alloc(dev, m_capacity * sizeof(vkmr_digest), &p) != VKMR_OK) return p;
     ++m_allocations;
     ++d.resident;
-    return static_cast<vkmr_digest*>(p);
+    return p;
 }
 
-void SlicePool::Release(int dev, vkmr_digest* cells)
+void SlicePool::Release(DeviceMem&& cells)
 {
-    PerDevice& d = Dev(dev);
-    d.free.push_back(cells);
+    PerDevice& d = Dev(cells.device());
+    d.free.push_back(std::move(cells));
     if (d.resident) --d.resident;
 }
 
 Slice::Slice(std::shared_ptr<SlicePool> pool, int dev, number_type number, size_type capacity, bool* budget_hit)
     : m_dev(dev), m_capacity(capacity), m_number(number)
 {
-    m_cells = pool->Acquire(dev, budget_hit);
+    m_memory = pool->Acquire(dev, budget_hit);
+    m_cells = m_memory.as<vkmr_digest>();
     if (m_cells) {
-        m_owns = true;
         m_pool = std::move(pool);
     } else {
         m_capacity = 0;
@@ -73,10 +67,10 @@ Slice& Slice::operator=(Slice&& o) noexcept
 {
     if (this != &o) {
         Release();
-        m_dev = o.m_dev; m_cells = o.m_cells; m_owns = o.m_owns; m_pool = std::move(o.m_pool);
+        m_dev = o.m_dev; m_cells = o.m_cells; m_memory = std::move(o.m_memory); m_pool = std::move(o.m_pool);
         m_capacity = o.m_capacity; m_sliced = o.m_sliced; m_reserved = o.m_reserved; m_filled = o.m_filled;
         m_number = o.m_number;
-        o.m_cells = nullptr; o.m_owns = false;
+        o.m_cells = nullptr;
         o.m_capacity = o.m_sliced = o.m_reserved = o.m_filled = 0; o.m_number = 0;
     }
     return *this;
@@ -84,9 +78,8 @@ Slice& Slice::operator=(Slice&& o) noexcept
 
 void Slice::Release()
 {
-    if (m_owns && m_cells && m_pool) m_pool->Release(m_dev, m_cells);   // kept for the next slice of this device
+    if (m_memory && m_pool) m_pool->Release(std::move(m_memory));   // kept for the next slice of this device
     m_cells = nullptr;
-    m_owns = false;
     m_pool.reset();
 }
 
@@ -96,7 +89,6 @@ Slice Slice::Sub()
     if (m_reserved > 0 && m_cells) {
         view.m_dev = m_dev;
         view.m_cells = m_cells + m_sliced;
-        view.m_owns = false;
         view.m_capacity = m_reserved;
         view.m_reserved = m_reserved;
         view.m_number = m_number;

@@ -19,6 +19,7 @@
 #include <utility>
 #include <vector>
 
+#include "hip_handles.hpp"
 #include "vkmr_hip.h"
 
 namespace vkmr {
@@ -28,19 +29,18 @@ namespace vkmr {
 class SlicePool {
 public:
     SlicePool(size_t capacity_cells, size_t budget_per_device) : m_capacity(capacity_cells), m_budget(budget_per_device) {}
-    ~SlicePool();
     SlicePool(const SlicePool&) = delete;
     SlicePool& operator=(const SlicePool&) = delete;
 
     // A digest array of the pool's capacity on `dev`: a retired one when there is one, otherwise
-    // freshly allocated; nullptr when the budget is used up or HBM is (`*budget_hit` tells which).
-    vkmr_digest* Acquire(int dev, bool* budget_hit);
-    void Release(int dev, vkmr_digest* cells);
+    // freshly allocated; empty when the budget is used up or HBM is (`*budget_hit` tells which).
+    DeviceMem Acquire(int dev, bool* budget_hit);
+    void Release(DeviceMem&& cells);
     size_t Resident(int dev) const;
     size_t Allocations() const { return m_allocations; }
 
 private:
-    struct PerDevice { int dev; size_t resident; std::vector<vkmr_digest*> free; };
+    struct PerDevice { int dev; size_t resident; std::vector<DeviceMem> free; };
     PerDevice& Dev(int dev);
     size_t m_capacity, m_budget, m_allocations = 0;
     std::vector<PerDevice> m_devs;
@@ -94,8 +94,8 @@ private:
     void Release();
 
     int m_dev = -1;
-    vkmr_digest* m_cells = nullptr;
-    bool m_owns = false;
+    vkmr_digest* m_cells = nullptr;      // a view: of m_memory, or (a sub-slice) of its parent's at an offset
+    DeviceMem m_memory;                  // an owning slice's array, on loan from m_pool
     std::shared_ptr<SlicePool> m_pool;   // where an owning slice returns its memory
     size_type m_capacity = 0, m_sliced = 0, m_reserved = 0, m_filled = 0;
     number_type m_number = 0;
