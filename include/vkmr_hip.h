@@ -430,6 +430,32 @@ VKMR_API vkmr_status vkmr_hip_verify_forest_proofs_async(int dev, vkmr_stream s,
                                                          uint32_t ntrees, uint32_t* ok_dev);
 
 /*
+ * LEAF UPDATES OF THE STORED FOREST: vkmr_hip_tree_update_async for a forest.  digests_dev, forest_dev and roots_dev as
+ * written by vkmr_hip_reduce_forest_tree_async; the call TRUSTS that offsets_dev, total, ntrees and max_count are those of
+ * that build and that the build reported status 0 (the rule of vkmr_hip_forest_proofs_async).  Entry q sets leaf
+ * indices_dev[q] (its index inside its tree) of tree trees_dev[q] to leaves_dev[q]; all three arrays live in DEVICE memory,
+ * and the (tree, index) pairs are strictly increasing in lexicographic order with index < c_t.  Every ancestor of an
+ * updated leaf is rehashed once, in its tree's own cells: sum over l >= 1 of the distinct (tree, index >> l) pairs with
+ * l <= h_t node hashes, and the root of every touched tree is written to roots_dev[t].
+ *   status_dev  one uint32_t in device memory, always written: 0 when the update was applied; bit 0 set if a tree was
+ *               >= ntrees or an index >= c_t (so for every entry into an empty tree), bit 1 if the pairs were not strictly
+ *               increasing (out of order or repeated).  When it is nonzero NOTHING of the caller's has changed: no leaf,
+ *               no cell of forest_dev, no root.
+ * After status 0 every cell of the leaves, of forest_dev and of roots_dev equals what a fresh
+ * vkmr_hip_reduce_forest_tree_async over the updated leaves writes; cells that a build never writes are not written here
+ * either, nor are the roots of trees no entry names.  Launches, all on the caller's stream: the status word zeroed, the
+ * check, the leaves, then one launch of k lanes per level, H = max(1, ceil(log2 min(max_count, total))) of them; never a
+ * launch per tree, no allocation, no host read of device data.  Refused on the host (VKMR_ERR_INVALID) with k > 0: a NULL
+ * pointer, ntrees == 0 or total == 0, max_count == 0, total > 2^58.  k == 0 does nothing whatever the other arguments.
+ * Stream-ordered: a proof gather or verify enqueued after it on the same stream sees the new forest.
+ */
+VKMR_API vkmr_status vkmr_hip_forest_update_async(int dev, vkmr_stream s, vkmr_digest* digests_dev, vkmr_digest* forest_dev,
+                                                  uint64_t total, const uint64_t* offsets_dev, uint32_t ntrees,
+                                                  uint64_t max_count, const uint32_t* trees_dev, const uint64_t* indices_dev,
+                                                  const vkmr_digest* leaves_dev, uint32_t k, vkmr_digest* roots_dev,
+                                                  uint32_t* status_dev);
+
+/*
  * COMBINE: duplicate-last Merkle root over n >= 1 slice roots given in slice order, always
  * at least one level -- the rule of CpuSha256D::Root that the reference applies to the slice
  * roots on the CPU (CpuSha256DforReductions, src/vkmr/Reductions.cpp:56-69, :703-712).  Here

@@ -11,6 +11,8 @@
 #   e2e [log2...]          `vkmr hip:0 < file` of 2^k strings (default 25 26): printed time and process wall, N runs each, the distribution
 #   frontend               VKMR_TIMING=1 phases, a pipe, hip-api stats and copy/kernel overlap of `vkmr hip:0`
 #   rehearsals             soaks against the oracle; torchrun --nproc 2 (gloo rehearsal; plain N=2 must fail on one GPU); --force-dist (RCCL, one rank)
+#   forestupdate [args]    tools/forest_update_timing.py: leaf updates of a stored forest against a rebuild and against the single tree's
+#                          update (one JSON line), then the same run under rocprofv3 --kernel-trace --stats; stops at the first failing step
 #   cumask                 tools/cu_mask_probe.py: where CU-mask bits land, map/reduce on half the CUs with and without neighbours
 #   issue <set>            tools/issue_patterns (python3 tools/gen_issue_patterns.py <set> and a build beforehand)
 #   proofs                 tools/proof_timing.py: a slice reduced with and without proofs written in the pass
@@ -133,6 +135,15 @@ treeupdate)
   find $OUT/prof_update -name "*kernel_stats.csv" -exec cp {} $OUT/tree_update_kernel_stats.csv \; &&
   cat $OUT/tree_update_kernel_stats.csv
   echo "treeupdate rc=$?"
+  ;;
+forestupdate)
+  timeout -k 10 400 python3 tools/forest_update_timing.py "$@" --out $OUT/forest_update_timing.json > /dev/null 2> $OUT/forest_update_timing.err && echo "forest_update_timing ok" &&
+  cat $OUT/forest_update_timing.json &&
+  repo=$(pwd) &&
+  ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $repo/$OUT/prof_forest_update -- python3 $repo/tools/forest_update_timing.py "$@" > $repo/$OUT/forest_update_prof.json 2> $repo/$OUT/forest_update_prof.err ) &&
+  find $OUT/prof_forest_update -name "*kernel_stats.csv" -exec cp {} $OUT/forest_update_kernel_stats.csv \; &&
+  cat $OUT/forest_update_kernel_stats.csv
+  echo "forestupdate rc=$?"
   ;;
 cumask)
   hipcc --offload-arch=gfx950 -O2 -shared -fPIC -o tools/libwhere.so tools/where.hip

@@ -83,6 +83,8 @@ SIGNATURES = {
                                                C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "vkmr_hip_verify_forest_proofs_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
                                                       C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "vkmr_hip_forest_update_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "vkmr_hip_combine_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "vkmr_hip_comm_init_all": (C.c_int, [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_void_p)]),
     "vkmr_hip_comm_create_id": (C.c_int, [C.c_void_p]),

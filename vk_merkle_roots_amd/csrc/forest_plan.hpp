@@ -60,4 +60,32 @@ inline uint64_t stored_level_base(uint64_t total, uint32_t ntrees, uint32_t l)
 // Cells of the stored forest: levels 1 .. `levels`.
 inline uint64_t stored_cells(uint64_t total, uint32_t ntrees, uint32_t levels) { return stored_level_base(total, ntrees, levels + 1); }
 
+// ---- leaf updates of a stored forest (vkmr_hip_forest_update_async): one step of one entry.  Entry (tree t with offset o
+// and count c, leaf index i < c) at level l >= 1 rehashes parent p = i >> l of tree t's level l from the n_in cells of its
+// level l - 1.  forest_update_level_kernel and the CPU replay in tests/c/forest_update_plan_test.cpp both run this text.
+struct UpdateStep {
+    bool active;        // tree t takes part in level l: l == 1, or its level l - 1 still had two nodes (forest_level_kernel's rule)
+    bool root;          // level l of tree t is one node: it goes to roots[t], not to level l's buffer
+    uint64_t p;         // the parent, a node of tree t's level l
+    uint64_t in_first;  // first cell of tree t's level l - 1: in the leaves for l == 1, else in level l - 1's buffer
+    uint64_t n_in;      // cells of tree t's level l - 1
+    uint64_t out;       // the parent's cell in level l's buffer (unused when root)
+};
+
+VKMR_FOREST_FN UpdateStep update_step(uint64_t o, uint64_t c, uint32_t t, uint64_t i, uint32_t l)
+{
+    UpdateStep s;
+    s.n_in = level_count(c, l - 1u);
+    s.active = c != 0ull && (l == 1u || s.n_in >= 2ull);
+    s.root = level_count(c, l) == 1ull;
+    s.p = i >> l;
+    s.in_first = pos(o, t, l - 1u);
+    s.out = pos(o, t, l) + s.p;
+    return s;
+}
+
+// Entries sorted by (tree, index) put equal parents side by side: entry q is the head of its run at level l, and alone
+// hashes the parent, when the entry in front of it (t0, i0) names another node.
+VKMR_FOREST_FN bool update_same_node(uint32_t t0, uint64_t i0, uint32_t t, uint64_t i, uint32_t l) { return t0 == t && (i0 >> l) == (i >> l); }
+
 }  // namespace vkmr_forest

@@ -14,6 +14,8 @@
 //                                              whole forest, level by level (no reference counterpart); builds the stored forest
 //   forest_tree_kernels.hpp  forest_proofs_kernel          proofs gathered from the stored forest, one lane per (query, level)
 //                            verify_forest_proofs_kernel   batch verification of proofs of unequal height, one lane per proof
+//   forest_update_kernels.hpp  forest_update_*_kernel   leaf updates of the stored forest: check, store the leaves, rehash the
+//                                              dirty nodes of every touched tree level by level
 //   sha256d_device.hpp  the SHA-256 round / compression building blocks, and the tree's: hash_parent, node_diff, store_node
 //   merkle_math.hpp     the integer rules, no HIP types (ceil_shift, height, right_child, sibling): shared with host/ and tests/c
 //   meta_kernels.hpp    sizes_*_kernel         metadata entries from 16-bit sizes   (Batches.cpp:64-121)
@@ -44,6 +46,7 @@ using vkmr_dev::Node;
 #include "tree_kernels.hpp"
 #include "forest_kernels.hpp"
 #include "forest_tree_kernels.hpp"
+#include "forest_update_kernels.hpp"
 
 // ============================================================================
 // C ABI
@@ -1087,6 +1090,41 @@ vkmr_status vkmr_hip_verify_forest_proofs_async(int dev, vkmr_stream s, const vk
     hipLaunchKernelGGL(verify_forest_proofs_kernel, grid, dim3(256), 0, S(s), nodes(leaves_dev), trees_dev, indices_dev,
                        nodes(siblings_dev), heights_dev, k, stride, nodes(roots_dev), ntrees, ok_dev);
     VKMR_TRY(hipGetLastError());
+    return VKMR_OK;
+}
+
+// ---- leaf updates of the stored forest (forest_update_kernels.hpp) ---------------------------------------------------------
+
+vkmr_status vkmr_hip_forest_update_async(int dev, vkmr_stream s, vkmr_digest* digests_dev, vkmr_digest* forest_dev, uint64_t total,
+                                         const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count, const uint32_t* trees_dev,
+                                         const uint64_t* indices_dev, const vkmr_digest* leaves_dev, uint32_t k, vkmr_digest* roots_dev,
+                                         uint32_t* status_dev)
+{
+    if (k == 0) return VKMR_OK;
+    if (!digests_dev || !forest_dev || !offsets_dev || !trees_dev || !indices_dev || !leaves_dev || !roots_dev || !status_dev)
+        return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_update_async: null pointer");
+    if (ntrees == 0 || total == 0) return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_update_async: a forest without a leaf has none to update");
+    if (max_count == 0) return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_update_async: max_count must be at least 1");
+    if (total > (1ull << 58)) return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_update_async: forest too large");
+    if (grid_too_large(groups_of(k))) return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_update_async: too many entries in one call");
+    const uint32_t H = vkmr_forest::launches(total, max_count);   // <= 58
+    const dim3 grid = grid_of(k);
+    Node* digests = nodes(digests_dev);
+    Node* forest = nodes(forest_dev);
+    Node* roots = nodes(roots_dev);
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_TRY(hipMemsetAsync(status_dev, 0, sizeof(uint32_t), S(s)));
+    hipLaunchKernelGGL(forest_update_check_kernel, grid, dim3(256), 0, S(s), offsets_dev, ntrees, trees_dev, indices_dev, k, status_dev);
+    VKMR_TRY(hipGetLastError());
+    hipLaunchKernelGGL(forest_update_leaves_kernel, grid, dim3(256), 0, S(s), digests, offsets_dev, trees_dev, indices_dev, nodes(leaves_dev), k,
+                       (const uint32_t*)status_dev);
+    VKMR_TRY(hipGetLastError());
+    for (uint32_t l = 1; l <= H; ++l) {   // level l from level l - 1, which the previous launch finished
+        const Node* in = (l == 1) ? digests : forest + vkmr_forest::stored_level_base(total, ntrees, l - 1);
+        hipLaunchKernelGGL(forest_update_level_kernel, grid, dim3(256), 0, S(s), in, forest + vkmr_forest::stored_level_base(total, ntrees, l), roots,
+                           offsets_dev, trees_dev, indices_dev, k, l, (const uint32_t*)status_dev);
+        VKMR_TRY(hipGetLastError());
+    }
     return VKMR_OK;
 }
 

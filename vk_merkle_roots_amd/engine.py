@@ -437,6 +437,13 @@ class HipDevice:
                                                            siblings_buf.ptr, heights_buf.ptr, k, stride, roots_buf.ptr, ntrees, ok_buf.ptr),
               "vkmr_hip_verify_forest_proofs_async")
 
+    def forest_update_async(self, digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, trees_buf, indices_buf, leaves_buf, k, roots_buf,
+                            status_buf, stream=None):
+        check(self.lib.vkmr_hip_forest_update_async(self.index, stream or self.stream, digests_buf.ptr if digests_buf else None,
+                                                    forest_buf.ptr if forest_buf else None, total, offsets_buf.ptr if offsets_buf else None, ntrees,
+                                                    max_count, trees_buf.ptr, indices_buf.ptr, leaves_buf.ptr, k,
+                                                    roots_buf.ptr if roots_buf else None, status_buf.ptr), "vkmr_hip_forest_update_async")
+
     def _build_forest_of_buffer(self, d_leaves, total, counts, max_count, what, owned=()):
         """A MerkleForest of the trees of `counts` leaves each over the `total` cells of d_leaves (its level 0)."""
         offsets, ntrees = _checked_offsets(counts, total, what)
@@ -694,6 +701,63 @@ class MerkleForest:
             self.proofs_async(d_trees, d_idx, k, d_sib, d_h)
             return self.dev.download(d_sib, 32 * k * self.levels).reshape(k, self.levels, 8), self.dev.download(d_h, 4 * k)
 
+    def update_async(self, trees_buf, indices_buf, leaves_buf, k, status_buf, stream=None):
+        """Leaf indices[q] of tree trees[q] = leaves[q], q < k, and every ancestor rehashed, on the device: trees [k] uint32 and
+        indices [k] uint64 strictly increasing as (tree, index) pairs with index < counts[tree], leaves [k, 8], status one
+        uint32 (0: applied; forest_update_status_text names the bits; nonzero: nothing changed).  All in device memory; ordered
+        on `stream` like the proof gather."""
+        self.dev.forest_update_async(self.digests, self.forest, self.total, self.offsets, self.ntrees, self.max_count, trees_buf, indices_buf,
+                                     leaves_buf, k, self.roots_buf, status_buf, stream=stream)
+
+    def _update_order(self, trees, indices, what="update"):
+        """(trees uint32, indices uint64, positions in the call they come from): the (tree, index) pairs sorted
+        lexicographically, each once; the last occurrence of a repeated pair wins.  ValueError when there is not one tree per
+        index, IndexError for a tree outside [0, ntrees) or an index outside [0, counts[tree]); no device call."""
+        if np.asarray(trees).size != np.asarray(indices).size:
+            raise ValueError(f"{what}: one tree per index")
+        t = _as_uint64(trees, what, "tree", "trees", below=self.ntrees)
+        idx = _as_uint64(indices, what, "index", "indices", below=int(self.counts.max()) if self.ntrees else 0)
+        if (idx >= self.counts[t.astype(np.int64)]).any():
+            raise IndexError(f"{what}: index outside its tree")
+        order = np.lexsort((idx, t))           # stable: repeats stay in call order, so the last of each run is the last occurrence
+        st, si = t[order], idx[order]
+        last = np.ones(st.shape[0], dtype=bool)
+        last[:-1] = (st[1:] != st[:-1]) | (si[1:] != si[:-1])
+        return st[last].astype(np.uint32), si[last], order[last]
+
+    def _apply(self, tmp, trees, idx, d_leaves):
+        """The update of the sorted, unique, in-range entries (trees, idx) to the digests in d_leaves; its buffers in the scope `tmp`."""
+        d_trees, d_idx, d_status = tmp.upload(trees), tmp.upload(idx), tmp.alloc(4)
+        self.update_async(d_trees, d_idx, d_leaves, idx.shape[0], d_status)
+        status = int(self.dev.download(d_status, 4)[0])
+        if status:
+            raise RuntimeError(f"MerkleForest.update: the device refused sorted in-range entries (status {status}: {forest_update_status_text(status)})")
+
+    def update(self, trees, indices, leaves):
+        """Set leaf indices[q] of tree trees[q] to leaves[q] ([k, 8] uint32; host arrays) and rehash every ancestor, on the
+        device; a repeated (tree, index) pair takes its last value.  A forest built over a caller's leaves buffer updates that
+        buffer (it is level 0).  ValueError when leaves is not [k, 8] or there is not one tree per index, IndexError for a tree
+        outside [0, ntrees) or an index outside [0, counts[tree]), all before any device call."""
+        lv = np.asarray(leaves)
+        k = int(np.asarray(indices).size)
+        if lv.shape != (k, 8):
+            raise ValueError(f"update: leaves must be [{k}, 8], not {list(lv.shape)}")
+        st, si, pos = self._update_order(trees, indices)
+        with self.dev.scope() as tmp:
+            if si.shape[0]:
+                self._apply(tmp, st, si, tmp.upload(np.ascontiguousarray(lv[pos], dtype=np.uint32)))
+
+    def update_packed(self, trees, indices, batch):
+        """Set leaf indices[q] of tree trees[q] to the digest of string q of `batch` (batch.count == len(indices)): the strings
+        are mapped on the device and the forest updated there, no digest goes through the host.  Same rules as update()."""
+        k = int(np.asarray(indices).size)
+        if batch.count != k:
+            raise ValueError(f"update_packed: {batch.count} strings for {k} indices")
+        st, si, pos = self._update_order(trees, indices, "update_packed")
+        with self.dev.scope() as tmp:
+            if si.shape[0]:      # map's entries are independent: the strings in sorted-entry order
+                self._apply(tmp, st, si, self.dev.map_packed(tmp, batch, meta=np.ascontiguousarray(batch.meta[pos])))
+
     def free(self):
         for b in [self.forest, self.roots_buf, self.offsets] + self._owned:
             if b:
@@ -739,6 +803,18 @@ def forest_status_text(status):
         names.append("bit 0: the offsets decrease or end past the leaves")
     if status & 2:
         names.append("bit 1: a tree holds more than max_count leaves")
+    if status & ~3:
+        names.append("unknown bits")
+    return "; ".join(names) if names else "ok"
+
+
+def forest_update_status_text(status):
+    """The bits of vkmr_hip_forest_update_async's status word, named."""
+    names = []
+    if status & 1:
+        names.append("bit 0: a tree outside the forest or an index outside its tree")
+    if status & 2:
+        names.append("bit 1: the (tree, index) pairs are not strictly increasing")
     if status & ~3:
         names.append("unknown bits")
     return "; ".join(names) if names else "ok"
