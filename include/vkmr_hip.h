@@ -456,6 +456,73 @@ VKMR_API vkmr_status vkmr_hip_forest_update_async(int dev, vkmr_stream s, vkmr_d
                                                   uint32_t* status_dev);
 
 /*
+ * MULTIPROOF FROM THE STORED FOREST: ONE compact proof for k leaves of MANY trees -- the matching transactions of many
+ * blocks, sampled files of an index, batches from many accounts -- instead of k independent vkmr_hip_forest_proofs_async
+ * proofs of H cells each whose paths merge on the way up.  digests_dev and forest_dev as written by
+ * vkmr_hip_reduce_forest_tree_async; the call TRUSTS that offsets_dev, total, ntrees and max_count are those of that build and
+ * that the build reported status 0 (the rule of vkmr_hip_forest_proofs_async).  Entry q is leaf indices_dev[q] (uint64, its
+ * index inside its tree) of tree trees_dev[q] (uint32); both arrays live in DEVICE memory and the (tree, index) pairs are
+ * strictly increasing in lexicographic order with tree < ntrees and index < c_t: the rule of vkmr_hip_forest_update_async,
+ * checked on the device with the same status bits.  With h_t = max(1, ceil(log2 c_t)), H = max(1, ceil(log2 min(max_count,
+ * total))) the forest's stride, and for tree t A_0(t) = its indices and A_{l+1}(t) = unique(A_l(t) >> 1): for l = 0..H-1 in
+ * this order, inside a level for t ascending over the trees with l < h_t, inside a tree for p in A_l(t) ascending: nothing
+ * when p ^ 1 is in A_l(t), else ONE node, L_t[l][p ^ 1], or L_t[l][p] where p ^ 1 >= n_l (the cell
+ * vkmr_hip_forest_proofs_async puts there).  Neighbours in another tree never count as siblings; a tree of one leaf emits
+ * the leaf itself.  The order is level-major over the WHOLE forest; restricted to one tree the nodes are that tree's
+ * vkmr_hip_tree_multiproof_async multiproof, level by level.  nodes_dev receives these M = sum of m_l cells in that order.
+ * Each emitted node belongs to one parent of a live tree, so m_l <= min(k, (total >> (l+1)) + ntrees):
+ * vkmr_hip_forest_multiproof_max_nodes returns the sum of that bound over l < H (0 for total == 0, ntrees == 0 or
+ * max_count == 0).  A gather, no hash.
+ *   scratch_dev     vkmr_hip_forest_multiproof_scratch_bytes(k, H) bytes of device memory (a multiple of 16), 16-byte aligned (0 for k == 0 or
+ *                   stride > 63; one size serves the gather and the verifier below)
+ *   nodes_capacity  cells nodes_dev can hold; nodes_dev may be NULL when it is 0
+ *   heights_dev     k uint32_t: heights_dev[q] = h of entry q's tree, as in vkmr_hip_forest_proofs_async
+ *   info_dev        2 + H uint64_t in device memory.  info_dev[0] = status, always written: 0 done; bit 0 a tree >= ntrees or
+ *                   an index >= c_t, bit 1 pairs not strictly increasing (both as vkmr_hip_forest_update_async defines them;
+ *                   then nothing else of the caller's is written: heights_dev, nodes_dev and info_dev[1..] keep what they
+ *                   held); bit 2 M > nodes_capacity (then the heights, info_dev[1] and the counts are written and valid and
+ *                   no node is, so the caller can allocate and call again).  info_dev[1] = M, info_dev[2 + l] = m_l over
+ *                   the whole forest.
+ * Launches, all on the caller's stream: the status zeroed, the check, the heights, the ranking of
+ * vkmr_hip_tree_multiproof_async with height := H, one gather of H x k lanes; never a launch per tree, no allocation, no host
+ * read of device data.  Refused on the host (VKMR_ERR_INVALID) with k > 0: a NULL pointer, ntrees == 0 or total == 0,
+ * max_count == 0, total > 2^58, scratch_dev not 16-byte aligned.  k == 0 does nothing whatever the other arguments.
+ * Stream-ordered: a multiproof gathered after an update on the same stream proves the new forest.
+ * vkmr_host_cpu_forest_multiproof (libvkmr_host.so) applies the same rule on the CPU, for a sender without a GPU.
+ */
+VKMR_API size_t vkmr_hip_forest_multiproof_max_nodes(uint64_t total, uint32_t ntrees, uint64_t max_count, uint32_t k);
+VKMR_API size_t vkmr_hip_forest_multiproof_scratch_bytes(uint32_t k, uint32_t stride);
+VKMR_API vkmr_status vkmr_hip_forest_multiproof_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev,
+                                                      const vkmr_digest* forest_dev, uint64_t total, const uint64_t* offsets_dev,
+                                                      uint32_t ntrees, uint64_t max_count, const uint32_t* trees_dev,
+                                                      const uint64_t* indices_dev, uint32_t k, void* scratch_dev,
+                                                      vkmr_digest* nodes_dev, uint64_t nodes_capacity, uint32_t* heights_dev,
+                                                      uint64_t* info_dev);
+
+/*
+ * FOREST MULTIPROOF VERIFICATION: many roots, one answer.  leaves_dev[0..k) are the proved leaves, (trees_dev[q],
+ * indices_dev[q]) their positions, heights_dev[q] the height of entry q's tree, nodes_dev[0..m) the multiproof in the order
+ * above; never the counts or the offsets of the forest.  ok_dev[0] = 1 iff the pairs are strictly increasing, every tree
+ * < ntrees, 1 <= heights_dev[q] <= stride, indices_dev[q] < 2^heights_dev[q], the entries of one tree carry one height, the
+ * indices and heights imply exactly m nodes, and for every tree that some entry names the fold equals roots_dev[t]; else 0.
+ * The fold is vkmr_hip_verify_multiproof_async's rule tree by tree, through heights_dev levels, a missing child being the
+ * next unread node in the order above.  Roots of trees no entry names are not read.  Work: the distinct (tree, index >> l)
+ * pairs with 1 <= l <= h_t node hashes, one launch of k lanes per level l < stride.  The leaves are not overwritten.
+ *   stride 1..63 (the H of vkmr_hip_forest_multiproof_async, or anything at least the tallest tree's height); roots_dev:
+ *   ntrees cells; scratch_dev: vkmr_hip_forest_multiproof_scratch_bytes(k, stride) bytes, 16-byte aligned; nodes_dev may be
+ *   NULL when m == 0; all buffers in device memory.
+ * As with vkmr_hip_verify_proofs_async, this shows membership AT POSITIONS, not the number of leaves: the known ambiguity
+ * of duplicate-last trees is unchanged.  k == 0 does nothing.  vkmr_host_cpu_verify_forest_multiproof (libvkmr_host.so)
+ * applies the same rule on the CPU, for a receiver without a GPU.
+ */
+VKMR_API vkmr_status vkmr_hip_verify_forest_multiproof_async(int dev, vkmr_stream s, const vkmr_digest* leaves_dev,
+                                                             const uint32_t* trees_dev, const uint64_t* indices_dev,
+                                                             const uint32_t* heights_dev, uint32_t k, uint32_t stride,
+                                                             const vkmr_digest* nodes_dev, uint64_t m,
+                                                             const vkmr_digest* roots_dev, uint32_t ntrees, void* scratch_dev,
+                                                             uint32_t* ok_dev);
+
+/*
  * COMBINE: duplicate-last Merkle root over n >= 1 slice roots given in slice order, always
  * at least one level -- the rule of CpuSha256D::Root that the reference applies to the slice
  * roots on the CPU (CpuSha256DforReductions, src/vkmr/Reductions.cpp:56-69, :703-712).  Here

@@ -189,3 +189,169 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_forest_proofs(const vkm
 }
 
 }  // extern "C"
+
+namespace {
+
+// The entries [a, b) of one tree (sorted, unique): adds to per_level[l], l < h, the nodes its multiproof emits at level l.
+// Index arithmetic only: a node is emitted for every p of A_l whose sibling p ^ 1 is not in A_l.
+void forest_multiproof_counts(const uint64_t* indices, uint32_t a, uint32_t b, uint32_t h, uint64_t* per_level)
+{
+    std::vector<uint64_t> cur(indices + a, indices + b);
+    for (uint32_t l = 0; l < h; ++l) {
+        size_t out = 0;
+        for (size_t i = 0; i < cur.size();) {
+            const bool both = !(cur[i] & 1ull) && i + 1 < cur.size() && cur[i + 1] == cur[i] + 1;
+            if (!both) ++per_level[l];
+            const uint64_t P = cur[i] >> 1;
+            i += both ? 2 : 1;
+            cur[out++] = P;            // out <= i: written behind what is still to be read
+        }
+        cur.resize(out);
+    }
+}
+
+// First entry behind the run of entries that name trees[a].
+uint32_t forest_run_end(const uint32_t* trees, uint32_t a, uint32_t k)
+{
+    uint32_t b = a + 1;
+    while (b < k && trees[b] == trees[a]) ++b;
+    return b;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Multiproof for leaves of many trees on the CPU, by the rule of vkmr_hip_forest_multiproof_async: entry q is leaf indices[q]
+// of tree trees[q] (tree t: digests[offsets[t] .. offsets[t+1])), the pairs strictly increasing; nodes[] receives the M nodes
+// in level-major order over the whole forest, heights[q] = h of entry q's tree, info[0] = status, info[1] = M,
+// info[2 + l] = m_l for l < stride.  Returns the status: 0 done; bit 0 a tree >= ntrees or an index >= c_t, bit 1 pairs not
+// strictly increasing (then only info[0] is written); bit 2 M > nodes_capacity (the heights, M and the counts are written, no
+// node is).  -1 for a missing pointer or k == 0, -2 when the offsets decrease somewhere, -3 when `stride` is above 63 or below
+// the height of a tree some entry names (nothing written).  A touched tree's levels are formed once, tree by tree.
+__attribute__((visibility("default"))) int vkmr_host_cpu_forest_multiproof(const vkmr_digest* digests, const uint64_t* offsets, uint32_t ntrees,
+                                                                            const uint32_t* trees, const uint64_t* indices, uint32_t k,
+                                                                            uint32_t stride, vkmr_digest* nodes, uint64_t nodes_capacity,
+                                                                            uint32_t* heights, uint64_t* info)
+{
+    if (k == 0 || !digests || !offsets || !trees || !indices || !heights || !info || (!nodes && nodes_capacity > 0)) return -1;
+    if (stride > 63) return -3;
+    for (uint32_t t = 0; t < ntrees; ++t)
+        if (offsets[t + 1] < offsets[t]) return -2;
+    int status = 0;
+    for (uint32_t q = 0; q < k; ++q) {
+        if (trees[q] >= ntrees || indices[q] >= offsets[trees[q] + 1] - offsets[trees[q]]) status |= 1;
+        if (q > 0 && (trees[q - 1] > trees[q] || (trees[q - 1] == trees[q] && indices[q - 1] >= indices[q]))) status |= 2;
+    }
+    if (status == 0)
+        for (uint32_t q = 0; q < k; ++q)
+            if (vkmr_math::height(offsets[trees[q] + 1] - offsets[trees[q]]) > stride) return -3;
+    info[0] = (uint64_t)status;
+    if (status) return status;
+    std::vector<uint64_t> per_level(stride + 1u, 0);
+    for (uint32_t a = 0; a < k;) {
+        const uint32_t b = forest_run_end(trees, a, k), t = trees[a];
+        const uint32_t h = vkmr_math::height(offsets[t + 1] - offsets[t]);
+        for (uint32_t q = a; q < b; ++q) heights[q] = h;
+        forest_multiproof_counts(indices, a, b, h, per_level.data());
+        a = b;
+    }
+    std::vector<uint64_t> at(stride + 1u, 0);             // where the next node of level l goes
+    uint64_t M = 0;
+    for (uint32_t l = 0; l < stride; ++l) {
+        at[l] = M;
+        M += per_level[l];
+        info[2 + l] = per_level[l];
+    }
+    info[1] = M;
+    if (M > nodes_capacity) {
+        info[0] = 4;
+        return 4;
+    }
+    std::vector<std::vector<vkmr_digest>> levels;
+    for (uint32_t a = 0; a < k;) {
+        const uint32_t b = forest_run_end(trees, a, k), t = trees[a];
+        const uint32_t h = heights[a];
+        levels.assign(h, {});
+        levels[0].assign(digests + offsets[t], digests + offsets[t + 1]);
+        for (uint32_t l = 1; l < h; ++l) {
+            const std::vector<vkmr_digest>& in = levels[l - 1];
+            levels[l].resize((in.size() + 1) / 2);
+            for (size_t j = 0; j < levels[l].size(); ++j)
+                vkmr::cpu_sha256d_pair(in[2 * j].data, in[vkmr_math::right_child(j, in.size())].data, levels[l][j].data);
+        }
+        std::vector<uint64_t> cur(indices + a, indices + b);
+        for (uint32_t l = 0; l < h; ++l) {
+            size_t out = 0;
+            for (size_t i = 0; i < cur.size();) {
+                const uint64_t p = cur[i];
+                const bool both = !(p & 1ull) && i + 1 < cur.size() && cur[i + 1] == p + 1;
+                if (!both) nodes[at[l]++] = levels[l][vkmr_math::sibling(p, levels[l].size())];
+                i += both ? 2 : 1;
+                cur[out++] = p >> 1;
+            }
+            cur.resize(out);
+        }
+        a = b;
+    }
+    return 0;
+}
+
+// Forest multiproof verification on the CPU, by the rule of vkmr_hip_verify_forest_multiproof_async: 1 when the (tree, index)
+// pairs are strictly increasing, every tree < ntrees, 1 <= heights[q] <= stride <= 63, indices[q] < 2^heights[q], the entries
+// of one tree carry one height, the indices and heights imply exactly m nodes, and every named tree's fold -- a missing child
+// being the next unread node of its level in forest order -- ends in roots[t]; else 0.
+__attribute__((visibility("default"))) int vkmr_host_cpu_verify_forest_multiproof(const vkmr_digest* leaves, const uint32_t* trees,
+                                                                                   const uint64_t* indices, const uint32_t* heights, uint32_t k,
+                                                                                   uint32_t stride, const vkmr_digest* nodes, uint64_t m,
+                                                                                   const vkmr_digest* roots, uint32_t ntrees)
+{
+    if (!leaves || !trees || !indices || !heights || !roots || k == 0 || stride == 0 || stride > 63 || (!nodes && m > 0)) return 0;
+    for (uint32_t q = 0; q < k; ++q) {
+        const uint32_t h = heights[q];
+        if (trees[q] >= ntrees || h < 1 || h > stride || (indices[q] >> h) != 0) return 0;
+        if (q == 0) continue;
+        if (trees[q - 1] > trees[q] || (trees[q - 1] == trees[q] && (indices[q - 1] >= indices[q] || heights[q - 1] != h))) return 0;
+    }
+    std::vector<uint64_t> per_level(stride + 1u, 0);
+    for (uint32_t a = 0; a < k;) {
+        const uint32_t b = forest_run_end(trees, a, k);
+        forest_multiproof_counts(indices, a, b, heights[a], per_level.data());
+        a = b;
+    }
+    std::vector<uint64_t> at(stride + 1u, 0);             // the next unread node of level l
+    uint64_t M = 0;
+    for (uint32_t l = 0; l < stride; ++l) {
+        at[l] = M;
+        M += per_level[l];
+    }
+    if (M != m) return 0;
+    for (uint32_t a = 0; a < k;) {
+        const uint32_t b = forest_run_end(trees, a, k), h = heights[a];
+        std::vector<uint64_t> pos(indices + a, indices + b);
+        std::vector<vkmr_digest> cur(leaves + a, leaves + b);
+        for (uint32_t l = 0; l < h; ++l) {
+            size_t out = 0;
+            for (size_t i = 0; i < pos.size();) {
+                const uint64_t p = pos[i];
+                const bool both = !(p & 1ull) && i + 1 < pos.size() && pos[i + 1] == p + 1;
+                const vkmr_digest* other = both ? &cur[i + 1] : &nodes[at[l]++];   // at[l] < the level's end: the counts above
+                vkmr_digest x;
+                if (p & 1ull)
+                    vkmr::cpu_sha256d_pair(other->data, cur[i].data, x.data);
+                else
+                    vkmr::cpu_sha256d_pair(cur[i].data, other->data, x.data);
+                i += both ? 2 : 1;
+                pos[out] = p >> 1;
+                cur[out++] = x;
+            }
+            pos.resize(out);
+            cur.resize(out);
+        }
+        if (pos.size() != 1 || pos[0] != 0 || std::memcmp(cur[0].data, roots[trees[a]].data, 32) != 0) return 0;
+        a = b;
+    }
+    return 1;
+}
+
+}  // extern "C"

@@ -16,6 +16,8 @@
 //                            verify_forest_proofs_kernel   batch verification of proofs of unequal height, one lane per proof
 //   forest_update_kernels.hpp  forest_update_*_kernel   leaf updates of the stored forest: check, store the leaves, rehash the
 //                                              dirty nodes of every touched tree level by level
+//   forest_multiproof_kernels.hpp  forest_multiproof_*_kernel, verify_forest_multiproof_*_kernel   one proof for leaves of many
+//                                              trees: tree_kernels.hpp's ranking with a tree and a height per entry
 //   sha256d_device.hpp  the SHA-256 round / compression building blocks, and the tree's: hash_parent, node_diff, store_node
 //   merkle_math.hpp     the integer rules, no HIP types (ceil_shift, height, right_child, sibling): shared with host/ and tests/c
 //   meta_kernels.hpp    sizes_*_kernel         metadata entries from 16-bit sizes   (Batches.cpp:64-121)
@@ -47,6 +49,7 @@ using vkmr_dev::Node;
 #include "forest_kernels.hpp"
 #include "forest_tree_kernels.hpp"
 #include "forest_update_kernels.hpp"
+#include "forest_multiproof_kernels.hpp"
 
 // ============================================================================
 // C ABI
@@ -1125,6 +1128,121 @@ vkmr_status vkmr_hip_forest_update_async(int dev, vkmr_stream s, vkmr_digest* di
                            offsets_dev, trees_dev, indices_dev, k, l, (const uint32_t*)status_dev);
         VKMR_TRY(hipGetLastError());
     }
+    return VKMR_OK;
+}
+
+// ---- multiproofs inside the stored forest (forest_multiproof_kernels.hpp) ---------------------------------------------------
+
+size_t vkmr_hip_forest_multiproof_max_nodes(uint64_t total, uint32_t ntrees, uint64_t max_count, uint32_t k)
+{
+    if (total == 0 || ntrees == 0 || max_count == 0) return 0;
+    const uint32_t H = vkmr_forest::launches(total, max_count);
+    uint64_t cells = 0;
+    for (uint32_t l = 0; l < H; ++l) {   // at most one node per parent of a live tree: the cells of level l + 1
+        const uint64_t parents = vkmr_forest::level_cells(total, ntrees, l + 1);
+        cells += parents < k ? parents : k;
+    }
+    return (size_t)cells;
+}
+
+size_t vkmr_hip_forest_multiproof_scratch_bytes(uint32_t k, uint32_t stride)
+{
+    return (vkmr_hip_multiproof_scratch_bytes(k, stride) + 15u) & ~(size_t)15u;   // the single tree's layout with height := stride, in whole 16-byte units
+}
+
+// The ranking launches both forest calls share, behind their own check: the flags, then tree_kernels.hpp's block sums, block
+// starts and word starts with height := stride.  limit / exact as multiproof_block_starts_kernel takes them.
+static vkmr_status forest_multiproof_rank_launch(hipStream_t stream, const uint32_t* trees_dev, const uint64_t* indices_dev,
+                                                 const uint32_t* heights_dev, uint32_t k, uint32_t stride, const MultiproofLayout& L, char* scratch,
+                                                 uint64_t* hdr, uint64_t limit, uint32_t exact)
+{
+    uint64_t* mask = reinterpret_cast<uint64_t*>(scratch + L.mask);
+    uint64_t* word_start = reinterpret_cast<uint64_t*>(scratch + L.word_start);
+    uint64_t* block = reinterpret_cast<uint64_t*>(scratch + L.block);
+    const dim3 wgrid((uint32_t)L.blocks, stride);
+    hipLaunchKernelGGL(forest_multiproof_masks_kernel, grid_of(k), dim3(256), 0, stream, trees_dev, indices_dev, heights_dev, k, stride, L.words,
+                       (const uint64_t*)hdr, mask);
+    VKMR_TRY(hipGetLastError());
+    hipLaunchKernelGGL(multiproof_block_sums_kernel, wgrid, dim3(VKMR_MP_BLOCK_WORDS), 0, stream, (const uint64_t*)mask, L.words, L.blocks, block);
+    VKMR_TRY(hipGetLastError());
+    hipLaunchKernelGGL(multiproof_block_starts_kernel, dim3(1), dim3(256), 0, stream, block, L.blocks, stride, limit, exact, hdr);
+    VKMR_TRY(hipGetLastError());
+    hipLaunchKernelGGL(multiproof_word_starts_kernel, wgrid, dim3(VKMR_MP_BLOCK_WORDS), 0, stream, (const uint64_t*)mask, L.words, L.blocks,
+                       (const uint64_t*)block, (const uint64_t*)hdr, word_start);
+    VKMR_TRY(hipGetLastError());
+    return VKMR_OK;
+}
+
+vkmr_status vkmr_hip_forest_multiproof_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* forest_dev, uint64_t total,
+                                             const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count, const uint32_t* trees_dev,
+                                             const uint64_t* indices_dev, uint32_t k, void* scratch_dev, vkmr_digest* nodes_dev,
+                                             uint64_t nodes_capacity, uint32_t* heights_dev, uint64_t* info_dev)
+{
+    if (k == 0) return VKMR_OK;
+    if (!digests_dev || !forest_dev || !offsets_dev || !trees_dev || !indices_dev || !scratch_dev || !heights_dev || !info_dev ||
+        (!nodes_dev && nodes_capacity > 0))
+        return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_multiproof_async: null pointer");
+    if (ntrees == 0 || total == 0) return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_multiproof_async: a forest without a leaf has none to prove");
+    if (max_count == 0) return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_multiproof_async: max_count must be at least 1");
+    if (total > (1ull << 58)) return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_multiproof_async: forest too large");
+    if (reinterpret_cast<uintptr_t>(scratch_dev) & 15u) return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_multiproof_async: scratch must be 16-byte aligned");
+    if (grid_too_large(groups_of(k))) return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_multiproof_async: too many entries in one call");
+    const uint32_t H = vkmr_forest::launches(total, max_count);   // <= 58
+    ForestLevels lv;
+    for (uint32_t l = 0; l < VKMR_TREE_MAX_LEVELS; ++l) lv.base[l] = (l >= 1 && l <= H) ? vkmr_forest::stored_level_base(total, ntrees, l) : 0;
+    const MultiproofLayout L = multiproof_layout(k, H);
+    char* scratch = static_cast<char*>(scratch_dev);
+    const dim3 grid = grid_of(k);
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_TRY(hipMemsetAsync(info_dev, 0, sizeof(uint64_t), S(s)));
+    hipLaunchKernelGGL(forest_update_check_kernel, grid, dim3(256), 0, S(s), offsets_dev, ntrees, trees_dev, indices_dev, k,
+                       reinterpret_cast<uint32_t*>(info_dev));
+    VKMR_TRY(hipGetLastError());
+    hipLaunchKernelGGL(forest_multiproof_heights_kernel, grid, dim3(256), 0, S(s), offsets_dev, trees_dev, k, (const uint64_t*)info_dev, heights_dev);
+    VKMR_TRY(hipGetLastError());
+    const vkmr_status st = forest_multiproof_rank_launch(S(s), trees_dev, indices_dev, heights_dev, k, H, L, scratch, info_dev, nodes_capacity, 0u);
+    if (st != VKMR_OK) return st;
+    hipLaunchKernelGGL(forest_multiproof_gather_kernel, grid_of(k, H), dim3(256), 0, S(s), nodes(digests_dev), nodes(forest_dev), lv, offsets_dev,
+                       trees_dev, indices_dev, k, L.words, reinterpret_cast<const uint64_t*>(scratch + L.mask),
+                       reinterpret_cast<const uint64_t*>(scratch + L.word_start), (const uint64_t*)info_dev, nodes(nodes_dev));
+    VKMR_TRY(hipGetLastError());
+    return VKMR_OK;
+}
+
+vkmr_status vkmr_hip_verify_forest_multiproof_async(int dev, vkmr_stream s, const vkmr_digest* leaves_dev, const uint32_t* trees_dev,
+                                                    const uint64_t* indices_dev, const uint32_t* heights_dev, uint32_t k, uint32_t stride,
+                                                    const vkmr_digest* nodes_dev, uint64_t m, const vkmr_digest* roots_dev, uint32_t ntrees,
+                                                    void* scratch_dev, uint32_t* ok_dev)
+{
+    if (k == 0) return VKMR_OK;
+    if (!leaves_dev || !trees_dev || !indices_dev || !heights_dev || !roots_dev || !scratch_dev || !ok_dev || (!nodes_dev && m > 0))
+        return fail(VKMR_ERR_INVALID, "vkmr_hip_verify_forest_multiproof_async: null pointer");
+    if (stride == 0 || stride > 63) return fail(VKMR_ERR_INVALID, "vkmr_hip_verify_forest_multiproof_async: stride must be 1..63");
+    if (reinterpret_cast<uintptr_t>(scratch_dev) & 15u)
+        return fail(VKMR_ERR_INVALID, "vkmr_hip_verify_forest_multiproof_async: scratch must be 16-byte aligned");
+    const MultiproofLayout L = multiproof_layout(k, stride);
+    char* scratch = static_cast<char*>(scratch_dev);
+    uint64_t* hdr = reinterpret_cast<uint64_t*>(scratch + L.hdr);
+    Node* cell = nodes(scratch + L.cell);
+    const dim3 grid = grid_of(k);
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_TRY(hipMemsetAsync(hdr, 0, sizeof(uint64_t), S(s)));
+    VKMR_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ok_dev), 1, 1, S(s)));   // the finish kernel clears it
+    hipLaunchKernelGGL(verify_forest_multiproof_check_kernel, grid, dim3(256), 0, S(s), trees_dev, indices_dev, heights_dev, k, stride, ntrees,
+                       reinterpret_cast<uint32_t*>(hdr));
+    VKMR_TRY(hipGetLastError());
+    const vkmr_status st = forest_multiproof_rank_launch(S(s), trees_dev, indices_dev, heights_dev, k, stride, L, scratch, hdr, m, 1u);   // exact: M == m
+    if (st != VKMR_OK) return st;
+    for (uint32_t l = 0; l < stride; ++l) {   // level l + 1 from level l, which the previous launch finished
+        hipLaunchKernelGGL(verify_forest_multiproof_level_kernel, grid, dim3(256), 0, S(s), l == 0 ? nodes(leaves_dev) : cell, cell,
+                           reinterpret_cast<uint32_t*>(scratch + L.end), trees_dev, indices_dev, heights_dev, k, l, L.words,
+                           reinterpret_cast<const uint64_t*>(scratch + L.mask), reinterpret_cast<const uint64_t*>(scratch + L.word_start),
+                           nodes(nodes_dev), (const uint64_t*)hdr);
+        VKMR_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(verify_forest_multiproof_finish_kernel, grid, dim3(256), 0, S(s), (const Node*)cell, trees_dev, k, nodes(roots_dev),
+                       (const uint64_t*)hdr, ok_dev);
+    VKMR_TRY(hipGetLastError());
     return VKMR_OK;
 }
 

@@ -444,6 +444,42 @@ class HipDevice:
                                                     max_count, trees_buf.ptr, indices_buf.ptr, leaves_buf.ptr, k,
                                                     roots_buf.ptr if roots_buf else None, status_buf.ptr), "vkmr_hip_forest_update_async")
 
+    def forest_multiproof_async(self, digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, trees_buf, indices_buf, k, scratch_buf,
+                                nodes_buf, nodes_capacity, heights_buf, info_buf, stream=None):
+        check(self.lib.vkmr_hip_forest_multiproof_async(self.index, stream or self.stream, digests_buf.ptr if digests_buf else None,
+                                                        forest_buf.ptr if forest_buf else None, total, offsets_buf.ptr if offsets_buf else None,
+                                                        ntrees, max_count, trees_buf.ptr, indices_buf.ptr, k,
+                                                        scratch_buf.ptr if scratch_buf else None, nodes_buf.ptr if nodes_buf else None,
+                                                        nodes_capacity, heights_buf.ptr, info_buf.ptr), "vkmr_hip_forest_multiproof_async")
+
+    def verify_forest_multiproof_async(self, leaves_buf, trees_buf, indices_buf, heights_buf, k, stride, nodes_buf, m, roots_buf, ntrees,
+                                       scratch_buf, ok_buf, stream=None):
+        check(self.lib.vkmr_hip_verify_forest_multiproof_async(self.index, stream or self.stream, leaves_buf.ptr, trees_buf.ptr, indices_buf.ptr,
+                                                               heights_buf.ptr, k, stride, nodes_buf.ptr if nodes_buf else None, m, roots_buf.ptr,
+                                                               ntrees, scratch_buf.ptr, ok_buf.ptr), "vkmr_hip_verify_forest_multiproof_async")
+
+    def verify_forest_multiproof(self, leaves, trees, indices, heights, nodes, roots):
+        """bool: the forest multiproof `nodes` ([M, 8], level-major over the whole forest) proves leaves ([k, 8]) at the
+        strictly increasing (trees[q], indices[q]) under roots[trees[q]] (roots [ntrees, 8]), heights[q] being the height of
+        entry q's tree (vkmr_hip_verify_forest_multiproof_async).  Host arrays in, verified on the device; no leaf proves
+        nothing: False."""
+        leaves, trees, idx = _host(leaves, np.uint32, -1, 8), _host(trees, np.uint32, -1), _host(indices, np.uint64, -1)
+        heights, nodes, roots = _host(heights, np.uint32, -1), _host(nodes, np.uint32, -1, 8), _host(roots, np.uint32, -1, 8)
+        k, m = int(idx.shape[0]), int(nodes.shape[0])
+        if leaves.shape[0] != k or trees.shape[0] != k or heights.shape[0] != k:
+            raise ValueError("verify_forest_multiproof: one leaf, one tree and one height per index")
+        if k == 0:
+            return False
+        if roots.shape[0] == 0:
+            raise ValueError("verify_forest_multiproof: no root")
+        stride = max(1, min(63, int(heights.max())))       # a height above 63 is refused by the device's check
+        with self.scope() as tmp:
+            d_leaves, d_trees, d_idx, d_h, d_nodes, d_roots = (tmp.upload(a) for a in (leaves, trees, idx, heights, nodes, roots))
+            d_scr, d_ok = tmp.alloc(self.lib.vkmr_hip_forest_multiproof_scratch_bytes(k, stride)), tmp.alloc(4)
+            self.verify_forest_multiproof_async(d_leaves, d_trees, d_idx, d_h, k, stride, d_nodes if m else None, m, d_roots, roots.shape[0],
+                                                d_scr, d_ok)
+            return int(self.download(d_ok, 4)[0]) == 1
+
     def _build_forest_of_buffer(self, d_leaves, total, counts, max_count, what, owned=()):
         """A MerkleForest of the trees of `counts` leaves each over the `total` cells of d_leaves (its level 0)."""
         offsets, ntrees = _checked_offsets(counts, total, what)
@@ -530,6 +566,50 @@ class Multiproof:
 
     def __init__(self, indices, nodes, level_counts, height):
         self.indices, self.nodes, self.level_counts, self.height = indices, nodes, level_counts, int(height)
+
+
+def _multiproof_level_counts(indices, height):
+    """[height] ints: the nodes a multiproof of the sorted unique `indices` holds per level.  Index arithmetic only."""
+    cur = np.asarray(indices, dtype=np.uint64)
+    counts = []
+    for _ in range(height):
+        have_next = np.zeros(cur.shape[0], dtype=bool)
+        have_next[:-1] = (cur[1:] == cur[:-1] + np.uint64(1)) & ((cur[:-1] & np.uint64(1)) == 0)   # an even node with its odd sibling behind it
+        pairs = int(have_next.sum())
+        counts.append(int(cur.shape[0]) - 2 * pairs)
+        cur = np.unique(cur >> np.uint64(1))
+    return counts
+
+
+class ForestMultiproof:
+    """One proof for leaves of many trees of a forest (vkmr_hip_forest_multiproof_async): `trees` uint32 [k] and `indices`
+    uint64 [k], the (tree, index) pairs sorted and unique; `heights` uint32 [k], the height of each entry's tree; `nodes`
+    uint32 [M, 8] in level-major order over the whole forest; `level_counts` uint64 [stride] (nodes per level); `stride`.
+    With the leaves at those positions and the forest's roots it is what HipDevice.verify_forest_multiproof and
+    vkmr_host_cpu_verify_forest_multiproof take."""
+
+    def __init__(self, trees, indices, heights, nodes, level_counts, stride):
+        self.trees, self.indices, self.heights, self.nodes, self.level_counts, self.stride = trees, indices, heights, nodes, level_counts, int(stride)
+
+    def split(self):
+        """{tree: Multiproof}: the level-major nodes regrouped per tree, from the indices and heights alone.  Each tree's
+        proof can be forwarded by itself and checked with HipDevice.verify_multiproof or vkmr_host_cpu_verify_multiproof."""
+        trees = np.asarray(self.trees)
+        starts = np.flatnonzero(np.concatenate([[True], trees[1:] != trees[:-1]])) if trees.shape[0] else np.zeros(0, dtype=np.int64)
+        ends = np.concatenate([starts[1:], [trees.shape[0]]]).astype(np.int64)
+        runs = [(int(trees[a]), self.indices[a:b], int(self.heights[a])) for a, b in zip(starts, ends)]
+        counts = [_multiproof_level_counts(idx, h) for _, idx, h in runs]
+        parts = [[] for _ in runs]
+        at = 0
+        for l in range(self.stride):               # level-major: level l of every tree that has one, tree by tree
+            for r, (_, _, h) in enumerate(runs):
+                if l < h:
+                    parts[r].append(self.nodes[at: at + counts[r][l]])
+                    at += counts[r][l]
+        if at != self.nodes.shape[0]:
+            raise ValueError(f"ForestMultiproof.split: the entries imply {at} nodes, the proof holds {self.nodes.shape[0]}")
+        return {t: Multiproof(idx, np.concatenate(parts[r]).reshape(-1, 8), np.array(counts[r], dtype=np.uint64), h)
+                for r, (t, idx, h) in enumerate(runs)}
 
 
 class MerkleTree:
@@ -701,6 +781,38 @@ class MerkleForest:
             self.proofs_async(d_trees, d_idx, k, d_sib, d_h)
             return self.dev.download(d_sib, 32 * k * self.levels).reshape(k, self.levels, 8), self.dev.download(d_h, 4 * k)
 
+    def multiproof_async(self, trees_buf, indices_buf, k, scratch_buf, nodes_buf, nodes_capacity, heights_buf, info_buf, stream=None):
+        """ONE proof for the k (tree, index) entries in device memory (strictly increasing pairs), written to nodes_buf
+        (nodes_capacity cells) and heights_buf [k]; info_buf: 2 + levels uint64 (status, M, the per-level counts).
+        include/vkmr_hip.h."""
+        self.dev.forest_multiproof_async(self.digests, self.forest, self.total, self.offsets, self.ntrees, self.max_count, trees_buf, indices_buf,
+                                         k, scratch_buf, nodes_buf, nodes_capacity, heights_buf, info_buf, stream=stream)
+
+    def multiproof(self, trees, indices):
+        """A ForestMultiproof of leaves `indices` of trees `trees` (host arrays; the pairs sorted and deduplicated here).
+        ValueError when there is not one tree per index or for no entry at all, IndexError for a tree outside [0, ntrees) or an
+        index outside [0, counts[tree]), all before any device call."""
+        st, si, _ = self._update_order(trees, indices, "multiproof")
+        k = int(si.shape[0])
+        if k == 0:
+            raise ValueError("multiproof: no entry")
+        lib = self.dev.lib
+        cap = lib.vkmr_hip_forest_multiproof_max_nodes(self.total, self.ntrees, self.max_count, k)
+        with self.dev.scope() as tmp:
+            d_trees, d_idx = tmp.upload(st), tmp.upload(si)
+            d_scr = tmp.alloc(lib.vkmr_hip_forest_multiproof_scratch_bytes(k, self.levels))
+            d_nodes, d_h, d_info = tmp.alloc(32 * cap), tmp.alloc(4 * k), tmp.alloc(8 * (2 + self.levels))
+            self.multiproof_async(d_trees, d_idx, k, d_scr, d_nodes, cap, d_h, d_info)
+            status = int(self.dev.download(d_info, 8, dtype=np.uint64)[0])
+            if status:                            # M and the counts are only written without one (or with bit 2)
+                raise RuntimeError(f"MerkleForest.multiproof: the device refused sorted in-range entries "
+                                   f"(status {status}: {forest_multiproof_status_text(status)})")
+            info = self.dev.download(d_info, 8 * (2 + self.levels), dtype=np.uint64)
+            m = int(info[1])
+            nodes = self.dev.download(d_nodes, 32 * m).reshape(m, 8) if m else np.zeros((0, 8), dtype=np.uint32)
+            heights = self.dev.download(d_h, 4 * k)
+        return ForestMultiproof(st, si, heights, nodes, info[2:].copy(), self.levels)
+
     def update_async(self, trees_buf, indices_buf, leaves_buf, k, status_buf, stream=None):
         """Leaf indices[q] of tree trees[q] = leaves[q], q < k, and every ancestor rehashed, on the device: trees [k] uint32 and
         indices [k] uint64 strictly increasing as (tree, index) pairs with index < counts[tree], leaves [k, 8], status one
@@ -816,6 +928,18 @@ def forest_update_status_text(status):
     if status & 2:
         names.append("bit 1: the (tree, index) pairs are not strictly increasing")
     if status & ~3:
+        names.append("unknown bits")
+    return "; ".join(names) if names else "ok"
+
+
+def forest_multiproof_status_text(status):
+    """The bits of vkmr_hip_forest_multiproof_async's status word (info[0]), named."""
+    names = []
+    if status & 3:
+        names.append(forest_update_status_text(status & 3))
+    if status & 4:
+        names.append("bit 2: more nodes than the node buffer holds")
+    if status & ~7:
         names.append("unknown bits")
     return "; ".join(names) if names else "ok"
 
