@@ -306,6 +306,24 @@ def test_the_split_of_the_restatement_is_each_tree_s_own_multiproof(native):
                 assert mc.host_verify(mine_leaves[idx.astype(np.int64)], idx, h, mine, roots[t])
 
 
+def test_the_two_host_verifiers_agree_on_a_forest_of_one_tree(native):
+    """vkmr_host_cpu_verify_multiproof and vkmr_host_cpu_verify_forest_multiproof walk a level with the same helper: on a forest
+    of one tree they give the same answer, for the single tree's case tables and for every corruption of a proof in them (an
+    index, a node, m, a leaf)."""
+    for count in mc.COUNTS:
+        rng = np.random.default_rng(4200 + count)
+        leaves = mc.random_leaves(rng, count)
+        levels = mc.cpu_levels(leaves)
+        height, root = len(levels) - 1, levels[-1][0]
+        for idx in mc.small_index_sets(count, rng):
+            nodes, _ = mc.make_multiproof(lambda l: levels[l], count, height, idx)
+            cases = [("as made", leaves[idx], np.array(idx, dtype=np.uint64), nodes)] + mc.mutations(leaves[idx], idx, nodes, height, rng)
+            for what, lv, ix, nd in cases:
+                one = mc.host_verify(lv, ix, height, nd, root)
+                many = fm.host_verify(lv, np.zeros(len(ix), dtype=np.uint32), ix, np.full(len(ix), height, dtype=np.uint32), height, nd, root)
+                assert one == many == (what == "as made"), (count, idx, what)
+
+
 def test_the_product_s_split_equals_the_restatement_s(native):
     import vk_merkle_roots_amd as vk
     counts = fc.CASES["sizes_1_to_130"]

@@ -1,25 +1,19 @@
-// forest_tree_kernels.hpp -- proofs from a stored forest and the batch verifier for proofs of unequal height
-// (include/vkmr_hip.h: vkmr_hip_forest_proofs_async, vkmr_hip_verify_forest_proofs_async).  The stored forest itself is
-// written by forest_level_kernel (forest_kernels.hpp), one launch per level: only the buffers the host passes differ.
-//
-// Layout (vkmr_hip_reduce_forest_tree_async, forest_plan.hpp): level 0 is the caller's leaves, tree t at cell offsets[t];
-// level l >= 1 has its own buffer of level_cells(l) cells starting at cell base[l] = sum of level_cells(j) over 1 <= j < l,
-// and tree t's n_l = ceil(c_t / 2^l) nodes start at cell pos_l(t) = (offsets[t] >> l) + t of it.  Level h_t of a tree is its
-// root and lies in roots_dev, not here; a proof reads levels 0 .. h_t - 1 only.
+// forest_tree_kernels.hpp -- the stored forest's proof gather, the batch verifier for proofs of unequal height, the leaf update
+// and the multiproofs (include/vkmr_hip.h: vkmr_hip_forest_proofs_async, vkmr_hip_verify_forest_proofs_async,
+// vkmr_hip_forest_update_async, vkmr_hip_forest_multiproof_async, vkmr_hip_verify_forest_multiproof_async).  The stored forest
+// itself is written by forest_level_kernel (forest_kernels.hpp), one launch per level: only the buffers the host passes
+// differ.  The layout, and the bodies of the kernels that have a counterpart in tree_kernels.hpp, are in entries.hpp: such a
+// kernel here is its arguments as ForestEntries and ForestCells / ForestSpan, and the call.  Every lane is one entry q < k,
+// the pair (trees[q], indices[q]); the updates and the multiproofs take the pairs strictly increasing, so the entries of one
+// tree are adjacent and, inside a tree, lanes with the same node are.
 #pragma once
 
-#include "forest_plan.hpp"
 #include "tree_kernels.hpp"
 
-// First cell of every level's buffer inside the stored forest, passed by value as TreeLevels is.  base[0] is unused:
-// level 0 is the leaves buffer.
-struct ForestLevels { uint64_t base[VKMR_TREE_MAX_LEVELS]; };
-
 // Gather, one lane per (query, level) pair, flattened as i = q * H + l: lane i stores siblings[i], so the 64 lanes of a
-// wavefront write 2 KiB back to back.  Query q is leaf indices[q] of tree trees[q]; for l < h_t the cell is
-// L_t[l][p ^ 1] with p = index >> l, or L_t[l][p] where p ^ 1 is past the level's end (tree_proofs_kernel's rule on tree t
-// alone), for l >= h_t it is zero.  A tree >= ntrees or an index >= c_t gets height 0 and zero cells.  The lane of l == 0
-// writes the height.  No hash: the count-leading-zeros of height() costs nothing that matters here.
+// wavefront write 2 KiB back to back.  Query q is leaf indices[q] of tree trees[q]; for l < h_t the cell is the sibling cell
+// of (l, index) in tree t alone, for l >= h_t it is zero.  A tree >= ntrees or an index >= c_t gets height 0 and zero
+// cells.  The lane of l == 0 writes the height.  No hash: the count-leading-zeros of height() costs nothing that matters here.
 __global__ __launch_bounds__(256) void forest_proofs_kernel(const Node* __restrict__ digests, const Node* __restrict__ forest, ForestLevels lv,
                                                             const uint64_t* __restrict__ offsets, uint32_t ntrees, uint32_t H,
                                                             const uint32_t* __restrict__ trees, const uint64_t* __restrict__ indices, uint64_t total,
@@ -34,15 +28,11 @@ __global__ __launch_bounds__(256) void forest_proofs_kernel(const Node* __restri
     uint32_t o[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t h = 0;
     if (t < ntrees) {
-        const uint64_t off = offsets[t], c = offsets[t + 1u] - off;
+        const uint64_t c = offsets[t + 1u] - offsets[t];
         if (index < c) {                               // never true for an empty tree
             h = vkmr_forest::height(c);                // <= H: the build checked c <= max_count
             if (l < h) {
-                const uint64_t n = vkmr_forest::level_count(c, l);
-                const uint64_t p = index >> l;
-                const uint64_t s = vkmr_math::sibling(p, n);
-                const Node* cell = (l == 0) ? digests + off + s : forest + lv.base[l] + vkmr_forest::pos(off, t, l) + s;
-                const Node v = vkmr_dev::load_node(cell);
+                const Node v = vkmr_dev::load_node(ForestCells{digests, forest, lv, offsets}.sibling_cell(t, l, index));
 #pragma unroll
                 for (int w = 0; w < 8; ++w) o[w] = v.w[w];
             }
@@ -52,8 +42,8 @@ __global__ __launch_bounds__(256) void forest_proofs_kernel(const Node* __restri
     if (l == 0) heights[q] = h;
 }
 
-// Batch verifier, one lane per proof: verify_proofs_kernel's body with a height per lane.  Proof q is valid to fold when
-// 1 <= heights[q] <= stride, indices[q] < 2^heights[q] and trees[q] < ntrees; it then folds leaves[q] with
+// Batch verifier, one lane per proof: verify_proofs_kernel's scheme with a height per lane, in a body of its own (the loop
+// here is ballot-driven, with per-lane selects and a cap on the scalar registers).  Proof q is valid to fold when 1 <= heights[q] <= stride, indices[q] < 2^heights[q] and trees[q] < ntrees; it then folds leaves[q] with
 // siblings[q * stride + 0 .. heights[q]) as vkmr_host_cpu_fold_proof does and is compared with roots[trees[q]].  The level
 // loop runs while any lane of the wavefront still has a level to fold -- a ballot, so the trip count is wave-uniform and the
 // loop's one hash_pair is the kernel's only hash block -- and a lane that has reached its own height keeps its value by a
@@ -100,4 +90,124 @@ void verify_forest_proofs_kernel(const Node* __restrict__ leaves, const uint32_t
         for (int w = 0; w < 8; ++w) diff |= cur.w[w] ^ root.w[w];
     }
     ok[q] = diff == 0u ? 1u : 0u;
+}
+
+// ---- leaf updates (vkmr_hip_forest_update_async): the check, then entries.hpp's two writers -------------------------------
+
+// No hash: bit 0 when trees[q] >= ntrees or indices[q] >= c_t (the offsets are read only for a tree in range; every entry
+// into an empty tree sets it), bit 1 when (trees[q-1], indices[q-1]) >= (trees[q], indices[q]) lexicographically (out of
+// order or repeated).
+__global__ __launch_bounds__(256) void forest_update_check_kernel(const uint64_t* __restrict__ offsets, uint32_t ntrees, const uint32_t* __restrict__ trees,
+                                                                  const uint64_t* __restrict__ indices, uint32_t k, uint32_t* __restrict__ status)
+{
+    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= k) return;
+    const uint32_t t = trees[q];
+    const uint64_t index = indices[q];
+    uint32_t bits = 1u;
+    if (t < ntrees && index < offsets[t + 1u] - offsets[t]) bits = 0u;
+    if (q > 0) {
+        const uint32_t t0 = trees[q - 1];
+        if (t0 > t || (t0 == t && indices[q - 1] >= index)) bits |= 2u;
+    }
+    if (bits) atomicOr(status, bits);
+}
+
+__global__ __launch_bounds__(256) void forest_update_leaves_kernel(Node* __restrict__ digests, const uint64_t* __restrict__ offsets,
+                                                                   const uint32_t* __restrict__ trees, const uint64_t* __restrict__ indices,
+                                                                   const Node* __restrict__ leaves, uint32_t k, const uint32_t* __restrict__ status)
+{
+    update_leaves(ForestEntries{trees, indices}, ForestSpan{offsets}, digests, leaves, k, status);
+}
+
+// in = the buffer of level l - 1 (the leaves for l == 1), out = the buffer of level l.  The check ran first: index_q < c_t, so
+// p is a node of level l and every cell read is one of tree t's own.
+__global__ __launch_bounds__(256) void forest_update_level_kernel(const Node* __restrict__ in, Node* __restrict__ out, Node* __restrict__ roots,
+                                                                  const uint64_t* __restrict__ offsets, const uint32_t* __restrict__ trees,
+                                                                  const uint64_t* __restrict__ indices, uint32_t k, uint32_t l,
+                                                                  const uint32_t* __restrict__ status)
+{
+    update_level(ForestEntries{trees, indices}, ForestSpan{offsets}, in, out, roots, k, l, status);
+}
+
+// ---- multiproofs (vkmr_hip_forest_multiproof_async, vkmr_hip_verify_forest_multiproof_async): the scheme is in entries.hpp,
+// the ranking kernels in tree_kernels.hpp, launched with height := the forest's stride --------------------------------------
+
+// No hash: heights[q] = h_t = max(1, ceil(log2 c_t)) of entry q's tree (a count-leading-zeros, as forest_proofs_kernel).  The
+// check ran first: the tree is one of the forest's and holds a leaf.  One tree's height is an argument: no counterpart.
+__global__ __launch_bounds__(256) void forest_multiproof_heights_kernel(const uint64_t* __restrict__ offsets, const uint32_t* __restrict__ trees,
+                                                                        uint32_t k, const uint64_t* __restrict__ hdr, uint32_t* __restrict__ heights)
+{
+    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= k || hdr[0] != 0ull) return;
+    const uint32_t t = trees[q];
+    heights[q] = vkmr_forest::height(offsets[t + 1u] - offsets[t]);
+}
+
+// The verifier's check (no hash; the heights are the caller's and nothing is trusted): bit 0 when trees[q] >= ntrees, the
+// height is outside 1..stride or indices[q] >= 2^height; bit 1 when the pairs are not strictly increasing (the two bits of
+// forest_update_check_kernel, with 2^height in the place of c_t); bit 3 when the entry in front names the same tree with
+// another height.
+__global__ __launch_bounds__(256) void verify_forest_multiproof_check_kernel(const uint32_t* __restrict__ trees, const uint64_t* __restrict__ indices,
+                                                                             const uint32_t* __restrict__ heights, uint32_t k, uint32_t stride,
+                                                                             uint32_t ntrees, uint32_t* __restrict__ status)
+{
+    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= k) return;
+    const uint32_t t = trees[q], h = heights[q];
+    const uint64_t index = indices[q];
+    uint32_t bits = 1u;
+    if (t < ntrees && h >= 1u && h <= stride && (index >> h) == 0ull) bits = 0u;   // stride <= 63
+    if (q > 0) {
+        const uint32_t t0 = trees[q - 1];
+        if (t0 > t || (t0 == t && indices[q - 1] >= index)) bits |= 2u;
+        if (t0 == t && heights[q - 1] != h) bits |= 8u;
+    }
+    if (bits) atomicOr(status, bits);
+}
+
+__global__ __launch_bounds__(256) void forest_multiproof_masks_kernel(const uint32_t* __restrict__ trees, const uint64_t* __restrict__ indices,
+                                                                      const uint32_t* __restrict__ heights, uint32_t k, uint32_t stride, uint64_t words,
+                                                                      const uint64_t* __restrict__ hdr, uint64_t* __restrict__ mask)
+{
+    multiproof_masks(ForestEntries{trees, indices, heights}, k, stride, words, hdr, mask);
+}
+
+// The check ran first: the tree is in range and index < c_t, so p is a node of the tree's level l.
+__global__ __launch_bounds__(256) void forest_multiproof_gather_kernel(const Node* __restrict__ digests, const Node* __restrict__ forest, ForestLevels lv,
+                                                                       const uint64_t* __restrict__ offsets, const uint32_t* __restrict__ trees,
+                                                                       const uint64_t* __restrict__ indices, uint32_t k, uint64_t words,
+                                                                       const uint64_t* __restrict__ mask, const uint64_t* __restrict__ word_start,
+                                                                       const uint64_t* __restrict__ hdr, Node* __restrict__ nodes)
+{
+    multiproof_gather(ForestEntries{trees, indices}, ForestCells{digests, forest, lv, offsets}, k, words, mask, word_start, hdr, nodes);
+}
+
+// One launch per level l = 0..stride-1.
+__global__ __launch_bounds__(256) void verify_forest_multiproof_level_kernel(const Node* __restrict__ in, Node* __restrict__ cell, uint32_t* __restrict__ end,
+                                                                             const uint32_t* __restrict__ trees, const uint64_t* __restrict__ indices,
+                                                                             const uint32_t* __restrict__ heights, uint32_t k, uint32_t l, uint64_t words,
+                                                                             const uint64_t* __restrict__ mask, const uint64_t* __restrict__ word_start,
+                                                                             const Node* __restrict__ nodes, const uint64_t* __restrict__ hdr)
+{
+    multiproof_verify_level(ForestEntries{trees, indices, heights}, in, cell, end, k, l, words, mask, word_start, nodes, hdr);
+}
+
+// One lane per entry; *ok was set to 1 before the launch.  A nonzero status (a check failed, or not exactly m nodes would be
+// consumed) clears it; else the first entry of each tree's run compares its cell, the tree's root, with roots[trees[q]], and
+// any mismatch clears it.  Roots of trees no entry names are not read.  One lane per tree run; the single tree's finish is
+// one lane against one root, so the two stay apart.
+__global__ __launch_bounds__(256) void verify_forest_multiproof_finish_kernel(const Node* __restrict__ cell, const uint32_t* __restrict__ trees, uint32_t k,
+                                                                              const Node* __restrict__ roots, const uint64_t* __restrict__ hdr,
+                                                                              uint32_t* __restrict__ ok)
+{
+    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= k) return;
+    if (hdr[0] != 0ull) {
+        if (q == 0) ok[0] = 0u;                  // the cells are only written when the status is 0
+        return;
+    }
+    const uint32_t t = trees[q];
+    if (q > 0 && trees[q - 1] == t) return;      // not the first entry of its tree
+    if (vkmr_dev::node_diff(vkmr_dev::load_node(cell + q), vkmr_dev::load_node(roots + t)) != 0u) ok[0] = 0u;
 }

@@ -9,6 +9,71 @@
 #include "cpu_sha256d.hpp"
 #include "vkmr_hip.h"
 
+namespace {
+
+// The node over `cur` and the node beside it: `other` is the left operand when cur is a right child.
+void pair_beside(const vkmr_digest& cur, const vkmr_digest& other, bool right, vkmr_digest* out)
+{
+    if (right)
+        vkmr::cpu_sha256d_pair(other.data, cur.data, out->data);
+    else
+        vkmr::cpu_sha256d_pair(cur.data, other.data, out->data);
+}
+
+// One level of a multiproof over the sorted, unique nodes pos[] of one tree: pairs p with p + 1 when both are there, else
+// takes p alone.  node(i, out, both) is called for each -- pos[i] is the node, both says that pos[i + 1] is its right sibling,
+// out is where the parent goes (out <= i: written behind what is still to be read) -- and may end the walk by returning
+// false, which level_walk then returns too.  pos[] becomes the parents.
+template <class Each>
+bool level_walk(std::vector<uint64_t>& pos, Each node)
+{
+    size_t out = 0;
+    for (size_t i = 0; i < pos.size();) {   // the children of one parent are adjacent
+        const uint64_t p = pos[i];
+        const bool both = !(p & 1ull) && i + 1 < pos.size() && pos[i + 1] == p + 1;
+        if (!node(i, out, both)) return false;
+        i += both ? 2 : 1;
+        pos[out++] = p >> 1;
+    }
+    pos.resize(out);
+    return true;
+}
+
+// The entries [a, b) of one tree (sorted, unique): adds to per_level[l], l < h, the nodes its multiproof emits at level l.
+// Index arithmetic only: a node is emitted for every p of A_l whose sibling p ^ 1 is not in A_l.
+void forest_multiproof_counts(const uint64_t* indices, uint32_t a, uint32_t b, uint32_t h, uint64_t* per_level)
+{
+    std::vector<uint64_t> cur(indices + a, indices + b);
+    for (uint32_t l = 0; l < h; ++l)
+        level_walk(cur, [&](size_t, size_t, bool both) {
+            if (!both) ++per_level[l];
+            return true;
+        });
+}
+
+// First entry behind the run of entries that name trees[a].
+uint32_t forest_run_end(const uint32_t* trees, uint32_t a, uint32_t k)
+{
+    uint32_t b = a + 1;
+    while (b < k && trees[b] == trees[a]) ++b;
+    return b;
+}
+
+// levels[l], l < h, of the tree over the leaves [first, last): level 0 the leaves themselves.
+void tree_levels(const vkmr_digest* first, const vkmr_digest* last, uint32_t h, std::vector<std::vector<vkmr_digest>>& levels)
+{
+    levels.assign(h, {});
+    levels[0].assign(first, last);
+    for (uint32_t l = 1; l < h; ++l) {
+        const std::vector<vkmr_digest>& in = levels[l - 1];
+        levels[l].resize((in.size() + 1) / 2);
+        for (size_t j = 0; j < levels[l].size(); ++j)
+            vkmr::cpu_sha256d_pair(in[2 * j].data, in[vkmr_math::right_child(j, in.size())].data, levels[l][j].data);
+    }
+}
+
+}  // namespace
+
 extern "C" {
 
 // Leaf digests of a packed batch with the CPU backend (CpuSha256D::Add per string).
@@ -60,18 +125,13 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_combine(const vkmr_dige
 __attribute__((visibility("default"))) void vkmr_host_cpu_fold_proof(const vkmr_digest* leaf, uint64_t index, const vkmr_digest* siblings,
                                                                       uint32_t height, vkmr_digest* root)
 {
-    uint32_t cur[8];
-    std::memcpy(cur, leaf->data, 32);
+    vkmr_digest cur = *leaf;
     for (uint32_t l = 0; l < height; ++l) {
-        uint32_t next[8];
-        const bool right = (l < 64) && ((index >> l) & 1ull);
-        if (right)
-            vkmr::cpu_sha256d_pair(siblings[l].data, cur, next);
-        else
-            vkmr::cpu_sha256d_pair(cur, siblings[l].data, next);
-        std::memcpy(cur, next, 32);
+        vkmr_digest next;
+        pair_beside(cur, siblings[l], (l < 64) && ((index >> l) & 1ull), &next);
+        cur = next;
     }
-    std::memcpy(root->data, cur, 32);
+    *root = cur;
 }
 
 // Multiproof verification on the CPU, by the rule of vkmr_hip_verify_multiproof_async: 1 when the indices are strictly
@@ -87,28 +147,15 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_verify_multiproof(const
     std::vector<vkmr_digest> cur(leaves, leaves + k);
     uint64_t used = 0;
     for (uint32_t l = 0; l < height; ++l) {
-        size_t out = 0;
-        for (size_t i = 0; i < pos.size();) {   // pos is strictly increasing: the children of one parent are adjacent
-            const uint64_t p = pos[i];
-            const bool both = !(p & 1ull) && i + 1 < pos.size() && pos[i + 1] == p + 1;
-            const vkmr_digest* other;
-            if (both) {
-                other = &cur[i + 1];
-            } else {
-                if (used >= m) return 0;
-                other = &nodes[used++];
-            }
+        const bool enough = level_walk(pos, [&](size_t i, size_t out, bool both) {
+            if (!both && used >= m) return false;
             vkmr_digest h;
-            if (p & 1ull)
-                vkmr::cpu_sha256d_pair(other->data, cur[i].data, h.data);
-            else
-                vkmr::cpu_sha256d_pair(cur[i].data, other->data, h.data);
-            i += both ? 2 : 1;
-            pos[out] = p >> 1;          // out <= i: written behind what is still to be read
-            cur[out++] = h;
-        }
-        pos.resize(out);
-        cur.resize(out);
+            pair_beside(cur[i], both ? cur[i + 1] : nodes[used++], pos[i] & 1ull, &h);
+            cur[out] = h;
+            return true;
+        });
+        if (!enough) return 0;
+        cur.resize(pos.size());
     }
     return used == m && pos.size() == 1 && pos[0] == 0 && std::memcmp(cur[0].data, root->data, 32) == 0 ? 1 : 0;
 }
@@ -170,16 +217,7 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_forest_proofs(const vkm
         const uint32_t q = order[i], t = trees[q];
         const uint64_t c = offsets[t + 1] - offsets[t];
         const uint32_t h = vkmr_math::height(c);
-        if (i == 0 || trees[order[i - 1]] != t) {
-            levels.assign(h, {});
-            levels[0].assign(digests + offsets[t], digests + offsets[t + 1]);
-            for (uint32_t l = 1; l < h; ++l) {
-                const std::vector<vkmr_digest>& in = levels[l - 1];
-                levels[l].resize((in.size() + 1) / 2);
-                for (size_t j = 0; j < levels[l].size(); ++j)
-                    vkmr::cpu_sha256d_pair(in[2 * j].data, in[vkmr_math::right_child(j, in.size())].data, levels[l][j].data);
-            }
-        }
+        if (i == 0 || trees[order[i - 1]] != t) tree_levels(digests + offsets[t], digests + offsets[t + 1], h, levels);
         heights[q] = h;
         for (uint32_t l = 0; l < h; ++l) {
             siblings[(size_t)q * stride + l] = levels[l][vkmr_math::sibling(indices[q] >> l, levels[l].size())];
@@ -187,40 +225,6 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_forest_proofs(const vkm
     }
     return 0;
 }
-
-}  // extern "C"
-
-namespace {
-
-// The entries [a, b) of one tree (sorted, unique): adds to per_level[l], l < h, the nodes its multiproof emits at level l.
-// Index arithmetic only: a node is emitted for every p of A_l whose sibling p ^ 1 is not in A_l.
-void forest_multiproof_counts(const uint64_t* indices, uint32_t a, uint32_t b, uint32_t h, uint64_t* per_level)
-{
-    std::vector<uint64_t> cur(indices + a, indices + b);
-    for (uint32_t l = 0; l < h; ++l) {
-        size_t out = 0;
-        for (size_t i = 0; i < cur.size();) {
-            const bool both = !(cur[i] & 1ull) && i + 1 < cur.size() && cur[i + 1] == cur[i] + 1;
-            if (!both) ++per_level[l];
-            const uint64_t P = cur[i] >> 1;
-            i += both ? 2 : 1;
-            cur[out++] = P;            // out <= i: written behind what is still to be read
-        }
-        cur.resize(out);
-    }
-}
-
-// First entry behind the run of entries that name trees[a].
-uint32_t forest_run_end(const uint32_t* trees, uint32_t a, uint32_t k)
-{
-    uint32_t b = a + 1;
-    while (b < k && trees[b] == trees[a]) ++b;
-    return b;
-}
-
-}  // namespace
-
-extern "C" {
 
 // Multiproof for leaves of many trees on the CPU, by the rule of vkmr_hip_forest_multiproof_async: entry q is leaf indices[q]
 // of tree trees[q] (tree t: digests[offsets[t] .. offsets[t+1])), the pairs strictly increasing; nodes[] receives the M nodes
@@ -272,26 +276,13 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_forest_multiproof(const
     for (uint32_t a = 0; a < k;) {
         const uint32_t b = forest_run_end(trees, a, k), t = trees[a];
         const uint32_t h = heights[a];
-        levels.assign(h, {});
-        levels[0].assign(digests + offsets[t], digests + offsets[t + 1]);
-        for (uint32_t l = 1; l < h; ++l) {
-            const std::vector<vkmr_digest>& in = levels[l - 1];
-            levels[l].resize((in.size() + 1) / 2);
-            for (size_t j = 0; j < levels[l].size(); ++j)
-                vkmr::cpu_sha256d_pair(in[2 * j].data, in[vkmr_math::right_child(j, in.size())].data, levels[l][j].data);
-        }
+        tree_levels(digests + offsets[t], digests + offsets[t + 1], h, levels);
         std::vector<uint64_t> cur(indices + a, indices + b);
-        for (uint32_t l = 0; l < h; ++l) {
-            size_t out = 0;
-            for (size_t i = 0; i < cur.size();) {
-                const uint64_t p = cur[i];
-                const bool both = !(p & 1ull) && i + 1 < cur.size() && cur[i + 1] == p + 1;
-                if (!both) nodes[at[l]++] = levels[l][vkmr_math::sibling(p, levels[l].size())];
-                i += both ? 2 : 1;
-                cur[out++] = p >> 1;
-            }
-            cur.resize(out);
-        }
+        for (uint32_t l = 0; l < h; ++l)
+            level_walk(cur, [&](size_t i, size_t, bool both) {
+                if (!both) nodes[at[l]++] = levels[l][vkmr_math::sibling(cur[i], levels[l].size())];
+                return true;
+            });
         a = b;
     }
     return 0;
@@ -331,22 +322,13 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_verify_forest_multiproo
         std::vector<uint64_t> pos(indices + a, indices + b);
         std::vector<vkmr_digest> cur(leaves + a, leaves + b);
         for (uint32_t l = 0; l < h; ++l) {
-            size_t out = 0;
-            for (size_t i = 0; i < pos.size();) {
-                const uint64_t p = pos[i];
-                const bool both = !(p & 1ull) && i + 1 < pos.size() && pos[i + 1] == p + 1;
-                const vkmr_digest* other = both ? &cur[i + 1] : &nodes[at[l]++];   // at[l] < the level's end: the counts above
+            level_walk(pos, [&](size_t i, size_t out, bool both) {
                 vkmr_digest x;
-                if (p & 1ull)
-                    vkmr::cpu_sha256d_pair(other->data, cur[i].data, x.data);
-                else
-                    vkmr::cpu_sha256d_pair(cur[i].data, other->data, x.data);
-                i += both ? 2 : 1;
-                pos[out] = p >> 1;
-                cur[out++] = x;
-            }
-            pos.resize(out);
-            cur.resize(out);
+                pair_beside(cur[i], both ? cur[i + 1] : nodes[at[l]++], pos[i] & 1ull, &x);   // at[l] < the level's end: the counts above
+                cur[out] = x;
+                return true;
+            });
+            cur.resize(pos.size());
         }
         if (pos.size() != 1 || pos[0] != 0 || std::memcmp(cur[0].data, roots[trees[a]].data, 32) != 0) return 0;
         a = b;

@@ -5,6 +5,7 @@
 //   reduce_kernels.hpp  reduce_pass_kernel     streaming sub-tree collapse per wave (SHA-256.comp:325-391)
 //                       reduce_collapse_kernel / reduce_tail_kernel   the latency-bound top, __shfl_down
 //                       reduce_level_kernel    one level per launch, cross-check    (SHA-256.comp:393-434); builds the stored tree
+//   entries.hpp         what one stored tree and a stored forest differ in (entries, cells), and one body per operation they share
 //   tree_kernels.hpp    tree_proofs_kernel     proofs gathered from the stored tree (README.md:118-120)
 //                       verify_proofs_kernel   batch proof verification, one lane per proof (no reference counterpart)
 //                       tree_update_*_kernel   leaf updates: check, store the leaves, rehash the dirty nodes level by level
@@ -14,10 +15,9 @@
 //                                              whole forest, level by level (no reference counterpart); builds the stored forest
 //   forest_tree_kernels.hpp  forest_proofs_kernel          proofs gathered from the stored forest, one lane per (query, level)
 //                            verify_forest_proofs_kernel   batch verification of proofs of unequal height, one lane per proof
-//   forest_update_kernels.hpp  forest_update_*_kernel   leaf updates of the stored forest: check, store the leaves, rehash the
-//                                              dirty nodes of every touched tree level by level
-//   forest_multiproof_kernels.hpp  forest_multiproof_*_kernel, verify_forest_multiproof_*_kernel   one proof for leaves of many
-//                                              trees: tree_kernels.hpp's ranking with a tree and a height per entry
+//                            forest_update_*_kernel        leaf updates of the stored forest: tree_update_*'s bodies, a tree per entry
+//                            forest_multiproof_*_kernel, verify_forest_multiproof_*_kernel   one proof for leaves of many trees:
+//                                              the multiproof bodies and tree_kernels.hpp's ranking, a tree and a height per entry
 //   sha256d_device.hpp  the SHA-256 round / compression building blocks, and the tree's: hash_parent, node_diff, store_node
 //   merkle_math.hpp     the integer rules, no HIP types (ceil_shift, height, right_child, sibling): shared with host/ and tests/c
 //   meta_kernels.hpp    sizes_*_kernel         metadata entries from 16-bit sizes   (Batches.cpp:64-121)
@@ -48,8 +48,6 @@ using vkmr_dev::Node;
 #include "tree_kernels.hpp"
 #include "forest_kernels.hpp"
 #include "forest_tree_kernels.hpp"
-#include "forest_update_kernels.hpp"
-#include "forest_multiproof_kernels.hpp"
 
 // ============================================================================
 // C ABI
@@ -91,6 +89,13 @@ static inline Node* nodes(void* p) { return static_cast<Node*>(p); }
 static inline uint64_t groups_of(uint64_t items) { return (items + 255) / 256; }
 static inline dim3 grid_of(uint64_t items, uint32_t y = 1) { return dim3((uint32_t)groups_of(items), y); }
 static inline bool grid_too_large(uint64_t groups) { return groups > 0x7fffffffull; }
+// A refusal in the words "<entry point>: <why>".
+static vkmr_status refuse(const char* who, const char* why)
+{
+    char what[128];
+    snprintf(what, sizeof what, "%s: %s", who, why);
+    return fail(VKMR_ERR_INVALID, what);
+}
 
 extern "C" {
 
@@ -909,30 +914,38 @@ size_t vkmr_hip_multiproof_scratch_bytes(uint32_t k, uint32_t height)
     return multiproof_layout(k, height).bytes;
 }
 
-// The launches both calls share: the index check into hdr[0], then the ranking of the emit flags (masks, block sums, block
-// starts, word starts).  `count` is the bound of the index check; limit / exact as multiproof_block_starts_kernel takes them.
-static vkmr_status multiproof_rank_launch(hipStream_t stream, const uint64_t* indices_dev, uint32_t k, uint64_t count, uint32_t height,
-                                          const MultiproofLayout& L, char* scratch, uint64_t* hdr, uint64_t limit, uint32_t exact)
+// The ranking launches every multiproof call shares, behind its own check and masks kernel: block sums, block starts, word
+// starts.  `levels` is one tree's height or a forest's stride; limit / exact as multiproof_block_starts_kernel takes them.
+static vkmr_status multiproof_rank_launch(hipStream_t stream, uint32_t levels, const MultiproofLayout& L, char* scratch, uint64_t* hdr, uint64_t limit,
+                                          uint32_t exact)
 {
-    const dim3 grid = grid_of(k);
-    VKMR_TRY(hipMemsetAsync(hdr, 0, (height == 0 ? 2 : 1) * sizeof(uint64_t), stream));
-    hipLaunchKernelGGL(tree_update_check_kernel, grid, dim3(256), 0, stream, indices_dev, k, count, reinterpret_cast<uint32_t*>(hdr));
-    VKMR_TRY(hipGetLastError());
-    if (height == 0) return VKMR_OK;
-    uint64_t* mask = reinterpret_cast<uint64_t*>(scratch + L.mask);
+    const uint64_t* mask = reinterpret_cast<const uint64_t*>(scratch + L.mask);
     uint64_t* word_start = reinterpret_cast<uint64_t*>(scratch + L.word_start);
     uint64_t* block = reinterpret_cast<uint64_t*>(scratch + L.block);
-    const dim3 wgrid((uint32_t)L.blocks, height);
-    hipLaunchKernelGGL(multiproof_masks_kernel, grid, dim3(256), 0, stream, indices_dev, k, height, L.words, mask);
+    const dim3 wgrid((uint32_t)L.blocks, levels);
+    hipLaunchKernelGGL(multiproof_block_sums_kernel, wgrid, dim3(VKMR_MP_BLOCK_WORDS), 0, stream, mask, L.words, L.blocks, block);
     VKMR_TRY(hipGetLastError());
-    hipLaunchKernelGGL(multiproof_block_sums_kernel, wgrid, dim3(VKMR_MP_BLOCK_WORDS), 0, stream, (const uint64_t*)mask, L.words, L.blocks, block);
+    hipLaunchKernelGGL(multiproof_block_starts_kernel, dim3(1), dim3(256), 0, stream, block, L.blocks, levels, limit, exact, hdr);
     VKMR_TRY(hipGetLastError());
-    hipLaunchKernelGGL(multiproof_block_starts_kernel, dim3(1), dim3(256), 0, stream, block, L.blocks, height, limit, exact, hdr);
-    VKMR_TRY(hipGetLastError());
-    hipLaunchKernelGGL(multiproof_word_starts_kernel, wgrid, dim3(VKMR_MP_BLOCK_WORDS), 0, stream, (const uint64_t*)mask, L.words, L.blocks,
-                       (const uint64_t*)block, (const uint64_t*)hdr, word_start);
+    hipLaunchKernelGGL(multiproof_word_starts_kernel, wgrid, dim3(VKMR_MP_BLOCK_WORDS), 0, stream, mask, L.words, L.blocks, (const uint64_t*)block,
+                       (const uint64_t*)hdr, word_start);
     VKMR_TRY(hipGetLastError());
     return VKMR_OK;
+}
+
+// The single tree's check and flags in front of the ranking: the index check into hdr[0] with `count` as its bound, then the
+// masks.  A tree of one leaf (height 0) has no level to rank: the check alone, and M = 0.
+static vkmr_status tree_multiproof_rank_launch(hipStream_t stream, const uint64_t* indices_dev, uint32_t k, uint64_t count, uint32_t height,
+                                               const MultiproofLayout& L, char* scratch, uint64_t* hdr, uint64_t limit, uint32_t exact)
+{
+    VKMR_TRY(hipMemsetAsync(hdr, 0, (height == 0 ? 2 : 1) * sizeof(uint64_t), stream));
+    hipLaunchKernelGGL(tree_update_check_kernel, grid_of(k), dim3(256), 0, stream, indices_dev, k, count, reinterpret_cast<uint32_t*>(hdr));
+    VKMR_TRY(hipGetLastError());
+    if (height == 0) return VKMR_OK;
+    hipLaunchKernelGGL(multiproof_masks_kernel, grid_of(k), dim3(256), 0, stream, indices_dev, k, height, L.words, (const uint64_t*)hdr,
+                       reinterpret_cast<uint64_t*>(scratch + L.mask));
+    VKMR_TRY(hipGetLastError());
+    return multiproof_rank_launch(stream, height, L, scratch, hdr, limit, exact);
 }
 
 vkmr_status vkmr_hip_tree_multiproof_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* tree_dev, uint64_t count,
@@ -949,7 +962,7 @@ vkmr_status vkmr_hip_tree_multiproof_async(int dev, vkmr_stream s, const vkmr_di
     const MultiproofLayout L = multiproof_layout(k, height);
     char* scratch = static_cast<char*>(scratch_dev);
     VKMR_TRY(hipSetDevice(dev));
-    const vkmr_status st = multiproof_rank_launch(S(s), indices_dev, k, count, height, L, scratch, info_dev, nodes_capacity, 0u);
+    const vkmr_status st = tree_multiproof_rank_launch(S(s), indices_dev, k, count, height, L, scratch, info_dev, nodes_capacity, 0u);
     if (st != VKMR_OK || height == 0) return st;
     hipLaunchKernelGGL(tree_multiproof_gather_kernel, grid_of(k, height), dim3(256), 0, S(s), nodes(digests_dev), nodes(tree_dev), lv, count,
                        indices_dev, k, L.words, reinterpret_cast<const uint64_t*>(scratch + L.mask),
@@ -972,7 +985,7 @@ vkmr_status vkmr_hip_verify_multiproof_async(int dev, vkmr_stream s, const vkmr_
     Node* cell = nodes(scratch + L.cell);
     VKMR_TRY(hipSetDevice(dev));
     // the index check with 2^height as the bound: bit 0 an index outside the tree, bit 1 not strictly increasing; exact: M == m
-    const vkmr_status st = multiproof_rank_launch(S(s), indices_dev, k, 1ull << height, height, L, scratch, hdr, m, 1u);
+    const vkmr_status st = tree_multiproof_rank_launch(S(s), indices_dev, k, 1ull << height, height, L, scratch, hdr, m, 1u);
     if (st != VKMR_OK) return st;
     const dim3 grid = grid_of(k);
     for (uint32_t l = 0; l < height; ++l) {   // level l + 1 from level l, which the previous launch finished
@@ -1004,15 +1017,10 @@ static vkmr_status forest_launch(const char* who, int dev, vkmr_stream s, const 
                                  uint32_t ntrees, uint64_t max_count, const void* buffer_dev, vkmr_digest* roots_dev, uint32_t* status_dev,
                                  LevelBuffer level)
 {
-    auto refuse = [who](const char* why) {
-        char what[128];
-        snprintf(what, sizeof what, "%s: %s", who, why);
-        return fail(VKMR_ERR_INVALID, what);
-    };
-    if ((!digests_dev && total > 0) || !offsets_dev || !buffer_dev || !roots_dev || !status_dev) return refuse("null pointer");
-    if (max_count == 0) return refuse("max_count must be at least 1");
-    if (reinterpret_cast<uintptr_t>(buffer_dev) & 15u) return refuse("the level buffer must be 16-byte aligned");
-    if (total > (1ull << 58) || grid_too_large(groups_of(vkmr_forest::level_cells(total, ntrees, 1)))) return refuse("forest too large");
+    if ((!digests_dev && total > 0) || !offsets_dev || !buffer_dev || !roots_dev || !status_dev) return refuse(who, "null pointer");
+    if (max_count == 0) return refuse(who, "max_count must be at least 1");
+    if (reinterpret_cast<uintptr_t>(buffer_dev) & 15u) return refuse(who, "the level buffer must be 16-byte aligned");
+    if (total > (1ull << 58) || grid_too_large(groups_of(vkmr_forest::level_cells(total, ntrees, 1)))) return refuse(who, "forest too large");
     if (max_count > total) max_count = total;
     const uint32_t levels = vkmr_forest::launches(total, max_count);
     const Node* digests = nodes(digests_dev);
@@ -1059,6 +1067,28 @@ vkmr_status vkmr_hip_reduce_forest_tree_async(int dev, vkmr_stream s, const vkmr
                          status_dev, [&](uint32_t l) { return forest + vkmr_forest::stored_level_base(total, ntrees, l); });
 }
 
+// What the stored forest's entry points refuse alike, behind their null-pointer test, in the order each tests it: a forest
+// without a leaf where the call needs one (`no_leaf` says why; null: an empty forest is fine), no max_count, too many leaves,
+// scratch off the 16-byte grid (null: none to test), more entries than a launch takes.
+static vkmr_status forest_args_check(const char* who, uint64_t total, uint32_t ntrees, uint64_t max_count, uint32_t k, const char* no_leaf,
+                                     const void* scratch_dev)
+{
+    if (no_leaf && (ntrees == 0 || total == 0)) return refuse(who, no_leaf);
+    if (max_count == 0) return refuse(who, "max_count must be at least 1");
+    if (total > (1ull << 58)) return refuse(who, "forest too large");
+    if (reinterpret_cast<uintptr_t>(scratch_dev) & 15u) return refuse(who, "scratch must be 16-byte aligned");
+    if (grid_too_large(groups_of(k))) return refuse(who, "too many entries in one call");
+    return VKMR_OK;
+}
+
+// First cell of the buffer of every level 1..H inside the stored forest (base[0] = 0, unused), as the kernels take it.
+static ForestLevels forest_levels(uint64_t total, uint32_t ntrees, uint32_t H)
+{
+    ForestLevels lv;
+    for (uint32_t l = 0; l < VKMR_TREE_MAX_LEVELS; ++l) lv.base[l] = (l >= 1 && l <= H) ? vkmr_forest::stored_level_base(total, ntrees, l) : 0;
+    return lv;
+}
+
 vkmr_status vkmr_hip_forest_proofs_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* forest_dev, uint64_t total,
                                          const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count, const uint32_t* trees_dev,
                                          const uint64_t* indices_dev, uint32_t k, vkmr_digest* siblings_dev, uint32_t* heights_dev)
@@ -1066,11 +1096,10 @@ vkmr_status vkmr_hip_forest_proofs_async(int dev, vkmr_stream s, const vkmr_dige
     if (k == 0) return VKMR_OK;
     if ((!digests_dev && total > 0) || !forest_dev || !offsets_dev || !trees_dev || !indices_dev || !siblings_dev || !heights_dev)
         return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_proofs_async: null pointer");
-    if (max_count == 0) return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_proofs_async: max_count must be at least 1");
-    if (total > (1ull << 58)) return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_proofs_async: forest too large");
+    const vkmr_status args = forest_args_check("vkmr_hip_forest_proofs_async", total, ntrees, max_count, k, nullptr, nullptr);
+    if (args != VKMR_OK) return args;
     const uint32_t H = vkmr_forest::launches(total, max_count);   // <= 58
-    ForestLevels lv;
-    for (uint32_t l = 0; l < VKMR_TREE_MAX_LEVELS; ++l) lv.base[l] = (l >= 1 && l <= H) ? vkmr_forest::stored_level_base(total, ntrees, l) : 0;
+    const ForestLevels lv = forest_levels(total, ntrees, H);
     const uint64_t cells = (uint64_t)k * H;
     if (grid_too_large(groups_of(cells))) return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_proofs_async: too many proofs in one call");
     VKMR_TRY(hipSetDevice(dev));
@@ -1096,7 +1125,7 @@ vkmr_status vkmr_hip_verify_forest_proofs_async(int dev, vkmr_stream s, const vk
     return VKMR_OK;
 }
 
-// ---- leaf updates of the stored forest (forest_update_kernels.hpp) ---------------------------------------------------------
+// ---- leaf updates of the stored forest (forest_tree_kernels.hpp) -----------------------------------------------------------
 
 vkmr_status vkmr_hip_forest_update_async(int dev, vkmr_stream s, vkmr_digest* digests_dev, vkmr_digest* forest_dev, uint64_t total,
                                          const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count, const uint32_t* trees_dev,
@@ -1106,10 +1135,8 @@ vkmr_status vkmr_hip_forest_update_async(int dev, vkmr_stream s, vkmr_digest* di
     if (k == 0) return VKMR_OK;
     if (!digests_dev || !forest_dev || !offsets_dev || !trees_dev || !indices_dev || !leaves_dev || !roots_dev || !status_dev)
         return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_update_async: null pointer");
-    if (ntrees == 0 || total == 0) return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_update_async: a forest without a leaf has none to update");
-    if (max_count == 0) return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_update_async: max_count must be at least 1");
-    if (total > (1ull << 58)) return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_update_async: forest too large");
-    if (grid_too_large(groups_of(k))) return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_update_async: too many entries in one call");
+    const vkmr_status args = forest_args_check("vkmr_hip_forest_update_async", total, ntrees, max_count, k, "a forest without a leaf has none to update", nullptr);
+    if (args != VKMR_OK) return args;
     const uint32_t H = vkmr_forest::launches(total, max_count);   // <= 58
     const dim3 grid = grid_of(k);
     Node* digests = nodes(digests_dev);
@@ -1131,7 +1158,7 @@ vkmr_status vkmr_hip_forest_update_async(int dev, vkmr_stream s, vkmr_digest* di
     return VKMR_OK;
 }
 
-// ---- multiproofs inside the stored forest (forest_multiproof_kernels.hpp) ---------------------------------------------------
+// ---- multiproofs inside the stored forest (forest_tree_kernels.hpp) ---------------------------------------------------------
 
 size_t vkmr_hip_forest_multiproof_max_nodes(uint64_t total, uint32_t ntrees, uint64_t max_count, uint32_t k)
 {
@@ -1150,29 +1177,6 @@ size_t vkmr_hip_forest_multiproof_scratch_bytes(uint32_t k, uint32_t stride)
     return (vkmr_hip_multiproof_scratch_bytes(k, stride) + 15u) & ~(size_t)15u;   // the single tree's layout with height := stride, in whole 16-byte units
 }
 
-// The ranking launches both forest calls share, behind their own check: the flags, then tree_kernels.hpp's block sums, block
-// starts and word starts with height := stride.  limit / exact as multiproof_block_starts_kernel takes them.
-static vkmr_status forest_multiproof_rank_launch(hipStream_t stream, const uint32_t* trees_dev, const uint64_t* indices_dev,
-                                                 const uint32_t* heights_dev, uint32_t k, uint32_t stride, const MultiproofLayout& L, char* scratch,
-                                                 uint64_t* hdr, uint64_t limit, uint32_t exact)
-{
-    uint64_t* mask = reinterpret_cast<uint64_t*>(scratch + L.mask);
-    uint64_t* word_start = reinterpret_cast<uint64_t*>(scratch + L.word_start);
-    uint64_t* block = reinterpret_cast<uint64_t*>(scratch + L.block);
-    const dim3 wgrid((uint32_t)L.blocks, stride);
-    hipLaunchKernelGGL(forest_multiproof_masks_kernel, grid_of(k), dim3(256), 0, stream, trees_dev, indices_dev, heights_dev, k, stride, L.words,
-                       (const uint64_t*)hdr, mask);
-    VKMR_TRY(hipGetLastError());
-    hipLaunchKernelGGL(multiproof_block_sums_kernel, wgrid, dim3(VKMR_MP_BLOCK_WORDS), 0, stream, (const uint64_t*)mask, L.words, L.blocks, block);
-    VKMR_TRY(hipGetLastError());
-    hipLaunchKernelGGL(multiproof_block_starts_kernel, dim3(1), dim3(256), 0, stream, block, L.blocks, stride, limit, exact, hdr);
-    VKMR_TRY(hipGetLastError());
-    hipLaunchKernelGGL(multiproof_word_starts_kernel, wgrid, dim3(VKMR_MP_BLOCK_WORDS), 0, stream, (const uint64_t*)mask, L.words, L.blocks,
-                       (const uint64_t*)block, (const uint64_t*)hdr, word_start);
-    VKMR_TRY(hipGetLastError());
-    return VKMR_OK;
-}
-
 vkmr_status vkmr_hip_forest_multiproof_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* forest_dev, uint64_t total,
                                              const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count, const uint32_t* trees_dev,
                                              const uint64_t* indices_dev, uint32_t k, void* scratch_dev, vkmr_digest* nodes_dev,
@@ -1182,14 +1186,10 @@ vkmr_status vkmr_hip_forest_multiproof_async(int dev, vkmr_stream s, const vkmr_
     if (!digests_dev || !forest_dev || !offsets_dev || !trees_dev || !indices_dev || !scratch_dev || !heights_dev || !info_dev ||
         (!nodes_dev && nodes_capacity > 0))
         return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_multiproof_async: null pointer");
-    if (ntrees == 0 || total == 0) return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_multiproof_async: a forest without a leaf has none to prove");
-    if (max_count == 0) return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_multiproof_async: max_count must be at least 1");
-    if (total > (1ull << 58)) return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_multiproof_async: forest too large");
-    if (reinterpret_cast<uintptr_t>(scratch_dev) & 15u) return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_multiproof_async: scratch must be 16-byte aligned");
-    if (grid_too_large(groups_of(k))) return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_multiproof_async: too many entries in one call");
+    const vkmr_status args = forest_args_check("vkmr_hip_forest_multiproof_async", total, ntrees, max_count, k, "a forest without a leaf has none to prove", scratch_dev);
+    if (args != VKMR_OK) return args;
     const uint32_t H = vkmr_forest::launches(total, max_count);   // <= 58
-    ForestLevels lv;
-    for (uint32_t l = 0; l < VKMR_TREE_MAX_LEVELS; ++l) lv.base[l] = (l >= 1 && l <= H) ? vkmr_forest::stored_level_base(total, ntrees, l) : 0;
+    const ForestLevels lv = forest_levels(total, ntrees, H);
     const MultiproofLayout L = multiproof_layout(k, H);
     char* scratch = static_cast<char*>(scratch_dev);
     const dim3 grid = grid_of(k);
@@ -1200,7 +1200,10 @@ vkmr_status vkmr_hip_forest_multiproof_async(int dev, vkmr_stream s, const vkmr_
     VKMR_TRY(hipGetLastError());
     hipLaunchKernelGGL(forest_multiproof_heights_kernel, grid, dim3(256), 0, S(s), offsets_dev, trees_dev, k, (const uint64_t*)info_dev, heights_dev);
     VKMR_TRY(hipGetLastError());
-    const vkmr_status st = forest_multiproof_rank_launch(S(s), trees_dev, indices_dev, heights_dev, k, H, L, scratch, info_dev, nodes_capacity, 0u);
+    hipLaunchKernelGGL(forest_multiproof_masks_kernel, grid, dim3(256), 0, S(s), trees_dev, indices_dev, (const uint32_t*)heights_dev, k, H, L.words,
+                       (const uint64_t*)info_dev, reinterpret_cast<uint64_t*>(scratch + L.mask));
+    VKMR_TRY(hipGetLastError());
+    const vkmr_status st = multiproof_rank_launch(S(s), H, L, scratch, info_dev, nodes_capacity, 0u);
     if (st != VKMR_OK) return st;
     hipLaunchKernelGGL(forest_multiproof_gather_kernel, grid_of(k, H), dim3(256), 0, S(s), nodes(digests_dev), nodes(forest_dev), lv, offsets_dev,
                        trees_dev, indices_dev, k, L.words, reinterpret_cast<const uint64_t*>(scratch + L.mask),
@@ -1218,8 +1221,7 @@ vkmr_status vkmr_hip_verify_forest_multiproof_async(int dev, vkmr_stream s, cons
     if (!leaves_dev || !trees_dev || !indices_dev || !heights_dev || !roots_dev || !scratch_dev || !ok_dev || (!nodes_dev && m > 0))
         return fail(VKMR_ERR_INVALID, "vkmr_hip_verify_forest_multiproof_async: null pointer");
     if (stride == 0 || stride > 63) return fail(VKMR_ERR_INVALID, "vkmr_hip_verify_forest_multiproof_async: stride must be 1..63");
-    if (reinterpret_cast<uintptr_t>(scratch_dev) & 15u)
-        return fail(VKMR_ERR_INVALID, "vkmr_hip_verify_forest_multiproof_async: scratch must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(scratch_dev) & 15u) return refuse("vkmr_hip_verify_forest_multiproof_async", "scratch must be 16-byte aligned");
     const MultiproofLayout L = multiproof_layout(k, stride);
     char* scratch = static_cast<char*>(scratch_dev);
     uint64_t* hdr = reinterpret_cast<uint64_t*>(scratch + L.hdr);
@@ -1231,7 +1233,10 @@ vkmr_status vkmr_hip_verify_forest_multiproof_async(int dev, vkmr_stream s, cons
     hipLaunchKernelGGL(verify_forest_multiproof_check_kernel, grid, dim3(256), 0, S(s), trees_dev, indices_dev, heights_dev, k, stride, ntrees,
                        reinterpret_cast<uint32_t*>(hdr));
     VKMR_TRY(hipGetLastError());
-    const vkmr_status st = forest_multiproof_rank_launch(S(s), trees_dev, indices_dev, heights_dev, k, stride, L, scratch, hdr, m, 1u);   // exact: M == m
+    hipLaunchKernelGGL(forest_multiproof_masks_kernel, grid, dim3(256), 0, S(s), trees_dev, indices_dev, heights_dev, k, stride, L.words,
+                       (const uint64_t*)hdr, reinterpret_cast<uint64_t*>(scratch + L.mask));
+    VKMR_TRY(hipGetLastError());
+    const vkmr_status st = multiproof_rank_launch(S(s), stride, L, scratch, hdr, m, 1u);   // exact: M == m
     if (st != VKMR_OK) return st;
     for (uint32_t l = 0; l < stride; ++l) {   // level l + 1 from level l, which the previous launch finished
         hipLaunchKernelGGL(verify_forest_multiproof_level_kernel, grid, dim3(256), 0, S(s), l == 0 ? nodes(leaves_dev) : cell, cell,
