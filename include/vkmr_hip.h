@@ -393,6 +393,47 @@ VKMR_API vkmr_status vkmr_hip_reduce_forest_tree_async(int dev, vkmr_stream s, c
                                                        vkmr_digest* forest_dev, vkmr_digest* roots_dev, uint32_t* status_dev);
 
 /*
+ * MUTATED TREES (CVE-2012-2459): the duplicate-last tree lets different leaf lists share a root -- [a, b, c] and
+ * [a, b, c, c]; [a, b, c, d, e, f] and [a, b, c, d, e, f, e, f] -- so a root alone does not commit to the leaf list.  The
+ * two builds above, with Bitcoin Core's ComputeMerkleRoot(hashes, &mutated) formed in the same launches, the level kept:
+ * mutated_dev[t] (ntrees uint64_t in device memory) gets bit l set iff level l of tree t (n_l = ceil(c_t / 2^l) nodes,
+ * 0 <= l < h_t) holds a j with 2j + 1 < n_l and node 2j equal to node 2j + 1: a pair in which BOTH nodes exist.  The last
+ * node of an odd level, hashed with itself, is no such pair; an empty tree and a tree of one leaf get 0.  A caller who wants
+ * Bitcoin Core's bool tests mutated[t] != 0.  A mutated tree is not refused: its root is written like any other.
+ * Contract, device-side checks, status bits, scratch / forest layout and the launches are those of
+ * vkmr_hip_reduce_forest_async and vkmr_hip_reduce_forest_tree_async (the status word zeroed, the check, one launch per
+ * level; each level launch compares the two children it has loaded for the hash), plus one memset of mutated_dev in the same
+ * sequence; the roots, and every cell of the stored forest, are the plain build's.  A nonzero status leaves mutated_dev all
+ * zero and writes no root.  ntrees == 0 does nothing whatever the other arguments.  Refused on the host (VKMR_ERR_INVALID)
+ * with ntrees > 0, before any HIP call: what the plain build refuses, and a NULL mutated_dev.
+ * vkmr_host_cpu_forest_mutated (libvkmr_host.so) applies the same rule on the CPU, for a receiver without a GPU.
+ */
+VKMR_API vkmr_status vkmr_hip_reduce_forest_mutated_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t total,
+                                                          const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count,
+                                                          void* scratch_dev, vkmr_digest* roots_dev, uint64_t* mutated_dev,
+                                                          uint32_t* status_dev);
+VKMR_API vkmr_status vkmr_hip_reduce_forest_tree_mutated_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t total,
+                                                               const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count,
+                                                               vkmr_digest* forest_dev, vkmr_digest* roots_dev, uint64_t* mutated_dev,
+                                                               uint32_t* status_dev);
+
+/*
+ * THE MASKS OF A STORED FOREST, formed again from its levels as they are now: for a forest whose leaves have changed through
+ * vkmr_hip_forest_update_async, which rehashes paths and compares nothing.  digests_dev and forest_dev as written by
+ * vkmr_hip_reduce_forest_tree_async (or its flagged twin); the call TRUSTS that offsets_dev, total, ntrees and max_count are
+ * those of that build and that the build reported status 0 (the rule of vkmr_hip_forest_proofs_async).  mutated_dev gets
+ * what vkmr_hip_reduce_forest_tree_mutated_async over the present leaves would write.  A compare, no hash: every level below
+ * the roots is read once.  Launches, all on the caller's stream: mutated_dev zeroed, then one launch per level,
+ * H = max(1, ceil(log2 min(max_count, total))) of them, with the build's grid; no allocation, no host read of device data.
+ * Refused on the host (VKMR_ERR_INVALID) with ntrees > 0: a NULL pointer (digests_dev may be NULL when total == 0),
+ * max_count == 0, total > 2^58.  ntrees == 0 does nothing whatever the other arguments.
+ * Stream-ordered: a scan enqueued after an update on the same stream sees the new forest.
+ */
+VKMR_API vkmr_status vkmr_hip_forest_tree_mutated_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev,
+                                                        const vkmr_digest* forest_dev, uint64_t total, const uint64_t* offsets_dev,
+                                                        uint32_t ntrees, uint64_t max_count, uint64_t* mutated_dev);
+
+/*
  * PROOFS FROM THE STORED FOREST ("is leaf i in tree t?"): a gather, no hash.  digests_dev and forest_dev as written by
  * vkmr_hip_reduce_forest_tree_async; the call TRUSTS that offsets_dev, total, ntrees and max_count are those of that build
  * and that the build reported status 0 -- it checks no offset again and follows them into the forest.  Query q is leaf

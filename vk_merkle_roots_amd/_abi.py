@@ -79,6 +79,12 @@ SIGNATURES = {
     "vkmr_hip_forest_tree_bytes": (C.c_size_t, [C.c_uint64, C.c_uint32, C.c_uint64]),
     "vkmr_hip_reduce_forest_tree_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p,
                                                     C.c_void_p, C.c_void_p]),
+    "vkmr_hip_reduce_forest_mutated_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p,
+                                                       C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vkmr_hip_reduce_forest_tree_mutated_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p,
+                                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vkmr_hip_forest_tree_mutated_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64,
+                                                     C.c_void_p]),
     "vkmr_hip_forest_proofs_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p,
                                                C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "vkmr_hip_verify_forest_proofs_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
@@ -112,6 +118,7 @@ HOST_SIGNATURES = {
     "vkmr_host_cpu_fold_proof": (None, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "vkmr_host_cpu_verify_multiproof": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p]),
     "vkmr_host_cpu_forest_roots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "vkmr_host_cpu_forest_mutated": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "vkmr_host_cpu_forest_proofs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
                                               C.c_void_p]),
     "vkmr_host_cpu_forest_multiproof": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,

@@ -30,14 +30,31 @@ __global__ __launch_bounds__(256) void forest_check_kernel(const uint64_t* __res
     if (bits) atomicOr(status, bits);
 }
 
-// Level l >= 1 from level l - 1 (`in`: the leaves for l == 1, else the buffer of level l - 1), `cells` lanes.  The check ran
-// first: the offsets do not decrease and end inside the leaves, so every cell read below is one of tree t's own.  One
-// hash_pair: the kernel's only hash block.
-__global__ __launch_bounds__(256) void forest_level_kernel(const Node* __restrict__ in, const uint64_t* __restrict__ offsets, uint32_t ntrees, uint32_t l,
-                                                           uint64_t cells, Node* __restrict__ out, Node* __restrict__ roots,
-                                                           const uint32_t* __restrict__ status)
+// ---- one level of a forest: the body of the three level kernels below ------------------------------------------------------
+// Level l >= 1 from level l - 1 (`in`: the leaves for l == 1, else the buffer of level l - 1), `cells` lanes, in entries.hpp's
+// manner: one body, and a __global__ kernel is its arguments and the call.  Two compile-time switches say what a lane does with
+// the two children of its node once it has found them:
+//   HASH     parent = hash_pair(children), stored to the level buffer, or to roots[t] when it is the tree's last (the builds).
+//            The check ran first and the body reads *status: the offsets do not decrease and end inside the leaves, so every
+//            cell read is one of tree t's own.  Without HASH nothing is stored and there is no status to read: the caller
+//            vouches for the offsets (vkmr_hip_forest_proofs_async's rule).
+//   COMPARE  the mutation flag (CVE-2012-2459; Bitcoin Core's ComputeMerkleRoot(hashes, &mutated) with the level kept): when
+//            both children exist (2j + 1 < n_in -- right_child() reads the last node twice at a ragged edge, and that is no
+//            pair) and are equal, bit l - 1 is ORed into mutated[t], zeroed by the host.
+// With HASH: one hash_pair, the kernel's only hash block.
+//
+// The atomics.  A forest of all-equal leaves hits in every lane.  A lane reads mutated[t] first and skips the atomic when its
+// bit is there already (a stale read only costs an atomic).  Where every lane of the wavefront has tree t0 -- the search's
+// existing wave-uniform case -- the hits are one ballot and the first hit lane alone issues the atomic; where a tree begins
+// inside the wavefront each hit lane issues its own, at most 64 to at least 2 addresses.
+template <bool HASH, bool COMPARE>
+__device__ __forceinline__ void forest_level(const Node* __restrict__ in, const uint64_t* __restrict__ offsets, uint32_t ntrees, uint32_t l, uint64_t cells,
+                                             Node* __restrict__ out, Node* __restrict__ roots, unsigned long long* __restrict__ mutated,
+                                             const uint32_t* __restrict__ status)
 {
-    if (*status != 0u) return;                   // the same word in every lane
+    if constexpr (HASH) {
+        if (*status != 0u) return;               // the same word in every lane
+    }
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t p0 = ((uint64_t)blockIdx.x * (256u / 64u) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))) * 64ull;
     if (p0 >= cells) return;                     // wave-uniform
@@ -50,7 +67,8 @@ __global__ __launch_bounds__(256) void forest_level_kernel(const Node* __restric
     }
     const uint64_t p = p0 + lane;
     uint32_t t = t0;
-    if (t0 + 1u < ntrees && vkmr_forest::pos(offsets[t0 + 1u], t0 + 1u, l) <= p0 + 63ull) {   // wave-uniform: a tree begins inside the wavefront
+    const bool mixed = t0 + 1u < ntrees && vkmr_forest::pos(offsets[t0 + 1u], t0 + 1u, l) <= p0 + 63ull;   // wave-uniform: a tree begins inside the wavefront
+    if (mixed) {
         top = (ntrees - 1u - t0 < lane) ? ntrees - 1u : t0 + lane;
         while (t < top) {
             const uint32_t mid = t + (top - t + 1u) / 2u;
@@ -63,9 +81,11 @@ __global__ __launch_bounds__(256) void forest_level_kernel(const Node* __restric
     if (p < first) return;                       // cells in front of tree 0 (offsets[0] > 0)
     const uint64_t j = p - first;                // this lane's node of tree t's level l
     if (c == 0ull) {                             // an empty tree: its reserved cell's lane writes the all-zero root, once
-        if (l == 1u && j == 0ull) {
-            const uint32_t zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-            vkmr_dev::store_node(roots + t, zero);
+        if constexpr (HASH) {
+            if (l == 1u && j == 0ull) {
+                const uint32_t zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+                vkmr_dev::store_node(roots + t, zero);
+            }
         }
         return;
     }
@@ -73,7 +93,46 @@ __global__ __launch_bounds__(256) void forest_level_kernel(const Node* __restric
     // is its last, h_t, when it has one node
     const uint64_t n_in = vkmr_forest::level_count(c, l - 1u), n_out = vkmr_forest::level_count(c, l);
     if ((l > 1u && n_in == 1ull) || j >= n_out) return;   // the tree is done, or the padding behind its nodes
-    uint32_t x[8];
-    vkmr_dev::hash_parent(in + vkmr_forest::pos(o, t, l - 1u), n_in, j, x);
-    vkmr_dev::store_node(n_out == 1ull ? roots + t : out + p, x);
+    const Node* level = in + vkmr_forest::pos(o, t, l - 1u);
+    const Node a = vkmr_dev::load_node(level + 2 * j), b = vkmr_dev::load_node(level + vkmr_math::right_child(j, n_in));   // hash_parent's loads
+    if constexpr (COMPARE) {
+        const bool hit = (vkmr_dev::node_diff(a, b) | (uint32_t)(2ull * j + 1ull >= n_in)) == 0u;   // one OR chain, no second branch
+        const unsigned long long bit = 1ull << (l - 1u);
+        if (mixed) {
+            if (hit && !(mutated[t] & bit)) atomicOr(mutated + t, bit);
+        } else {                                 // t == t0 in every lane that is still here
+            const uint64_t hits = __ballot(hit);
+            if (hits != 0ull && lane == (uint32_t)__builtin_ctzll(hits) && !(mutated[t] & bit)) atomicOr(mutated + t, bit);
+        }
+    }
+    if constexpr (HASH) {
+        uint32_t x[8];
+        vkmr_dev::hash_pair(a.w, b.w, x);
+        vkmr_dev::store_node(n_out == 1ull ? roots + t : out + p, x);
+    }
+}
+
+// The build's level: hash, no compare.
+__global__ __launch_bounds__(256) void forest_level_kernel(const Node* __restrict__ in, const uint64_t* __restrict__ offsets, uint32_t ntrees, uint32_t l,
+                                                           uint64_t cells, Node* __restrict__ out, Node* __restrict__ roots,
+                                                           const uint32_t* __restrict__ status)
+{
+    forest_level<true, false>(in, offsets, ntrees, l, cells, out, roots, nullptr, status);
+}
+
+// The flagged build's level (vkmr_hip_reduce_forest_mutated_async, vkmr_hip_reduce_forest_tree_mutated_async): forest_level_kernel
+// plus the compare of the two children it holds anyway.
+__global__ __launch_bounds__(256) void forest_level_mutated_kernel(const Node* __restrict__ in, const uint64_t* __restrict__ offsets, uint32_t ntrees,
+                                                                   uint32_t l, uint64_t cells, Node* __restrict__ out, Node* __restrict__ roots,
+                                                                   unsigned long long* __restrict__ mutated, const uint32_t* __restrict__ status)
+{
+    forest_level<true, true>(in, offsets, ntrees, l, cells, out, roots, mutated, status);
+}
+
+// The scan of a stored forest (vkmr_hip_forest_tree_mutated_async): the same search, the compare, no hash.  `in` is level l - 1
+// as the build or an update left it; a tree is read below its root only, so every cell read is one the build wrote.
+__global__ __launch_bounds__(256) void forest_scan_mutated_kernel(const Node* __restrict__ in, const uint64_t* __restrict__ offsets, uint32_t ntrees,
+                                                                  uint32_t l, uint64_t cells, unsigned long long* __restrict__ mutated)
+{
+    forest_level<false, true>(in, offsets, ntrees, l, cells, nullptr, nullptr, mutated, nullptr);
 }

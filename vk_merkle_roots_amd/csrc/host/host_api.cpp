@@ -182,6 +182,48 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_forest_roots(const vkmr
     return 0;
 }
 
+// Roots and mutation masks of a forest on the CPU, by the rule of vkmr_hip_reduce_forest_mutated_async: bit l of mutated[t] is
+// set iff level l of tree t (n_l nodes) holds a j with 2j + 1 < n_l and node 2j equal to node 2j + 1 -- Bitcoin Core's
+// ComputeMerkleRoot(hashes, &mutated) with the level kept; the last node of an odd level, hashed with itself, is no pair.  An
+// empty tree gets an all-zero root and mask 0.  `roots` may be null (the masks alone).  Nonzero, and nothing written, when the
+// offsets decrease somewhere (1) or a pointer is missing (-1).
+__attribute__((visibility("default"))) int vkmr_host_cpu_forest_mutated(const vkmr_digest* digests, const uint64_t* offsets, uint32_t ntrees,
+                                                                         vkmr_digest* roots, uint64_t* mutated)
+{
+    if (ntrees == 0) return 0;
+    if (!offsets || !mutated) return -1;
+    for (uint32_t t = 0; t < ntrees; ++t)
+        if (offsets[t + 1] < offsets[t]) return 1;
+    if (!digests && offsets[ntrees] > offsets[0]) return -1;
+    std::vector<vkmr_digest> cur;
+    for (uint32_t t = 0; t < ntrees; ++t) {
+        const uint64_t c = offsets[t + 1] - offsets[t];
+        mutated[t] = 0;
+        if (c == 0) {
+            if (roots) std::memset(roots[t].data, 0, 32);
+            continue;
+        }
+        cur.assign(digests + offsets[t], digests + offsets[t + 1]);
+        const uint32_t h = vkmr_math::height(c);
+        for (uint32_t l = 0; l < h; ++l) {
+            const size_t n = cur.size();
+            for (size_t j = 0; 2 * j + 1 < n; ++j)
+                if (std::memcmp(cur[2 * j].data, cur[2 * j + 1].data, 32) == 0) {
+                    mutated[t] |= 1ull << l;
+                    break;
+                }
+            for (size_t j = 0; 2 * j < n; ++j) {   // in place: parent j is written behind what is still to be read
+                vkmr_digest p;
+                vkmr::cpu_sha256d_pair(cur[2 * j].data, cur[vkmr_math::right_child(j, n)].data, p.data);
+                cur[j] = p;
+            }
+            cur.resize((n + 1) / 2);
+        }
+        if (roots) roots[t] = cur[0];
+    }
+    return 0;
+}
+
 // Proofs from a forest on the CPU, by the rule of vkmr_hip_forest_proofs_async: query q is leaf indices[q] of tree trees[q]
 // (tree t: digests[offsets[t] .. offsets[t+1])); heights[q] = h_t = max(1, ceil(log2 c_t)) and siblings[q * stride + l] is
 // L_t[l][p ^ 1] with p = index >> l, or L_t[l][p] where p ^ 1 is past the level's end, for l < h_t and all-zero behind.  A

@@ -13,6 +13,8 @@
 //                                              rank the nodes to emit, gather them; fold leaves and nodes level by level
 //   forest_kernels.hpp  forest_check_kernel, forest_level_kernel   roots of many trees of unequal size: one lane per node of the
 //                                              whole forest, level by level (no reference counterpart); builds the stored forest
+//                       forest_level_mutated_kernel, forest_scan_mutated_kernel   the same level with the mutation flag (equal
+//                                              sibling pairs, CVE-2012-2459) formed beside the hash, and the flag alone from stored levels
 //   forest_tree_kernels.hpp  forest_proofs_kernel          proofs gathered from the stored forest, one lane per (query, level)
 //                            verify_forest_proofs_kernel   batch verification of proofs of unequal height, one lane per proof
 //                            forest_update_*_kernel        leaf updates of the stored forest: tree_update_*'s bodies, a tree per entry
@@ -1008,14 +1010,15 @@ size_t vkmr_hip_forest_scratch_bytes(uint64_t total, uint32_t ntrees)
     return (size_t)vkmr_forest::scratch_cells(total, ntrees) * sizeof(vkmr_digest);
 }
 
-// The launches of both forest builds: the status word zeroed, the check, then level l from level l - 1 for l = 1 .. levels.
+// The launches of the forest builds: the status word zeroed, the check, then level l from level l - 1 for l = 1 .. levels.
 // level(l) is where level l >= 1 is kept: one of two alternating buffers (the roots alone are wanted) or a buffer of its own
-// (the stored forest).
+// (the stored forest).  With mutated_dev (the flagged builds; null in the plain ones) the masks are zeroed in the same
+// sequence and every level is forest_level_mutated_kernel's: the same launches, grids and buffers.
 extern "C++" {   // a template inside the C block
 template <class LevelBuffer>
 static vkmr_status forest_launch(const char* who, int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t total, const uint64_t* offsets_dev,
-                                 uint32_t ntrees, uint64_t max_count, const void* buffer_dev, vkmr_digest* roots_dev, uint32_t* status_dev,
-                                 LevelBuffer level)
+                                 uint32_t ntrees, uint64_t max_count, const void* buffer_dev, vkmr_digest* roots_dev, uint64_t* mutated_dev,
+                                 uint32_t* status_dev, LevelBuffer level)
 {
     if ((!digests_dev && total > 0) || !offsets_dev || !buffer_dev || !roots_dev || !status_dev) return refuse(who, "null pointer");
     if (max_count == 0) return refuse(who, "max_count must be at least 1");
@@ -1027,13 +1030,18 @@ static vkmr_status forest_launch(const char* who, int dev, vkmr_stream s, const 
     Node* roots = nodes(roots_dev);
     VKMR_TRY(hipSetDevice(dev));
     VKMR_TRY(hipMemsetAsync(status_dev, 0, sizeof(uint32_t), S(s)));
+    if (mutated_dev) VKMR_TRY(hipMemsetAsync(mutated_dev, 0, sizeof(uint64_t) * ntrees, S(s)));
     hipLaunchKernelGGL(forest_check_kernel, grid_of(ntrees), dim3(256), 0, S(s), offsets_dev, ntrees, total, max_count, status_dev);
     VKMR_TRY(hipGetLastError());
     for (uint32_t l = 1; l <= levels; ++l) {   // level l from level l - 1, which the previous launch finished
         const Node* in = (l == 1) ? digests : level(l - 1);
         const uint64_t cells = vkmr_forest::level_cells(total, ntrees, l);
-        hipLaunchKernelGGL(forest_level_kernel, grid_of(cells), dim3(256), 0, S(s), in, offsets_dev, ntrees, l, cells, level(l),
-                           roots, (const uint32_t*)status_dev);
+        if (mutated_dev)
+            hipLaunchKernelGGL(forest_level_mutated_kernel, grid_of(cells), dim3(256), 0, S(s), in, offsets_dev, ntrees, l, cells, level(l),
+                               roots, reinterpret_cast<unsigned long long*>(mutated_dev), (const uint32_t*)status_dev);
+        else
+            hipLaunchKernelGGL(forest_level_kernel, grid_of(cells), dim3(256), 0, S(s), in, offsets_dev, ntrees, l, cells, level(l),
+                               roots, (const uint32_t*)status_dev);
         VKMR_TRY(hipGetLastError());
     }
     return VKMR_OK;
@@ -1045,8 +1053,19 @@ vkmr_status vkmr_hip_reduce_forest_async(int dev, vkmr_stream s, const vkmr_dige
 {
     if (ntrees == 0) return VKMR_OK;
     Node* scratch = nodes(scratch_dev);
-    return forest_launch("vkmr_hip_reduce_forest_async", dev, s, digests_dev, total, offsets_dev, ntrees, max_count, scratch_dev, roots_dev, status_dev,
-                         [&](uint32_t l) { return scratch + vkmr_forest::level_base(total, ntrees, l); });
+    return forest_launch("vkmr_hip_reduce_forest_async", dev, s, digests_dev, total, offsets_dev, ntrees, max_count, scratch_dev, roots_dev, nullptr,
+                         status_dev, [&](uint32_t l) { return scratch + vkmr_forest::level_base(total, ntrees, l); });
+}
+
+vkmr_status vkmr_hip_reduce_forest_mutated_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t total, const uint64_t* offsets_dev,
+                                                 uint32_t ntrees, uint64_t max_count, void* scratch_dev, vkmr_digest* roots_dev,
+                                                 uint64_t* mutated_dev, uint32_t* status_dev)
+{
+    if (ntrees == 0) return VKMR_OK;
+    if (!mutated_dev) return refuse("vkmr_hip_reduce_forest_mutated_async", "null pointer");
+    Node* scratch = nodes(scratch_dev);
+    return forest_launch("vkmr_hip_reduce_forest_mutated_async", dev, s, digests_dev, total, offsets_dev, ntrees, max_count, scratch_dev, roots_dev,
+                         mutated_dev, status_dev, [&](uint32_t l) { return scratch + vkmr_forest::level_base(total, ntrees, l); });
 }
 
 // ---- stored forest: every level kept, proofs gathered from it, proofs of unequal height verified (forest_tree_kernels.hpp) ----
@@ -1064,7 +1083,18 @@ vkmr_status vkmr_hip_reduce_forest_tree_async(int dev, vkmr_stream s, const vkmr
     if (ntrees == 0) return VKMR_OK;
     Node* forest = nodes(forest_dev);
     return forest_launch("vkmr_hip_reduce_forest_tree_async", dev, s, digests_dev, total, offsets_dev, ntrees, max_count, forest_dev, roots_dev,
-                         status_dev, [&](uint32_t l) { return forest + vkmr_forest::stored_level_base(total, ntrees, l); });
+                         nullptr, status_dev, [&](uint32_t l) { return forest + vkmr_forest::stored_level_base(total, ntrees, l); });
+}
+
+vkmr_status vkmr_hip_reduce_forest_tree_mutated_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t total,
+                                                      const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count, vkmr_digest* forest_dev,
+                                                      vkmr_digest* roots_dev, uint64_t* mutated_dev, uint32_t* status_dev)
+{
+    if (ntrees == 0) return VKMR_OK;
+    if (!mutated_dev) return refuse("vkmr_hip_reduce_forest_tree_mutated_async", "null pointer");
+    Node* forest = nodes(forest_dev);
+    return forest_launch("vkmr_hip_reduce_forest_tree_mutated_async", dev, s, digests_dev, total, offsets_dev, ntrees, max_count, forest_dev,
+                         roots_dev, mutated_dev, status_dev, [&](uint32_t l) { return forest + vkmr_forest::stored_level_base(total, ntrees, l); });
 }
 
 // What the stored forest's entry points refuse alike, behind their null-pointer test, in the order each tests it: a forest
@@ -1087,6 +1117,32 @@ static ForestLevels forest_levels(uint64_t total, uint32_t ntrees, uint32_t H)
     ForestLevels lv;
     for (uint32_t l = 0; l < VKMR_TREE_MAX_LEVELS; ++l) lv.base[l] = (l >= 1 && l <= H) ? vkmr_forest::stored_level_base(total, ntrees, l) : 0;
     return lv;
+}
+
+// The masks of a stored forest, formed again from its levels as they are now (behind updates): the memset, then one launch per
+// level with the build's grid; level l - 1 is read, nothing but the masks is written.
+vkmr_status vkmr_hip_forest_tree_mutated_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* forest_dev, uint64_t total,
+                                               const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count, uint64_t* mutated_dev)
+{
+    const char* who = "vkmr_hip_forest_tree_mutated_async";
+    if (ntrees == 0) return VKMR_OK;
+    if ((!digests_dev && total > 0) || !forest_dev || !offsets_dev || !mutated_dev) return refuse(who, "null pointer");
+    const vkmr_status args = forest_args_check(who, total, ntrees, max_count, 0, nullptr, nullptr);
+    if (args != VKMR_OK) return args;
+    if (grid_too_large(groups_of(vkmr_forest::level_cells(total, ntrees, 1)))) return refuse(who, "forest too large");
+    const uint32_t H = vkmr_forest::launches(total, max_count);   // <= 58
+    const Node* digests = nodes(digests_dev);
+    const Node* forest = nodes(forest_dev);
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_TRY(hipMemsetAsync(mutated_dev, 0, sizeof(uint64_t) * ntrees, S(s)));
+    for (uint32_t l = 1; l <= H; ++l) {
+        const Node* in = (l == 1) ? digests : forest + vkmr_forest::stored_level_base(total, ntrees, l - 1);
+        const uint64_t cells = vkmr_forest::level_cells(total, ntrees, l);
+        hipLaunchKernelGGL(forest_scan_mutated_kernel, grid_of(cells), dim3(256), 0, S(s), in, offsets_dev, ntrees, l, cells,
+                           reinterpret_cast<unsigned long long*>(mutated_dev));
+        VKMR_TRY(hipGetLastError());
+    }
+    return VKMR_OK;
 }
 
 vkmr_status vkmr_hip_forest_proofs_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* forest_dev, uint64_t total,

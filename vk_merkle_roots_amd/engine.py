@@ -378,16 +378,30 @@ class HipDevice:
                                                     scratch_buf.ptr if scratch_buf else None, roots_buf.ptr if roots_buf else None,
                                                     status_buf.ptr if status_buf else None), "vkmr_hip_reduce_forest_async")
 
-    def _reduce_forest(self, tmp, d_leaves, total, offsets, ntrees, max_count, what, stored):
+    def reduce_forest_mutated_async(self, digests_buf, total, offsets_buf, ntrees, max_count, scratch_buf, roots_buf, mutated_buf, status_buf,
+                                    stream=None):
+        check(self.lib.vkmr_hip_reduce_forest_mutated_async(self.index, stream or self.stream, digests_buf.ptr if digests_buf else None, total,
+                                                            offsets_buf.ptr if offsets_buf else None, ntrees, max_count,
+                                                            scratch_buf.ptr if scratch_buf else None, roots_buf.ptr if roots_buf else None,
+                                                            mutated_buf.ptr if mutated_buf else None,
+                                                            status_buf.ptr if status_buf else None), "vkmr_hip_reduce_forest_mutated_async")
+
+    def _reduce_forest(self, tmp, d_leaves, total, offsets, ntrees, max_count, what, stored, d_mutated=None):
         """One forest call over checked offsets (ntrees >= 1), its buffers in the scope `tmp`: the roots alone, or with
-        `stored` every level kept.  (max_count, offsets buffer, level buffer, roots buffer); ValueError when the device
-        refuses the forest."""
+        `stored` every level kept; with d_mutated (8 * ntrees bytes) the flagged build, which fills it.  (max_count, offsets
+        buffer, level buffer, roots buffer); ValueError when the device refuses the forest."""
         if max_count is None:
             max_count = max(1, int(np.diff(offsets).max()))
         d_off, d_roots, d_status = tmp.upload(offsets), tmp.alloc(32 * ntrees), tmp.alloc(4)
         if stored:
             d_levels = tmp.alloc(self.forest_tree_bytes(total, ntrees, max_count))
-            self.reduce_forest_tree_async(d_leaves, total, d_off, ntrees, max_count, d_levels, d_roots, d_status)
+            if d_mutated:
+                self.reduce_forest_tree_mutated_async(d_leaves, total, d_off, ntrees, max_count, d_levels, d_roots, d_mutated, d_status)
+            else:
+                self.reduce_forest_tree_async(d_leaves, total, d_off, ntrees, max_count, d_levels, d_roots, d_status)
+        elif d_mutated:
+            d_levels = tmp.alloc(self.lib.vkmr_hip_forest_scratch_bytes(total, ntrees))
+            self.reduce_forest_mutated_async(d_leaves, total, d_off, ntrees, max_count, d_levels, d_roots, d_mutated, d_status)
         else:
             d_levels = tmp.alloc(self.lib.vkmr_hip_forest_scratch_bytes(total, ntrees))
             self.reduce_forest_async(d_leaves, total, d_off, ntrees, max_count, d_levels, d_roots, d_status)
@@ -415,6 +429,25 @@ class HipDevice:
         with self.scope() as tmp:
             return self._forest_of_buffer(tmp.upload(digests) if total else None, total, counts, max_count, "forest_roots")
 
+    def _forest_mutated_of_buffer(self, d_leaves, total, counts, max_count, what):
+        """(roots [ntrees, 8] uint32, masks [ntrees] uint64) of the trees of `counts` leaves each over the `total` cells of d_leaves."""
+        offsets, ntrees = _checked_offsets(counts, total, what)
+        if ntrees == 0:
+            return np.zeros((0, 8), dtype=np.uint32), np.zeros(0, dtype=np.uint64)
+        with self.scope() as tmp:
+            d_mut = tmp.alloc(8 * ntrees)
+            d_roots = self._reduce_forest(tmp, d_leaves, total, offsets, ntrees, max_count, what, stored=False, d_mutated=d_mut)[3]
+            return self.download(d_roots, 32 * ntrees).reshape(ntrees, 8), self.download(d_mut, 8 * ntrees, dtype=np.uint64)
+
+    def forest_roots_mutated(self, digests, counts, max_count=None):
+        """(roots, mutated): forest_roots, and uint64 [ntrees] whose bit l is set when level l of the tree holds two equal
+        siblings that both exist (vkmr_hip_reduce_forest_mutated_async; CVE-2012-2459: such a tree shares its root with a
+        shorter leaf list).  `mutated != 0` is Bitcoin Core's flag.  Same arguments and errors as forest_roots."""
+        digests = _host(digests, np.uint32, -1, 8)
+        total = int(digests.shape[0])
+        with self.scope() as tmp:
+            return self._forest_mutated_of_buffer(tmp.upload(digests) if total else None, total, counts, max_count, "forest_roots_mutated")
+
     # -- stored forest: every level kept, proofs gathered from it, proofs of unequal height verified --
     def forest_tree_bytes(self, total, ntrees, max_count):
         return self.lib.vkmr_hip_forest_tree_bytes(total, ntrees, max_count)
@@ -424,6 +457,20 @@ class HipDevice:
                                                          offsets_buf.ptr if offsets_buf else None, ntrees, max_count,
                                                          forest_buf.ptr if forest_buf else None, roots_buf.ptr if roots_buf else None,
                                                          status_buf.ptr if status_buf else None), "vkmr_hip_reduce_forest_tree_async")
+
+    def reduce_forest_tree_mutated_async(self, digests_buf, total, offsets_buf, ntrees, max_count, forest_buf, roots_buf, mutated_buf, status_buf,
+                                         stream=None):
+        check(self.lib.vkmr_hip_reduce_forest_tree_mutated_async(self.index, stream or self.stream, digests_buf.ptr if digests_buf else None, total,
+                                                                 offsets_buf.ptr if offsets_buf else None, ntrees, max_count,
+                                                                 forest_buf.ptr if forest_buf else None, roots_buf.ptr if roots_buf else None,
+                                                                 mutated_buf.ptr if mutated_buf else None,
+                                                                 status_buf.ptr if status_buf else None), "vkmr_hip_reduce_forest_tree_mutated_async")
+
+    def forest_tree_mutated_async(self, digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, mutated_buf, stream=None):
+        check(self.lib.vkmr_hip_forest_tree_mutated_async(self.index, stream or self.stream, digests_buf.ptr if digests_buf else None,
+                                                          forest_buf.ptr if forest_buf else None, total, offsets_buf.ptr if offsets_buf else None,
+                                                          ntrees, max_count, mutated_buf.ptr if mutated_buf else None),
+              "vkmr_hip_forest_tree_mutated_async")
 
     def forest_proofs_async(self, digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, trees_buf, indices_buf, k, siblings_buf,
                             heights_buf, stream=None):
@@ -480,26 +527,32 @@ class HipDevice:
                                                 d_scr, d_ok)
             return int(self.download(d_ok, 4)[0]) == 1
 
-    def _build_forest_of_buffer(self, d_leaves, total, counts, max_count, what, owned=()):
-        """A MerkleForest of the trees of `counts` leaves each over the `total` cells of d_leaves (its level 0)."""
+    def _build_forest_of_buffer(self, d_leaves, total, counts, max_count, what, owned=(), mutated=False):
+        """A MerkleForest of the trees of `counts` leaves each over the `total` cells of d_leaves (its level 0); with `mutated`
+        built by the flagged twin, whose masks it keeps."""
         offsets, ntrees = _checked_offsets(counts, total, what)
         if ntrees == 0:
             raise ValueError(f"{what}: no tree")
         with self.scope() as tmp:
-            max_count, d_off, d_forest, d_roots = self._reduce_forest(tmp, d_leaves, total, offsets, ntrees, max_count, what, stored=True)
+            d_mut = tmp.alloc(8 * ntrees) if mutated else None
+            max_count, d_off, d_forest, d_roots = self._reduce_forest(tmp, d_leaves, total, offsets, ntrees, max_count, what, stored=True,
+                                                                      d_mutated=d_mut)
+            masks = self.download(d_mut, 8 * ntrees, dtype=np.uint64) if mutated else None
             tmp.release(d_off, d_forest, d_roots)      # the forest's from here on
-        return MerkleForest(self, d_leaves, total, np.diff(offsets), d_off, max_count, d_forest, d_roots, owned=owned)
+        return MerkleForest(self, d_leaves, total, np.diff(offsets), d_off, max_count, d_forest, d_roots, owned=owned, built_mutated=masks)
 
-    def build_forest(self, digests, counts, max_count=None):
+    def build_forest(self, digests, counts, max_count=None, mutated=False):
         """Every level of every tree of a forest, kept on the device: a MerkleForest (vkmr_hip_reduce_forest_tree_async).
         `digests` [total, 8] (a host array) holds the leaves of all trees back to back, tree t the next counts[t] of them;
-        max_count: an upper bound on every count (the largest count when None).  ValueError when the counts do not add up to
-        the leaves, for no tree at all, or when the device refuses the forest (a count above max_count)."""
+        max_count: an upper bound on every count (the largest count when None).  mutated=True builds with
+        vkmr_hip_reduce_forest_tree_mutated_async -- the same forest -- and keeps the build's masks in `built_mutated`.
+        ValueError when the counts do not add up to the leaves, for no tree at all, or when the device refuses the forest (a
+        count above max_count)."""
         digests = _host(digests, np.uint32, -1, 8)
         total = int(digests.shape[0])
         with self.scope() as tmp:
             d_in = tmp.upload(digests) if total else None
-            forest = self._build_forest_of_buffer(d_in, total, counts, max_count, "build_forest", owned=[d_in] if d_in else [])
+            forest = self._build_forest_of_buffer(d_in, total, counts, max_count, "build_forest", owned=[d_in] if d_in else [], mutated=mutated)
             tmp.release(d_in)
         return forest
 
@@ -746,9 +799,11 @@ class MerkleTree:
 class MerkleForest:
     """Every level of every tree of a forest, resident on the device (vkmr_hip_reduce_forest_tree_async): level 0 is the
     leaves buffer it was built from, levels 1..`levels` one buffer laid out as include/vkmr_hip.h describes, the roots a
-    buffer of their own.  `levels` is also the stride of its proofs."""
+    buffer of their own.  `levels` is also the stride of its proofs.  `built_mutated`: the mutation masks of the build
+    (uint64 [ntrees]) when it was a flagged one, else None; mutated() gives those of the forest as it is now."""
 
-    def __init__(self, dev, digests_buf, total, counts, offsets_buf, max_count, forest_buf, roots_buf, owned=()):
+    def __init__(self, dev, digests_buf, total, counts, offsets_buf, max_count, forest_buf, roots_buf, owned=(), built_mutated=None):
+        self.built_mutated = built_mutated
         self.dev, self.digests, self.total, self.offsets, self.max_count = dev, digests_buf, int(total), offsets_buf, int(max_count)
         self.counts = np.asarray(counts, dtype=np.uint64)
         self.ntrees = int(self.counts.shape[0])
@@ -759,6 +814,20 @@ class MerkleForest:
     def roots(self):
         """[ntrees, 8] uint32: what forest_roots gives for the same leaves (an all-zero root for an empty tree)."""
         return self.dev.download(self.roots_buf, 32 * self.ntrees).reshape(self.ntrees, 8)
+
+    def mutated_async(self, mutated_buf, stream=None):
+        """The mutation masks of the forest as it is now, written to mutated_buf (ntrees uint64 in device memory): a scan of
+        the stored levels, ordered on `stream` behind earlier updates (vkmr_hip_forest_tree_mutated_async)."""
+        self.dev.forest_tree_mutated_async(self.digests, self.forest, self.total, self.offsets, self.ntrees, self.max_count, mutated_buf,
+                                           stream=stream)
+
+    def mutated(self):
+        """uint64 [ntrees]: bit l set when level l of the tree holds two equal siblings that both exist (CVE-2012-2459), for
+        the leaves as they are now -- after update() and update_packed() too.  What forest_roots_mutated gives for them."""
+        with self.dev.scope() as tmp:
+            d_mut = tmp.alloc(8 * self.ntrees)
+            self.mutated_async(d_mut)
+            return self.dev.download(d_mut, 8 * self.ntrees, dtype=np.uint64)
 
     def proofs_async(self, trees_buf, indices_buf, k, siblings_buf, heights_buf, stream=None):
         """Proofs of k (tree, index) queries in device memory, written to siblings_buf [k, levels] and heights_buf [k]."""
@@ -968,6 +1037,16 @@ def merkle_roots_packed_forest(dev, batch, counts, max_count=None):
     over the next counts[t] of them.  [ntrees, 8] uint32 (digest_hex gives the canonical text); no digest goes through
     the host."""
     return _forest_packed(dev, batch, counts, max_count, "merkle_roots_packed_forest", stored=False)
+
+
+def merkle_roots_packed_forest_mutated(dev, batch, counts, max_count=None):
+    """merkle_roots_packed_forest with the verdict on every block: (roots [ntrees, 8] uint32, mutated [ntrees] uint64), bit l
+    of mutated[t] set when level l of tree t holds two equal siblings that both exist (HipDevice.forest_roots_mutated).  The
+    strings are mapped ONCE and ONE flagged forest call reduces them; no digest goes through the host."""
+    what = "merkle_roots_packed_forest_mutated"
+    _checked_offsets(counts, batch.count, what, "strings")
+    with dev.scope() as tmp:
+        return dev._forest_mutated_of_buffer(dev.map_packed(tmp, batch) if batch.count else None, batch.count, counts, max_count, what)
 
 
 def digest_hex(words):
