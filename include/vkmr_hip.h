@@ -564,6 +564,50 @@ VKMR_API vkmr_status vkmr_hip_verify_forest_multiproof_async(int dev, vkmr_strea
                                                              uint32_t* ok_dev);
 
 /*
+ * FIND LEAVES BY DIGEST ("where is this hash?"; the reference has no counterpart): the step from a digest a caller holds -- a
+ * txid, a file hash, an account key -- to the position every call above takes.  digests_dev, total, offsets_dev and ntrees
+ * as in vkmr_hip_reduce_forest_async; the call TRUSTS the offsets as vkmr_hip_forest_proofs_async does (non-decreasing,
+ * offsets[ntrees] <= total).  It reads level 0 alone and needs no stored level, so it also serves a caller who only ever
+ * reduced.  queries_dev[0..k) are digests in DEVICE memory, in any order, repeats allowed.  The answer to query q is the LOWEST
+ * flat position p with offsets[0] <= p < offsets[ntrees] and digests_dev[p] == queries_dev[q] on all 32 bytes, reported as
+ *   trees_dev[q]   = t, the one tree with offsets[t] <= p < offsets[t+1] (an empty tree is never named)
+ *   indices_dev[q] = p - offsets[t]
+ * and as trees_dev[q] = 0xFFFFFFFF, indices_dev[q] = 0xFFFFFFFFFFFFFFFF when there is no such p.  Equal leaves may exist
+ * (Bitcoin's chain holds two txids that each appear in two blocks): the lowest position wins, whatever the scheduling.  Inner
+ * nodes, roots and the duplicated last node of an odd level are not leaves, and cells of digests_dev outside
+ * [offsets[0], offsets[ntrees]) belong to no tree: none of them is ever found.  The two output arrays are what
+ * vkmr_hip_forest_proofs_async takes, with no host step in between: a found query gets its proof there, an unfound one (a
+ * tree >= ntrees) height 0 and all-zero cells.
+ *   scratch_dev  vkmr_hip_find_scratch_bytes(k) bytes of device memory, 8-byte aligned: T slots of 8 bytes, T the smallest
+ *                power of two >= max(64, 2k), then 8k + 4k bytes, the sum rounded up to 16.  The call sets it itself.
+ * The queries are put into an open-addressed table in the scratch and the leaves are streamed past it ONCE, each read once,
+ * whatever k: the time is that of reading 32 * total bytes plus the table's traffic.  The table holds queries only, so the
+ * length of a probe walk depends on the caller's own queries, never on the forest's leaves.
+ * Launches, all on the caller's stream: one memset of the scratch, the insert (k lanes), the scan (a grid sized from the
+ * device's compute units; none when total == 0), the resolve (k lanes).  They depend on (total, k) only and never grow with
+ * ntrees; no allocation, no host synchronisation, no host read of device data.
+ * k == 0 does nothing whatever the other arguments.  ntrees == 0 or total == 0 with k > 0 writes "not found" for every
+ * query; digests_dev may then be NULL (and offsets_dev when ntrees == 0).  Refused on the host (VKMR_ERR_INVALID) with k > 0,
+ * before any HIP call: a NULL pointer that is needed, total above 2^58, scratch_dev not 8-byte aligned.
+ * Stream-ordered: a lookup enqueued after an update on the same stream sees the new leaves.
+ * vkmr_host_cpu_forest_find (libvkmr_host.so) applies the same rule on the CPU, for a party without a GPU.
+ */
+VKMR_API size_t vkmr_hip_find_scratch_bytes(uint32_t k);
+VKMR_API vkmr_status vkmr_hip_forest_find_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t total,
+                                                const uint64_t* offsets_dev, uint32_t ntrees,
+                                                const vkmr_digest* queries_dev, uint32_t k, void* scratch_dev,
+                                                uint32_t* trees_dev, uint64_t* indices_dev);
+/*
+ * The same lookup in ONE tree, the leaves being cells [0, count) of digests_dev: indices_dev[q] = the lowest index whose leaf
+ * equals queries_dev[q], or UINT64_MAX when there is none -- which vkmr_hip_tree_proofs_async already treats as a bad index
+ * (all-zero cells).  Same scratch, launches and refusals (count above 2^58); count == 0 writes "not found" for every query
+ * and digests_dev may then be NULL.  vkmr_host_cpu_tree_find is the CPU's.
+ */
+VKMR_API vkmr_status vkmr_hip_tree_find_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t count,
+                                              const vkmr_digest* queries_dev, uint32_t k, void* scratch_dev,
+                                              uint64_t* indices_dev);
+
+/*
  * COMBINE: duplicate-last Merkle root over n >= 1 slice roots given in slice order, always
  * at least one level -- the rule of CpuSha256D::Root that the reference applies to the slice
  * roots on the CPU (CpuSha256DforReductions, src/vkmr/Reductions.cpp:56-69, :703-712).  Here

@@ -13,6 +13,7 @@
 #   rehearsals             soaks against the oracle; torchrun --nproc 2 (gloo rehearsal; plain N=2 must fail on one GPU); --force-dist (RCCL, one rank)
 #   forestupdate [args]    tools/forest_update_timing.py: leaf updates of a stored forest against a rebuild and against the single tree's
 #                          update (one JSON line), then the same run under rocprofv3 --kernel-trace --stats; stops at the first failing step
+#   find [args]            tools/find_timing.py: the lookup by digest beside a read-only pass of torch's over as many bytes (one JSON line)
 #   cumask                 tools/cu_mask_probe.py: where CU-mask bits land, map/reduce on half the CUs with and without neighbours
 #   issue <set>            tools/issue_patterns (python3 tools/gen_issue_patterns.py <set> and a build beforehand)
 #   proofs                 tools/proof_timing.py: a slice reduced with and without proofs written in the pass
@@ -144,6 +145,11 @@ forestupdate)
   find $OUT/prof_forest_update -name "*kernel_stats.csv" -exec cp {} $OUT/forest_update_kernel_stats.csv \; &&
   cat $OUT/forest_update_kernel_stats.csv
   echo "forestupdate rc=$?"
+  ;;
+find)
+  timeout -k 10 500 python3 tools/find_timing.py "$@" --out $OUT/find_timing.json > /dev/null 2> $OUT/find_timing.err && echo "find_timing ok" &&
+  cat $OUT/find_timing.json
+  echo "find rc=$?"
   ;;
 cumask)
   hipcc --offload-arch=gfx950 -O2 -shared -fPIC -o tools/libwhere.so tools/where.hip

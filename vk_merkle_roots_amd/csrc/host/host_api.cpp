@@ -378,4 +378,58 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_verify_forest_multiproo
     return 1;
 }
 
+// Leaves by digest on the CPU, by the rule of vkmr_hip_forest_find_async: query q's answer is the lowest flat position p in
+// [offsets[0], offsets[ntrees]) with digests[p] == queries[q] on all 32 bytes, as trees[q] = the tree that holds p and
+// indices[q] = p - offsets[trees[q]]; no such p: 0xFFFFFFFF and UINT64_MAX.  The queries are sorted once and every leaf is
+// looked up among them: O((total + k) log k).  Nonzero, and nothing written, when the offsets decrease somewhere or end past
+// `total` (1) or a needed pointer is missing (-1).  k == 0 does nothing.
+__attribute__((visibility("default"))) int vkmr_host_cpu_forest_find(const vkmr_digest* digests, uint64_t total, const uint64_t* offsets,
+                                                                      uint32_t ntrees, const vkmr_digest* queries, uint32_t k, uint32_t* trees,
+                                                                      uint64_t* indices)
+{
+    if (k == 0) return 0;
+    if (!queries || !trees || !indices || (ntrees > 0 && !offsets)) return -1;
+    for (uint32_t t = 0; t < ntrees; ++t)
+        if (offsets[t + 1] < offsets[t]) return 1;
+    const uint64_t lo = ntrees ? offsets[0] : 0, hi = ntrees ? offsets[ntrees] : 0;
+    if (hi > total) return 1;
+    if (!digests && hi > lo) return -1;
+    const auto less = [&](uint32_t a, uint32_t b) { return std::memcmp(queries[a].data, queries[b].data, 32) < 0; };
+    std::vector<uint32_t> order(k);
+    for (uint32_t q = 0; q < k; ++q) order[q] = q;
+    std::sort(order.begin(), order.end(), less);
+    std::vector<uint64_t> best(k, UINT64_MAX);             // per place in `order`; kept at the first of a run of equal queries
+    for (uint64_t p = lo; p < hi; ++p) {
+        const auto at = std::lower_bound(order.begin(), order.end(), digests[p],
+                                         [&](uint32_t a, const vkmr_digest& d) { return std::memcmp(queries[a].data, d.data, 32) < 0; });
+        if (at == order.end() || std::memcmp(queries[*at].data, digests[p].data, 32) != 0) continue;
+        uint64_t& b = best[at - order.begin()];
+        if (b == UINT64_MAX) b = p;                        // p rises: the first one seen is the lowest
+    }
+    for (uint32_t i = 0; i < k; ++i) {
+        if (i > 0 && std::memcmp(queries[order[i]].data, queries[order[i - 1]].data, 32) == 0) best[i] = best[i - 1];
+        const uint32_t q = order[i];
+        if (best[i] == UINT64_MAX) {
+            trees[q] = UINT32_MAX;
+            indices[q] = UINT64_MAX;
+            continue;
+        }
+        const uint64_t* next = std::upper_bound(offsets, offsets + ntrees + 1, best[i]);   // the first offset above p: behind p's tree
+        trees[q] = (uint32_t)(next - offsets) - 1u;
+        indices[q] = best[i] - next[-1];
+    }
+    return 0;
+}
+
+// The same for one tree over digests[0 .. count): indices[q] = the lowest index whose leaf equals queries[q], or UINT64_MAX.
+__attribute__((visibility("default"))) int vkmr_host_cpu_tree_find(const vkmr_digest* digests, uint64_t count, const vkmr_digest* queries,
+                                                                    uint32_t k, uint64_t* indices)
+{
+    if (k == 0) return 0;
+    if (!indices) return -1;
+    const uint64_t offsets[2] = {0, count};
+    std::vector<uint32_t> trees(k);
+    return vkmr_host_cpu_forest_find(digests, count, offsets, 1, queries, k, trees.data(), indices);
+}
+
 }  // extern "C"

@@ -20,6 +20,8 @@
 //                            forest_update_*_kernel        leaf updates of the stored forest: tree_update_*'s bodies, a tree per entry
 //                            forest_multiproof_*_kernel, verify_forest_multiproof_*_kernel   one proof for leaves of many trees:
 //                                              the multiproof bodies and tree_kernels.hpp's ranking, a tree and a height per entry
+//   find_kernels.hpp    find_insert_kernel, *_find_scan_kernel, *_find_resolve_kernel   lookup by digest: the queries in an open-addressed
+//                                              table, every leaf streamed past it once, lowest position per query (sizes: find_plan.hpp)
 //   sha256d_device.hpp  the SHA-256 round / compression building blocks, and the tree's: hash_parent, node_diff, store_node
 //   merkle_math.hpp     the integer rules, no HIP types (ceil_shift, height, right_child, sibling): shared with host/ and tests/c
 //   meta_kernels.hpp    sizes_*_kernel         metadata entries from 16-bit sizes   (Batches.cpp:64-121)
@@ -50,6 +52,7 @@ using vkmr_dev::Node;
 #include "tree_kernels.hpp"
 #include "forest_kernels.hpp"
 #include "forest_tree_kernels.hpp"
+#include "find_kernels.hpp"
 
 // ============================================================================
 // C ABI
@@ -1305,6 +1308,87 @@ vkmr_status vkmr_hip_verify_forest_multiproof_async(int dev, vkmr_stream s, cons
                        (const uint64_t*)hdr, ok_dev);
     VKMR_TRY(hipGetLastError());
     return VKMR_OK;
+}
+
+// ---- lookup by digest (find_kernels.hpp, find_plan.hpp) ---------------------------------------------------------------------
+
+size_t vkmr_hip_find_scratch_bytes(uint32_t k) { return (size_t)vkmr_find::scratch_bytes(k); }
+
+// Compute units of device `dev`, asked for once per device: the scan's grid is sized from it.
+static vkmr_status compute_units_of(int dev, uint32_t* cus)
+{
+    static std::atomic<int> known[64];
+    int n = (dev >= 0 && dev < 64) ? known[dev].load(std::memory_order_relaxed) : 0;
+    if (n <= 0) {
+        VKMR_TRY(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
+        if (n <= 0) n = 1;
+        if (dev >= 0 && dev < 64) known[dev].store(n, std::memory_order_relaxed);
+    }
+    *cus = (uint32_t)n;
+    return VKMR_OK;
+}
+
+// The launches of both lookups, all on the caller's stream: the scratch set to 0xFF (every slot empty, every best position
+// "none"), the queries inserted, the leaves scanned (no launch when there is no cell to scan), the answers resolved.  They
+// depend on (cells, k) and the device alone.  trees_dev null: one tree over [0, cells), and no offsets.
+static vkmr_status find_launch(const char* who, int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t cells, const uint64_t* offsets_dev,
+                               uint32_t ntrees, const vkmr_digest* queries_dev, uint32_t k, void* scratch_dev, uint32_t* trees_dev,
+                               uint64_t* indices_dev)
+{
+    if (cells > (1ull << 58)) return refuse(who, "too many leaves");
+    if (reinterpret_cast<uintptr_t>(scratch_dev) & 7u) return refuse(who, "scratch must be 8-byte aligned");
+    const uint64_t mask = vkmr_find::table_slots(k) - 1ull;
+    char* scratch = static_cast<char*>(scratch_dev);
+    unsigned long long* table = reinterpret_cast<unsigned long long*>(scratch);
+    unsigned long long* best = reinterpret_cast<unsigned long long*>(scratch + vkmr_find::best_offset(k));
+    uint32_t* rep = reinterpret_cast<uint32_t*>(scratch + vkmr_find::rep_offset(k));
+    uint32_t cus = 0;
+    VKMR_TRY(hipSetDevice(dev));
+    const vkmr_status st = compute_units_of(dev, &cus);
+    if (st != VKMR_OK) return st;
+    VKMR_TRY(hipMemsetAsync(scratch_dev, 0xFF, (size_t)vkmr_find::scratch_bytes(k), S(s)));
+    hipLaunchKernelGGL(find_insert_kernel, grid_of(k), dim3(256), 0, S(s), nodes(queries_dev), k, table, mask, rep);
+    VKMR_TRY(hipGetLastError());
+    if (cells > 0) {
+        const dim3 grid((uint32_t)vkmr_find::scan_groups(cells, cus));
+        if (trees_dev)
+            hipLaunchKernelGGL(forest_find_scan_kernel, grid, dim3(VKMR_FIND_THREADS), 0, S(s), nodes(digests_dev), offsets_dev, ntrees, cells,
+                               nodes(queries_dev), (const unsigned long long*)table, mask, best);
+        else
+            hipLaunchKernelGGL(tree_find_scan_kernel, grid, dim3(VKMR_FIND_THREADS), 0, S(s), nodes(digests_dev), cells, nodes(queries_dev),
+                               (const unsigned long long*)table, mask, best);
+        VKMR_TRY(hipGetLastError());
+    }
+    if (trees_dev)
+        hipLaunchKernelGGL(forest_find_resolve_kernel, grid_of(k), dim3(256), 0, S(s), offsets_dev, ntrees, cells, k, (const unsigned long long*)best,
+                           (const uint32_t*)rep, trees_dev, indices_dev);
+    else
+        hipLaunchKernelGGL(tree_find_resolve_kernel, grid_of(k), dim3(256), 0, S(s), cells, k, (const unsigned long long*)best, (const uint32_t*)rep,
+                           indices_dev);
+    VKMR_TRY(hipGetLastError());
+    return VKMR_OK;
+}
+
+vkmr_status vkmr_hip_forest_find_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t total, const uint64_t* offsets_dev,
+                                       uint32_t ntrees, const vkmr_digest* queries_dev, uint32_t k, void* scratch_dev, uint32_t* trees_dev,
+                                       uint64_t* indices_dev)
+{
+    const char* who = "vkmr_hip_forest_find_async";
+    if (k == 0) return VKMR_OK;
+    const bool leaves = ntrees > 0 && total > 0;       // without a tree or a cell nothing is read but the queries
+    if (!queries_dev || !scratch_dev || !trees_dev || !indices_dev || (ntrees > 0 && !offsets_dev) || (leaves && !digests_dev))
+        return refuse(who, "null pointer");
+    // no tree: the kernels read no offset and scan an empty range; the launches stay those of (total, k)
+    return find_launch(who, dev, s, digests_dev, total, offsets_dev, ntrees, queries_dev, k, scratch_dev, trees_dev, indices_dev);
+}
+
+vkmr_status vkmr_hip_tree_find_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t count, const vkmr_digest* queries_dev,
+                                     uint32_t k, void* scratch_dev, uint64_t* indices_dev)
+{
+    const char* who = "vkmr_hip_tree_find_async";
+    if (k == 0) return VKMR_OK;
+    if (!queries_dev || !scratch_dev || !indices_dev || (count > 0 && !digests_dev)) return refuse(who, "null pointer");
+    return find_launch(who, dev, s, digests_dev, count, nullptr, 0, queries_dev, k, scratch_dev, nullptr, indices_dev);
 }
 
 // ---- combine --------------------------------------------------------------------

@@ -13,6 +13,10 @@ from . import _abi
 from ._abi import check
 
 
+NO_TREE = 0xFFFFFFFF                # trees[q] of a digest that is no leaf (vkmr_hip_forest_find_async)
+NOT_FOUND = 0xFFFFFFFFFFFFFFFF      # its index
+
+
 def tree_height(count):
     """Levels of the duplicate-last tree over `count` leaves; a lone leaf is still
     hashed with itself once (CpuSha256D::Root's do-while, reference
@@ -576,6 +580,25 @@ class HipDevice:
             self.verify_forest_proofs_async(d_leaves, d_trees, d_idx, d_sib, d_h, k, siblings.shape[1], d_roots, roots.shape[0], d_ok)
             return self.download(d_ok, 4 * k) == 1
 
+    # -- leaves by digest: where in a tree or forest is this hash? ------------------------------
+    def find_scratch_bytes(self, k):
+        return self.lib.vkmr_hip_find_scratch_bytes(k)
+
+    def forest_find_async(self, digests_buf, total, offsets_buf, ntrees, queries_buf, k, scratch_buf, trees_buf, indices_buf, stream=None):
+        """trees_buf[q], indices_buf[q] = where queries_buf[q] (a digest) is a leaf of the forest: the lowest position wins; not
+        found: 0xFFFFFFFF and 2^64 - 1.  All in device memory; scratch_buf: find_scratch_bytes(k).  include/vkmr_hip.h."""
+        check(self.lib.vkmr_hip_forest_find_async(self.index, stream or self.stream, digests_buf.ptr if digests_buf else None, total,
+                                                  offsets_buf.ptr if offsets_buf else None, ntrees, queries_buf.ptr if queries_buf else None, k,
+                                                  scratch_buf.ptr if scratch_buf else None, trees_buf.ptr if trees_buf else None,
+                                                  indices_buf.ptr if indices_buf else None), "vkmr_hip_forest_find_async")
+
+    def tree_find_async(self, digests_buf, count, queries_buf, k, scratch_buf, indices_buf, stream=None):
+        """indices_buf[q] = the lowest index at which queries_buf[q] is a leaf of the tree over digests_buf[0 .. count), or
+        2^64 - 1.  All in device memory; scratch_buf: find_scratch_bytes(k)."""
+        check(self.lib.vkmr_hip_tree_find_async(self.index, stream or self.stream, digests_buf.ptr if digests_buf else None, count,
+                                                queries_buf.ptr if queries_buf else None, k, scratch_buf.ptr if scratch_buf else None,
+                                                indices_buf.ptr if indices_buf else None), "vkmr_hip_tree_find_async")
+
     def reduce_scratch(self, count, levels_variant=False):
         fn = self.lib.vkmr_hip_reduce_levels_scratch_bytes if levels_variant else self.lib.vkmr_hip_reduce_scratch_bytes
         return self.alloc(fn(count))
@@ -709,6 +732,40 @@ class MerkleTree:
             d_idx, d_sib = tmp.upload(idx), tmp.alloc(32 * k * self.height)
             self.proofs_async(d_idx, k, d_sib)
             return self.dev.download(d_sib, 32 * k * self.height).reshape(k, self.height, 8)
+
+    def find_async(self, queries_buf, k, scratch_buf, indices_buf, stream=None):
+        """indices_buf[q] = the lowest index whose leaf equals the digest queries_buf[q], or 2^64 - 1 (NOT_FOUND): device
+        memory throughout, scratch_buf of dev.find_scratch_bytes(k) bytes; ordered on `stream` behind earlier updates."""
+        self.dev.tree_find_async(self.digests, self.count, queries_buf, k, scratch_buf, indices_buf, stream=stream)
+
+    def find(self, digests):
+        """uint64 [k]: for each digest ([k, 8] uint32, a host array) the lowest index at which it is a leaf, or NOT_FOUND
+        (2^64 - 1).  Inner nodes and the root are not leaves."""
+        q = _host(digests, np.uint32, -1, 8)
+        k = int(q.shape[0])
+        if k == 0:
+            return np.zeros(0, dtype=np.uint64)
+        with self.dev.scope() as tmp:
+            d_q, d_scr, d_idx = tmp.upload(q), tmp.alloc(self.dev.find_scratch_bytes(k)), tmp.alloc(8 * k)
+            self.find_async(d_q, k, d_scr, d_idx)
+            return self.dev.download(d_idx, 8 * k, dtype=np.uint64)
+
+    def proofs_of(self, digests):
+        """(siblings [k, height, 8] uint32, indices [k] uint64): hash -> position -> proof on the device, nothing downloaded
+        in between.  A digest that is no leaf gets NOT_FOUND and zero cells, as proofs() gives for a bad index."""
+        q = _host(digests, np.uint32, -1, 8)
+        k = int(q.shape[0])
+        if k == 0:
+            return np.zeros((0, self.height, 8), dtype=np.uint32), np.zeros(0, dtype=np.uint64)
+        with self.dev.scope() as tmp:
+            d_q, d_scr, d_idx = tmp.upload(q), tmp.alloc(self.dev.find_scratch_bytes(k)), tmp.alloc(8 * k)
+            self.find_async(d_q, k, d_scr, d_idx)
+            sib = np.zeros((k, self.height, 8), dtype=np.uint32)
+            if self.height:
+                d_sib = tmp.alloc(32 * k * self.height)
+                self.proofs_async(d_idx, k, d_sib)
+                sib = self.dev.download(d_sib, 32 * k * self.height).reshape(k, self.height, 8)
+            return sib, self.dev.download(d_idx, 8 * k, dtype=np.uint64)
 
     def multiproof_async(self, indices_buf, k, scratch_buf, nodes_buf, nodes_capacity, info_buf, stream=None):
         """ONE proof for the k leaves whose strictly increasing indices are in device memory, written to nodes_buf
@@ -849,6 +906,43 @@ class MerkleForest:
             d_sib, d_h = tmp.alloc(32 * k * self.levels), tmp.alloc(4 * k)
             self.proofs_async(d_trees, d_idx, k, d_sib, d_h)
             return self.dev.download(d_sib, 32 * k * self.levels).reshape(k, self.levels, 8), self.dev.download(d_h, 4 * k)
+
+    def find_async(self, queries_buf, k, scratch_buf, trees_buf, indices_buf, stream=None):
+        """trees_buf[q], indices_buf[q] = where the digest queries_buf[q] is a leaf: the lowest position of the forest wins;
+        NO_TREE (0xFFFFFFFF) and NOT_FOUND (2^64 - 1) when it is none.  Device memory throughout, scratch_buf of
+        dev.find_scratch_bytes(k) bytes; ordered on `stream` behind earlier updates.  The two outputs are what proofs_async takes."""
+        self.dev.forest_find_async(self.digests, self.total, self.offsets, self.ntrees, queries_buf, k, scratch_buf, trees_buf, indices_buf,
+                                   stream=stream)
+
+    def find(self, digests):
+        """(trees [k] uint32, indices [k] uint64): for each digest ([k, 8] uint32, a host array) the tree and the index inside
+        it at which it is a leaf -- the lowest position of the forest when there are several -- or NO_TREE and NOT_FOUND.
+        Inner nodes and roots are not leaves."""
+        q = _host(digests, np.uint32, -1, 8)
+        k = int(q.shape[0])
+        if k == 0:
+            return np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint64)
+        with self.dev.scope() as tmp:
+            d_q, d_scr, d_trees, d_idx = tmp.upload(q), tmp.alloc(self.dev.find_scratch_bytes(k)), tmp.alloc(4 * k), tmp.alloc(8 * k)
+            self.find_async(d_q, k, d_scr, d_trees, d_idx)
+            return self.dev.download(d_trees, 4 * k), self.dev.download(d_idx, 8 * k, dtype=np.uint64)
+
+    def proofs_of(self, digests):
+        """(siblings [k, levels, 8] uint32, heights [k] uint32, trees [k] uint32, indices [k] uint64): hash -> position ->
+        proof on the device, nothing downloaded in between.  What proofs(trees, indices) returns, and the positions; a digest
+        that is no leaf gets NO_TREE, NOT_FOUND, height 0 and zero cells."""
+        q = _host(digests, np.uint32, -1, 8)
+        k = int(q.shape[0])
+        if k == 0:
+            return (np.zeros((0, self.levels, 8), dtype=np.uint32), np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint32),
+                    np.zeros(0, dtype=np.uint64))
+        with self.dev.scope() as tmp:
+            d_q, d_scr, d_trees, d_idx = tmp.upload(q), tmp.alloc(self.dev.find_scratch_bytes(k)), tmp.alloc(4 * k), tmp.alloc(8 * k)
+            d_sib, d_h = tmp.alloc(32 * k * self.levels), tmp.alloc(4 * k)
+            self.find_async(d_q, k, d_scr, d_trees, d_idx)
+            self.proofs_async(d_trees, d_idx, k, d_sib, d_h)
+            return (self.dev.download(d_sib, 32 * k * self.levels).reshape(k, self.levels, 8), self.dev.download(d_h, 4 * k),
+                    self.dev.download(d_trees, 4 * k), self.dev.download(d_idx, 8 * k, dtype=np.uint64))
 
     def multiproof_async(self, trees_buf, indices_buf, k, scratch_buf, nodes_buf, nodes_capacity, heights_buf, info_buf, stream=None):
         """ONE proof for the k (tree, index) entries in device memory (strictly increasing pairs), written to nodes_buf
