@@ -444,16 +444,17 @@ vkmr_status vkmr_hip_roots_in_slice_order_async(int, vkmr_stream, const vkmr_dig
 
 size_t vkmr_hip_reduce_slices_scratch_bytes(uint64_t capacity, uint32_t nslices)
 {
-    if (nslices == 0) nslices = 1;
-    return (size_t)vkmr_plan::cells_upper_bound(capacity, nslices) * nslices * sizeof(vkmr_digest);
+    return (size_t)vkmr_plan::slices_scratch_cells(capacity, nslices) * sizeof(vkmr_digest);
 }
 
 vkmr_status vkmr_hip_reduce_slices_async(int dev, vkmr_stream s, const vkmr_digest* digests, uint32_t nslices, uint64_t capacity,
                                          uint64_t count_last, uint32_t height, void* scratch, vkmr_digest* roots)
 {
     if (!digests || !roots || nslices == 0 || count_last == 0 || count_last > capacity) return fail(VKMR_ERR_INVALID, "reduce_slices: bad argument");
-    if (capacity > 128 && room_at(scratch) < vkmr_plan::cells_written(nslices == 1 ? count_last : capacity, nslices) * nslices * 32)
-        return fail(VKMR_ERR_INVALID, "reduce_slices: scratch smaller than the real kernels need");
+    const vkmr_plan::SliceChunks chunks = vkmr_plan::slice_chunks(nslices);   // the real library reuses the scratch chunk by chunk
+    for (uint32_t c = 0; c < chunks.count(); ++c)
+        if (capacity > 128 && room_at(scratch) < vkmr_plan::cells_written(nslices == 1 ? count_last : capacity, chunks.size(c)) * chunks.size(c) * 32)
+            return fail(VKMR_ERR_INVALID, "reduce_slices: scratch smaller than the real kernels need");
     for (uint32_t k = 0; k < nslices; ++k) {
         const uint64_t n = (k + 1 == nslices) ? count_last : capacity;
         if (vkmr_plan::ceil_shift(n, height) != 1) return fail(VKMR_ERR_INVALID, "reduce_slices: height");
@@ -464,7 +465,7 @@ vkmr_status vkmr_hip_reduce_slices_async(int dev, vkmr_stream s, const vkmr_dige
     return VKMR_OK;
 }
 
-size_t vkmr_hip_reduce_levels_scratch_bytes(uint64_t count) { return (size_t)(vkmr_plan::ceil_shift(count, 1) + vkmr_plan::ceil_shift(count, 2) + 2) * 32; }
+size_t vkmr_hip_reduce_levels_scratch_bytes(uint64_t count) { return (size_t)vkmr_plan::levels_scratch_cells(count) * sizeof(vkmr_digest); }
 vkmr_status vkmr_hip_reduce_levels_async(int dev, vkmr_stream s, const vkmr_digest* digests, uint64_t count, uint32_t height, void* scratch,
                                          vkmr_digest* root)
 {

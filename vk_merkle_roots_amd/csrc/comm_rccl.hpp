@@ -113,7 +113,7 @@ extern "C" {
 
 vkmr_status vkmr_hip_comm_create_id(void* id)
 {
-    if (!id) return fail(VKMR_ERR_INVALID, "vkmr_hip_comm_create_id: null pointer");
+    if (!id) return refuse(__func__, "null pointer");
     const auto& r = vkmr_comm_detail::rccl();
     if (!r.ok) return fail(VKMR_ERR_COMM, r.why);
     static_assert(sizeof(ncclUniqueId) == VKMR_COMM_ID_BYTES, "VKMR_COMM_ID_BYTES must be sizeof(ncclUniqueId)");
@@ -125,7 +125,7 @@ vkmr_status vkmr_hip_comm_create_id(void* id)
 
 vkmr_status vkmr_hip_comm_init_rank(int dev, const void* id, int nranks, int rank, vkmr_comm* out)
 {
-    if (!id || !out || nranks < 1 || rank < 0 || rank >= nranks) return fail(VKMR_ERR_INVALID, "vkmr_hip_comm_init_rank: bad argument");
+    if (!id || !out || nranks < 1 || rank < 0 || rank >= nranks) return refuse(__func__, "bad argument");
     const auto& r = vkmr_comm_detail::rccl();
     if (!r.ok) return fail(VKMR_ERR_COMM, r.why);
     VKMR_TRY(hipSetDevice(dev));
@@ -144,7 +144,7 @@ vkmr_status vkmr_hip_comm_init_rank(int dev, const void* id, int nranks, int ran
 
 vkmr_status vkmr_hip_comm_init_all(const int* devs, int ndev, vkmr_comm* out)
 {
-    if (!devs || !out || ndev < 1) return fail(VKMR_ERR_INVALID, "vkmr_hip_comm_init_all: bad argument");
+    if (!devs || !out || ndev < 1) return refuse(__func__, "bad argument");
     const auto& r = vkmr_comm_detail::rccl();
     if (!r.ok) return fail(VKMR_ERR_COMM, r.why);
     vkmr_comm_s* comm = new vkmr_comm_s;
@@ -198,7 +198,7 @@ vkmr_status vkmr_hip_comm_destroy(vkmr_comm c)
 
 vkmr_status vkmr_hip_comm_size(vkmr_comm c, int* nranks, int* nlocal)
 {
-    if (!c) return fail(VKMR_ERR_INVALID, "vkmr_hip_comm_size: null communicator");
+    if (!c) return refuse(__func__, "null communicator");
     if (nranks) *nranks = c->nranks;
     if (nlocal) *nlocal = (int)c->comms.size();
     return VKMR_OK;
@@ -207,12 +207,12 @@ vkmr_status vkmr_hip_comm_size(vkmr_comm c, int* nranks, int* nlocal)
 vkmr_status vkmr_hip_gather_roots_async(vkmr_comm c, const vkmr_stream* streams, const vkmr_digest* const* roots_dev,
                                         uint32_t per_rank, vkmr_digest* const* all_dev)
 {
-    if (!c || !streams || !roots_dev || !all_dev || per_rank == 0) return fail(VKMR_ERR_INVALID, "vkmr_hip_gather_roots_async: bad argument");
+    if (!c || !streams || !roots_dev || !all_dev || per_rank == 0) return refuse(__func__, "bad argument");
     const auto& r = vkmr_comm_detail::rccl();
     if (!r.ok) return fail(VKMR_ERR_COMM, r.why);
     const size_t nlocal = c->comms.size();
     for (size_t i = 0; i < nlocal; ++i)
-        if (!roots_dev[i] || !all_dev[i]) return fail(VKMR_ERR_INVALID, "vkmr_hip_gather_roots_async: null buffer");
+        if (!roots_dev[i] || !all_dev[i]) return refuse(__func__, "null buffer");
     // one collective; a process that drives several ranks issues them as one group
     if (nlocal > 1) VKMR_NCCL(r.GroupStart());
     ncclResult_t first_err = ncclSuccess;
@@ -232,14 +232,11 @@ vkmr_status vkmr_hip_gather_roots_async(vkmr_comm c, const vkmr_stream* streams,
 vkmr_status vkmr_hip_roots_in_slice_order_async(int dev, vkmr_stream s, const vkmr_digest* gathered_dev, uint32_t nranks,
                                                 uint32_t per_rank, uint32_t total, vkmr_digest* out_dev)
 {
-    if (!gathered_dev || !out_dev || nranks == 0 || per_rank == 0) return fail(VKMR_ERR_INVALID, "vkmr_hip_roots_in_slice_order_async: bad argument");
-    if ((uint64_t)total > (uint64_t)nranks * per_rank) return fail(VKMR_ERR_INVALID, "vkmr_hip_roots_in_slice_order_async: more roots than were gathered");
+    if (!gathered_dev || !out_dev || nranks == 0 || per_rank == 0) return refuse(__func__, "bad argument");
+    if ((uint64_t)total > (uint64_t)nranks * per_rank) return refuse(__func__, "more roots than were gathered");
     if (total == 0) return VKMR_OK;
     VKMR_TRY(hipSetDevice(dev));
-    hipLaunchKernelGGL(roots_in_slice_order_kernel, dim3((total + 255u) / 256u), dim3(256), 0, S(s), reinterpret_cast<const Node*>(gathered_dev),
-                       nranks, per_rank, total, reinterpret_cast<Node*>(out_dev));
-    VKMR_TRY(hipGetLastError());
-    return VKMR_OK;
+    return launch(roots_in_slice_order_kernel, dim3((total + 255u) / 256u), dim3(256), S(s), nodes(gathered_dev), nranks, per_rank, total, nodes(out_dev));
 }
 
 }  // extern "C"

@@ -14,8 +14,7 @@
 #pragma once
 
 #include "forest_plan.hpp"
-
-#define VKMR_TREE_MAX_LEVELS 64
+#include "tree_plan.hpp"   // VKMR_TREE_MAX_LEVELS, VKMR_MP_HEADER_WORDS, VKMR_MP_BLOCK_WORDS
 
 // off[l] / base[l] for every level, passed by value (kernel arguments: 512 bytes).  Entry 0 is unused: level 0 is the digests.
 struct TreeLevels { uint64_t off[VKMR_TREE_MAX_LEVELS]; };
@@ -130,9 +129,6 @@ __device__ __forceinline__ void update_level(const Entries e, const Span span, c
 // Header (uint64 words): [0] status (the checks OR into its low 32 bits), [1] M, [2 + l] m_l over all trees.  Every kernel
 // behind a check reads [0] first and does nothing when it is nonzero.  The gather's header is the caller's info_dev, the
 // verifier's lies in its scratch.
-
-#define VKMR_MP_HEADER_WORDS (2 + VKMR_TREE_MAX_LEVELS)   // status, M, up to 64 level counts
-#define VKMR_MP_BLOCK_WORDS 256                           // ballot words per block of the prefix sum: 16384 entries
 
 // The flags of every level l < levels (the height of one tree, the stride of a forest).  The status is the same word in
 // every lane and `levels` a kernel argument, so every lane of a wavefront reaches every ballot: the predicate goes inside it,

@@ -60,6 +60,19 @@ inline uint64_t stored_level_base(uint64_t total, uint32_t ntrees, uint32_t l)
 // Cells of the stored forest: levels 1 .. `levels`.
 inline uint64_t stored_cells(uint64_t total, uint32_t ntrees, uint32_t levels) { return stored_level_base(total, ntrees, levels + 1); }
 
+// The most nodes a multiproof of k leaves of the forest holds (vkmr_hip_forest_multiproof_async): at most one per parent of
+// a live tree -- the cells of level l + 1 -- and no more than k a level.
+inline uint64_t multiproof_max_nodes(uint64_t total, uint32_t ntrees, uint64_t max_count, uint32_t k)
+{
+    const uint32_t levels = launches(total, max_count);
+    uint64_t nodes = 0;
+    for (uint32_t l = 0; l < levels; ++l) {
+        const uint64_t parents = level_cells(total, ntrees, l + 1);
+        nodes += parents < k ? parents : k;
+    }
+    return nodes;
+}
+
 // ---- leaf updates of a stored forest (vkmr_hip_forest_update_async): one step of one entry.  Entry (tree t with offset o
 // and count c, leaf index i < c) at level l >= 1 rehashes parent p = i >> l of tree t's level l from the n_in cells of its
 // level l - 1.  forest_update_level_kernel and the CPU replay in tests/c/forest_update_plan_test.cpp both run this text.

@@ -98,4 +98,47 @@ inline uint64_t cells_upper_bound(uint64_t count, uint32_t nslices)
     return first + ceil_shift(first, 1) + 2;
 }
 
+// `height` levels must take `count` nodes to exactly one.  A tree over 2^64 leaves does not
+// exist, so heights beyond 63 are refused rather than special-cased.
+inline bool height_ok(uint64_t count, uint32_t height)
+{
+    if (count == 0 || height > 63) return false;
+    return ceil_shift(count, height) == 1;
+}
+
+// ---- runs of slices (vkmr_hip_reduce_slices_async).  grid.y carries the slice index: at most SLICE_CHUNK slices per
+// launch sequence; a longer run goes in chunks on the same stream (the scratch is reused, the stream serialises them).
+constexpr uint32_t SLICE_CHUNK = 32768u;
+
+// The chunks a run of nslices >= 1 is reduced in: `nfull` of `full` slices, then one of `rest` (0: none).
+struct SliceChunks {
+    uint32_t full, nfull, rest;
+    uint32_t count() const { return nfull + (rest ? 1u : 0u); }
+    uint32_t first(uint32_t c) const { return c * full; }
+    uint32_t size(uint32_t c) const { return c < nfull ? full : rest; }
+};
+
+inline SliceChunks slice_chunks(uint32_t nslices)
+{
+    SliceChunks ch;
+    ch.full = nslices > SLICE_CHUNK ? SLICE_CHUNK : nslices;
+    ch.nfull = nslices > SLICE_CHUNK ? nslices / SLICE_CHUNK : 1u;
+    ch.rest = nslices > SLICE_CHUNK ? nslices % SLICE_CHUNK : 0u;
+    return ch;
+}
+
+// Scratch cells of such a run: what the largest chunk's passes write -- the full chunks or the shorter last one.
+inline uint64_t slices_scratch_cells(uint64_t capacity, uint32_t nslices)
+{
+    const SliceChunks ch = slice_chunks(nslices ? nslices : 1u);
+    const uint64_t cells = cells_upper_bound(capacity, ch.full) * ch.full;
+    const uint64_t last = ch.rest ? cells_upper_bound(capacity, ch.rest) * ch.rest : 0;
+    return last > cells ? last : cells;
+}
+
+// ---- one level per launch (vkmr_hip_reduce_levels_async): two ping-pong buffers, levels 1 and 2 (every later level is no
+// larger than the one two below it), the second behind the first.
+inline uint64_t levels_second_buffer(uint64_t count) { return ceil_shift(count, 1); }
+inline uint64_t levels_scratch_cells(uint64_t count) { return levels_second_buffer(count) + ceil_shift(count, 2) + 2; }
+
 }  // namespace vkmr_plan

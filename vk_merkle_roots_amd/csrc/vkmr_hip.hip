@@ -26,8 +26,15 @@
 //   merkle_math.hpp     the integer rules, no HIP types (ceil_shift, height, right_child, sibling): shared with host/ and tests/c
 //   meta_kernels.hpp    sizes_*_kernel         metadata entries from 16-bit sizes   (Batches.cpp:64-121)
 //
-// Host side: plain launches on the caller's stream; no allocation, no sync inside
-// the *_async entry points.
+// Plans (no HIP types either: g++ compiles them, tests/c replays them, the test double sizes its scratch with them)
+//   map_plan.hpp        the map kernel's fetch mode and tile for a batch
+//   reduce_plan.hpp     the launch schedule of a slice reduction, height_ok, the chunks of a run of slices, the scratch sizes
+//   tree_plan.hpp       the stored tree's level offsets, the multiproof node bound and scratch layout
+//   forest_plan.hpp     where a forest's nodes lie, level by level; its scratch, stored size and multiproof node bound
+//   find_plan.hpp       the lookup's scratch layout and scan grid
+//
+// Host side: plain launches on the caller's stream, each through launch() and so each checked; every argument refusal
+// through refuse(__func__, why); no allocation, no sync inside the *_async entry points.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -42,6 +49,7 @@
 using vkmr_dev::Node;
 
 #include "map_kernel.hpp"
+#include "map_plan.hpp"
 #include "meta_kernels.hpp"
 #ifdef VKMR_EXPERIMENTS
 #include "../../include/vkmr_hip_experiments.h"
@@ -49,6 +57,7 @@ using vkmr_dev::Node;
 #endif
 #include "reduce_kernels.hpp"
 #include "reduce_plan.hpp"
+#include "tree_plan.hpp"
 #include "tree_kernels.hpp"
 #include "forest_kernels.hpp"
 #include "forest_tree_kernels.hpp"
@@ -78,11 +87,13 @@ static vkmr_status from_hip(hipError_t e, const char* what)
     return fail(VKMR_ERR_HIP, what, e);
 }
 
-#define VKMR_TRY(expr)                                   \
+// Return this vkmr_status unless it is VKMR_OK; VKMR_TRY: the same for a hipError_t.
+#define VKMR_CHECK(expr)                                 \
     do {                                                 \
-        vkmr_status st__ = from_hip((expr), #expr);      \
+        const vkmr_status st__ = (expr);                 \
         if (st__ != VKMR_OK) return st__;                \
     } while (0)
+#define VKMR_TRY(expr) VKMR_CHECK(from_hip((expr), #expr))
 
 static inline hipStream_t S(vkmr_stream s) { return reinterpret_cast<hipStream_t>(s); }
 static inline hipEvent_t E(vkmr_event e) { return reinterpret_cast<hipEvent_t>(e); }
@@ -94,12 +105,20 @@ static inline Node* nodes(void* p) { return static_cast<Node*>(p); }
 static inline uint64_t groups_of(uint64_t items) { return (items + 255) / 256; }
 static inline dim3 grid_of(uint64_t items, uint32_t y = 1) { return dim3((uint32_t)groups_of(items), y); }
 static inline bool grid_too_large(uint64_t groups) { return groups > 0x7fffffffull; }
-// A refusal in the words "<entry point>: <why>".
+// A refusal in the words "<entry point>: <why>".  An entry point passes __func__; a helper that refuses on its behalf is given it.
 static vkmr_status refuse(const char* who, const char* why)
 {
-    char what[128];
-    snprintf(what, sizeof what, "%s: %s", who, why);
-    return fail(VKMR_ERR_INVALID, what);
+    snprintf(g_err, sizeof g_err, "%s: %s", who, why);
+    return VKMR_ERR_INVALID;
+}
+
+// One launch without dynamic LDS, checked.  The arguments convert to the kernel's own parameter types as in a plain call.
+template <class T> struct as_declared { typedef T type; };
+template <class... P>
+static vkmr_status launch(void (*kernel)(P...), dim3 grid, dim3 block, hipStream_t stream, typename as_declared<P>::type... args)
+{
+    hipLaunchKernelGGL(kernel, grid, block, 0, stream, args...);
+    return from_hip(hipGetLastError(), "hipGetLastError()");
 }
 
 extern "C" {
@@ -126,7 +145,7 @@ const char* vkmr_hip_kernel_info(void);   // defined after the map entry point: 
 
 vkmr_status vkmr_hip_device_count(int* count)
 {
-    if (!count) return fail(VKMR_ERR_INVALID, "vkmr_hip_device_count: null out pointer");
+    if (!count) return refuse(__func__, "null out pointer");
     int n = 0;
     hipError_t e = hipGetDeviceCount(&n);
     if (e != hipSuccess) {   // no driver / no GPU: zero devices, like an empty Vulkan enumeration
@@ -141,7 +160,7 @@ vkmr_status vkmr_hip_device_count(int* count)
 
 vkmr_status vkmr_hip_device_name(int dev, char* buf, size_t buflen)
 {
-    if (!buf || buflen == 0) return fail(VKMR_ERR_INVALID, "vkmr_hip_device_name: null buffer");
+    if (!buf || buflen == 0) return refuse(__func__, "null buffer");
     hipDeviceProp_t p;
     VKMR_TRY(hipGetDeviceProperties(&p, dev));
     // some ROCm installs leave the marketing name empty: fall back to the ISA name
@@ -151,7 +170,7 @@ vkmr_status vkmr_hip_device_name(int dev, char* buf, size_t buflen)
 
 vkmr_status vkmr_hip_device_mem_info(int dev, size_t* free_bytes, size_t* total_bytes)
 {
-    if (!free_bytes || !total_bytes) return fail(VKMR_ERR_INVALID, "vkmr_hip_device_mem_info: null out pointer");
+    if (!free_bytes || !total_bytes) return refuse(__func__, "null out pointer");
     VKMR_TRY(hipSetDevice(dev));
     VKMR_TRY(hipMemGetInfo(free_bytes, total_bytes));
     return VKMR_OK;
@@ -168,7 +187,7 @@ vkmr_status vkmr_hip_device_geometry(int dev, int* compute_units, int* wavefront
 
 vkmr_status vkmr_hip_host_alloc(size_t bytes, void** out)
 {
-    if (!out || bytes == 0) return fail(VKMR_ERR_INVALID, "vkmr_hip_host_alloc: bad argument");
+    if (!out || bytes == 0) return refuse(__func__, "bad argument");
     void* p = nullptr;
     VKMR_TRY(hipHostMalloc(&p, bytes, hipHostMallocDefault));
     memset(p, 0, bytes);
@@ -185,7 +204,7 @@ vkmr_status vkmr_hip_host_free(void* p)
 
 vkmr_status vkmr_hip_device_alloc(int dev, size_t bytes, void** out)
 {
-    if (!out || bytes == 0) return fail(VKMR_ERR_INVALID, "vkmr_hip_device_alloc: bad argument");
+    if (!out || bytes == 0) return refuse(__func__, "bad argument");
     VKMR_TRY(hipSetDevice(dev));
     void* p = nullptr;
     VKMR_TRY(hipMalloc(&p, bytes));
@@ -203,7 +222,7 @@ vkmr_status vkmr_hip_device_free(int dev, void* p)
 
 vkmr_status vkmr_hip_memset_async(int dev, vkmr_stream s, void* dst, int value, size_t bytes)
 {
-    if (!dst) return fail(VKMR_ERR_INVALID, "vkmr_hip_memset_async: null pointer");
+    if (!dst) return refuse(__func__, "null pointer");
     VKMR_TRY(hipSetDevice(dev));
     VKMR_TRY(hipMemsetAsync(dst, value, bytes, S(s)));
     return VKMR_OK;
@@ -211,7 +230,7 @@ vkmr_status vkmr_hip_memset_async(int dev, vkmr_stream s, void* dst, int value, 
 
 vkmr_status vkmr_hip_memcpy_h2d_async(int dev, vkmr_stream s, void* dst_dev, const void* src_host, size_t bytes)
 {
-    if (!dst_dev || !src_host) return fail(VKMR_ERR_INVALID, "vkmr_hip_memcpy_h2d_async: null pointer");
+    if (!dst_dev || !src_host) return refuse(__func__, "null pointer");
     VKMR_TRY(hipSetDevice(dev));
     VKMR_TRY(hipMemcpyAsync(dst_dev, src_host, bytes, hipMemcpyHostToDevice, S(s)));
     return VKMR_OK;
@@ -219,7 +238,7 @@ vkmr_status vkmr_hip_memcpy_h2d_async(int dev, vkmr_stream s, void* dst_dev, con
 
 vkmr_status vkmr_hip_memcpy_d2h_async(int dev, vkmr_stream s, void* dst_host, const void* src_dev, size_t bytes)
 {
-    if (!dst_host || !src_dev) return fail(VKMR_ERR_INVALID, "vkmr_hip_memcpy_d2h_async: null pointer");
+    if (!dst_host || !src_dev) return refuse(__func__, "null pointer");
     VKMR_TRY(hipSetDevice(dev));
     VKMR_TRY(hipMemcpyAsync(dst_host, src_dev, bytes, hipMemcpyDeviceToHost, S(s)));
     return VKMR_OK;
@@ -227,7 +246,7 @@ vkmr_status vkmr_hip_memcpy_d2h_async(int dev, vkmr_stream s, void* dst_host, co
 
 vkmr_status vkmr_hip_stream_create(int dev, vkmr_stream* out)
 {
-    if (!out) return fail(VKMR_ERR_INVALID, "vkmr_hip_stream_create: null out pointer");
+    if (!out) return refuse(__func__, "null out pointer");
     VKMR_TRY(hipSetDevice(dev));
     hipStream_t s;
     VKMR_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
@@ -252,7 +271,7 @@ vkmr_status vkmr_hip_stream_sync(int dev, vkmr_stream s)
 
 vkmr_status vkmr_hip_event_create(int dev, vkmr_event* out)
 {
-    if (!out) return fail(VKMR_ERR_INVALID, "vkmr_hip_event_create: null out pointer");
+    if (!out) return refuse(__func__, "null out pointer");
     VKMR_TRY(hipSetDevice(dev));
     hipEvent_t e;
     VKMR_TRY(hipEventCreate(&e));
@@ -270,7 +289,7 @@ vkmr_status vkmr_hip_event_destroy(int dev, vkmr_event e)
 
 vkmr_status vkmr_hip_event_record(int dev, vkmr_event e, vkmr_stream s)
 {
-    if (!e) return fail(VKMR_ERR_INVALID, "vkmr_hip_event_record: null event");
+    if (!e) return refuse(__func__, "null event");
     VKMR_TRY(hipSetDevice(dev));
     VKMR_TRY(hipEventRecord(E(e), S(s)));
     return VKMR_OK;
@@ -278,7 +297,7 @@ vkmr_status vkmr_hip_event_record(int dev, vkmr_event e, vkmr_stream s)
 
 vkmr_status vkmr_hip_event_query(int dev, vkmr_event e)
 {
-    if (!e) return fail(VKMR_ERR_INVALID, "vkmr_hip_event_query: null event");
+    if (!e) return refuse(__func__, "null event");
     VKMR_TRY(hipSetDevice(dev));
     hipError_t r = hipEventQuery(E(e));
     if (r == hipErrorNotReady) {
@@ -290,7 +309,7 @@ vkmr_status vkmr_hip_event_query(int dev, vkmr_event e)
 
 vkmr_status vkmr_hip_event_wait(int dev, vkmr_event e)
 {
-    if (!e) return fail(VKMR_ERR_INVALID, "vkmr_hip_event_wait: null event");
+    if (!e) return refuse(__func__, "null event");
     VKMR_TRY(hipSetDevice(dev));
     VKMR_TRY(hipEventSynchronize(E(e)));
     return VKMR_OK;
@@ -298,7 +317,7 @@ vkmr_status vkmr_hip_event_wait(int dev, vkmr_event e)
 
 vkmr_status vkmr_hip_stream_wait_event(int dev, vkmr_stream s, vkmr_event e)
 {
-    if (!e) return fail(VKMR_ERR_INVALID, "vkmr_hip_stream_wait_event: null event");
+    if (!e) return refuse(__func__, "null event");
     VKMR_TRY(hipSetDevice(dev));
     VKMR_TRY(hipStreamWaitEvent(S(s), E(e), 0));
     return VKMR_OK;
@@ -306,7 +325,7 @@ vkmr_status vkmr_hip_stream_wait_event(int dev, vkmr_stream s, vkmr_event e)
 
 vkmr_status vkmr_hip_event_elapsed_ms(int dev, vkmr_event begin, vkmr_event end, float* ms)
 {
-    if (!begin || !end || !ms) return fail(VKMR_ERR_INVALID, "vkmr_hip_event_elapsed_ms: null argument");
+    if (!begin || !end || !ms) return refuse(__func__, "null argument");
     VKMR_TRY(hipSetDevice(dev));
     VKMR_TRY(hipEventElapsedTime(ms, E(begin), E(end)));
     return VKMR_OK;
@@ -314,23 +333,12 @@ vkmr_status vkmr_hip_event_elapsed_ms(int dev, vkmr_event begin, vkmr_event end,
 
 // ---- map ------------------------------------------------------------------------
 
-// What the last vkmr_hip_map_async of this process chose (reported by vkmr_hip_kernel_info).
-enum { MAP_NONE = 0, MAP_STAGED, MAP_DIRECT512, MAP_DIRECT256, MAP_LONG512, MAP_LONG256, MAP_EXPERIMENT };
+// What the last vkmr_hip_map_async of this process chose (reported by vkmr_hip_kernel_info): a vkmr_map::Mode, or one of these.
+enum { MAP_NONE = -1, MAP_EXPERIMENT = -2 };
 static std::atomic<int> g_last_map_mode{MAP_NONE};       // diagnostics only; several host threads may drive different devices
 static std::atomic<uint32_t> g_last_map_tile{0};
 
-// The shipped fetch modes (csrc/map_kernel.hpp).  The mode is chosen from the batch alone:
-//   average packed string < 128 B   LDS-staged tiles (HBM traffic == algorithmic bytes)
-//   128 B .. 512 B                  per-lane 16-byte loads, one 64-byte block per trip, 8 wavefronts per SIMD (256-lane workgroups when the launch is short)
-//   512 B and more                  per-lane loads, TWO blocks (128 bytes) per trip: a 128-byte line is asked for by at most two trips instead
-//                                   of three -- 8.6 instead of 11.3 GB at the L2-fabric boundary for 4.3 GB of rndm * 4096, the same
-//                                   2.29 ms (87 VGPRs, 5 wavefronts per SIMD); at 150 B on average it is 3 % slower, hence the threshold
-//                                   (profiles/r04_long_strings_two_blocks.txt)
-// Round 2 also shipped a third mode for strings of 1 KiB and more -- whole 128-byte lines through a per-lane LDS window,
-// 1.06x instead of 1.46x the algorithmic reads for 1-2 % of time.  Its 272 bytes of LDS per lane allow two wavefronts
-// per SIMD, and since the issue pass (isa_prio_pass.py) the instruction pairing that decides the speed needs
-// occupancy: 2.56 ms against 2.26 ms for the per-lane loads on rndm * 4096 (profiles/r03_long_strings_modes.txt).
-// It stays in the experiments build (VKMR_MAP_VARIANT=5).
+// The shipped fetch modes (csrc/map_kernel.hpp); which one a batch gets, and with which tile: map_plan.hpp.
 // (spelled with every template argument: the names must read exactly as a profiler prints them, provenance.py)
 #define VKMR_MAP_STAGED_KERNEL map_kernel<512, 1024, 17664, 0, false, 0>
 #define VKMR_MAP_DIRECT512_KERNEL map_kernel<512, 2048, 64, 2, true, 0>
@@ -338,36 +346,9 @@ static std::atomic<uint32_t> g_last_map_tile{0};
 #define VKMR_MAP_LONG512_KERNEL map_kernel<512, 2048, 64, 5, true, 0>
 #define VKMR_MAP_LONG256_KERNEL map_kernel<256, 2048, 64, 5, true, 0>
 
-// Strings per LDS-staged tile: what is expected to fit the staging area, three standard deviations of a tile's
-// size below it (string lengths spread like rndm's, uniform in [1, max]: sigma / mean of T strings is about
-// 0.6 / sqrt(T)); a tile that overflows anyway falls back to per-lane loads inside the kernel.  The more strings a
-// tile sorts the better: fewer of its groups straddle a block-count boundary, and 1024 strings are exactly two
-// groups of 64 for each of the 8 wavefronts (profiles/r02_map_tile_fill.txt).  69 KiB of staging is what still
-// lets two workgroups share a CU's LDS.  `fit_pct` (experiments build only) replaces the 3-sigma rule.
-static uint32_t staged_tile(uint64_t data_words, uint32_t count, uint32_t max_tile, uint32_t stage_words, int fit_pct = 0)
-{
-    uint32_t tile = max_tile;
-    if (data_words > 0) {
-        const double r = (double)stage_words * (double)count / (double)data_words;   // strings that fill the area on average
-        const double want = fit_pct ? r * fit_pct / 100.0 : r * (1.0 - 1.8 / __builtin_sqrt(r > 4.0 ? r : 4.0));
-        const uint64_t fit = want > 0.0 ? (uint64_t)want : 0;
-        if (fit >= max_tile / 4 && fit < tile) tile = (uint32_t)(fit & ~63ull);
-    }
-    // a launch too short to give every CU its two workgroups: smaller tiles, so that it still spreads over the chip
-    const uint32_t spread = (uint32_t)((count / 512u) & ~63u);
-    if (spread < tile) tile = spread < max_tile / 4 ? max_tile / 4 : spread;
-    return tile;
-}
-
-// Tiles of the per-lane modes: up to 2048 strings, smaller when the batch is short so that it still spreads over
-// the chip (>= ~1024 workgroups when it can).
-static uint32_t direct_tile(uint32_t count)
-{
-    const uint32_t tile = (count / 1024u) & ~63u;
-    return tile < 256u ? 256u : (tile > 2048u ? 2048u : tile);
-}
-
-static inline uint32_t tiles_of(uint32_t count, uint32_t tile) { return (uint32_t)(((uint64_t)count + tile - 1) / tile); }   // count + tile can pass 2^32
+using vkmr_map::direct_tile;
+using vkmr_map::staged_tile;
+using vkmr_map::tiles_of;
 
 #ifdef VKMR_EXPERIMENTS
 #include "map_experiments.hpp"   // tools build only: VKMR_MAP_VARIANT / _FIT / _TILE / _DYNLDS and the non-shipped instantiations
@@ -377,44 +358,28 @@ vkmr_status vkmr_hip_map_async(int dev, vkmr_stream s, const uint32_t* data_dev,
                                const vkmr_metadata* meta_dev, uint32_t count, vkmr_digest* out_dev)
 {
     if (count == 0) return VKMR_OK;
-    if (!meta_dev || !out_dev || (!data_dev && data_words != 0))
-        return fail(VKMR_ERR_INVALID, "vkmr_hip_map_async: null pointer");
+    if (!meta_dev || !out_dev || (!data_dev && data_words != 0)) return refuse(__func__, "null pointer");
     VKMR_TRY(hipSetDevice(dev));
-    const uint64_t avg_words = (data_words + count - 1) / count;
     Node* out = nodes(out_dev);
 #ifdef VKMR_EXPERIMENTS
-    if (vkmr_map_experiment(S(s), data_dev, data_words, meta_dev, count, out, avg_words)) {
+    if (vkmr_map_experiment(S(s), data_dev, data_words, meta_dev, count, out, vkmr_map::avg_words(data_words, count))) {
         g_last_map_mode = MAP_EXPERIMENT;
         VKMR_TRY(hipGetLastError());
         return VKMR_OK;
     }
 #endif
-    uint32_t tile = direct_tile(count);
-    if (avg_words >= 32) {
-        // strings of 128 B and more on average (a short launch: smaller workgroups spread it over the chip)
-        if (avg_words >= 128 && tile >= 1024u) {
-            g_last_map_mode = MAP_LONG512;
-            hipLaunchKernelGGL((VKMR_MAP_LONG512_KERNEL), dim3(tiles_of(count, tile)), dim3(512), 0, S(s), data_dev, data_words, meta_dev, count, out, tile);
-        } else if (avg_words >= 128) {
-            g_last_map_mode = MAP_LONG256;
-            hipLaunchKernelGGL((VKMR_MAP_LONG256_KERNEL), dim3(tiles_of(count, tile)), dim3(256), 0, S(s), data_dev, data_words, meta_dev, count, out, tile);
-        } else if (tile >= 1024u) {
-            g_last_map_mode = MAP_DIRECT512;
-            hipLaunchKernelGGL((VKMR_MAP_DIRECT512_KERNEL), dim3(tiles_of(count, tile)), dim3(512), 0, S(s), data_dev, data_words, meta_dev, count, out, tile);
-        } else {
-            g_last_map_mode = MAP_DIRECT256;
-            hipLaunchKernelGGL((VKMR_MAP_DIRECT256_KERNEL), dim3(tiles_of(count, tile)), dim3(256), 0, S(s), data_dev, data_words, meta_dev, count, out, tile);
-        }
-    } else {
-        // short strings (a cache line holds several): the per-lane mode is 1-2 % faster but re-reads lines that
-        // fell out of L2 (1.6x traffic, profiles/r01_map_fetch_modes.txt)
-        tile = staged_tile(data_words, count, 1024, 17664);
-        g_last_map_mode = MAP_STAGED;
-        hipLaunchKernelGGL((VKMR_MAP_STAGED_KERNEL), dim3(tiles_of(count, tile)), dim3(512), 0, S(s), data_dev, data_words, meta_dev, count, out, tile);
+    const vkmr_map::Plan p = vkmr_map::plan(data_words, count);
+    const dim3 grid(tiles_of(count, p.tile));
+    g_last_map_mode = p.mode;
+    g_last_map_tile = p.tile;
+    switch (p.mode) {
+        case vkmr_map::LONG512: return launch(VKMR_MAP_LONG512_KERNEL, grid, dim3(512), S(s), data_dev, data_words, meta_dev, count, out, p.tile);
+        case vkmr_map::LONG256: return launch(VKMR_MAP_LONG256_KERNEL, grid, dim3(256), S(s), data_dev, data_words, meta_dev, count, out, p.tile);
+        case vkmr_map::DIRECT512: return launch(VKMR_MAP_DIRECT512_KERNEL, grid, dim3(512), S(s), data_dev, data_words, meta_dev, count, out, p.tile);
+        case vkmr_map::DIRECT256: return launch(VKMR_MAP_DIRECT256_KERNEL, grid, dim3(256), S(s), data_dev, data_words, meta_dev, count, out, p.tile);
+        case vkmr_map::STAGED: break;
     }
-    g_last_map_tile = tile;
-    VKMR_TRY(hipGetLastError());
-    return VKMR_OK;
+    return launch(VKMR_MAP_STAGED_KERNEL, grid, dim3(512), S(s), data_dev, data_words, meta_dev, count, out, p.tile);
 }
 
 // ---- metadata from sizes (meta_kernels.hpp) ---------------------------------------------------------------------------
@@ -427,17 +392,15 @@ vkmr_status vkmr_hip_metadata_from_sizes_async(int dev, vkmr_stream s, const uin
                                                void* scratch_dev, vkmr_metadata* meta_dev)
 {
     if (count == 0) return VKMR_OK;
-    if (!sizes_dev || !scratch_dev || !meta_dev) return fail(VKMR_ERR_INVALID, "vkmr_hip_metadata_from_sizes_async: null pointer");
+    if (!sizes_dev || !scratch_dev || !meta_dev) return refuse(__func__, "null pointer");
     if ((reinterpret_cast<uintptr_t>(sizes_dev) & 15u) || (reinterpret_cast<uintptr_t>(meta_dev) & 15u))
-        return fail(VKMR_ERR_INVALID, "vkmr_hip_metadata_from_sizes_async: sizes and metadata must be 16-byte aligned");
+        return refuse(__func__, "sizes and metadata must be 16-byte aligned");
     VKMR_TRY(hipSetDevice(dev));
     const uint32_t nblocks = (uint32_t)(((uint64_t)count + VKMR_SIZES_BLOCK - 1) / VKMR_SIZES_BLOCK);
     uint32_t* blocks = static_cast<uint32_t*>(scratch_dev);
-    hipLaunchKernelGGL(sizes_block_words_kernel, dim3(nblocks), dim3(VKMR_SIZES_THREADS), 0, S(s), sizes_dev, count, blocks);
-    hipLaunchKernelGGL(sizes_block_starts_kernel, dim3(1), dim3(VKMR_SIZES_THREADS), 0, S(s), blocks, nblocks, first_word);
-    hipLaunchKernelGGL(sizes_expand_kernel, dim3(nblocks), dim3(VKMR_SIZES_THREADS), 0, S(s), sizes_dev, count, (const uint32_t*)blocks, meta_dev);
-    VKMR_TRY(hipGetLastError());
-    return VKMR_OK;
+    VKMR_CHECK(launch(sizes_block_words_kernel, dim3(nblocks), dim3(VKMR_SIZES_THREADS), S(s), sizes_dev, count, blocks));
+    VKMR_CHECK(launch(sizes_block_starts_kernel, dim3(1), dim3(VKMR_SIZES_THREADS), S(s), blocks, nblocks, first_word));
+    return launch(sizes_expand_kernel, dim3(nblocks), dim3(VKMR_SIZES_THREADS), S(s), sizes_dev, count, blocks, meta_dev);
 }
 
 #ifdef VKMR_EXPERIMENTS
@@ -464,30 +427,25 @@ size_t vkmr_hip_split_scratch_bytes(uint32_t text_bytes, uint32_t meta_capacity)
 vkmr_status vkmr_hip_split_text_async(int dev, vkmr_stream s, const uint8_t* text_dev, uint32_t text_bytes, void* scratch_dev, uint32_t* data_dev,
                                       uint64_t data_capacity_words, vkmr_metadata* meta_dev, uint32_t meta_capacity, uint32_t* result_dev)
 {
-    if (!result_dev) return fail(VKMR_ERR_INVALID, "vkmr_hip_split_text_async: null result pointer");
+    if (!result_dev) return refuse(__func__, "null result pointer");
     VKMR_TRY(hipSetDevice(dev));
     VKMR_TRY(hipMemsetAsync(result_dev, 0, 3 * sizeof(uint32_t), S(s)));
     if (text_bytes == 0) return VKMR_OK;
     if (!text_dev || !scratch_dev || !data_dev || !meta_dev || meta_capacity == 0)
-        return fail(VKMR_ERR_INVALID, "vkmr_hip_split_text_async: null pointer");
+        return refuse(__func__, "null pointer");
     if ((reinterpret_cast<uintptr_t>(text_dev) & 15u) || text_bytes > 0xFFFFFFE0u)
-        return fail(VKMR_ERR_INVALID, "vkmr_hip_split_text_async: the text must be 16-byte aligned and shorter than 4 GiB");
+        return refuse(__func__, "the text must be 16-byte aligned and shorter than 4 GiB");
     const SplitScratch sc = split_scratch(scratch_dev, text_bytes, meta_capacity);
     const uint32_t nb = (uint32_t)(((uint64_t)text_bytes + VKMR_SPLIT_BLOCK - 1) / VKMR_SPLIT_BLOCK);
     const uint32_t nwb = (uint32_t)(((uint64_t)meta_capacity + VKMR_SIZES_BLOCK - 1) / VKMR_SIZES_BLOCK);
-    hipLaunchKernelGGL(split_count_kernel, dim3(nb), dim3(VKMR_SPLIT_THREADS), 0, S(s), text_dev, text_bytes, sc.blk_count, sc.blk_after);
-    hipLaunchKernelGGL(split_scan_kernel, dim3(1), dim3(VKMR_SPLIT_THREADS), 0, S(s), sc.blk_count, sc.blk_after, nb, result_dev);
-    hipLaunchKernelGGL(split_lines_kernel, dim3(nb), dim3(VKMR_SPLIT_THREADS), 0, S(s), text_dev, text_bytes, (const uint32_t*)sc.blk_count,
-                       (const uint32_t*)sc.blk_after, sc.lines, meta_capacity, result_dev);
-    hipLaunchKernelGGL(split_block_words_kernel, dim3(nwb), dim3(VKMR_SIZES_THREADS), 0, S(s), (const vkmr_split::Line*)sc.lines, (const uint32_t*)result_dev,
-                       meta_capacity, sc.wblocks);
-    hipLaunchKernelGGL(sizes_block_starts_kernel, dim3(1), dim3(VKMR_SIZES_THREADS), 0, S(s), sc.wblocks, nwb, 0u);
-    hipLaunchKernelGGL(split_expand_kernel, dim3(nwb), dim3(VKMR_SIZES_THREADS), 0, S(s), (const vkmr_split::Line*)sc.lines, result_dev, meta_capacity,
-                       (const uint32_t*)sc.wblocks, meta_dev);
-    hipLaunchKernelGGL(split_pack_kernel, dim3((meta_capacity + 255u) / 256u), dim3(256), 0, S(s), text_dev, (const vkmr_split::Line*)sc.lines,
-                       (const vkmr_metadata*)meta_dev, result_dev, meta_capacity, data_dev, data_capacity_words);
-    VKMR_TRY(hipGetLastError());
-    return VKMR_OK;
+    const dim3 text_grid(nb), text_block(VKMR_SPLIT_THREADS), lines_grid(nwb), lines_block(VKMR_SIZES_THREADS);
+    VKMR_CHECK(launch(split_count_kernel, text_grid, text_block, S(s), text_dev, text_bytes, sc.blk_count, sc.blk_after));
+    VKMR_CHECK(launch(split_scan_kernel, dim3(1), text_block, S(s), sc.blk_count, sc.blk_after, nb, result_dev));
+    VKMR_CHECK(launch(split_lines_kernel, text_grid, text_block, S(s), text_dev, text_bytes, sc.blk_count, sc.blk_after, sc.lines, meta_capacity, result_dev));
+    VKMR_CHECK(launch(split_block_words_kernel, lines_grid, lines_block, S(s), sc.lines, result_dev, meta_capacity, sc.wblocks));
+    VKMR_CHECK(launch(sizes_block_starts_kernel, dim3(1), lines_block, S(s), sc.wblocks, nwb, 0));
+    VKMR_CHECK(launch(split_expand_kernel, lines_grid, lines_block, S(s), sc.lines, result_dev, meta_capacity, sc.wblocks, meta_dev));
+    return launch(split_pack_kernel, dim3((meta_capacity + 255u) / 256u), dim3(256), S(s), text_dev, sc.lines, meta_dev, result_dev, meta_capacity, data_dev, data_capacity_words);
 }
 #endif   // VKMR_EXPERIMENTS
 
@@ -507,15 +465,14 @@ vkmr_status vkmr_hip_warm_up(int dev, vkmr_stream s, unsigned what, size_t copy_
         if (what & VKMR_WARM_COPY) e = hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, S(s));
         else e = hipMemsetAsync(d, 0, 256, S(s));
     }
-    if (e == hipSuccess && (what & VKMR_WARM_KERNELS)) {
-        char* base = static_cast<char*>(d);
-        hipLaunchKernelGGL((VKMR_MAP_STAGED_KERNEL), dim3(1), dim3(512), 0, S(s), reinterpret_cast<const uint32_t*>(base + 64), (uint64_t)1,
-                           reinterpret_cast<const vkmr_metadata*>(base), 1u, reinterpret_cast<Node*>(base + 128), 1024u);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(S(s));
+    vkmr_status launched = VKMR_OK;
+    if (e == hipSuccess && (what & VKMR_WARM_KERNELS))
+        launched = launch(VKMR_MAP_STAGED_KERNEL, dim3(1), dim3(512), S(s), static_cast<const uint32_t*>(d) + 16, 1, static_cast<const vkmr_metadata*>(d), 1,
+                          nodes(d) + 4, 1024);
+    if (e == hipSuccess && launched == VKMR_OK) e = hipStreamSynchronize(S(s));
     if (d) (void)hipFree(d);
     if (h) (void)hipHostFree(h);
+    VKMR_CHECK(launched);
     VKMR_TRY(e);
     return VKMR_OK;
 }
@@ -527,11 +484,11 @@ const char* vkmr_hip_kernel_info(void)
     static thread_local char buf[512];
     const char* map = "map=(no launch yet; staged: " VKMR_STR((VKMR_MAP_STAGED_KERNEL)) ")";
     switch (g_last_map_mode.load()) {
-        case MAP_STAGED: map = "map=" VKMR_STR((VKMR_MAP_STAGED_KERNEL)) " LDS-staged tiles sorted by block count"; break;
-        case MAP_DIRECT512: map = "map=" VKMR_STR((VKMR_MAP_DIRECT512_KERNEL)) " per-lane 16-byte loads"; break;
-        case MAP_DIRECT256: map = "map=" VKMR_STR((VKMR_MAP_DIRECT256_KERNEL)) " per-lane 16-byte loads, short launch"; break;
-        case MAP_LONG512: map = "map=" VKMR_STR((VKMR_MAP_LONG512_KERNEL)) " per-lane 16-byte loads, two blocks per trip"; break;
-        case MAP_LONG256: map = "map=" VKMR_STR((VKMR_MAP_LONG256_KERNEL)) " per-lane 16-byte loads, two blocks per trip, short launch"; break;
+        case vkmr_map::STAGED: map = "map=" VKMR_STR((VKMR_MAP_STAGED_KERNEL)) " LDS-staged tiles sorted by block count"; break;
+        case vkmr_map::DIRECT512: map = "map=" VKMR_STR((VKMR_MAP_DIRECT512_KERNEL)) " per-lane 16-byte loads"; break;
+        case vkmr_map::DIRECT256: map = "map=" VKMR_STR((VKMR_MAP_DIRECT256_KERNEL)) " per-lane 16-byte loads, short launch"; break;
+        case vkmr_map::LONG512: map = "map=" VKMR_STR((VKMR_MAP_LONG512_KERNEL)) " per-lane 16-byte loads, two blocks per trip"; break;
+        case vkmr_map::LONG256: map = "map=" VKMR_STR((VKMR_MAP_LONG256_KERNEL)) " per-lane 16-byte loads, two blocks per trip, short launch"; break;
 #ifdef VKMR_EXPERIMENTS
         case MAP_EXPERIMENT: map = "map=EXPERIMENT (VKMR_MAP_VARIANT; not a product build)"; break;
 #endif
@@ -554,13 +511,7 @@ using vkmr_plan::STEP_BULK;
 using vkmr_plan::STEP_COLLAPSE;
 using vkmr_plan::STEP_TAIL;
 
-// `height` levels must take `count` nodes to exactly one.  A tree over 2^64 leaves does not
-// exist, so heights beyond 63 are refused rather than special-cased.
-static bool height_ok(uint64_t count, uint32_t height)
-{
-    if (count == 0 || height > 63) return false;
-    return ceil_shift(count, height) == 1;
-}
+using vkmr_plan::height_ok;
 
 size_t vkmr_hip_reduce_scratch_bytes(uint64_t count)
 {
@@ -572,7 +523,7 @@ size_t vkmr_hip_reduce_scratch_bytes(uint64_t count)
 // Reduces `nslices` slices (n_full nodes each, the last n_last) through `height`
 // levels each; slice k's root goes to roots[k].  The step sequence is that of a full
 // slice; a shorter last slice rides along (its surplus wavefronts exit at once).
-static vkmr_status reduce_launch(hipStream_t stream, const Node* digests, uint32_t nslices, uint64_t n_full, uint64_t n_last,
+static vkmr_status reduce_launch(const char* who, hipStream_t stream, const Node* digests, uint32_t nslices, uint64_t n_full, uint64_t n_last,
                                  uint32_t height, Node* scratch, Node* roots, const ProofArgs* proofs = nullptr)
 {
     const Node* in = digests;
@@ -588,10 +539,8 @@ static vkmr_status reduce_launch(hipStream_t stream, const Node* digests, uint32
         g.n_full = n; g.n_last = nl; g.in_stride = in_stride; g.nslices = nslices;
         if (st.kind == STEP_TAIL) {
             g.out_stride = 1;
-            if (prove) hipLaunchKernelGGL(reduce_tail_proofs_kernel, dim3(1, nslices), dim3(64), 0, stream, in, g, left, roots, *proofs, level0);
-            else hipLaunchKernelGGL(reduce_tail_kernel, dim3(1, nslices), dim3(64), 0, stream, in, g, left, roots);
-            VKMR_TRY(hipGetLastError());
-            return VKMR_OK;
+            if (prove) return launch(reduce_tail_proofs_kernel, dim3(1, nslices), dim3(64), stream, in, g, left, roots, *proofs, level0);
+            return launch(reduce_tail_kernel, dim3(1, nslices), dim3(64), stream, in, g, left, roots);
         }
         Node* out;
         if (pass == 0) {
@@ -605,16 +554,17 @@ static vkmr_status reduce_launch(hipStream_t stream, const Node* digests, uint32
             const uint32_t m = st.levels - 1u;
             const uint64_t waves = ceil_shift(n, 7 + m);
             const uint64_t grid = (waves + VKMR_PASS_WAVES - 1) / VKMR_PASS_WAVES;
-            if (grid_too_large(grid)) return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_async: slice too large");
-            if (prove) hipLaunchKernelGGL(reduce_pass_proofs_kernel, dim3((uint32_t)grid, nslices), dim3(VKMR_PASS_WAVES * 64), 0, stream, in, g, out, m, *proofs, level0);
-            else hipLaunchKernelGGL(reduce_pass_kernel, dim3((uint32_t)grid, nslices), dim3(VKMR_PASS_WAVES * 64), 0, stream, in, g, out, m);
+            if (grid_too_large(grid)) return refuse(who, "slice too large");
+            const dim3 pgrid((uint32_t)grid, nslices), pblock(VKMR_PASS_WAVES * 64);
+            VKMR_CHECK(prove ? launch(reduce_pass_proofs_kernel, pgrid, pblock, stream, in, g, out, m, *proofs, level0)
+                             : launch(reduce_pass_kernel, pgrid, pblock, stream, in, g, out, m));
         } else {
             const uint64_t cwaves = ceil_shift(n, 7);
             const dim3 cgrid((uint32_t)((cwaves + VKMR_COLLAPSE_WAVES - 1) / VKMR_COLLAPSE_WAVES), nslices);
-            if (prove) hipLaunchKernelGGL(reduce_collapse_proofs_kernel, cgrid, dim3(VKMR_COLLAPSE_WAVES * 64), 0, stream, in, g, st.levels, out, *proofs, level0);
-            else hipLaunchKernelGGL(reduce_collapse_kernel, cgrid, dim3(VKMR_COLLAPSE_WAVES * 64), 0, stream, in, g, st.levels, out);
+            const dim3 cblock(VKMR_COLLAPSE_WAVES * 64);
+            VKMR_CHECK(prove ? launch(reduce_collapse_proofs_kernel, cgrid, cblock, stream, in, g, st.levels, out, *proofs, level0)
+                             : launch(reduce_collapse_kernel, cgrid, cblock, stream, in, g, st.levels, out));
         }
-        VKMR_TRY(hipGetLastError());
         in = out;
         in_stride = st.n_out;
         n = st.n_out;
@@ -626,12 +576,12 @@ static vkmr_status reduce_launch(hipStream_t stream, const Node* digests, uint32
 vkmr_status vkmr_hip_reduce_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t count,
                                   uint32_t height, void* scratch_dev, vkmr_digest* root_dev)
 {
-    if (!digests_dev || !root_dev) return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_async: null pointer");
+    if (!digests_dev || !root_dev) return refuse(__func__, "null pointer");
     if (!height_ok(count, height))
-        return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_async: height does not reduce count to one node");
-    if (count > VKMR_TAIL_MAX && !scratch_dev) return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_async: null scratch");
+        return refuse(__func__, "height does not reduce count to one node");
+    if (count > VKMR_TAIL_MAX && !scratch_dev) return refuse(__func__, "null scratch");
     VKMR_TRY(hipSetDevice(dev));
-    return reduce_launch(S(s), nodes(digests_dev), 1, count, count, height, nodes(scratch_dev), nodes(root_dev));
+    return reduce_launch(__func__, S(s), nodes(digests_dev), 1, count, count, height, nodes(scratch_dev), nodes(root_dev));
 }
 
 // ---- proof ----------------------------------------------------------------------
@@ -639,10 +589,10 @@ vkmr_status vkmr_hip_reduce_async(int dev, vkmr_stream s, const vkmr_digest* dig
 vkmr_status vkmr_hip_proof_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t count, uint32_t height,
                                  uint64_t index, void* scratch_dev, vkmr_digest* siblings_dev, vkmr_digest* root_dev)
 {
-    if (!digests_dev || !siblings_dev) return fail(VKMR_ERR_INVALID, "vkmr_hip_proof_async: null pointer");
-    if (!height_ok(count, height)) return fail(VKMR_ERR_INVALID, "vkmr_hip_proof_async: height does not reduce count to one node");
-    if (index >= count) return fail(VKMR_ERR_INVALID, "vkmr_hip_proof_async: index out of range");
-    if (count > VKMR_TAIL_MAX && !scratch_dev) return fail(VKMR_ERR_INVALID, "vkmr_hip_proof_async: null scratch");
+    if (!digests_dev || !siblings_dev) return refuse(__func__, "null pointer");
+    if (!height_ok(count, height)) return refuse(__func__, "height does not reduce count to one node");
+    if (index >= count) return refuse(__func__, "index out of range");
+    if (count > VKMR_TAIL_MAX && !scratch_dev) return refuse(__func__, "null scratch");
     VKMR_TRY(hipSetDevice(dev));
     const Node* leaves = nodes(digests_dev);
     Node* sib = nodes(siblings_dev);
@@ -656,12 +606,11 @@ vkmr_status vkmr_hip_proof_async(int dev, vkmr_stream s, const vkmr_digest* dige
         if (l == 0) {
             VKMR_TRY(hipMemcpyAsync(sib, leaves + lo, sizeof(Node), hipMemcpyDeviceToDevice, S(s)));
         } else {
-            const vkmr_status st = reduce_launch(S(s), leaves + lo, 1, n, n, l, nodes(scratch_dev), sib + l);
-            if (st != VKMR_OK) return st;
+            VKMR_CHECK(reduce_launch(__func__, S(s), leaves + lo, 1, n, n, l, nodes(scratch_dev), sib + l));
         }
     }
     if (root_dev)
-        return reduce_launch(S(s), leaves, 1, count, count, height, nodes(scratch_dev), nodes(root_dev));
+        return reduce_launch(__func__, S(s), leaves, 1, count, count, height, nodes(scratch_dev), nodes(root_dev));
     return VKMR_OK;
 }
 
@@ -672,86 +621,72 @@ vkmr_status vkmr_hip_reduce_proofs_async(int dev, vkmr_stream s, const vkmr_dige
                                          vkmr_digest* root_dev, const uint64_t* indices, uint32_t k, vkmr_digest* siblings_dev)
 {
     if (k == 0) return vkmr_hip_reduce_async(dev, s, digests_dev, count, height, scratch_dev, root_dev);
-    if (!digests_dev || !root_dev || !indices || !siblings_dev) return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_proofs_async: null pointer");
-    if (k > VKMR_MAX_PROOFS) return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_proofs_async: more than 16 proofs in one reduction");
-    if (!height_ok(count, height)) return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_proofs_async: height does not reduce count to one node");
-    if (count > VKMR_TAIL_MAX && !scratch_dev) return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_proofs_async: null scratch");
+    if (!digests_dev || !root_dev || !indices || !siblings_dev) return refuse(__func__, "null pointer");
+    if (k > VKMR_MAX_PROOFS) return refuse(__func__, "more than 16 proofs in one reduction");
+    if (!height_ok(count, height)) return refuse(__func__, "height does not reduce count to one node");
+    if (count > VKMR_TAIL_MAX && !scratch_dev) return refuse(__func__, "null scratch");
     ProofArgs pa;
     pa.k = k;
     pa.height = height;
     pa.sib = nodes(siblings_dev);
     for (uint32_t q = 0; q < VKMR_MAX_PROOFS; ++q) pa.index[q] = 0;
     for (uint32_t q = 0; q < k; ++q) {
-        if (indices[q] >= count) return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_proofs_async: index out of range");
+        if (indices[q] >= count) return refuse(__func__, "index out of range");
         pa.index[q] = indices[q];
     }
     VKMR_TRY(hipSetDevice(dev));
     if (height == 0) {   // one node, no level: the root is the node (reduce_tail_kernel), no sibling exists
-        return reduce_launch(S(s), nodes(digests_dev), 1, count, count, height, nodes(scratch_dev), nodes(root_dev));
+        return reduce_launch(__func__, S(s), nodes(digests_dev), 1, count, count, height, nodes(scratch_dev), nodes(root_dev));
     }
-    return reduce_launch(S(s), nodes(digests_dev), 1, count, count, height, nodes(scratch_dev), nodes(root_dev), &pa);
+    return reduce_launch(__func__, S(s), nodes(digests_dev), 1, count, count, height, nodes(scratch_dev), nodes(root_dev), &pa);
 }
 
 vkmr_status vkmr_hip_reduce_slices_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint32_t nslices,
                                          uint64_t capacity, uint64_t count_last, uint32_t height, void* scratch_dev,
                                          vkmr_digest* roots_dev)
 {
-    if (!digests_dev || !roots_dev || nslices == 0) return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_slices_async: bad argument");
+    if (!digests_dev || !roots_dev || nslices == 0) return refuse(__func__, "bad argument");
     if (count_last == 0 || count_last > capacity)
-        return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_slices_async: bad slice geometry");
+        return refuse(__func__, "bad slice geometry");
     if (!height_ok(nslices == 1 ? count_last : capacity, height))
-        return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_slices_async: height does not reduce a slice to one node");
-    if (capacity > VKMR_TAIL_MAX && !scratch_dev) return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_slices_async: null scratch");
+        return refuse(__func__, "height does not reduce a slice to one node");
+    if (capacity > VKMR_TAIL_MAX && !scratch_dev) return refuse(__func__, "null scratch");
     VKMR_TRY(hipSetDevice(dev));
-    // grid.y carries the slice index: at most 32768 slices per launch sequence; longer runs go in
-    // chunks on the same stream (the scratch is reused, the stream serialises them)
-    const uint32_t chunk = 32768u;
+    const vkmr_plan::SliceChunks chunks = vkmr_plan::slice_chunks(nslices);   // at most 32768 slices per launch sequence
     const Node* digests = nodes(digests_dev);
     Node* roots = nodes(roots_dev);
-    for (uint32_t first = 0; first < nslices; first += chunk) {
-        const uint32_t n = (nslices - first < chunk) ? nslices - first : chunk;
-        const bool has_last = (first + n == nslices);
-        const uint64_t n_full = (nslices == 1) ? count_last : capacity;
-        const vkmr_status st = reduce_launch(S(s), digests + (uint64_t)first * capacity, n, n_full, has_last ? count_last : capacity, height,
-                                             nodes(scratch_dev), roots + first);
-        if (st != VKMR_OK) return st;
+    const uint64_t n_full = (nslices == 1) ? count_last : capacity;
+    for (uint32_t c = 0; c < chunks.count(); ++c) {
+        const uint32_t first = chunks.first(c);
+        const bool has_last = (c + 1 == chunks.count());
+        VKMR_CHECK(reduce_launch(__func__, S(s), digests + (uint64_t)first * capacity, chunks.size(c), n_full, has_last ? count_last : capacity, height,
+                                 nodes(scratch_dev), roots + first));
     }
     return VKMR_OK;
 }
 
 size_t vkmr_hip_reduce_slices_scratch_bytes(uint64_t capacity, uint32_t nslices)
 {
-    if (nslices == 0) nslices = 1;
-    // runs longer than 32768 slices are reduced in chunks (see vkmr_hip_reduce_slices_async): the
-    // scratch must hold the largest chunk's passes -- the full chunks and the shorter last one
-    const uint32_t full = nslices > 32768u ? 32768u : nslices;
-    const uint32_t rest = nslices > 32768u ? nslices % 32768u : 0u;
-    size_t cells = (size_t)vkmr_plan::cells_upper_bound(capacity, full) * full;
-    if (rest) {
-        const size_t c2 = (size_t)vkmr_plan::cells_upper_bound(capacity, rest) * rest;
-        cells = c2 > cells ? c2 : cells;
-    }
-    return cells * sizeof(vkmr_digest);
+    return (size_t)vkmr_plan::slices_scratch_cells(capacity, nslices) * sizeof(vkmr_digest);
 }
 
 size_t vkmr_hip_reduce_levels_scratch_bytes(uint64_t count)
 {
-    return (size_t)(ceil_shift(count, 1) + ceil_shift(count, 2) + 2) * sizeof(vkmr_digest);
+    return (size_t)vkmr_plan::levels_scratch_cells(count) * sizeof(vkmr_digest);
 }
 
 // Level lv + 1 from level lv, lv = 0..height-1, one reduce_level_kernel launch each; dst(lv) is where level lv + 1 goes.
 // Shared by the levels cross-check (ping-pong scratch, root last) and the stored tree (every level kept).
 extern "C++" {   // a template inside the C block
 template <class Dst>
-static vkmr_status levels_launch(hipStream_t stream, const Node* in, uint64_t count, uint32_t height, Dst dst, const char* too_large)
+static vkmr_status levels_launch(const char* who, hipStream_t stream, const Node* in, uint64_t count, uint32_t height, Dst dst)
 {
     uint64_t n = count;
     for (uint32_t lv = 0; lv < height; ++lv) {
         const uint64_t pairs = ceil_shift(n, 1);
         Node* out = dst(lv);
-        if (grid_too_large(groups_of(pairs))) return fail(VKMR_ERR_INVALID, too_large);
-        hipLaunchKernelGGL(reduce_level_kernel, grid_of(pairs), dim3(256), 0, stream, in, n, out);
-        VKMR_TRY(hipGetLastError());
+        if (grid_too_large(groups_of(pairs))) return refuse(who, "slice too large");
+        VKMR_CHECK(launch(reduce_level_kernel, grid_of(pairs), dim3(256), stream, in, n, out));
         in = out;
         n = pairs;
     }
@@ -763,54 +698,46 @@ vkmr_status vkmr_hip_reduce_levels_async(int dev, vkmr_stream s, const vkmr_dige
                                          uint32_t height, void* scratch_dev, vkmr_digest* root_dev)
 {
     if (!digests_dev || !root_dev || !scratch_dev)
-        return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_levels_async: null pointer");
+        return refuse(__func__, "null pointer");
     if (!height_ok(count, height))
-        return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_levels_async: height does not reduce count to one node");
+        return refuse(__func__, "height does not reduce count to one node");
     VKMR_TRY(hipSetDevice(dev));
     Node* bufA = nodes(scratch_dev);
-    Node* bufB = bufA + ceil_shift(count, 1);
+    Node* bufB = bufA + vkmr_plan::levels_second_buffer(count);
     Node* root = nodes(root_dev);
-    const vkmr_status st = levels_launch(S(s), nodes(digests_dev), count, height,
-                                         [=](uint32_t lv) { return (lv + 1 == height) ? root : ((lv & 1) ? bufB : bufA); },
-                                         "vkmr_hip_reduce_levels_async: slice too large");
-    if (st != VKMR_OK) return st;
+    VKMR_CHECK(levels_launch(__func__, S(s), nodes(digests_dev), count, height,
+                             [=](uint32_t lv) { return (lv + 1 == height) ? root : ((lv & 1) ? bufB : bufA); }));
     if (height == 0) VKMR_TRY(hipMemcpyAsync(root_dev, digests_dev, sizeof(vkmr_digest), hipMemcpyDeviceToDevice, S(s)));
     return VKMR_OK;
 }
 
 // ---- stored tree: build, gather proofs, verify (tree_kernels.hpp) -------------------------------------------------------
 
-// Start cell of every level 1..height inside the tree buffer (off[0] = 0, unused); returns the buffer's cell count.
-static uint64_t tree_levels(uint64_t count, uint32_t height, TreeLevels* lv)
+// Start cell of every level 1..height inside the tree buffer, as the kernels take it (tree_plan.hpp).
+static TreeLevels tree_levels(uint64_t count, uint32_t height)
 {
-    uint64_t cells = 0;
-    if (lv) lv->off[0] = 0;
-    for (uint32_t l = 1; l <= height && l < VKMR_TREE_MAX_LEVELS; ++l) {
-        if (lv) lv->off[l] = cells;
-        cells += ceil_shift(count, l);
-    }
-    return cells;
+    TreeLevels lv;
+    vkmr_tree::levels(count, height, lv.off);
+    return lv;
 }
 
 size_t vkmr_hip_tree_bytes(uint64_t count, uint32_t height)
 {
     if (count == 0 || height > 63) return 0;
-    return (size_t)tree_levels(count, height, nullptr) * sizeof(vkmr_digest);
+    return (size_t)vkmr_tree::cells(count, height) * sizeof(vkmr_digest);
 }
 
 vkmr_status vkmr_hip_reduce_tree_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t count, uint32_t height,
                                        vkmr_digest* tree_dev)
 {
-    if (!digests_dev || (!tree_dev && height > 0)) return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_tree_async: null pointer");
+    if (!digests_dev || (!tree_dev && height > 0)) return refuse(__func__, "null pointer");
     if (!height_ok(count, height))
-        return fail(VKMR_ERR_INVALID, "vkmr_hip_reduce_tree_async: height does not reduce count to one node");
+        return refuse(__func__, "height does not reduce count to one node");
     if (height == 0) return VKMR_OK;   // one leaf, no level: the root is the leaf
-    TreeLevels lv;
-    tree_levels(count, height, &lv);
+    const TreeLevels lv = tree_levels(count, height);
     VKMR_TRY(hipSetDevice(dev));
     Node* tree = nodes(tree_dev);
-    return levels_launch(S(s), nodes(digests_dev), count, height, [&](uint32_t l) { return tree + lv.off[l + 1]; },
-                         "vkmr_hip_reduce_tree_async: slice too large");
+    return levels_launch(__func__, S(s), nodes(digests_dev), count, height, [&](uint32_t l) { return tree + lv.off[l + 1]; });
 }
 
 vkmr_status vkmr_hip_tree_proofs_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* tree_dev, uint64_t count,
@@ -818,19 +745,16 @@ vkmr_status vkmr_hip_tree_proofs_async(int dev, vkmr_stream s, const vkmr_digest
 {
     if (k == 0) return VKMR_OK;
     if (!digests_dev || (!tree_dev && height > 0) || !indices_dev || !siblings_dev)
-        return fail(VKMR_ERR_INVALID, "vkmr_hip_tree_proofs_async: null pointer");
+        return refuse(__func__, "null pointer");
     if (!height_ok(count, height))
-        return fail(VKMR_ERR_INVALID, "vkmr_hip_tree_proofs_async: height does not reduce count to one node");
+        return refuse(__func__, "height does not reduce count to one node");
     if (height == 0) return VKMR_OK;   // no level, no sibling
-    TreeLevels lv;
-    tree_levels(count, height, &lv);
+    const TreeLevels lv = tree_levels(count, height);
     const uint64_t total = (uint64_t)k * height;
-    if (grid_too_large(groups_of(total))) return fail(VKMR_ERR_INVALID, "vkmr_hip_tree_proofs_async: too many proofs in one call");
+    if (grid_too_large(groups_of(total))) return refuse(__func__, "too many proofs in one call");
     VKMR_TRY(hipSetDevice(dev));
-    hipLaunchKernelGGL(tree_proofs_kernel, grid_of(total), dim3(256), 0, S(s), nodes(digests_dev),
-                       nodes(tree_dev), lv, count, height, indices_dev, total, nodes(siblings_dev));
-    VKMR_TRY(hipGetLastError());
-    return VKMR_OK;
+    return launch(tree_proofs_kernel, grid_of(total), dim3(256), S(s), nodes(digests_dev), nodes(tree_dev), lv, count, height, indices_dev, total,
+                  nodes(siblings_dev));
 }
 
 vkmr_status vkmr_hip_verify_proofs_async(int dev, vkmr_stream s, const vkmr_digest* leaves_dev, const uint64_t* indices_dev,
@@ -839,14 +763,12 @@ vkmr_status vkmr_hip_verify_proofs_async(int dev, vkmr_stream s, const vkmr_dige
 {
     if (k == 0) return VKMR_OK;
     if (!leaves_dev || !indices_dev || !siblings_dev || !roots_dev || !ok_dev)
-        return fail(VKMR_ERR_INVALID, "vkmr_hip_verify_proofs_async: null pointer");
-    if (height == 0 || height > 63) return fail(VKMR_ERR_INVALID, "vkmr_hip_verify_proofs_async: height must be 1..63");
-    if (nroots != 1 && nroots != k) return fail(VKMR_ERR_INVALID, "vkmr_hip_verify_proofs_async: nroots must be 1 or k");
+        return refuse(__func__, "null pointer");
+    if (height == 0 || height > 63) return refuse(__func__, "height must be 1..63");
+    if (nroots != 1 && nroots != k) return refuse(__func__, "nroots must be 1 or k");
     VKMR_TRY(hipSetDevice(dev));
-    hipLaunchKernelGGL(verify_proofs_kernel, grid_of(k), dim3(256), 0, S(s), nodes(leaves_dev), indices_dev, nodes(siblings_dev), k, height,
-                       nodes(roots_dev), (uint32_t)(nroots == 1 ? 0u : 1u), ok_dev);
-    VKMR_TRY(hipGetLastError());
-    return VKMR_OK;
+    return launch(verify_proofs_kernel, grid_of(k), dim3(256), S(s), nodes(leaves_dev), indices_dev, nodes(siblings_dev), k, height, nodes(roots_dev),
+                  nroots == 1 ? 0 : 1, ok_dev);
 }
 
 vkmr_status vkmr_hip_tree_update_async(int dev, vkmr_stream s, vkmr_digest* digests_dev, vkmr_digest* tree_dev, uint64_t count,
@@ -855,25 +777,20 @@ vkmr_status vkmr_hip_tree_update_async(int dev, vkmr_stream s, vkmr_digest* dige
 {
     if (k == 0) return VKMR_OK;
     if (!digests_dev || (!tree_dev && height > 0) || !indices_dev || !leaves_dev || !status_dev)
-        return fail(VKMR_ERR_INVALID, "vkmr_hip_tree_update_async: null pointer");
+        return refuse(__func__, "null pointer");
     if (!height_ok(count, height))
-        return fail(VKMR_ERR_INVALID, "vkmr_hip_tree_update_async: height does not reduce count to one node");
-    TreeLevels lv;
-    tree_levels(count, height, &lv);
+        return refuse(__func__, "height does not reduce count to one node");
+    const TreeLevels lv = tree_levels(count, height);
     const dim3 grid = grid_of(k);
     Node* digests = nodes(digests_dev);
     Node* tree = nodes(tree_dev);
     VKMR_TRY(hipSetDevice(dev));
     VKMR_TRY(hipMemsetAsync(status_dev, 0, sizeof(uint32_t), S(s)));
-    hipLaunchKernelGGL(tree_update_check_kernel, grid, dim3(256), 0, S(s), indices_dev, k, count, status_dev);
-    VKMR_TRY(hipGetLastError());
-    hipLaunchKernelGGL(tree_update_leaves_kernel, grid, dim3(256), 0, S(s), digests, indices_dev, nodes(leaves_dev), k, (const uint32_t*)status_dev);
-    VKMR_TRY(hipGetLastError());
+    VKMR_CHECK(launch(tree_update_check_kernel, grid, dim3(256), S(s), indices_dev, k, count, status_dev));
+    VKMR_CHECK(launch(tree_update_leaves_kernel, grid, dim3(256), S(s), digests, indices_dev, nodes(leaves_dev), k, status_dev));
     for (uint32_t l = 1; l <= height; ++l) {   // level l from level l - 1, which the previous launch finished
         const Node* in = (l == 1) ? digests : tree + lv.off[l - 1];
-        hipLaunchKernelGGL(tree_update_level_kernel, grid, dim3(256), 0, S(s), in, ceil_shift(count, l - 1), tree + lv.off[l],
-                           indices_dev, k, l, (const uint32_t*)status_dev);
-        VKMR_TRY(hipGetLastError());
+        VKMR_CHECK(launch(tree_update_level_kernel, grid, dim3(256), S(s), in, ceil_shift(count, l - 1), tree + lv.off[l], indices_dev, k, l, status_dev));
     }
     return VKMR_OK;
 }
@@ -883,35 +800,12 @@ vkmr_status vkmr_hip_tree_update_async(int dev, vkmr_stream s, vkmr_digest* dige
 size_t vkmr_hip_multiproof_max_nodes(uint64_t count, uint32_t height, uint32_t k)
 {
     if (count == 0 || height > 63) return 0;
-    uint64_t cells = 0;
-    for (uint32_t l = 0; l < height; ++l) {   // at most one node per pair of level l
-        const uint64_t pairs = ceil_shift(count, l + 1);
-        cells += pairs < k ? pairs : k;
-    }
-    return (size_t)cells;
+    return (size_t)vkmr_tree::multiproof_max_nodes(count, height, k);
 }
 
-// Where the parts of scratch_dev lie.  The cells come first (16-byte loads); the gather uses mask, word_start and block only.
-struct MultiproofLayout {
-    uint64_t words, blocks;   // ballot words per level, blocks of VKMR_MP_BLOCK_WORDS words per level
-    size_t cell, mask, word_start, block, hdr, end, bytes;
-};
-
-static MultiproofLayout multiproof_layout(uint32_t k, uint32_t height)
-{
-    MultiproofLayout L;
-    L.words = ((uint64_t)k + 63) / 64;
-    L.blocks = (L.words + VKMR_MP_BLOCK_WORDS - 1) / VKMR_MP_BLOCK_WORDS;
-    size_t at = 0;
-    L.cell = at;       at += (size_t)k * sizeof(vkmr_digest);
-    L.mask = at;       at += (size_t)(L.words * height) * sizeof(uint64_t);
-    L.word_start = at; at += (size_t)(L.words * height) * sizeof(uint64_t);
-    L.block = at;      at += (size_t)(L.blocks * height) * sizeof(uint64_t);
-    L.hdr = at;        at += VKMR_MP_HEADER_WORDS * sizeof(uint64_t);
-    L.end = at;        at += (size_t)k * sizeof(uint32_t);
-    L.bytes = at;
-    return L;
-}
+using vkmr_tree::MultiproofLayout;
+using vkmr_tree::multiproof_layout;
+static_assert(sizeof(vkmr_digest) == vkmr_tree::CELL_BYTES && sizeof(Node) == vkmr_tree::CELL_BYTES, "tree_plan.hpp counts cells of 32 bytes");
 
 size_t vkmr_hip_multiproof_scratch_bytes(uint32_t k, uint32_t height)
 {
@@ -919,38 +813,46 @@ size_t vkmr_hip_multiproof_scratch_bytes(uint32_t k, uint32_t height)
     return multiproof_layout(k, height).bytes;
 }
 
+// The parts of a multiproof call's scratch_dev as the kernels take them.  (Integer arithmetic: a tree of one leaf has no
+// scratch, and none of these is then used.)
+struct MultiproofScratch {
+    Node* cell;
+    uint64_t *mask, *word_start, *block, *hdr;
+    uint32_t* end;
+    MultiproofScratch(void* scratch_dev, const MultiproofLayout& L)
+    {
+        const uintptr_t at = reinterpret_cast<uintptr_t>(scratch_dev);
+        cell = reinterpret_cast<Node*>(at + L.cell);
+        mask = reinterpret_cast<uint64_t*>(at + L.mask);
+        word_start = reinterpret_cast<uint64_t*>(at + L.word_start);
+        block = reinterpret_cast<uint64_t*>(at + L.block);
+        hdr = reinterpret_cast<uint64_t*>(at + L.hdr);
+        end = reinterpret_cast<uint32_t*>(at + L.end);
+    }
+};
+
 // The ranking launches every multiproof call shares, behind its own check and masks kernel: block sums, block starts, word
 // starts.  `levels` is one tree's height or a forest's stride; limit / exact as multiproof_block_starts_kernel takes them.
-static vkmr_status multiproof_rank_launch(hipStream_t stream, uint32_t levels, const MultiproofLayout& L, char* scratch, uint64_t* hdr, uint64_t limit,
-                                          uint32_t exact)
+// `hdr` is the call's header: the caller's info_dev in a gather, the scratch's own in a verification.
+static vkmr_status multiproof_rank_launch(hipStream_t stream, uint32_t levels, const MultiproofLayout& L, const MultiproofScratch& sc, uint64_t* hdr,
+                                          uint64_t limit, uint32_t exact)
 {
-    const uint64_t* mask = reinterpret_cast<const uint64_t*>(scratch + L.mask);
-    uint64_t* word_start = reinterpret_cast<uint64_t*>(scratch + L.word_start);
-    uint64_t* block = reinterpret_cast<uint64_t*>(scratch + L.block);
-    const dim3 wgrid((uint32_t)L.blocks, levels);
-    hipLaunchKernelGGL(multiproof_block_sums_kernel, wgrid, dim3(VKMR_MP_BLOCK_WORDS), 0, stream, mask, L.words, L.blocks, block);
-    VKMR_TRY(hipGetLastError());
-    hipLaunchKernelGGL(multiproof_block_starts_kernel, dim3(1), dim3(256), 0, stream, block, L.blocks, levels, limit, exact, hdr);
-    VKMR_TRY(hipGetLastError());
-    hipLaunchKernelGGL(multiproof_word_starts_kernel, wgrid, dim3(VKMR_MP_BLOCK_WORDS), 0, stream, mask, L.words, L.blocks, (const uint64_t*)block,
-                       (const uint64_t*)hdr, word_start);
-    VKMR_TRY(hipGetLastError());
-    return VKMR_OK;
+    const dim3 wgrid((uint32_t)L.blocks, levels), wblock(VKMR_MP_BLOCK_WORDS);
+    VKMR_CHECK(launch(multiproof_block_sums_kernel, wgrid, wblock, stream, sc.mask, L.words, L.blocks, sc.block));
+    VKMR_CHECK(launch(multiproof_block_starts_kernel, dim3(1), dim3(256), stream, sc.block, L.blocks, levels, limit, exact, hdr));
+    return launch(multiproof_word_starts_kernel, wgrid, wblock, stream, sc.mask, L.words, L.blocks, sc.block, hdr, sc.word_start);
 }
 
 // The single tree's check and flags in front of the ranking: the index check into hdr[0] with `count` as its bound, then the
 // masks.  A tree of one leaf (height 0) has no level to rank: the check alone, and M = 0.
 static vkmr_status tree_multiproof_rank_launch(hipStream_t stream, const uint64_t* indices_dev, uint32_t k, uint64_t count, uint32_t height,
-                                               const MultiproofLayout& L, char* scratch, uint64_t* hdr, uint64_t limit, uint32_t exact)
+                                               const MultiproofLayout& L, const MultiproofScratch& sc, uint64_t* hdr, uint64_t limit, uint32_t exact)
 {
     VKMR_TRY(hipMemsetAsync(hdr, 0, (height == 0 ? 2 : 1) * sizeof(uint64_t), stream));
-    hipLaunchKernelGGL(tree_update_check_kernel, grid_of(k), dim3(256), 0, stream, indices_dev, k, count, reinterpret_cast<uint32_t*>(hdr));
-    VKMR_TRY(hipGetLastError());
+    VKMR_CHECK(launch(tree_update_check_kernel, grid_of(k), dim3(256), stream, indices_dev, k, count, reinterpret_cast<uint32_t*>(hdr)));
     if (height == 0) return VKMR_OK;
-    hipLaunchKernelGGL(multiproof_masks_kernel, grid_of(k), dim3(256), 0, stream, indices_dev, k, height, L.words, (const uint64_t*)hdr,
-                       reinterpret_cast<uint64_t*>(scratch + L.mask));
-    VKMR_TRY(hipGetLastError());
-    return multiproof_rank_launch(stream, height, L, scratch, hdr, limit, exact);
+    VKMR_CHECK(launch(multiproof_masks_kernel, grid_of(k), dim3(256), stream, indices_dev, k, height, L.words, hdr, sc.mask));
+    return multiproof_rank_launch(stream, height, L, sc, hdr, limit, exact);
 }
 
 vkmr_status vkmr_hip_tree_multiproof_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* tree_dev, uint64_t count,
@@ -959,21 +861,16 @@ vkmr_status vkmr_hip_tree_multiproof_async(int dev, vkmr_stream s, const vkmr_di
 {
     if (k == 0) return VKMR_OK;
     if (!digests_dev || !indices_dev || !info_dev || (height > 0 && (!tree_dev || !scratch_dev)) || (!nodes_dev && nodes_capacity > 0))
-        return fail(VKMR_ERR_INVALID, "vkmr_hip_tree_multiproof_async: null pointer");
-    if (!height_ok(count, height))
-        return fail(VKMR_ERR_INVALID, "vkmr_hip_tree_multiproof_async: height does not reduce count to one node");
-    TreeLevels lv;
-    tree_levels(count, height, &lv);
+        return refuse(__func__, "null pointer");
+    if (!height_ok(count, height)) return refuse(__func__, "height does not reduce count to one node");
+    const TreeLevels lv = tree_levels(count, height);
     const MultiproofLayout L = multiproof_layout(k, height);
-    char* scratch = static_cast<char*>(scratch_dev);
+    const MultiproofScratch sc(scratch_dev, L);
     VKMR_TRY(hipSetDevice(dev));
-    const vkmr_status st = tree_multiproof_rank_launch(S(s), indices_dev, k, count, height, L, scratch, info_dev, nodes_capacity, 0u);
-    if (st != VKMR_OK || height == 0) return st;
-    hipLaunchKernelGGL(tree_multiproof_gather_kernel, grid_of(k, height), dim3(256), 0, S(s), nodes(digests_dev), nodes(tree_dev), lv, count,
-                       indices_dev, k, L.words, reinterpret_cast<const uint64_t*>(scratch + L.mask),
-                       reinterpret_cast<const uint64_t*>(scratch + L.word_start), (const uint64_t*)info_dev, nodes(nodes_dev));
-    VKMR_TRY(hipGetLastError());
-    return VKMR_OK;
+    VKMR_CHECK(tree_multiproof_rank_launch(S(s), indices_dev, k, count, height, L, sc, info_dev, nodes_capacity, 0u));
+    if (height == 0) return VKMR_OK;
+    return launch(tree_multiproof_gather_kernel, grid_of(k, height), dim3(256), S(s), nodes(digests_dev), nodes(tree_dev), lv, count, indices_dev, k, L.words,
+                  sc.mask, sc.word_start, info_dev, nodes(nodes_dev));
 }
 
 vkmr_status vkmr_hip_verify_multiproof_async(int dev, vkmr_stream s, const vkmr_digest* leaves_dev, const uint64_t* indices_dev, uint32_t k,
@@ -981,28 +878,18 @@ vkmr_status vkmr_hip_verify_multiproof_async(int dev, vkmr_stream s, const vkmr_
                                              void* scratch_dev, uint32_t* ok_dev)
 {
     if (k == 0) return VKMR_OK;
-    if (!leaves_dev || !indices_dev || !root_dev || !scratch_dev || !ok_dev || (!nodes_dev && m > 0))
-        return fail(VKMR_ERR_INVALID, "vkmr_hip_verify_multiproof_async: null pointer");
-    if (height == 0 || height > 63) return fail(VKMR_ERR_INVALID, "vkmr_hip_verify_multiproof_async: height must be 1..63");
+    if (!leaves_dev || !indices_dev || !root_dev || !scratch_dev || !ok_dev || (!nodes_dev && m > 0)) return refuse(__func__, "null pointer");
+    if (height == 0 || height > 63) return refuse(__func__, "height must be 1..63");
     const MultiproofLayout L = multiproof_layout(k, height);
-    char* scratch = static_cast<char*>(scratch_dev);
-    uint64_t* hdr = reinterpret_cast<uint64_t*>(scratch + L.hdr);
-    Node* cell = nodes(scratch + L.cell);
+    const MultiproofScratch sc(scratch_dev, L);
     VKMR_TRY(hipSetDevice(dev));
     // the index check with 2^height as the bound: bit 0 an index outside the tree, bit 1 not strictly increasing; exact: M == m
-    const vkmr_status st = tree_multiproof_rank_launch(S(s), indices_dev, k, 1ull << height, height, L, scratch, hdr, m, 1u);
-    if (st != VKMR_OK) return st;
+    VKMR_CHECK(tree_multiproof_rank_launch(S(s), indices_dev, k, 1ull << height, height, L, sc, sc.hdr, m, 1u));
     const dim3 grid = grid_of(k);
-    for (uint32_t l = 0; l < height; ++l) {   // level l + 1 from level l, which the previous launch finished
-        hipLaunchKernelGGL(verify_multiproof_level_kernel, grid, dim3(256), 0, S(s), l == 0 ? nodes(leaves_dev) : cell,
-                           cell, reinterpret_cast<uint32_t*>(scratch + L.end), indices_dev, k, l, L.words,
-                           reinterpret_cast<const uint64_t*>(scratch + L.mask), reinterpret_cast<const uint64_t*>(scratch + L.word_start),
-                           nodes(nodes_dev), (const uint64_t*)hdr);
-        VKMR_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(verify_multiproof_finish_kernel, dim3(1), dim3(64), 0, S(s), (const Node*)cell, nodes(root_dev), (const uint64_t*)hdr, ok_dev);
-    VKMR_TRY(hipGetLastError());
-    return VKMR_OK;
+    for (uint32_t l = 0; l < height; ++l)   // level l + 1 from level l, which the previous launch finished
+        VKMR_CHECK(launch(verify_multiproof_level_kernel, grid, dim3(256), S(s), l == 0 ? nodes(leaves_dev) : sc.cell, sc.cell, sc.end, indices_dev, k, l,
+                          L.words, sc.mask, sc.word_start, nodes(nodes_dev), sc.hdr));
+    return launch(verify_multiproof_finish_kernel, dim3(1), dim3(64), S(s), sc.cell, nodes(root_dev), sc.hdr, ok_dev);
 }
 
 // ---- forest: the roots of many trees of unequal size (forest_kernels.hpp, forest_plan.hpp) ---------------------------------
@@ -1034,18 +921,13 @@ static vkmr_status forest_launch(const char* who, int dev, vkmr_stream s, const 
     VKMR_TRY(hipSetDevice(dev));
     VKMR_TRY(hipMemsetAsync(status_dev, 0, sizeof(uint32_t), S(s)));
     if (mutated_dev) VKMR_TRY(hipMemsetAsync(mutated_dev, 0, sizeof(uint64_t) * ntrees, S(s)));
-    hipLaunchKernelGGL(forest_check_kernel, grid_of(ntrees), dim3(256), 0, S(s), offsets_dev, ntrees, total, max_count, status_dev);
-    VKMR_TRY(hipGetLastError());
+    VKMR_CHECK(launch(forest_check_kernel, grid_of(ntrees), dim3(256), S(s), offsets_dev, ntrees, total, max_count, status_dev));
     for (uint32_t l = 1; l <= levels; ++l) {   // level l from level l - 1, which the previous launch finished
         const Node* in = (l == 1) ? digests : level(l - 1);
         const uint64_t cells = vkmr_forest::level_cells(total, ntrees, l);
-        if (mutated_dev)
-            hipLaunchKernelGGL(forest_level_mutated_kernel, grid_of(cells), dim3(256), 0, S(s), in, offsets_dev, ntrees, l, cells, level(l),
-                               roots, reinterpret_cast<unsigned long long*>(mutated_dev), (const uint32_t*)status_dev);
-        else
-            hipLaunchKernelGGL(forest_level_kernel, grid_of(cells), dim3(256), 0, S(s), in, offsets_dev, ntrees, l, cells, level(l),
-                               roots, (const uint32_t*)status_dev);
-        VKMR_TRY(hipGetLastError());
+        VKMR_CHECK(mutated_dev ? launch(forest_level_mutated_kernel, grid_of(cells), dim3(256), S(s), in, offsets_dev, ntrees, l, cells, level(l), roots,
+                                        reinterpret_cast<unsigned long long*>(mutated_dev), status_dev)
+                               : launch(forest_level_kernel, grid_of(cells), dim3(256), S(s), in, offsets_dev, ntrees, l, cells, level(l), roots, status_dev));
     }
     return VKMR_OK;
 }
@@ -1056,7 +938,7 @@ vkmr_status vkmr_hip_reduce_forest_async(int dev, vkmr_stream s, const vkmr_dige
 {
     if (ntrees == 0) return VKMR_OK;
     Node* scratch = nodes(scratch_dev);
-    return forest_launch("vkmr_hip_reduce_forest_async", dev, s, digests_dev, total, offsets_dev, ntrees, max_count, scratch_dev, roots_dev, nullptr,
+    return forest_launch(__func__, dev, s, digests_dev, total, offsets_dev, ntrees, max_count, scratch_dev, roots_dev, nullptr,
                          status_dev, [&](uint32_t l) { return scratch + vkmr_forest::level_base(total, ntrees, l); });
 }
 
@@ -1065,9 +947,9 @@ vkmr_status vkmr_hip_reduce_forest_mutated_async(int dev, vkmr_stream s, const v
                                                  uint64_t* mutated_dev, uint32_t* status_dev)
 {
     if (ntrees == 0) return VKMR_OK;
-    if (!mutated_dev) return refuse("vkmr_hip_reduce_forest_mutated_async", "null pointer");
+    if (!mutated_dev) return refuse(__func__, "null pointer");
     Node* scratch = nodes(scratch_dev);
-    return forest_launch("vkmr_hip_reduce_forest_mutated_async", dev, s, digests_dev, total, offsets_dev, ntrees, max_count, scratch_dev, roots_dev,
+    return forest_launch(__func__, dev, s, digests_dev, total, offsets_dev, ntrees, max_count, scratch_dev, roots_dev,
                          mutated_dev, status_dev, [&](uint32_t l) { return scratch + vkmr_forest::level_base(total, ntrees, l); });
 }
 
@@ -1085,7 +967,7 @@ vkmr_status vkmr_hip_reduce_forest_tree_async(int dev, vkmr_stream s, const vkmr
 {
     if (ntrees == 0) return VKMR_OK;
     Node* forest = nodes(forest_dev);
-    return forest_launch("vkmr_hip_reduce_forest_tree_async", dev, s, digests_dev, total, offsets_dev, ntrees, max_count, forest_dev, roots_dev,
+    return forest_launch(__func__, dev, s, digests_dev, total, offsets_dev, ntrees, max_count, forest_dev, roots_dev,
                          nullptr, status_dev, [&](uint32_t l) { return forest + vkmr_forest::stored_level_base(total, ntrees, l); });
 }
 
@@ -1094,9 +976,9 @@ vkmr_status vkmr_hip_reduce_forest_tree_mutated_async(int dev, vkmr_stream s, co
                                                       vkmr_digest* roots_dev, uint64_t* mutated_dev, uint32_t* status_dev)
 {
     if (ntrees == 0) return VKMR_OK;
-    if (!mutated_dev) return refuse("vkmr_hip_reduce_forest_tree_mutated_async", "null pointer");
+    if (!mutated_dev) return refuse(__func__, "null pointer");
     Node* forest = nodes(forest_dev);
-    return forest_launch("vkmr_hip_reduce_forest_tree_mutated_async", dev, s, digests_dev, total, offsets_dev, ntrees, max_count, forest_dev,
+    return forest_launch(__func__, dev, s, digests_dev, total, offsets_dev, ntrees, max_count, forest_dev,
                          roots_dev, mutated_dev, status_dev, [&](uint32_t l) { return forest + vkmr_forest::stored_level_base(total, ntrees, l); });
 }
 
@@ -1127,12 +1009,10 @@ static ForestLevels forest_levels(uint64_t total, uint32_t ntrees, uint32_t H)
 vkmr_status vkmr_hip_forest_tree_mutated_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* forest_dev, uint64_t total,
                                                const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count, uint64_t* mutated_dev)
 {
-    const char* who = "vkmr_hip_forest_tree_mutated_async";
     if (ntrees == 0) return VKMR_OK;
-    if ((!digests_dev && total > 0) || !forest_dev || !offsets_dev || !mutated_dev) return refuse(who, "null pointer");
-    const vkmr_status args = forest_args_check(who, total, ntrees, max_count, 0, nullptr, nullptr);
-    if (args != VKMR_OK) return args;
-    if (grid_too_large(groups_of(vkmr_forest::level_cells(total, ntrees, 1)))) return refuse(who, "forest too large");
+    if ((!digests_dev && total > 0) || !forest_dev || !offsets_dev || !mutated_dev) return refuse(__func__, "null pointer");
+    VKMR_CHECK(forest_args_check(__func__, total, ntrees, max_count, 0, nullptr, nullptr));
+    if (grid_too_large(groups_of(vkmr_forest::level_cells(total, ntrees, 1)))) return refuse(__func__, "forest too large");
     const uint32_t H = vkmr_forest::launches(total, max_count);   // <= 58
     const Node* digests = nodes(digests_dev);
     const Node* forest = nodes(forest_dev);
@@ -1141,9 +1021,8 @@ vkmr_status vkmr_hip_forest_tree_mutated_async(int dev, vkmr_stream s, const vkm
     for (uint32_t l = 1; l <= H; ++l) {
         const Node* in = (l == 1) ? digests : forest + vkmr_forest::stored_level_base(total, ntrees, l - 1);
         const uint64_t cells = vkmr_forest::level_cells(total, ntrees, l);
-        hipLaunchKernelGGL(forest_scan_mutated_kernel, grid_of(cells), dim3(256), 0, S(s), in, offsets_dev, ntrees, l, cells,
-                           reinterpret_cast<unsigned long long*>(mutated_dev));
-        VKMR_TRY(hipGetLastError());
+        VKMR_CHECK(launch(forest_scan_mutated_kernel, grid_of(cells), dim3(256), S(s), in, offsets_dev, ntrees, l, cells,
+                          reinterpret_cast<unsigned long long*>(mutated_dev)));
     }
     return VKMR_OK;
 }
@@ -1154,18 +1033,15 @@ vkmr_status vkmr_hip_forest_proofs_async(int dev, vkmr_stream s, const vkmr_dige
 {
     if (k == 0) return VKMR_OK;
     if ((!digests_dev && total > 0) || !forest_dev || !offsets_dev || !trees_dev || !indices_dev || !siblings_dev || !heights_dev)
-        return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_proofs_async: null pointer");
-    const vkmr_status args = forest_args_check("vkmr_hip_forest_proofs_async", total, ntrees, max_count, k, nullptr, nullptr);
-    if (args != VKMR_OK) return args;
+        return refuse(__func__, "null pointer");
+    VKMR_CHECK(forest_args_check(__func__, total, ntrees, max_count, k, nullptr, nullptr));
     const uint32_t H = vkmr_forest::launches(total, max_count);   // <= 58
     const ForestLevels lv = forest_levels(total, ntrees, H);
     const uint64_t cells = (uint64_t)k * H;
-    if (grid_too_large(groups_of(cells))) return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_proofs_async: too many proofs in one call");
+    if (grid_too_large(groups_of(cells))) return refuse(__func__, "too many proofs in one call");
     VKMR_TRY(hipSetDevice(dev));
-    hipLaunchKernelGGL(forest_proofs_kernel, grid_of(cells), dim3(256), 0, S(s), nodes(digests_dev), nodes(forest_dev), lv, offsets_dev, ntrees, H,
-                       trees_dev, indices_dev, cells, nodes(siblings_dev), heights_dev);
-    VKMR_TRY(hipGetLastError());
-    return VKMR_OK;
+    return launch(forest_proofs_kernel, grid_of(cells), dim3(256), S(s), nodes(digests_dev), nodes(forest_dev), lv, offsets_dev, ntrees, H, trees_dev,
+                  indices_dev, cells, nodes(siblings_dev), heights_dev);
 }
 
 vkmr_status vkmr_hip_verify_forest_proofs_async(int dev, vkmr_stream s, const vkmr_digest* leaves_dev, const uint32_t* trees_dev,
@@ -1174,14 +1050,11 @@ vkmr_status vkmr_hip_verify_forest_proofs_async(int dev, vkmr_stream s, const vk
 {
     if (k == 0) return VKMR_OK;
     if (!leaves_dev || !trees_dev || !indices_dev || !siblings_dev || !heights_dev || !roots_dev || !ok_dev)
-        return fail(VKMR_ERR_INVALID, "vkmr_hip_verify_forest_proofs_async: null pointer");
-    if (stride == 0 || stride > 63) return fail(VKMR_ERR_INVALID, "vkmr_hip_verify_forest_proofs_async: stride must be 1..63");
+        return refuse(__func__, "null pointer");
+    if (stride == 0 || stride > 63) return refuse(__func__, "stride must be 1..63");
     VKMR_TRY(hipSetDevice(dev));
-    const dim3 grid = grid_of(k);
-    hipLaunchKernelGGL(verify_forest_proofs_kernel, grid, dim3(256), 0, S(s), nodes(leaves_dev), trees_dev, indices_dev,
-                       nodes(siblings_dev), heights_dev, k, stride, nodes(roots_dev), ntrees, ok_dev);
-    VKMR_TRY(hipGetLastError());
-    return VKMR_OK;
+    return launch(verify_forest_proofs_kernel, grid_of(k), dim3(256), S(s), nodes(leaves_dev), trees_dev, indices_dev, nodes(siblings_dev), heights_dev, k,
+                  stride, nodes(roots_dev), ntrees, ok_dev);
 }
 
 // ---- leaf updates of the stored forest (forest_tree_kernels.hpp) -----------------------------------------------------------
@@ -1193,9 +1066,8 @@ vkmr_status vkmr_hip_forest_update_async(int dev, vkmr_stream s, vkmr_digest* di
 {
     if (k == 0) return VKMR_OK;
     if (!digests_dev || !forest_dev || !offsets_dev || !trees_dev || !indices_dev || !leaves_dev || !roots_dev || !status_dev)
-        return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_update_async: null pointer");
-    const vkmr_status args = forest_args_check("vkmr_hip_forest_update_async", total, ntrees, max_count, k, "a forest without a leaf has none to update", nullptr);
-    if (args != VKMR_OK) return args;
+        return refuse(__func__, "null pointer");
+    VKMR_CHECK(forest_args_check(__func__, total, ntrees, max_count, k, "a forest without a leaf has none to update", nullptr));
     const uint32_t H = vkmr_forest::launches(total, max_count);   // <= 58
     const dim3 grid = grid_of(k);
     Node* digests = nodes(digests_dev);
@@ -1203,16 +1075,12 @@ vkmr_status vkmr_hip_forest_update_async(int dev, vkmr_stream s, vkmr_digest* di
     Node* roots = nodes(roots_dev);
     VKMR_TRY(hipSetDevice(dev));
     VKMR_TRY(hipMemsetAsync(status_dev, 0, sizeof(uint32_t), S(s)));
-    hipLaunchKernelGGL(forest_update_check_kernel, grid, dim3(256), 0, S(s), offsets_dev, ntrees, trees_dev, indices_dev, k, status_dev);
-    VKMR_TRY(hipGetLastError());
-    hipLaunchKernelGGL(forest_update_leaves_kernel, grid, dim3(256), 0, S(s), digests, offsets_dev, trees_dev, indices_dev, nodes(leaves_dev), k,
-                       (const uint32_t*)status_dev);
-    VKMR_TRY(hipGetLastError());
+    VKMR_CHECK(launch(forest_update_check_kernel, grid, dim3(256), S(s), offsets_dev, ntrees, trees_dev, indices_dev, k, status_dev));
+    VKMR_CHECK(launch(forest_update_leaves_kernel, grid, dim3(256), S(s), digests, offsets_dev, trees_dev, indices_dev, nodes(leaves_dev), k, status_dev));
     for (uint32_t l = 1; l <= H; ++l) {   // level l from level l - 1, which the previous launch finished
         const Node* in = (l == 1) ? digests : forest + vkmr_forest::stored_level_base(total, ntrees, l - 1);
-        hipLaunchKernelGGL(forest_update_level_kernel, grid, dim3(256), 0, S(s), in, forest + vkmr_forest::stored_level_base(total, ntrees, l), roots,
-                           offsets_dev, trees_dev, indices_dev, k, l, (const uint32_t*)status_dev);
-        VKMR_TRY(hipGetLastError());
+        VKMR_CHECK(launch(forest_update_level_kernel, grid, dim3(256), S(s), in, forest + vkmr_forest::stored_level_base(total, ntrees, l), roots, offsets_dev,
+                          trees_dev, indices_dev, k, l, status_dev));
     }
     return VKMR_OK;
 }
@@ -1222,13 +1090,7 @@ vkmr_status vkmr_hip_forest_update_async(int dev, vkmr_stream s, vkmr_digest* di
 size_t vkmr_hip_forest_multiproof_max_nodes(uint64_t total, uint32_t ntrees, uint64_t max_count, uint32_t k)
 {
     if (total == 0 || ntrees == 0 || max_count == 0) return 0;
-    const uint32_t H = vkmr_forest::launches(total, max_count);
-    uint64_t cells = 0;
-    for (uint32_t l = 0; l < H; ++l) {   // at most one node per parent of a live tree: the cells of level l + 1
-        const uint64_t parents = vkmr_forest::level_cells(total, ntrees, l + 1);
-        cells += parents < k ? parents : k;
-    }
-    return (size_t)cells;
+    return (size_t)vkmr_forest::multiproof_max_nodes(total, ntrees, max_count, k);
 }
 
 size_t vkmr_hip_forest_multiproof_scratch_bytes(uint32_t k, uint32_t stride)
@@ -1244,31 +1106,21 @@ vkmr_status vkmr_hip_forest_multiproof_async(int dev, vkmr_stream s, const vkmr_
     if (k == 0) return VKMR_OK;
     if (!digests_dev || !forest_dev || !offsets_dev || !trees_dev || !indices_dev || !scratch_dev || !heights_dev || !info_dev ||
         (!nodes_dev && nodes_capacity > 0))
-        return fail(VKMR_ERR_INVALID, "vkmr_hip_forest_multiproof_async: null pointer");
-    const vkmr_status args = forest_args_check("vkmr_hip_forest_multiproof_async", total, ntrees, max_count, k, "a forest without a leaf has none to prove", scratch_dev);
-    if (args != VKMR_OK) return args;
+        return refuse(__func__, "null pointer");
+    VKMR_CHECK(forest_args_check(__func__, total, ntrees, max_count, k, "a forest without a leaf has none to prove", scratch_dev));
     const uint32_t H = vkmr_forest::launches(total, max_count);   // <= 58
     const ForestLevels lv = forest_levels(total, ntrees, H);
     const MultiproofLayout L = multiproof_layout(k, H);
-    char* scratch = static_cast<char*>(scratch_dev);
+    const MultiproofScratch sc(scratch_dev, L);
     const dim3 grid = grid_of(k);
     VKMR_TRY(hipSetDevice(dev));
     VKMR_TRY(hipMemsetAsync(info_dev, 0, sizeof(uint64_t), S(s)));
-    hipLaunchKernelGGL(forest_update_check_kernel, grid, dim3(256), 0, S(s), offsets_dev, ntrees, trees_dev, indices_dev, k,
-                       reinterpret_cast<uint32_t*>(info_dev));
-    VKMR_TRY(hipGetLastError());
-    hipLaunchKernelGGL(forest_multiproof_heights_kernel, grid, dim3(256), 0, S(s), offsets_dev, trees_dev, k, (const uint64_t*)info_dev, heights_dev);
-    VKMR_TRY(hipGetLastError());
-    hipLaunchKernelGGL(forest_multiproof_masks_kernel, grid, dim3(256), 0, S(s), trees_dev, indices_dev, (const uint32_t*)heights_dev, k, H, L.words,
-                       (const uint64_t*)info_dev, reinterpret_cast<uint64_t*>(scratch + L.mask));
-    VKMR_TRY(hipGetLastError());
-    const vkmr_status st = multiproof_rank_launch(S(s), H, L, scratch, info_dev, nodes_capacity, 0u);
-    if (st != VKMR_OK) return st;
-    hipLaunchKernelGGL(forest_multiproof_gather_kernel, grid_of(k, H), dim3(256), 0, S(s), nodes(digests_dev), nodes(forest_dev), lv, offsets_dev,
-                       trees_dev, indices_dev, k, L.words, reinterpret_cast<const uint64_t*>(scratch + L.mask),
-                       reinterpret_cast<const uint64_t*>(scratch + L.word_start), (const uint64_t*)info_dev, nodes(nodes_dev));
-    VKMR_TRY(hipGetLastError());
-    return VKMR_OK;
+    VKMR_CHECK(launch(forest_update_check_kernel, grid, dim3(256), S(s), offsets_dev, ntrees, trees_dev, indices_dev, k, reinterpret_cast<uint32_t*>(info_dev)));
+    VKMR_CHECK(launch(forest_multiproof_heights_kernel, grid, dim3(256), S(s), offsets_dev, trees_dev, k, info_dev, heights_dev));
+    VKMR_CHECK(launch(forest_multiproof_masks_kernel, grid, dim3(256), S(s), trees_dev, indices_dev, heights_dev, k, H, L.words, info_dev, sc.mask));
+    VKMR_CHECK(multiproof_rank_launch(S(s), H, L, sc, info_dev, nodes_capacity, 0u));
+    return launch(forest_multiproof_gather_kernel, grid_of(k, H), dim3(256), S(s), nodes(digests_dev), nodes(forest_dev), lv, offsets_dev, trees_dev,
+                  indices_dev, k, L.words, sc.mask, sc.word_start, info_dev, nodes(nodes_dev));
 }
 
 vkmr_status vkmr_hip_verify_forest_multiproof_async(int dev, vkmr_stream s, const vkmr_digest* leaves_dev, const uint32_t* trees_dev,
@@ -1278,36 +1130,23 @@ vkmr_status vkmr_hip_verify_forest_multiproof_async(int dev, vkmr_stream s, cons
 {
     if (k == 0) return VKMR_OK;
     if (!leaves_dev || !trees_dev || !indices_dev || !heights_dev || !roots_dev || !scratch_dev || !ok_dev || (!nodes_dev && m > 0))
-        return fail(VKMR_ERR_INVALID, "vkmr_hip_verify_forest_multiproof_async: null pointer");
-    if (stride == 0 || stride > 63) return fail(VKMR_ERR_INVALID, "vkmr_hip_verify_forest_multiproof_async: stride must be 1..63");
-    if (reinterpret_cast<uintptr_t>(scratch_dev) & 15u) return refuse("vkmr_hip_verify_forest_multiproof_async", "scratch must be 16-byte aligned");
+        return refuse(__func__, "null pointer");
+    if (stride == 0 || stride > 63) return refuse(__func__, "stride must be 1..63");
+    if (reinterpret_cast<uintptr_t>(scratch_dev) & 15u) return refuse(__func__, "scratch must be 16-byte aligned");
     const MultiproofLayout L = multiproof_layout(k, stride);
-    char* scratch = static_cast<char*>(scratch_dev);
-    uint64_t* hdr = reinterpret_cast<uint64_t*>(scratch + L.hdr);
-    Node* cell = nodes(scratch + L.cell);
+    const MultiproofScratch sc(scratch_dev, L);
     const dim3 grid = grid_of(k);
     VKMR_TRY(hipSetDevice(dev));
-    VKMR_TRY(hipMemsetAsync(hdr, 0, sizeof(uint64_t), S(s)));
+    VKMR_TRY(hipMemsetAsync(sc.hdr, 0, sizeof(uint64_t), S(s)));
     VKMR_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ok_dev), 1, 1, S(s)));   // the finish kernel clears it
-    hipLaunchKernelGGL(verify_forest_multiproof_check_kernel, grid, dim3(256), 0, S(s), trees_dev, indices_dev, heights_dev, k, stride, ntrees,
-                       reinterpret_cast<uint32_t*>(hdr));
-    VKMR_TRY(hipGetLastError());
-    hipLaunchKernelGGL(forest_multiproof_masks_kernel, grid, dim3(256), 0, S(s), trees_dev, indices_dev, heights_dev, k, stride, L.words,
-                       (const uint64_t*)hdr, reinterpret_cast<uint64_t*>(scratch + L.mask));
-    VKMR_TRY(hipGetLastError());
-    const vkmr_status st = multiproof_rank_launch(S(s), stride, L, scratch, hdr, m, 1u);   // exact: M == m
-    if (st != VKMR_OK) return st;
-    for (uint32_t l = 0; l < stride; ++l) {   // level l + 1 from level l, which the previous launch finished
-        hipLaunchKernelGGL(verify_forest_multiproof_level_kernel, grid, dim3(256), 0, S(s), l == 0 ? nodes(leaves_dev) : cell, cell,
-                           reinterpret_cast<uint32_t*>(scratch + L.end), trees_dev, indices_dev, heights_dev, k, l, L.words,
-                           reinterpret_cast<const uint64_t*>(scratch + L.mask), reinterpret_cast<const uint64_t*>(scratch + L.word_start),
-                           nodes(nodes_dev), (const uint64_t*)hdr);
-        VKMR_TRY(hipGetLastError());
-    }
-    hipLaunchKernelGGL(verify_forest_multiproof_finish_kernel, grid, dim3(256), 0, S(s), (const Node*)cell, trees_dev, k, nodes(roots_dev),
-                       (const uint64_t*)hdr, ok_dev);
-    VKMR_TRY(hipGetLastError());
-    return VKMR_OK;
+    VKMR_CHECK(launch(verify_forest_multiproof_check_kernel, grid, dim3(256), S(s), trees_dev, indices_dev, heights_dev, k, stride, ntrees,
+                      reinterpret_cast<uint32_t*>(sc.hdr)));
+    VKMR_CHECK(launch(forest_multiproof_masks_kernel, grid, dim3(256), S(s), trees_dev, indices_dev, heights_dev, k, stride, L.words, sc.hdr, sc.mask));
+    VKMR_CHECK(multiproof_rank_launch(S(s), stride, L, sc, sc.hdr, m, 1u));   // exact: M == m
+    for (uint32_t l = 0; l < stride; ++l)   // level l + 1 from level l, which the previous launch finished
+        VKMR_CHECK(launch(verify_forest_multiproof_level_kernel, grid, dim3(256), S(s), l == 0 ? nodes(leaves_dev) : sc.cell, sc.cell, sc.end, trees_dev,
+                          indices_dev, heights_dev, k, l, L.words, sc.mask, sc.word_start, nodes(nodes_dev), sc.hdr));
+    return launch(verify_forest_multiproof_finish_kernel, grid, dim3(256), S(s), sc.cell, trees_dev, k, nodes(roots_dev), sc.hdr, ok_dev);
 }
 
 // ---- lookup by digest (find_kernels.hpp, find_plan.hpp) ---------------------------------------------------------------------
@@ -1328,6 +1167,19 @@ static vkmr_status compute_units_of(int dev, uint32_t* cus)
     return VKMR_OK;
 }
 
+// The parts of a lookup's scratch_dev (find_plan.hpp) as the kernels take them.
+struct FindScratch {
+    unsigned long long *table, *best;
+    uint32_t* rep;
+    FindScratch(void* scratch_dev, uint32_t k)
+    {
+        char* at = static_cast<char*>(scratch_dev);
+        table = reinterpret_cast<unsigned long long*>(at);
+        best = reinterpret_cast<unsigned long long*>(at + vkmr_find::best_offset(k));
+        rep = reinterpret_cast<uint32_t*>(at + vkmr_find::rep_offset(k));
+    }
+};
+
 // The launches of both lookups, all on the caller's stream: the scratch set to 0xFF (every slot empty, every best position
 // "none"), the queries inserted, the leaves scanned (no launch when there is no cell to scan), the answers resolved.  They
 // depend on (cells, k) and the device alone.  trees_dev null: one tree over [0, cells), and no offsets.
@@ -1338,57 +1190,40 @@ static vkmr_status find_launch(const char* who, int dev, vkmr_stream s, const vk
     if (cells > (1ull << 58)) return refuse(who, "too many leaves");
     if (reinterpret_cast<uintptr_t>(scratch_dev) & 7u) return refuse(who, "scratch must be 8-byte aligned");
     const uint64_t mask = vkmr_find::table_slots(k) - 1ull;
-    char* scratch = static_cast<char*>(scratch_dev);
-    unsigned long long* table = reinterpret_cast<unsigned long long*>(scratch);
-    unsigned long long* best = reinterpret_cast<unsigned long long*>(scratch + vkmr_find::best_offset(k));
-    uint32_t* rep = reinterpret_cast<uint32_t*>(scratch + vkmr_find::rep_offset(k));
+    const FindScratch sc(scratch_dev, k);
     uint32_t cus = 0;
     VKMR_TRY(hipSetDevice(dev));
-    const vkmr_status st = compute_units_of(dev, &cus);
-    if (st != VKMR_OK) return st;
+    VKMR_CHECK(compute_units_of(dev, &cus));
     VKMR_TRY(hipMemsetAsync(scratch_dev, 0xFF, (size_t)vkmr_find::scratch_bytes(k), S(s)));
-    hipLaunchKernelGGL(find_insert_kernel, grid_of(k), dim3(256), 0, S(s), nodes(queries_dev), k, table, mask, rep);
-    VKMR_TRY(hipGetLastError());
+    VKMR_CHECK(launch(find_insert_kernel, grid_of(k), dim3(256), S(s), nodes(queries_dev), k, sc.table, mask, sc.rep));
     if (cells > 0) {
-        const dim3 grid((uint32_t)vkmr_find::scan_groups(cells, cus));
-        if (trees_dev)
-            hipLaunchKernelGGL(forest_find_scan_kernel, grid, dim3(VKMR_FIND_THREADS), 0, S(s), nodes(digests_dev), offsets_dev, ntrees, cells,
-                               nodes(queries_dev), (const unsigned long long*)table, mask, best);
-        else
-            hipLaunchKernelGGL(tree_find_scan_kernel, grid, dim3(VKMR_FIND_THREADS), 0, S(s), nodes(digests_dev), cells, nodes(queries_dev),
-                               (const unsigned long long*)table, mask, best);
-        VKMR_TRY(hipGetLastError());
+        const dim3 grid((uint32_t)vkmr_find::scan_groups(cells, cus)), block(VKMR_FIND_THREADS);
+        VKMR_CHECK(trees_dev ? launch(forest_find_scan_kernel, grid, block, S(s), nodes(digests_dev), offsets_dev, ntrees, cells, nodes(queries_dev), sc.table,
+                                      mask, sc.best)
+                             : launch(tree_find_scan_kernel, grid, block, S(s), nodes(digests_dev), cells, nodes(queries_dev), sc.table, mask, sc.best));
     }
-    if (trees_dev)
-        hipLaunchKernelGGL(forest_find_resolve_kernel, grid_of(k), dim3(256), 0, S(s), offsets_dev, ntrees, cells, k, (const unsigned long long*)best,
-                           (const uint32_t*)rep, trees_dev, indices_dev);
-    else
-        hipLaunchKernelGGL(tree_find_resolve_kernel, grid_of(k), dim3(256), 0, S(s), cells, k, (const unsigned long long*)best, (const uint32_t*)rep,
-                           indices_dev);
-    VKMR_TRY(hipGetLastError());
-    return VKMR_OK;
+    if (trees_dev) return launch(forest_find_resolve_kernel, grid_of(k), dim3(256), S(s), offsets_dev, ntrees, cells, k, sc.best, sc.rep, trees_dev, indices_dev);
+    return launch(tree_find_resolve_kernel, grid_of(k), dim3(256), S(s), cells, k, sc.best, sc.rep, indices_dev);
 }
 
 vkmr_status vkmr_hip_forest_find_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t total, const uint64_t* offsets_dev,
                                        uint32_t ntrees, const vkmr_digest* queries_dev, uint32_t k, void* scratch_dev, uint32_t* trees_dev,
                                        uint64_t* indices_dev)
 {
-    const char* who = "vkmr_hip_forest_find_async";
     if (k == 0) return VKMR_OK;
     const bool leaves = ntrees > 0 && total > 0;       // without a tree or a cell nothing is read but the queries
     if (!queries_dev || !scratch_dev || !trees_dev || !indices_dev || (ntrees > 0 && !offsets_dev) || (leaves && !digests_dev))
-        return refuse(who, "null pointer");
+        return refuse(__func__, "null pointer");
     // no tree: the kernels read no offset and scan an empty range; the launches stay those of (total, k)
-    return find_launch(who, dev, s, digests_dev, total, offsets_dev, ntrees, queries_dev, k, scratch_dev, trees_dev, indices_dev);
+    return find_launch(__func__, dev, s, digests_dev, total, offsets_dev, ntrees, queries_dev, k, scratch_dev, trees_dev, indices_dev);
 }
 
 vkmr_status vkmr_hip_tree_find_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t count, const vkmr_digest* queries_dev,
                                      uint32_t k, void* scratch_dev, uint64_t* indices_dev)
 {
-    const char* who = "vkmr_hip_tree_find_async";
     if (k == 0) return VKMR_OK;
-    if (!queries_dev || !scratch_dev || !indices_dev || (count > 0 && !digests_dev)) return refuse(who, "null pointer");
-    return find_launch(who, dev, s, digests_dev, count, nullptr, 0, queries_dev, k, scratch_dev, nullptr, indices_dev);
+    if (!queries_dev || !scratch_dev || !indices_dev || (count > 0 && !digests_dev)) return refuse(__func__, "null pointer");
+    return find_launch(__func__, dev, s, digests_dev, count, nullptr, 0, queries_dev, k, scratch_dev, nullptr, indices_dev);
 }
 
 // ---- combine --------------------------------------------------------------------
@@ -1396,7 +1231,7 @@ vkmr_status vkmr_hip_tree_find_async(int dev, vkmr_stream s, const vkmr_digest* 
 vkmr_status vkmr_hip_combine_async(int dev, vkmr_stream s, const vkmr_digest* roots_dev, uint32_t n, void* scratch_dev,
                                    vkmr_digest* root_dev)
 {
-    if (!roots_dev || !root_dev || n == 0) return fail(VKMR_ERR_INVALID, "vkmr_hip_combine_async: bad argument");
+    if (!roots_dev || !root_dev || n == 0) return refuse(__func__, "bad argument");
     return vkmr_hip_reduce_async(dev, s, roots_dev, n, vkmr_math::height(n), scratch_dev, root_dev);   // at least one level
 }
 
