@@ -608,6 +608,58 @@ VKMR_API vkmr_status vkmr_hip_tree_find_async(int dev, vkmr_stream s, const vkmr
                                               uint64_t* indices_dev);
 
 /*
+ * SORT AND DEDUP LEAF ENTRIES (the reference has no counterpart): the step from entries in CALL order -- what
+ * vkmr_hip_forest_find_async writes, "not found" markers in between, or a caller's own batch -- to the strictly increasing
+ * (tree, index) pairs that vkmr_hip_forest_update_async, vkmr_hip_forest_multiproof_async and their tree twins require, with
+ * no entry and no digest going through the host.  total, offsets_dev and ntrees as in vkmr_hip_reduce_forest_async; the call
+ * TRUSTS the offsets as vkmr_hip_forest_find_async does.  trees_dev[0..k), indices_dev[0..k) are the entries, in device
+ * memory, in any order, repeats allowed.  Entry q is VALID iff trees_dev[q] < ntrees and indices_dev[q] < c_t; its key is the
+ * flat position offsets[t] + index < total, whose order is the lexicographic order of the pairs.  Every entry is exactly one of
+ *   a survivor                                                      info_dev[0] = n
+ *   find's "not found" marker (trees_dev[q] == 0xFFFFFFFF), left out   info_dev[1]
+ *   out of range (any other entry that is not valid), left out      info_dev[2]
+ *   an earlier repeat of a pair that occurs again later, left out   info_dev[3]
+ * so info_dev[0] + [1] + [2] + [3] == k.  info_dev: 4 uint64_t of device memory, always written when k > 0.
+ * Cells [0, n) of trees_out_dev, indices_out_dev: the distinct valid pairs, strictly increasing -- exactly what the four
+ * calls above accept.  order_out_dev[j] (uint32) is the LARGEST q whose pair equals output pair j: the last occurrence wins,
+ * so the result is a function of the input alone, whatever the scheduling.  Cells at and behind n are unspecified.  The
+ * outputs (k cells each) must not overlap the inputs or the scratch.  n stays on the device and the next call takes its k
+ * on the host: the caller reads info_dev back (32 bytes), as with vkmr_hip_forest_multiproof_async's info_dev.
+ *   scratch_dev  vkmr_hip_sort_entries_scratch_bytes(total, k) bytes of device memory, 16-byte aligned (layout:
+ *                csrc/sort_plan.hpp: ping-pong keys and payloads, 24 k bytes, the histograms, the ranking words).
+ * A stable LSD radix sort of (key, q), 8 bits per pass over bit_length(total) bits -- one pass for total < 256, at most 8 --
+ * then the last pair of every run of equal keys is kept.  Launches, all on the caller's stream: two memsets, the keys, three
+ * per pass (histogram, scan, scatter), the flags, three ranking launches, the emit.  They depend on (total, k) only; no
+ * allocation, no host synchronisation, no host read of device data; no kernel waits for another workgroup.
+ * k == 0 does nothing whatever the other arguments.  ntrees == 0 or total == 0 with k > 0 writes n = 0 and counts every entry
+ * in info_dev[1] or info_dev[2]; offsets_dev may be NULL when ntrees == 0.  Refused on the host (VKMR_ERR_INVALID) with k > 0,
+ * before any HIP call: a NULL pointer that is needed, total above 2^58, scratch_dev not 16-byte aligned.
+ * vkmr_host_cpu_forest_sort_entries (libvkmr_host.so) applies the same rule on the CPU.
+ */
+VKMR_API size_t vkmr_hip_sort_entries_scratch_bytes(uint64_t total, uint32_t k);
+VKMR_API vkmr_status vkmr_hip_forest_sort_entries_async(int dev, vkmr_stream s, uint64_t total, const uint64_t* offsets_dev,
+                                                        uint32_t ntrees, const uint32_t* trees_dev, const uint64_t* indices_dev,
+                                                        uint32_t k, void* scratch_dev, uint32_t* trees_out_dev,
+                                                        uint64_t* indices_out_dev, uint32_t* order_out_dev, uint64_t* info_dev);
+/*
+ * The same for ONE tree of `count` leaves: every entry is in tree 0, the key is the index, the marker is indices_dev[q] ==
+ * UINT64_MAX (what vkmr_hip_tree_find_async writes), out of range is any other index >= count.  Same scratch
+ * (vkmr_hip_sort_entries_scratch_bytes(count, k)), launches and refusals (count above 2^58); count == 0 writes n = 0.
+ * vkmr_host_cpu_tree_sort_entries is the CPU's.
+ */
+VKMR_API vkmr_status vkmr_hip_tree_sort_entries_async(int dev, vkmr_stream s, uint64_t count, const uint64_t* indices_dev,
+                                                      uint32_t k, void* scratch_dev, uint64_t* indices_out_dev,
+                                                      uint32_t* order_out_dev, uint64_t* info_dev);
+/*
+ * GATHER DIGESTS: dst_dev[j] = src_dev[order_dev[j]], j < n -- the payload of a sorted batch (new leaves, proved leaves)
+ * brought into the order of the sorted entries, order_dev being the sort's order_out_dev and n its info_dev[0].  One launch
+ * of n lanes on the caller's stream.  Every order_dev[j] must be a cell of src_dev (the sort's are < k); dst_dev must not
+ * overlap src_dev.  n == 0 does nothing; a NULL pointer with n > 0 is refused on the host.
+ */
+VKMR_API vkmr_status vkmr_hip_gather_digests_async(int dev, vkmr_stream s, const vkmr_digest* src_dev, const uint32_t* order_dev,
+                                                   uint32_t n, vkmr_digest* dst_dev);
+
+/*
  * COMBINE: duplicate-last Merkle root over n >= 1 slice roots given in slice order, always
  * at least one level -- the rule of CpuSha256D::Root that the reference applies to the slice
  * roots on the CPU (CpuSha256DforReductions, src/vkmr/Reductions.cpp:56-69, :703-712).  Here

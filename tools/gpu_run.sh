@@ -13,6 +13,9 @@
 #   rehearsals             soaks against the oracle; torchrun --nproc 2 (gloo rehearsal; plain N=2 must fail on one GPU); --force-dist (RCCL, one rank)
 #   forestupdate [args]    tools/forest_update_timing.py: leaf updates of a stored forest against a rebuild and against the single tree's
 #                          update (one JSON line), then the same run under rocprofv3 --kernel-trace --stats; stops at the first failing step
+#   sortentries [args]     tools/sort_entries_timing.py: entries sorted on the device in front of a forest update against the route through
+#                          the host, and the sort alone beside torch.sort (one JSON line), then the same run under rocprofv3
+#                          --kernel-trace --stats; stops at the first failing step
 #   find [args]            tools/find_timing.py: the lookup by digest beside a read-only pass of torch's over as many bytes (one JSON line)
 #   cumask                 tools/cu_mask_probe.py: where CU-mask bits land, map/reduce on half the CUs with and without neighbours
 #   issue <set>            tools/issue_patterns (python3 tools/gen_issue_patterns.py <set> and a build beforehand)
@@ -145,6 +148,15 @@ forestupdate)
   find $OUT/prof_forest_update -name "*kernel_stats.csv" -exec cp {} $OUT/forest_update_kernel_stats.csv \; &&
   cat $OUT/forest_update_kernel_stats.csv
   echo "forestupdate rc=$?"
+  ;;
+sortentries)
+  timeout -k 10 500 python3 tools/sort_entries_timing.py "$@" --out $OUT/sort_entries_timing.json > /dev/null 2> $OUT/sort_entries_timing.err && echo "sort_entries_timing ok" &&
+  cat $OUT/sort_entries_timing.json &&
+  repo=$(pwd) &&
+  ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $repo/$OUT/prof_sort_entries -- python3 $repo/tools/sort_entries_timing.py "$@" --runs 3 > $repo/$OUT/sort_entries_prof.json 2> $repo/$OUT/sort_entries_prof.err ) &&
+  find $OUT/prof_sort_entries -name "*kernel_stats.csv" -exec cp {} $OUT/sort_entries_kernel_stats.csv \; &&
+  cat $OUT/sort_entries_kernel_stats.csv
+  echo "sortentries rc=$?"
   ;;
 find)
   timeout -k 10 500 python3 tools/find_timing.py "$@" --out $OUT/find_timing.json > /dev/null 2> $OUT/find_timing.err && echo "find_timing ok" &&

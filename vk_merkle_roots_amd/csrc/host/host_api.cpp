@@ -432,4 +432,70 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_tree_find(const vkmr_di
     return vkmr_host_cpu_forest_find(digests, count, offsets, 1, queries, k, trees.data(), indices);
 }
 
+// Leaf entries sorted and deduplicated on the CPU, by the rule of vkmr_hip_forest_sort_entries_async: cells [0, n) of the
+// outputs are the distinct valid (tree, index) pairs, strictly increasing, order_out[j] the largest q whose pair is output
+// pair j; info[0..4) = survivors n, "not found" markers (trees[q] == 0xFFFFFFFF), entries out of range, earlier repeats.
+// trees == NULL: one tree (offsets {0, total}), the marker being indices[q] == UINT64_MAX, and trees_out is not written.
+// A stable sort of q by flat position.  Nonzero, and nothing written, when the offsets decrease somewhere or end past
+// `total` (1) or a needed pointer is missing (-1).  k == 0 does nothing (the two entry points below see to that).
+static int sort_entries_cpu(uint64_t total, const uint64_t* offsets, uint32_t ntrees, const uint32_t* trees, const uint64_t* indices, uint32_t k,
+                           uint32_t* trees_out, uint64_t* indices_out, uint32_t* order_out, uint64_t* info)
+{
+    if (!indices || !indices_out || !order_out || !info || (ntrees > 0 && !offsets)) return -1;
+    for (uint32_t t = 0; t < ntrees; ++t)
+        if (offsets[t + 1] < offsets[t]) return 1;
+    if (ntrees && offsets[ntrees] > total) return 1;
+    uint64_t markers = 0, outside = 0, repeats = 0, n = 0;
+    std::vector<uint64_t> key(k);
+    std::vector<uint32_t> order;
+    order.reserve(k);
+    for (uint32_t q = 0; q < k; ++q) {
+        const uint32_t t = trees ? trees[q] : 0u;
+        if (trees ? t == UINT32_MAX : indices[q] == UINT64_MAX) {
+            ++markers;
+        } else if (t >= ntrees || indices[q] >= offsets[t + 1] - offsets[t]) {
+            ++outside;
+        } else {
+            key[q] = offsets[t] + indices[q];
+            order.push_back(q);
+        }
+    }
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
+    for (size_t j = 0; j < order.size(); ++j) {
+        const uint32_t q = order[j];
+        if (j + 1 < order.size() && key[order[j + 1]] == key[q]) {   // repeats stay in call order: the last of a run is the last occurrence
+            ++repeats;
+            continue;
+        }
+        if (trees) trees_out[n] = trees[q];
+        indices_out[n] = indices[q];
+        order_out[n] = q;
+        ++n;
+    }
+    info[0] = n;
+    info[1] = markers;
+    info[2] = outside;
+    info[3] = repeats;
+    return 0;
+}
+
+__attribute__((visibility("default"))) int vkmr_host_cpu_forest_sort_entries(uint64_t total, const uint64_t* offsets, uint32_t ntrees,
+                                                                              const uint32_t* trees, const uint64_t* indices, uint32_t k,
+                                                                              uint32_t* trees_out, uint64_t* indices_out, uint32_t* order_out,
+                                                                              uint64_t* info)
+{
+    if (k == 0) return 0;
+    if (!trees || !trees_out) return -1;
+    return sort_entries_cpu(total, offsets, ntrees, trees, indices, k, trees_out, indices_out, order_out, info);
+}
+
+// The same for one tree of `count` leaves: every entry in tree 0.
+__attribute__((visibility("default"))) int vkmr_host_cpu_tree_sort_entries(uint64_t count, const uint64_t* indices, uint32_t k, uint64_t* indices_out,
+                                                                            uint32_t* order_out, uint64_t* info)
+{
+    if (k == 0) return 0;
+    const uint64_t offsets[2] = {0, count};
+    return sort_entries_cpu(count, offsets, 1, nullptr, indices, k, nullptr, indices_out, order_out, info);
+}
+
 }  // extern "C"

@@ -22,6 +22,9 @@
 //                                              the multiproof bodies and tree_kernels.hpp's ranking, a tree and a height per entry
 //   find_kernels.hpp    find_insert_kernel, *_find_scan_kernel, *_find_resolve_kernel   lookup by digest: the queries in an open-addressed
 //                                              table, every leaf streamed past it once, lowest position per query (sizes: find_plan.hpp)
+//   sort_kernels.hpp    *_sort_keys_kernel, sort_histogram_kernel, sort_scan_kernel, sort_scatter_kernel, sort_flags_kernel, *_sort_emit_kernel,
+//                                              gather_digests_kernel   leaf entries sorted and deduplicated: a stable LSD radix sort of
+//                                              (flat position, q) pairs, the last of every run kept (sizes: sort_plan.hpp)
 //   sha256d_device.hpp  the SHA-256 round / compression building blocks, and the tree's: hash_parent, node_diff, store_node
 //   merkle_math.hpp     the integer rules, no HIP types (ceil_shift, height, right_child, sibling): shared with host/ and tests/c
 //   meta_kernels.hpp    sizes_*_kernel         metadata entries from 16-bit sizes   (Batches.cpp:64-121)
@@ -32,6 +35,7 @@
 //   tree_plan.hpp       the stored tree's level offsets, the multiproof node bound and scratch layout
 //   forest_plan.hpp     where a forest's nodes lie, level by level; its scratch, stored size and multiproof node bound
 //   find_plan.hpp       the lookup's scratch layout and scan grid
+//   sort_plan.hpp       the entry sort's passes, tiles, histogram words and scratch layout
 //
 // Host side: plain launches on the caller's stream, each through launch() and so each checked; every argument refusal
 // through refuse(__func__, why); no allocation, no sync inside the *_async entry points.
@@ -62,6 +66,7 @@ using vkmr_dev::Node;
 #include "forest_kernels.hpp"
 #include "forest_tree_kernels.hpp"
 #include "find_kernels.hpp"
+#include "sort_kernels.hpp"
 
 // ============================================================================
 // C ABI
@@ -1224,6 +1229,99 @@ vkmr_status vkmr_hip_tree_find_async(int dev, vkmr_stream s, const vkmr_digest* 
     if (k == 0) return VKMR_OK;
     if (!queries_dev || !scratch_dev || !indices_dev || (count > 0 && !digests_dev)) return refuse(__func__, "null pointer");
     return find_launch(__func__, dev, s, digests_dev, count, nullptr, 0, queries_dev, k, scratch_dev, nullptr, indices_dev);
+}
+
+// ---- leaf entries sorted and deduplicated (sort_kernels.hpp, sort_plan.hpp) -------------------------------------------------
+
+static_assert(VKMR_SORT_RANK_BLOCK_WORDS == VKMR_MP_BLOCK_WORDS, "the survivors are ranked by the multiproof's ranking kernels");
+static_assert(VKMR_SORT_THREADS == VKMR_SIZES_THREADS && VKMR_SORT_BINS == VKMR_SORT_THREADS, "one bin per lane, and block_exclusive's workgroup");
+
+size_t vkmr_hip_sort_entries_scratch_bytes(uint64_t total, uint32_t k) { return vkmr_sort::scratch_bytes(total, k); }
+
+// The parts of a sort's scratch_dev (sort_plan.hpp) as the kernels take them.
+struct SortScratch {
+    uint64_t *key[2], *mask, *word_start, *block, *hdr;
+    uint32_t *val[2], *hist, *totals;
+    SortScratch(void* scratch_dev, const vkmr_sort::Layout& L)
+    {
+        char* at = static_cast<char*>(scratch_dev);
+        for (int b = 0; b < 2; ++b) {
+            key[b] = reinterpret_cast<uint64_t*>(at + L.key[b]);
+            val[b] = reinterpret_cast<uint32_t*>(at + L.val[b]);
+        }
+        hist = reinterpret_cast<uint32_t*>(at + L.hist);
+        totals = reinterpret_cast<uint32_t*>(at + L.totals);
+        mask = reinterpret_cast<uint64_t*>(at + L.mask);
+        word_start = reinterpret_cast<uint64_t*>(at + L.word_start);
+        block = reinterpret_cast<uint64_t*>(at + L.block);
+        hdr = reinterpret_cast<uint64_t*>(at + L.hdr);
+    }
+};
+
+// The launches of both sorts, all on the caller's stream: the counters and the ranking header zeroed, the keys, three launches
+// per pass, the flags, the three ranking launches (one level), the emit.  They depend on (cells, k) alone.  trees_dev null:
+// one tree over [0, cells), and no offsets.
+static vkmr_status sort_launch(const char* who, int dev, vkmr_stream s, uint64_t cells, const uint64_t* offsets_dev, uint32_t ntrees,
+                               const uint32_t* trees_dev, const uint64_t* indices_dev, uint32_t k, void* scratch_dev, uint32_t* trees_out_dev,
+                               uint64_t* indices_out_dev, uint32_t* order_out_dev, uint64_t* info_dev)
+{
+    if (cells > vkmr_sort::MAX_TOTAL) return refuse(who, "too many leaves");
+    if (reinterpret_cast<uintptr_t>(scratch_dev) & 15u) return refuse(who, "scratch must be 16-byte aligned");
+    const vkmr_sort::Layout L = vkmr_sort::layout(k);
+    const SortScratch sc(scratch_dev, L);
+    const uint32_t passes = vkmr_sort::passes(cells);
+    unsigned long long* info = reinterpret_cast<unsigned long long*>(info_dev);
+    const dim3 lanes = grid_of(k), tiles((uint32_t)L.G), block(VKMR_SORT_THREADS);
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_TRY(hipMemsetAsync(info_dev, 0, 4 * sizeof(uint64_t), S(s)));
+    VKMR_TRY(hipMemsetAsync(sc.hdr, 0, 4 * sizeof(uint64_t), S(s)));
+    VKMR_CHECK(trees_dev ? launch(forest_sort_keys_kernel, lanes, dim3(256), S(s), offsets_dev, ntrees, cells, trees_dev, indices_dev, k, sc.key[0], sc.val[0], info)
+                         : launch(tree_sort_keys_kernel, lanes, dim3(256), S(s), cells, indices_dev, k, sc.key[0], sc.val[0], info));
+    for (uint32_t p = 0; p < passes; ++p) {   // pass p from buffer p & 1 into the other, which the previous launches are done with
+        const uint32_t in = vkmr_sort::pass_input(p), out = in ^ 1u;
+        VKMR_CHECK(launch(sort_histogram_kernel, tiles, block, S(s), sc.key[in], k, p, L.G, sc.hist));
+        VKMR_CHECK(launch(sort_scan_kernel, dim3(VKMR_SORT_BINS), block, S(s), sc.hist, L.G, sc.totals));
+        VKMR_CHECK(launch(sort_scatter_kernel, tiles, block, S(s), sc.key[in], sc.val[in], k, p, L.G, sc.hist, sc.totals, sc.key[out], sc.val[out]));
+    }
+    const uint32_t at = vkmr_sort::result_buffer(cells);
+    VKMR_CHECK(launch(sort_flags_kernel, lanes, dim3(256), S(s), sc.key[at], k, cells, L.words, sc.mask));
+    const dim3 wgrid((uint32_t)L.blocks, 1), wblock(VKMR_MP_BLOCK_WORDS);
+    VKMR_CHECK(launch(multiproof_block_sums_kernel, wgrid, wblock, S(s), sc.mask, L.words, L.blocks, sc.block));
+    VKMR_CHECK(launch(multiproof_block_starts_kernel, dim3(1), dim3(256), S(s), sc.block, L.blocks, 1u, ~0ull, 0u, sc.hdr));
+    VKMR_CHECK(launch(multiproof_word_starts_kernel, wgrid, wblock, S(s), sc.mask, L.words, L.blocks, sc.block, sc.hdr, sc.word_start));
+    if (trees_dev)
+        return launch(forest_sort_emit_kernel, lanes, dim3(256), S(s), offsets_dev, ntrees, sc.key[at], sc.val[at], k, sc.mask, sc.word_start, sc.hdr,
+                      trees_out_dev, indices_out_dev, order_out_dev, info_dev);
+    return launch(tree_sort_emit_kernel, lanes, dim3(256), S(s), sc.key[at], sc.val[at], k, sc.mask, sc.word_start, sc.hdr, indices_out_dev, order_out_dev, info_dev);
+}
+
+vkmr_status vkmr_hip_forest_sort_entries_async(int dev, vkmr_stream s, uint64_t total, const uint64_t* offsets_dev, uint32_t ntrees,
+                                               const uint32_t* trees_dev, const uint64_t* indices_dev, uint32_t k, void* scratch_dev,
+                                               uint32_t* trees_out_dev, uint64_t* indices_out_dev, uint32_t* order_out_dev, uint64_t* info_dev)
+{
+    if (k == 0) return VKMR_OK;
+    if (!trees_dev || !indices_dev || !scratch_dev || !trees_out_dev || !indices_out_dev || !order_out_dev || !info_dev || (ntrees > 0 && !offsets_dev))
+        return refuse(__func__, "null pointer");
+    // no tree: the kernels read no offset and every entry is a marker or outside; the launches stay those of (total, k)
+    return sort_launch(__func__, dev, s, total, offsets_dev, ntrees, trees_dev, indices_dev, k, scratch_dev, trees_out_dev, indices_out_dev,
+                       order_out_dev, info_dev);
+}
+
+vkmr_status vkmr_hip_tree_sort_entries_async(int dev, vkmr_stream s, uint64_t count, const uint64_t* indices_dev, uint32_t k, void* scratch_dev,
+                                             uint64_t* indices_out_dev, uint32_t* order_out_dev, uint64_t* info_dev)
+{
+    if (k == 0) return VKMR_OK;
+    if (!indices_dev || !scratch_dev || !indices_out_dev || !order_out_dev || !info_dev) return refuse(__func__, "null pointer");
+    return sort_launch(__func__, dev, s, count, nullptr, 0, nullptr, indices_dev, k, scratch_dev, nullptr, indices_out_dev, order_out_dev, info_dev);
+}
+
+vkmr_status vkmr_hip_gather_digests_async(int dev, vkmr_stream s, const vkmr_digest* src_dev, const uint32_t* order_dev, uint32_t n,
+                                          vkmr_digest* dst_dev)
+{
+    if (n == 0) return VKMR_OK;
+    if (!src_dev || !order_dev || !dst_dev) return refuse(__func__, "null pointer");
+    VKMR_TRY(hipSetDevice(dev));
+    return launch(gather_digests_kernel, grid_of(n), dim3(256), S(s), nodes(src_dev), order_dev, n, nodes(dst_dev));
 }
 
 // ---- combine --------------------------------------------------------------------

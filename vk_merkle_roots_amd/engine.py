@@ -599,6 +599,36 @@ class HipDevice:
                                                 queries_buf.ptr if queries_buf else None, k, scratch_buf.ptr if scratch_buf else None,
                                                 indices_buf.ptr if indices_buf else None), "vkmr_hip_tree_find_async")
 
+    # -- leaf entries sorted and deduplicated on the device: find -> update, find -> multiproof -----
+    def sort_entries_scratch_bytes(self, total, k):
+        return self.lib.vkmr_hip_sort_entries_scratch_bytes(total, k)
+
+    def forest_sort_entries_async(self, total, offsets_buf, ntrees, trees_buf, indices_buf, k, scratch_buf, trees_out_buf, indices_out_buf,
+                                  order_out_buf, info_buf, stream=None):
+        """The k entries (trees_buf[q], indices_buf[q]), in any order, as the distinct valid pairs in strictly increasing order
+        in cells [0, n) of trees_out_buf / indices_out_buf, order_out_buf[j] (uint32) the last q that holds pair j; info_buf:
+        4 uint64 = n, "not found" markers, entries out of range, earlier repeats.  All in device memory; scratch_buf:
+        sort_entries_scratch_bytes(total, k), 16-byte aligned.  include/vkmr_hip.h."""
+        check(self.lib.vkmr_hip_forest_sort_entries_async(self.index, stream or self.stream, total, offsets_buf.ptr if offsets_buf else None, ntrees,
+                                                          trees_buf.ptr if trees_buf else None, indices_buf.ptr if indices_buf else None, k,
+                                                          scratch_buf.ptr if scratch_buf else None, trees_out_buf.ptr if trees_out_buf else None,
+                                                          indices_out_buf.ptr if indices_out_buf else None,
+                                                          order_out_buf.ptr if order_out_buf else None, info_buf.ptr if info_buf else None),
+              "vkmr_hip_forest_sort_entries_async")
+
+    def tree_sort_entries_async(self, count, indices_buf, k, scratch_buf, indices_out_buf, order_out_buf, info_buf, stream=None):
+        """forest_sort_entries_async for one tree of `count` leaves: indices alone, the marker being 2^64 - 1."""
+        check(self.lib.vkmr_hip_tree_sort_entries_async(self.index, stream or self.stream, count, indices_buf.ptr if indices_buf else None, k,
+                                                        scratch_buf.ptr if scratch_buf else None, indices_out_buf.ptr if indices_out_buf else None,
+                                                        order_out_buf.ptr if order_out_buf else None, info_buf.ptr if info_buf else None),
+              "vkmr_hip_tree_sort_entries_async")
+
+    def gather_digests_async(self, src_buf, order_buf, n, dst_buf, stream=None):
+        """dst_buf[j] = src_buf[order_buf[j]], j < n: digests of 32 bytes, order uint32, all in device memory."""
+        check(self.lib.vkmr_hip_gather_digests_async(self.index, stream or self.stream, src_buf.ptr if src_buf else None,
+                                                     order_buf.ptr if order_buf else None, n, dst_buf.ptr if dst_buf else None),
+              "vkmr_hip_gather_digests_async")
+
     def reduce_scratch(self, count, levels_variant=False):
         fn = self.lib.vkmr_hip_reduce_levels_scratch_bytes if levels_variant else self.lib.vkmr_hip_reduce_scratch_bytes
         return self.alloc(fn(count))
@@ -633,6 +663,28 @@ class HipDevice:
             d_in, d_scratch, d_root = tmp.upload(digests), tmp.keep(self.reduce_scratch(count, levels_variant)), tmp.alloc(32)
             self.reduce_async(d_in, count, height, d_scratch, d_root, levels_variant=levels_variant)
             return self.download(d_root, 32)
+
+
+class _SortedEntries:
+    """The buffers of one device sort of k entries, in the scope `tmp`: the sorted pairs (trees only for a forest), the
+    order, and the four counters once read()."""
+
+    def __init__(self, dev, tmp, total, k, forest):
+        self.dev, self.k = dev, k
+        self.scratch = tmp.alloc(dev.sort_entries_scratch_bytes(total, k))
+        self.trees = tmp.alloc(4 * k) if forest else None
+        self.indices, self.order, self.info = tmp.alloc(8 * k), tmp.alloc(4 * k), tmp.alloc(32)
+
+    def read(self):
+        """(n, not found, out of range, repeats): the one read-back of a sort, 32 bytes."""
+        return tuple(int(x) for x in self.dev.download(self.info, 32, dtype=np.uint64))
+
+
+def _digest_pairs(old_digests, new_digests, what):
+    old, new = _host(old_digests, np.uint32, -1, 8), _host(new_digests, np.uint32, -1, 8)
+    if old.shape[0] != new.shape[0]:
+        raise ValueError(f"{what}: one new digest per old digest")
+    return old, new
 
 
 class Multiproof:
@@ -844,6 +896,82 @@ class MerkleTree:
             if idx.shape[0]:      # map's entries are independent: the strings in sorted-index order
                 self._apply(tmp, idx, self.dev.map_packed(tmp, batch, meta=np.ascontiguousarray(batch.meta[pos])))
 
+    def sort_entries_async(self, indices_buf, k, scratch_buf, indices_out_buf, order_out_buf, info_buf, stream=None):
+        """The k indices in device memory, in any order, sorted and deduplicated for update_async / multiproof_async:
+        HipDevice.tree_sort_entries_async with this tree's count; scratch_buf of dev.sort_entries_scratch_bytes(count, k)."""
+        self.dev.tree_sort_entries_async(self.count, indices_buf, k, scratch_buf, indices_out_buf, order_out_buf, info_buf, stream=stream)
+
+    def update_entries(self, indices_buf, leaves_buf, k):
+        """Set leaf indices[q] to leaves[q], q < k, both in DEVICE memory and in any order: sorted and deduplicated on the
+        device (a repeated index takes its last value, NOT_FOUND markers are left out), the leaves gathered into that order,
+        the tree updated; only the sort's 32 bytes of counters come back.  (applied, not_found, repeats).  IndexError when an
+        index is >= count (and no marker), before anything of the tree changes."""
+        k = int(k)
+        if k <= 0:
+            return 0, 0, 0
+        with self.dev.scope() as tmp:
+            se = _SortedEntries(self.dev, tmp, self.count, k, forest=False)
+            self.sort_entries_async(indices_buf, k, se.scratch, se.indices, se.order, se.info)
+            n, missing, outside, repeats = se.read()
+            if outside:
+                raise IndexError(f"update_entries: {outside} indices outside [0, {self.count})")
+            if n:
+                d_leaves, d_status = tmp.alloc(32 * n), tmp.alloc(4)
+                self.dev.gather_digests_async(leaves_buf, se.order, n, d_leaves)
+                self.update_async(se.indices, d_leaves, n, d_status)
+                status = int(self.dev.download(d_status, 4)[0])
+                if status:
+                    raise RuntimeError(f"MerkleTree.update_entries: the device refused its own sorted indices (status {status})")
+            return n, missing, repeats
+
+    def replace(self, old_digests, new_digests):
+        """The leaves that hold old_digests[q] become new_digests[q] (host arrays [k, 8]): find -> sort -> gather -> update on
+        the device, no position and no digest coming back.  (replaced, missing): leaves written, and old digests that are no
+        leaf.  Two equal old digests take the last new value.  A digest held by several leaves replaces the LOWEST index only:
+        that is find's rule."""
+        old, new = _digest_pairs(old_digests, new_digests, "replace")
+        k = int(old.shape[0])
+        if k == 0:
+            return 0, 0
+        with self.dev.scope() as tmp:
+            d_old, d_new, d_scr, d_idx = tmp.upload(old), tmp.upload(new), tmp.alloc(self.dev.find_scratch_bytes(k)), tmp.alloc(8 * k)
+            self.find_async(d_old, k, d_scr, d_idx)
+            applied, missing, _ = self.update_entries(d_idx, d_new, k)
+            return applied, missing
+
+    def multiproof_of(self, digests):
+        """(Multiproof, order): ONE proof for the leaves that hold `digests` (a host array [k, 8]): find -> sort -> multiproof on
+        the device.  digests[order[j]] is the leaf of entry j; digests that are no leaf are left out, repeats count once.
+        ValueError when none is found."""
+        q = _host(digests, np.uint32, -1, 8)
+        k = int(q.shape[0])
+        if k == 0:
+            raise ValueError("multiproof_of: no digest")
+        lib = self.dev.lib
+        with self.dev.scope() as tmp:
+            n = 0
+            if k:
+                d_q, d_scr, d_idx = tmp.upload(q), tmp.alloc(self.dev.find_scratch_bytes(k)), tmp.alloc(8 * k)
+                se = _SortedEntries(self.dev, tmp, self.count, k, forest=False)
+                self.find_async(d_q, k, d_scr, d_idx)
+                self.sort_entries_async(d_idx, k, se.scratch, se.indices, se.order, se.info)
+                n = se.read()[0]
+            if n == 0:
+                raise ValueError("multiproof_of: none of the digests is a leaf")
+            cap = lib.vkmr_hip_multiproof_max_nodes(self.count, self.height, n)
+            d_mp = tmp.alloc(lib.vkmr_hip_multiproof_scratch_bytes(n, self.height)) if self.height else None
+            d_nodes = tmp.alloc(32 * cap) if cap else None
+            d_info = tmp.alloc(8 * (2 + self.height))
+            self.multiproof_async(se.indices, n, d_mp, d_nodes, cap, d_info)
+            info = self.dev.download(d_info, 8 * (2 + self.height), dtype=np.uint64)
+            if int(info[0]):
+                raise RuntimeError(f"MerkleTree.multiproof_of: the device refused its own sorted indices (status {int(info[0])})")
+            m = int(info[1]) if self.height else 0
+            nodes = self.dev.download(d_nodes, 32 * m).reshape(m, 8) if m else np.zeros((0, 8), dtype=np.uint32)
+            idx = self.dev.download(se.indices, 8 * n, dtype=np.uint64)
+            order = self.dev.download(se.order, 4 * n)
+        return Multiproof(idx, nodes, info[2:].copy(), self.height), order
+
     def free(self):
         if self.tree:
             self.tree.free()
@@ -1032,6 +1160,86 @@ class MerkleForest:
         with self.dev.scope() as tmp:
             if si.shape[0]:      # map's entries are independent: the strings in sorted-entry order
                 self._apply(tmp, st, si, self.dev.map_packed(tmp, batch, meta=np.ascontiguousarray(batch.meta[pos])))
+
+    def sort_entries_async(self, trees_buf, indices_buf, k, scratch_buf, trees_out_buf, indices_out_buf, order_out_buf, info_buf, stream=None):
+        """The k (tree, index) entries in device memory, in any order -- find_async's outputs as they are -- sorted and
+        deduplicated for update_async / multiproof_async: HipDevice.forest_sort_entries_async with this forest's offsets;
+        scratch_buf of dev.sort_entries_scratch_bytes(total, k)."""
+        self.dev.forest_sort_entries_async(self.total, self.offsets, self.ntrees, trees_buf, indices_buf, k, scratch_buf, trees_out_buf,
+                                           indices_out_buf, order_out_buf, info_buf, stream=stream)
+
+    def update_entries(self, trees_buf, indices_buf, leaves_buf, k):
+        """Set leaf indices[q] of tree trees[q] to leaves[q], q < k, all three in DEVICE memory and in any order: sorted and
+        deduplicated on the device (a repeated pair takes its last value, find's NO_TREE markers are left out), the leaves
+        gathered into that order, the forest updated; only the sort's 32 bytes of counters come back.  (applied, not_found,
+        repeats).  IndexError when an entry is out of range (and no marker), before anything of the forest changes."""
+        k = int(k)
+        if k <= 0:
+            return 0, 0, 0
+        with self.dev.scope() as tmp:
+            se = _SortedEntries(self.dev, tmp, self.total, k, forest=True)
+            self.sort_entries_async(trees_buf, indices_buf, k, se.scratch, se.trees, se.indices, se.order, se.info)
+            n, missing, outside, repeats = se.read()
+            if outside:
+                raise IndexError(f"update_entries: {outside} entries name a tree outside the forest or an index outside its tree")
+            if n:
+                d_leaves, d_status = tmp.alloc(32 * n), tmp.alloc(4)
+                self.dev.gather_digests_async(leaves_buf, se.order, n, d_leaves)
+                self.update_async(se.trees, se.indices, d_leaves, n, d_status)
+                status = int(self.dev.download(d_status, 4)[0])
+                if status:
+                    raise RuntimeError(f"MerkleForest.update_entries: the device refused its own sorted entries "
+                                       f"(status {status}: {forest_update_status_text(status)})")
+            return n, missing, repeats
+
+    def replace(self, old_digests, new_digests):
+        """The leaves that hold old_digests[q] become new_digests[q] (host arrays [k, 8]): find -> sort -> gather -> update on
+        the device, no position and no digest coming back.  (replaced, missing): leaves written, and old digests that are no
+        leaf.  Two equal old digests take the last new value.  A digest held by several leaves replaces the LOWEST position
+        of the forest only: that is find's rule."""
+        old, new = _digest_pairs(old_digests, new_digests, "replace")
+        k = int(old.shape[0])
+        if k == 0:
+            return 0, 0
+        with self.dev.scope() as tmp:
+            d_old, d_new, d_scr = tmp.upload(old), tmp.upload(new), tmp.alloc(self.dev.find_scratch_bytes(k))
+            d_trees, d_idx = tmp.alloc(4 * k), tmp.alloc(8 * k)
+            self.find_async(d_old, k, d_scr, d_trees, d_idx)
+            applied, missing, _ = self.update_entries(d_trees, d_idx, d_new, k)
+            return applied, missing
+
+    def multiproof_of(self, digests):
+        """(ForestMultiproof, order): ONE proof for the leaves that hold `digests` (a host array [k, 8]): find -> sort ->
+        multiproof on the device.  digests[order[j]] is the leaf of entry j; digests that are no leaf are left out, repeats
+        count once.  ValueError when none is found."""
+        q = _host(digests, np.uint32, -1, 8)
+        k = int(q.shape[0])
+        if k == 0:
+            raise ValueError("multiproof_of: no digest")
+        lib = self.dev.lib
+        with self.dev.scope() as tmp:
+            n = 0
+            if k:
+                d_q, d_scr, d_trees, d_idx = tmp.upload(q), tmp.alloc(self.dev.find_scratch_bytes(k)), tmp.alloc(4 * k), tmp.alloc(8 * k)
+                se = _SortedEntries(self.dev, tmp, self.total, k, forest=True)
+                self.find_async(d_q, k, d_scr, d_trees, d_idx)
+                self.sort_entries_async(d_trees, d_idx, k, se.scratch, se.trees, se.indices, se.order, se.info)
+                n = se.read()[0]
+            if n == 0:
+                raise ValueError("multiproof_of: none of the digests is a leaf")
+            cap = lib.vkmr_hip_forest_multiproof_max_nodes(self.total, self.ntrees, self.max_count, n)
+            d_mp = tmp.alloc(lib.vkmr_hip_forest_multiproof_scratch_bytes(n, self.levels))
+            d_nodes, d_h, d_info = tmp.alloc(32 * cap), tmp.alloc(4 * n), tmp.alloc(8 * (2 + self.levels))
+            self.multiproof_async(se.trees, se.indices, n, d_mp, d_nodes, cap, d_h, d_info)
+            info = self.dev.download(d_info, 8 * (2 + self.levels), dtype=np.uint64)
+            if int(info[0]):
+                raise RuntimeError(f"MerkleForest.multiproof_of: the device refused its own sorted entries "
+                                   f"(status {int(info[0])}: {forest_multiproof_status_text(int(info[0]))})")
+            m = int(info[1])
+            nodes = self.dev.download(d_nodes, 32 * m).reshape(m, 8) if m else np.zeros((0, 8), dtype=np.uint32)
+            st, si = self.dev.download(se.trees, 4 * n), self.dev.download(se.indices, 8 * n, dtype=np.uint64)
+            heights, order = self.dev.download(d_h, 4 * n), self.dev.download(se.order, 4 * n)
+        return ForestMultiproof(st, si, heights, nodes, info[2:].copy(), self.levels), order
 
     def free(self):
         for b in [self.forest, self.roots_buf, self.offsets] + self._owned:
