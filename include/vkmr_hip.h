@@ -660,6 +660,76 @@ VKMR_API vkmr_status vkmr_hip_gather_digests_async(int dev, vkmr_stream s, const
                                                    uint32_t n, vkmr_digest* dst_dev);
 
 /*
+ * DIFF TWO STORED FORESTS ("which leaves differ?"; the reference has no counterpart): two replicas of one shape -- a node and
+ * its snapshot, a primary and a follower, a state before and after a batch -- and the leaves in which they differ, found from
+ * the roots down.  A (digests_a_dev, forest_a_dev, roots_a_dev) and B (digests_b_dev, forest_b_dev, roots_b_dev) are two
+ * stored forests built by vkmr_hip_reduce_forest_tree_async (or its flagged twin), and kept by vkmr_hip_forest_update_async,
+ * over the SAME offsets_dev, total, ntrees and max_count, both with status 0; the call TRUSTS this as
+ * vkmr_hip_forest_proofs_async trusts its offsets.  The answer is every (t, i) with i < c_t whose leaf differs between A and B
+ * on any of the 32 bytes, as strictly increasing pairs in cells [0, n) of trees_out_dev (uint32) and indices_out_dev (uint64)
+ * -- exactly what vkmr_hip_forest_update_async and vkmr_hip_forest_multiproof_async take -- and, when leaves_b_out_dev is not
+ * NULL, B's leaf at each of those positions in cells [0, n) of it: diff -> update of A with k = n makes A equal to B, diff ->
+ * multiproof on B proves exactly what changed.  Cells of the leaves outside [offsets[0], offsets[ntrees]) are no leaves and are
+ * never compared; cells of a level buffer that are no node of a tree ("STORED FOREST": unspecified) are never read.
+ * The walk is a descent, never a scan of level 0.  Step 0 compares roots_a[t] with roots_b[t]; the frontier is the trees whose
+ * roots differ, each as node 0 of its level h_t = max(1, ceil(log2 c_t)) (an empty tree never enters).  Steps 1..H, H the
+ * forest's stride: an entry (t, p) at level l >= 1 compares the children 2p and 2p + 1 of p, nodes of tree t's level l - 1, in
+ * both forests and emits each differing child, in child order; node 2p + 1 exists only below ceil(c_t / 2^(l - 1)), so the
+ * duplicated last node of an odd level is no second child; an entry already at level 0 (a tree shorter than H) is carried
+ * forward.  Emission keeps order, so the frontier is sorted by (t, p) at every step and after step H it is the answer: no
+ * sort follows and the result does not depend on scheduling.  The work and the traffic are those of the changed paths (at
+ * most 128 bytes per compared node), not of the forest.  Two facts the call relies on: in consistent forests a differing node
+ * has a differing child, so the frontier never shrinks on the way down and is at most n at every step -- a frontier that
+ * outgrows `capacity` at any step proves n > capacity, and the call stops there; and EQUAL NODES ARE TAKEN TO COVER EQUAL
+ * LEAVES (anything else is a SHA-256d collision) -- both sides having the same counts, the duplicate-last ambiguity of
+ * CVE-2012-2459 (two leaf lists of different length under one root) does not arise.
+ *   capacity   cells of each output; 0 is legal, the outputs may then be NULL: identical forests give n = 0, anything else bit 2
+ *   info_dev   4 uint64_t of device memory, always written when ntrees > 0:
+ *     [0] status: 0 done; bit 2 (value 4): more than `capacity` leaves differ -- the outputs are then unspecified, nothing
+ *         outside their `capacity` cells is touched, and [1] is the size of the frontier that overflowed, a lower bound of n
+ *     [1] n
+ *     [2] the trees whose roots differ
+ *     [3] the nodes whose children were compared: for a completed call exactly the distinct ancestors (t, l, i >> l),
+ *         1 <= l <= h_t, of the differing leaves -- the descent visited the changed paths and nothing else
+ *   scratch_dev  vkmr_hip_diff_scratch_bytes(capacity) bytes of device memory, 16-byte aligned (layout: csrc/diff_plan.hpp:
+ *                two ping-pong frontiers of 12 bytes an entry, two mask bits per entry, their ranking words, a header)
+ * Cells [0, n) of the outputs hold the answer, cells at and behind n are unspecified; the outputs must not overlap the inputs
+ * or the scratch.  n stays on the device: the caller reads info_dev back (32 bytes) before the update or multiproof that
+ * takes it as k, as with vkmr_hip_forest_sort_entries_async.
+ * Launches, all on the caller's stream: one memset; step 0 is a count of differing roots per workgroup, one ranking launch
+ * and the emit; every later step the mask (one lane per frontier entry), the three ranking launches of
+ * vkmr_hip_forest_multiproof_async with one level, and the emit -- the last one writes the outputs and info_dev.  The grids
+ * are sized from min(capacity, the nodes that far below the roots), so the top steps launch a handful of lanes.  The launches
+ * are a function of (total, ntrees, max_count, capacity) alone; no allocation, no host synchronisation, no host read of device
+ * data; no kernel waits for another workgroup, and no entry is appended through a counter in memory.
+ * ntrees == 0 does nothing.  Refused on the host (VKMR_ERR_INVALID) with ntrees > 0, before any HIP call: a NULL pointer that
+ * is needed (the leaves when total > 0, both forests, both roots, the offsets, the scratch, info_dev, the two entry outputs
+ * when capacity > 0), max_count == 0, total above 2^58, scratch_dev not 16-byte aligned.
+ * Stream-ordered: a diff enqueued behind an update on the same stream sees the updated forest.
+ */
+VKMR_API size_t vkmr_hip_diff_scratch_bytes(uint32_t capacity);
+VKMR_API vkmr_status vkmr_hip_forest_diff_async(int dev, vkmr_stream s, const vkmr_digest* digests_a_dev,
+                                                const vkmr_digest* forest_a_dev, const vkmr_digest* roots_a_dev,
+                                                const vkmr_digest* digests_b_dev, const vkmr_digest* forest_b_dev,
+                                                const vkmr_digest* roots_b_dev, uint64_t total, const uint64_t* offsets_dev,
+                                                uint32_t ntrees, uint64_t max_count, void* scratch_dev, uint32_t* trees_out_dev,
+                                                uint64_t* indices_out_dev, vkmr_digest* leaves_b_out_dev, uint32_t capacity,
+                                                uint64_t* info_dev);
+/*
+ * The same for two stored TREES (vkmr_hip_reduce_tree_async) of one `count` and `height`: the root is the last cell of the
+ * tree buffer (the leaf itself for height 0), every entry is in tree 0 and indices_out_dev alone carries the answer; info_dev[2]
+ * is 1 when the roots differ.  Same scratch, counters and launches (step 0 is one lane); H = height, which may be above the
+ * count's own, as everywhere.  count == 0 does nothing.  Refused on the host: a NULL pointer that is needed (the tree buffers
+ * only when height > 0), a height that does not reduce count to one node -- as vkmr_hip_tree_proofs_async refuses it --, count
+ * above 2^58, scratch_dev not 16-byte aligned.
+ */
+VKMR_API vkmr_status vkmr_hip_tree_diff_async(int dev, vkmr_stream s, const vkmr_digest* digests_a_dev,
+                                              const vkmr_digest* tree_a_dev, const vkmr_digest* digests_b_dev,
+                                              const vkmr_digest* tree_b_dev, uint64_t count, uint32_t height, void* scratch_dev,
+                                              uint64_t* indices_out_dev, vkmr_digest* leaves_b_out_dev, uint32_t capacity,
+                                              uint64_t* info_dev);
+
+/*
  * COMBINE: duplicate-last Merkle root over n >= 1 slice roots given in slice order, always
  * at least one level -- the rule of CpuSha256D::Root that the reference applies to the slice
  * roots on the CPU (CpuSha256DforReductions, src/vkmr/Reductions.cpp:56-69, :703-712).  Here

@@ -17,6 +17,8 @@
 #                          the host, and the sort alone beside torch.sort (one JSON line), then the same run under rocprofv3
 #                          --kernel-trace --stats; stops at the first failing step
 #   find [args]            tools/find_timing.py: the lookup by digest beside a read-only pass of torch's over as many bytes (one JSON line)
+#   diff [args]            tools/diff_timing.py: the diff of two stored forests beside torch's compare of the two level-0 buffers, and
+#                          sync_from beside a rebuild (one JSON line)
 #   cumask                 tools/cu_mask_probe.py: where CU-mask bits land, map/reduce on half the CUs with and without neighbours
 #   issue <set>            tools/issue_patterns (python3 tools/gen_issue_patterns.py <set> and a build beforehand)
 #   proofs                 tools/proof_timing.py: a slice reduced with and without proofs written in the pass
@@ -162,6 +164,11 @@ find)
   timeout -k 10 500 python3 tools/find_timing.py "$@" --out $OUT/find_timing.json > /dev/null 2> $OUT/find_timing.err && echo "find_timing ok" &&
   cat $OUT/find_timing.json
   echo "find rc=$?"
+  ;;
+diff)
+  timeout -k 10 500 python3 tools/diff_timing.py "$@" --out $OUT/diff_timing.json > /dev/null 2> $OUT/diff_timing.err && echo "diff_timing ok" &&
+  cat $OUT/diff_timing.json
+  echo "diff rc=$?"
   ;;
 cumask)
   hipcc --offload-arch=gfx950 -O2 -shared -fPIC -o tools/libwhere.so tools/where.hip

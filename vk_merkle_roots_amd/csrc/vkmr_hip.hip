@@ -25,6 +25,9 @@
 //   sort_kernels.hpp    *_sort_keys_kernel, sort_histogram_kernel, sort_scan_kernel, sort_scatter_kernel, sort_flags_kernel, *_sort_emit_kernel,
 //                                              gather_digests_kernel   leaf entries sorted and deduplicated: a stable LSD radix sort of
 //                                              (flat position, q) pairs, the last of every run kept (sizes: sort_plan.hpp)
+//   diff_kernels.hpp    *_diff_roots_count_kernel, *_diff_roots_emit_kernel, *_diff_mask_kernel, *_diff_emit_kernel   the leaves that differ
+//                                              between two stored forests or trees of one shape: a descent from the roots, the frontier
+//                                              ranked by the multiproof's ranking kernels at every step (steps and sizes: diff_plan.hpp)
 //   sha256d_device.hpp  the SHA-256 round / compression building blocks, and the tree's: hash_parent, node_diff, store_node
 //   merkle_math.hpp     the integer rules, no HIP types (ceil_shift, height, right_child, sibling): shared with host/ and tests/c
 //   meta_kernels.hpp    sizes_*_kernel         metadata entries from 16-bit sizes   (Batches.cpp:64-121)
@@ -36,6 +39,7 @@
 //   forest_plan.hpp     where a forest's nodes lie, level by level; its scratch, stored size and multiproof node bound
 //   find_plan.hpp       the lookup's scratch layout and scan grid
 //   sort_plan.hpp       the entry sort's passes, tiles, histogram words and scratch layout
+//   diff_plan.hpp       one step of a diff's descent, the bound on every step's frontier and the scratch layout
 //
 // Host side: plain launches on the caller's stream, each through launch() and so each checked; every argument refusal
 // through refuse(__func__, why); no allocation, no sync inside the *_async entry points.
@@ -67,6 +71,7 @@ using vkmr_dev::Node;
 #include "forest_tree_kernels.hpp"
 #include "find_kernels.hpp"
 #include "sort_kernels.hpp"
+#include "diff_kernels.hpp"
 
 // ============================================================================
 // C ABI
@@ -1322,6 +1327,121 @@ vkmr_status vkmr_hip_gather_digests_async(int dev, vkmr_stream s, const vkmr_dig
     if (!src_dev || !order_dev || !dst_dev) return refuse(__func__, "null pointer");
     VKMR_TRY(hipSetDevice(dev));
     return launch(gather_digests_kernel, grid_of(n), dim3(256), S(s), nodes(src_dev), order_dev, n, nodes(dst_dev));
+}
+
+// ---- the leaves that differ between two stored forests or trees (diff_kernels.hpp, diff_plan.hpp) ----------------------------
+
+static_assert(VKMR_DIFF_RANK_BLOCK_WORDS == VKMR_MP_BLOCK_WORDS, "the frontier is ranked by the multiproof's ranking kernels");
+static_assert(VKMR_DIFF_HEADER_WORDS >= 2 + 1 + 2, "the ranking's header of one level, then the diff's two counters");
+
+size_t vkmr_hip_diff_scratch_bytes(uint32_t capacity) { return vkmr_diff::scratch_bytes(capacity); }
+
+// The parts of a diff's scratch_dev (diff_plan.hpp) as the kernels take them.
+struct DiffScratch {
+    uint64_t *node[2], *mask, *word_start, *block, *hdr;
+    uint32_t* tree[2];
+    DiffScratch(void* scratch_dev, const vkmr_diff::Layout& L)
+    {
+        char* at = static_cast<char*>(scratch_dev);
+        for (int b = 0; b < 2; ++b) {
+            node[b] = reinterpret_cast<uint64_t*>(at + L.node[b]);
+            tree[b] = reinterpret_cast<uint32_t*>(at + L.tree[b]);
+        }
+        mask = reinterpret_cast<uint64_t*>(at + L.mask);
+        word_start = reinterpret_cast<uint64_t*>(at + L.word_start);
+        block = reinterpret_cast<uint64_t*>(at + L.block);
+        hdr = reinterpret_cast<uint64_t*>(at + L.hdr);
+    }
+};
+
+// The ranking of one step's mask words: the multiproof's three launches with one level; more than `capacity` set bits is
+// status bit 2, and everything behind reads the status first.
+static vkmr_status diff_rank_launch(hipStream_t stream, const DiffScratch& sc, uint64_t words, uint32_t capacity)
+{
+    const uint64_t blocks = vkmr_diff::rank_blocks(words);
+    const dim3 wgrid((uint32_t)blocks, 1), wblock(VKMR_MP_BLOCK_WORDS);
+    VKMR_CHECK(launch(multiproof_block_sums_kernel, wgrid, wblock, stream, sc.mask, words, blocks, sc.block));
+    VKMR_CHECK(launch(multiproof_block_starts_kernel, dim3(1), dim3(256), stream, sc.block, blocks, 1u, (uint64_t)capacity, 0u, sc.hdr));
+    return launch(multiproof_word_starts_kernel, wgrid, wblock, stream, sc.mask, words, blocks, sc.block, sc.hdr, sc.word_start);
+}
+
+vkmr_status vkmr_hip_forest_diff_async(int dev, vkmr_stream s, const vkmr_digest* digests_a_dev, const vkmr_digest* forest_a_dev,
+                                       const vkmr_digest* roots_a_dev, const vkmr_digest* digests_b_dev, const vkmr_digest* forest_b_dev,
+                                       const vkmr_digest* roots_b_dev, uint64_t total, const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count,
+                                       void* scratch_dev, uint32_t* trees_out_dev, uint64_t* indices_out_dev, vkmr_digest* leaves_b_out_dev,
+                                       uint32_t capacity, uint64_t* info_dev)
+{
+    if (ntrees == 0) return VKMR_OK;
+    if (((!digests_a_dev || !digests_b_dev) && total > 0) || !forest_a_dev || !forest_b_dev || !roots_a_dev || !roots_b_dev || !offsets_dev ||
+        !scratch_dev || !info_dev || ((!trees_out_dev || !indices_out_dev) && capacity > 0))
+        return refuse(__func__, "null pointer");
+    VKMR_CHECK(forest_args_check(__func__, total, ntrees, max_count, 0, nullptr, scratch_dev));
+    const uint32_t H = vkmr_forest::launches(total, max_count);   // <= 58
+    const ForestLevels lv = forest_levels(total, ntrees, H);
+    const DiffScratch sc(scratch_dev, vkmr_diff::layout(capacity));
+    const uint32_t steps = (capacity == 0 || total == 0) ? 0u : H;   // no room for an entry, or no leaf to differ: step 0 alone
+    const dim3 roots(vkmr_diff::root_groups(ntrees)), block(VKMR_DIFF_THREADS);
+    const uint64_t span = vkmr_diff::root_span(ntrees);
+    const Node *da = nodes(digests_a_dev), *fa = nodes(forest_a_dev), *db = nodes(digests_b_dev), *fb = nodes(forest_b_dev);
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_TRY(hipMemsetAsync(sc.hdr, 0, VKMR_DIFF_HEADER_WORDS * sizeof(uint64_t), S(s)));
+    VKMR_CHECK(launch(forest_diff_roots_count_kernel, roots, block, S(s), nodes(roots_a_dev), nodes(roots_b_dev), offsets_dev, ntrees, span, sc.block));
+    VKMR_CHECK(launch(multiproof_block_starts_kernel, dim3(1), dim3(256), S(s), sc.block, (uint64_t)roots.x, 1u, (uint64_t)capacity, 0u, sc.hdr));
+    VKMR_CHECK(launch(forest_diff_roots_emit_kernel, roots, block, S(s), nodes(roots_a_dev), nodes(roots_b_dev), offsets_dev, ntrees, span, sc.block, sc.hdr,
+                      sc.tree[0], sc.node[0], info_dev, steps == 0 ? 1u : 0u));
+    for (uint32_t step = 1; step <= steps; ++step) {   // frontier (step - 1) & 1 into the other, or into the outputs at the end
+        const uint32_t in = (step - 1u) & 1u, out = in ^ 1u;
+        const bool last = step == steps;
+        const uint64_t bound = vkmr_diff::forest_frontier_bound(total, ntrees, capacity, step);   // >= 1
+        const uint64_t words = vkmr_diff::mask_words(bound);
+        VKMR_CHECK(launch(forest_diff_mask_kernel, grid_of(bound), block, S(s), da, fa, db, fb, lv, offsets_dev, ntrees, sc.tree[in], sc.node[in], step, words,
+                          sc.hdr, sc.mask));
+        VKMR_CHECK(diff_rank_launch(S(s), sc, words, capacity));
+        VKMR_CHECK(launch(forest_diff_emit_kernel, grid_of(bound), block, S(s), db, offsets_dev, ntrees, sc.tree[in], sc.node[in], step, bound, sc.mask,
+                          sc.word_start, sc.hdr, last ? trees_out_dev : sc.tree[out], last ? indices_out_dev : sc.node[out],
+                          last ? nodes(leaves_b_out_dev) : (Node*)nullptr, info_dev, last ? 1u : 0u));
+    }
+    return VKMR_OK;
+}
+
+vkmr_status vkmr_hip_tree_diff_async(int dev, vkmr_stream s, const vkmr_digest* digests_a_dev, const vkmr_digest* tree_a_dev,
+                                     const vkmr_digest* digests_b_dev, const vkmr_digest* tree_b_dev, uint64_t count, uint32_t height, void* scratch_dev,
+                                     uint64_t* indices_out_dev, vkmr_digest* leaves_b_out_dev, uint32_t capacity, uint64_t* info_dev)
+{
+    if (count == 0) return VKMR_OK;
+    if (!digests_a_dev || !digests_b_dev || (height > 0 && (!tree_a_dev || !tree_b_dev)) || !scratch_dev || !info_dev ||
+        (!indices_out_dev && capacity > 0))
+        return refuse(__func__, "null pointer");
+    if (!height_ok(count, height)) return refuse(__func__, "height does not reduce count to one node");
+    if (count > vkmr_diff::MAX_TOTAL) return refuse(__func__, "too many leaves");
+    if (reinterpret_cast<uintptr_t>(scratch_dev) & 15u) return refuse(__func__, "scratch must be 16-byte aligned");
+    const TreeLevels lv = tree_levels(count, height);
+    const DiffScratch sc(scratch_dev, vkmr_diff::layout(capacity));
+    const uint32_t steps = capacity == 0 ? 0u : height;
+    const dim3 block(VKMR_DIFF_THREADS);
+    const Node *da = nodes(digests_a_dev), *ta = nodes(tree_a_dev), *db = nodes(digests_b_dev), *tb = nodes(tree_b_dev);
+    const uint64_t root_cell = lv.off[height];         // level `height` is one cell; height 0: the leaf, and this is not used
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_TRY(hipMemsetAsync(sc.hdr, 0, VKMR_DIFF_HEADER_WORDS * sizeof(uint64_t), S(s)));
+    VKMR_CHECK(launch(tree_diff_roots_count_kernel, dim3(1), block, S(s), da, ta, db, tb, count, height, root_cell, sc.block));
+    VKMR_CHECK(launch(multiproof_block_starts_kernel, dim3(1), dim3(256), S(s), sc.block, 1ull, 1u, (uint64_t)capacity, 0u, sc.hdr));
+    // a tree of one leaf without a level: the root is the leaf, and step 0 writes the answer
+    const bool leaf = height == 0 && capacity > 0;
+    VKMR_CHECK(launch(tree_diff_roots_emit_kernel, dim3(1), block, S(s), da, ta, db, tb, count, height, root_cell, sc.block, sc.hdr,
+                      leaf ? indices_out_dev : sc.node[0], leaf ? nodes(leaves_b_out_dev) : (Node*)nullptr, info_dev, steps == 0 ? 1u : 0u));
+    for (uint32_t step = 1; step <= steps; ++step) {
+        const uint32_t in = (step - 1u) & 1u, out = in ^ 1u;
+        const bool last = step == steps;
+        const uint32_t l = vkmr_diff::level_at(height, step);
+        const uint64_t bound = vkmr_diff::tree_frontier_bound(count, height, capacity, step);      // >= 1
+        const uint64_t words = vkmr_diff::mask_words(bound);
+        VKMR_CHECK(launch(tree_diff_mask_kernel, grid_of(bound), block, S(s), da, ta, db, tb, count, height, vkmr_diff::tree_child_base(lv.off, l), sc.node[in],
+                          step, words, sc.hdr, sc.mask));
+        VKMR_CHECK(diff_rank_launch(S(s), sc, words, capacity));
+        VKMR_CHECK(launch(tree_diff_emit_kernel, grid_of(bound), block, S(s), db, sc.node[in], step, bound, sc.mask, sc.word_start, sc.hdr,
+                          last ? indices_out_dev : sc.node[out], last ? nodes(leaves_b_out_dev) : (Node*)nullptr, info_dev, last ? 1u : 0u));
+    }
+    return VKMR_OK;
 }
 
 // ---- combine --------------------------------------------------------------------

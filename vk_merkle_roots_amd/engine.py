@@ -629,6 +629,30 @@ class HipDevice:
                                                      order_buf.ptr if order_buf else None, n, dst_buf.ptr if dst_buf else None),
               "vkmr_hip_gather_digests_async")
 
+    # -- two stored forests or trees of one shape: the leaves that differ, found from the roots down -----
+    def diff_scratch_bytes(self, capacity):
+        return self.lib.vkmr_hip_diff_scratch_bytes(capacity)
+
+    def forest_diff_async(self, digests_a_buf, forest_a_buf, roots_a_buf, digests_b_buf, forest_b_buf, roots_b_buf, total, offsets_buf, ntrees,
+                          max_count, scratch_buf, trees_buf, indices_buf, leaves_buf, capacity, info_buf, stream=None):
+        """Cells [0, n) of trees_buf / indices_buf = the (tree, index) pairs, strictly increasing, of the leaves in which the
+        stored forests A and B (same offsets, total, ntrees, max_count) differ; leaves_buf (or None): B's leaves there.
+        info_buf: 4 uint64 = status (bit 2: more than `capacity` differ), n, trees whose roots differ, nodes whose children
+        were compared.  All in device memory; scratch_buf: diff_scratch_bytes(capacity), 16-byte aligned.  include/vkmr_hip.h."""
+        p = lambda b: b.ptr if b else None     # noqa: E731
+        check(self.lib.vkmr_hip_forest_diff_async(self.index, stream or self.stream, p(digests_a_buf), p(forest_a_buf), p(roots_a_buf),
+                                                  p(digests_b_buf), p(forest_b_buf), p(roots_b_buf), total, p(offsets_buf), ntrees, max_count,
+                                                  p(scratch_buf), p(trees_buf), p(indices_buf), p(leaves_buf), capacity, p(info_buf)),
+              "vkmr_hip_forest_diff_async")
+
+    def tree_diff_async(self, digests_a_buf, tree_a_buf, digests_b_buf, tree_b_buf, count, height, scratch_buf, indices_buf, leaves_buf, capacity,
+                        info_buf, stream=None):
+        """forest_diff_async for two stored trees of one `count` and `height`: indices alone."""
+        p = lambda b: b.ptr if b else None     # noqa: E731
+        check(self.lib.vkmr_hip_tree_diff_async(self.index, stream or self.stream, p(digests_a_buf), p(tree_a_buf), p(digests_b_buf), p(tree_b_buf),
+                                                count, height, p(scratch_buf), p(indices_buf), p(leaves_buf), capacity, p(info_buf)),
+              "vkmr_hip_tree_diff_async")
+
     def reduce_scratch(self, count, levels_variant=False):
         fn = self.lib.vkmr_hip_reduce_levels_scratch_bytes if levels_variant else self.lib.vkmr_hip_reduce_scratch_bytes
         return self.alloc(fn(count))
@@ -678,6 +702,44 @@ class _SortedEntries:
     def read(self):
         """(n, not found, out of range, repeats): the one read-back of a sort, 32 bytes."""
         return tuple(int(x) for x in self.dev.download(self.info, 32, dtype=np.uint64))
+
+
+DIFF_FIRST_CAPACITY = 65536      # diff(capacity=None) starts here and grows DIFF_GROWTH-fold while more leaves differ
+DIFF_GROWTH = 16
+DIFF_MAX_CAPACITY = 2**32 - 1
+
+
+class DiffOverflow(RuntimeError):
+    """More leaves differ than the capacity a diff was given."""
+
+
+def _run_diff(dev, tmp, call, cells, capacity, forest, leaves, what):
+    """One diff in the scope `tmp`: call(scratch, trees, indices, leaves, capacity, info) enqueues it, the 32 bytes of info
+    are read back.  (n, trees buffer or None, indices buffer, leaves buffer or None).  capacity None: from
+    min(cells, DIFF_FIRST_CAPACITY), DIFF_GROWTH times more while the device reports more, up to `cells`; an integer:
+    DiffOverflow when more leaves differ."""
+    grow = capacity is None
+    cap = min(cells, DIFF_FIRST_CAPACITY) if grow else int(capacity)
+    if not 0 <= cap <= DIFF_MAX_CAPACITY:
+        raise ValueError(f"{what}: capacity outside [0, 2^32)")
+    while True:
+        d_scr, d_info = tmp.alloc(dev.diff_scratch_bytes(cap)), tmp.alloc(32)
+        d_trees = tmp.alloc(4 * cap) if forest and cap else None
+        d_idx = tmp.alloc(8 * cap) if cap else None
+        d_leaves = tmp.alloc(32 * cap) if leaves and cap else None
+        call(d_scr, d_trees, d_idx, d_leaves, cap, d_info)
+        status, n = (int(x) for x in dev.download(d_info, 32, dtype=np.uint64)[:2])
+        if status == 0:
+            return n, d_trees, d_idx, d_leaves
+        if status != 4:
+            raise RuntimeError(f"{what}: the device reports status {status}")
+        if not grow or cap >= min(cells, DIFF_MAX_CAPACITY):
+            raise DiffOverflow(f"{what}: more than {cap} leaves differ (a frontier of {n} on the way down)")
+        for b in (d_scr, d_info, d_trees, d_idx, d_leaves):
+            if b:
+                b.free()
+                tmp.release(b)
+        cap = min(cells, DIFF_MAX_CAPACITY, cap * DIFF_GROWTH)
 
 
 def _digest_pairs(old_digests, new_digests, what):
@@ -972,6 +1034,50 @@ class MerkleTree:
             order = self.dev.download(se.order, 4 * n)
         return Multiproof(idx, nodes, info[2:].copy(), self.height), order
 
+    def _same_shape(self, other, what):
+        """ValueError unless `other` is a MerkleTree of this tree's device, count and height; no device call."""
+        if not isinstance(other, MerkleTree):
+            raise ValueError(f"{what}: the other side is no MerkleTree")
+        if other.dev.index != self.dev.index:
+            raise ValueError(f"{what}: the trees live on devices {self.dev.index} and {other.dev.index}")
+        if other.count != self.count or other.height != self.height:
+            raise ValueError(f"{what}: a tree of {self.count} leaves and height {self.height} against one of {other.count} and {other.height}")
+
+    def diff_async(self, other, scratch_buf, indices_buf, leaves_buf, capacity, info_buf, stream=None):
+        """Cells [0, n) of indices_buf = the strictly increasing indices of the leaves in which this tree (A) and `other` (B,
+        same count and height) differ, found from the roots down; leaves_buf (or None): B's leaves there; info_buf: 4 uint64
+        (status, n, roots differing, nodes compared).  Device memory throughout, scratch_buf of dev.diff_scratch_bytes(capacity)
+        bytes; ordered on `stream` behind earlier updates of either tree.  include/vkmr_hip.h."""
+        self._same_shape(other, "diff_async")
+        self.dev.tree_diff_async(self.digests, self.tree, other.digests, other.tree, self.count, self.height, scratch_buf, indices_buf, leaves_buf,
+                                 capacity, info_buf, stream=stream)
+
+    def _diff(self, tmp, other, capacity, leaves, what):
+        self._same_shape(other, what)
+        return _run_diff(self.dev, tmp, lambda scr, _, idx, lv, cap, info: self.diff_async(other, scr, idx, lv, cap, info), self.count, capacity,
+                         False, leaves, what)
+
+    def diff(self, other, capacity=None):
+        """uint64 [n]: the indices, increasing, of the leaves in which this tree and `other` differ.  capacity None: room for
+        min(count, 65536) answers first, 16 times more while more differ; an integer: DiffOverflow when more differ.
+        ValueError for a tree of another device, count or height, before any device call."""
+        with self.dev.scope() as tmp:
+            n, _, d_idx, _ = self._diff(tmp, other, capacity, False, "diff")
+            return self.dev.download(d_idx, 8 * n, dtype=np.uint64) if n else np.zeros(0, dtype=np.uint64)
+
+    def sync_from(self, other):
+        """Make this tree equal to `other`: the diff with other's leaves at the differing positions, then the update of
+        exactly those, all on the device; the 32 bytes of counters are what comes back.  The number of leaves written."""
+        with self.dev.scope() as tmp:
+            n, _, d_idx, d_leaves = self._diff(tmp, other, None, True, "sync_from")
+            if n:
+                d_status = tmp.alloc(4)
+                self.update_async(d_idx, d_leaves, n, d_status)
+                status = int(self.dev.download(d_status, 4)[0])
+                if status:
+                    raise RuntimeError(f"MerkleTree.sync_from: the device refused the diff's own indices (status {status})")
+            return n
+
     def free(self):
         if self.tree:
             self.tree.free()
@@ -1240,6 +1346,59 @@ class MerkleForest:
             st, si = self.dev.download(se.trees, 4 * n), self.dev.download(se.indices, 8 * n, dtype=np.uint64)
             heights, order = self.dev.download(d_h, 4 * n), self.dev.download(se.order, 4 * n)
         return ForestMultiproof(st, si, heights, nodes, info[2:].copy(), self.levels), order
+
+    def _same_shape(self, other, what):
+        """ValueError unless `other` is a MerkleForest of this forest's device, counts, cells and max_count; no device call."""
+        if not isinstance(other, MerkleForest):
+            raise ValueError(f"{what}: the other side is no MerkleForest")
+        if other.dev.index != self.dev.index:
+            raise ValueError(f"{what}: the forests live on devices {self.dev.index} and {other.dev.index}")
+        if other.ntrees != self.ntrees or other.total != self.total or not np.array_equal(other.counts, self.counts):
+            raise ValueError(f"{what}: the forests do not have the same counts")
+        if other.max_count != self.max_count:
+            raise ValueError(f"{what}: max_count {self.max_count} against {other.max_count}")
+
+    def diff_async(self, other, scratch_buf, trees_buf, indices_buf, leaves_buf, capacity, info_buf, stream=None):
+        """Cells [0, n) of trees_buf / indices_buf = the strictly increasing (tree, index) pairs of the leaves in which this
+        forest (A) and `other` (B, same counts and max_count, laid out at the same offsets) differ, found from the roots down --
+        what update_async and multiproof_async take; leaves_buf (or None): B's leaves there; info_buf: 4 uint64 (status, n,
+        trees whose roots differ, nodes compared).  Device memory throughout, scratch_buf of dev.diff_scratch_bytes(capacity)
+        bytes; ordered on `stream` behind earlier updates of either forest.  include/vkmr_hip.h."""
+        self._same_shape(other, "diff_async")
+        self.dev.forest_diff_async(self.digests, self.forest, self.roots_buf, other.digests, other.forest, other.roots_buf, self.total, self.offsets,
+                                   self.ntrees, self.max_count, scratch_buf, trees_buf, indices_buf, leaves_buf, capacity, info_buf, stream=stream)
+
+    def _diff(self, tmp, other, capacity, leaves, what):
+        self._same_shape(other, what)
+        if self.ntrees == 0:                      # the call does nothing and writes no counters
+            return 0, None, None, None
+        return _run_diff(self.dev, tmp, lambda scr, t, idx, lv, cap, info: self.diff_async(other, scr, t, idx, lv, cap, info), self.total, capacity,
+                         True, leaves, what)
+
+    def diff(self, other, capacity=None):
+        """(trees uint32 [n], indices uint64 [n]): the leaves in which this forest and `other` differ, as strictly increasing
+        (tree, index) pairs.  capacity None: room for min(total, 65536) answers first, 16 times more while more differ; an
+        integer: DiffOverflow when more differ.  ValueError for a forest of another device, other counts or another max_count,
+        before any device call."""
+        with self.dev.scope() as tmp:
+            n, d_trees, d_idx, _ = self._diff(tmp, other, capacity, False, "diff")
+            if n == 0:
+                return np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint64)
+            return self.dev.download(d_trees, 4 * n), self.dev.download(d_idx, 8 * n, dtype=np.uint64)
+
+    def sync_from(self, other):
+        """Make this forest equal to `other`: the diff with other's leaves at the differing positions, then the update of
+        exactly those, all on the device; the 32 bytes of counters are what comes back.  The number of leaves written."""
+        with self.dev.scope() as tmp:
+            n, d_trees, d_idx, d_leaves = self._diff(tmp, other, None, True, "sync_from")
+            if n:
+                d_status = tmp.alloc(4)
+                self.update_async(d_trees, d_idx, d_leaves, n, d_status)
+                status = int(self.dev.download(d_status, 4)[0])
+                if status:
+                    raise RuntimeError(f"MerkleForest.sync_from: the device refused the diff's own entries "
+                                       f"(status {status}: {forest_update_status_text(status)})")
+            return n
 
     def free(self):
         for b in [self.forest, self.roots_buf, self.offsets] + self._owned:
