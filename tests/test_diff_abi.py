@@ -8,6 +8,7 @@ import pytest
 
 import diff_cases as dc
 import merkle_model
+from no_device import NoDeviceAt as NoDevice
 
 NEW = {"vkmr_hip_diff_scratch_bytes": 1, "vkmr_hip_forest_diff_async": 18, "vkmr_hip_tree_diff_async": 13}
 
@@ -119,17 +120,6 @@ def test_the_tree_call_refuses_bad_arguments_before_any_hip_call(native):
         assert fn(0, None, *args) == _abi.ERR_INVALID, i
     # no leaf: nothing to do, whatever the rest
     assert fn(0, None, None, None, None, None, 0, 99, None, None, None, 7, None) == _abi.OK
-
-
-class NoDevice:
-    """Stands where a HipDevice would: any device call is an AttributeError."""
-
-    def __init__(self, index):
-        self.index = index
-
-    def scope(self):
-        from vk_merkle_roots_amd import engine
-        return engine.BufferScope(self)
 
 
 def test_the_python_layer_refuses_other_shapes_before_any_device_call():

@@ -17,6 +17,7 @@ import forest_multiproof_cases as fm
 import multiproof_cases as mc
 from conftest import ROOT
 from merkle_model import random_counts
+from no_device import NoDevice
 
 ENTRY_POINTS = ("vkmr_hip_forest_multiproof_max_nodes", "vkmr_hip_forest_multiproof_scratch_bytes", "vkmr_hip_forest_multiproof_async",
                 "vkmr_hip_verify_forest_multiproof_async")
@@ -340,13 +341,6 @@ def test_the_product_s_split_equals_the_restatement_s(native):
             assert (got[t].indices == idx).all() and (got[t].nodes == mine).all() and [int(x) for x in got[t].level_counts] == per_level
     with pytest.raises(ValueError):        # a proof that lost a node cannot be regrouped
         vk.ForestMultiproof(trees, indices, heights, nodes[:-1], None, stride).split()
-
-
-class NoDevice:
-    """Any attribute access is a device call: the host-side checks must raise before one."""
-
-    def __getattr__(self, name):
-        raise AssertionError(f"device touched: {name}")
 
 
 def test_multiproof_refuses_bad_entries_before_any_device_call(native):

@@ -14,6 +14,7 @@ import forest_cases as fc
 import forest_update_cases as fu
 from conftest import ROOT
 from merkle_model import random_counts
+from no_device import NoDevice
 
 NAME = "vkmr_hip_forest_update_async"
 
@@ -58,13 +59,6 @@ def test_bad_arguments_are_refused_before_any_hip_call(native):
     assert lib.vkmr_hip_forest_update_async(0, None, None, None, 100, None, 4, 50, None, None, None, 0, None, None) == _abi.OK
     assert lib.vkmr_hip_forest_update_async(0, None, None, None, 0, None, 0, 0, None, None, None, 0, None, None) == _abi.OK
     assert lib.vkmr_hip_forest_update_async(0, None, d, d, (1 << 58) + 1, d, 4, 0, d, d, d, 0, d, d) == _abi.OK
-
-
-class NoDevice:
-    """Any attribute access is a device call: the host-side checks must raise before one."""
-
-    def __getattr__(self, name):
-        raise AssertionError(f"device touched: {name}")
 
 
 COUNTS = [4, 0, 0, 7, 0, 0, 0, 1]          # fc.CASES["empty_adjacent"]

@@ -10,6 +10,7 @@ import pytest
 
 import multiproof_cases as mc
 from conftest import ROOT
+from no_device import NoDevice
 
 ENTRY_POINTS = ("vkmr_hip_multiproof_max_nodes", "vkmr_hip_multiproof_scratch_bytes", "vkmr_hip_tree_multiproof_async",
                 "vkmr_hip_verify_multiproof_async")
@@ -126,13 +127,6 @@ def test_host_verifier_refuses_bad_arguments(native):
     z = np.zeros((1, 8), np.uint32)
     assert not mc.host_verify(z[:0], [], 3, z[:0], z[0])          # no leaf proves nothing
     assert not mc.host_verify(z, [0], 64, z[:0], z[0])
-
-
-class NoDevice:
-    """Any attribute access is a device call: the host-side checks must raise before one."""
-
-    def __getattr__(self, name):
-        raise AssertionError(f"device touched: {name}")
 
 
 def host_tree(count=10, height=4):

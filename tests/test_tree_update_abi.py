@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from conftest import ROOT
+from no_device import NoDevice
 
 
 def test_header_declares_the_update_and_the_stub_binds_it():
@@ -37,13 +38,6 @@ def test_bad_arguments_are_refused_before_any_hip_call(native):
     # k == 0 is a no-op whatever the rest
     assert lib.vkmr_hip_tree_update_async(0, None, None, None, 8, 3, None, None, 0, None) == _abi.OK
     assert lib.vkmr_hip_tree_update_async(0, None, None, None, 0, 64, None, None, 0, None) == _abi.OK
-
-
-class NoDevice:
-    """Any attribute access is a device call: the host-side checks must raise before one."""
-
-    def __getattr__(self, name):
-        raise AssertionError(f"device touched: {name}")
 
 
 def host_tree(count=10, height=4):

@@ -194,6 +194,11 @@ class HipDevice:
         self.stream = s.value
 
     # -- plumbing -----------------------------------------------------------------
+    def _call(self, name, *args, stream=None):
+        """The C function `name` on this device and `stream` (the device's own when None): a buffer goes as its pointer,
+        None as NULL, an integer as it is.  VkmrError, naming the function, when the ABI refuses the call."""
+        check(getattr(self.lib, name)(self.index, stream or self.stream, *[getattr(a, "ptr", a) for a in args]), name)
+
     def name(self):
         buf = C.create_string_buffer(256)
         check(self.lib.vkmr_hip_device_name(self.index, buf, 256), "vkmr_hip_device_name")
@@ -210,21 +215,19 @@ class HipDevice:
         arr = np.ascontiguousarray(arr)
         buf = DeviceBuffer(self, arr.nbytes)
         if arr.nbytes:
-            check(self.lib.vkmr_hip_memcpy_h2d_async(self.index, stream or self.stream, buf.ptr, arr.ctypes.data, arr.nbytes),
-                  "vkmr_hip_memcpy_h2d_async")
+            self._call("vkmr_hip_memcpy_h2d_async", buf, arr.ctypes.data, arr.nbytes, stream=stream)
             self.sync(stream)
         return buf
 
     def download(self, buf, nbytes, dtype=np.uint32, offset=0, stream=None):
         out = np.empty(nbytes // np.dtype(dtype).itemsize, dtype=dtype)
         if nbytes:
-            check(self.lib.vkmr_hip_memcpy_d2h_async(self.index, stream or self.stream, out.ctypes.data, buf.at(offset), nbytes),
-                  "vkmr_hip_memcpy_d2h_async")
+            self._call("vkmr_hip_memcpy_d2h_async", out.ctypes.data, buf.at(offset), nbytes, stream=stream)
             self.sync(stream)
         return out
 
     def sync(self, stream=None):
-        check(self.lib.vkmr_hip_stream_sync(self.index, stream or self.stream), "vkmr_hip_stream_sync")
+        self._call("vkmr_hip_stream_sync", stream=stream)
 
     def new_stream(self):
         s = C.c_void_p()
@@ -234,8 +237,7 @@ class HipDevice:
     def warm_up(self, kernels=True, copy_bytes=1 << 20, stream=None):
         """vkmr_hip_warm_up: the kernels loaded onto the device, the copy engine up -- what a caller does at start-up
         instead of inside its first copy and first launch (the reference builds its pipelines then: Devices.cpp:225-280)."""
-        what = (1 if kernels else 0) | (2 if copy_bytes else 0)
-        check(self.lib.vkmr_hip_warm_up(self.index, stream or self.stream, what, copy_bytes or 0), "vkmr_hip_warm_up")
+        self._call("vkmr_hip_warm_up", (1 if kernels else 0) | (2 if copy_bytes else 0), copy_bytes or 0, stream=stream)
 
     def new_event(self):
         e = C.c_void_p()
@@ -255,9 +257,7 @@ class HipDevice:
 
     # -- the hot path -------------------------------------------------------------
     def map_async(self, data_buf, data_words, meta_buf, count, out_buf, out_offset_digests=0, meta_offset=0, stream=None):
-        check(self.lib.vkmr_hip_map_async(self.index, stream or self.stream, data_buf.ptr, data_words,
-                                          meta_buf.at(8 * meta_offset), count, out_buf.at(32 * out_offset_digests)),
-              "vkmr_hip_map_async")
+        self._call("vkmr_hip_map_async", data_buf, data_words, meta_buf.at(8 * meta_offset), count, out_buf.at(32 * out_offset_digests), stream=stream)
 
     def map_packed(self, tmp, batch, out_buf=None, out_offset_digests=0, meta=None):
         """The strings of `batch` (those of `meta`, rows of batch.meta, when given) mapped to leaf digests in device memory:
@@ -272,22 +272,17 @@ class HipDevice:
         return out
 
     def reduce_async(self, digests_buf, count, height, scratch_buf, root_buf, root_index=0, levels_variant=False, stream=None):
-        fn = self.lib.vkmr_hip_reduce_levels_async if levels_variant else self.lib.vkmr_hip_reduce_async
-        check(fn(self.index, stream or self.stream, digests_buf.ptr, count, height, scratch_buf.ptr if scratch_buf else None,
-                 root_buf.at(32 * root_index)),
-              "vkmr_hip_reduce_async")
+        self._call("vkmr_hip_reduce_levels_async" if levels_variant else "vkmr_hip_reduce_async", digests_buf, count, height, scratch_buf,
+                   root_buf.at(32 * root_index), stream=stream)
 
     def reduce_slices_async(self, digests_buf, nslices, capacity, count_last, height, scratch_buf, roots_buf, stream=None):
-        check(self.lib.vkmr_hip_reduce_slices_async(self.index, stream or self.stream, digests_buf.ptr, nslices, capacity, count_last,
-                                                    height, scratch_buf.ptr if scratch_buf else None, roots_buf.ptr),
-              "vkmr_hip_reduce_slices_async")
+        self._call("vkmr_hip_reduce_slices_async", digests_buf, nslices, capacity, count_last, height, scratch_buf, roots_buf, stream=stream)
 
     def proof(self, digests_buf, count, height, index):
         """(siblings [height, 8], root [8]) of leaf `index` in the tree reduce_async(count, height) computes."""
         with self.scope() as tmp:
             d_sib, d_root, d_scratch = tmp.alloc(32 * max(height, 1)), tmp.alloc(32), tmp.keep(self.reduce_scratch(count))
-            check(self.lib.vkmr_hip_proof_async(self.index, self.stream, digests_buf.ptr, count, height, index, d_scratch.ptr, d_sib.ptr,
-                                                d_root.ptr), "vkmr_hip_proof_async")
+            self._call("vkmr_hip_proof_async", digests_buf, count, height, index, d_scratch, d_sib, d_root)
             sib = self.download(d_sib, 32 * height).reshape(-1, 8) if height else np.zeros((0, 8), np.uint32)
             return sib, self.download(d_root, 32)
 
@@ -298,8 +293,7 @@ class HipDevice:
         k = int(idx.shape[0])
         with self.scope() as tmp:
             d_sib, d_root, d_scratch = tmp.alloc(32 * max(height, 1) * max(k, 1)), tmp.alloc(32), tmp.keep(self.reduce_scratch(count))
-            check(self.lib.vkmr_hip_reduce_proofs_async(self.index, self.stream, digests_buf.ptr, count, height, d_scratch.ptr, d_root.ptr,
-                                                        idx.ctypes.data if k else None, k, d_sib.ptr), "vkmr_hip_reduce_proofs_async")
+            self._call("vkmr_hip_reduce_proofs_async", digests_buf, count, height, d_scratch, d_root, idx.ctypes.data if k else None, k, d_sib)
             sib = self.download(d_sib, 32 * height * k).reshape(k, height, 8) if height and k else np.zeros((k, height, 8), np.uint32)
             return sib, self.download(d_root, 32)
 
@@ -308,33 +302,24 @@ class HipDevice:
         return self.lib.vkmr_hip_tree_bytes(count, height)
 
     def reduce_tree_async(self, digests_buf, count, height, tree_buf, stream=None):
-        check(self.lib.vkmr_hip_reduce_tree_async(self.index, stream or self.stream, digests_buf.ptr, count, height,
-                                                  tree_buf.ptr if tree_buf else None), "vkmr_hip_reduce_tree_async")
+        self._call("vkmr_hip_reduce_tree_async", digests_buf, count, height, tree_buf, stream=stream)
 
     def tree_proofs_async(self, digests_buf, tree_buf, count, height, indices_buf, k, siblings_buf, stream=None):
-        check(self.lib.vkmr_hip_tree_proofs_async(self.index, stream or self.stream, digests_buf.ptr, tree_buf.ptr if tree_buf else None,
-                                                  count, height, indices_buf.ptr, k, siblings_buf.ptr), "vkmr_hip_tree_proofs_async")
+        self._call("vkmr_hip_tree_proofs_async", digests_buf, tree_buf, count, height, indices_buf, k, siblings_buf, stream=stream)
 
     def verify_proofs_async(self, leaves_buf, indices_buf, siblings_buf, k, height, roots_buf, nroots, ok_buf, stream=None):
-        check(self.lib.vkmr_hip_verify_proofs_async(self.index, stream or self.stream, leaves_buf.ptr, indices_buf.ptr, siblings_buf.ptr, k,
-                                                    height, roots_buf.ptr, nroots, ok_buf.ptr), "vkmr_hip_verify_proofs_async")
+        self._call("vkmr_hip_verify_proofs_async", leaves_buf, indices_buf, siblings_buf, k, height, roots_buf, nroots, ok_buf, stream=stream)
 
     def tree_update_async(self, digests_buf, tree_buf, count, height, indices_buf, leaves_buf, k, status_buf, stream=None):
-        check(self.lib.vkmr_hip_tree_update_async(self.index, stream or self.stream, digests_buf.ptr, tree_buf.ptr if tree_buf else None,
-                                                  count, height, indices_buf.ptr, leaves_buf.ptr, k, status_buf.ptr),
-              "vkmr_hip_tree_update_async")
+        self._call("vkmr_hip_tree_update_async", digests_buf, tree_buf, count, height, indices_buf, leaves_buf, k, status_buf, stream=stream)
 
     def tree_multiproof_async(self, digests_buf, tree_buf, count, height, indices_buf, k, scratch_buf, nodes_buf, nodes_capacity, info_buf,
                               stream=None):
-        check(self.lib.vkmr_hip_tree_multiproof_async(self.index, stream or self.stream, digests_buf.ptr, tree_buf.ptr if tree_buf else None,
-                                                      count, height, indices_buf.ptr, k, scratch_buf.ptr if scratch_buf else None,
-                                                      nodes_buf.ptr if nodes_buf else None, nodes_capacity, info_buf.ptr),
-              "vkmr_hip_tree_multiproof_async")
+        self._call("vkmr_hip_tree_multiproof_async", digests_buf, tree_buf, count, height, indices_buf, k, scratch_buf, nodes_buf, nodes_capacity,
+                   info_buf, stream=stream)
 
     def verify_multiproof_async(self, leaves_buf, indices_buf, k, height, nodes_buf, m, root_buf, scratch_buf, ok_buf, stream=None):
-        check(self.lib.vkmr_hip_verify_multiproof_async(self.index, stream or self.stream, leaves_buf.ptr, indices_buf.ptr, k, height,
-                                                        nodes_buf.ptr if nodes_buf else None, m, root_buf.ptr, scratch_buf.ptr, ok_buf.ptr),
-              "vkmr_hip_verify_multiproof_async")
+        self._call("vkmr_hip_verify_multiproof_async", leaves_buf, indices_buf, k, height, nodes_buf, m, root_buf, scratch_buf, ok_buf, stream=stream)
 
     def verify_multiproof(self, leaves, indices, nodes, root, height):
         """bool: the multiproof `nodes` ([M, 8]) proves leaves ([k, 8]) at `indices` ([k], strictly increasing) under `root`
@@ -377,18 +362,12 @@ class HipDevice:
 
     # -- forest: the roots of many trees of unequal size in one call ----------------------
     def reduce_forest_async(self, digests_buf, total, offsets_buf, ntrees, max_count, scratch_buf, roots_buf, status_buf, stream=None):
-        check(self.lib.vkmr_hip_reduce_forest_async(self.index, stream or self.stream, digests_buf.ptr if digests_buf else None, total,
-                                                    offsets_buf.ptr if offsets_buf else None, ntrees, max_count,
-                                                    scratch_buf.ptr if scratch_buf else None, roots_buf.ptr if roots_buf else None,
-                                                    status_buf.ptr if status_buf else None), "vkmr_hip_reduce_forest_async")
+        self._call("vkmr_hip_reduce_forest_async", digests_buf, total, offsets_buf, ntrees, max_count, scratch_buf, roots_buf, status_buf, stream=stream)
 
     def reduce_forest_mutated_async(self, digests_buf, total, offsets_buf, ntrees, max_count, scratch_buf, roots_buf, mutated_buf, status_buf,
                                     stream=None):
-        check(self.lib.vkmr_hip_reduce_forest_mutated_async(self.index, stream or self.stream, digests_buf.ptr if digests_buf else None, total,
-                                                            offsets_buf.ptr if offsets_buf else None, ntrees, max_count,
-                                                            scratch_buf.ptr if scratch_buf else None, roots_buf.ptr if roots_buf else None,
-                                                            mutated_buf.ptr if mutated_buf else None,
-                                                            status_buf.ptr if status_buf else None), "vkmr_hip_reduce_forest_mutated_async")
+        self._call("vkmr_hip_reduce_forest_mutated_async", digests_buf, total, offsets_buf, ntrees, max_count, scratch_buf, roots_buf, mutated_buf,
+                   status_buf, stream=stream)
 
     def _reduce_forest(self, tmp, d_leaves, total, offsets, ntrees, max_count, what, stored, d_mutated=None):
         """One forest call over checked offsets (ntrees >= 1), its buffers in the scope `tmp`: the roots alone, or with
@@ -397,117 +376,87 @@ class HipDevice:
         if max_count is None:
             max_count = max(1, int(np.diff(offsets).max()))
         d_off, d_roots, d_status = tmp.upload(offsets), tmp.alloc(32 * ntrees), tmp.alloc(4)
-        if stored:
-            d_levels = tmp.alloc(self.forest_tree_bytes(total, ntrees, max_count))
-            if d_mutated:
-                self.reduce_forest_tree_mutated_async(d_leaves, total, d_off, ntrees, max_count, d_levels, d_roots, d_mutated, d_status)
-            else:
-                self.reduce_forest_tree_async(d_leaves, total, d_off, ntrees, max_count, d_levels, d_roots, d_status)
-        elif d_mutated:
-            d_levels = tmp.alloc(self.lib.vkmr_hip_forest_scratch_bytes(total, ntrees))
-            self.reduce_forest_mutated_async(d_leaves, total, d_off, ntrees, max_count, d_levels, d_roots, d_mutated, d_status)
-        else:
-            d_levels = tmp.alloc(self.lib.vkmr_hip_forest_scratch_bytes(total, ntrees))
-            self.reduce_forest_async(d_leaves, total, d_off, ntrees, max_count, d_levels, d_roots, d_status)
+        build = {(False, False): self.reduce_forest_async, (False, True): self.reduce_forest_mutated_async,
+                 (True, False): self.reduce_forest_tree_async, (True, True): self.reduce_forest_tree_mutated_async}[stored, bool(d_mutated)]
+        d_levels = tmp.alloc(self.forest_tree_bytes(total, ntrees, max_count) if stored else self.lib.vkmr_hip_forest_scratch_bytes(total, ntrees))
+        build(d_leaves, total, d_off, ntrees, max_count, d_levels, d_roots, *([d_mutated] if d_mutated else []), d_status)
         status = int(self.download(d_status, 4)[0])
         if status:
             raise ValueError(f"{what}: the device refused the forest (status {status}: {forest_status_text(status)})")
         return max_count, d_off, d_levels, d_roots
 
-    def _forest_of_buffer(self, d_leaves, total, counts, max_count, what):
-        """[ntrees, 8] uint32: the roots of the trees of `counts` leaves each over the `total` cells of d_leaves."""
+    def _forest_of_buffer(self, d_leaves, total, counts, max_count, what, mutated=False):
+        """[ntrees, 8] uint32: the roots of the trees of `counts` leaves each over the `total` cells of d_leaves; with
+        `mutated` from the flagged build, and (roots, masks [ntrees] uint64)."""
         offsets, ntrees = _checked_offsets(counts, total, what)
         if ntrees == 0:
-            return np.zeros((0, 8), dtype=np.uint32)
+            roots, masks = np.zeros((0, 8), dtype=np.uint32), np.zeros(0, dtype=np.uint64)
+            return (roots, masks) if mutated else roots
         with self.scope() as tmp:
-            d_roots = self._reduce_forest(tmp, d_leaves, total, offsets, ntrees, max_count, what, stored=False)[3]
-            return self.download(d_roots, 32 * ntrees).reshape(ntrees, 8)
+            d_mut = tmp.alloc(8 * ntrees) if mutated else None
+            d_roots = self._reduce_forest(tmp, d_leaves, total, offsets, ntrees, max_count, what, stored=False, d_mutated=d_mut)[3]
+            roots = self.download(d_roots, 32 * ntrees).reshape(ntrees, 8)
+            return (roots, self.download(d_mut, 8 * ntrees, dtype=np.uint64)) if mutated else roots
+
+    def _forest_of_digests(self, digests, counts, max_count, what, mutated):
+        digests = _host(digests, np.uint32, -1, 8)
+        total = int(digests.shape[0])
+        with self.scope() as tmp:
+            return self._forest_of_buffer(tmp.upload(digests) if total else None, total, counts, max_count, what, mutated=mutated)
 
     def forest_roots(self, digests, counts, max_count=None):
         """[ntrees, 8] uint32: the root of every tree of a forest (vkmr_hip_reduce_forest_async).  `digests` [total, 8] holds the
         leaves of all trees back to back, tree t the next counts[t] of them; an empty tree gets an all-zero root.  max_count:
         an upper bound on every count (the largest count when None).  ValueError when the counts do not add up to the
         leaves, or when the device refuses the forest (a count above max_count)."""
-        digests = _host(digests, np.uint32, -1, 8)
-        total = int(digests.shape[0])
-        with self.scope() as tmp:
-            return self._forest_of_buffer(tmp.upload(digests) if total else None, total, counts, max_count, "forest_roots")
-
-    def _forest_mutated_of_buffer(self, d_leaves, total, counts, max_count, what):
-        """(roots [ntrees, 8] uint32, masks [ntrees] uint64) of the trees of `counts` leaves each over the `total` cells of d_leaves."""
-        offsets, ntrees = _checked_offsets(counts, total, what)
-        if ntrees == 0:
-            return np.zeros((0, 8), dtype=np.uint32), np.zeros(0, dtype=np.uint64)
-        with self.scope() as tmp:
-            d_mut = tmp.alloc(8 * ntrees)
-            d_roots = self._reduce_forest(tmp, d_leaves, total, offsets, ntrees, max_count, what, stored=False, d_mutated=d_mut)[3]
-            return self.download(d_roots, 32 * ntrees).reshape(ntrees, 8), self.download(d_mut, 8 * ntrees, dtype=np.uint64)
+        return self._forest_of_digests(digests, counts, max_count, "forest_roots", mutated=False)
 
     def forest_roots_mutated(self, digests, counts, max_count=None):
         """(roots, mutated): forest_roots, and uint64 [ntrees] whose bit l is set when level l of the tree holds two equal
         siblings that both exist (vkmr_hip_reduce_forest_mutated_async; CVE-2012-2459: such a tree shares its root with a
         shorter leaf list).  `mutated != 0` is Bitcoin Core's flag.  Same arguments and errors as forest_roots."""
-        digests = _host(digests, np.uint32, -1, 8)
-        total = int(digests.shape[0])
-        with self.scope() as tmp:
-            return self._forest_mutated_of_buffer(tmp.upload(digests) if total else None, total, counts, max_count, "forest_roots_mutated")
+        return self._forest_of_digests(digests, counts, max_count, "forest_roots_mutated", mutated=True)
 
     # -- stored forest: every level kept, proofs gathered from it, proofs of unequal height verified --
     def forest_tree_bytes(self, total, ntrees, max_count):
         return self.lib.vkmr_hip_forest_tree_bytes(total, ntrees, max_count)
 
     def reduce_forest_tree_async(self, digests_buf, total, offsets_buf, ntrees, max_count, forest_buf, roots_buf, status_buf, stream=None):
-        check(self.lib.vkmr_hip_reduce_forest_tree_async(self.index, stream or self.stream, digests_buf.ptr if digests_buf else None, total,
-                                                         offsets_buf.ptr if offsets_buf else None, ntrees, max_count,
-                                                         forest_buf.ptr if forest_buf else None, roots_buf.ptr if roots_buf else None,
-                                                         status_buf.ptr if status_buf else None), "vkmr_hip_reduce_forest_tree_async")
+        self._call("vkmr_hip_reduce_forest_tree_async", digests_buf, total, offsets_buf, ntrees, max_count, forest_buf, roots_buf, status_buf,
+                   stream=stream)
 
     def reduce_forest_tree_mutated_async(self, digests_buf, total, offsets_buf, ntrees, max_count, forest_buf, roots_buf, mutated_buf, status_buf,
                                          stream=None):
-        check(self.lib.vkmr_hip_reduce_forest_tree_mutated_async(self.index, stream or self.stream, digests_buf.ptr if digests_buf else None, total,
-                                                                 offsets_buf.ptr if offsets_buf else None, ntrees, max_count,
-                                                                 forest_buf.ptr if forest_buf else None, roots_buf.ptr if roots_buf else None,
-                                                                 mutated_buf.ptr if mutated_buf else None,
-                                                                 status_buf.ptr if status_buf else None), "vkmr_hip_reduce_forest_tree_mutated_async")
+        self._call("vkmr_hip_reduce_forest_tree_mutated_async", digests_buf, total, offsets_buf, ntrees, max_count, forest_buf, roots_buf, mutated_buf,
+                   status_buf, stream=stream)
 
     def forest_tree_mutated_async(self, digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, mutated_buf, stream=None):
-        check(self.lib.vkmr_hip_forest_tree_mutated_async(self.index, stream or self.stream, digests_buf.ptr if digests_buf else None,
-                                                          forest_buf.ptr if forest_buf else None, total, offsets_buf.ptr if offsets_buf else None,
-                                                          ntrees, max_count, mutated_buf.ptr if mutated_buf else None),
-              "vkmr_hip_forest_tree_mutated_async")
+        self._call("vkmr_hip_forest_tree_mutated_async", digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, mutated_buf, stream=stream)
 
     def forest_proofs_async(self, digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, trees_buf, indices_buf, k, siblings_buf,
                             heights_buf, stream=None):
-        check(self.lib.vkmr_hip_forest_proofs_async(self.index, stream or self.stream, digests_buf.ptr if digests_buf else None, forest_buf.ptr,
-                                                    total, offsets_buf.ptr, ntrees, max_count, trees_buf.ptr, indices_buf.ptr, k, siblings_buf.ptr,
-                                                    heights_buf.ptr), "vkmr_hip_forest_proofs_async")
+        self._call("vkmr_hip_forest_proofs_async", digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, trees_buf, indices_buf, k,
+                   siblings_buf, heights_buf, stream=stream)
 
     def verify_forest_proofs_async(self, leaves_buf, trees_buf, indices_buf, siblings_buf, heights_buf, k, stride, roots_buf, ntrees, ok_buf,
                                    stream=None):
-        check(self.lib.vkmr_hip_verify_forest_proofs_async(self.index, stream or self.stream, leaves_buf.ptr, trees_buf.ptr, indices_buf.ptr,
-                                                           siblings_buf.ptr, heights_buf.ptr, k, stride, roots_buf.ptr, ntrees, ok_buf.ptr),
-              "vkmr_hip_verify_forest_proofs_async")
+        self._call("vkmr_hip_verify_forest_proofs_async", leaves_buf, trees_buf, indices_buf, siblings_buf, heights_buf, k, stride, roots_buf, ntrees,
+                   ok_buf, stream=stream)
 
     def forest_update_async(self, digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, trees_buf, indices_buf, leaves_buf, k, roots_buf,
                             status_buf, stream=None):
-        check(self.lib.vkmr_hip_forest_update_async(self.index, stream or self.stream, digests_buf.ptr if digests_buf else None,
-                                                    forest_buf.ptr if forest_buf else None, total, offsets_buf.ptr if offsets_buf else None, ntrees,
-                                                    max_count, trees_buf.ptr, indices_buf.ptr, leaves_buf.ptr, k,
-                                                    roots_buf.ptr if roots_buf else None, status_buf.ptr), "vkmr_hip_forest_update_async")
+        self._call("vkmr_hip_forest_update_async", digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, trees_buf, indices_buf, leaves_buf,
+                   k, roots_buf, status_buf, stream=stream)
 
     def forest_multiproof_async(self, digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, trees_buf, indices_buf, k, scratch_buf,
                                 nodes_buf, nodes_capacity, heights_buf, info_buf, stream=None):
-        check(self.lib.vkmr_hip_forest_multiproof_async(self.index, stream or self.stream, digests_buf.ptr if digests_buf else None,
-                                                        forest_buf.ptr if forest_buf else None, total, offsets_buf.ptr if offsets_buf else None,
-                                                        ntrees, max_count, trees_buf.ptr, indices_buf.ptr, k,
-                                                        scratch_buf.ptr if scratch_buf else None, nodes_buf.ptr if nodes_buf else None,
-                                                        nodes_capacity, heights_buf.ptr, info_buf.ptr), "vkmr_hip_forest_multiproof_async")
+        self._call("vkmr_hip_forest_multiproof_async", digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, trees_buf, indices_buf, k,
+                   scratch_buf, nodes_buf, nodes_capacity, heights_buf, info_buf, stream=stream)
 
     def verify_forest_multiproof_async(self, leaves_buf, trees_buf, indices_buf, heights_buf, k, stride, nodes_buf, m, roots_buf, ntrees,
                                        scratch_buf, ok_buf, stream=None):
-        check(self.lib.vkmr_hip_verify_forest_multiproof_async(self.index, stream or self.stream, leaves_buf.ptr, trees_buf.ptr, indices_buf.ptr,
-                                                               heights_buf.ptr, k, stride, nodes_buf.ptr if nodes_buf else None, m, roots_buf.ptr,
-                                                               ntrees, scratch_buf.ptr, ok_buf.ptr), "vkmr_hip_verify_forest_multiproof_async")
+        self._call("vkmr_hip_verify_forest_multiproof_async", leaves_buf, trees_buf, indices_buf, heights_buf, k, stride, nodes_buf, m, roots_buf,
+                   ntrees, scratch_buf, ok_buf, stream=stream)
 
     def verify_forest_multiproof(self, leaves, trees, indices, heights, nodes, roots):
         """bool: the forest multiproof `nodes` ([M, 8], level-major over the whole forest) proves leaves ([k, 8]) at the
@@ -587,17 +536,13 @@ class HipDevice:
     def forest_find_async(self, digests_buf, total, offsets_buf, ntrees, queries_buf, k, scratch_buf, trees_buf, indices_buf, stream=None):
         """trees_buf[q], indices_buf[q] = where queries_buf[q] (a digest) is a leaf of the forest: the lowest position wins; not
         found: 0xFFFFFFFF and 2^64 - 1.  All in device memory; scratch_buf: find_scratch_bytes(k).  include/vkmr_hip.h."""
-        check(self.lib.vkmr_hip_forest_find_async(self.index, stream or self.stream, digests_buf.ptr if digests_buf else None, total,
-                                                  offsets_buf.ptr if offsets_buf else None, ntrees, queries_buf.ptr if queries_buf else None, k,
-                                                  scratch_buf.ptr if scratch_buf else None, trees_buf.ptr if trees_buf else None,
-                                                  indices_buf.ptr if indices_buf else None), "vkmr_hip_forest_find_async")
+        self._call("vkmr_hip_forest_find_async", digests_buf, total, offsets_buf, ntrees, queries_buf, k, scratch_buf, trees_buf, indices_buf,
+                   stream=stream)
 
     def tree_find_async(self, digests_buf, count, queries_buf, k, scratch_buf, indices_buf, stream=None):
         """indices_buf[q] = the lowest index at which queries_buf[q] is a leaf of the tree over digests_buf[0 .. count), or
         2^64 - 1.  All in device memory; scratch_buf: find_scratch_bytes(k)."""
-        check(self.lib.vkmr_hip_tree_find_async(self.index, stream or self.stream, digests_buf.ptr if digests_buf else None, count,
-                                                queries_buf.ptr if queries_buf else None, k, scratch_buf.ptr if scratch_buf else None,
-                                                indices_buf.ptr if indices_buf else None), "vkmr_hip_tree_find_async")
+        self._call("vkmr_hip_tree_find_async", digests_buf, count, queries_buf, k, scratch_buf, indices_buf, stream=stream)
 
     # -- leaf entries sorted and deduplicated on the device: find -> update, find -> multiproof -----
     def sort_entries_scratch_bytes(self, total, k):
@@ -609,25 +554,16 @@ class HipDevice:
         in cells [0, n) of trees_out_buf / indices_out_buf, order_out_buf[j] (uint32) the last q that holds pair j; info_buf:
         4 uint64 = n, "not found" markers, entries out of range, earlier repeats.  All in device memory; scratch_buf:
         sort_entries_scratch_bytes(total, k), 16-byte aligned.  include/vkmr_hip.h."""
-        check(self.lib.vkmr_hip_forest_sort_entries_async(self.index, stream or self.stream, total, offsets_buf.ptr if offsets_buf else None, ntrees,
-                                                          trees_buf.ptr if trees_buf else None, indices_buf.ptr if indices_buf else None, k,
-                                                          scratch_buf.ptr if scratch_buf else None, trees_out_buf.ptr if trees_out_buf else None,
-                                                          indices_out_buf.ptr if indices_out_buf else None,
-                                                          order_out_buf.ptr if order_out_buf else None, info_buf.ptr if info_buf else None),
-              "vkmr_hip_forest_sort_entries_async")
+        self._call("vkmr_hip_forest_sort_entries_async", total, offsets_buf, ntrees, trees_buf, indices_buf, k, scratch_buf, trees_out_buf,
+                   indices_out_buf, order_out_buf, info_buf, stream=stream)
 
     def tree_sort_entries_async(self, count, indices_buf, k, scratch_buf, indices_out_buf, order_out_buf, info_buf, stream=None):
         """forest_sort_entries_async for one tree of `count` leaves: indices alone, the marker being 2^64 - 1."""
-        check(self.lib.vkmr_hip_tree_sort_entries_async(self.index, stream or self.stream, count, indices_buf.ptr if indices_buf else None, k,
-                                                        scratch_buf.ptr if scratch_buf else None, indices_out_buf.ptr if indices_out_buf else None,
-                                                        order_out_buf.ptr if order_out_buf else None, info_buf.ptr if info_buf else None),
-              "vkmr_hip_tree_sort_entries_async")
+        self._call("vkmr_hip_tree_sort_entries_async", count, indices_buf, k, scratch_buf, indices_out_buf, order_out_buf, info_buf, stream=stream)
 
     def gather_digests_async(self, src_buf, order_buf, n, dst_buf, stream=None):
         """dst_buf[j] = src_buf[order_buf[j]], j < n: digests of 32 bytes, order uint32, all in device memory."""
-        check(self.lib.vkmr_hip_gather_digests_async(self.index, stream or self.stream, src_buf.ptr if src_buf else None,
-                                                     order_buf.ptr if order_buf else None, n, dst_buf.ptr if dst_buf else None),
-              "vkmr_hip_gather_digests_async")
+        self._call("vkmr_hip_gather_digests_async", src_buf, order_buf, n, dst_buf, stream=stream)
 
     # -- two stored forests or trees of one shape: the leaves that differ, found from the roots down -----
     def diff_scratch_bytes(self, capacity):
@@ -639,27 +575,21 @@ class HipDevice:
         stored forests A and B (same offsets, total, ntrees, max_count) differ; leaves_buf (or None): B's leaves there.
         info_buf: 4 uint64 = status (bit 2: more than `capacity` differ), n, trees whose roots differ, nodes whose children
         were compared.  All in device memory; scratch_buf: diff_scratch_bytes(capacity), 16-byte aligned.  include/vkmr_hip.h."""
-        p = lambda b: b.ptr if b else None     # noqa: E731
-        check(self.lib.vkmr_hip_forest_diff_async(self.index, stream or self.stream, p(digests_a_buf), p(forest_a_buf), p(roots_a_buf),
-                                                  p(digests_b_buf), p(forest_b_buf), p(roots_b_buf), total, p(offsets_buf), ntrees, max_count,
-                                                  p(scratch_buf), p(trees_buf), p(indices_buf), p(leaves_buf), capacity, p(info_buf)),
-              "vkmr_hip_forest_diff_async")
+        self._call("vkmr_hip_forest_diff_async", digests_a_buf, forest_a_buf, roots_a_buf, digests_b_buf, forest_b_buf, roots_b_buf, total, offsets_buf,
+                   ntrees, max_count, scratch_buf, trees_buf, indices_buf, leaves_buf, capacity, info_buf, stream=stream)
 
     def tree_diff_async(self, digests_a_buf, tree_a_buf, digests_b_buf, tree_b_buf, count, height, scratch_buf, indices_buf, leaves_buf, capacity,
                         info_buf, stream=None):
         """forest_diff_async for two stored trees of one `count` and `height`: indices alone."""
-        p = lambda b: b.ptr if b else None     # noqa: E731
-        check(self.lib.vkmr_hip_tree_diff_async(self.index, stream or self.stream, p(digests_a_buf), p(tree_a_buf), p(digests_b_buf), p(tree_b_buf),
-                                                count, height, p(scratch_buf), p(indices_buf), p(leaves_buf), capacity, p(info_buf)),
-              "vkmr_hip_tree_diff_async")
+        self._call("vkmr_hip_tree_diff_async", digests_a_buf, tree_a_buf, digests_b_buf, tree_b_buf, count, height, scratch_buf, indices_buf,
+                   leaves_buf, capacity, info_buf, stream=stream)
 
     def reduce_scratch(self, count, levels_variant=False):
         fn = self.lib.vkmr_hip_reduce_levels_scratch_bytes if levels_variant else self.lib.vkmr_hip_reduce_scratch_bytes
         return self.alloc(fn(count))
 
     def combine_async(self, roots_buf, n, scratch_buf, root_buf, stream=None):
-        check(self.lib.vkmr_hip_combine_async(self.index, stream or self.stream, roots_buf.ptr, n, scratch_buf.ptr if scratch_buf else None,
-                                              root_buf.ptr), "vkmr_hip_combine_async")
+        self._call("vkmr_hip_combine_async", roots_buf, n, scratch_buf, root_buf, stream=stream)
 
     def combine(self, roots):
         """Root ([8] uint32) over slice roots given as a host array, in slice order."""
@@ -689,21 +619,6 @@ class HipDevice:
             return self.download(d_root, 32)
 
 
-class _SortedEntries:
-    """The buffers of one device sort of k entries, in the scope `tmp`: the sorted pairs (trees only for a forest), the
-    order, and the four counters once read()."""
-
-    def __init__(self, dev, tmp, total, k, forest):
-        self.dev, self.k = dev, k
-        self.scratch = tmp.alloc(dev.sort_entries_scratch_bytes(total, k))
-        self.trees = tmp.alloc(4 * k) if forest else None
-        self.indices, self.order, self.info = tmp.alloc(8 * k), tmp.alloc(4 * k), tmp.alloc(32)
-
-    def read(self):
-        """(n, not found, out of range, repeats): the one read-back of a sort, 32 bytes."""
-        return tuple(int(x) for x in self.dev.download(self.info, 32, dtype=np.uint64))
-
-
 DIFF_FIRST_CAPACITY = 65536      # diff(capacity=None) starts here and grows DIFF_GROWTH-fold while more leaves differ
 DIFF_GROWTH = 16
 DIFF_MAX_CAPACITY = 2**32 - 1
@@ -711,35 +626,6 @@ DIFF_MAX_CAPACITY = 2**32 - 1
 
 class DiffOverflow(RuntimeError):
     """More leaves differ than the capacity a diff was given."""
-
-
-def _run_diff(dev, tmp, call, cells, capacity, forest, leaves, what):
-    """One diff in the scope `tmp`: call(scratch, trees, indices, leaves, capacity, info) enqueues it, the 32 bytes of info
-    are read back.  (n, trees buffer or None, indices buffer, leaves buffer or None).  capacity None: from
-    min(cells, DIFF_FIRST_CAPACITY), DIFF_GROWTH times more while the device reports more, up to `cells`; an integer:
-    DiffOverflow when more leaves differ."""
-    grow = capacity is None
-    cap = min(cells, DIFF_FIRST_CAPACITY) if grow else int(capacity)
-    if not 0 <= cap <= DIFF_MAX_CAPACITY:
-        raise ValueError(f"{what}: capacity outside [0, 2^32)")
-    while True:
-        d_scr, d_info = tmp.alloc(dev.diff_scratch_bytes(cap)), tmp.alloc(32)
-        d_trees = tmp.alloc(4 * cap) if forest and cap else None
-        d_idx = tmp.alloc(8 * cap) if cap else None
-        d_leaves = tmp.alloc(32 * cap) if leaves and cap else None
-        call(d_scr, d_trees, d_idx, d_leaves, cap, d_info)
-        status, n = (int(x) for x in dev.download(d_info, 32, dtype=np.uint64)[:2])
-        if status == 0:
-            return n, d_trees, d_idx, d_leaves
-        if status != 4:
-            raise RuntimeError(f"{what}: the device reports status {status}")
-        if not grow or cap >= min(cells, DIFF_MAX_CAPACITY):
-            raise DiffOverflow(f"{what}: more than {cap} leaves differ (a frontier of {n} on the way down)")
-        for b in (d_scr, d_info, d_trees, d_idx, d_leaves):
-            if b:
-                b.free()
-                tmp.release(b)
-        cap = min(cells, DIFF_MAX_CAPACITY, cap * DIFF_GROWTH)
 
 
 def _digest_pairs(old_digests, new_digests, what):
@@ -802,9 +688,246 @@ class ForestMultiproof:
                 for r, (t, idx, h) in enumerate(runs)}
 
 
-class MerkleTree:
+def _empty(columns):
+    return tuple(np.zeros(0, dtype=t) for t in columns)
+
+
+def _bare(parts):
+    """A tuple of one as the thing itself: a tree's `indices` where a forest gives `(trees, indices)`."""
+    return parts[0] if len(parts) == 1 else parts
+
+
+class _Stored:
+    """What MerkleTree and MerkleForest share: every operation over host arrays, written once.  A leaf is named by an ENTRY,
+    one cell of each entry column -- (index) in a tree, (tree, index) in a forest -- and the `*_async` methods of both classes
+    take their entry buffers side by side, so the bodies here hand them on as one splatted tuple.  A subclass supplies
+      _columns         the dtypes of the entry columns
+      _proof_columns   the dtypes of what a proof call writes per entry besides its cells (a forest: the heights)
+      _Proof           the class of its multiproofs: _Proof(*entry columns, *proof columns, nodes, level counts, stride)
+      ntrees, cells, stride            its trees, its leaf cells, the cells of one proof
+      _multiproof_sizes, _status_text, _same_shape, _update_order
+    the thin *_async methods, and the public methods whose signature names the entry columns."""
+
+    @staticmethod
+    def _alloc(tmp, columns, k):
+        return tuple(tmp.alloc(np.dtype(t).itemsize * k) for t in columns)
+
+    def _read(self, bufs, columns, n):
+        return tuple(self.dev.download(b, np.dtype(t).itemsize * n, dtype=t) for b, t in zip(bufs, columns))
+
+    def _refuse(self, method, status, whose):
+        """RuntimeError when a status word the device wrote is not 0: it refused entries (`whose`) that were checked or made here."""
+        if status:
+            text = self._status_text(status)
+            raise RuntimeError(f"{type(self).__name__}.{method}: the device refused {whose} (status {status}{': ' + text if text else ''})")
+
+    def _find(self, tmp, queries, k):
+        """find_async of the k digests `queries` (a host array) enqueued, its buffers in the scope `tmp`: the entry buffers it fills."""
+        d_entries = self._alloc(tmp, self._columns, k)
+        self.find_async(tmp.upload(queries), k, tmp.alloc(self.dev.find_scratch_bytes(k)), *d_entries)
+        return d_entries
+
+    def find(self, digests):
+        """For each digest ([k, 8] uint32, a host array) the lowest position at which it is a leaf: a tree gives indices
+        uint64 [k], NOT_FOUND (2^64 - 1) for none; a forest (trees [k] uint32, indices [k] uint64), NO_TREE and NOT_FOUND for
+        none.  Inner nodes and roots are not leaves."""
+        q = _host(digests, np.uint32, -1, 8)
+        k = int(q.shape[0])
+        if k == 0:
+            return _bare(_empty(self._columns))
+        with self.dev.scope() as tmp:
+            return _bare(self._read(self._find(tmp, q, k), self._columns, k))
+
+    def proofs_of(self, digests):
+        """hash -> position -> proof on the device, nothing downloaded in between.  A tree gives (siblings [k, height, 8]
+        uint32, indices [k] uint64); a forest (siblings [k, levels, 8], heights [k] uint32, trees [k] uint32, indices [k]
+        uint64): what proofs() returns for those positions, and the positions.  A digest that is no leaf gets find's markers
+        and zero cells (a forest: height 0), as proofs() gives for a bad position."""
+        q = _host(digests, np.uint32, -1, 8)
+        k = int(q.shape[0])
+        if k == 0:
+            return (*self._no_proofs(0), *_empty(self._columns))
+        with self.dev.scope() as tmp:
+            d_entries = self._find(tmp, q, k)
+            return (*self._gather_proofs(tmp, d_entries, k), *self._read(d_entries, self._columns, k))
+
+    def _no_proofs(self, k):
+        """What k proofs without a cell are: (siblings [k, stride, 8], *the proof columns), all zero."""
+        return (np.zeros((k, self.stride, 8), dtype=np.uint32), *(np.zeros(k, dtype=t) for t in self._proof_columns))
+
+    def _gather_proofs(self, tmp, d_entries, k):
+        """proofs_async of the k entries in d_entries and its results read back: (siblings [k, stride, 8], *the proof columns).
+        A tree of one leaf has no level and no sibling: zero cells, no device call."""
+        if self.stride == 0:
+            return self._no_proofs(k)
+        d_sib, d_extra = tmp.alloc(32 * k * self.stride), self._alloc(tmp, self._proof_columns, k)
+        self.proofs_async(*d_entries, k, d_sib, *d_extra)
+        return (self.dev.download(d_sib, 32 * k * self.stride).reshape(k, self.stride, 8), *self._read(d_extra, self._proof_columns, k))
+
+    def _proofs(self, cols):
+        k = int(cols[-1].shape[0])
+        if k == 0 or self.stride == 0:
+            return _bare(self._no_proofs(k))
+        with self.dev.scope() as tmp:
+            return _bare(self._gather_proofs(tmp, [tmp.upload(c) for c in cols], k))
+
+    def _gather_multiproof(self, tmp, d_entries, k, method, whose):
+        """multiproof_async over the k sorted entries in d_entries and its results read back, status and counts in one
+        download: (nodes [M, 8], the proof columns, the level counts)."""
+        cap, scratch_bytes = self._multiproof_sizes(k)
+        d_scr = tmp.alloc(scratch_bytes) if self.stride else None
+        d_nodes = tmp.alloc(32 * cap) if cap else None
+        d_extra, d_info = self._alloc(tmp, self._proof_columns, k), tmp.alloc(8 * (2 + self.stride))
+        self.multiproof_async(*d_entries, k, d_scr, d_nodes, cap, *d_extra, d_info)
+        info = self.dev.download(d_info, 8 * (2 + self.stride), dtype=np.uint64)
+        self._refuse(method, int(info[0]), whose)      # M and the counts are only written without a status
+        m = int(info[1]) if self.stride else 0
+        nodes = self.dev.download(d_nodes, 32 * m).reshape(m, 8) if m else np.zeros((0, 8), dtype=np.uint32)
+        return nodes, self._read(d_extra, self._proof_columns, k), info[2:].copy()
+
+    def _multiproof(self, entries):
+        *cols, _ = self._update_order(*entries, "multiproof")
+        k = int(cols[-1].shape[0])
+        if k == 0:
+            raise ValueError("multiproof: no entry")
+        with self.dev.scope() as tmp:
+            nodes, extra, counts = self._gather_multiproof(tmp, [tmp.upload(c) for c in cols], k, "multiproof", "sorted in-range entries")
+        return self._Proof(*cols, *extra, nodes, counts, self.stride)
+
+    def multiproof_of(self, digests):
+        """(Multiproof or ForestMultiproof, order): ONE proof for the leaves that hold `digests` (a host array [k, 8]): find ->
+        sort -> multiproof on the device.  digests[order[j]] is the leaf of entry j; digests that are no leaf are left out,
+        repeats count once.  ValueError when none is found."""
+        q = _host(digests, np.uint32, -1, 8)
+        k = int(q.shape[0])
+        if k == 0:
+            raise ValueError("multiproof_of: no digest")
+        with self.dev.scope() as tmp:
+            d_sorted, d_order, (n, _, _, _) = self._sort(tmp, self._find(tmp, q, k), k)
+            if n == 0:
+                raise ValueError("multiproof_of: none of the digests is a leaf")
+            nodes, extra, counts = self._gather_multiproof(tmp, d_sorted, n, "multiproof_of", "its own sorted entries")
+            cols, order = self._read(d_sorted, self._columns, n), self.dev.download(d_order, 4 * n)
+        return self._Proof(*cols, *extra, nodes, counts, self.stride), order
+
+    def _apply(self, tmp, method, whose, d_entries, d_leaves, n):
+        """update_async of the n sorted entries in d_entries to the digests in d_leaves, and its status word read back."""
+        d_status = tmp.alloc(4)
+        self.update_async(*d_entries, d_leaves, n, d_status)
+        self._refuse(method, int(self.dev.download(d_status, 4)[0]), whose)
+
+    def _update(self, entries, leaves):
+        lv = np.asarray(leaves)
+        k = int(np.asarray(entries[-1]).size)
+        if lv.shape != (k, 8):
+            raise ValueError(f"update: leaves must be [{k}, 8], not {list(lv.shape)}")
+        *cols, pos = self._update_order(*entries, "update")
+        with self.dev.scope() as tmp:
+            if pos.shape[0]:
+                d_leaves = tmp.upload(np.ascontiguousarray(lv[pos], dtype=np.uint32))
+                self._apply(tmp, "update", "sorted in-range entries", [tmp.upload(c) for c in cols], d_leaves, pos.shape[0])
+
+    def _update_packed(self, entries, batch):
+        k = int(np.asarray(entries[-1]).size)
+        if batch.count != k:
+            raise ValueError(f"update_packed: {batch.count} strings for {k} indices")
+        *cols, pos = self._update_order(*entries, "update_packed")
+        with self.dev.scope() as tmp:
+            if pos.shape[0]:      # map's entries are independent: the strings in sorted-entry order
+                d_leaves = self.dev.map_packed(tmp, batch, meta=np.ascontiguousarray(batch.meta[pos]))
+                self._apply(tmp, "update_packed", "sorted in-range entries", [tmp.upload(c) for c in cols], d_leaves, pos.shape[0])
+
+    def _sort(self, tmp, d_entries, k):
+        """sort_entries_async of the k entries in d_entries, its buffers in the scope `tmp`, and the one read-back of a sort,
+        32 bytes: (sorted entry buffers, order buffer, (n, not found, out of range, repeats))."""
+        d_sorted, d_order, d_info = self._alloc(tmp, self._columns, k), tmp.alloc(4 * k), tmp.alloc(32)
+        self.sort_entries_async(*d_entries, k, tmp.alloc(self.dev.sort_entries_scratch_bytes(self.cells, k)), *d_sorted, d_order, d_info)
+        return d_sorted, d_order, tuple(int(x) for x in self.dev.download(d_info, 32, dtype=np.uint64))
+
+    def _update_entries(self, d_entries, leaves_buf, k):
+        k = int(k)
+        if k <= 0:
+            return 0, 0, 0
+        with self.dev.scope() as tmp:
+            d_sorted, d_order, (n, missing, outside, repeats) = self._sort(tmp, d_entries, k)
+            if outside:
+                raise IndexError(f"update_entries: {outside} entries name no leaf (and are no marker)")
+            if n:
+                d_leaves = tmp.alloc(32 * n)
+                self.dev.gather_digests_async(leaves_buf, d_order, n, d_leaves)
+                self._apply(tmp, "update_entries", "its own sorted entries", d_sorted, d_leaves, n)
+            return n, missing, repeats
+
+    def replace(self, old_digests, new_digests):
+        """The leaves that hold old_digests[q] become new_digests[q] (host arrays [k, 8]): find -> sort -> gather -> update on
+        the device, no position and no digest coming back.  (replaced, missing): leaves written, and old digests that are no
+        leaf.  Two equal old digests take the last new value.  A digest held by several leaves replaces the LOWEST position
+        only: that is find's rule."""
+        old, new = _digest_pairs(old_digests, new_digests, "replace")
+        k = int(old.shape[0])
+        if k == 0:
+            return 0, 0
+        with self.dev.scope() as tmp:
+            applied, missing, _ = self._update_entries(self._find(tmp, old, k), tmp.upload(new), k)
+            return applied, missing
+
+    def _diff(self, tmp, other, capacity, leaves, what):
+        """One diff against `other` in the scope `tmp`, the 32 bytes of its info read back: (n, entry buffers, leaves buffer or
+        None).  capacity None: from min(cells, DIFF_FIRST_CAPACITY), DIFF_GROWTH times more while the device reports more, up
+        to `cells`; an integer: DiffOverflow when more leaves differ."""
+        self._same_shape(other, what)
+        nothing = (None,) * len(self._columns)
+        if self.ntrees == 0:                      # the call does nothing and writes no counters
+            return 0, nothing, None
+        grow = capacity is None
+        cap = min(self.cells, DIFF_FIRST_CAPACITY) if grow else int(capacity)
+        if not 0 <= cap <= DIFF_MAX_CAPACITY:
+            raise ValueError(f"{what}: capacity outside [0, 2^32)")
+        while True:
+            d_scr, d_info = tmp.alloc(self.dev.diff_scratch_bytes(cap)), tmp.alloc(32)
+            d_entries = self._alloc(tmp, self._columns, cap) if cap else nothing
+            d_leaves = tmp.alloc(32 * cap) if leaves and cap else None
+            self.diff_async(other, d_scr, *d_entries, d_leaves, cap, d_info)
+            status, n = (int(x) for x in self.dev.download(d_info, 32, dtype=np.uint64)[:2])
+            if status == 0:
+                return n, d_entries, d_leaves
+            if status != 4:
+                raise RuntimeError(f"{what}: the device reports status {status}")
+            if not grow or cap >= min(self.cells, DIFF_MAX_CAPACITY):
+                raise DiffOverflow(f"{what}: more than {cap} leaves differ (a frontier of {n} on the way down)")
+            for b in (d_scr, d_info, *d_entries, d_leaves):
+                if b:
+                    b.free()
+                    tmp.release(b)
+            cap = min(self.cells, DIFF_MAX_CAPACITY, cap * DIFF_GROWTH)
+
+    def diff(self, other, capacity=None):
+        """The leaves in which this tree or forest and `other` differ, in increasing order: a tree gives indices uint64 [n],
+        a forest (trees uint32 [n], indices uint64 [n]).  capacity None: room for min(cells, 65536) answers first, 16 times
+        more while more differ; an integer: DiffOverflow when more differ.  ValueError for another device or another shape
+        (a tree's count and height; a forest's counts and max_count), before any device call."""
+        with self.dev.scope() as tmp:
+            n, d_entries, _ = self._diff(tmp, other, capacity, False, "diff")
+            return _bare(self._read(d_entries, self._columns, n) if n else _empty(self._columns))
+
+    def sync_from(self, other):
+        """Make this tree or forest equal to `other`: the diff with other's leaves at the differing positions, then the update
+        of exactly those, all on the device; the 32 bytes of counters are what comes back.  The number of leaves written."""
+        with self.dev.scope() as tmp:
+            n, d_entries, d_leaves = self._diff(tmp, other, None, True, "sync_from")
+            if n:
+                self._apply(tmp, "sync_from", "the diff's own entries", d_entries, d_leaves, n)
+            return n
+
+
+class MerkleTree(_Stored):
     """Every level of a duplicate-last tree, resident on the device (vkmr_hip_reduce_tree_async): level 0 is the digests
     buffer it was built from, levels 1..height one buffer laid out as include/vkmr_hip.h describes."""
+
+    _columns, _proof_columns, _Proof = (np.uint64,), (), Multiproof
+    ntrees = 1
+    cells = property(lambda self: self.count)
+    stride = property(lambda self: self.height)
 
     def __init__(self, dev, digests_buf, count, height, tree_buf, owned=()):
         self.dev, self.digests, self.count, self.height, self.tree = dev, digests_buf, int(count), int(height), tree_buf
@@ -838,48 +961,12 @@ class MerkleTree:
 
     def proofs(self, indices):
         """[k, height, 8] uint32: the proofs of leaves `indices` (a host array); an index >= count gets zero cells."""
-        idx = _host(indices, np.uint64, -1)
-        k = int(idx.shape[0])
-        if k == 0 or self.height == 0:
-            return np.zeros((k, self.height, 8), dtype=np.uint32)
-        with self.dev.scope() as tmp:
-            d_idx, d_sib = tmp.upload(idx), tmp.alloc(32 * k * self.height)
-            self.proofs_async(d_idx, k, d_sib)
-            return self.dev.download(d_sib, 32 * k * self.height).reshape(k, self.height, 8)
+        return self._proofs((_host(indices, np.uint64, -1),))
 
     def find_async(self, queries_buf, k, scratch_buf, indices_buf, stream=None):
         """indices_buf[q] = the lowest index whose leaf equals the digest queries_buf[q], or 2^64 - 1 (NOT_FOUND): device
         memory throughout, scratch_buf of dev.find_scratch_bytes(k) bytes; ordered on `stream` behind earlier updates."""
         self.dev.tree_find_async(self.digests, self.count, queries_buf, k, scratch_buf, indices_buf, stream=stream)
-
-    def find(self, digests):
-        """uint64 [k]: for each digest ([k, 8] uint32, a host array) the lowest index at which it is a leaf, or NOT_FOUND
-        (2^64 - 1).  Inner nodes and the root are not leaves."""
-        q = _host(digests, np.uint32, -1, 8)
-        k = int(q.shape[0])
-        if k == 0:
-            return np.zeros(0, dtype=np.uint64)
-        with self.dev.scope() as tmp:
-            d_q, d_scr, d_idx = tmp.upload(q), tmp.alloc(self.dev.find_scratch_bytes(k)), tmp.alloc(8 * k)
-            self.find_async(d_q, k, d_scr, d_idx)
-            return self.dev.download(d_idx, 8 * k, dtype=np.uint64)
-
-    def proofs_of(self, digests):
-        """(siblings [k, height, 8] uint32, indices [k] uint64): hash -> position -> proof on the device, nothing downloaded
-        in between.  A digest that is no leaf gets NOT_FOUND and zero cells, as proofs() gives for a bad index."""
-        q = _host(digests, np.uint32, -1, 8)
-        k = int(q.shape[0])
-        if k == 0:
-            return np.zeros((0, self.height, 8), dtype=np.uint32), np.zeros(0, dtype=np.uint64)
-        with self.dev.scope() as tmp:
-            d_q, d_scr, d_idx = tmp.upload(q), tmp.alloc(self.dev.find_scratch_bytes(k)), tmp.alloc(8 * k)
-            self.find_async(d_q, k, d_scr, d_idx)
-            sib = np.zeros((k, self.height, 8), dtype=np.uint32)
-            if self.height:
-                d_sib = tmp.alloc(32 * k * self.height)
-                self.proofs_async(d_idx, k, d_sib)
-                sib = self.dev.download(d_sib, 32 * k * self.height).reshape(k, self.height, 8)
-            return sib, self.dev.download(d_idx, 8 * k, dtype=np.uint64)
 
     def multiproof_async(self, indices_buf, k, scratch_buf, nodes_buf, nodes_capacity, info_buf, stream=None):
         """ONE proof for the k leaves whose strictly increasing indices are in device memory, written to nodes_buf
@@ -887,34 +974,24 @@ class MerkleTree:
         self.dev.tree_multiproof_async(self.digests, self.tree, self.count, self.height, indices_buf, k, scratch_buf, nodes_buf, nodes_capacity,
                                        info_buf, stream=stream)
 
+    def _multiproof_sizes(self, k):
+        """(the most nodes a multiproof of k leaves holds, the bytes of its scratch)."""
+        lib = self.dev.lib
+        return lib.vkmr_hip_multiproof_max_nodes(self.count, self.height, k), lib.vkmr_hip_multiproof_scratch_bytes(k, self.height)
+
     def multiproof(self, indices):
         """A Multiproof of leaves `indices` (a host array; sorted and deduplicated here).  IndexError for an index < 0 or
         >= count, ValueError for indices that are not integers or for none at all, before any device call."""
-        idx, _ = self._update_order(indices, "multiproof")
-        k = int(idx.shape[0])
-        if k == 0:
-            raise ValueError("multiproof: no index")
-        lib = self.dev.lib
-        cap = lib.vkmr_hip_multiproof_max_nodes(self.count, self.height, k)
-        with self.dev.scope() as tmp:
-            d_idx = tmp.upload(idx)
-            d_scr = tmp.alloc(lib.vkmr_hip_multiproof_scratch_bytes(k, self.height)) if self.height else None
-            d_nodes = tmp.alloc(32 * cap) if cap else None
-            d_info = tmp.alloc(8 * (2 + self.height))
-            self.multiproof_async(d_idx, k, d_scr, d_nodes, cap, d_info)
-            status = int(self.dev.download(d_info, 8, dtype=np.uint64)[0])
-            if status:                            # M and the counts are only written without one (or with bit 2)
-                raise RuntimeError(f"MerkleTree.multiproof: the device refused sorted in-range indices (status {status})")
-            info = self.dev.download(d_info, 8 * (2 + self.height), dtype=np.uint64)
-            m = int(info[1])
-            nodes = self.dev.download(d_nodes, 32 * m).reshape(m, 8) if m else np.zeros((0, 8), dtype=np.uint32)
-        return Multiproof(idx, nodes, info[2:].copy(), self.height)
+        return self._multiproof((indices,))
 
     def update_async(self, indices_buf, leaves_buf, k, status_buf, stream=None):
         """Leaves indices[q] = leaves[q], q < k, and every ancestor rehashed, on the device: indices [k] uint64 strictly
         increasing and < count, leaves [k, 8], status one uint32 (0: applied; bit 0: an index >= count, bit 1: not strictly
         increasing; nonzero: nothing changed).  All in device memory; ordered on `stream` like the proof gather."""
         self.dev.tree_update_async(self.digests, self.tree, self.count, self.height, indices_buf, leaves_buf, k, status_buf, stream=stream)
+
+    def _status_text(self, status):
+        return ""
 
     def _update_order(self, indices, what="update"):
         """(sorted unique uint64 indices, positions in `indices` they come from): the last occurrence of a repeated index
@@ -926,37 +1003,16 @@ class MerkleTree:
         last[:-1] = s[1:] != s[:-1]        # a stable sort keeps repeats in call order: the last of each run is the last occurrence
         return s[last], order[last]
 
-    def _apply(self, tmp, idx, d_leaves):
-        """The update of leaves idx (sorted, unique, in range) to the digests in d_leaves; its buffers in the scope `tmp`."""
-        d_idx, d_status = tmp.upload(idx), tmp.alloc(4)
-        self.update_async(d_idx, d_leaves, idx.shape[0], d_status)
-        status = int(self.dev.download(d_status, 4)[0])
-        if status:
-            raise RuntimeError(f"MerkleTree.update: the device refused sorted in-range indices (status {status})")
-
     def update(self, indices, leaves):
         """Set leaf indices[q] to leaves[q] ([k, 8] uint32; host arrays) and rehash every ancestor, on the device; a repeated
         index takes its last value.  A tree built over a caller's digests buffer updates that buffer (it is level 0).
         IndexError for an index < 0 or >= count, ValueError when leaves is not [k, 8], both before any device call."""
-        lv = np.asarray(leaves)
-        k = int(np.asarray(indices).size)
-        if lv.shape != (k, 8):
-            raise ValueError(f"update: leaves must be [{k}, 8], not {list(lv.shape)}")
-        idx, pos = self._update_order(indices)
-        with self.dev.scope() as tmp:
-            if idx.shape[0]:
-                self._apply(tmp, idx, tmp.upload(np.ascontiguousarray(lv[pos], dtype=np.uint32)))
+        self._update((indices,), leaves)
 
     def update_packed(self, indices, batch):
         """Set leaf indices[q] to the digest of string q of `batch` (batch.count == len(indices)): the strings are mapped on
         the device and the tree updated there, no digest goes through the host.  Same index rules as update()."""
-        k = int(np.asarray(indices).size)
-        if batch.count != k:
-            raise ValueError(f"update_packed: {batch.count} strings for {k} indices")
-        idx, pos = self._update_order(indices)
-        with self.dev.scope() as tmp:
-            if idx.shape[0]:      # map's entries are independent: the strings in sorted-index order
-                self._apply(tmp, idx, self.dev.map_packed(tmp, batch, meta=np.ascontiguousarray(batch.meta[pos])))
+        self._update_packed((indices,), batch)
 
     def sort_entries_async(self, indices_buf, k, scratch_buf, indices_out_buf, order_out_buf, info_buf, stream=None):
         """The k indices in device memory, in any order, sorted and deduplicated for update_async / multiproof_async:
@@ -968,71 +1024,7 @@ class MerkleTree:
         device (a repeated index takes its last value, NOT_FOUND markers are left out), the leaves gathered into that order,
         the tree updated; only the sort's 32 bytes of counters come back.  (applied, not_found, repeats).  IndexError when an
         index is >= count (and no marker), before anything of the tree changes."""
-        k = int(k)
-        if k <= 0:
-            return 0, 0, 0
-        with self.dev.scope() as tmp:
-            se = _SortedEntries(self.dev, tmp, self.count, k, forest=False)
-            self.sort_entries_async(indices_buf, k, se.scratch, se.indices, se.order, se.info)
-            n, missing, outside, repeats = se.read()
-            if outside:
-                raise IndexError(f"update_entries: {outside} indices outside [0, {self.count})")
-            if n:
-                d_leaves, d_status = tmp.alloc(32 * n), tmp.alloc(4)
-                self.dev.gather_digests_async(leaves_buf, se.order, n, d_leaves)
-                self.update_async(se.indices, d_leaves, n, d_status)
-                status = int(self.dev.download(d_status, 4)[0])
-                if status:
-                    raise RuntimeError(f"MerkleTree.update_entries: the device refused its own sorted indices (status {status})")
-            return n, missing, repeats
-
-    def replace(self, old_digests, new_digests):
-        """The leaves that hold old_digests[q] become new_digests[q] (host arrays [k, 8]): find -> sort -> gather -> update on
-        the device, no position and no digest coming back.  (replaced, missing): leaves written, and old digests that are no
-        leaf.  Two equal old digests take the last new value.  A digest held by several leaves replaces the LOWEST index only:
-        that is find's rule."""
-        old, new = _digest_pairs(old_digests, new_digests, "replace")
-        k = int(old.shape[0])
-        if k == 0:
-            return 0, 0
-        with self.dev.scope() as tmp:
-            d_old, d_new, d_scr, d_idx = tmp.upload(old), tmp.upload(new), tmp.alloc(self.dev.find_scratch_bytes(k)), tmp.alloc(8 * k)
-            self.find_async(d_old, k, d_scr, d_idx)
-            applied, missing, _ = self.update_entries(d_idx, d_new, k)
-            return applied, missing
-
-    def multiproof_of(self, digests):
-        """(Multiproof, order): ONE proof for the leaves that hold `digests` (a host array [k, 8]): find -> sort -> multiproof on
-        the device.  digests[order[j]] is the leaf of entry j; digests that are no leaf are left out, repeats count once.
-        ValueError when none is found."""
-        q = _host(digests, np.uint32, -1, 8)
-        k = int(q.shape[0])
-        if k == 0:
-            raise ValueError("multiproof_of: no digest")
-        lib = self.dev.lib
-        with self.dev.scope() as tmp:
-            n = 0
-            if k:
-                d_q, d_scr, d_idx = tmp.upload(q), tmp.alloc(self.dev.find_scratch_bytes(k)), tmp.alloc(8 * k)
-                se = _SortedEntries(self.dev, tmp, self.count, k, forest=False)
-                self.find_async(d_q, k, d_scr, d_idx)
-                self.sort_entries_async(d_idx, k, se.scratch, se.indices, se.order, se.info)
-                n = se.read()[0]
-            if n == 0:
-                raise ValueError("multiproof_of: none of the digests is a leaf")
-            cap = lib.vkmr_hip_multiproof_max_nodes(self.count, self.height, n)
-            d_mp = tmp.alloc(lib.vkmr_hip_multiproof_scratch_bytes(n, self.height)) if self.height else None
-            d_nodes = tmp.alloc(32 * cap) if cap else None
-            d_info = tmp.alloc(8 * (2 + self.height))
-            self.multiproof_async(se.indices, n, d_mp, d_nodes, cap, d_info)
-            info = self.dev.download(d_info, 8 * (2 + self.height), dtype=np.uint64)
-            if int(info[0]):
-                raise RuntimeError(f"MerkleTree.multiproof_of: the device refused its own sorted indices (status {int(info[0])})")
-            m = int(info[1]) if self.height else 0
-            nodes = self.dev.download(d_nodes, 32 * m).reshape(m, 8) if m else np.zeros((0, 8), dtype=np.uint32)
-            idx = self.dev.download(se.indices, 8 * n, dtype=np.uint64)
-            order = self.dev.download(se.order, 4 * n)
-        return Multiproof(idx, nodes, info[2:].copy(), self.height), order
+        return self._update_entries((indices_buf,), leaves_buf, k)
 
     def _same_shape(self, other, what):
         """ValueError unless `other` is a MerkleTree of this tree's device, count and height; no device call."""
@@ -1052,32 +1044,6 @@ class MerkleTree:
         self.dev.tree_diff_async(self.digests, self.tree, other.digests, other.tree, self.count, self.height, scratch_buf, indices_buf, leaves_buf,
                                  capacity, info_buf, stream=stream)
 
-    def _diff(self, tmp, other, capacity, leaves, what):
-        self._same_shape(other, what)
-        return _run_diff(self.dev, tmp, lambda scr, _, idx, lv, cap, info: self.diff_async(other, scr, idx, lv, cap, info), self.count, capacity,
-                         False, leaves, what)
-
-    def diff(self, other, capacity=None):
-        """uint64 [n]: the indices, increasing, of the leaves in which this tree and `other` differ.  capacity None: room for
-        min(count, 65536) answers first, 16 times more while more differ; an integer: DiffOverflow when more differ.
-        ValueError for a tree of another device, count or height, before any device call."""
-        with self.dev.scope() as tmp:
-            n, _, d_idx, _ = self._diff(tmp, other, capacity, False, "diff")
-            return self.dev.download(d_idx, 8 * n, dtype=np.uint64) if n else np.zeros(0, dtype=np.uint64)
-
-    def sync_from(self, other):
-        """Make this tree equal to `other`: the diff with other's leaves at the differing positions, then the update of
-        exactly those, all on the device; the 32 bytes of counters are what comes back.  The number of leaves written."""
-        with self.dev.scope() as tmp:
-            n, _, d_idx, d_leaves = self._diff(tmp, other, None, True, "sync_from")
-            if n:
-                d_status = tmp.alloc(4)
-                self.update_async(d_idx, d_leaves, n, d_status)
-                status = int(self.dev.download(d_status, 4)[0])
-                if status:
-                    raise RuntimeError(f"MerkleTree.sync_from: the device refused the diff's own indices (status {status})")
-            return n
-
     def free(self):
         if self.tree:
             self.tree.free()
@@ -1087,11 +1053,15 @@ class MerkleTree:
         self._owned = []
 
 
-class MerkleForest:
+class MerkleForest(_Stored):
     """Every level of every tree of a forest, resident on the device (vkmr_hip_reduce_forest_tree_async): level 0 is the
     leaves buffer it was built from, levels 1..`levels` one buffer laid out as include/vkmr_hip.h describes, the roots a
     buffer of their own.  `levels` is also the stride of its proofs.  `built_mutated`: the mutation masks of the build
     (uint64 [ntrees]) when it was a flagged one, else None; mutated() gives those of the forest as it is now."""
+
+    _columns, _proof_columns, _Proof = (np.uint32, np.uint64), (np.uint32,), ForestMultiproof
+    cells = property(lambda self: self.total)
+    stride = property(lambda self: self.levels)
 
     def __init__(self, dev, digests_buf, total, counts, offsets_buf, max_count, forest_buf, roots_buf, owned=(), built_mutated=None):
         self.built_mutated = built_mutated
@@ -1130,16 +1100,9 @@ class MerkleForest:
         first heights[q] cells of proof q count, the rest are zero; a tree >= ntrees or an index >= its tree's count gets
         height 0 and zero cells."""
         trees, idx = _host(trees, np.uint32, -1), _host(indices, np.uint64, -1)
-        k = int(idx.shape[0])
-        if trees.shape[0] != k:
+        if trees.shape[0] != idx.shape[0]:
             raise ValueError("proofs: one tree per index")
-        if k == 0:
-            return np.zeros((0, self.levels, 8), dtype=np.uint32), np.zeros(0, dtype=np.uint32)
-        with self.dev.scope() as tmp:
-            d_trees, d_idx = tmp.upload(trees), tmp.upload(idx)
-            d_sib, d_h = tmp.alloc(32 * k * self.levels), tmp.alloc(4 * k)
-            self.proofs_async(d_trees, d_idx, k, d_sib, d_h)
-            return self.dev.download(d_sib, 32 * k * self.levels).reshape(k, self.levels, 8), self.dev.download(d_h, 4 * k)
+        return self._proofs((trees, idx))
 
     def find_async(self, queries_buf, k, scratch_buf, trees_buf, indices_buf, stream=None):
         """trees_buf[q], indices_buf[q] = where the digest queries_buf[q] is a leaf: the lowest position of the forest wins;
@@ -1148,36 +1111,6 @@ class MerkleForest:
         self.dev.forest_find_async(self.digests, self.total, self.offsets, self.ntrees, queries_buf, k, scratch_buf, trees_buf, indices_buf,
                                    stream=stream)
 
-    def find(self, digests):
-        """(trees [k] uint32, indices [k] uint64): for each digest ([k, 8] uint32, a host array) the tree and the index inside
-        it at which it is a leaf -- the lowest position of the forest when there are several -- or NO_TREE and NOT_FOUND.
-        Inner nodes and roots are not leaves."""
-        q = _host(digests, np.uint32, -1, 8)
-        k = int(q.shape[0])
-        if k == 0:
-            return np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint64)
-        with self.dev.scope() as tmp:
-            d_q, d_scr, d_trees, d_idx = tmp.upload(q), tmp.alloc(self.dev.find_scratch_bytes(k)), tmp.alloc(4 * k), tmp.alloc(8 * k)
-            self.find_async(d_q, k, d_scr, d_trees, d_idx)
-            return self.dev.download(d_trees, 4 * k), self.dev.download(d_idx, 8 * k, dtype=np.uint64)
-
-    def proofs_of(self, digests):
-        """(siblings [k, levels, 8] uint32, heights [k] uint32, trees [k] uint32, indices [k] uint64): hash -> position ->
-        proof on the device, nothing downloaded in between.  What proofs(trees, indices) returns, and the positions; a digest
-        that is no leaf gets NO_TREE, NOT_FOUND, height 0 and zero cells."""
-        q = _host(digests, np.uint32, -1, 8)
-        k = int(q.shape[0])
-        if k == 0:
-            return (np.zeros((0, self.levels, 8), dtype=np.uint32), np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint32),
-                    np.zeros(0, dtype=np.uint64))
-        with self.dev.scope() as tmp:
-            d_q, d_scr, d_trees, d_idx = tmp.upload(q), tmp.alloc(self.dev.find_scratch_bytes(k)), tmp.alloc(4 * k), tmp.alloc(8 * k)
-            d_sib, d_h = tmp.alloc(32 * k * self.levels), tmp.alloc(4 * k)
-            self.find_async(d_q, k, d_scr, d_trees, d_idx)
-            self.proofs_async(d_trees, d_idx, k, d_sib, d_h)
-            return (self.dev.download(d_sib, 32 * k * self.levels).reshape(k, self.levels, 8), self.dev.download(d_h, 4 * k),
-                    self.dev.download(d_trees, 4 * k), self.dev.download(d_idx, 8 * k, dtype=np.uint64))
-
     def multiproof_async(self, trees_buf, indices_buf, k, scratch_buf, nodes_buf, nodes_capacity, heights_buf, info_buf, stream=None):
         """ONE proof for the k (tree, index) entries in device memory (strictly increasing pairs), written to nodes_buf
         (nodes_capacity cells) and heights_buf [k]; info_buf: 2 + levels uint64 (status, M, the per-level counts).
@@ -1185,30 +1118,17 @@ class MerkleForest:
         self.dev.forest_multiproof_async(self.digests, self.forest, self.total, self.offsets, self.ntrees, self.max_count, trees_buf, indices_buf,
                                          k, scratch_buf, nodes_buf, nodes_capacity, heights_buf, info_buf, stream=stream)
 
+    def _multiproof_sizes(self, k):
+        """(the most nodes a multiproof of k entries holds, the bytes of its scratch)."""
+        lib = self.dev.lib
+        return (lib.vkmr_hip_forest_multiproof_max_nodes(self.total, self.ntrees, self.max_count, k),
+                lib.vkmr_hip_forest_multiproof_scratch_bytes(k, self.levels))
+
     def multiproof(self, trees, indices):
         """A ForestMultiproof of leaves `indices` of trees `trees` (host arrays; the pairs sorted and deduplicated here).
         ValueError when there is not one tree per index or for no entry at all, IndexError for a tree outside [0, ntrees) or an
         index outside [0, counts[tree]), all before any device call."""
-        st, si, _ = self._update_order(trees, indices, "multiproof")
-        k = int(si.shape[0])
-        if k == 0:
-            raise ValueError("multiproof: no entry")
-        lib = self.dev.lib
-        cap = lib.vkmr_hip_forest_multiproof_max_nodes(self.total, self.ntrees, self.max_count, k)
-        with self.dev.scope() as tmp:
-            d_trees, d_idx = tmp.upload(st), tmp.upload(si)
-            d_scr = tmp.alloc(lib.vkmr_hip_forest_multiproof_scratch_bytes(k, self.levels))
-            d_nodes, d_h, d_info = tmp.alloc(32 * cap), tmp.alloc(4 * k), tmp.alloc(8 * (2 + self.levels))
-            self.multiproof_async(d_trees, d_idx, k, d_scr, d_nodes, cap, d_h, d_info)
-            status = int(self.dev.download(d_info, 8, dtype=np.uint64)[0])
-            if status:                            # M and the counts are only written without one (or with bit 2)
-                raise RuntimeError(f"MerkleForest.multiproof: the device refused sorted in-range entries "
-                                   f"(status {status}: {forest_multiproof_status_text(status)})")
-            info = self.dev.download(d_info, 8 * (2 + self.levels), dtype=np.uint64)
-            m = int(info[1])
-            nodes = self.dev.download(d_nodes, 32 * m).reshape(m, 8) if m else np.zeros((0, 8), dtype=np.uint32)
-            heights = self.dev.download(d_h, 4 * k)
-        return ForestMultiproof(st, si, heights, nodes, info[2:].copy(), self.levels)
+        return self._multiproof((trees, indices))
 
     def update_async(self, trees_buf, indices_buf, leaves_buf, k, status_buf, stream=None):
         """Leaf indices[q] of tree trees[q] = leaves[q], q < k, and every ancestor rehashed, on the device: trees [k] uint32 and
@@ -1217,6 +1137,9 @@ class MerkleForest:
         on `stream` like the proof gather."""
         self.dev.forest_update_async(self.digests, self.forest, self.total, self.offsets, self.ntrees, self.max_count, trees_buf, indices_buf,
                                      leaves_buf, k, self.roots_buf, status_buf, stream=stream)
+
+    def _status_text(self, status):
+        return forest_multiproof_status_text(status)      # the update's bits, and the multiproof's bit 2 that an update never sets
 
     def _update_order(self, trees, indices, what="update"):
         """(trees uint32, indices uint64, positions in the call they come from): the (tree, index) pairs sorted
@@ -1234,38 +1157,17 @@ class MerkleForest:
         last[:-1] = (st[1:] != st[:-1]) | (si[1:] != si[:-1])
         return st[last].astype(np.uint32), si[last], order[last]
 
-    def _apply(self, tmp, trees, idx, d_leaves):
-        """The update of the sorted, unique, in-range entries (trees, idx) to the digests in d_leaves; its buffers in the scope `tmp`."""
-        d_trees, d_idx, d_status = tmp.upload(trees), tmp.upload(idx), tmp.alloc(4)
-        self.update_async(d_trees, d_idx, d_leaves, idx.shape[0], d_status)
-        status = int(self.dev.download(d_status, 4)[0])
-        if status:
-            raise RuntimeError(f"MerkleForest.update: the device refused sorted in-range entries (status {status}: {forest_update_status_text(status)})")
-
     def update(self, trees, indices, leaves):
         """Set leaf indices[q] of tree trees[q] to leaves[q] ([k, 8] uint32; host arrays) and rehash every ancestor, on the
         device; a repeated (tree, index) pair takes its last value.  A forest built over a caller's leaves buffer updates that
         buffer (it is level 0).  ValueError when leaves is not [k, 8] or there is not one tree per index, IndexError for a tree
         outside [0, ntrees) or an index outside [0, counts[tree]), all before any device call."""
-        lv = np.asarray(leaves)
-        k = int(np.asarray(indices).size)
-        if lv.shape != (k, 8):
-            raise ValueError(f"update: leaves must be [{k}, 8], not {list(lv.shape)}")
-        st, si, pos = self._update_order(trees, indices)
-        with self.dev.scope() as tmp:
-            if si.shape[0]:
-                self._apply(tmp, st, si, tmp.upload(np.ascontiguousarray(lv[pos], dtype=np.uint32)))
+        self._update((trees, indices), leaves)
 
     def update_packed(self, trees, indices, batch):
         """Set leaf indices[q] of tree trees[q] to the digest of string q of `batch` (batch.count == len(indices)): the strings
         are mapped on the device and the forest updated there, no digest goes through the host.  Same rules as update()."""
-        k = int(np.asarray(indices).size)
-        if batch.count != k:
-            raise ValueError(f"update_packed: {batch.count} strings for {k} indices")
-        st, si, pos = self._update_order(trees, indices, "update_packed")
-        with self.dev.scope() as tmp:
-            if si.shape[0]:      # map's entries are independent: the strings in sorted-entry order
-                self._apply(tmp, st, si, self.dev.map_packed(tmp, batch, meta=np.ascontiguousarray(batch.meta[pos])))
+        self._update_packed((trees, indices), batch)
 
     def sort_entries_async(self, trees_buf, indices_buf, k, scratch_buf, trees_out_buf, indices_out_buf, order_out_buf, info_buf, stream=None):
         """The k (tree, index) entries in device memory, in any order -- find_async's outputs as they are -- sorted and
@@ -1279,73 +1181,7 @@ class MerkleForest:
         deduplicated on the device (a repeated pair takes its last value, find's NO_TREE markers are left out), the leaves
         gathered into that order, the forest updated; only the sort's 32 bytes of counters come back.  (applied, not_found,
         repeats).  IndexError when an entry is out of range (and no marker), before anything of the forest changes."""
-        k = int(k)
-        if k <= 0:
-            return 0, 0, 0
-        with self.dev.scope() as tmp:
-            se = _SortedEntries(self.dev, tmp, self.total, k, forest=True)
-            self.sort_entries_async(trees_buf, indices_buf, k, se.scratch, se.trees, se.indices, se.order, se.info)
-            n, missing, outside, repeats = se.read()
-            if outside:
-                raise IndexError(f"update_entries: {outside} entries name a tree outside the forest or an index outside its tree")
-            if n:
-                d_leaves, d_status = tmp.alloc(32 * n), tmp.alloc(4)
-                self.dev.gather_digests_async(leaves_buf, se.order, n, d_leaves)
-                self.update_async(se.trees, se.indices, d_leaves, n, d_status)
-                status = int(self.dev.download(d_status, 4)[0])
-                if status:
-                    raise RuntimeError(f"MerkleForest.update_entries: the device refused its own sorted entries "
-                                       f"(status {status}: {forest_update_status_text(status)})")
-            return n, missing, repeats
-
-    def replace(self, old_digests, new_digests):
-        """The leaves that hold old_digests[q] become new_digests[q] (host arrays [k, 8]): find -> sort -> gather -> update on
-        the device, no position and no digest coming back.  (replaced, missing): leaves written, and old digests that are no
-        leaf.  Two equal old digests take the last new value.  A digest held by several leaves replaces the LOWEST position
-        of the forest only: that is find's rule."""
-        old, new = _digest_pairs(old_digests, new_digests, "replace")
-        k = int(old.shape[0])
-        if k == 0:
-            return 0, 0
-        with self.dev.scope() as tmp:
-            d_old, d_new, d_scr = tmp.upload(old), tmp.upload(new), tmp.alloc(self.dev.find_scratch_bytes(k))
-            d_trees, d_idx = tmp.alloc(4 * k), tmp.alloc(8 * k)
-            self.find_async(d_old, k, d_scr, d_trees, d_idx)
-            applied, missing, _ = self.update_entries(d_trees, d_idx, d_new, k)
-            return applied, missing
-
-    def multiproof_of(self, digests):
-        """(ForestMultiproof, order): ONE proof for the leaves that hold `digests` (a host array [k, 8]): find -> sort ->
-        multiproof on the device.  digests[order[j]] is the leaf of entry j; digests that are no leaf are left out, repeats
-        count once.  ValueError when none is found."""
-        q = _host(digests, np.uint32, -1, 8)
-        k = int(q.shape[0])
-        if k == 0:
-            raise ValueError("multiproof_of: no digest")
-        lib = self.dev.lib
-        with self.dev.scope() as tmp:
-            n = 0
-            if k:
-                d_q, d_scr, d_trees, d_idx = tmp.upload(q), tmp.alloc(self.dev.find_scratch_bytes(k)), tmp.alloc(4 * k), tmp.alloc(8 * k)
-                se = _SortedEntries(self.dev, tmp, self.total, k, forest=True)
-                self.find_async(d_q, k, d_scr, d_trees, d_idx)
-                self.sort_entries_async(d_trees, d_idx, k, se.scratch, se.trees, se.indices, se.order, se.info)
-                n = se.read()[0]
-            if n == 0:
-                raise ValueError("multiproof_of: none of the digests is a leaf")
-            cap = lib.vkmr_hip_forest_multiproof_max_nodes(self.total, self.ntrees, self.max_count, n)
-            d_mp = tmp.alloc(lib.vkmr_hip_forest_multiproof_scratch_bytes(n, self.levels))
-            d_nodes, d_h, d_info = tmp.alloc(32 * cap), tmp.alloc(4 * n), tmp.alloc(8 * (2 + self.levels))
-            self.multiproof_async(se.trees, se.indices, n, d_mp, d_nodes, cap, d_h, d_info)
-            info = self.dev.download(d_info, 8 * (2 + self.levels), dtype=np.uint64)
-            if int(info[0]):
-                raise RuntimeError(f"MerkleForest.multiproof_of: the device refused its own sorted entries "
-                                   f"(status {int(info[0])}: {forest_multiproof_status_text(int(info[0]))})")
-            m = int(info[1])
-            nodes = self.dev.download(d_nodes, 32 * m).reshape(m, 8) if m else np.zeros((0, 8), dtype=np.uint32)
-            st, si = self.dev.download(se.trees, 4 * n), self.dev.download(se.indices, 8 * n, dtype=np.uint64)
-            heights, order = self.dev.download(d_h, 4 * n), self.dev.download(se.order, 4 * n)
-        return ForestMultiproof(st, si, heights, nodes, info[2:].copy(), self.levels), order
+        return self._update_entries((trees_buf, indices_buf), leaves_buf, k)
 
     def _same_shape(self, other, what):
         """ValueError unless `other` is a MerkleForest of this forest's device, counts, cells and max_count; no device call."""
@@ -1367,38 +1203,6 @@ class MerkleForest:
         self._same_shape(other, "diff_async")
         self.dev.forest_diff_async(self.digests, self.forest, self.roots_buf, other.digests, other.forest, other.roots_buf, self.total, self.offsets,
                                    self.ntrees, self.max_count, scratch_buf, trees_buf, indices_buf, leaves_buf, capacity, info_buf, stream=stream)
-
-    def _diff(self, tmp, other, capacity, leaves, what):
-        self._same_shape(other, what)
-        if self.ntrees == 0:                      # the call does nothing and writes no counters
-            return 0, None, None, None
-        return _run_diff(self.dev, tmp, lambda scr, t, idx, lv, cap, info: self.diff_async(other, scr, t, idx, lv, cap, info), self.total, capacity,
-                         True, leaves, what)
-
-    def diff(self, other, capacity=None):
-        """(trees uint32 [n], indices uint64 [n]): the leaves in which this forest and `other` differ, as strictly increasing
-        (tree, index) pairs.  capacity None: room for min(total, 65536) answers first, 16 times more while more differ; an
-        integer: DiffOverflow when more differ.  ValueError for a forest of another device, other counts or another max_count,
-        before any device call."""
-        with self.dev.scope() as tmp:
-            n, d_trees, d_idx, _ = self._diff(tmp, other, capacity, False, "diff")
-            if n == 0:
-                return np.zeros(0, dtype=np.uint32), np.zeros(0, dtype=np.uint64)
-            return self.dev.download(d_trees, 4 * n), self.dev.download(d_idx, 8 * n, dtype=np.uint64)
-
-    def sync_from(self, other):
-        """Make this forest equal to `other`: the diff with other's leaves at the differing positions, then the update of
-        exactly those, all on the device; the 32 bytes of counters are what comes back.  The number of leaves written."""
-        with self.dev.scope() as tmp:
-            n, d_trees, d_idx, d_leaves = self._diff(tmp, other, None, True, "sync_from")
-            if n:
-                d_status = tmp.alloc(4)
-                self.update_async(d_trees, d_idx, d_leaves, n, d_status)
-                status = int(self.dev.download(d_status, 4)[0])
-                if status:
-                    raise RuntimeError(f"MerkleForest.sync_from: the device refused the diff's own entries "
-                                       f"(status {status}: {forest_update_status_text(status)})")
-            return n
 
     def free(self):
         for b in [self.forest, self.roots_buf, self.offsets] + self._owned:
@@ -1474,14 +1278,14 @@ def forest_multiproof_status_text(status):
     return "; ".join(names) if names else "ok"
 
 
-def _forest_packed(dev, batch, counts, max_count, what, stored):
-    """`batch` mapped to leaf digests ONCE and one forest call over them: the roots, or with `stored` a MerkleForest that
-    owns its leaves."""
+def _forest_packed(dev, batch, counts, max_count, what, stored, mutated=False):
+    """`batch` mapped to leaf digests ONCE and one forest call over them: the roots (with `mutated`: and the masks), or with
+    `stored` a MerkleForest that owns its leaves."""
     _checked_offsets(counts, batch.count, what, "strings")
     with dev.scope() as tmp:
         d_leaves = dev.map_packed(tmp, batch) if batch.count else None
         if not stored:
-            return dev._forest_of_buffer(d_leaves, batch.count, counts, max_count, what)
+            return dev._forest_of_buffer(d_leaves, batch.count, counts, max_count, what, mutated=mutated)
         forest = dev._build_forest_of_buffer(d_leaves, batch.count, counts, max_count, what, owned=[d_leaves] if d_leaves else [])
         tmp.release(d_leaves)
     return forest
@@ -1504,10 +1308,7 @@ def merkle_roots_packed_forest_mutated(dev, batch, counts, max_count=None):
     """merkle_roots_packed_forest with the verdict on every block: (roots [ntrees, 8] uint32, mutated [ntrees] uint64), bit l
     of mutated[t] set when level l of tree t holds two equal siblings that both exist (HipDevice.forest_roots_mutated).  The
     strings are mapped ONCE and ONE flagged forest call reduces them; no digest goes through the host."""
-    what = "merkle_roots_packed_forest_mutated"
-    _checked_offsets(counts, batch.count, what, "strings")
-    with dev.scope() as tmp:
-        return dev._forest_mutated_of_buffer(dev.map_packed(tmp, batch) if batch.count else None, batch.count, counts, max_count, what)
+    return _forest_packed(dev, batch, counts, max_count, "merkle_roots_packed_forest_mutated", stored=False, mutated=True)
 
 
 def digest_hex(words):
