@@ -730,6 +730,63 @@ VKMR_API vkmr_status vkmr_hip_tree_diff_async(int dev, vkmr_stream s, const vkmr
                                               uint64_t* info_dev);
 
 /*
+ * AUDIT A STORED FOREST IN PLACE ("which nodes are not the hash of their children?"; the reference has no counterpart): the
+ * fsck of what vkmr_hip_reduce_forest_tree_async built and the update calls rewrote.  With S(0, i) leaf i of tree t, and S(l, j)
+ * for 1 <= l <= h_t = max(1, ceil(log2 c_t)) the STORED cell of node j of tree t's level l -- roots_dev[t] for l == h_t, else
+ * cell stored_level_base(l) + pos_l(t) + j of forest_dev -- node (t, l, j) is BAD when
+ *     S(l, j) != hash_pair(S(l - 1, 2j), S(l - 1, right_child(j, n_{l-1}))),
+ * the children as they are stored NOW, not as a rebuild would make them.  An empty tree has one checkable node, (t, 1, 0), bad
+ * when roots_dev[t] is not all zero.  So one flipped inner cell gives two bad nodes (the cell and its parent), a flipped root or
+ * leaf one, and an inner node replaced with every ancestor rehashed consistently exactly one.  No bad node <=> the levels and
+ * roots are cell for cell what a rebuild from the current leaves would write (induction over the levels).  Cells of a level
+ * buffer that are no node of a tree are never read and never reported.
+ *   masks_dev      ntrees uint64_t: bit l - 1 of masks_dev[t] set when level l of tree t holds a bad node (mutated_dev's shape)
+ *   bad_trees_dev, bad_levels_dev (uint32_t), bad_nodes_dev (uint64_t)   `capacity` cells each: the bad nodes in strictly
+ *                  increasing (level, tree, node) order, the first `capacity` of them; nothing is written behind the list or
+ *                  behind `capacity`
+ *   capacity       0 is legal, the three lists and scratch_dev may then be NULL: masks and counters only, one launch per level
+ *   info_dev       4 uint64_t of device memory, always written when ntrees > 0:
+ *     [0] status: bits 0 and 1 are vkmr_hip_reduce_forest_async's (offsets decreasing or past `total`; a tree above max_count):
+ *         nothing is audited, the masks are all zero and no entry is written; bit 2 (value 4): capacity > 0 and more than
+ *         `capacity` nodes are bad -- the first `capacity` entries are there
+ *     [1] the bad nodes, the true count also above `capacity`
+ *     [2] the trees with a nonzero mask
+ *     [3] the nodes checked: every node of levels 1 .. h_t of every tree, one for an empty tree
+ *   scratch_dev    vkmr_hip_audit_scratch_bytes(total, ntrees, capacity) bytes of device memory, 16-byte aligned; 0 bytes for
+ *                  capacity == 0 (layout: csrc/audit_plan.hpp -- one ballot word per wavefront of cells and its ranking words)
+ * READ ONLY: the leaves, the levels, the roots and the offsets are byte for byte what they were.  The work is the build's: one
+ * hash per node, 96 bytes read for the build's 64 read and 32 written, and no second copy of anything.
+ * Launches, all on the caller's stream: the memsets, the offsets check, one launch per level 1 .. H with the build's grid; with
+ * capacity > 0 the three ranking launches of vkmr_hip_forest_multiproof_async over all the levels' ballot words as one level,
+ * then one emit launch per level.  They are a function of (total, ntrees, max_count, capacity) alone; no allocation, no host
+ * synchronisation, no host read of device data; no kernel waits for another workgroup, and no entry is appended through a
+ * counter in memory.  ntrees == 0 does nothing.  Refused on the host (VKMR_ERR_INVALID) with ntrees > 0, before any HIP call: a
+ * NULL pointer that is needed (the leaves when total > 0, the forest, the roots, the offsets, the masks, info_dev; the scratch
+ * and the three lists when capacity > 0), max_count == 0, total above 2^58, scratch_dev not 16-byte aligned, and with
+ * capacity > 0 a level of more than 2^32 - 1 cells (the masks-only form has no such limit).
+ * vkmr_host_cpu_forest_audit (libvkmr_host.so) applies the same rule on the CPU.
+ */
+VKMR_API size_t vkmr_hip_audit_scratch_bytes(uint64_t total, uint32_t ntrees, uint32_t capacity);
+VKMR_API vkmr_status vkmr_hip_forest_audit_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev,
+                                                 const vkmr_digest* forest_dev, const vkmr_digest* roots_dev, uint64_t total,
+                                                 const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count,
+                                                 void* scratch_dev, uint64_t* masks_dev, uint32_t* bad_trees_dev,
+                                                 uint32_t* bad_levels_dev, uint64_t* bad_nodes_dev, uint32_t capacity,
+                                                 uint64_t* info_dev);
+/*
+ * The same for one stored TREE (vkmr_hip_reduce_tree_async): levels 1 .. height, the root inside tree_dev; a lone-node level
+ * above ceil(log2 count) must be hash(a, a) of the node below.  Every entry is in tree 0: bad_levels_dev and bad_nodes_dev carry
+ * the list, and info_dev[2] is the tree's own level mask.  scratch_dev: vkmr_hip_audit_scratch_bytes(count, 1, capacity).
+ * count == 0 does nothing; height 0 (one leaf) has no node to check and leaves info_dev all zero.  Refused on the host: a NULL
+ * pointer that is needed, a height that does not reduce count to one node, count above 2^58, scratch_dev not 16-byte aligned,
+ * and with capacity > 0 a level of more than 2^32 - 1 cells.  vkmr_host_cpu_tree_audit is the CPU's.
+ */
+VKMR_API vkmr_status vkmr_hip_tree_audit_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev,
+                                               const vkmr_digest* tree_dev, uint64_t count, uint32_t height, void* scratch_dev,
+                                               uint32_t* bad_levels_dev, uint64_t* bad_nodes_dev, uint32_t capacity,
+                                               uint64_t* info_dev);
+
+/*
  * COMBINE: duplicate-last Merkle root over n >= 1 slice roots given in slice order, always
  * at least one level -- the rule of CpuSha256D::Root that the reference applies to the slice
  * roots on the CPU (CpuSha256DforReductions, src/vkmr/Reductions.cpp:56-69, :703-712).  Here

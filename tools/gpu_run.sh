@@ -19,6 +19,8 @@
 #   find [args]            tools/find_timing.py: the lookup by digest beside a read-only pass of torch's over as many bytes (one JSON line)
 #   diff [args]            tools/diff_timing.py: the diff of two stored forests beside torch's compare of the two level-0 buffers, and
 #                          sync_from beside a rebuild (one JSON line)
+#   audit [args]           tools/audit_timing.py: the audit of a stored forest or tree beside its build, masks only and with the list
+#                          (one JSON line), then the same run under rocprofv3 --kernel-trace --stats; stops at the first failing step
 #   cumask                 tools/cu_mask_probe.py: where CU-mask bits land, map/reduce on half the CUs with and without neighbours
 #   issue <set>            tools/issue_patterns (python3 tools/gen_issue_patterns.py <set> and a build beforehand)
 #   proofs                 tools/proof_timing.py: a slice reduced with and without proofs written in the pass
@@ -169,6 +171,15 @@ diff)
   timeout -k 10 500 python3 tools/diff_timing.py "$@" --out $OUT/diff_timing.json > /dev/null 2> $OUT/diff_timing.err && echo "diff_timing ok" &&
   cat $OUT/diff_timing.json
   echo "diff rc=$?"
+  ;;
+audit)
+  timeout -k 10 500 python3 tools/audit_timing.py "$@" --out $OUT/audit_timing.json > /dev/null 2> $OUT/audit_timing.err && echo "audit_timing ok" &&
+  cat $OUT/audit_timing.json &&
+  repo=$(pwd) &&
+  ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d $repo/$OUT/prof_audit -- python3 $repo/tools/audit_timing.py "$@" --runs 3 > $repo/$OUT/audit_prof.json 2> $repo/$OUT/audit_prof.err ) &&
+  find $OUT/prof_audit -name "*kernel_stats.csv" -exec cp {} $OUT/audit_kernel_stats.csv \; &&
+  cat $OUT/audit_kernel_stats.csv
+  echo "audit rc=$?"
   ;;
 cumask)
   hipcc --offload-arch=gfx950 -O2 -shared -fPIC -o tools/libwhere.so tools/where.hip

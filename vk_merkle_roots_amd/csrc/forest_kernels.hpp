@@ -30,6 +30,37 @@ __global__ __launch_bounds__(256) void forest_check_kernel(const uint64_t* __res
     if (bits) atomicOr(status, bits);
 }
 
+// ---- the search every level kernel of a forest begins with (forest_level below, audit_kernels.hpp) -----------------------------
+// The tree of lane `lane`'s cell p0 + lane of level l, p0 the wavefront's first cell; `mixed` (wave-uniform) says that a tree
+// begins inside the wavefront, so that its lanes may hold different trees.
+struct ForestLane {
+    uint32_t t;
+    bool mixed;
+};
+
+__device__ __forceinline__ ForestLane forest_find_tree(const uint64_t* __restrict__ offsets, uint32_t ntrees, uint32_t l, uint64_t p0, uint32_t lane)
+{
+    // the tree of the wavefront's first cell: the largest t0 with pos_l(t0) <= p0 (0 when there is none)
+    uint32_t t0 = 0, top = ntrees - 1u;
+    while (t0 < top) {
+        const uint32_t mid = t0 + (top - t0 + 1u) / 2u;
+        if (vkmr_forest::pos(offsets[mid], mid, l) <= p0) t0 = mid;
+        else top = mid - 1u;
+    }
+    const uint64_t p = p0 + lane;
+    uint32_t t = t0;
+    const bool mixed = t0 + 1u < ntrees && vkmr_forest::pos(offsets[t0 + 1u], t0 + 1u, l) <= p0 + 63ull;   // wave-uniform: a tree begins inside the wavefront
+    if (mixed) {
+        top = (ntrees - 1u - t0 < lane) ? ntrees - 1u : t0 + lane;
+        while (t < top) {
+            const uint32_t mid = t + (top - t + 1u) / 2u;
+            if (vkmr_forest::pos(offsets[mid], mid, l) <= p) t = mid;
+            else top = mid - 1u;
+        }
+    }
+    return {t, mixed};
+}
+
 // ---- one level of a forest: the body of the three level kernels below ------------------------------------------------------
 // Level l >= 1 from level l - 1 (`in`: the leaves for l == 1, else the buffer of level l - 1), `cells` lanes, in entries.hpp's
 // manner: one body, and a __global__ kernel is its arguments and the call.  Two compile-time switches say what a lane does with
@@ -58,24 +89,10 @@ __device__ __forceinline__ void forest_level(const Node* __restrict__ in, const 
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t p0 = ((uint64_t)blockIdx.x * (256u / 64u) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))) * 64ull;
     if (p0 >= cells) return;                     // wave-uniform
-    // the tree of the wavefront's first cell: the largest t0 with pos_l(t0) <= p0 (0 when there is none)
-    uint32_t t0 = 0, top = ntrees - 1u;
-    while (t0 < top) {
-        const uint32_t mid = t0 + (top - t0 + 1u) / 2u;
-        if (vkmr_forest::pos(offsets[mid], mid, l) <= p0) t0 = mid;
-        else top = mid - 1u;
-    }
     const uint64_t p = p0 + lane;
-    uint32_t t = t0;
-    const bool mixed = t0 + 1u < ntrees && vkmr_forest::pos(offsets[t0 + 1u], t0 + 1u, l) <= p0 + 63ull;   // wave-uniform: a tree begins inside the wavefront
-    if (mixed) {
-        top = (ntrees - 1u - t0 < lane) ? ntrees - 1u : t0 + lane;
-        while (t < top) {
-            const uint32_t mid = t + (top - t + 1u) / 2u;
-            if (vkmr_forest::pos(offsets[mid], mid, l) <= p) t = mid;
-            else top = mid - 1u;
-        }
-    }
+    const ForestLane at = forest_find_tree(offsets, ntrees, l, p0, lane);
+    const uint32_t t = at.t;
+    const bool mixed = at.mixed;
     const uint64_t o = offsets[t], c = offsets[t + 1u] - o;
     const uint64_t first = vkmr_forest::pos(o, t, l);
     if (p < first) return;                       // cells in front of tree 0 (offsets[0] > 0)

@@ -5,6 +5,7 @@
 #include <cstring>
 #include <vector>
 
+#include "../audit_plan.hpp"   // forest_plan.hpp, tree_plan.hpp: where the stored levels lie
 #include "../merkle_math.hpp"
 #include "cpu_sha256d.hpp"
 #include "vkmr_hip.h"
@@ -496,6 +497,95 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_tree_sort_entries(uint6
     if (k == 0) return 0;
     const uint64_t offsets[2] = {0, count};
     return sort_entries_cpu(count, offsets, 1, nullptr, indices, k, nullptr, indices_out, order_out, info);
+}
+
+// A stored forest audited on the CPU, by the rule of vkmr_hip_forest_audit_async and with its outputs: node (t, l, j) is bad when
+// its stored cell -- roots[t] for the tree's last level, else cell stored_level_base(l) + pos_l(t) + j of `forest` -- is not
+// hash_pair of the two stored cells beneath it; an empty tree's root must be all zero.  masks[t] bit l - 1, the first
+// `capacity` bad nodes in (level, tree, node) order, info[0..4) = status (bits 0, 1: the offsets and max_count check, and then
+// nothing is audited; bit 2: more than `capacity` > 0 bad nodes), bad nodes, trees with a nonzero mask, nodes checked.  Reads
+// only.  -1, and nothing written, when a needed pointer is missing, max_count is 0 or total is above 2^58.
+__attribute__((visibility("default"))) int vkmr_host_cpu_forest_audit(const vkmr_digest* digests, const vkmr_digest* forest, const vkmr_digest* roots,
+                                                                       uint64_t total, const uint64_t* offsets, uint32_t ntrees, uint64_t max_count,
+                                                                       uint64_t* masks, uint32_t* bad_trees, uint32_t* bad_levels, uint64_t* bad_nodes,
+                                                                       uint32_t capacity, uint64_t* info)
+{
+    if (ntrees == 0) return 0;
+    if ((!digests && total > 0) || !forest || !roots || !offsets || !masks || !info || (capacity > 0 && (!bad_trees || !bad_levels || !bad_nodes)))
+        return -1;
+    if (max_count == 0 || total > (1ull << 58)) return -1;
+    if (max_count > total) max_count = total;
+    info[0] = info[1] = info[2] = info[3] = 0;
+    std::memset(masks, 0, sizeof(uint64_t) * ntrees);
+    for (uint32_t t = 0; t < ntrees; ++t) {
+        if (offsets[t + 1] < offsets[t] || (t + 1 == ntrees && offsets[t + 1] > total)) info[0] |= 1u;
+        if (offsets[t + 1] >= offsets[t] && offsets[t + 1] - offsets[t] > max_count) info[0] |= 2u;
+    }
+    if (info[0]) return 0;
+    const uint32_t H = vkmr_forest::launches(total, max_count);
+    static const vkmr_digest zero = {{0, 0, 0, 0, 0, 0, 0, 0}};
+    for (uint32_t l = 1; l <= H; ++l) {
+        const vkmr_digest* in = l == 1 ? digests : forest + vkmr_forest::stored_level_base(total, ntrees, l - 1);
+        const vkmr_digest* out = forest + vkmr_forest::stored_level_base(total, ntrees, l);
+        for (uint32_t t = 0; t < ntrees; ++t) {
+            const uint64_t o = offsets[t], c = offsets[t + 1] - o;
+            const uint64_t n_in = vkmr_forest::level_count(c, l - 1), n_out = vkmr_forest::level_count(c, l);
+            const bool empty = c == 0 && l == 1;
+            if (!empty && (c == 0 || (l > 1 && n_in == 1))) continue;   // no such level in this tree
+            for (uint64_t j = 0; j < (empty ? 1 : n_out); ++j) {
+                const vkmr_digest* stored = (empty || n_out == 1) ? roots + t : out + vkmr_forest::pos(o, t, l) + j;
+                vkmr_digest want = zero;
+                if (!empty) {
+                    const vkmr_digest* level = in + vkmr_forest::pos(o, t, l - 1);
+                    vkmr::cpu_sha256d_pair(level[2 * j].data, level[vkmr_math::right_child(j, n_in)].data, want.data);
+                }
+                ++info[3];
+                if (std::memcmp(want.data, stored->data, 32) == 0) continue;
+                if (masks[t] == 0) ++info[2];
+                masks[t] |= 1ull << (l - 1);
+                if (info[1] < capacity) {
+                    bad_trees[info[1]] = t;
+                    bad_levels[info[1]] = l;
+                    bad_nodes[info[1]] = j;
+                }
+                ++info[1];
+            }
+        }
+    }
+    if (capacity > 0 && info[1] > capacity) info[0] |= 4u;
+    return 0;
+}
+
+// The same for one stored tree (vkmr_hip_tree_audit_async): levels 1 .. height in `tree` as tree_plan.hpp lays them out, a
+// lone-node level above ceil(log2 count) being hash(a, a) of the node below; info[2] is the tree's own level mask.  -1 when a
+// needed pointer is missing or `height` does not reduce `count` to one node.
+__attribute__((visibility("default"))) int vkmr_host_cpu_tree_audit(const vkmr_digest* digests, const vkmr_digest* tree, uint64_t count, uint32_t height,
+                                                                     uint32_t* bad_levels, uint64_t* bad_nodes, uint32_t capacity, uint64_t* info)
+{
+    if (count == 0) return 0;
+    if (!digests || (height > 0 && !tree) || !info || (capacity > 0 && (!bad_levels || !bad_nodes))) return -1;
+    if (height > 63 || count > (1ull << 58) || vkmr_math::ceil_shift(count, height) != 1) return -1;
+    info[0] = info[1] = info[2] = info[3] = 0;
+    uint64_t off[VKMR_TREE_MAX_LEVELS];
+    vkmr_tree::levels(count, height, off);
+    for (uint32_t l = 1; l <= height; ++l) {
+        const vkmr_digest* in = l == 1 ? digests : tree + off[l - 1];
+        const uint64_t n_in = vkmr_math::ceil_shift(count, l - 1), n_out = vkmr_math::ceil_shift(count, l);
+        for (uint64_t j = 0; j < n_out; ++j) {
+            vkmr_digest want;
+            vkmr::cpu_sha256d_pair(in[2 * j].data, in[vkmr_math::right_child(j, n_in)].data, want.data);
+            ++info[3];
+            if (std::memcmp(want.data, tree[off[l] + j].data, 32) == 0) continue;
+            info[2] |= 1ull << (l - 1);
+            if (info[1] < capacity) {
+                bad_levels[info[1]] = l;
+                bad_nodes[info[1]] = j;
+            }
+            ++info[1];
+        }
+    }
+    if (capacity > 0 && info[1] > capacity) info[0] |= 4u;
+    return 0;
 }
 
 }  // extern "C"

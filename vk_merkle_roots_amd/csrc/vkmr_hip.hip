@@ -28,6 +28,9 @@
 //   diff_kernels.hpp    *_diff_roots_count_kernel, *_diff_roots_emit_kernel, *_diff_mask_kernel, *_diff_emit_kernel   the leaves that differ
 //                                              between two stored forests or trees of one shape: a descent from the roots, the frontier
 //                                              ranked by the multiproof's ranking kernels at every step (steps and sizes: diff_plan.hpp)
+//   audit_kernels.hpp   *_audit_level_kernel, *_audit_emit_kernel   the nodes of a stored forest or tree that are not the hash of their
+//                                              stored children: the build's launches with a compare for the store, the bad nodes ranked
+//                                              by the multiproof's ranking kernels (sizes: audit_plan.hpp)
 //   sha256d_device.hpp  the SHA-256 round / compression building blocks, and the tree's: hash_parent, node_diff, store_node
 //   merkle_math.hpp     the integer rules, no HIP types (ceil_shift, height, right_child, sibling): shared with host/ and tests/c
 //   meta_kernels.hpp    sizes_*_kernel         metadata entries from 16-bit sizes   (Batches.cpp:64-121)
@@ -40,6 +43,7 @@
 //   find_plan.hpp       the lookup's scratch layout and scan grid
 //   sort_plan.hpp       the entry sort's passes, tiles, histogram words and scratch layout
 //   diff_plan.hpp       one step of a diff's descent, the bound on every step's frontier and the scratch layout
+//   audit_plan.hpp      the ballot words of an audit's levels, the nodes it checks and the scratch layout
 //
 // Host side: plain launches on the caller's stream, each through launch() and so each checked; every argument refusal
 // through refuse(__func__, why); no allocation, no sync inside the *_async entry points.
@@ -72,6 +76,7 @@ using vkmr_dev::Node;
 #include "find_kernels.hpp"
 #include "sort_kernels.hpp"
 #include "diff_kernels.hpp"
+#include "audit_kernels.hpp"
 
 // ============================================================================
 // C ABI
@@ -1440,6 +1445,112 @@ vkmr_status vkmr_hip_tree_diff_async(int dev, vkmr_stream s, const vkmr_digest* 
         VKMR_CHECK(diff_rank_launch(S(s), sc, words, capacity));
         VKMR_CHECK(launch(tree_diff_emit_kernel, grid_of(bound), block, S(s), db, sc.node[in], step, bound, sc.mask, sc.word_start, sc.hdr,
                           last ? indices_out_dev : sc.node[out], last ? nodes(leaves_b_out_dev) : (Node*)nullptr, info_dev, last ? 1u : 0u));
+    }
+    return VKMR_OK;
+}
+
+// ---- the nodes of a stored forest or tree that are not the hash of their children (audit_kernels.hpp, audit_plan.hpp) -------------
+
+static_assert(VKMR_AUDIT_RANK_BLOCK_WORDS == VKMR_MP_BLOCK_WORDS, "the ballot words are ranked by the multiproof's ranking kernels");
+static_assert(VKMR_AUDIT_HEADER_WORDS >= 2 + 1, "the ranking's header of one level");
+static_assert(VKMR_AUDIT_THREADS == 256u, "grid_of() counts workgroups of 256");
+
+size_t vkmr_hip_audit_scratch_bytes(uint64_t total, uint32_t ntrees, uint32_t capacity) { return vkmr_audit::scratch_bytes(total, ntrees, capacity); }
+
+// The parts of an audit's scratch_dev (audit_plan.hpp) as the kernels take them; all null for the masks-only form.
+struct AuditScratch {
+    uint64_t *mask, *word_start, *block, *hdr;
+    AuditScratch(void* scratch_dev, const vkmr_audit::Layout& L, uint32_t capacity)
+    {
+        char* at = capacity ? static_cast<char*>(scratch_dev) : nullptr;
+        mask = at ? reinterpret_cast<uint64_t*>(at + L.mask) : nullptr;
+        word_start = at ? reinterpret_cast<uint64_t*>(at + L.word_start) : nullptr;
+        block = at ? reinterpret_cast<uint64_t*>(at + L.block) : nullptr;
+        hdr = at ? reinterpret_cast<uint64_t*>(at + L.hdr) : nullptr;
+    }
+};
+
+// The ranking of the `words` ballot words a call left: the multiproof's three launches with one level and no limit -- the
+// emit launches cut the list at `capacity` themselves, so that the first `capacity` entries are written also when there are more.
+static vkmr_status audit_rank_launch(hipStream_t stream, const AuditScratch& sc, uint64_t words)
+{
+    const uint64_t blocks = vkmr_audit::rank_blocks(words);
+    const dim3 wgrid((uint32_t)blocks, 1), wblock(VKMR_MP_BLOCK_WORDS);
+    VKMR_CHECK(launch(multiproof_block_sums_kernel, wgrid, wblock, stream, sc.mask, words, blocks, sc.block));
+    VKMR_CHECK(launch(multiproof_block_starts_kernel, dim3(1), dim3(256), stream, sc.block, blocks, 1u, ~0ull, 0u, sc.hdr));
+    return launch(multiproof_word_starts_kernel, wgrid, wblock, stream, sc.mask, words, blocks, sc.block, sc.hdr, sc.word_start);
+}
+
+vkmr_status vkmr_hip_forest_audit_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* forest_dev, const vkmr_digest* roots_dev,
+                                        uint64_t total, const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count, void* scratch_dev,
+                                        uint64_t* masks_dev, uint32_t* bad_trees_dev, uint32_t* bad_levels_dev, uint64_t* bad_nodes_dev, uint32_t capacity,
+                                        uint64_t* info_dev)
+{
+    if (ntrees == 0) return VKMR_OK;
+    if ((!digests_dev && total > 0) || !forest_dev || !roots_dev || !offsets_dev || !masks_dev || !info_dev ||
+        (capacity > 0 && (!scratch_dev || !bad_trees_dev || !bad_levels_dev || !bad_nodes_dev)))
+        return refuse(__func__, "null pointer");
+    VKMR_CHECK(forest_args_check(__func__, total, ntrees, max_count, 0, nullptr, capacity ? scratch_dev : nullptr));
+    const uint64_t cells1 = vkmr_forest::level_cells(total, ntrees, 1);
+    if (grid_too_large(groups_of(cells1))) return refuse(__func__, "forest too large");
+    if (capacity > 0 && cells1 > vkmr_audit::MAX_LIST_CELLS) return refuse(__func__, "a level of more than 2^32 - 1 cells cannot be listed: capacity must be 0");
+    if (max_count > total) max_count = total;
+    const uint32_t H = vkmr_forest::launches(total, max_count);   // <= 58
+    const AuditScratch sc(scratch_dev, vkmr_audit::layout(total, ntrees, capacity), capacity);
+    const Node *digests = nodes(digests_dev), *forest = nodes(forest_dev), *roots = nodes(roots_dev);
+    const dim3 block(VKMR_AUDIT_THREADS);
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_TRY(hipMemsetAsync(info_dev, 0, 4 * sizeof(uint64_t), S(s)));
+    VKMR_TRY(hipMemsetAsync(masks_dev, 0, sizeof(uint64_t) * ntrees, S(s)));
+    if (capacity) VKMR_TRY(hipMemsetAsync(sc.hdr, 0, VKMR_AUDIT_HEADER_WORDS * sizeof(uint64_t), S(s)));
+    VKMR_CHECK(launch(forest_check_kernel, grid_of(ntrees), dim3(256), S(s), offsets_dev, ntrees, total, max_count, reinterpret_cast<uint32_t*>(info_dev)));
+    for (uint32_t l = 1; l <= H; ++l) {   // level l against level l - 1, both as they are stored
+        const Node* in = (l == 1) ? digests : forest + vkmr_forest::stored_level_base(total, ntrees, l - 1);
+        const uint64_t cells = vkmr_forest::level_cells(total, ntrees, l);
+        VKMR_CHECK(launch(forest_audit_level_kernel, grid_of(cells), block, S(s), in, forest + vkmr_forest::stored_level_base(total, ntrees, l), roots,
+                          offsets_dev, ntrees, l, cells, masks_dev, capacity ? sc.mask + vkmr_audit::forest_word_base(total, ntrees, l) : (uint64_t*)nullptr,
+                          info_dev));
+    }
+    if (capacity == 0) return VKMR_OK;
+    VKMR_CHECK(audit_rank_launch(S(s), sc, vkmr_audit::forest_word_base(total, ntrees, H + 1u)));
+    for (uint32_t l = 1; l <= H; ++l) {
+        const uint64_t cells = vkmr_forest::level_cells(total, ntrees, l), base = vkmr_audit::forest_word_base(total, ntrees, l);
+        VKMR_CHECK(launch(forest_audit_emit_kernel, grid_of(cells), block, S(s), offsets_dev, ntrees, l, cells, sc.mask + base, sc.word_start + base,
+                          bad_trees_dev, bad_levels_dev, bad_nodes_dev, capacity, info_dev, l == H ? 1u : 0u));
+    }
+    return VKMR_OK;
+}
+
+vkmr_status vkmr_hip_tree_audit_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* tree_dev, uint64_t count, uint32_t height,
+                                      void* scratch_dev, uint32_t* bad_levels_dev, uint64_t* bad_nodes_dev, uint32_t capacity, uint64_t* info_dev)
+{
+    if (count == 0) return VKMR_OK;
+    if (!digests_dev || (height > 0 && !tree_dev) || !info_dev || (capacity > 0 && (!scratch_dev || !bad_levels_dev || !bad_nodes_dev)))
+        return refuse(__func__, "null pointer");
+    if (!height_ok(count, height)) return refuse(__func__, "height does not reduce count to one node");
+    if (count > (1ull << 58) || grid_too_large(groups_of(ceil_shift(count, 1)))) return refuse(__func__, "too many leaves");
+    if (capacity > 0 && (reinterpret_cast<uintptr_t>(scratch_dev) & 15u)) return refuse(__func__, "scratch must be 16-byte aligned");
+    if (capacity > 0 && ceil_shift(count, 1) > vkmr_audit::MAX_LIST_CELLS)
+        return refuse(__func__, "a level of more than 2^32 - 1 cells cannot be listed: capacity must be 0");
+    const TreeLevels lv = tree_levels(count, height);
+    const AuditScratch sc(scratch_dev, vkmr_audit::layout(count, 1u, capacity), capacity);
+    const Node *digests = nodes(digests_dev), *tree = nodes(tree_dev);
+    const dim3 block(VKMR_AUDIT_THREADS);
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_TRY(hipMemsetAsync(info_dev, 0, 4 * sizeof(uint64_t), S(s)));
+    if (height == 0) return VKMR_OK;   // one leaf, no level: the root is the leaf, and there is no node to check
+    if (capacity) VKMR_TRY(hipMemsetAsync(sc.hdr, 0, VKMR_AUDIT_HEADER_WORDS * sizeof(uint64_t), S(s)));
+    for (uint32_t l = 1; l <= height; ++l) {
+        const uint64_t n_in = ceil_shift(count, l - 1), n_out = ceil_shift(count, l);
+        VKMR_CHECK(launch(tree_audit_level_kernel, grid_of(n_out), block, S(s), l == 1 ? digests : tree + lv.off[l - 1], tree + lv.off[l], n_in, n_out, l,
+                          capacity ? sc.mask + vkmr_audit::tree_word_base(count, l) : (uint64_t*)nullptr, info_dev));
+    }
+    if (capacity == 0) return VKMR_OK;
+    VKMR_CHECK(audit_rank_launch(S(s), sc, vkmr_audit::tree_word_base(count, height + 1u)));
+    for (uint32_t l = 1; l <= height; ++l) {
+        const uint64_t n_out = ceil_shift(count, l), base = vkmr_audit::tree_word_base(count, l);
+        VKMR_CHECK(launch(tree_audit_emit_kernel, grid_of(n_out), block, S(s), n_out, l, sc.mask + base, sc.word_start + base, bad_levels_dev, bad_nodes_dev,
+                          capacity, info_dev, l == height ? 1u : 0u));
     }
     return VKMR_OK;
 }

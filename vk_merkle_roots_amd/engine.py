@@ -584,6 +584,30 @@ class HipDevice:
         self._call("vkmr_hip_tree_diff_async", digests_a_buf, tree_a_buf, digests_b_buf, tree_b_buf, count, height, scratch_buf, indices_buf,
                    leaves_buf, capacity, info_buf, stream=stream)
 
+    # -- a stored forest or tree audited in place: the nodes that are not the hash of their stored children -----
+    def audit_scratch_bytes(self, total, ntrees, capacity):
+        """Scratch of an audit with room for `capacity` listed nodes: 0 for capacity 0; a tree: (count, 1, capacity)."""
+        return self.lib.vkmr_hip_audit_scratch_bytes(total, ntrees, capacity)
+
+    # The two wrappers below are asynchronous like every *_async wrapper above.  They do not carry that suffix because the
+    # *_async wrappers of this class are a closed list, recorded call by call in tests/golden/engine_calls.json
+    # (tests/test_engine_calls.py); tests/test_audit_abi.py pins what these two hand to the ABI in the same way.
+    def forest_audit_enqueue(self, digests_buf, forest_buf, roots_buf, total, offsets_buf, ntrees, max_count, scratch_buf, masks_buf, trees_buf,
+                             levels_buf, nodes_buf, capacity, info_buf, stream=None):
+        """masks_buf[t] (uint64) bit l - 1 = level l of tree t holds a node that is not hash_pair of its two stored children;
+        cells [0, min(n, capacity)) of trees_buf / levels_buf (uint32) and nodes_buf (uint64) = the bad nodes in increasing
+        (level, tree, node) order; info_buf: 4 uint64 = status (bits 0, 1: the offsets check; bit 2: more than `capacity` > 0),
+        n, trees with a nonzero mask, nodes checked.  capacity 0: masks and counters only, the lists and scratch_buf may be
+        None.  Reads only.  All in device memory; scratch_buf: audit_scratch_bytes(total, ntrees, capacity).  include/vkmr_hip.h."""
+        self._call("vkmr_hip_forest_audit_async", digests_buf, forest_buf, roots_buf, total, offsets_buf, ntrees, max_count, scratch_buf, masks_buf,
+                   trees_buf, levels_buf, nodes_buf, capacity, info_buf, stream=stream)
+
+    def tree_audit_enqueue(self, digests_buf, tree_buf, count, height, scratch_buf, levels_buf, nodes_buf, capacity, info_buf, stream=None):
+        """forest_audit_enqueue for one stored tree of `count` leaves and `height` levels: levels and nodes alone, and
+        info_buf[2] is the tree's own level mask.  scratch_buf: audit_scratch_bytes(count, 1, capacity)."""
+        self._call("vkmr_hip_tree_audit_async", digests_buf, tree_buf, count, height, scratch_buf, levels_buf, nodes_buf, capacity, info_buf,
+                   stream=stream)
+
     def reduce_scratch(self, count, levels_variant=False):
         fn = self.lib.vkmr_hip_reduce_levels_scratch_bytes if levels_variant else self.lib.vkmr_hip_reduce_scratch_bytes
         return self.alloc(fn(count))
@@ -686,6 +710,26 @@ class ForestMultiproof:
             raise ValueError(f"ForestMultiproof.split: the entries imply {at} nodes, the proof holds {self.nodes.shape[0]}")
         return {t: Multiproof(idx, np.concatenate(parts[r]).reshape(-1, 8), np.array(counts[r], dtype=np.uint64), h)
                 for r, (t, idx, h) in enumerate(runs)}
+
+
+AUDIT_MAX_CAPACITY = 2**32 - 1
+
+
+class AuditReport:
+    """What an audit of a stored tree or forest found.  `clean`: no node differs from the hash of its stored children -- the
+    levels and roots are what a rebuild from the current leaves would write.  n_bad: the bad nodes; trees / levels uint32 [m],
+    nodes uint64 [m]: the first m = min(n_bad, capacity) of them in increasing (level, tree, node) order (a tree: trees all
+    0); masks uint64 [ntrees]: bit l - 1 = level l of that tree holds a bad node; flagged: trees with a nonzero mask; checked:
+    the nodes that were hashed and compared; status: bit 2 (value 4) when the lists were cut at the capacity."""
+
+    def __init__(self, status, n_bad, flagged, checked, trees, levels, nodes, masks):
+        self.status, self.n_bad, self.flagged, self.checked = int(status), int(n_bad), int(flagged), int(checked)
+        self.trees, self.levels, self.nodes, self.masks = trees, levels, nodes, masks
+        self.clean = self.n_bad == 0
+
+    def __repr__(self):
+        listed = ", ".join(f"(t={t}, l={l}, j={j})" for t, l, j in zip(self.trees.tolist(), self.levels.tolist(), self.nodes.tolist()))
+        return f"AuditReport(clean={self.clean}, n_bad={self.n_bad}, checked={self.checked}, bad=[{listed}])"
 
 
 def _empty(columns):
@@ -919,6 +963,41 @@ class _Stored:
                 self._apply(tmp, "sync_from", "the diff's own entries", d_entries, d_leaves, n)
             return n
 
+    def _audit(self, tmp, cap):
+        """One audit with room for `cap` listed nodes in the scope `tmp`, the 32 bytes of its info read back: the report."""
+        columns = self._audit_columns
+        nothing = (None,) * len(columns)
+        d_masks = tmp.alloc(8 * self.ntrees) if self._audit_masks else None
+        d_lists = self._alloc(tmp, columns, cap) if cap else nothing
+        d_scr = tmp.alloc(self.dev.audit_scratch_bytes(self.cells, self.ntrees, cap)) if cap else None
+        d_info = tmp.alloc(32)
+        self.audit_async(d_scr, *((d_masks,) if self._audit_masks else ()), *d_lists, cap, d_info)
+        status, n_bad, third, checked = (int(x) for x in self.dev.download(d_info, 32, dtype=np.uint64))
+        if status & 3:
+            raise RuntimeError(f"{type(self).__name__}.audit: the device refused the shape (status {status}: {forest_status_text(status & 3)})")
+        m = min(n_bad, cap)
+        lists = self._read(d_lists, columns, m) if m else _empty(columns)
+        if self._audit_masks:
+            masks, flagged, trees = self.dev.download(d_masks, 8 * self.ntrees, dtype=np.uint64), third, lists[0]
+        else:
+            masks, flagged, trees = np.array([third], dtype=np.uint64), int(third != 0), np.zeros(m, dtype=np.uint32)
+        return AuditReport(status, n_bad, flagged, checked, trees, lists[-2], lists[-1], masks)
+
+    def audit(self, capacity=None):
+        """Which nodes are not the hash of their two stored children?  An AuditReport; nothing of the structure is written.
+        capacity None: the masks-only form first, and the list only when there is a bad node, sized from their number; an
+        integer: one call with room for that many (0: masks and counters alone), status bit 2 in the report when there are more."""
+        cap = 0 if capacity is None else int(capacity)
+        if not 0 <= cap <= AUDIT_MAX_CAPACITY:
+            raise ValueError("audit: capacity outside [0, 2^32)")
+        if self.ntrees == 0 or self.cells == 0 and not self._audit_masks:     # the call does nothing and writes no counters
+            return AuditReport(0, 0, 0, 0, *_empty((np.uint32, np.uint32, np.uint64)), np.zeros(self.ntrees, dtype=np.uint64))
+        with self.dev.scope() as tmp:
+            report = self._audit(tmp, cap)
+            if capacity is None and report.n_bad:
+                report = self._audit(tmp, min(report.n_bad, AUDIT_MAX_CAPACITY))
+            return report
+
 
 class MerkleTree(_Stored):
     """Every level of a duplicate-last tree, resident on the device (vkmr_hip_reduce_tree_async): level 0 is the digests
@@ -1043,6 +1122,17 @@ class MerkleTree(_Stored):
         self._same_shape(other, "diff_async")
         self.dev.tree_diff_async(self.digests, self.tree, other.digests, other.tree, self.count, self.height, scratch_buf, indices_buf, leaves_buf,
                                  capacity, info_buf, stream=stream)
+
+    _audit_masks = False          # the tree's one level mask comes back in info_buf[2]
+    _audit_columns = (np.uint32, np.uint64)                  # what the list holds per bad node: level, node
+
+    def audit_async(self, scratch_buf, levels_buf, nodes_buf, capacity, info_buf, stream=None):
+        """Cells [0, min(n, capacity)) of levels_buf (uint32) / nodes_buf (uint64) = the nodes (level, node) that are not
+        hash_pair of their two stored children, in increasing order; info_buf: 4 uint64 (status, n, the level mask, nodes
+        checked).  capacity 0: counters only, the other buffers may be None.  Reads only; device memory throughout, scratch_buf
+        of dev.audit_scratch_bytes(count, 1, capacity) bytes; ordered on `stream` behind earlier updates.  include/vkmr_hip.h."""
+        self.dev.tree_audit_enqueue(self.digests, self.tree, self.count, self.height, scratch_buf, levels_buf, nodes_buf, capacity, info_buf,
+                                    stream=stream)
 
     def free(self):
         if self.tree:
@@ -1203,6 +1293,18 @@ class MerkleForest(_Stored):
         self._same_shape(other, "diff_async")
         self.dev.forest_diff_async(self.digests, self.forest, self.roots_buf, other.digests, other.forest, other.roots_buf, self.total, self.offsets,
                                    self.ntrees, self.max_count, scratch_buf, trees_buf, indices_buf, leaves_buf, capacity, info_buf, stream=stream)
+
+    _audit_masks = True
+    _audit_columns = (np.uint32, np.uint32, np.uint64)       # what the list holds per bad node: tree, level, node
+
+    def audit_async(self, scratch_buf, masks_buf, trees_buf, levels_buf, nodes_buf, capacity, info_buf, stream=None):
+        """masks_buf[t] (uint64) bit l - 1 = level l of tree t holds a node that is not hash_pair of its two stored children;
+        cells [0, min(n, capacity)) of trees_buf / levels_buf (uint32) / nodes_buf (uint64) = those nodes in increasing (level,
+        tree, node) order; info_buf: 4 uint64 (status, n, trees with a nonzero mask, nodes checked).  capacity 0: masks and
+        counters only, the lists and the scratch may be None.  Reads only; device memory throughout, scratch_buf of
+        dev.audit_scratch_bytes(total, ntrees, capacity) bytes; ordered on `stream` behind earlier updates.  include/vkmr_hip.h."""
+        self.dev.forest_audit_enqueue(self.digests, self.forest, self.roots_buf, self.total, self.offsets, self.ntrees, self.max_count, scratch_buf,
+                                      masks_buf, trees_buf, levels_buf, nodes_buf, capacity, info_buf, stream=stream)
 
     def free(self):
         for b in [self.forest, self.roots_buf, self.offsets] + self._owned:
