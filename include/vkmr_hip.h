@@ -564,6 +564,57 @@ VKMR_API vkmr_status vkmr_hip_verify_forest_multiproof_async(int dev, vkmr_strea
                                                              uint32_t* ok_dev);
 
 /*
+ * APPLYING A MULTIPROOF (the reference has no counterpart): a party that holds ONLY THE ROOTS follows leaf updates.  The
+ * primary replaces k leaves (vkmr_hip_forest_update_async) and sends the multiproof it gathered BEFORE the update, the old
+ * and the new leaves and the counts; the follower checks the old leaves against its roots and folds the new leaves up the
+ * same paths, and its roots advance without a leaf of the forest ever reaching it.  The forest form; the tree form is the
+ * same with one tree, one `count` and one `height`.
+ *   old_leaves_dev, new_leaves_dev   k cells each: the leaves at the entries before and after the update
+ *   trees_dev, indices_dev, nodes_dev, m, roots_dev, ntrees, stride   as vkmr_hip_verify_forest_multiproof_async takes them
+ *   counts_dev      k uint64_t in device memory: counts_dev[q] = c_t of entry q's tree.  Heights are not passed: the device
+ *                   derives h = max(1, ceil(log2 c)).  The tree call takes `count` and `height`, height 1..63 with
+ *                   2^height >= count, which may lie above the minimal one as in vkmr_hip_reduce_tree_async.
+ *   scratch_dev     vkmr_hip_apply_multiproof_scratch_bytes(k, stride or height) bytes of device memory, 16-byte aligned: the
+ *                   verifier's scratch in whole 16-byte units, then a second array of k cells, a second array of k uint32_t
+ *                   and k uint32_t of heights, each part starting on 16 bytes (0 for k == 0 or levels > 63)
+ *   new_roots_dev   ntrees cells (the tree call: one); may be roots_dev itself, so that a replica's roots advance in place:
+ *                   the old roots are last read before the first new root is written
+ * ok_dev[0] = 1 iff every count is >= 1, indices_dev[q] < counts_dev[q], the entries of one tree carry one count (status bit
+ * 3, as for unequal heights) and vkmr_hip_verify_forest_multiproof_async would answer 1 for (old_leaves_dev, trees_dev,
+ * indices_dev, the heights derived from the counts, stride, nodes_dev, m, roots_dev); else 0.  In the tree call a count of 0
+ * or above 2^height answers 0.  No condition is added on the node consumed at a duplicate position: with honest counts the old
+ * fold already fails when it is wrong.
+ * THE NEW SIDE.  The same fold runs over new_leaves_dev with one change.  The verifier never learns a count -- a duplicated
+ * last node arrives as an ordinary node of the proof -- which is sound for checking and wrong for applying: where a path node
+ * is the last node of an odd level, the proof carries that node's OLD value as its own sibling.  So for a left child p of tree
+ * t's level l whose sibling is not among the entries, when p + 1 >= n_l(t) = ceil(c_t / 2^l) the proof's node is still
+ * consumed, but the new side's right operand is the new side's own value of p.  Everywhere else both sides take the same node.
+ * When ok is 1 the cell new_roots_dev[t] of every tree that some entry names receives the new root; cells of trees no entry
+ * names are never written; when ok is 0 nothing is written.  ok == 1 means: the new roots are those of the forest with these
+ * counts, the old roots, and the new leaves at these positions.  The counts are no more authenticated by a root than they
+ * ever were: the ambiguity of duplicate-last trees named above is unchanged, and the `mutated` calls exist for it.
+ * Work: two node hashes per distinct (tree, index >> l) pair with 1 <= l <= h_t, over the verifier's loads plus one cell.
+ * Launches, all on the caller's stream and a function of (k, stride) alone: the status zeroed and ok set, the heights and
+ * count checks, the verifier's check, masks and ranking, one launch of 2 x k lanes per level, the verifier's finish, one
+ * commit; no allocation, no host synchronisation, no host read of device data.  Refused on the host (VKMR_ERR_INVALID) with
+ * k > 0: a NULL pointer (nodes_dev may be NULL when m == 0), stride or height outside 1..63, scratch_dev not 16-byte aligned.
+ * k == 0 does nothing.  vkmr_host_cpu_apply_multiproof and vkmr_host_cpu_apply_forest_multiproof (libvkmr_host.so) apply the
+ * same two rules on the CPU, for a follower without a GPU.
+ */
+VKMR_API size_t vkmr_hip_apply_multiproof_scratch_bytes(uint32_t k, uint32_t levels);
+VKMR_API vkmr_status vkmr_hip_apply_multiproof_async(int dev, vkmr_stream s, const vkmr_digest* old_leaves_dev,
+                                                     const vkmr_digest* new_leaves_dev, const uint64_t* indices_dev, uint32_t k,
+                                                     uint64_t count, uint32_t height, const vkmr_digest* nodes_dev, uint64_t m,
+                                                     const vkmr_digest* root_dev, void* scratch_dev, uint32_t* ok_dev,
+                                                     vkmr_digest* new_root_dev);
+VKMR_API vkmr_status vkmr_hip_apply_forest_multiproof_async(int dev, vkmr_stream s, const vkmr_digest* old_leaves_dev,
+                                                            const vkmr_digest* new_leaves_dev, const uint32_t* trees_dev,
+                                                            const uint64_t* indices_dev, const uint64_t* counts_dev, uint32_t k,
+                                                            uint32_t stride, const vkmr_digest* nodes_dev, uint64_t m,
+                                                            const vkmr_digest* roots_dev, uint32_t ntrees, void* scratch_dev,
+                                                            uint32_t* ok_dev, vkmr_digest* new_roots_dev);
+
+/*
  * FIND LEAVES BY DIGEST ("where is this hash?"; the reference has no counterpart): the step from a digest a caller holds -- a
  * txid, a file hash, an account key -- to the position every call above takes.  digests_dev, total, offsets_dev and ntrees
  * as in vkmr_hip_reduce_forest_async; the call TRUSTS the offsets as vkmr_hip_forest_proofs_async does (non-decreasing,

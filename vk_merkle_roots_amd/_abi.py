@@ -97,6 +97,12 @@ SIGNATURES = {
                                                    C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "vkmr_hip_verify_forest_multiproof_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
                                                           C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "vkmr_hip_apply_multiproof_scratch_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
+    "vkmr_hip_apply_multiproof_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32,
+                                                  C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vkmr_hip_apply_forest_multiproof_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32,
+                                                         C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                         C.c_void_p]),
     "vkmr_hip_find_scratch_bytes": (C.c_size_t, [C.c_uint32]),
     "vkmr_hip_forest_find_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p,
                                              C.c_void_p, C.c_void_p]),
@@ -145,6 +151,10 @@ HOST_SIGNATURES = {
                                                   C.c_uint64, C.c_void_p, C.c_void_p]),
     "vkmr_host_cpu_verify_forest_multiproof": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64,
                                                          C.c_void_p, C.c_uint32]),
+    "vkmr_host_cpu_apply_multiproof": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint64,
+                                                 C.c_void_p, C.c_void_p]),
+    "vkmr_host_cpu_apply_forest_multiproof": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
+                                                        C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "vkmr_host_cpu_forest_find": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "vkmr_host_cpu_tree_find": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "vkmr_host_cpu_forest_sort_entries": (C.c_int, [C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,

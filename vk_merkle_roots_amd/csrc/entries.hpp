@@ -192,8 +192,29 @@ __device__ __forceinline__ void multiproof_gather(const Entries e, const Cells c
 // For l > 0 `in` and `cell` are the same buffer, deliberately: a lane writes only its own cell and end, and reads cells that
 // no lane of this launch writes (its own before it writes it, and the cell at end[q], which lies inside P's run, not at its
 // head), so __restrict__ on both holds for every lane and the levels run in place.  One hash_pair: the only hash block.
-template <class Entries>
-__device__ __forceinline__ void multiproof_verify_level(const Entries e, const Node* __restrict__ in, Node* __restrict__ cell, uint32_t* __restrict__ end,
+//
+// `Own` is where applying a proof parts from checking it (vkmr_hip_apply_multiproof_async).  The verifier never learns a
+// count: a duplicated last node arrives as an ordinary node of the proof, the node's own OLD value.  A fold over NEW leaves
+// must take the node's own new value there, which is its own cell: own(q, p, l) says that the even node p of entry q's tree
+// has no right sibling at level l (p + 1 >= n_l).  The proof's node is consumed all the same -- the ranks do not move.
+struct NeverOwn {                                // the verifiers: every missing child is the proof's node
+    static constexpr bool substitutes = false;
+    __device__ __forceinline__ bool own(uint64_t, uint64_t, uint32_t) const { return false; }
+};
+struct TreeCountOwn {                            // one tree of `count` leaves; `side` 1 folds the new leaves
+    static constexpr bool substitutes = true;
+    uint64_t count; uint32_t side;
+    __device__ __forceinline__ bool own(uint64_t, uint64_t p, uint32_t l) const { return side != 0u && p + 1ull >= vkmr_forest::level_count(count, l); }
+};
+struct ForestCountOwn {                          // counts[q] = c_t of entry q's tree (the check: >= 1, one per tree)
+    static constexpr bool substitutes = true;
+    const uint64_t* counts; uint32_t side;
+    __device__ __forceinline__ bool own(uint64_t q, uint64_t p, uint32_t l) const { return side != 0u && p + 1ull >= vkmr_forest::level_count(counts[q], l); }
+};
+
+template <class Entries, class Own>
+__device__ __forceinline__ void multiproof_verify_level(const Entries e, const Own own, const Node* __restrict__ in, Node* __restrict__ cell,
+                                                        uint32_t* __restrict__ end,
                                                         uint32_t k, uint32_t l, uint64_t words, const uint64_t* __restrict__ mask,
                                                         const uint64_t* __restrict__ word_start, const Node* __restrict__ nodes,
                                                         const uint64_t* __restrict__ hdr)
@@ -216,6 +237,8 @@ __device__ __forceinline__ void multiproof_verify_level(const Entries e, const N
         b2 = (l == 0) ? b + 1 : (uint64_t)end[b];
     } else {
         other = nodes + multiproof_rank(mask, word_start, words, l, b - 1);
+        if constexpr (Own::substitutes)          // a select on the pointer, like the operand order below
+            if (own.own(q, p, l)) other = in + q;
     }
     // the operand order is chosen on the pointers: selecting between the loaded nodes word by word went through scratch
     const Node x = vkmr_dev::load_node(right ? other : in + q), y = vkmr_dev::load_node(right ? in + q : other);

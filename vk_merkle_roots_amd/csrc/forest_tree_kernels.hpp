@@ -1,6 +1,7 @@
 // forest_tree_kernels.hpp -- the stored forest's proof gather, the batch verifier for proofs of unequal height, the leaf update
 // and the multiproofs (include/vkmr_hip.h: vkmr_hip_forest_proofs_async, vkmr_hip_verify_forest_proofs_async,
-// vkmr_hip_forest_update_async, vkmr_hip_forest_multiproof_async, vkmr_hip_verify_forest_multiproof_async).  The stored forest
+// vkmr_hip_forest_update_async, vkmr_hip_forest_multiproof_async, vkmr_hip_verify_forest_multiproof_async,
+// vkmr_hip_apply_forest_multiproof_async).  The stored forest
 // itself is written by forest_level_kernel (forest_kernels.hpp), one launch per level: only the buffers the host passes
 // differ.  The layout, and the bodies of the kernels that have a counterpart in tree_kernels.hpp, are in entries.hpp: such a
 // kernel here is its arguments as ForestEntries and ForestCells / ForestSpan, and the call.  Every lane is one entry q < k,
@@ -190,7 +191,7 @@ __global__ __launch_bounds__(256) void verify_forest_multiproof_level_kernel(con
                                                                              const uint64_t* __restrict__ mask, const uint64_t* __restrict__ word_start,
                                                                              const Node* __restrict__ nodes, const uint64_t* __restrict__ hdr)
 {
-    multiproof_verify_level(ForestEntries{trees, indices, heights}, in, cell, end, k, l, words, mask, word_start, nodes, hdr);
+    multiproof_verify_level(ForestEntries{trees, indices, heights}, NeverOwn{}, in, cell, end, k, l, words, mask, word_start, nodes, hdr);
 }
 
 // One lane per entry; *ok was set to 1 before the launch.  A nonzero status (a check failed, or not exactly m nodes would be
@@ -210,4 +211,52 @@ __global__ __launch_bounds__(256) void verify_forest_multiproof_finish_kernel(co
     const uint32_t t = trees[q];
     if (q > 0 && trees[q - 1] == t) return;      // not the first entry of its tree
     if (vkmr_dev::node_diff(vkmr_dev::load_node(cell + q), vkmr_dev::load_node(roots + t)) != 0u) ok[0] = 0u;
+}
+
+// ---- applying a forest multiproof (vkmr_hip_apply_forest_multiproof_async): the verifier's launches on heights derived from
+// the counts, the level kernel twice as wide, one commit behind the finish ---------------------------------------------------
+
+// No hash, in front of the verifier's own check: heights[q] = max(1, ceil(log2 counts[q])), and what only the counts can
+// violate ORed into the status -- bit 0 for a count of 0 (its height is written as 0, which the verifier's check refuses as
+// well) or an index >= the count, bit 3 when the entry in front names the same tree with another count.
+__global__ __launch_bounds__(256) void forest_apply_heights_kernel(const uint32_t* __restrict__ trees, const uint64_t* __restrict__ indices,
+                                                                              const uint64_t* __restrict__ counts, uint32_t k,
+                                                                              uint32_t* __restrict__ heights, uint32_t* __restrict__ status)
+{
+    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= k) return;
+    const uint64_t c = counts[q];
+    heights[q] = c == 0ull ? 0u : vkmr_forest::height(c);
+    uint32_t bits = (c == 0ull || indices[q] >= c) ? 1u : 0u;
+    if (q > 0 && trees[q - 1] == trees[q] && counts[q - 1] != c) bits |= 8u;
+    if (bits) atomicOr(status, bits);
+}
+
+// One launch per level l = 0..stride-1, grid.y = 2: tree_apply_level_kernel (tree_kernels.hpp) with a tree, a height
+// and a count per entry.
+__global__ __launch_bounds__(256) void forest_apply_level_kernel(const Node* __restrict__ in0, const Node* __restrict__ in1,
+                                                                            Node* __restrict__ cell0, Node* __restrict__ cell1,
+                                                                            uint32_t* __restrict__ end0, uint32_t* __restrict__ end1,
+                                                                            const uint32_t* __restrict__ trees, const uint64_t* __restrict__ indices,
+                                                                            const uint32_t* __restrict__ heights, const uint64_t* __restrict__ counts,
+                                                                            uint32_t k, uint32_t l, uint64_t words, const uint64_t* __restrict__ mask,
+                                                                            const uint64_t* __restrict__ word_start, const Node* __restrict__ nodes,
+                                                                            const uint64_t* __restrict__ hdr)
+{
+    const uint32_t side = blockIdx.y;
+    multiproof_verify_level(ForestEntries{trees, indices, heights}, ForestCountOwn{counts, side}, side ? in1 : in0, side ? cell1 : cell0,
+                            side ? end1 : end0, k, l, words, mask, word_start, nodes, hdr);
+}
+
+// Behind the finish kernel, which compared side 0 with the old roots and left ok: when it is 1, the first entry of each
+// tree's run stores its side-1 cell, the tree's new root, to new_roots[t], which may be the old roots themselves (the finish
+// read them last).  Cells of trees no entry names are not written, and nothing is when ok is 0.
+__global__ __launch_bounds__(256) void forest_apply_commit_kernel(const Node* __restrict__ cell1, const uint32_t* __restrict__ trees, uint32_t k,
+                                                                             const uint32_t* __restrict__ ok, Node* __restrict__ new_roots)
+{
+    const uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (q >= k || ok[0] != 1u) return;
+    const uint32_t t = trees[q];
+    if (q > 0 && trees[q - 1] == t) return;      // not the first entry of its tree
+    vkmr_dev::store_node(new_roots + t, vkmr_dev::load_node(cell1 + q));
 }

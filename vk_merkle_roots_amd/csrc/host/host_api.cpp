@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
+#include <utility>
 #include <vector>
 
 #include "../audit_plan.hpp"   // forest_plan.hpp, tree_plan.hpp: where the stored levels lie
@@ -376,6 +377,119 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_verify_forest_multiproo
         if (pos.size() != 1 || pos[0] != 0 || std::memcmp(cur[0].data, roots[trees[a]].data, 32) != 0) return 0;
         a = b;
     }
+    return 1;
+}
+
+}  // extern "C"
+
+namespace {
+
+// One tree's fold on both sides at once, by the rule of vkmr_hip_apply_multiproof_async: the entries [a, b) of a tree of
+// `count` leaves through h levels, `old_cur` and `new_cur` their old and new leaves, a missing child being nodes[at[l]++] --
+// consumed on both sides -- except that the new side takes its own node where p is even and p + 1 >= ceil(count / 2^l).
+// False when the proof runs out (at[l] reaches end[l]); the two roots are left in old_cur[0] and new_cur[0].
+bool apply_fold(const uint64_t* indices, uint32_t a, uint32_t b, uint64_t count, uint32_t h, std::vector<vkmr_digest>& old_cur,
+                std::vector<vkmr_digest>& new_cur, const vkmr_digest* nodes, uint64_t* at, const uint64_t* end)
+{
+    std::vector<uint64_t> pos(indices + a, indices + b);
+    for (uint32_t l = 0; l < h; ++l) {
+        const uint64_t n = vkmr_forest::level_count(count, l);
+        const bool enough = level_walk(pos, [&](size_t i, size_t out, bool both) {
+            if (!both && at[l] >= end[l]) return false;
+            const vkmr_digest* node = both ? nullptr : &nodes[at[l]++];
+            const bool right = pos[i] & 1ull, own = !both && !right && pos[i] + 1 >= n;
+            vkmr_digest x, y;
+            pair_beside(old_cur[i], both ? old_cur[i + 1] : *node, right, &x);
+            pair_beside(new_cur[i], both ? new_cur[i + 1] : own ? new_cur[i] : *node, right, &y);
+            old_cur[out] = x;
+            new_cur[out] = y;
+            return true;
+        });
+        if (!enough) return false;
+        old_cur.resize(pos.size());
+        new_cur.resize(pos.size());
+    }
+    return pos.size() == 1 && pos[0] == 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+// Applying a multiproof on the CPU, by the rule of vkmr_hip_apply_multiproof_async: 1, and *new_root written, when
+// 1 <= count <= 2^height, height is 1..63, the indices are strictly increasing and < count, the fold of the old leaves
+// consumes exactly m nodes and ends in `root`; else 0 and nothing written.  new_root may be root.
+__attribute__((visibility("default"))) int vkmr_host_cpu_apply_multiproof(const vkmr_digest* old_leaves, const vkmr_digest* new_leaves,
+                                                                           const uint64_t* indices, uint32_t k, uint64_t count, uint32_t height,
+                                                                           const vkmr_digest* nodes, uint64_t m, const vkmr_digest* root,
+                                                                           vkmr_digest* new_root)
+{
+    if (!old_leaves || !new_leaves || !indices || !root || !new_root || k == 0 || height == 0 || height > 63 || (!nodes && m > 0)) return 0;
+    if (count == 0 || count > (1ull << height)) return 0;
+    for (uint32_t q = 0; q < k; ++q)
+        if (indices[q] >= count || (q > 0 && indices[q - 1] >= indices[q])) return 0;
+    std::vector<uint64_t> at(height, 0), end(height, 0);   // the next unread node of level l, and the level's end
+    std::vector<vkmr_digest> old_cur(old_leaves, old_leaves + k), new_cur(new_leaves, new_leaves + k);
+    std::vector<uint64_t> per_level(height + 1u, 0);
+    forest_multiproof_counts(indices, 0, k, height, per_level.data());
+    uint64_t M = 0;
+    for (uint32_t l = 0; l < height; ++l) {
+        at[l] = M;
+        M += per_level[l];
+        end[l] = M;
+    }
+    if (M != m) return 0;
+    if (!apply_fold(indices, 0, k, count, height, old_cur, new_cur, nodes, at.data(), end.data())) return 0;
+    if (std::memcmp(old_cur[0].data, root->data, 32) != 0) return 0;
+    *new_root = new_cur[0];
+    return 1;
+}
+
+// Applying a forest multiproof on the CPU, by the rule of vkmr_hip_apply_forest_multiproof_async: 1 when every count is
+// >= 1, indices[q] < counts[q], the entries of one tree carry one count and vkmr_host_cpu_verify_forest_multiproof answers 1
+// for the old leaves with the heights max(1, ceil(log2 count)); then new_roots[t] of every named tree is written (new_roots
+// may be roots; the cells of other trees are not touched).  Else 0 and nothing written.
+__attribute__((visibility("default"))) int vkmr_host_cpu_apply_forest_multiproof(const vkmr_digest* old_leaves, const vkmr_digest* new_leaves,
+                                                                                  const uint32_t* trees, const uint64_t* indices,
+                                                                                  const uint64_t* counts, uint32_t k, uint32_t stride,
+                                                                                  const vkmr_digest* nodes, uint64_t m, const vkmr_digest* roots,
+                                                                                  uint32_t ntrees, vkmr_digest* new_roots)
+{
+    if (!old_leaves || !new_leaves || !trees || !indices || !counts || !roots || !new_roots || k == 0 || stride == 0 || stride > 63 ||
+        (!nodes && m > 0))
+        return 0;
+    std::vector<uint32_t> heights(k);
+    for (uint32_t q = 0; q < k; ++q) {
+        if (counts[q] == 0 || indices[q] >= counts[q] || trees[q] >= ntrees) return 0;
+        heights[q] = vkmr_math::height(counts[q]);
+        if (heights[q] > stride) return 0;
+        if (q == 0) continue;
+        if (trees[q - 1] > trees[q] || (trees[q - 1] == trees[q] && (indices[q - 1] >= indices[q] || counts[q - 1] != counts[q]))) return 0;
+    }
+    std::vector<uint64_t> per_level(stride + 1u, 0);
+    for (uint32_t a = 0; a < k;) {
+        const uint32_t b = forest_run_end(trees, a, k);
+        forest_multiproof_counts(indices, a, b, heights[a], per_level.data());
+        a = b;
+    }
+    std::vector<uint64_t> at(stride, 0), end(stride, 0);   // the next unread node of level l, and the level's end
+    uint64_t M = 0;
+    for (uint32_t l = 0; l < stride; ++l) {
+        at[l] = M;
+        M += per_level[l];
+        end[l] = M;
+    }
+    if (M != m) return 0;
+    std::vector<std::pair<uint32_t, vkmr_digest>> fresh;    // written only when every tree's old fold has met its root
+    for (uint32_t a = 0; a < k;) {
+        const uint32_t b = forest_run_end(trees, a, k);
+        std::vector<vkmr_digest> old_cur(old_leaves + a, old_leaves + b), new_cur(new_leaves + a, new_leaves + b);
+        if (!apply_fold(indices, a, b, counts[a], heights[a], old_cur, new_cur, nodes, at.data(), end.data())) return 0;
+        if (std::memcmp(old_cur[0].data, roots[trees[a]].data, 32) != 0) return 0;
+        fresh.emplace_back(trees[a], new_cur[0]);
+        a = b;
+    }
+    for (const auto& f : fresh) new_roots[f.first] = f.second;
     return 1;
 }
 

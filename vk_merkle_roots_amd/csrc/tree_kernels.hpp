@@ -1,9 +1,9 @@
 // tree_kernels.hpp -- the stored tree's proof gather, the batch verifier, the leaf update and the multiproofs (include/vkmr_hip.h:
 // vkmr_hip_tree_proofs_async, vkmr_hip_verify_proofs_async, vkmr_hip_tree_update_async, vkmr_hip_tree_multiproof_async,
-// vkmr_hip_verify_multiproof_async), and the ranking kernels that the forest's multiproofs launch as well.  The tree itself is
-// built by reduce_level_kernel (reduce_kernels.hpp), one launch per level.  The layout, and the bodies of the kernels that
-// have a counterpart in forest_tree_kernels.hpp, are in entries.hpp: such a kernel here is its arguments as TreeEntries and
-// TreeCells / TreeSpan, and the call.
+// vkmr_hip_verify_multiproof_async, vkmr_hip_apply_multiproof_async), and the ranking kernels that the forest's multiproofs
+// launch as well.  The tree itself is built by reduce_level_kernel (reduce_kernels.hpp), one launch per level.  The layout,
+// and the bodies of the kernels that have a counterpart in forest_tree_kernels.hpp, are in entries.hpp: such a kernel here
+// is its arguments as TreeEntries and TreeCells / TreeSpan, and the call.
 #pragma once
 
 #include "entries.hpp"
@@ -173,7 +173,7 @@ __global__ __launch_bounds__(256) void verify_multiproof_level_kernel(const Node
                                                                       const Node* __restrict__ nodes, const uint64_t* __restrict__ hdr)
 {
     __builtin_assume(l < VKMR_TREE_MAX_LEVELS);
-    multiproof_verify_level(TreeEntries{indices, VKMR_TREE_MAX_LEVELS}, in, cell, end, k, l, words, mask, word_start, nodes, hdr);
+    multiproof_verify_level(TreeEntries{indices, VKMR_TREE_MAX_LEVELS}, NeverOwn{}, in, cell, end, k, l, words, mask, word_start, nodes, hdr);
 }
 
 // ok = 1 when the checks passed (status 0: indices strictly increasing and < 2^height, exactly m nodes consumed) and the
@@ -186,4 +186,32 @@ __global__ void verify_multiproof_finish_kernel(const Node* __restrict__ cell, c
     uint32_t diff = hdr[0] != 0ull ? 1u : 0u;
     if (!diff) diff = vkmr_dev::node_diff(vkmr_dev::load_node(cell), vkmr_dev::load_node(root));   // the cells are only written when the status is 0
     ok[0] = diff == 0u ? 1u : 0u;
+}
+
+// ---- applying a multiproof (vkmr_hip_apply_multiproof_async): the verifier's launches, the level kernel twice as wide ------
+
+// One launch per level l = 0..height-1, grid.y = 2: blockIdx.y is the side, the same in every lane of a workgroup.  Side 0
+// folds the old leaves in cell0 / end0, the verifier's fold to the letter; side 1 folds the new leaves in cell1 / end1 and
+// takes its own cell where the tree of `count` leaves has no right sibling (entries.hpp: TreeCountOwn).  The sides share
+// nothing they write: a lane reads end[q] and end[b] before it writes end[q], so one end array would let the other side's
+// lane read a value already advanced.  in0 / in1 are the leaves at l == 0, the side's cells above.  One hash_pair.
+__global__ __launch_bounds__(256) void tree_apply_level_kernel(const Node* __restrict__ in0, const Node* __restrict__ in1, Node* __restrict__ cell0,
+                                                                     Node* __restrict__ cell1, uint32_t* __restrict__ end0, uint32_t* __restrict__ end1,
+                                                                     const uint64_t* __restrict__ indices, uint64_t count, uint32_t k, uint32_t l,
+                                                                     uint64_t words, const uint64_t* __restrict__ mask,
+                                                                     const uint64_t* __restrict__ word_start, const Node* __restrict__ nodes,
+                                                                     const uint64_t* __restrict__ hdr)
+{
+    __builtin_assume(l < VKMR_TREE_MAX_LEVELS);
+    const uint32_t side = blockIdx.y;
+    multiproof_verify_level(TreeEntries{indices, VKMR_TREE_MAX_LEVELS}, TreeCountOwn{count, side}, side ? in1 : in0, side ? cell1 : cell0,
+                            side ? end1 : end0, k, l, words, mask, word_start, nodes, hdr);
+}
+
+// Behind the finish kernel, which compared side 0 with the old root and wrote ok: when it is 1, cell 0 of side 1 -- the new
+// root -- goes to new_root, which may be the old root's own cell (it was last read by the finish).  Else nothing is written.
+__global__ void tree_apply_commit_kernel(const Node* __restrict__ cell1, const uint32_t* __restrict__ ok, Node* __restrict__ new_root)
+{
+    if (threadIdx.x != 0 || blockIdx.x != 0 || ok[0] != 1u) return;
+    vkmr_dev::store_node(new_root, vkmr_dev::load_node(cell1));
 }

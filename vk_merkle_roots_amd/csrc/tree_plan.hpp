@@ -1,6 +1,7 @@
 // tree_plan.hpp -- where the levels of one stored tree lie (vkmr_hip_reduce_tree_async) and the sizes of its multiproofs:
-// the node bound and the scratch layout.  Plain integer arithmetic, no HIP types: shared by the kernels (entries.hpp takes
-// the constants), the C ABI (vkmr_hip.hip) and the CPU-side replay in tests/c/abi_plan_test.cpp.
+// the node bound and the scratch layout, and the scratch layout of the calls that apply one.  Plain integer arithmetic, no HIP
+// types: shared by the kernels (entries.hpp takes the constants), the C ABI (vkmr_hip.hip) and the CPU-side replays in
+// tests/c/abi_plan_test.cpp and tests/c/apply_plan_test.cpp.
 //
 // Level 0 is the caller's digests; levels 1..height lie back to back in one buffer, level l (n_l = ceil(count / 2^l) cells)
 // starting at cell off[l] = sum of n_j over 1 <= j < l.
@@ -65,6 +66,28 @@ inline MultiproofLayout multiproof_layout(uint32_t k, uint32_t height)
     L.end = at;        at += (size_t)k * sizeof(uint32_t);
     L.bytes = at;
     return L;
+}
+
+// The scratch of an apply call (vkmr_hip_apply_multiproof_async and its forest twin): the verifier's layout whole -- side 0,
+// the old leaves, folds in its cells and ends -- and behind it, each part starting on 16 bytes, the cells and ends of side 1
+// (the new leaves) and the heights the check derives from the counts.  `levels` is one tree's height or a forest's stride.
+struct ApplyLayout {
+    MultiproofLayout mp;
+    size_t cell1, end1, heights, bytes;
+};
+
+inline size_t round_up_16(size_t bytes) { return (bytes + 15u) & ~(size_t)15u; }
+
+inline ApplyLayout apply_layout(uint32_t k, uint32_t levels)
+{
+    ApplyLayout A;
+    A.mp = multiproof_layout(k, levels);
+    size_t at = round_up_16(A.mp.bytes);
+    A.cell1 = at;   at = round_up_16(at + (size_t)k * CELL_BYTES);
+    A.end1 = at;    at = round_up_16(at + (size_t)k * sizeof(uint32_t));
+    A.heights = at; at = round_up_16(at + (size_t)k * sizeof(uint32_t));
+    A.bytes = at;
+    return A;
 }
 
 }  // namespace vkmr_tree

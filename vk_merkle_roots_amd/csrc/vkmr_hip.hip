@@ -11,6 +11,8 @@
 //                       tree_update_*_kernel   leaf updates: check, store the leaves, rehash the dirty nodes level by level
 //                       multiproof_*_kernel, tree_multiproof_gather_kernel, verify_multiproof_*_kernel   one proof for k leaves:
 //                                              rank the nodes to emit, gather them; fold leaves and nodes level by level
+//                       tree_apply_*_kernel   the new root from the old root: the verifier's fold of the old leaves and, in
+//                                              the same launches (grid.y = the side), the fold of the new leaves; one commit
 //   forest_kernels.hpp  forest_check_kernel, forest_level_kernel   roots of many trees of unequal size: one lane per node of the
 //                                              whole forest, level by level (no reference counterpart); builds the stored forest
 //                       forest_level_mutated_kernel, forest_scan_mutated_kernel   the same level with the mutation flag (equal
@@ -20,7 +22,9 @@
 //                            forest_update_*_kernel        leaf updates of the stored forest: tree_update_*'s bodies, a tree per entry
 //                            forest_multiproof_*_kernel, verify_forest_multiproof_*_kernel   one proof for leaves of many trees:
 //                                              the multiproof bodies and tree_kernels.hpp's ranking, a tree and a height per entry
-//   find_kernels.hpp    find_insert_kernel, *_find_scan_kernel, *_find_resolve_kernel   lookup by digest: the queries in an open-addressed
+//                            forest_apply_*_kernel   the new roots from the old roots: heights from the counts, the
+//                                              verifier's launches on them, the level kernel twice as wide, one commit
+//   find_kernels.hpp   find_insert_kernel, *_find_scan_kernel, *_find_resolve_kernel   lookup by digest: the queries in an open-addressed
 //                                              table, every leaf streamed past it once, lowest position per query (sizes: find_plan.hpp)
 //   sort_kernels.hpp    *_sort_keys_kernel, sort_histogram_kernel, sort_scan_kernel, sort_scatter_kernel, sort_flags_kernel, *_sort_emit_kernel,
 //                                              gather_digests_kernel   leaf entries sorted and deduplicated: a stable LSD radix sort of
@@ -38,7 +42,7 @@
 // Plans (no HIP types either: g++ compiles them, tests/c replays them, the test double sizes its scratch with them)
 //   map_plan.hpp        the map kernel's fetch mode and tile for a batch
 //   reduce_plan.hpp     the launch schedule of a slice reduction, height_ok, the chunks of a run of slices, the scratch sizes
-//   tree_plan.hpp       the stored tree's level offsets, the multiproof node bound and scratch layout
+//   tree_plan.hpp       the stored tree's level offsets, the multiproof node bound and scratch layout, the apply calls' scratch layout
 //   forest_plan.hpp     where a forest's nodes lie, level by level; its scratch, stored size and multiproof node bound
 //   find_plan.hpp       the lookup's scratch layout and scan grid
 //   sort_plan.hpp       the entry sort's passes, tiles, histogram words and scratch layout
@@ -907,6 +911,56 @@ vkmr_status vkmr_hip_verify_multiproof_async(int dev, vkmr_stream s, const vkmr_
     return launch(verify_multiproof_finish_kernel, dim3(1), dim3(64), S(s), sc.cell, nodes(root_dev), sc.hdr, ok_dev);
 }
 
+// ---- applying a multiproof: the new root from the old root, the old and the new leaves (tree_kernels.hpp) ------------------
+
+using vkmr_tree::ApplyLayout;
+using vkmr_tree::apply_layout;
+
+size_t vkmr_hip_apply_multiproof_scratch_bytes(uint32_t k, uint32_t levels)
+{
+    if (k == 0 || levels > 63) return 0;
+    return apply_layout(k, levels).bytes;
+}
+
+// What an apply call's scratch_dev holds behind the verifier's parts: side 1's cells and ends, the derived heights.
+struct ApplyScratch {
+    MultiproofScratch mp;
+    Node* cell1;
+    uint32_t *end1, *heights;
+    ApplyScratch(void* scratch_dev, const ApplyLayout& A) : mp(scratch_dev, A.mp)
+    {
+        const uintptr_t at = reinterpret_cast<uintptr_t>(scratch_dev);
+        cell1 = reinterpret_cast<Node*>(at + A.cell1);
+        end1 = reinterpret_cast<uint32_t*>(at + A.end1);
+        heights = reinterpret_cast<uint32_t*>(at + A.heights);
+    }
+};
+
+vkmr_status vkmr_hip_apply_multiproof_async(int dev, vkmr_stream s, const vkmr_digest* old_leaves_dev, const vkmr_digest* new_leaves_dev,
+                                            const uint64_t* indices_dev, uint32_t k, uint64_t count, uint32_t height, const vkmr_digest* nodes_dev,
+                                            uint64_t m, const vkmr_digest* root_dev, void* scratch_dev, uint32_t* ok_dev, vkmr_digest* new_root_dev)
+{
+    if (k == 0) return VKMR_OK;
+    if (!old_leaves_dev || !new_leaves_dev || !indices_dev || !root_dev || !scratch_dev || !ok_dev || !new_root_dev || (!nodes_dev && m > 0))
+        return refuse(__func__, "null pointer");
+    if (height == 0 || height > 63) return refuse(__func__, "height must be 1..63");
+    if (reinterpret_cast<uintptr_t>(scratch_dev) & 15u) return refuse(__func__, "scratch must be 16-byte aligned");
+    const ApplyLayout A = apply_layout(k, height);
+    const ApplyScratch sc(scratch_dev, A);
+    VKMR_TRY(hipSetDevice(dev));
+    // the verifier's check with the count as the bound: bit 0 an index that is no leaf.  A count of 0 has no leaf, and one
+    // above 2^height is none this height can hold: the bound 0 refuses every index.  exact: M == m
+    const uint64_t bound = count <= (1ull << height) ? count : 0ull;
+    VKMR_CHECK(tree_multiproof_rank_launch(S(s), indices_dev, k, bound, height, A.mp, sc.mp, sc.mp.hdr, m, 1u));
+    const dim3 grid = grid_of(k, 2);
+    for (uint32_t l = 0; l < height; ++l)   // level l + 1 from level l on both sides, which the previous launch finished
+        VKMR_CHECK(launch(tree_apply_level_kernel, grid, dim3(256), S(s), l == 0 ? nodes(old_leaves_dev) : sc.mp.cell,
+                          l == 0 ? nodes(new_leaves_dev) : sc.cell1, sc.mp.cell, sc.cell1, sc.mp.end, sc.end1, indices_dev, count, k, l, A.mp.words,
+                          sc.mp.mask, sc.mp.word_start, nodes(nodes_dev), sc.mp.hdr));
+    VKMR_CHECK(launch(verify_multiproof_finish_kernel, dim3(1), dim3(64), S(s), sc.mp.cell, nodes(root_dev), sc.mp.hdr, ok_dev));
+    return launch(tree_apply_commit_kernel, dim3(1), dim3(64), S(s), sc.cell1, ok_dev, nodes(new_root_dev));
+}
+
 // ---- forest: the roots of many trees of unequal size (forest_kernels.hpp, forest_plan.hpp) ---------------------------------
 
 size_t vkmr_hip_forest_scratch_bytes(uint64_t total, uint32_t ntrees)
@@ -1162,6 +1216,40 @@ vkmr_status vkmr_hip_verify_forest_multiproof_async(int dev, vkmr_stream s, cons
         VKMR_CHECK(launch(verify_forest_multiproof_level_kernel, grid, dim3(256), S(s), l == 0 ? nodes(leaves_dev) : sc.cell, sc.cell, sc.end, trees_dev,
                           indices_dev, heights_dev, k, l, L.words, sc.mask, sc.word_start, nodes(nodes_dev), sc.hdr));
     return launch(verify_forest_multiproof_finish_kernel, grid, dim3(256), S(s), sc.cell, trees_dev, k, nodes(roots_dev), sc.hdr, ok_dev);
+}
+
+// ---- applying a forest multiproof: the new roots from the old roots, the old and the new leaves (forest_tree_kernels.hpp) ----
+
+vkmr_status vkmr_hip_apply_forest_multiproof_async(int dev, vkmr_stream s, const vkmr_digest* old_leaves_dev, const vkmr_digest* new_leaves_dev,
+                                                   const uint32_t* trees_dev, const uint64_t* indices_dev, const uint64_t* counts_dev, uint32_t k,
+                                                   uint32_t stride, const vkmr_digest* nodes_dev, uint64_t m, const vkmr_digest* roots_dev,
+                                                   uint32_t ntrees, void* scratch_dev, uint32_t* ok_dev, vkmr_digest* new_roots_dev)
+{
+    if (k == 0) return VKMR_OK;
+    if (!old_leaves_dev || !new_leaves_dev || !trees_dev || !indices_dev || !counts_dev || !roots_dev || !scratch_dev || !ok_dev || !new_roots_dev ||
+        (!nodes_dev && m > 0))
+        return refuse(__func__, "null pointer");
+    if (stride == 0 || stride > 63) return refuse(__func__, "stride must be 1..63");
+    if (reinterpret_cast<uintptr_t>(scratch_dev) & 15u) return refuse(__func__, "scratch must be 16-byte aligned");
+    const ApplyLayout A = apply_layout(k, stride);
+    const ApplyScratch sc(scratch_dev, A);
+    const MultiproofLayout& L = A.mp;
+    const dim3 grid = grid_of(k);
+    uint32_t* status = reinterpret_cast<uint32_t*>(sc.mp.hdr);
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_TRY(hipMemsetAsync(sc.mp.hdr, 0, sizeof(uint64_t), S(s)));
+    VKMR_TRY(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ok_dev), 1, 1, S(s)));   // the finish kernel clears it
+    // the heights from the counts, then the verifier's own launches on them: no flag is computed a second way
+    VKMR_CHECK(launch(forest_apply_heights_kernel, grid, dim3(256), S(s), trees_dev, indices_dev, counts_dev, k, sc.heights, status));
+    VKMR_CHECK(launch(verify_forest_multiproof_check_kernel, grid, dim3(256), S(s), trees_dev, indices_dev, sc.heights, k, stride, ntrees, status));
+    VKMR_CHECK(launch(forest_multiproof_masks_kernel, grid, dim3(256), S(s), trees_dev, indices_dev, sc.heights, k, stride, L.words, sc.mp.hdr, sc.mp.mask));
+    VKMR_CHECK(multiproof_rank_launch(S(s), stride, L, sc.mp, sc.mp.hdr, m, 1u));   // exact: M == m
+    for (uint32_t l = 0; l < stride; ++l)   // level l + 1 from level l on both sides, which the previous launch finished
+        VKMR_CHECK(launch(forest_apply_level_kernel, grid_of(k, 2), dim3(256), S(s), l == 0 ? nodes(old_leaves_dev) : sc.mp.cell,
+                          l == 0 ? nodes(new_leaves_dev) : sc.cell1, sc.mp.cell, sc.cell1, sc.mp.end, sc.end1, trees_dev, indices_dev, sc.heights,
+                          counts_dev, k, l, L.words, sc.mp.mask, sc.mp.word_start, nodes(nodes_dev), sc.mp.hdr));
+    VKMR_CHECK(launch(verify_forest_multiproof_finish_kernel, grid, dim3(256), S(s), sc.mp.cell, trees_dev, k, nodes(roots_dev), sc.mp.hdr, ok_dev));
+    return launch(forest_apply_commit_kernel, grid, dim3(256), S(s), sc.cell1, trees_dev, k, ok_dev, nodes(new_roots_dev));
 }
 
 // ---- lookup by digest (find_kernels.hpp, find_plan.hpp) ---------------------------------------------------------------------

@@ -480,6 +480,67 @@ class HipDevice:
                                                 d_scr, d_ok)
             return int(self.download(d_ok, 4)[0]) == 1
 
+    # -- applying a multiproof: a holder of the roots alone follows leaf updates ----------
+    def apply_multiproof_scratch_bytes(self, k, levels):
+        return self.lib.vkmr_hip_apply_multiproof_scratch_bytes(k, levels)
+
+    def apply_multiproof_enqueue(self, old_leaves_buf, new_leaves_buf, indices_buf, k, count, height, nodes_buf, m, root_buf, scratch_buf, ok_buf,
+                                 new_root_buf, stream=None):
+        self._call("vkmr_hip_apply_multiproof_async", old_leaves_buf, new_leaves_buf, indices_buf, k, count, height, nodes_buf, m, root_buf,
+                   scratch_buf, ok_buf, new_root_buf, stream=stream)
+
+    def apply_forest_multiproof_enqueue(self, old_leaves_buf, new_leaves_buf, trees_buf, indices_buf, counts_buf, k, stride, nodes_buf, m,
+                                        roots_buf, ntrees, scratch_buf, ok_buf, new_roots_buf, stream=None):
+        self._call("vkmr_hip_apply_forest_multiproof_async", old_leaves_buf, new_leaves_buf, trees_buf, indices_buf, counts_buf, k, stride,
+                   nodes_buf, m, roots_buf, ntrees, scratch_buf, ok_buf, new_roots_buf, stream=stream)
+
+    def apply_multiproof(self, old_leaves, new_leaves, indices, nodes, root, count, height=None):
+        """The new root [8] of a tree of `count` leaves (and `height` levels; None: the minimal height) after the leaves at
+        `indices` ([k], strictly increasing) went from old_leaves to new_leaves ([k, 8] each), from the old `root` and the
+        multiproof `nodes` ([M, 8]) gathered before the update alone; None when the proof is refused: the old leaves do not
+        fold to `root`, or the indices and the count do not fit (vkmr_hip_apply_multiproof_async).  Host arrays in, folded
+        on the device; no leaf changes nothing: None."""
+        old, new = _digest_pairs(old_leaves, new_leaves, "apply_multiproof")
+        idx, nodes, root = _host(indices, np.uint64, -1), _host(nodes, np.uint32, -1, 8), _host(root, np.uint32, 8)
+        k, m = int(idx.shape[0]), int(nodes.shape[0])
+        if old.shape[0] != k:
+            raise ValueError("apply_multiproof: one old and one new leaf per index")
+        height = (tree_height(int(count)) if int(count) > 0 else 1) if height is None else int(height)   # no leaf: the device answers 0
+        if k == 0:
+            return None
+        with self.scope() as tmp:
+            d_old, d_new, d_idx, d_nodes, d_root = (tmp.upload(a) for a in (old, new, idx, nodes, root))
+            d_scr, d_ok, d_out = tmp.alloc(self.apply_multiproof_scratch_bytes(k, height)), tmp.alloc(4), tmp.alloc(32)
+            self.apply_multiproof_enqueue(d_old, d_new, d_idx, k, int(count), height, d_nodes if m else None, m, d_root, d_scr, d_ok, d_out)
+            return self.download(d_out, 32) if int(self.download(d_ok, 4)[0]) == 1 else None
+
+    def apply_forest_multiproof(self, old_leaves, new_leaves, trees, indices, counts, nodes, roots):
+        """The roots [ntrees, 8] of a forest after the leaves at the strictly increasing (trees[q], indices[q]) went from
+        old_leaves to new_leaves ([k, 8] each) -- a copy of `roots` with the named trees advanced -- from the old roots, the
+        forest multiproof `nodes` ([M, 8]) gathered before the update and counts[q], the leaf count of entry q's tree, alone;
+        None when the proof is refused (vkmr_hip_apply_forest_multiproof_async).  Host arrays in, folded on the device; no
+        leaf changes nothing: None."""
+        old, new = _digest_pairs(old_leaves, new_leaves, "apply_forest_multiproof")
+        trees, idx, counts = _host(trees, np.uint32, -1), _host(indices, np.uint64, -1), _host(counts, np.uint64, -1)
+        nodes, roots = _host(nodes, np.uint32, -1, 8), _host(roots, np.uint32, -1, 8)
+        k, m = int(idx.shape[0]), int(nodes.shape[0])
+        if old.shape[0] != k or trees.shape[0] != k or counts.shape[0] != k:
+            raise ValueError("apply_forest_multiproof: one old leaf, one new leaf, one tree and one count per index")
+        if k == 0:
+            return None
+        if roots.shape[0] == 0:
+            raise ValueError("apply_forest_multiproof: no root")
+        # a count of 0 and a height above 63 are refused by the device's checks
+        stride = min(63, max(tree_height(int(c)) if c else 1 for c in np.unique(counts)))
+        with self.scope() as tmp:
+            d_old, d_new, d_trees, d_idx, d_counts, d_nodes, d_roots = (tmp.upload(a) for a in (old, new, trees, idx, counts, nodes, roots))
+            d_scr, d_ok = tmp.alloc(self.apply_multiproof_scratch_bytes(k, stride)), tmp.alloc(4)
+            self.apply_forest_multiproof_enqueue(d_old, d_new, d_trees, d_idx, d_counts, k, stride, d_nodes if m else None, m, d_roots,
+                                                 roots.shape[0], d_scr, d_ok, d_roots)      # in place: d_roots is this call's own copy
+            if int(self.download(d_ok, 4)[0]) != 1:
+                return None
+            return self.download(d_roots, roots.nbytes).reshape(-1, 8)
+
     def _build_forest_of_buffer(self, d_leaves, total, counts, max_count, what, owned=(), mutated=False):
         """A MerkleForest of the trees of `counts` leaves each over the `total` cells of d_leaves (its level 0); with `mutated`
         built by the flagged twin, whose masks it keeps."""
@@ -712,6 +773,23 @@ class ForestMultiproof:
                 for r, (t, idx, h) in enumerate(runs)}
 
 
+class UpdateWitness:
+    """What a primary sends beside an update so that a holder of the roots alone can follow it (update_with_witness):
+    `proof`, the Multiproof or ForestMultiproof of the updated positions gathered BEFORE the update; `counts` uint64 [k], the
+    leaf count of each entry's tree; `old_leaves` and `new_leaves` uint32 [k, 8], the leaves there before and after."""
+
+    def __init__(self, proof, counts, old_leaves, new_leaves):
+        self.proof, self.counts, self.old_leaves, self.new_leaves = proof, counts, old_leaves, new_leaves
+
+    def apply(self, dev, roots):
+        """The follower's step on `dev`: a forest's old `roots` [ntrees, 8] give the new roots [ntrees, 8], a tree's old root
+        [8] its new root [8]; None when the witness does not fit them (HipDevice.apply_forest_multiproof / apply_multiproof)."""
+        p = self.proof
+        if isinstance(p, ForestMultiproof):
+            return dev.apply_forest_multiproof(self.old_leaves, self.new_leaves, p.trees, p.indices, self.counts, p.nodes, roots)
+        return dev.apply_multiproof(self.old_leaves, self.new_leaves, p.indices, p.nodes, roots, int(self.counts[0]), p.height)
+
+
 AUDIT_MAX_CAPACITY = 2**32 - 1
 
 
@@ -870,6 +948,40 @@ class _Stored:
             if pos.shape[0]:
                 d_leaves = tmp.upload(np.ascontiguousarray(lv[pos], dtype=np.uint32))
                 self._apply(tmp, "update", "sorted in-range entries", [tmp.upload(c) for c in cols], d_leaves, pos.shape[0])
+
+    def _update_with_witness(self, entries, leaves):
+        """update() that also returns what a holder of the roots needs to follow it: the old leaves and the multiproof of the
+        sorted entries gathered, then the update, enqueued back to back on the device's stream and read back at the end."""
+        what = "update_with_witness"
+        lv = np.asarray(leaves)
+        k = int(np.asarray(entries[-1]).size)
+        if lv.shape != (k, 8):
+            raise ValueError(f"{what}: leaves must be [{k}, 8], not {list(lv.shape)}")
+        *cols, pos = self._update_order(*entries, what)
+        n = int(pos.shape[0])
+        if n == 0:
+            raise ValueError(f"{what}: no entry")
+        if self.stride == 0:
+            raise ValueError(f"{what}: a tree of one leaf and no level has no path to fold")
+        cells, counts = self._entry_cells(*cols)
+        if int(cells.max()) >= 2**32:
+            raise ValueError(f"{what}: a leaf at cell 2^32 or beyond")      # gather_digests_async takes uint32 positions
+        new = np.ascontiguousarray(lv[pos], dtype=np.uint32)
+        cap, scratch_bytes = self._multiproof_sizes(n)
+        with self.dev.scope() as tmp:
+            d_entries, d_new, d_cells = [tmp.upload(c) for c in cols], tmp.upload(new), tmp.upload(cells.astype(np.uint32))
+            d_old, d_scr, d_nodes = tmp.alloc(32 * n), tmp.alloc(scratch_bytes), tmp.alloc(32 * cap) if cap else None
+            d_extra, d_info, d_status = self._alloc(tmp, self._proof_columns, n), tmp.alloc(8 * (2 + self.stride)), tmp.alloc(4)
+            self.dev.gather_digests_async(self.digests, d_cells, n, d_old)
+            self.multiproof_async(*d_entries, n, d_scr, d_nodes, cap, *d_extra, d_info)
+            self.update_async(*d_entries, d_new, n, d_status)
+            info = self.dev.download(d_info, 8 * (2 + self.stride), dtype=np.uint64)
+            self._refuse(what, int(info[0]), "sorted in-range entries")
+            self._refuse(what, int(self.dev.download(d_status, 4)[0]), "sorted in-range entries")
+            m = int(info[1])
+            nodes = self.dev.download(d_nodes, 32 * m).reshape(m, 8) if m else np.zeros((0, 8), dtype=np.uint32)
+            extra, old = self._read(d_extra, self._proof_columns, n), self.dev.download(d_old, 32 * n).reshape(n, 8)
+        return UpdateWitness(self._Proof(*cols, *extra, nodes, info[2:].copy(), self.stride), counts, old, new)
 
     def _update_packed(self, entries, batch):
         k = int(np.asarray(entries[-1]).size)
@@ -1088,6 +1200,16 @@ class MerkleTree(_Stored):
         IndexError for an index < 0 or >= count, ValueError when leaves is not [k, 8], both before any device call."""
         self._update((indices,), leaves)
 
+    def _entry_cells(self, indices):
+        """(each entry's cell in the digests buffer, the leaf count of its tree)."""
+        return indices, np.full(indices.shape[0], self.count, dtype=np.uint64)
+
+    def update_with_witness(self, indices, leaves):
+        """update(), returning the UpdateWitness of it: the Multiproof of the sorted unique indices gathered before the update,
+        the count, and the leaves there before and after.  witness.apply(dev, old root) gives a holder of the root alone
+        the root after the update.  update()'s rules; ValueError also for no index at all or a tree of height 0."""
+        return self._update_with_witness((indices,), leaves)
+
     def update_packed(self, indices, batch):
         """Set leaf indices[q] to the digest of string q of `batch` (batch.count == len(indices)): the strings are mapped on
         the device and the tree updated there, no digest goes through the host.  Same index rules as update()."""
@@ -1253,6 +1375,18 @@ class MerkleForest(_Stored):
         buffer (it is level 0).  ValueError when leaves is not [k, 8] or there is not one tree per index, IndexError for a tree
         outside [0, ntrees) or an index outside [0, counts[tree]), all before any device call."""
         self._update((trees, indices), leaves)
+
+    def _entry_cells(self, trees, indices):
+        """(each entry's cell in the leaves buffer, the leaf count of its tree)."""
+        t = trees.astype(np.int64)
+        offsets = np.concatenate([[0], np.cumsum(self.counts)]).astype(np.uint64)
+        return offsets[t] + indices, self.counts[t]
+
+    def update_with_witness(self, trees, indices, leaves):
+        """update(), returning the UpdateWitness of it: the ForestMultiproof of the sorted unique entries gathered before the
+        update, the count of each entry's tree, and the leaves there before and after.  witness.apply(dev, old roots) gives a
+        holder of the roots alone the roots after the update.  update()'s rules; ValueError also for no entry at all."""
+        return self._update_with_witness((trees, indices), leaves)
 
     def update_packed(self, trees, indices, batch):
         """Set leaf indices[q] of tree trees[q] to the digest of string q of `batch` (batch.count == len(indices)): the strings
