@@ -838,6 +838,54 @@ VKMR_API vkmr_status vkmr_hip_tree_audit_async(int dev, vkmr_stream s, const vkm
                                                uint64_t* info_dev);
 
 /*
+ * STORED FORESTS THAT GROW: trees appended into room reserved at the build, and the last trees dropped again.  Node j of tree
+ * t's level l is cell (offsets[t] >> l) + t + j of that level's buffer: it depends on tree t's own offset and number alone, so
+ * nothing behind tree t moves it.  A forest built (vkmr_hip_reduce_forest_tree_async) with empty trees at its end and with
+ * offsets[ntrees] < total therefore has its level buffers laid out for its CAPACITY -- `total` leaves, `ntrees` trees, none
+ * above max_count -- and appending is filling the next empty trees: the work is that of the new trees alone, every earlier
+ * cell stays where it is, and the grown forest is byte for byte one the build could have written, which every call above takes.
+ *   total, ntrees, max_count   those of the build (the capacity), TRUSTED as vkmr_hip_forest_update_async trusts them
+ *   first_tree, used           trees first_tree .. ntrees - 1 are empty and used == offsets[first_tree] == .. == offsets[ntrees];
+ *                              host values, so that every grid is sized without reading device memory; checked on the device
+ *   new_offsets_dev            m + 1 uint64_t in device memory, relative to `used`: new_offsets[0] == 0, none decreasing,
+ *                              new_offsets[m] == n_leaves; new tree j holds leaves [new_offsets[j], new_offsets[j + 1])
+ *   leaves_dev                 the n_leaves new leaves in device memory; leaves_dev == digests_dev + used says that they are in
+ *                              place already (vkmr_hip_map_async writes at an output offset) and no copy is launched
+ *   mutated_dev                NULL, or the ntrees masks of the flagged builds: those of the m new trees are zeroed and formed in
+ *                              the same launches (each level compares the two children it loads); no other mask is touched
+ *   status_dev                 one uint32_t in device memory, always written: 0 when the trees were appended; bit 0 set if the
+ *                              new offsets decrease, do not start at 0 or do not end at n_leaves; bit 1 if a new count is above
+ *                              max_count; bit 2 (value 4) if some offsets[t] != used for first_tree <= t <= ntrees.  When it is
+ *                              nonzero NOTHING of the caller's has changed: no leaf cell (but those the caller put in place
+ *                              itself), no offset, no cell of forest_dev, no root, no mask.
+ * After status 0 the leaves lie at cells [used, used + n_leaves), offsets[first_tree + j] = used + new_offsets[j] for
+ * 1 <= j <= m, every later offset up to offsets[ntrees] is used + n_leaves, and the levels and roots of trees first_tree ..
+ * first_tree + m - 1 are written: every cell of the leaves, forest_dev, roots_dev and offsets_dev equals what a fresh
+ * vkmr_hip_reduce_forest_tree_async over the resulting offsets writes; cells a build never writes are not written here either.
+ * Launches, all on the caller's stream: the status word zeroed, one check (the new offsets and the placement), the leaves unless
+ * in place, the offsets (which zeroes the new trees' masks too), then one launch per level, H = max(1, ceil(log2 min(max_count,
+ * total))) of them, level l over the cells [pos_l(used, first_tree), pos_l(used + n_leaves, first_tree + m)) alone, never a
+ * level's whole buffer; no launch per tree, no allocation, no host read of device data.  Refused on the host (VKMR_ERR_INVALID)
+ * with m > 0, before any HIP call: a NULL pointer (leaves_dev may be NULL when n_leaves == 0, mutated_dev always),
+ * first_tree + m > ntrees, used + n_leaves > total, max_count == 0, total > 2^58.  m == 0 does nothing whatever the other
+ * arguments.  Stream-ordered: a proof gather enqueued after it on the same stream sees the new trees.
+ */
+VKMR_API vkmr_status vkmr_hip_forest_append_async(int dev, vkmr_stream s, vkmr_digest* digests_dev, vkmr_digest* forest_dev,
+                                                  uint64_t total, uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count,
+                                                  uint32_t first_tree, uint64_t used, const vkmr_digest* leaves_dev,
+                                                  uint64_t n_leaves, const uint64_t* new_offsets_dev, uint32_t m,
+                                                  vkmr_digest* roots_dev, uint64_t* mutated_dev, uint32_t* status_dev);
+/*
+ * The inverse, for a reorganisation (drop the last trees, then append others): for keep_trees <= t < ntrees,
+ * offsets[t + 1] = offsets[keep_trees] and roots_dev[t] all zero -- one launch, no hash.  The cells of the level buffers are left
+ * as they are: they belong to no tree any more and nothing reads them.  Afterwards the forest is what a build over the shortened
+ * offsets writes, in every cell such a build writes.  keep_trees == ntrees does nothing; keep_trees > ntrees, or a NULL pointer
+ * with keep_trees < ntrees, is refused on the host.
+ */
+VKMR_API vkmr_status vkmr_hip_forest_truncate_async(int dev, vkmr_stream s, uint64_t* offsets_dev, uint32_t ntrees,
+                                                    uint32_t keep_trees, vkmr_digest* roots_dev);
+
+/*
  * COMBINE: duplicate-last Merkle root over n >= 1 slice roots given in slice order, always
  * at least one level -- the rule of CpuSha256D::Root that the reference applies to the slice
  * roots on the CPU (CpuSha256DforReductions, src/vkmr/Reductions.cpp:56-69, :703-712).  Here

@@ -78,16 +78,19 @@ __device__ __forceinline__ ForestLane forest_find_tree(const uint64_t* __restric
 // bit is there already (a stale read only costs an atomic).  Where every lane of the wavefront has tree t0 -- the search's
 // existing wave-uniform case -- the hits are one ballot and the first hit lane alone issues the atomic; where a tree begins
 // inside the wavefront each hit lane issues its own, at most 64 to at least 2 addresses.
+//
+// `base` is the cell the first wavefront begins at: 0 in the kernels that cover a level's whole buffer, the first cell of the
+// first new tree in the append's (below), whose `cells` is the end of its range and whose `ntrees` ends with the last new tree.
 template <bool HASH, bool COMPARE>
-__device__ __forceinline__ void forest_level(const Node* __restrict__ in, const uint64_t* __restrict__ offsets, uint32_t ntrees, uint32_t l, uint64_t cells,
-                                             Node* __restrict__ out, Node* __restrict__ roots, unsigned long long* __restrict__ mutated,
+__device__ __forceinline__ void forest_level(const Node* __restrict__ in, const uint64_t* __restrict__ offsets, uint32_t ntrees, uint32_t l, uint64_t base,
+                                             uint64_t cells, Node* __restrict__ out, Node* __restrict__ roots, unsigned long long* __restrict__ mutated,
                                              const uint32_t* __restrict__ status)
 {
     if constexpr (HASH) {
         if (*status != 0u) return;               // the same word in every lane
     }
     const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t p0 = ((uint64_t)blockIdx.x * (256u / 64u) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))) * 64ull;
+    const uint64_t p0 = base + ((uint64_t)blockIdx.x * (256u / 64u) + (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6))) * 64ull;
     if (p0 >= cells) return;                     // wave-uniform
     const uint64_t p = p0 + lane;
     const ForestLane at = forest_find_tree(offsets, ntrees, l, p0, lane);
@@ -134,7 +137,7 @@ __global__ __launch_bounds__(256) void forest_level_kernel(const Node* __restric
                                                            uint64_t cells, Node* __restrict__ out, Node* __restrict__ roots,
                                                            const uint32_t* __restrict__ status)
 {
-    forest_level<true, false>(in, offsets, ntrees, l, cells, out, roots, nullptr, status);
+    forest_level<true, false>(in, offsets, ntrees, l, 0ull, cells, out, roots, nullptr, status);
 }
 
 // The flagged build's level (vkmr_hip_reduce_forest_mutated_async, vkmr_hip_reduce_forest_tree_mutated_async): forest_level_kernel
@@ -143,7 +146,7 @@ __global__ __launch_bounds__(256) void forest_level_mutated_kernel(const Node* _
                                                                    uint32_t l, uint64_t cells, Node* __restrict__ out, Node* __restrict__ roots,
                                                                    unsigned long long* __restrict__ mutated, const uint32_t* __restrict__ status)
 {
-    forest_level<true, true>(in, offsets, ntrees, l, cells, out, roots, mutated, status);
+    forest_level<true, true>(in, offsets, ntrees, l, 0ull, cells, out, roots, mutated, status);
 }
 
 // The scan of a stored forest (vkmr_hip_forest_tree_mutated_async): the same search, the compare, no hash.  `in` is level l - 1
@@ -151,5 +154,86 @@ __global__ __launch_bounds__(256) void forest_level_mutated_kernel(const Node* _
 __global__ __launch_bounds__(256) void forest_scan_mutated_kernel(const Node* __restrict__ in, const uint64_t* __restrict__ offsets, uint32_t ntrees,
                                                                   uint32_t l, uint64_t cells, unsigned long long* __restrict__ mutated)
 {
-    forest_level<false, true>(in, offsets, ntrees, l, cells, nullptr, nullptr, mutated, nullptr);
+    forest_level<false, true>(in, offsets, ntrees, l, 0ull, cells, nullptr, nullptr, mutated, nullptr);
+}
+
+// ---- appending trees to a stored forest (vkmr_hip_forest_append_async; forest_plan.hpp: append_first_cell, append_end_cell) ----
+// Trees first_tree .. first_tree + m - 1, empty at offset `used` until now, take the n_leaves cells behind `used`.  The check,
+// the leaves, the offsets, then the build's own level body over the new trees' range of every level.  Every kernel behind the
+// check reads *status first and does nothing when it is nonzero.
+
+// No hash, a lane per item i: the new offsets (new_offsets[0] == 0, none decreasing, new_offsets[m] == n_leaves: bit 0; a
+// count above max_count: bit 1) for i < m, and the placement (offsets[first_tree + i] == used for every i up to
+// ntrees - first_tree, the forest's last offset included: bit 2, value 4).  ORed into *status, zeroed by the host.
+__global__ __launch_bounds__(256) void forest_append_check_kernel(const uint64_t* __restrict__ offsets, uint32_t ntrees, uint32_t first_tree, uint64_t used,
+                                                                  const uint64_t* __restrict__ new_offsets, uint32_t m, uint64_t n_leaves,
+                                                                  uint64_t max_count, uint32_t* __restrict__ status)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    uint32_t bits = 0u;
+    if (i < m) {
+        const uint64_t lo = new_offsets[i], hi = new_offsets[i + 1];
+        if (hi < lo || (i == 0 && lo != 0ull) || (i + 1 == m && hi != n_leaves)) bits |= 1u;
+        if (hi >= lo && hi - lo > max_count) bits |= 2u;
+    }
+    if (i <= (uint64_t)(ntrees - first_tree) && offsets[first_tree + i] != used) bits |= 4u;
+    if (bits) atomicOr(status, bits);
+}
+
+// The new leaves into level 0, a lane per leaf (not launched when the caller has put them there).  The check has passed: the
+// new offsets end at n_leaves and the host has seen used + n_leaves <= total.
+__global__ __launch_bounds__(256) void forest_append_leaves_kernel(Node* __restrict__ digests, uint64_t used, const Node* __restrict__ leaves,
+                                                                   uint64_t n_leaves, const uint32_t* __restrict__ status)
+{
+    if (*status != 0u) return;
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_leaves) return;
+    const Node x = vkmr_dev::load_node(leaves + i);
+    vkmr_dev::store_node(digests + used + i, x.w);
+}
+
+// A lane per tree first_tree + i, i < ntrees - first_tree: offsets[first_tree + i + 1], the end of that tree -- of a new one
+// used + new_offsets[i + 1], of every tree still empty behind them used + n_leaves.  offsets[first_tree] stays `used`.  With
+// `mutated` the mask of a new tree is zeroed here, so that a refused append leaves the masks alone as well.
+__global__ __launch_bounds__(256) void forest_append_offsets_kernel(uint64_t* __restrict__ offsets, uint32_t ntrees, uint32_t first_tree, uint64_t used,
+                                                                    const uint64_t* __restrict__ new_offsets, uint32_t m,
+                                                                    unsigned long long* __restrict__ mutated, const uint32_t* __restrict__ status)
+{
+    if (*status != 0u) return;
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (uint64_t)(ntrees - first_tree)) return;
+    offsets[first_tree + i + 1] = used + new_offsets[i < m ? i + 1 : m];
+    if (mutated != nullptr && i < m) mutated[first_tree + i] = 0ull;
+}
+
+// The build's level over the new trees alone: forest_level from cell `base` = append_first_cell(used, first_tree, l) to `end` =
+// append_end_cell(used + n_leaves, first_tree + m, l), searching among the `end_tree` = first_tree + m trees in front of that
+// end.  The first wavefront begins at the first new tree's first cell, so no lane holds a cell of an earlier tree; a lane
+// behind `end` finds the last new tree and is padding behind its nodes; a new tree without a leaf gets its zero root from the
+// lane of its reserved cell at level 1, as in the build.
+__global__ __launch_bounds__(256) void forest_append_level_kernel(const Node* __restrict__ in, const uint64_t* __restrict__ offsets, uint32_t end_tree,
+                                                                  uint32_t l, uint64_t base, uint64_t end, Node* __restrict__ out, Node* __restrict__ roots,
+                                                                  const uint32_t* __restrict__ status)
+{
+    forest_level<true, false>(in, offsets, end_tree, l, base, end, out, roots, nullptr, status);
+}
+
+// The same with the compare of the flagged build: the masks of the new trees, zeroed by forest_append_offsets_kernel.
+__global__ __launch_bounds__(256) void forest_append_level_flagged_kernel(const Node* __restrict__ in, const uint64_t* __restrict__ offsets,
+                                                                          uint32_t end_tree, uint32_t l, uint64_t base, uint64_t end, Node* __restrict__ out,
+                                                                          Node* __restrict__ roots, unsigned long long* __restrict__ mutated,
+                                                                          const uint32_t* __restrict__ status)
+{
+    forest_level<true, true>(in, offsets, end_tree, l, base, end, out, roots, mutated, status);
+}
+
+// Dropping the last trees (vkmr_hip_forest_truncate_async): a lane per tree t = keep_trees + i < ntrees ends it where tree
+// keep_trees begins and zeroes its root, as a build over the shortened offsets would.  offsets[keep_trees] is only read.
+__global__ __launch_bounds__(256) void forest_truncate_kernel(uint64_t* __restrict__ offsets, uint32_t ntrees, uint32_t keep_trees, Node* __restrict__ roots)
+{
+    const uint64_t t = (uint64_t)keep_trees + (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= ntrees) return;
+    offsets[t + 1] = offsets[keep_trees];
+    const uint32_t zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    vkmr_dev::store_node(roots + t, zero);
 }

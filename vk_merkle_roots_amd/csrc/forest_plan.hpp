@@ -101,4 +101,15 @@ VKMR_FOREST_FN UpdateStep update_step(uint64_t o, uint64_t c, uint32_t t, uint64
 // hashes the parent, when the entry in front of it (t0, i0) names another node.
 VKMR_FOREST_FN bool update_same_node(uint32_t t0, uint64_t i0, uint32_t t, uint64_t i, uint32_t l) { return t0 == t && (i0 >> l) == (i >> l); }
 
+// ---- appending trees to a stored forest (vkmr_hip_forest_append_async): trees first_tree .. first_tree + m - 1, until now
+// empty at offset `used`, take the n leaves behind `used`.  pos_l(t) depends on tree t's own offset and number alone, so
+// nothing in front moves, and the cells of the new trees at level l are one range of that level's buffer:
+//     [append_first_cell(used, first_tree, l), append_end_cell(used + n, first_tree + m, l))
+// from the first cell of the first new tree to the first cell of the tree behind the last new one (which may not exist:
+// the cell is inside level_cells all the same, see the head of this file).  Level 0's range is the new leaves themselves.
+// The ABI sizes its launches by it, forest_append_level_kernel starts its wavefronts at the first cell and searches among
+// trees 0 .. first_tree + m - 1 only, and tests/c/forest_append_plan_test.cpp replays both on the CPU.
+VKMR_FOREST_FN uint64_t append_first_cell(uint64_t used, uint32_t first_tree, uint32_t l) { return pos(used, first_tree, l); }
+VKMR_FOREST_FN uint64_t append_end_cell(uint64_t used_after, uint32_t end_tree, uint32_t l) { return pos(used_after, end_tree, l); }
+
 }  // namespace vkmr_forest

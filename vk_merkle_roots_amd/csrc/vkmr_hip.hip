@@ -17,6 +17,8 @@
 //                                              whole forest, level by level (no reference counterpart); builds the stored forest
 //                       forest_level_mutated_kernel, forest_scan_mutated_kernel   the same level with the mutation flag (equal
 //                                              sibling pairs, CVE-2012-2459) formed beside the hash, and the flag alone from stored levels
+//                       forest_append_*_kernel, forest_truncate_kernel   trees appended into the room a stored forest was built
+//                                              with (the level body again, over the new trees' cells alone), the last trees dropped
 //   forest_tree_kernels.hpp  forest_proofs_kernel          proofs gathered from the stored forest, one lane per (query, level)
 //                            verify_forest_proofs_kernel   batch verification of proofs of unequal height, one lane per proof
 //                            forest_update_*_kernel        leaf updates of the stored forest: tree_update_*'s bodies, a tree per entry
@@ -1152,6 +1154,57 @@ vkmr_status vkmr_hip_forest_update_async(int dev, vkmr_stream s, vkmr_digest* di
                           trees_dev, indices_dev, k, l, status_dev));
     }
     return VKMR_OK;
+}
+
+// ---- stored forests that grow: trees appended into reserved room, the last trees dropped (forest_kernels.hpp) ----------------
+
+vkmr_status vkmr_hip_forest_append_async(int dev, vkmr_stream s, vkmr_digest* digests_dev, vkmr_digest* forest_dev, uint64_t total,
+                                         uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count, uint32_t first_tree, uint64_t used,
+                                         const vkmr_digest* leaves_dev, uint64_t n_leaves, const uint64_t* new_offsets_dev, uint32_t m,
+                                         vkmr_digest* roots_dev, uint64_t* mutated_dev, uint32_t* status_dev)
+{
+    if (m == 0) return VKMR_OK;
+    if (!digests_dev || !forest_dev || !offsets_dev || (!leaves_dev && n_leaves > 0) || !new_offsets_dev || !roots_dev || !status_dev)
+        return refuse(__func__, "null pointer");
+    if (first_tree > ntrees || m > ntrees - first_tree) return refuse(__func__, "more trees than the forest has room for");
+    if (used > total || n_leaves > total - used) return refuse(__func__, "more leaves than the forest has room for");
+    VKMR_CHECK(forest_args_check(__func__, total, ntrees, max_count, 0, nullptr, nullptr));
+    if (grid_too_large(groups_of(n_leaves))) return refuse(__func__, "too many leaves in one call");
+    const uint32_t H = vkmr_forest::launches(total, max_count);   // <= 58: the build's, so every level buffer is where the build put it
+    const uint32_t end_tree = first_tree + m, behind = ntrees - first_tree;
+    Node* digests = nodes(digests_dev);
+    Node* forest = nodes(forest_dev);
+    Node* roots = nodes(roots_dev);
+    unsigned long long* mutated = reinterpret_cast<unsigned long long*>(mutated_dev);
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_TRY(hipMemsetAsync(status_dev, 0, sizeof(uint32_t), S(s)));
+    // a lane per offset from first_tree to ntrees: behind + 1 of them, and m <= behind new trees among them
+    VKMR_CHECK(launch(forest_append_check_kernel, grid_of((uint64_t)behind + 1), dim3(256), S(s), offsets_dev, ntrees, first_tree, used, new_offsets_dev,
+                      m, n_leaves, max_count, status_dev));
+    if (n_leaves > 0 && leaves_dev != digests_dev + used)   // not yet in place
+        VKMR_CHECK(launch(forest_append_leaves_kernel, grid_of(n_leaves), dim3(256), S(s), digests, used, nodes(leaves_dev), n_leaves, status_dev));
+    // the offsets, and the masks of the new trees zeroed in the same launch: a memset could not read the status word
+    VKMR_CHECK(launch(forest_append_offsets_kernel, grid_of(behind), dim3(256), S(s), offsets_dev, ntrees, first_tree, used, new_offsets_dev, m, mutated,
+                      status_dev));
+    for (uint32_t l = 1; l <= H; ++l) {   // level l from level l - 1, over the new trees' cells alone
+        const Node* in = (l == 1) ? digests : forest + vkmr_forest::stored_level_base(total, ntrees, l - 1);
+        Node* out = forest + vkmr_forest::stored_level_base(total, ntrees, l);
+        const uint64_t base = vkmr_forest::append_first_cell(used, first_tree, l), end = vkmr_forest::append_end_cell(used + n_leaves, end_tree, l);
+        VKMR_CHECK(mutated ? launch(forest_append_level_flagged_kernel, grid_of(end - base), dim3(256), S(s), in, offsets_dev, end_tree, l, base, end, out, roots,
+                                    mutated, status_dev)
+                           : launch(forest_append_level_kernel, grid_of(end - base), dim3(256), S(s), in, offsets_dev, end_tree, l, base, end, out, roots,
+                                    status_dev));
+    }
+    return VKMR_OK;
+}
+
+vkmr_status vkmr_hip_forest_truncate_async(int dev, vkmr_stream s, uint64_t* offsets_dev, uint32_t ntrees, uint32_t keep_trees, vkmr_digest* roots_dev)
+{
+    if (keep_trees > ntrees) return refuse(__func__, "more trees to keep than the forest has");
+    if (keep_trees == ntrees) return VKMR_OK;
+    if (!offsets_dev || !roots_dev) return refuse(__func__, "null pointer");
+    VKMR_TRY(hipSetDevice(dev));
+    return launch(forest_truncate_kernel, grid_of(ntrees - keep_trees), dim3(256), S(s), offsets_dev, ntrees, keep_trees, nodes(roots_dev));
 }
 
 // ---- multiproofs inside the stored forest (forest_tree_kernels.hpp) ---------------------------------------------------------

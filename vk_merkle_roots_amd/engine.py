@@ -541,10 +541,15 @@ class HipDevice:
                 return None
             return self.download(d_roots, roots.nbytes).reshape(-1, 8)
 
-    def _build_forest_of_buffer(self, d_leaves, total, counts, max_count, what, owned=(), mutated=False):
+    def _build_forest_of_buffer(self, d_leaves, total, counts, max_count, what, owned=(), mutated=False, reserve_trees=0, reserve_leaves=0):
         """A MerkleForest of the trees of `counts` leaves each over the `total` cells of d_leaves (its level 0); with `mutated`
-        built by the flagged twin, whose masks it keeps."""
-        offsets, ntrees = _checked_offsets(counts, total, what)
+        built by the flagged twin, whose masks it keeps.  The last reserve_leaves of the `total` cells stay free behind the
+        last leaf, and reserve_trees empty trees follow the last tree: room for MerkleForest.append."""
+        reserve_trees, reserve_leaves = _reserve(what, reserve_trees, reserve_leaves, max_count)
+        offsets, used_trees = _checked_offsets(counts, total, what, slack=reserve_leaves)
+        ntrees = used_trees + reserve_trees
+        if reserve_trees:
+            offsets = np.concatenate([offsets, np.full(reserve_trees, offsets[-1], dtype=np.uint64)])
         if ntrees == 0:
             raise ValueError(f"{what}: no tree")
         with self.scope() as tmp:
@@ -553,20 +558,31 @@ class HipDevice:
                                                                       d_mutated=d_mut)
             masks = self.download(d_mut, 8 * ntrees, dtype=np.uint64) if mutated else None
             tmp.release(d_off, d_forest, d_roots)      # the forest's from here on
-        return MerkleForest(self, d_leaves, total, np.diff(offsets), d_off, max_count, d_forest, d_roots, owned=owned, built_mutated=masks)
+        return MerkleForest(self, d_leaves, total, np.diff(offsets), d_off, max_count, d_forest, d_roots, owned=owned, built_mutated=masks,
+                            used_trees=used_trees)
 
-    def build_forest(self, digests, counts, max_count=None, mutated=False):
+    def build_forest(self, digests, counts, max_count=None, mutated=False, reserve_trees=0, reserve_leaves=0):
         """Every level of every tree of a forest, kept on the device: a MerkleForest (vkmr_hip_reduce_forest_tree_async).
         `digests` [total, 8] (a host array) holds the leaves of all trees back to back, tree t the next counts[t] of them;
         max_count: an upper bound on every count (the largest count when None).  mutated=True builds with
         vkmr_hip_reduce_forest_tree_mutated_async -- the same forest -- and keeps the build's masks in `built_mutated`.
-        ValueError when the counts do not add up to the leaves, for no tree at all, or when the device refuses the forest (a
-        count above max_count)."""
+        reserve_trees, reserve_leaves: room for MerkleForest.append -- that many empty trees behind the last tree and spare
+        cells behind the last leaf; max_count must then be given, it bounds the trees still to come.
+        ValueError when the counts do not add up to the leaves, for no tree at all, for room reserved without a max_count, or
+        when the device refuses the forest (a count above max_count)."""
         digests = _host(digests, np.uint32, -1, 8)
-        total = int(digests.shape[0])
+        reserve_trees, reserve_leaves = _reserve("build_forest", reserve_trees, reserve_leaves, max_count)
+        used, total = int(digests.shape[0]), int(digests.shape[0]) + reserve_leaves
         with self.scope() as tmp:
-            d_in = tmp.upload(digests) if total else None
-            forest = self._build_forest_of_buffer(d_in, total, counts, max_count, "build_forest", owned=[d_in] if d_in else [], mutated=mutated)
+            if reserve_leaves:
+                d_in = tmp.alloc(32 * total)
+                if used:
+                    self._call("vkmr_hip_memcpy_h2d_async", d_in, digests.ctypes.data, digests.nbytes)
+                    self.sync()
+            else:
+                d_in = tmp.upload(digests) if total else None
+            forest = self._build_forest_of_buffer(d_in, total, counts, max_count, "build_forest", owned=[d_in] if d_in else [], mutated=mutated,
+                                                  reserve_trees=reserve_trees, reserve_leaves=reserve_leaves)
             tmp.release(d_in)
         return forest
 
@@ -668,6 +684,22 @@ class HipDevice:
         info_buf[2] is the tree's own level mask.  scratch_buf: audit_scratch_bytes(count, 1, capacity)."""
         self._call("vkmr_hip_tree_audit_async", digests_buf, tree_buf, count, height, scratch_buf, levels_buf, nodes_buf, capacity, info_buf,
                    stream=stream)
+
+    # -- stored forests that grow: trees appended into reserved room, the last trees dropped (named like the two above) -----
+    def forest_append_enqueue(self, digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, first_tree, used, leaves_buf, n_leaves,
+                              new_offsets_buf, m, roots_buf, mutated_buf, status_buf, stream=None):
+        """Trees first_tree .. first_tree + m - 1 of a stored forest built with room to spare (total, ntrees, max_count: the
+        build's), empty at offset `used` until now, take the n_leaves digests of leaves_buf: new tree j those from
+        new_offsets_buf[j] to new_offsets_buf[j + 1] (m + 1 uint64, from 0 to n_leaves).  leaves_buf at digests_buf.at(32 * used):
+        the leaves are in place.  mutated_buf (ntrees uint64) or None: the masks of the new trees.  status_buf: one uint32,
+        forest_append_status_text names its bits; nonzero: nothing changed.  All in device memory.  include/vkmr_hip.h."""
+        self._call("vkmr_hip_forest_append_async", digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, first_tree, used, leaves_buf,
+                   n_leaves, new_offsets_buf, m, roots_buf, mutated_buf, status_buf, stream=stream)
+
+    def forest_truncate_enqueue(self, offsets_buf, ntrees, keep_trees, roots_buf, stream=None):
+        """Trees keep_trees .. ntrees - 1 of a stored forest emptied: their offsets end where tree keep_trees begins, their
+        roots are zero; one launch, no hash."""
+        self._call("vkmr_hip_forest_truncate_async", offsets_buf, ntrees, keep_trees, roots_buf, stream=stream)
 
     def reduce_scratch(self, count, levels_variant=False):
         fn = self.lib.vkmr_hip_reduce_levels_scratch_bytes if levels_variant else self.lib.vkmr_hip_reduce_scratch_bytes
@@ -1275,14 +1307,110 @@ class MerkleForest(_Stored):
     cells = property(lambda self: self.total)
     stride = property(lambda self: self.levels)
 
-    def __init__(self, dev, digests_buf, total, counts, offsets_buf, max_count, forest_buf, roots_buf, owned=(), built_mutated=None):
+    def __init__(self, dev, digests_buf, total, counts, offsets_buf, max_count, forest_buf, roots_buf, owned=(), built_mutated=None, used_trees=None):
         self.built_mutated = built_mutated
         self.dev, self.digests, self.total, self.offsets, self.max_count = dev, digests_buf, int(total), offsets_buf, int(max_count)
-        self.counts = np.asarray(counts, dtype=np.uint64)
+        self.counts = np.array(counts, dtype=np.uint64)      # one entry per tree of the capacity; a copy, append() writes into it
         self.ntrees = int(self.counts.shape[0])
         self.levels = tree_height(min(self.max_count, self.total)) if self.total else 1
         self.forest, self.roots_buf = forest_buf, roots_buf
         self._owned = list(owned)
+        self.used_trees = self.ntrees if used_trees is None else int(used_trees)
+
+    # -- room to grow: `total` and `ntrees` are the capacity the level buffers are laid out for; the trees in use are the first
+    # used_trees, their leaves the first used_leaves cells; the trees behind them are empty and the cells behind them free
+    used_leaves = property(lambda self: int(self.counts.sum()))
+    free_trees = property(lambda self: self.ntrees - self.used_trees)
+    free_leaves = property(lambda self: self.total - self.used_leaves)
+
+    def append_async(self, leaves_buf, n_leaves, new_offsets_buf, m, status_buf, mutated_buf=None, stream=None):
+        """The next m free trees take the n_leaves digests of leaves_buf, new tree j those from new_offsets_buf[j] to
+        new_offsets_buf[j + 1] (m + 1 uint64 from 0 to n_leaves, none above max_count apart); all in device memory.
+        leaves_buf at digests.at(32 * used_leaves): they are in place.  status_buf: one uint32, 0 when appended
+        (forest_append_status_text names the bits; nonzero: nothing changed); mutated_buf: ntrees uint64 or None, the masks
+        of the new trees.  Ordered on `stream`: a proof gather behind it sees the new trees.  Only enqueues: the caller who
+        has seen status 0 tells the handle with appended(counts)."""
+        self.dev.forest_append_enqueue(self.digests, self.forest, self.total, self.offsets, self.ntrees, self.max_count, self.used_trees,
+                                       self.used_leaves, leaves_buf, n_leaves, new_offsets_buf, m, self.roots_buf, mutated_buf, status_buf,
+                                       stream=stream)
+
+    def appended(self, counts):
+        """The host's view after an append_async that reported status 0: the next len(counts) trees are in use with these counts."""
+        m = len(counts)
+        self.counts[self.used_trees: self.used_trees + m] = np.asarray(counts, dtype=np.uint64)
+        self.used_trees += m
+
+    def _append_counts(self, counts, n, what, cells="digests"):
+        """The new trees' offsets relative to used_leaves (uint64 [m + 1]) and the counts (uint64 [m]), refused here -- before
+        any device call -- when they do not add up to the n digests, do not fit the free trees or leaves, or exceed max_count."""
+        offsets, m = _checked_offsets(counts, n, what, cells)
+        new = np.diff(offsets)
+        if m > self.free_trees:
+            raise ValueError(f"{what}: {m} trees, room for {self.free_trees}")
+        if n > self.free_leaves:
+            raise ValueError(f"{what}: {n} leaves, room for {self.free_leaves}")
+        if m and int(new.max()) > self.max_count:
+            raise ValueError(f"{what}: a tree of {int(new.max())} leaves, max_count is {self.max_count}")
+        return offsets, new
+
+    def _append(self, tmp, leaves_buf, offsets, new, mutated, what):
+        """append_async of leaves in device memory with its buffers in the scope `tmp`, waited for: the numbers of the new
+        trees, with `mutated` (numbers, their masks).  RuntimeError when the device refuses what was checked here."""
+        first, m = self.used_trees, int(new.shape[0])
+        trees = np.arange(first, first + m, dtype=np.uint32)
+        masks = np.zeros(m, dtype=np.uint64)
+        if m:
+            d_status, d_mut = tmp.alloc(4), tmp.alloc(8 * self.ntrees) if mutated else None
+            self.append_async(leaves_buf, int(offsets[-1]), tmp.upload(offsets), m, d_status, d_mut)
+            status = int(self.dev.download(d_status, 4)[0])
+            if status:
+                raise RuntimeError(f"MerkleForest.{what}: the device refused the trees (status {status}: {forest_append_status_text(status)})")
+            if mutated:
+                masks = self.dev.download(d_mut, 8 * m, dtype=np.uint64, offset=8 * first)
+            self.appended(new)
+        return (trees, masks) if mutated else trees
+
+    def append(self, digests, counts, mutated=False):
+        """New trees behind the last one in use, into the room reserved at the build (build_forest(reserve_trees=,
+        reserve_leaves=)): `digests` [n, 8] (a host array) holds their leaves back to back, new tree j the next counts[j] of
+        them.  Only the new trees are hashed; nothing of an earlier tree moves, and the forest is afterwards what a build over
+        all its trees gives.  The numbers of the new trees (uint32 [m]); mutated=True: (numbers, their mutation masks uint64
+        [m], what forest_roots_mutated gives for them).  ValueError, before any device call, when the counts do not add up
+        to the digests, when there is no room for the trees or the leaves, or for a count above max_count."""
+        digests = _host(digests, np.uint32, -1, 8)
+        offsets, new = self._append_counts(counts, int(digests.shape[0]), "append")
+        if new.shape[0] == 0:
+            return self._append(None, None, offsets, new, mutated, "append")
+        with self.dev.scope() as tmp:
+            return self._append(tmp, tmp.upload(digests) if digests.shape[0] else None, offsets, new, mutated, "append")
+
+    def append_packed(self, batch, counts):
+        """append() of the digests of the strings of `batch`, new tree j over the next counts[j] of them: the strings are
+        mapped on the device straight into level 0 behind the last leaf and the trees appended in place; no digest goes
+        through the host.  append()'s refusals; the numbers of the new trees."""
+        offsets, new = self._append_counts(counts, batch.count, "append_packed", "strings")
+        if new.shape[0] == 0:
+            return self._append(None, None, offsets, new, False, "append_packed")
+        with self.dev.scope() as tmp:
+            if batch.count:
+                self.dev.map_packed(tmp, batch, out_buf=self.digests, out_offset_digests=self.used_leaves)
+            return self._append(tmp, self.digests.at(32 * self.used_leaves) if batch.count else None, offsets, new, False, "append_packed")
+
+    def truncate_async(self, keep_trees, stream=None):
+        """Trees keep_trees .. ntrees - 1 emptied on the device (their roots zero, their leaves' cells free again) and in the
+        host's view; one launch on `stream`.  ValueError for keep_trees above used_trees."""
+        keep_trees = int(keep_trees)
+        if not 0 <= keep_trees <= self.used_trees:
+            raise ValueError(f"truncate: {keep_trees} trees to keep, {self.used_trees} in use")
+        self.dev.forest_truncate_enqueue(self.offsets, self.ntrees, keep_trees, self.roots_buf, stream=stream)
+        self.counts[keep_trees:] = 0
+        self.used_trees = keep_trees
+
+    def truncate(self, keep_trees):
+        """Drop the last trees in use, all from number keep_trees on: the inverse of append(), for appending others in their
+        place.  Trees cannot be dropped from the front.  ValueError for keep_trees above used_trees."""
+        self.truncate_async(keep_trees)
+        self.dev.sync()
 
     def roots(self):
         """[ntrees, 8] uint32: what forest_roots gives for the same leaves (an all-zero root for an empty tree)."""
@@ -1408,7 +1536,8 @@ class MerkleForest(_Stored):
         return self._update_entries((trees_buf, indices_buf), leaves_buf, k)
 
     def _same_shape(self, other, what):
-        """ValueError unless `other` is a MerkleForest of this forest's device, counts, cells and max_count; no device call."""
+        """ValueError unless `other` is a MerkleForest of this forest's device, counts, capacity (cells and trees, room to grow
+        included) and max_count; no device call."""
         if not isinstance(other, MerkleForest):
             raise ValueError(f"{what}: the other side is no MerkleForest")
         if other.dev.index != self.dev.index:
@@ -1470,12 +1599,24 @@ def forest_offsets(counts):
     return offsets, int(raw.size)
 
 
-def _checked_offsets(counts, total, what, cells="leaves"):
-    """forest_offsets(counts); ValueError when they do not add up to the `total` leaves (or strings) at hand."""
+def _checked_offsets(counts, total, what, cells="leaves", slack=0):
+    """forest_offsets(counts); ValueError when they do not add up to the leaves (or strings) at hand: the `total` cells less
+    the `slack` kept free behind the last of them."""
     offsets, ntrees = forest_offsets(counts)
-    if int(offsets[-1]) != total:
-        raise ValueError(f"{what}: the counts add up to {int(offsets[-1])}, not to the {total} {cells}")
+    if int(offsets[-1]) + slack != total:
+        raise ValueError(f"{what}: the counts add up to {int(offsets[-1])}, not to the {total - slack} {cells}")
     return offsets, ntrees
+
+
+def _reserve(what, reserve_trees, reserve_leaves, max_count):
+    """(reserve_trees, reserve_leaves) as non-negative ints; ValueError for a negative one, or when room is reserved and
+    max_count is left open: the largest count of today's trees would bound the trees still to come."""
+    reserve_trees, reserve_leaves = int(reserve_trees), int(reserve_leaves)
+    if reserve_trees < 0 or reserve_leaves < 0:
+        raise ValueError(f"{what}: negative reserve")
+    if (reserve_trees or reserve_leaves) and max_count is None:
+        raise ValueError(f"{what}: a forest with room to grow needs an explicit max_count")
+    return reserve_trees, reserve_leaves
 
 
 def forest_status_text(status):
@@ -1502,6 +1643,20 @@ def forest_update_status_text(status):
     return "; ".join(names) if names else "ok"
 
 
+def forest_append_status_text(status):
+    """The bits of vkmr_hip_forest_append_async's status word, named."""
+    names = []
+    if status & 1:
+        names.append("bit 0: the new offsets decrease, do not start at 0 or do not end at the new leaves")
+    if status & 2:
+        names.append("bit 1: a new tree holds more than max_count leaves")
+    if status & 4:
+        names.append("bit 2: the forest's free trees do not begin where the caller says")
+    if status & ~7:
+        names.append("unknown bits")
+    return "; ".join(names) if names else "ok"
+
+
 def forest_multiproof_status_text(status):
     """The bits of vkmr_hip_forest_multiproof_async's status word (info[0]), named."""
     names = []
@@ -1514,23 +1669,32 @@ def forest_multiproof_status_text(status):
     return "; ".join(names) if names else "ok"
 
 
-def _forest_packed(dev, batch, counts, max_count, what, stored, mutated=False):
+def _forest_packed(dev, batch, counts, max_count, what, stored, mutated=False, reserve_trees=0, reserve_leaves=0):
     """`batch` mapped to leaf digests ONCE and one forest call over them: the roots (with `mutated`: and the masks), or with
-    `stored` a MerkleForest that owns its leaves."""
+    `stored` a MerkleForest that owns its leaves, with room to grow when some is reserved."""
     _checked_offsets(counts, batch.count, what, "strings")
+    reserve_trees, reserve_leaves = _reserve(what, reserve_trees, reserve_leaves, max_count)
     with dev.scope() as tmp:
-        d_leaves = dev.map_packed(tmp, batch) if batch.count else None
+        if reserve_leaves:                       # the leaves buffer with spare cells behind the last leaf
+            d_leaves = tmp.alloc(32 * (batch.count + reserve_leaves))
+            if batch.count:
+                dev.map_packed(tmp, batch, out_buf=d_leaves)
+        else:
+            d_leaves = dev.map_packed(tmp, batch) if batch.count else None
         if not stored:
             return dev._forest_of_buffer(d_leaves, batch.count, counts, max_count, what, mutated=mutated)
-        forest = dev._build_forest_of_buffer(d_leaves, batch.count, counts, max_count, what, owned=[d_leaves] if d_leaves else [])
+        forest = dev._build_forest_of_buffer(d_leaves, batch.count + reserve_leaves, counts, max_count, what, owned=[d_leaves] if d_leaves else [],
+                                             reserve_trees=reserve_trees, reserve_leaves=reserve_leaves)
         tmp.release(d_leaves)
     return forest
 
 
-def merkle_forest_packed(dev, batch, counts, max_count=None):
+def merkle_forest_packed(dev, batch, counts, max_count=None, reserve_trees=0, reserve_leaves=0):
     """The strings of `batch` mapped to leaf digests ONCE and the stored forest built over them, tree t over the next
-    counts[t] of them, all on the device (a MerkleForest that owns its leaves)."""
-    return _forest_packed(dev, batch, counts, max_count, "merkle_forest_packed", stored=True)
+    counts[t] of them, all on the device (a MerkleForest that owns its leaves).  reserve_trees, reserve_leaves: room for
+    MerkleForest.append and append_packed, as HipDevice.build_forest reserves it; max_count must then be given."""
+    return _forest_packed(dev, batch, counts, max_count, "merkle_forest_packed", stored=True, reserve_trees=reserve_trees,
+                          reserve_leaves=reserve_leaves)
 
 
 def merkle_roots_packed_forest(dev, batch, counts, max_count=None):
