@@ -886,6 +886,50 @@ VKMR_API vkmr_status vkmr_hip_forest_truncate_async(int dev, vkmr_stream s, uint
                                                     uint32_t keep_trees, vkmr_digest* roots_dev);
 
 /*
+ * THE OPEN TREE GROWS OR SHRINKS BY LEAVES, at its right edge: a block still collecting transactions, the newest file of an
+ * index, a log kept as one tree (a forest of one tree built with a reserve).  The open tree is the last tree in use: every
+ * tree behind it is empty.  Its cells do not move -- node j of its level l is cell (offsets[tree] >> l) + tree + j whatever its
+ * count -- so taking n more leaves, or dropping the last r, rehashes only the nodes whose value changes: those from
+ * min(count, new count) >> l on at level l, at most (n >> l) + 2 of them; where the old or the new tree has a single node at
+ * level l the range starts at node 0, because the build keeps a tree's last level in roots_dev alone (growing 2 -> 3 must form
+ * a cell never stored; shrinking 3 -> 2 must carry an inner cell to roots_dev).
+ *   total, ntrees, max_count   those of the build (the capacity), TRUSTED as vkmr_hip_forest_update_async trusts them, and
+ *                              with them the offsets of the trees in front of `tree`, which the build checked
+ *   tree, count, used          the open tree, its leaves now, the leaves in use: offsets[tree] + count == used ==
+ *                              offsets[tree + 1] == .. == offsets[ntrees]; host values, so that every grid is sized without
+ *                              reading device memory; checked on the device
+ *   leaves_dev                 (extend) the n_leaves new leaves in device memory; leaves_dev == digests_dev + used says that they
+ *                              are in place already (vkmr_hip_map_async writes at an output offset) and no copy is launched
+ *   r                          (shrink) the leaves dropped from the end; their cells are free again and are not written
+ *   mutated_dev                NULL, or the ntrees masks of the flagged builds: the open tree's is zeroed and formed again
+ *                              from the whole tree (a compare without a hash behind each level: an old right-edge pair may have
+ *                              set a bit that must clear, so the edge alone cannot say); no other mask is touched
+ *   status_dev                 one uint32_t in device memory, always written, in vkmr_hip_forest_append_async's numbering:
+ *                              0 when done; bit 2 (value 4) if offsets[tree] + count != used or some offsets[t] != used for
+ *                              tree < t <= ntrees.  When it is nonzero NOTHING of the caller's has changed: no leaf cell (but
+ *                              those the caller put in place itself), no offset, no cell of forest_dev, no root, no mask.
+ * After status 0 offsets[t + 1] is offsets[tree] + the new count for every t >= tree, and every cell of the leaves, forest_dev,
+ * roots_dev and offsets_dev that a fresh vkmr_hip_reduce_forest_tree_async over those offsets writes holds what it writes (a
+ * tree shrunk to no leaf: the zero root).  Cells such a build does not write -- those of dropped nodes -- keep what they held.
+ * Launches, all on the caller's stream: the status word zeroed, one check, the leaves unless in place (extend), the offsets
+ * (which zeroes the mask too), then at most one launch per level, H = max(1, ceil(log2 min(max_count, total))) of them, level
+ * l over the dirty nodes alone, never a level's whole buffer, and none where there is no dirty node (and with mutated_dev the
+ * compare behind it, over the one tree); no launch per node, no allocation, no host read of device data.  Refused on the host
+ * (VKMR_ERR_INVALID), before any HIP call: a NULL pointer (mutated_dev may always be NULL), tree >= ntrees, count + n_leaves
+ * > max_count, used + n_leaves > total, r > count, count > used, used > total, max_count == 0, total > 2^58.  n_leaves == 0 or
+ * r == 0 does nothing whatever the other arguments.  Stream-ordered: a proof gather enqueued after it on the same stream sees
+ * the new leaves.  The host advances its own count and used by n_leaves, or takes r from both.
+ */
+VKMR_API vkmr_status vkmr_hip_forest_extend_async(int dev, vkmr_stream s, vkmr_digest* digests_dev, vkmr_digest* forest_dev,
+                                                  uint64_t total, uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count,
+                                                  uint32_t tree, uint64_t count, uint64_t used, const vkmr_digest* leaves_dev,
+                                                  uint64_t n_leaves, vkmr_digest* roots_dev, uint64_t* mutated_dev, uint32_t* status_dev);
+VKMR_API vkmr_status vkmr_hip_forest_shrink_async(int dev, vkmr_stream s, vkmr_digest* digests_dev, vkmr_digest* forest_dev,
+                                                  uint64_t total, uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count,
+                                                  uint32_t tree, uint64_t count, uint64_t used, uint64_t r, vkmr_digest* roots_dev,
+                                                  uint64_t* mutated_dev, uint32_t* status_dev);
+
+/*
  * COMBINE: duplicate-last Merkle root over n >= 1 slice roots given in slice order, always
  * at least one level -- the rule of CpuSha256D::Root that the reference applies to the slice
  * roots on the CPU (CpuSha256DforReductions, src/vkmr/Reductions.cpp:56-69, :703-712).  Here

@@ -237,3 +237,64 @@ __global__ __launch_bounds__(256) void forest_truncate_kernel(uint64_t* __restri
     const uint32_t zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     vkmr_dev::store_node(roots + t, zero);
 }
+
+// ---- the open tree grown or shrunk by leaves (vkmr_hip_forest_extend_async, vkmr_hip_forest_shrink_async; forest_plan.hpp:
+// extend_first_cell, extend_end_cell) ----
+// Tree `tree`, the last in use, at offset used - count goes from `count` to `new_end - (used - count)` leaves; every tree
+// behind it is empty at `used`.  The check, the leaves (forest_append_leaves_kernel, when growing and not in place), the
+// offsets, then the build's own level body over the dirty nodes of the tree's right edge.  Every kernel behind the check
+// reads *status first and does nothing when it is nonzero.
+
+// No hash, a lane per offset tree + i, i <= ntrees - tree: the open tree begins where the caller says (offsets[tree] + count ==
+// used) and every later offset, the forest's last included, is `used`: the trees behind are empty.  Bit 2 (value 4), the
+// append's numbering, ORed into *status, zeroed by the host.  count <= used is the host's.
+__global__ __launch_bounds__(256) void forest_extend_check_kernel(const uint64_t* __restrict__ offsets, uint32_t ntrees, uint32_t tree, uint64_t count,
+                                                                  uint64_t used, uint32_t* __restrict__ status)
+{
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i > (uint64_t)(ntrees - tree)) return;
+    if (offsets[tree + i] != (i == 0ull ? used - count : used)) atomicOr(status, 4u);
+}
+
+// A lane per tree tree + i, i < ntrees - tree: offsets[tree + i + 1] = new_end, the end of the open tree and of every empty tree
+// behind it.  offsets[tree] stays.  With `mutated` the open tree's mask is zeroed here, not by a memset, so that a refused
+// call leaves it alone; forest_extend_scan_kernel forms it again.
+__global__ __launch_bounds__(256) void forest_extend_offsets_kernel(uint64_t* __restrict__ offsets, uint32_t ntrees, uint32_t tree, uint64_t new_end,
+                                                                    unsigned long long* __restrict__ mutated, const uint32_t* __restrict__ status)
+{
+    if (*status != 0u) return;
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (uint64_t)(ntrees - tree)) return;
+    offsets[tree + i + 1] = new_end;
+    if (mutated != nullptr && i == 0ull) mutated[tree] = 0ull;
+}
+
+// The build's level over the open tree's dirty nodes alone: forest_level from cell `base` = extend_first_cell to `end` =
+// extend_end_cell, searching among the `end_tree` = tree + 1 trees up to the open one.  What the body does at the edges:
+//   the first wavefront begins at pos_l(tree) + first_l, inside the open tree, and pos_l grows with t: the search ends at the
+//     last of its end_tree trees, `tree`, in every wavefront, t0 + 1 == end_tree makes `mixed` false, and no lane holds an
+//     earlier tree's cell (p >= pos_l(tree) always);
+//   the offsets kernel ran first, so c is the NEW count; a lane behind `end` finds the open tree as well and has
+//     j >= n_out: padding, it returns in front of every load and store.  The reserved cells and the roots of the empty trees
+//     behind are therefore not written -- the search does not know those trees;
+//   a tree shrunk to no leaf: the range is its reserved cell at level 1, whose lane writes the zero root (the c == 0 branch).
+// Forcing the first node to 0 at a lone-node level (forest_plan.hpp) is the host's: it arrives here as `base`, the body's
+// existing argument, and the body is the text the build and the append compile.
+__global__ __launch_bounds__(256) void forest_extend_level_kernel(const Node* __restrict__ in, const uint64_t* __restrict__ offsets, uint32_t end_tree,
+                                                                  uint32_t l, uint64_t base, uint64_t end, Node* __restrict__ out, Node* __restrict__ roots,
+                                                                  const uint32_t* __restrict__ status)
+{
+    forest_level<true, false>(in, offsets, end_tree, l, base, end, out, roots, nullptr, status);
+}
+
+// The open tree's mask formed again: the scan's body (compare, no hash) over ALL nodes of the tree at level l, from `base` =
+// pos_l(tree) to `end` = extend_end_cell -- an old right-edge pair may have set a bit that no pair of the new tree sets, so
+// the edge alone cannot say.  `in` is level l - 1 as the hash launches of this call have left it.  The scan's body reads no
+// status word, so this kernel does.
+__global__ __launch_bounds__(256) void forest_extend_scan_kernel(const Node* __restrict__ in, const uint64_t* __restrict__ offsets, uint32_t end_tree,
+                                                                 uint32_t l, uint64_t base, uint64_t end, unsigned long long* __restrict__ mutated,
+                                                                 const uint32_t* __restrict__ status)
+{
+    if (*status != 0u) return;
+    forest_level<false, true>(in, offsets, end_tree, l, base, end, nullptr, nullptr, mutated, nullptr);
+}

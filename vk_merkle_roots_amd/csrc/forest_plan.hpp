@@ -112,4 +112,31 @@ VKMR_FOREST_FN bool update_same_node(uint32_t t0, uint64_t i0, uint32_t t, uint6
 VKMR_FOREST_FN uint64_t append_first_cell(uint64_t used, uint32_t first_tree, uint32_t l) { return pos(used, first_tree, l); }
 VKMR_FOREST_FN uint64_t append_end_cell(uint64_t used_after, uint32_t end_tree, uint32_t l) { return pos(used_after, end_tree, l); }
 
+// ---- growing or shrinking the open tree by leaves (vkmr_hip_forest_extend_async, vkmr_hip_forest_shrink_async): tree t, the
+// last tree in use (every tree behind it empty), at offset o goes from c to c2 leaves at its right edge.  pos_l(o, t) does not
+// move, so node j of its level l stays in its cell, and the nodes whose value changes are those from min(c, c2) >> l on: the
+// launch of level l >= 1 covers nodes [extend_first_node(c, c2, l), extend_end_node(c2, l)) of tree t, the cells
+//     [extend_first_cell(o, t, c, c2, l), extend_end_cell(o, t, c2, l))
+// of level l's buffer.  THE LONE NODE.  The build writes a tree's last level to roots[t] only, never to its cell.  So where the
+// old tree had one node at level l (c a power of two grows past it: 2 -> 3) that node's cell has never been stored and must be
+// formed now; and where the new tree has one node at level l (c shrinks to a power of two: 3 -> 2) that node is an inner
+// cell nothing touched, and must reach roots[t].  Both are node 0, so the range starts at 0 wherever either count leaves one
+// node: the body needs no word of it, it takes the first cell.  The range is empty (first == end == 0) where the new tree
+// takes no part in level l: l > 1 and its level l - 1 had one node, the body's own "tree is done" test.  A tree shrunk to no
+// leaf gets one lane at level 1, its reserved cell's, which writes the zero root as in the build.  The ABI sizes its launches
+// by these, forest_extend_level_kernel starts at the first cell and tests/c/forest_extend_plan_test.cpp replays both.
+VKMR_FOREST_FN uint64_t extend_end_node(uint64_t c2, uint32_t l)
+{
+    if (c2 == 0) return l == 1u ? 1 : 0;
+    return (l > 1u && level_count(c2, l - 1u) == 1) ? 0 : level_count(c2, l);
+}
+VKMR_FOREST_FN uint64_t extend_first_node(uint64_t c, uint64_t c2, uint32_t l)
+{
+    if (extend_end_node(c2, l) == 0) return 0;
+    if (level_count(c, l) <= 1 || level_count(c2, l) <= 1) return 0;
+    return (c < c2 ? c : c2) >> l;
+}
+VKMR_FOREST_FN uint64_t extend_first_cell(uint64_t o, uint32_t t, uint64_t c, uint64_t c2, uint32_t l) { return pos(o, t, l) + extend_first_node(c, c2, l); }
+VKMR_FOREST_FN uint64_t extend_end_cell(uint64_t o, uint32_t t, uint64_t c2, uint32_t l) { return pos(o, t, l) + extend_end_node(c2, l); }
+
 }  // namespace vkmr_forest

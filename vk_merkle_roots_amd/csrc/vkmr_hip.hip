@@ -19,6 +19,8 @@
 //                                              sibling pairs, CVE-2012-2459) formed beside the hash, and the flag alone from stored levels
 //                       forest_append_*_kernel, forest_truncate_kernel   trees appended into the room a stored forest was built
 //                                              with (the level body again, over the new trees' cells alone), the last trees dropped
+//                       forest_extend_*_kernel   the last tree in use grown or shrunk by leaves: the level body once more, over
+//                                              the nodes of its right edge alone
 //   forest_tree_kernels.hpp  forest_proofs_kernel          proofs gathered from the stored forest, one lane per (query, level)
 //                            verify_forest_proofs_kernel   batch verification of proofs of unequal height, one lane per proof
 //                            forest_update_*_kernel        leaf updates of the stored forest: tree_update_*'s bodies, a tree per entry
@@ -1205,6 +1207,72 @@ vkmr_status vkmr_hip_forest_truncate_async(int dev, vkmr_stream s, uint64_t* off
     if (!offsets_dev || !roots_dev) return refuse(__func__, "null pointer");
     VKMR_TRY(hipSetDevice(dev));
     return launch(forest_truncate_kernel, grid_of(ntrees - keep_trees), dim3(256), S(s), offsets_dev, ntrees, keep_trees, nodes(roots_dev));
+}
+
+// ---- the open tree of a stored forest grown or shrunk by leaves, at its right edge (forest_kernels.hpp) ----------------------
+
+// Both calls behind their own refusals: tree `tree` at offset used - count goes from `count` to `new_count` leaves; `n_new`
+// leaves of leaves_dev are copied behind `used` first unless they lie there already (0 when shrinking).
+static vkmr_status forest_edge(const char* who, int dev, vkmr_stream s, vkmr_digest* digests_dev, vkmr_digest* forest_dev, uint64_t total,
+                               uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count, uint32_t tree, uint64_t count, uint64_t used,
+                               const vkmr_digest* leaves_dev, uint64_t n_new, uint64_t new_count, vkmr_digest* roots_dev, uint64_t* mutated_dev,
+                               uint32_t* status_dev)
+{
+    if (!digests_dev || !forest_dev || !offsets_dev || !roots_dev || !status_dev) return refuse(who, "null pointer");
+    if (tree >= ntrees) return refuse(who, "no such tree");
+    if (count > used || used > total) return refuse(who, "more leaves in use than the forest holds");
+    VKMR_CHECK(forest_args_check(who, total, ntrees, max_count, 0, nullptr, nullptr));
+    if (grid_too_large(groups_of(n_new))) return refuse(who, "too many leaves in one call");
+    const uint32_t H = vkmr_forest::launches(total, max_count);   // the build's, so every level buffer is where the build put it
+    const uint32_t end_tree = tree + 1u, behind = ntrees - tree;
+    const uint64_t o = used - count;
+    Node* digests = nodes(digests_dev);
+    Node* forest = nodes(forest_dev);
+    Node* roots = nodes(roots_dev);
+    unsigned long long* mutated = reinterpret_cast<unsigned long long*>(mutated_dev);
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_TRY(hipMemsetAsync(status_dev, 0, sizeof(uint32_t), S(s)));
+    // a lane per offset from `tree` to ntrees: behind + 1 of them
+    VKMR_CHECK(launch(forest_extend_check_kernel, grid_of((uint64_t)behind + 1), dim3(256), S(s), offsets_dev, ntrees, tree, count, used, status_dev));
+    if (n_new > 0 && leaves_dev != digests_dev + used)   // not yet in place
+        VKMR_CHECK(launch(forest_append_leaves_kernel, grid_of(n_new), dim3(256), S(s), digests, used, nodes(leaves_dev), n_new, status_dev));
+    VKMR_CHECK(launch(forest_extend_offsets_kernel, grid_of(behind), dim3(256), S(s), offsets_dev, ntrees, tree, o + new_count, mutated, status_dev));
+    for (uint32_t l = 1; l <= H; ++l) {   // level l from level l - 1, over the dirty nodes of the open tree's right edge alone
+        const Node* in = (l == 1) ? digests : forest + vkmr_forest::stored_level_base(total, ntrees, l - 1);
+        Node* out = forest + vkmr_forest::stored_level_base(total, ntrees, l);
+        const uint64_t base = vkmr_forest::extend_first_cell(o, tree, count, new_count, l), end = vkmr_forest::extend_end_cell(o, tree, new_count, l);
+        if (end > base)   // empty where the edge ends on a node boundary, and above the new tree's root
+            VKMR_CHECK(launch(forest_extend_level_kernel, grid_of(end - base), dim3(256), S(s), in, offsets_dev, end_tree, l, base, end, out, roots,
+                              status_dev));
+        const uint64_t whole = vkmr_forest::pos(o, tree, l);
+        if (mutated && new_count > 0 && end > whole)   // the mask again from the whole tree: level l - 1 is final behind launch l - 1
+            VKMR_CHECK(launch(forest_extend_scan_kernel, grid_of(end - whole), dim3(256), S(s), in, offsets_dev, end_tree, l, whole, end, mutated,
+                              status_dev));
+    }
+    return VKMR_OK;
+}
+
+vkmr_status vkmr_hip_forest_extend_async(int dev, vkmr_stream s, vkmr_digest* digests_dev, vkmr_digest* forest_dev, uint64_t total,
+                                         uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count, uint32_t tree, uint64_t count, uint64_t used,
+                                         const vkmr_digest* leaves_dev, uint64_t n_leaves, vkmr_digest* roots_dev, uint64_t* mutated_dev,
+                                         uint32_t* status_dev)
+{
+    if (n_leaves == 0) return VKMR_OK;
+    if (!leaves_dev) return refuse(__func__, "null pointer");
+    if (count > max_count || n_leaves > max_count - count) return refuse(__func__, "the tree would pass max_count");
+    if (used > total || n_leaves > total - used) return refuse(__func__, "more leaves than the forest has room for");
+    return forest_edge(__func__, dev, s, digests_dev, forest_dev, total, offsets_dev, ntrees, max_count, tree, count, used, leaves_dev, n_leaves,
+                       count + n_leaves, roots_dev, mutated_dev, status_dev);
+}
+
+vkmr_status vkmr_hip_forest_shrink_async(int dev, vkmr_stream s, vkmr_digest* digests_dev, vkmr_digest* forest_dev, uint64_t total,
+                                         uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count, uint32_t tree, uint64_t count, uint64_t used,
+                                         uint64_t r, vkmr_digest* roots_dev, uint64_t* mutated_dev, uint32_t* status_dev)
+{
+    if (r == 0) return VKMR_OK;
+    if (r > count) return refuse(__func__, "more leaves to drop than the tree has");
+    return forest_edge(__func__, dev, s, digests_dev, forest_dev, total, offsets_dev, ntrees, max_count, tree, count, used, nullptr, 0, count - r,
+                       roots_dev, mutated_dev, status_dev);
 }
 
 // ---- multiproofs inside the stored forest (forest_tree_kernels.hpp) ---------------------------------------------------------

@@ -701,6 +701,22 @@ class HipDevice:
         roots are zero; one launch, no hash."""
         self._call("vkmr_hip_forest_truncate_async", offsets_buf, ntrees, keep_trees, roots_buf, stream=stream)
 
+    def forest_extend_enqueue(self, digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, tree, count, used, leaves_buf, n_leaves, roots_buf,
+                              mutated_buf, status_buf, stream=None):
+        """The open tree `tree` of a stored forest (total, ntrees, max_count: the build's) -- `count` leaves ending at cell
+        `used`, every tree behind it empty -- takes the n_leaves digests of leaves_buf; only its right edge is hashed.
+        leaves_buf at digests_buf.at(32 * used): the leaves are in place.  mutated_buf (ntrees uint64) or None: the open tree's
+        mask formed again.  status_buf: one uint32, forest_append_status_text names its bits; nonzero: nothing changed.  All
+        in device memory.  include/vkmr_hip.h."""
+        self._call("vkmr_hip_forest_extend_async", digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, tree, count, used, leaves_buf,
+                   n_leaves, roots_buf, mutated_buf, status_buf, stream=stream)
+
+    def forest_shrink_enqueue(self, digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, tree, count, used, r, roots_buf, mutated_buf,
+                              status_buf, stream=None):
+        """The open tree drops its last r leaves; the other arguments as forest_extend_enqueue's."""
+        self._call("vkmr_hip_forest_shrink_async", digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, tree, count, used, r, roots_buf,
+                   mutated_buf, status_buf, stream=stream)
+
     def reduce_scratch(self, count, levels_variant=False):
         fn = self.lib.vkmr_hip_reduce_levels_scratch_bytes if levels_variant else self.lib.vkmr_hip_reduce_scratch_bytes
         return self.alloc(fn(count))
@@ -1411,6 +1427,113 @@ class MerkleForest(_Stored):
         place.  Trees cannot be dropped from the front.  ValueError for keep_trees above used_trees."""
         self.truncate_async(keep_trees)
         self.dev.sync()
+
+    # -- the open tree: the last tree in use takes more leaves, or drops its last, at its right edge ------------------------
+    @property
+    def open_tree(self):
+        """The number of the last tree in use, the one extend() and shrink() work on; None when no tree is in use."""
+        return self.used_trees - 1 if self.used_trees else None
+
+    def _open(self, what, more=0, fewer=0):
+        """(the open tree, its count, the leaves in use); ValueError -- before any device call -- when no tree is in use, when
+        `more` leaves do not fit the free cells or take the tree past max_count, or for more than its count to drop."""
+        tree = self.open_tree
+        if tree is None:
+            raise ValueError(f"{what}: no tree in use")
+        count = int(self.counts[tree])
+        if more < 0 or fewer < 0:
+            raise ValueError(f"{what}: a negative number of leaves")
+        if more > self.free_leaves:
+            raise ValueError(f"{what}: {more} leaves, room for {self.free_leaves}")
+        if count + more > self.max_count:
+            raise ValueError(f"{what}: a tree of {count + more} leaves, max_count is {self.max_count}")
+        if fewer > count:
+            raise ValueError(f"{what}: {fewer} leaves to drop, the open tree has {count}")
+        return tree, count, self.used_leaves
+
+    def extend_async(self, leaves_buf, n, status_buf, mutated_buf=None, stream=None):
+        """The open tree takes the n digests of leaves_buf (device memory) behind its last leaf; only the nodes of its right
+        edge are hashed.  leaves_buf at digests.at(32 * used_leaves): they are in place.  status_buf: one uint32, 0 when done
+        (forest_append_status_text names the bits; nonzero: nothing changed); mutated_buf: ntrees uint64 or None, the open
+        tree's mask formed again.  Ordered on `stream`.  Only enqueues: the caller who has seen status 0 tells the handle
+        with extended(n).  ValueError as extend()."""
+        n = int(n)
+        tree, count, used = self._open("extend_async", more=n)
+        self.dev.forest_extend_enqueue(self.digests, self.forest, self.total, self.offsets, self.ntrees, self.max_count, tree, count, used,
+                                       leaves_buf, n, self.roots_buf, mutated_buf, status_buf, stream=stream)
+
+    def extended(self, n):
+        """The host's view after an extend_async that reported status 0: the open tree holds n more leaves."""
+        self.counts[self.open_tree] += np.uint64(n)
+
+    def shrink_async(self, r, status_buf, mutated_buf=None, stream=None):
+        """The open tree drops its last r leaves; status_buf and mutated_buf as extend_async's.  Only enqueues: the caller who
+        has seen status 0 tells the handle with shrunk(r).  ValueError as shrink()."""
+        r = int(r)
+        tree, count, used = self._open("shrink_async", fewer=r)
+        self.dev.forest_shrink_enqueue(self.digests, self.forest, self.total, self.offsets, self.ntrees, self.max_count, tree, count, used, r,
+                                       self.roots_buf, mutated_buf, status_buf, stream=stream)
+
+    def shrunk(self, r):
+        """The host's view after a shrink_async that reported status 0: the open tree holds r leaves fewer."""
+        self.counts[self.open_tree] -= np.uint64(r)
+
+    def _edge(self, tmp, enqueue, done, n, mutated, what):
+        """enqueue(status_buf, mutated_buf) of n leaves with its buffers in the scope `tmp`, waited for, then done(n): the open
+        tree's count, with `mutated` (count, its mask).  RuntimeError when the device refuses what was checked here."""
+        tree = self.open_tree
+        mask = np.uint64(0)
+        if n:
+            d_status, d_mut = tmp.alloc(4), tmp.alloc(8 * self.ntrees) if mutated else None
+            enqueue(d_status, d_mut)
+            status = int(self.dev.download(d_status, 4)[0])
+            if status:
+                raise RuntimeError(f"MerkleForest.{what}: the device refused (status {status}: {forest_append_status_text(status)})")
+            done(n)
+            if mutated:
+                mask = self.dev.download(d_mut, 8, dtype=np.uint64, offset=8 * tree)[0]
+        elif mutated:
+            mask = self.mutated()[tree]
+        count = int(self.counts[tree])
+        return (count, mask) if mutated else count
+
+    def extend(self, digests, mutated=False):
+        """More leaves for the open tree (the last tree in use), into the cells reserved at the build (reserve_leaves):
+        `digests` [n, 8] (a host array) go behind its last leaf and only the nodes of its right edge are hashed, at most
+        (n >> l) + 2 at level l; the forest is afterwards what a build over the new counts gives.  The open tree's count;
+        mutated=True: (count, its mutation mask, what forest_roots_mutated gives for it).  ValueError, before any device call,
+        when no tree is in use, when there is no room for the leaves or the tree would pass max_count."""
+        digests = _host(digests, np.uint32, -1, 8)
+        n = int(digests.shape[0])
+        self._open("extend", more=n)
+        if n == 0 and not mutated:
+            return self._edge(None, None, None, 0, False, "extend")
+        with self.dev.scope() as tmp:
+            d_new = tmp.upload(digests) if n else None
+            return self._edge(tmp, lambda d_status, d_mut: self.extend_async(d_new, n, d_status, d_mut), self.extended, n, mutated, "extend")
+
+    def extend_packed(self, batch):
+        """extend() by the digests of the strings of `batch`: mapped on the device straight into level 0 behind the last leaf,
+        then the tree extended in place; no digest goes through the host.  extend()'s refusals; the open tree's count."""
+        n = int(batch.count)
+        self._open("extend_packed", more=n)
+        if n == 0:
+            return self._edge(None, None, None, 0, False, "extend_packed")
+        with self.dev.scope() as tmp:
+            self.dev.map_packed(tmp, batch, out_buf=self.digests, out_offset_digests=self.used_leaves)
+            place = self.digests.at(32 * self.used_leaves)
+            return self._edge(tmp, lambda d_status, d_mut: self.extend_async(place, n, d_status, d_mut), self.extended, n, False, "extend_packed")
+
+    def shrink(self, r, mutated=False):
+        """The open tree drops its last r leaves: the inverse of extend(); their cells are free again.  Only the nodes of the
+        new right edge are hashed.  The open tree's count (it may reach 0: the tree stays in use, empty); mutated=True:
+        (count, its mask).  ValueError, before any device call, when no tree is in use or r is above the open tree's count."""
+        r = int(r)
+        self._open("shrink", fewer=r)
+        if r == 0 and not mutated:
+            return self._edge(None, None, None, 0, False, "shrink")
+        with self.dev.scope() as tmp:
+            return self._edge(tmp, lambda d_status, d_mut: self.shrink_async(r, d_status, d_mut), self.shrunk, r, mutated, "shrink")
 
     def roots(self):
         """[ntrees, 8] uint32: what forest_roots gives for the same leaves (an all-zero root for an empty tree)."""
