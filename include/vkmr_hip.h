@@ -930,6 +930,74 @@ VKMR_API vkmr_status vkmr_hip_forest_shrink_async(int dev, vkmr_stream s, vkmr_d
                                                   uint64_t* mutated_dev, uint32_t* status_dev);
 
 /*
+ * FRONTIERS: A HOLDER OF THE ROOTS ALONE FOLLOWS TREES THAT GROW.  vkmr_hip_apply_forest_multiproof_async lets a follower keep up
+ * with leaf updates; the calls above let the primary's trees grow.  A follower of a growing tree needs no witness at all: a
+ * duplicate-last tree of c leaves is determined, for every future extension, by its FRONTIER -- the count c and one PEAK per
+ * set bit l of c, node (c >> l) - 1 of level l, the root of a complete subtree of 2^l leaves that no later leaf changes.  A
+ * frontier is `stride` digests per tree (1 <= stride <= 64), cell l for bit l of the count; the cell of a clear bit is never
+ * read and always written as zero, so that two frontiers of equal trees compare byte for byte.  c == 0 is a tree not yet
+ * begun (every cell zero): appending a tree and extending the open tree are the same call.
+ *   counts_dev, peaks_dev      T counts (uint64_t) and T x stride digests in device memory
+ * ROOT OF A FRONTIER.  c == 0: the all-zero root.  Else, with no carry to begin with, for l = 0 .. H(c) - 1,
+ * H(c) = max(1, ceil(log2 c)): where bit l of c is set carry = node_hash(P_l, carry if there is one, else P_l); else where
+ * there is a carry carry = node_hash(carry, carry).  The root is the carry, or P_H(c) when there is none (c a power of two, at
+ * least 2).  A tree of one leaf: node_hash(leaf, leaf), as everywhere in this library.
+ *
+ * vkmr_hip_forest_frontier_async: the frontiers of every tree of a stored forest, as vkmr_hip_forest_proofs_async takes it
+ * (digests_dev, forest_dev, total, offsets_dev, ntrees, max_count: those of the build, trusted in the same way) with its
+ * roots_dev, which holds the peak of a tree whose count is a power of two.  counts_out_dev[t] and the stride cells of
+ * peaks_out_dev behind t * stride are written for every tree; one launch, a lane per cell, no hash.  Refused: a NULL pointer,
+ * what vkmr_hip_forest_proofs_async refuses of the forest, stride outside 1..64, and a stride below the bits of
+ * min(max_count, total) (a tree the build allows would lose a peak).  ntrees == 0 does nothing.
+ *
+ * vkmr_hip_frontier_roots_async: roots_out_dev[q] = the root of frontier q by the rule above, T of them, one launch, a lane
+ * per tree and at most 63 node hashes in it.  A count above 2^58 or of more bits than stride reads no peak and gives the zero
+ * root.  vkmr_hip_verify_frontier_async: the same walk compared with roots_dev[q]: ok_dev[q] (uint32_t) = 1 when equal, else 0
+ * (0 for such a count).  This is how a follower ADOPTS a frontier it is sent under roots it already trusts: a peak or a
+ * count that was changed gives another root.  The roots authenticate the frontier as far as SHA-256d binds a root to its
+ * tree; nothing else is checked.  Refused: a NULL pointer, stride outside 1..64.  T == 0 does nothing.
+ *
+ * vkmr_hip_frontier_extend_async: T frontiers each take new leaves; the new roots and the new frontiers come out.
+ *   leaves_dev, total_new      the new leaves of all trees back to back, in device memory (may be NULL when total_new == 0)
+ *   offsets_dev                T + 1 offsets into them: tree q takes n_q = offsets[q+1] - offsets[q] leaves; in device memory
+ *                              and CHECKED there (below).  n_q == 0: the tree keeps its frontier and still gets its root
+ *   max_new                    the caller's bound on n_q, checked
+ *   scratch_dev                vkmr_hip_frontier_extend_scratch_bytes(total_new, T) bytes, 16-byte aligned: two level buffers of
+ *                              (total_new >> 1) + 2 T digests and 64 T staging cells
+ *   new_counts_dev, new_peaks_dev   T counts and T x stride digests; MAY BE counts_dev and peaks_dev: the frontiers then
+ *                              advance in place.  Cells of clear bits are written as zero
+ *   roots_dev                  T digests: the root of every tree after the call (zero for a tree still without a leaf)
+ *   status_dev                 one uint32_t, always written: 0 when done; bit 0 (1) offsets that decrease, offsets[0] != 0 or
+ *                              offsets[T] != total_new; bit 1 (2) n_q > max_new; bit 2 (4) a new count above 2^58; bit 3 (8) a
+ *                              new count of more bits than stride.  When it is nonzero NOTHING of the caller's is written:
+ *                              no count, no peak, no root (scratch is).
+ * Level l >= 1 forms, of tree q going from c to c2 = c + n_q leaves, the nodes c >> l .. ceil(c2 / 2^l) - 1, at most
+ * (n_q >> l) + 2 of them, from the nodes the level below formed (the new leaves for l == 1) and ONE old value, the peak
+ * P_(l-1) where bit l - 1 of c is set; no other cell of the frontier is read and no stored level exists.  Launches, all on the
+ * caller's stream: the status word zeroed, one check, one launch per level for ALL trees, min(stride, 58) of them (level l:
+ * (total_new >> l) + 2 T lanes), and one commit that writes the counts and the peaks behind the last level; never a launch
+ * per tree, no allocation, no host read of device data.  Refused on the host (VKMR_ERR_INVALID), before any HIP call: a NULL
+ * pointer, stride outside 1..64, total_new above 2^58, scratch off the 16-byte grid, more cells than a launch takes.
+ * T == 0 does nothing.  vkmr_host_cpu_frontier_roots, vkmr_host_cpu_frontier_extend and vkmr_host_cpu_forest_frontier
+ * (libvkmr_host.so) apply the same rules on the CPU, for a follower without a GPU.  Not offered: shrinking a frontier (the
+ * dropped peaks are gone; the primary must send them).
+ */
+VKMR_API vkmr_status vkmr_hip_forest_frontier_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* forest_dev,
+                                                    uint64_t total, const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count,
+                                                    const vkmr_digest* roots_dev, uint32_t stride, uint64_t* counts_out_dev,
+                                                    vkmr_digest* peaks_out_dev);
+VKMR_API vkmr_status vkmr_hip_frontier_roots_async(int dev, vkmr_stream s, const uint64_t* counts_dev, const vkmr_digest* peaks_dev,
+                                                   uint32_t stride, uint32_t T, vkmr_digest* roots_out_dev);
+VKMR_API vkmr_status vkmr_hip_verify_frontier_async(int dev, vkmr_stream s, const uint64_t* counts_dev, const vkmr_digest* peaks_dev,
+                                                    uint32_t stride, uint32_t T, const vkmr_digest* roots_dev, uint32_t* ok_dev);
+VKMR_API size_t vkmr_hip_frontier_extend_scratch_bytes(uint64_t total_new, uint32_t T);
+VKMR_API vkmr_status vkmr_hip_frontier_extend_async(int dev, vkmr_stream s, const uint64_t* counts_dev, const vkmr_digest* peaks_dev,
+                                                    uint32_t stride, uint32_t T, const vkmr_digest* leaves_dev, uint64_t total_new,
+                                                    const uint64_t* offsets_dev, uint64_t max_new, void* scratch_dev,
+                                                    uint64_t* new_counts_dev, vkmr_digest* new_peaks_dev, vkmr_digest* roots_dev,
+                                                    uint32_t* status_dev);
+
+/*
  * COMBINE: duplicate-last Merkle root over n >= 1 slice roots given in slice order, always
  * at least one level -- the rule of CpuSha256D::Root that the reference applies to the slice
  * roots on the CPU (CpuSha256DforReductions, src/vkmr/Reductions.cpp:56-69, :703-712).  Here

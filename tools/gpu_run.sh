@@ -25,6 +25,8 @@
 #                          resident) beside the stored build of the final forest and the roots-only reduction of the new leaves (one JSON line)
 #   forest_extend [args]   tools/forest_extend_timing.py: the open tree of a stored forest grown by leaves (one tree of 2^26; the last of 2^15
 #                          trees) beside truncate + append of the whole tree and the stored build (one JSON line)
+#   frontier_extend [args] tools/frontier_extend_timing.py: a holder of the frontier alone following the same growth, beside the primary's
+#                          extend and the reduction of all the leaves (one JSON line)
 #   cumask                 tools/cu_mask_probe.py: where CU-mask bits land, map/reduce on half the CUs with and without neighbours
 #   issue <set>            tools/issue_patterns (python3 tools/gen_issue_patterns.py <set> and a build beforehand)
 #   proofs                 tools/proof_timing.py: a slice reduced with and without proofs written in the pass
@@ -194,6 +196,11 @@ forest_extend)
   timeout -k 10 500 python3 tools/forest_extend_timing.py "$@" --out $OUT/forest_extend_timing.json > /dev/null 2> $OUT/forest_extend_timing.err && echo "forest_extend_timing ok" &&
   cat $OUT/forest_extend_timing.json
   echo "forest_extend rc=$?"
+  ;;
+frontier_extend)
+  timeout -k 10 500 python3 tools/frontier_extend_timing.py "$@" --out $OUT/frontier_extend_timing.json > /dev/null 2> $OUT/frontier_extend_timing.err && echo "frontier_extend_timing ok" &&
+  cat $OUT/frontier_extend_timing.json
+  echo "frontier_extend rc=$?"
   ;;
 cumask)
   hipcc --offload-arch=gfx950 -O2 -shared -fPIC -o tools/libwhere.so tools/where.hip

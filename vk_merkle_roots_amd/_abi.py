@@ -98,6 +98,13 @@ SIGNATURES = {
                                                C.c_uint64, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vkmr_hip_forest_shrink_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32,
                                                C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vkmr_hip_forest_frontier_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p,
+                                                 C.c_uint32, C.c_void_p, C.c_void_p]),
+    "vkmr_hip_frontier_roots_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "vkmr_hip_verify_frontier_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "vkmr_hip_frontier_extend_scratch_bytes": (C.c_size_t, [C.c_uint64, C.c_uint32]),
+    "vkmr_hip_frontier_extend_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                 C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vkmr_hip_forest_multiproof_max_nodes":(C.c_size_t, [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32]),
     "vkmr_hip_forest_multiproof_scratch_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
     "vkmr_hip_forest_multiproof_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p,
@@ -162,6 +169,10 @@ HOST_SIGNATURES = {
                                                  C.c_void_p, C.c_void_p]),
     "vkmr_host_cpu_apply_forest_multiproof": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32,
                                                         C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "vkmr_host_cpu_frontier_roots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "vkmr_host_cpu_frontier_extend": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vkmr_host_cpu_forest_frontier": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
     "vkmr_host_cpu_forest_find": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "vkmr_host_cpu_tree_find": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "vkmr_host_cpu_forest_sort_entries": (C.c_int, [C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,

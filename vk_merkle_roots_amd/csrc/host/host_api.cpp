@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../audit_plan.hpp"   // forest_plan.hpp, tree_plan.hpp: where the stored levels lie
+#include "../frontier_plan.hpp"
 #include "../merkle_math.hpp"
 #include "cpu_sha256d.hpp"
 #include "vkmr_hip.h"
@@ -699,6 +700,120 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_tree_audit(const vkmr_d
         }
     }
     if (capacity > 0 && info[1] > capacity) info[0] |= 4u;
+    return 0;
+}
+
+// ---- frontiers (frontier_plan.hpp; vkmr_hip_frontier_roots_async, vkmr_hip_frontier_extend_async, vkmr_hip_forest_frontier_async)
+// for a follower without a GPU.  The extension here is NOT the device's level rule: a leaf at a time, the carry chain of a
+// binary counter (the node climbs while the count's bit is set, merging with the peak it meets), so the two check each other.
+
+// The root of one frontier by the rule of vkmr_hip_frontier_roots_async; `peaks` are its stride cells, c fits them.
+static void frontier_root(uint64_t c, const vkmr_digest* peaks, vkmr_digest* root)
+{
+    std::memset(root->data, 0, 32);
+    if (c == 0) return;
+    const uint32_t H = vkmr_math::height(c);
+    bool have = false;
+    vkmr_digest carry;
+    for (uint32_t l = 0; l < H; ++l) {
+        if (vkmr_frontier::has_peak(c, l)) {
+            vkmr_digest next;
+            vkmr::cpu_sha256d_pair(peaks[l].data, have ? carry.data : peaks[l].data, next.data);
+            carry = next;
+            have = true;
+        } else if (have) {
+            vkmr_digest next;
+            vkmr::cpu_sha256d_pair(carry.data, carry.data, next.data);
+            carry = next;
+        }
+    }
+    *root = have ? carry : peaks[H];
+}
+
+// One more leaf for the frontier (c, peaks[0 .. 64)): c + 1 and its peaks; cells of bits that clear are zeroed.
+static void frontier_push(uint64_t& c, vkmr_digest* peaks, const vkmr_digest& leaf)
+{
+    vkmr_digest node = leaf;
+    uint32_t l = 0;
+    for (; vkmr_frontier::has_peak(c, l); ++l) {
+        vkmr_digest next;
+        vkmr::cpu_sha256d_pair(peaks[l].data, node.data, next.data);
+        node = next;
+        std::memset(peaks[l].data, 0, 32);
+    }
+    peaks[l] = node;
+    ++c;
+}
+
+// roots[q] = the root of frontier q (counts[q], the stride cells behind peaks + q * stride), T of them.  A count above 2^58 or
+// of more bits than stride gives the zero root and makes the call return 1; -1 for a missing pointer or a stride outside 1..64.
+__attribute__((visibility("default"))) int vkmr_host_cpu_frontier_roots(const uint64_t* counts, const vkmr_digest* peaks, uint32_t stride, uint32_t T,
+                                                                         vkmr_digest* roots)
+{
+    if (T == 0) return 0;
+    if (!counts || !peaks || !roots || stride == 0 || stride > VKMR_FRONTIER_MAX_STRIDE) return -1;
+    int rc = 0;
+    for (uint32_t q = 0; q < T; ++q) {
+        if (counts[q] > vkmr_frontier::max_count() || vkmr_frontier::bit_length(counts[q]) > stride) {
+            std::memset(roots[q].data, 0, 32);
+            rc = 1;
+            continue;
+        }
+        frontier_root(counts[q], peaks + (size_t)q * stride, &roots[q]);
+    }
+    return rc;
+}
+
+// T frontiers each take leaves[offsets[q] .. offsets[q+1]): the new counts, the new peaks (cells of clear bits zero) and the
+// roots, by the contract of vkmr_hip_frontier_extend_async; new_counts / new_peaks may be counts / peaks.  Returns the status
+// word of that call (0: done; nonzero: nothing written), or -1 for a missing pointer or a stride outside 1..64.
+__attribute__((visibility("default"))) int vkmr_host_cpu_frontier_extend(const uint64_t* counts, const vkmr_digest* peaks, uint32_t stride, uint32_t T,
+                                                                          const vkmr_digest* leaves, uint64_t total_new, const uint64_t* offsets,
+                                                                          uint64_t max_new, uint64_t* new_counts, vkmr_digest* new_peaks,
+                                                                          vkmr_digest* roots)
+{
+    if (T == 0) return 0;
+    if (!counts || !peaks || (!leaves && total_new > 0) || !offsets || !new_counts || !new_peaks || !roots) return -1;
+    if (stride == 0 || stride > VKMR_FRONTIER_MAX_STRIDE) return -1;
+    uint32_t status = 0;
+    for (uint32_t q = 0; q < T; ++q) status |= vkmr_frontier::refusal(counts[q], offsets[q], offsets[q + 1], q, T, total_new, max_new, stride);
+    if (status) return (int)status;
+    for (uint32_t q = 0; q < T; ++q) {
+        vkmr_digest mine[VKMR_FRONTIER_MAX_STRIDE + 1];
+        std::memset(mine, 0, sizeof mine);
+        uint64_t c = counts[q];
+        for (uint32_t l = 0; l < stride; ++l)
+            if (vkmr_frontier::has_peak(c, l)) mine[l] = peaks[(size_t)q * stride + l];
+        for (uint64_t i = offsets[q]; i < offsets[q + 1]; ++i) frontier_push(c, mine, leaves[i]);
+        new_counts[q] = c;
+        std::memcpy(new_peaks + (size_t)q * stride, mine, sizeof(vkmr_digest) * stride);
+        frontier_root(c, mine, &roots[q]);
+    }
+    return 0;
+}
+
+// The frontiers of the trees of a forest from its leaves: tree t is digests[offsets[t] .. offsets[t+1]).  What
+// vkmr_hip_forest_frontier_async reads out of a stored forest.  1, and nothing written, when the offsets decrease or a tree has
+// more leaves than 2^58 or than stride bits hold; -1 for a missing pointer or a stride outside 1..64.
+__attribute__((visibility("default"))) int vkmr_host_cpu_forest_frontier(const vkmr_digest* digests, const uint64_t* offsets, uint32_t ntrees,
+                                                                          uint32_t stride, uint64_t* counts_out, vkmr_digest* peaks_out)
+{
+    if (ntrees == 0) return 0;
+    if (!offsets || !counts_out || !peaks_out || stride == 0 || stride > VKMR_FRONTIER_MAX_STRIDE) return -1;
+    for (uint32_t t = 0; t < ntrees; ++t) {
+        if (offsets[t + 1] < offsets[t]) return 1;
+        const uint64_t c = offsets[t + 1] - offsets[t];
+        if (c > vkmr_frontier::max_count() || vkmr_frontier::bit_length(c) > stride) return 1;
+    }
+    if (!digests && offsets[ntrees] > offsets[0]) return -1;
+    for (uint32_t t = 0; t < ntrees; ++t) {
+        vkmr_digest mine[VKMR_FRONTIER_MAX_STRIDE + 1];
+        std::memset(mine, 0, sizeof mine);
+        uint64_t c = 0;
+        for (uint64_t i = offsets[t]; i < offsets[t + 1]; ++i) frontier_push(c, mine, digests[i]);
+        counts_out[t] = c;
+        std::memcpy(peaks_out + (size_t)t * stride, mine, sizeof(vkmr_digest) * stride);
+    }
     return 0;
 }
 

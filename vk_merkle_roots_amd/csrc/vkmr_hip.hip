@@ -21,6 +21,9 @@
 //                                              with (the level body again, over the new trees' cells alone), the last trees dropped
 //                       forest_extend_*_kernel   the last tree in use grown or shrunk by leaves: the level body once more, over
 //                                              the nodes of its right edge alone
+//   frontier_kernels.hpp  frontier_*_kernel     trees followed by their frontiers alone (a count and one peak per set bit): the
+//                                              new roots and frontiers from the new leaves, the root of a frontier, the frontier
+//                                              of a stored tree
 //   forest_tree_kernels.hpp  forest_proofs_kernel          proofs gathered from the stored forest, one lane per (query, level)
 //                            verify_forest_proofs_kernel   batch verification of proofs of unequal height, one lane per proof
 //                            forest_update_*_kernel        leaf updates of the stored forest: tree_update_*'s bodies, a tree per entry
@@ -85,6 +88,7 @@ using vkmr_dev::Node;
 #include "sort_kernels.hpp"
 #include "diff_kernels.hpp"
 #include "audit_kernels.hpp"
+#include "frontier_kernels.hpp"
 
 // ============================================================================
 // C ABI
@@ -1273,6 +1277,92 @@ vkmr_status vkmr_hip_forest_shrink_async(int dev, vkmr_stream s, vkmr_digest* di
     if (r > count) return refuse(__func__, "more leaves to drop than the tree has");
     return forest_edge(__func__, dev, s, digests_dev, forest_dev, total, offsets_dev, ntrees, max_count, tree, count, used, nullptr, 0, count - r,
                        roots_dev, mutated_dev, status_dev);
+}
+
+// ---- trees followed by their frontiers alone (frontier_kernels.hpp, frontier_plan.hpp) ----------------------------------------
+
+static vkmr_status frontier_args_check(const char* who, uint32_t stride, uint32_t T)
+{
+    if (stride == 0 || stride > VKMR_FRONTIER_MAX_STRIDE) return refuse(who, "stride must be 1..64");
+    if (grid_too_large(groups_of((uint64_t)T * VKMR_FRONTIER_MAX_STRIDE))) return refuse(who, "too many trees in one call");
+    return VKMR_OK;
+}
+
+vkmr_status vkmr_hip_forest_frontier_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* forest_dev, uint64_t total,
+                                           const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count, const vkmr_digest* roots_dev,
+                                           uint32_t stride, uint64_t* counts_out_dev, vkmr_digest* peaks_out_dev)
+{
+    if (ntrees == 0) return VKMR_OK;
+    if ((!digests_dev && total > 0) || !forest_dev || !offsets_dev || !roots_dev || !counts_out_dev || !peaks_out_dev)
+        return refuse(__func__, "null pointer");
+    VKMR_CHECK(forest_args_check(__func__, total, ntrees, max_count, 0, nullptr, nullptr));
+    VKMR_CHECK(frontier_args_check(__func__, stride, ntrees));
+    if (vkmr_frontier::bit_length(max_count < total ? max_count : total) > stride) return refuse(__func__, "a tree of max_count leaves has more peaks than stride");
+    const ForestLevels lv = forest_levels(total, ntrees, vkmr_forest::launches(total, max_count));
+    VKMR_TRY(hipSetDevice(dev));
+    return launch(frontier_gather_kernel, grid_of((uint64_t)ntrees * stride), dim3(256), S(s), nodes(digests_dev), nodes(forest_dev), lv, offsets_dev, ntrees,
+                  nodes(roots_dev), stride, counts_out_dev, nodes(peaks_out_dev));
+}
+
+// Both forms of the root walk: the roots written, or compared with `want_dev` into ok_dev.
+static vkmr_status frontier_roots(const char* who, int dev, vkmr_stream s, const uint64_t* counts_dev, const vkmr_digest* peaks_dev, uint32_t stride,
+                                  uint32_t T, vkmr_digest* roots_out_dev, const vkmr_digest* want_dev, uint32_t* ok_dev)
+{
+    if (T == 0) return VKMR_OK;
+    if (!counts_dev || !peaks_dev || (!roots_out_dev && !want_dev) || (want_dev && !ok_dev)) return refuse(who, "null pointer");
+    VKMR_CHECK(frontier_args_check(who, stride, T));
+    VKMR_TRY(hipSetDevice(dev));
+    return launch(frontier_roots_kernel, grid_of(T), dim3(256), S(s), counts_dev, nodes(peaks_dev), stride, T, nodes(roots_out_dev), nodes(want_dev), ok_dev);
+}
+
+vkmr_status vkmr_hip_frontier_roots_async(int dev, vkmr_stream s, const uint64_t* counts_dev, const vkmr_digest* peaks_dev, uint32_t stride, uint32_t T,
+                                          vkmr_digest* roots_out_dev)
+{
+    if (T != 0 && !roots_out_dev) return refuse(__func__, "null pointer");
+    return frontier_roots(__func__, dev, s, counts_dev, peaks_dev, stride, T, roots_out_dev, nullptr, nullptr);
+}
+
+vkmr_status vkmr_hip_verify_frontier_async(int dev, vkmr_stream s, const uint64_t* counts_dev, const vkmr_digest* peaks_dev, uint32_t stride, uint32_t T,
+                                           const vkmr_digest* roots_dev, uint32_t* ok_dev)
+{
+    if (T != 0 && (!roots_dev || !ok_dev)) return refuse(__func__, "null pointer");
+    return frontier_roots(__func__, dev, s, counts_dev, peaks_dev, stride, T, nullptr, roots_dev, ok_dev);
+}
+
+size_t vkmr_hip_frontier_extend_scratch_bytes(uint64_t total_new, uint32_t T)
+{
+    if (total_new > vkmr_frontier::max_count()) return 0;
+    return (size_t)vkmr_frontier::scratch_cells(total_new, T) * sizeof(vkmr_digest);
+}
+
+vkmr_status vkmr_hip_frontier_extend_async(int dev, vkmr_stream s, const uint64_t* counts_dev, const vkmr_digest* peaks_dev, uint32_t stride, uint32_t T,
+                                           const vkmr_digest* leaves_dev, uint64_t total_new, const uint64_t* offsets_dev, uint64_t max_new,
+                                           void* scratch_dev, uint64_t* new_counts_dev, vkmr_digest* new_peaks_dev, vkmr_digest* roots_dev,
+                                           uint32_t* status_dev)
+{
+    if (T == 0) return VKMR_OK;
+    if (!counts_dev || !peaks_dev || (!leaves_dev && total_new > 0) || !offsets_dev || !scratch_dev || !new_counts_dev || !new_peaks_dev || !roots_dev ||
+        !status_dev)
+        return refuse(__func__, "null pointer");
+    VKMR_CHECK(frontier_args_check(__func__, stride, T));
+    if (total_new > vkmr_frontier::max_count()) return refuse(__func__, "too many leaves in one call");
+    if (reinterpret_cast<uintptr_t>(scratch_dev) & 15u) return refuse(__func__, "scratch must be 16-byte aligned");
+    if (grid_too_large(groups_of(vkmr_frontier::level_cells(total_new, T, 1)))) return refuse(__func__, "too many leaves in one call");
+    Node* scratch = nodes(scratch_dev);
+    Node* staging = scratch + vkmr_frontier::staging_base(total_new, T);
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_TRY(hipMemsetAsync(status_dev, 0, sizeof(uint32_t), S(s)));
+    VKMR_CHECK(launch(frontier_check_kernel, grid_of(T), dim3(256), S(s), counts_dev, offsets_dev, T, total_new, max_new, stride, status_dev));
+    const uint32_t H = vkmr_frontier::launches(stride);
+    for (uint32_t l = 1; l <= H; ++l) {   // level l of every tree's extension from level l - 1: one launch for all trees
+        const Node* in = (l == 1) ? nodes(leaves_dev) : scratch + vkmr_frontier::level_base(total_new, T, l - 1);
+        const uint64_t cells = vkmr_frontier::level_cells(total_new, T, l);
+        VKMR_CHECK(launch(frontier_level_kernel, grid_of(cells), dim3(256), S(s), in, counts_dev, nodes(peaks_dev), stride, offsets_dev, T, l, cells,
+                          scratch + vkmr_frontier::level_base(total_new, T, l), staging, nodes(roots_dev), status_dev));
+    }
+    // a wavefront per tree: four trees a workgroup
+    return launch(frontier_commit_kernel, dim3((uint32_t)(((uint64_t)T + 3) / 4)), dim3(256), S(s), counts_dev, nodes(peaks_dev), stride, offsets_dev, T,
+                  nodes(leaves_dev), staging, new_counts_dev, nodes(new_peaks_dev), nodes(roots_dev), status_dev);
 }
 
 // ---- multiproofs inside the stored forest (forest_tree_kernels.hpp) ---------------------------------------------------------

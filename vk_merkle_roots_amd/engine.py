@@ -717,6 +717,34 @@ class HipDevice:
         self._call("vkmr_hip_forest_shrink_async", digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, tree, count, used, r, roots_buf,
                    mutated_buf, status_buf, stream=stream)
 
+    def forest_frontier_enqueue(self, digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, roots_buf, stride, counts_out_buf, peaks_out_buf,
+                                stream=None):
+        """The frontier of every tree of a stored forest (total, ntrees, max_count: the build's; roots_buf its roots): ntrees
+        uint64 counts and ntrees x stride digests, cell l of a tree the peak of bit l of its count, zero for a clear bit.  All
+        in device memory.  include/vkmr_hip.h."""
+        self._call("vkmr_hip_forest_frontier_async", digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, roots_buf, stride, counts_out_buf,
+                   peaks_out_buf, stream=stream)
+
+    def frontier_roots_enqueue(self, counts_buf, peaks_buf, stride, T, roots_out_buf, stream=None):
+        """roots_out_buf[q] = the root of frontier q (counts_buf[q], the stride cells of peaks_buf behind q * stride)."""
+        self._call("vkmr_hip_frontier_roots_async", counts_buf, peaks_buf, stride, T, roots_out_buf, stream=stream)
+
+    def verify_frontier_enqueue(self, counts_buf, peaks_buf, stride, T, roots_buf, ok_buf, stream=None):
+        """ok_buf[q] (uint32) = 1 when frontier q has the root roots_buf[q], else 0."""
+        self._call("vkmr_hip_verify_frontier_async", counts_buf, peaks_buf, stride, T, roots_buf, ok_buf, stream=stream)
+
+    def frontier_extend_enqueue(self, counts_buf, peaks_buf, stride, T, leaves_buf, total_new, offsets_buf, max_new, scratch_buf, new_counts_buf,
+                                new_peaks_buf, roots_buf, status_buf, stream=None):
+        """T frontiers take the total_new digests of leaves_buf, tree q those from offsets_buf[q] to offsets_buf[q + 1] (T + 1
+        uint64 from 0 to total_new, none more than max_new apart): the new counts and peaks (they may be the old buffers) and
+        the T roots.  scratch_buf: frontier_extend_scratch(total_new, T).  status_buf: one uint32, frontier_status_text names
+        its bits; nonzero: nothing written.  All in device memory.  include/vkmr_hip.h."""
+        self._call("vkmr_hip_frontier_extend_async", counts_buf, peaks_buf, stride, T, leaves_buf, total_new, offsets_buf, max_new, scratch_buf,
+                   new_counts_buf, new_peaks_buf, roots_buf, status_buf, stream=stream)
+
+    def frontier_extend_scratch(self, total_new, T):
+        return self.alloc(self.lib.vkmr_hip_frontier_extend_scratch_bytes(total_new, T))
+
     def reduce_scratch(self, count, levels_variant=False):
         fn = self.lib.vkmr_hip_reduce_levels_scratch_bytes if levels_variant else self.lib.vkmr_hip_reduce_scratch_bytes
         return self.alloc(fn(count))
@@ -1535,6 +1563,21 @@ class MerkleForest(_Stored):
         with self.dev.scope() as tmp:
             return self._edge(tmp, lambda d_status, d_mut: self.shrink_async(r, d_status, d_mut), self.shrunk, r, mutated, "shrink")
 
+    def frontier(self, stride=None):
+        """The Frontier of every tree as it is now, read out of the stored levels (no hash): what a follower adopts
+        (Frontier.verify under the roots it trusts) and then advances by Frontier.extend with the leaves the primary appends
+        or extends by.  stride: cells per tree, by default the bits of min(max_count, total), the least that holds every
+        tree the forest allows."""
+        stride = max(1, min(self.max_count, self.total).bit_length()) if stride is None else int(stride)
+        if self.ntrees == 0:
+            return Frontier.empty(0, stride)
+        with self.dev.scope() as tmp:
+            d_counts, d_peaks = tmp.alloc(8 * self.ntrees), tmp.alloc(32 * self.ntrees * stride)
+            self.dev.forest_frontier_enqueue(self.digests, self.forest, self.total, self.offsets, self.ntrees, self.max_count, self.roots_buf, stride,
+                                             d_counts, d_peaks)
+            return Frontier(self.dev.download(d_counts, 8 * self.ntrees, dtype=np.uint64),
+                            self.dev.download(d_peaks, 32 * self.ntrees * stride).reshape(self.ntrees, stride, 8))
+
     def roots(self):
         """[ntrees, 8] uint32: what forest_roots gives for the same leaves (an all-zero root for an empty tree)."""
         return self.dev.download(self.roots_buf, 32 * self.ntrees).reshape(self.ntrees, 8)
@@ -1762,6 +1805,118 @@ def forest_update_status_text(status):
     if status & 2:
         names.append("bit 1: the (tree, index) pairs are not strictly increasing")
     if status & ~3:
+        names.append("unknown bits")
+    return "; ".join(names) if names else "ok"
+
+
+class Frontier:
+    """What a holder of the roots alone keeps of T trees that grow: `counts` (uint64 [T]) and `peaks` (uint32 [T, stride, 8]),
+    cell l of a tree the root of the complete subtree of 2^l leaves that ends at its last leaf, for every set bit l of its
+    count, zero for a clear bit (include/vkmr_hip.h).  Host arrays; every method is one ABI call on `dev` around them.  The
+    roots and every later frontier follow from it and the leaves that arrive: no stored level, no witness."""
+
+    MAX_COUNT = 1 << 58
+
+    def __init__(self, counts, peaks):
+        self.counts = np.array(counts, dtype=np.uint64).reshape(-1)
+        T = int(self.counts.shape[0])
+        peaks = np.array(peaks, dtype=np.uint32)
+        self.peaks = peaks if peaks.ndim == 3 else peaks.reshape(T, -1, 8)
+        if self.peaks.shape[0] != T or self.peaks.shape[2] != 8 or not 1 <= self.stride <= 64:
+            raise ValueError("Frontier: peaks must be [T, stride, 8] with stride in 1..64")
+
+    T = property(lambda self: int(self.counts.shape[0]))
+    stride = property(lambda self: int(self.peaks.shape[1]))
+
+    @classmethod
+    def empty(cls, T, stride=64):
+        """T trees not yet begun."""
+        return cls(np.zeros(int(T), np.uint64), np.zeros((int(T), int(stride), 8), np.uint32))
+
+    def same_as(self, other):
+        """Byte for byte: equal counts and equal cells, the zero ones included."""
+        return (self.counts.shape == other.counts.shape and self.peaks.shape == other.peaks.shape and bool((self.counts == other.counts).all())
+                and bool((self.peaks == other.peaks).all()))
+
+    def _walk(self, dev, want):
+        """The root walk over the frontiers on `dev`: the roots [T, 8], or with `want` (roots [T, 8]) the answers uint32 [T]."""
+        T = self.T
+        if T == 0:
+            return np.zeros((0, 8), np.uint32) if want is None else np.zeros(0, np.uint32)
+        with dev.scope() as tmp:
+            d_counts, d_peaks = tmp.upload(self.counts), tmp.upload(self.peaks)
+            if want is None:
+                d_roots = tmp.alloc(32 * T)
+                dev.frontier_roots_enqueue(d_counts, d_peaks, self.stride, T, d_roots)
+                return dev.download(d_roots, 32 * T).reshape(T, 8)
+            d_ok = tmp.alloc(4 * T)
+            dev.verify_frontier_enqueue(d_counts, d_peaks, self.stride, T, tmp.upload(_host(want, np.uint32, T, 8)), d_ok)
+            return dev.download(d_ok, 4 * T)
+
+    def roots(self, dev):
+        """[T, 8] uint32: the root of every tree (all zero for one not yet begun)."""
+        return self._walk(dev, None)
+
+    def verify(self, dev, roots):
+        """uint32 [T]: 1 where the frontier has the root roots[q], else 0 -- how a frontier that was sent is adopted under
+        roots already trusted."""
+        return self._walk(dev, roots)
+
+    def _new_offsets(self, counts, n, what):
+        """The offsets of the new leaves (uint64 [T + 1]); ValueError, before any device call, when the counts are not one per
+        tree, do not add up to the n leaves, or take a tree past 2^58 leaves or past the bits a frontier of this stride holds."""
+        offsets, m = _checked_offsets(counts, n, what)
+        if m != self.T:
+            raise ValueError(f"{what}: {m} counts for {self.T} trees")
+        after = [int(c) + int(k) for c, k in zip(self.counts, np.diff(offsets))]
+        if any(c > self.MAX_COUNT or c.bit_length() > self.stride for c in after):
+            raise ValueError(f"{what}: a tree of {max(after)} leaves does not fit a frontier of stride {self.stride}")
+        return offsets
+
+    def _extend(self, dev, tmp, leaves_buf, offsets, what):
+        """The one extend: the leaves in device memory, the frontier up and back, in place on the device.  The new roots."""
+        T, n = self.T, int(offsets[-1])
+        if T == 0:
+            return np.zeros((0, 8), np.uint32)
+        d_counts, d_peaks, d_roots, d_status = tmp.upload(self.counts), tmp.upload(self.peaks), tmp.alloc(32 * T), tmp.alloc(4)
+        scratch = tmp.keep(dev.frontier_extend_scratch(n, T))
+        dev.frontier_extend_enqueue(d_counts, d_peaks, self.stride, T, leaves_buf, n, tmp.upload(offsets), int(np.diff(offsets).max()), scratch,
+                                    d_counts, d_peaks, d_roots, d_status)
+        status = int(dev.download(d_status, 4)[0])
+        if status:
+            raise RuntimeError(f"Frontier.{what}: the device refused (status {status}: {frontier_status_text(status)})")
+        self.counts = dev.download(d_counts, 8 * T, dtype=np.uint64)
+        self.peaks = dev.download(d_peaks, 32 * T * self.stride).reshape(T, self.stride, 8)
+        return dev.download(d_roots, 32 * T).reshape(T, 8)
+
+    def extend(self, dev, digests, counts):
+        """Tree q takes the next counts[q] rows of `digests` [n, 8] (a host array; 0 for a tree that takes none): the frontier
+        advances and the new roots [T, 8] are returned -- what the primary's trees have after the same leaves.  ValueError
+        as _new_offsets says."""
+        digests = _host(digests, np.uint32, -1, 8)
+        offsets = self._new_offsets(counts, int(digests.shape[0]), "extend")
+        with dev.scope() as tmp:
+            return self._extend(dev, tmp, tmp.upload(digests) if digests.shape[0] else None, offsets, "extend")
+
+    def extend_packed(self, dev, batch, counts):
+        """extend() by the digests of the strings of `batch`, mapped on the device; no digest goes through the host."""
+        offsets = self._new_offsets(counts, int(batch.count), "extend_packed")
+        with dev.scope() as tmp:
+            return self._extend(dev, tmp, dev.map_packed(tmp, batch) if batch.count else None, offsets, "extend_packed")
+
+
+def frontier_status_text(status):
+    """The bits of vkmr_hip_frontier_extend_async's status word, named."""
+    names = []
+    if status & 1:
+        names.append("bit 0: the offsets decrease, do not start at 0 or do not end at the new leaves")
+    if status & 2:
+        names.append("bit 1: a tree takes more than max_new leaves")
+    if status & 4:
+        names.append("bit 2: a tree would hold more than 2^58 leaves")
+    if status & 8:
+        names.append("bit 3: a new count has more bits than the frontier has cells")
+    if status & ~15:
         names.append("unknown bits")
     return "; ".join(names) if names else "ok"
 
