@@ -884,6 +884,66 @@ VKMR_API vkmr_status vkmr_hip_forest_append_async(int dev, vkmr_stream s, vkmr_d
  */
 VKMR_API vkmr_status vkmr_hip_forest_truncate_async(int dev, vkmr_stream s, uint64_t* offsets_dev, uint32_t ntrees,
                                                     uint32_t keep_trees, vkmr_digest* roots_dev);
+/*
+ * The same at the other end, for a window that loses its oldest trees: for t < drop_trees, offsets[t] = offsets[drop_trees],
+ * roots_dev[t] all zero and, with mutated_dev (the ntrees masks, or NULL), mutated_dev[t] = 0 -- one launch, one lane per
+ * dropped tree, no hash; offsets[drop_trees] is read and never written.  Trees 0 .. drop_trees - 1 are then empty trees at the
+ * offset where tree drop_trees begins: pos_l stays strictly increasing (neighbouring dropped trees are one cell apart), every
+ * tree from drop_trees on keeps its offset and its NUMBER and so every cell of its own, and the forest is what a build over the
+ * new offsets writes (offsets[0] > 0 is a forest every call above takes), in every cell such a build writes.  The leaves and
+ * level cells in front belong to no tree any more; offsets do not decrease, so they cannot be used again in place --
+ * vkmr_hip_forest_copy_trees_async into another forest reclaims them.  drop_trees == 0 does nothing; drop_trees > ntrees, or a
+ * NULL offsets_dev or roots_dev with drop_trees > 0, is refused on the host before any HIP call.  Stream-ordered.
+ */
+VKMR_API vkmr_status vkmr_hip_forest_drop_front_async(int dev, vkmr_stream s, uint64_t* offsets_dev, uint32_t ntrees,
+                                                      uint32_t drop_trees, vkmr_digest* roots_dev, uint64_t* mutated_dev);
+
+/*
+ * STORED TREES COPIED INTO ANOTHER FOREST: repack a forest whose reserve is used up or whose front was dropped, delete trees from
+ * the middle, merge two forests, split one -- without hashing.  A stored tree at another offset, under another number or in
+ * another forest has the same nodes; only their cells differ, and differently per level, because (offset >> l) does not commute
+ * with a shift of the offset.  So the call is vkmr_hip_forest_append_async with "hash the two children" replaced by "copy the
+ * node": 32 bytes read and 32 written per cell.
+ *   src_*                      a stored forest (vkmr_hip_reduce_forest_tree_async, grown or not), TRUSTED as every reader trusts
+ *                              it: src_digests_dev its leaves, src_forest_dev its levels, src_total / src_ntrees / src_max_count
+ *                              its capacity, src_offsets_dev its src_ntrees + 1 offsets, src_roots_dev its roots;
+ *                              src_mutated_dev NULL or its src_ntrees masks
+ *   sel_dev                    m uint32_t in device memory: destination tree first_tree + j becomes source tree sel[j]; any
+ *                              order, repeats and empty trees allowed
+ *   n_leaves, new_offsets_dev  as append's (m + 1 uint64_t relative to `used`, from 0 to n_leaves): host values and their
+ *                              prefix sums, which the host forms from the counts it knows; checked on the device against the
+ *                              source's own offsets
+ *   dst_*, first_tree, used    append's arguments: the destination's leaves, levels, capacity, offsets and roots; trees
+ *                              first_tree .. dst_ntrees - 1 are empty at `used`.  dst_mutated_dev NULL or its dst_ntrees masks:
+ *                              those of the m new trees are copied from src_mutated_dev, or zeroed when that is NULL
+ *   status_dev                 one uint32_t in device memory, always written: 0 when the trees were copied; append's bits --
+ *                              bit 0: the new offsets decrease, do not start at 0 or do not end at n_leaves; bit 1: a count
+ *                              above dst_max_count; bit 2 (value 4): some dst offsets[t] != used for first_tree <= t <=
+ *                              dst_ntrees -- and bit 3 (value 8): some sel[j] >= src_ntrees, or new count j is not the count of
+ *                              source tree sel[j].  An unchecked sel[j] is never followed into the source's offsets.  When it
+ *                              is nonzero NOTHING of the destination has changed.
+ * After status 0 every cell of the destination's leaves, dst_forest_dev, dst_roots_dev and dst_offsets_dev that a fresh
+ * vkmr_hip_reduce_forest_tree_async over the resulting offsets writes holds what that build writes, and no other cell is
+ * written (a tree's last level is kept in the roots alone, here as there).  Launches, all on the caller's stream: the status
+ * word zeroed, one check, the offsets (append's own kernel, which zeroes the new trees' masks too), then one launch per level
+ * l = 0 .. H_d = max(1, ceil(log2 min(dst_max_count, dst_total))), level 0 being the leaves, each over the cells
+ * [pos_l(used, first_tree), pos_l(used + n_leaves, first_tree + m)) alone, one lane per destination cell; no launch per tree, no
+ * allocation, no host read of device data, no hash.  Refused on the host (VKMR_ERR_INVALID) with m > 0, before any HIP call: a
+ * NULL pointer (the two mask arrays may be NULL, the two leaves buffers when n_leaves == 0), first_tree + m > dst_ntrees,
+ * used + n_leaves > dst_total, either max_count == 0, either total > 2^58, and dst_digests_dev == src_digests_dev, dst_forest_dev == src_forest_dev, dst_offsets_dev ==
+ * src_offsets_dev or dst_roots_dev == src_roots_dev: a copy inside one forest is not offered.  Buffers that overlap in part
+ * are the caller's business: the call does not look for them, and the result is then undefined.  m == 0 does nothing whatever
+ * the other arguments.  Stream-ordered: a proof gather enqueued after it on the same stream sees the copied trees.
+ */
+VKMR_API vkmr_status vkmr_hip_forest_copy_trees_async(int dev, vkmr_stream s, const vkmr_digest* src_digests_dev,
+                                                      const vkmr_digest* src_forest_dev, uint64_t src_total,
+                                                      const uint64_t* src_offsets_dev, uint32_t src_ntrees, uint64_t src_max_count,
+                                                      const vkmr_digest* src_roots_dev, const uint64_t* src_mutated_dev,
+                                                      const uint32_t* sel_dev, uint32_t m, uint64_t n_leaves,
+                                                      const uint64_t* new_offsets_dev, vkmr_digest* dst_digests_dev,
+                                                      vkmr_digest* dst_forest_dev, uint64_t dst_total, uint64_t* dst_offsets_dev,
+                                                      uint32_t dst_ntrees, uint64_t dst_max_count, uint32_t first_tree, uint64_t used,
+                                                      vkmr_digest* dst_roots_dev, uint64_t* dst_mutated_dev, uint32_t* status_dev);
 
 /*
  * THE OPEN TREE GROWS OR SHRINKS BY LEAVES, at its right edge: a block still collecting transactions, the newest file of an

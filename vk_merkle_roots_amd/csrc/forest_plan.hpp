@@ -139,4 +139,69 @@ VKMR_FOREST_FN uint64_t extend_first_node(uint64_t c, uint64_t c2, uint32_t l)
 VKMR_FOREST_FN uint64_t extend_first_cell(uint64_t o, uint32_t t, uint64_t c, uint64_t c2, uint32_t l) { return pos(o, t, l) + extend_first_node(c, c2, l); }
 VKMR_FOREST_FN uint64_t extend_end_cell(uint64_t o, uint32_t t, uint64_t c2, uint32_t l) { return pos(o, t, l) + extend_end_node(c2, l); }
 
+// ---- dropping the oldest trees (vkmr_hip_forest_drop_front_async): after dropping k trees, offsets[t] = offsets[k] for every
+// t < k.  Trees 0 .. k - 1 are then empty trees at the offset where tree k begins, and nothing else changes:
+//   - pos_l stays strictly increasing: for t + 1 < k, pos_l(t + 1) - pos_l(t) = (offsets[k] >> l) - (offsets[k] >> l) + 1 = 1; for
+//     t + 1 == k it is 1 as well, tree k keeping its offset; from tree k on both terms are the old ones.
+//   - no cell of a tree >= k moves: pos_l(t) is a function of offsets[t] and t alone, and neither changes for t >= k.
+// The cells in front of offsets[k] belong to no tree afterwards and cannot be used again in place (offsets are monotone):
+// copying the trees that remain into another forest (below) is what reclaims them.
+VKMR_FOREST_FN uint64_t drop_front_offset(uint64_t offset_t, uint64_t offset_k, uint32_t t, uint32_t k) { return t < k ? offset_k : offset_t; }
+
+// ---- copying stored trees into another forest (vkmr_hip_forest_copy_trees_async): one step of one lane.  Destination tree u
+// (offset o_d, count c) is source tree ts (offset o_s, the same count); lane j of tree u's level l >= 0 moves one node, and hashes
+// nothing: a stored tree at another offset, under another number or in another forest has the same nodes, only their cells
+// differ, and differently per level, because (offset >> l) does not commute with a shift of the offset.  The source cell of a
+// lane is its destination cell plus a constant of (tree, level), so both sides are contiguous inside a tree.
+// THE PROPERTY: over l = 0 .. H_d and every lane of append's range of level l, the cells (leaves, level cells, roots) written are
+// exactly those a fresh vkmr_hip_reduce_forest_tree_async over the destination offsets writes for trees first_tree ..
+// first_tree + m - 1: the tests below are the build's own (forest_level), with "hash the two children" replaced by "copy".
+// forest_copy_level_kernel and the CPU replay in tests/c/forest_copy_plan_test.cpp both run this text.
+enum CopyKind : uint32_t {
+    COPY_NOTHING = 0,   // padding behind the tree's nodes, or the tree was done a level below (the build's "tree is done" test)
+    COPY_ZERO_ROOT,     // an empty tree: its reserved cell's lane at level 1 writes the all-zero root, once
+    COPY_ROOT,          // level l is the tree's last: dst_roots[u] = src_roots[ts] (and the mask); no cell, as in the build
+    COPY_CELL,          // cell src of the source's level l to cell dst of the destination's level l
+    COPY_LEAF           // l == 0: cell src of the source's leaves to cell dst of the destination's
+};
+struct CopyStep {
+    CopyKind kind;
+    uint64_t src, dst;  // cells of level l's buffers (of the leaves for l == 0); unused for the roots
+};
+
+VKMR_FOREST_FN CopyStep copy_step(uint64_t o_d, uint32_t u, uint64_t c, uint64_t o_s, uint32_t ts, uint32_t l, uint64_t j)
+{
+    CopyStep s;
+    s.kind = COPY_NOTHING;
+    s.src = pos(o_s, ts, l) + j;
+    s.dst = pos(o_d, u, l) + j;
+    if (l == 0u) {
+        if (j < c) s.kind = COPY_LEAF;
+        return s;
+    }
+    if (c == 0ull) {
+        if (l == 1u && j == 0ull) s.kind = COPY_ZERO_ROOT;
+        return s;
+    }
+    const uint64_t n_out = level_count(c, l);
+    if ((l > 1u && level_count(c, l - 1u) == 1ull) || j >= n_out) return s;
+    s.kind = n_out == 1ull ? COPY_ROOT : COPY_CELL;
+    return s;
+}
+
+// The tree of cell p of level l among trees 0 .. ntrees - 1 (ntrees >= 1): the last whose first cell is at or before p, 0 when
+// there is none.  For l >= 1 pos_l is strictly increasing and this is forest_find_tree's answer.  At l == 0 the first cells are
+// the offsets themselves, which only do not decrease -- empty trees share theirs with the tree behind them -- and the last tree
+// at or before p is still the one that holds leaf p; forest_copy_level_kernel searches level 0 this way in every lane.
+VKMR_FOREST_FN uint32_t copy_find_tree(const uint64_t* offsets, uint32_t ntrees, uint32_t l, uint64_t p, uint32_t t = 0)
+{
+    uint32_t top = ntrees - 1u;
+    while (t < top) {
+        const uint32_t mid = t + (top - t + 1u) / 2u;
+        if (pos(offsets[mid], mid, l) <= p) t = mid;
+        else top = mid - 1u;
+    }
+    return t;
+}
+
 }  // namespace vkmr_forest

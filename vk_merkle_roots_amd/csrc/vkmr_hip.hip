@@ -19,6 +19,8 @@
 //                                              sibling pairs, CVE-2012-2459) formed beside the hash, and the flag alone from stored levels
 //                       forest_append_*_kernel, forest_truncate_kernel   trees appended into the room a stored forest was built
 //                                              with (the level body again, over the new trees' cells alone), the last trees dropped
+//   forest_copy_kernels.hpp  forest_drop_front_kernel, forest_copy_*_kernel   the oldest trees dropped (offsets alone), stored trees
+//                                              copied into another forest cell by cell: no hash
 //                       forest_extend_*_kernel   the last tree in use grown or shrunk by leaves: the level body once more, over
 //                                              the nodes of its right edge alone
 //   frontier_kernels.hpp  frontier_*_kernel     trees followed by their frontiers alone (a count and one peak per set bit): the
@@ -83,6 +85,7 @@ using vkmr_dev::Node;
 #include "tree_plan.hpp"
 #include "tree_kernels.hpp"
 #include "forest_kernels.hpp"
+#include "forest_copy_kernels.hpp"
 #include "forest_tree_kernels.hpp"
 #include "find_kernels.hpp"
 #include "sort_kernels.hpp"
@@ -1211,6 +1214,62 @@ vkmr_status vkmr_hip_forest_truncate_async(int dev, vkmr_stream s, uint64_t* off
     if (!offsets_dev || !roots_dev) return refuse(__func__, "null pointer");
     VKMR_TRY(hipSetDevice(dev));
     return launch(forest_truncate_kernel, grid_of(ntrees - keep_trees), dim3(256), S(s), offsets_dev, ntrees, keep_trees, nodes(roots_dev));
+}
+
+// ---- forests that slide: the oldest trees dropped, stored trees copied into another forest (forest_copy_kernels.hpp) ----------
+
+vkmr_status vkmr_hip_forest_drop_front_async(int dev, vkmr_stream s, uint64_t* offsets_dev, uint32_t ntrees, uint32_t drop_trees,
+                                             vkmr_digest* roots_dev, uint64_t* mutated_dev)
+{
+    if (drop_trees > ntrees) return refuse(__func__, "more trees to drop than the forest has");
+    if (drop_trees == 0) return VKMR_OK;
+    if (!offsets_dev || !roots_dev) return refuse(__func__, "null pointer");
+    VKMR_TRY(hipSetDevice(dev));
+    return launch(forest_drop_front_kernel, grid_of(drop_trees), dim3(256), S(s), offsets_dev, drop_trees, nodes(roots_dev),
+                  reinterpret_cast<unsigned long long*>(mutated_dev));
+}
+
+vkmr_status vkmr_hip_forest_copy_trees_async(int dev, vkmr_stream s, const vkmr_digest* src_digests_dev, const vkmr_digest* src_forest_dev,
+                                             uint64_t src_total, const uint64_t* src_offsets_dev, uint32_t src_ntrees, uint64_t src_max_count,
+                                             const vkmr_digest* src_roots_dev, const uint64_t* src_mutated_dev, const uint32_t* sel_dev, uint32_t m,
+                                             uint64_t n_leaves, const uint64_t* new_offsets_dev, vkmr_digest* dst_digests_dev,
+                                             vkmr_digest* dst_forest_dev, uint64_t dst_total, uint64_t* dst_offsets_dev, uint32_t dst_ntrees,
+                                             uint64_t dst_max_count, uint32_t first_tree, uint64_t used, vkmr_digest* dst_roots_dev,
+                                             uint64_t* dst_mutated_dev, uint32_t* status_dev)
+{
+    if (m == 0) return VKMR_OK;
+    if (((!src_digests_dev || !dst_digests_dev) && n_leaves > 0) || !src_forest_dev || !src_offsets_dev || !src_roots_dev || !sel_dev ||
+        !new_offsets_dev || !dst_forest_dev || !dst_offsets_dev || !dst_roots_dev || !status_dev)
+        return refuse(__func__, "null pointer");
+    if (first_tree > dst_ntrees || m > dst_ntrees - first_tree) return refuse(__func__, "more trees than the forest has room for");
+    if (used > dst_total || n_leaves > dst_total - used) return refuse(__func__, "more leaves than the forest has room for");
+    VKMR_CHECK(forest_args_check(__func__, src_total, src_ntrees, src_max_count, 0, nullptr, nullptr));
+    VKMR_CHECK(forest_args_check(__func__, dst_total, dst_ntrees, dst_max_count, 0, nullptr, nullptr));
+    if ((dst_digests_dev && dst_digests_dev == src_digests_dev) || dst_forest_dev == src_forest_dev || dst_offsets_dev == src_offsets_dev || dst_roots_dev == src_roots_dev)
+        return refuse(__func__, "a copy inside one forest is not offered");
+    if (grid_too_large(groups_of(n_leaves))) return refuse(__func__, "too many leaves in one call");
+    const uint32_t H = vkmr_forest::launches(dst_total, dst_max_count);   // <= 58: the destination's build's
+    const uint32_t H_src = vkmr_forest::launches(src_total, src_max_count);
+    const uint32_t end_tree = first_tree + m, behind = dst_ntrees - first_tree;
+    Node* roots = nodes(dst_roots_dev);
+    unsigned long long* mutated = reinterpret_cast<unsigned long long*>(dst_mutated_dev);
+    const unsigned long long* src_mutated = reinterpret_cast<const unsigned long long*>(src_mutated_dev);
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_TRY(hipMemsetAsync(status_dev, 0, sizeof(uint32_t), S(s)));
+    VKMR_CHECK(launch(forest_copy_check_kernel, grid_of((uint64_t)behind + 1), dim3(256), S(s), dst_offsets_dev, dst_ntrees, first_tree, used,
+                      new_offsets_dev, m, n_leaves, dst_max_count, sel_dev, src_offsets_dev, src_ntrees, status_dev));
+    // append's own: the destination offsets, and the masks of the new trees zeroed in the same launch
+    VKMR_CHECK(launch(forest_append_offsets_kernel, grid_of(behind), dim3(256), S(s), dst_offsets_dev, dst_ntrees, first_tree, used, new_offsets_dev, m,
+                      mutated, status_dev));
+    for (uint32_t l = 0; l <= H; ++l) {   // level l of the new trees from level l of their source trees: a cell is copied at l < height(c) <= H_src only
+        const Node* src = (l == 0) ? nodes(src_digests_dev) : nodes(src_forest_dev) + vkmr_forest::stored_level_base(src_total, src_ntrees, l < H_src ? l : H_src);
+        Node* dst = (l == 0) ? nodes(dst_digests_dev) : nodes(dst_forest_dev) + vkmr_forest::stored_level_base(dst_total, dst_ntrees, l);
+        const uint64_t base = vkmr_forest::append_first_cell(used, first_tree, l), end = vkmr_forest::append_end_cell(used + n_leaves, end_tree, l);
+        if (end == base) continue;        // level 0 of trees that are all empty
+        VKMR_CHECK(launch(forest_copy_level_kernel, grid_of(end - base), dim3(256), S(s), src, src_offsets_dev, nodes(src_roots_dev), src_mutated, sel_dev,
+                          dst_offsets_dev, first_tree, end_tree, l, base, end, dst, roots, mutated, status_dev));
+    }
+    return VKMR_OK;
 }
 
 // ---- the open tree of a stored forest grown or shrunk by leaves, at its right edge (forest_kernels.hpp) ----------------------

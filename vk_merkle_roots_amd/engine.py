@@ -701,6 +701,24 @@ class HipDevice:
         roots are zero; one launch, no hash."""
         self._call("vkmr_hip_forest_truncate_async", offsets_buf, ntrees, keep_trees, roots_buf, stream=stream)
 
+    # -- forests that slide: the oldest trees dropped, stored trees copied into another forest; no hash in either ------------
+    def forest_drop_front_enqueue(self, offsets_buf, ntrees, drop_trees, roots_buf, mutated_buf=None, stream=None):
+        """Trees 0 .. drop_trees - 1 of a stored forest emptied where tree drop_trees begins: their offsets are its offset,
+        their roots zero (and their masks in mutated_buf, ntrees uint64 or None); one launch, no hash, nothing else moves."""
+        self._call("vkmr_hip_forest_drop_front_async", offsets_buf, ntrees, drop_trees, roots_buf, mutated_buf, stream=stream)
+
+    def forest_copy_trees_enqueue(self, src_digests_buf, src_forest_buf, src_total, src_offsets_buf, src_ntrees, src_max_count, src_roots_buf,
+                                  src_mutated_buf, sel_buf, m, n_leaves, new_offsets_buf, dst_digests_buf, dst_forest_buf, dst_total, dst_offsets_buf,
+                                  dst_ntrees, dst_max_count, first_tree, used, dst_roots_buf, dst_mutated_buf, status_buf, stream=None):
+        """Trees first_tree .. first_tree + m - 1 of the destination forest (dst_*: forest_append_enqueue's arguments), empty at
+        offset `used` until now, become trees sel_buf[0 .. m) (uint32) of the stored source forest src_*, copied cell by
+        cell and never hashed.  new_offsets_buf: m + 1 uint64 from 0 to n_leaves, the prefix sums of the chosen trees' counts.
+        src_mutated_buf / dst_mutated_buf: the forests' masks or None (copied; zeroed without the source's).  status_buf: one
+        uint32, forest_copy_status_text names its bits; nonzero: nothing changed.  All in device memory.  include/vkmr_hip.h."""
+        self._call("vkmr_hip_forest_copy_trees_async", src_digests_buf, src_forest_buf, src_total, src_offsets_buf, src_ntrees, src_max_count,
+                   src_roots_buf, src_mutated_buf, sel_buf, m, n_leaves, new_offsets_buf, dst_digests_buf, dst_forest_buf, dst_total, dst_offsets_buf,
+                   dst_ntrees, dst_max_count, first_tree, used, dst_roots_buf, dst_mutated_buf, status_buf, stream=stream)
+
     def forest_extend_enqueue(self, digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, tree, count, used, leaves_buf, n_leaves, roots_buf,
                               mutated_buf, status_buf, stream=None):
         """The open tree `tree` of a stored forest (total, ntrees, max_count: the build's) -- `count` leaves ending at cell
@@ -1360,10 +1378,14 @@ class MerkleForest(_Stored):
         self.forest, self.roots_buf = forest_buf, roots_buf
         self._owned = list(owned)
         self.used_trees = self.ntrees if used_trees is None else int(used_trees)
+        self.dropped_trees = self.dropped_leaves = 0         # drop_front(): trees emptied at the front, cells in front that are no tree's
 
     # -- room to grow: `total` and `ntrees` are the capacity the level buffers are laid out for; the trees in use are the first
-    # used_trees, their leaves the first used_leaves cells; the trees behind them are empty and the cells behind them free
-    used_leaves = property(lambda self: int(self.counts.sum()))
+    # used_trees, their leaves end at cell used_leaves; the trees behind them are empty and the cells behind them free.  After
+    # drop_front() the first dropped_leaves cells belong to no tree: used_leaves still is the cell behind the last leaf in
+    # use, where append and extend go on, and live_leaves counts the leaves that trees hold
+    used_leaves = property(lambda self: self.dropped_leaves + int(self.counts.sum()))
+    live_leaves = property(lambda self: int(self.counts.sum()))
     free_trees = property(lambda self: self.ntrees - self.used_trees)
     free_leaves = property(lambda self: self.total - self.used_leaves)
 
@@ -1446,15 +1468,122 @@ class MerkleForest(_Stored):
         keep_trees = int(keep_trees)
         if not 0 <= keep_trees <= self.used_trees:
             raise ValueError(f"truncate: {keep_trees} trees to keep, {self.used_trees} in use")
+        if keep_trees < self.dropped_trees:
+            raise ValueError(f"truncate: {keep_trees} trees to keep, the first {self.dropped_trees} were dropped from the front")
         self.dev.forest_truncate_enqueue(self.offsets, self.ntrees, keep_trees, self.roots_buf, stream=stream)
         self.counts[keep_trees:] = 0
         self.used_trees = keep_trees
 
     def truncate(self, keep_trees):
         """Drop the last trees in use, all from number keep_trees on: the inverse of append(), for appending others in their
-        place.  Trees cannot be dropped from the front.  ValueError for keep_trees above used_trees."""
+        place.  drop_front() is its counterpart for the oldest trees.  ValueError for keep_trees above used_trees, or below
+        the trees dropped from the front."""
         self.truncate_async(keep_trees)
         self.dev.sync()
+
+    # -- forests that slide: the oldest trees dropped where they lie, the rest copied into a forest with fresh room ----------
+    def drop_front_async(self, k, stream=None):
+        """Trees 0 .. k - 1 emptied on the device and in the host's view; one launch on `stream`, no hash.  They become empty
+        trees where tree k begins, so every tree from k on keeps its NUMBER, its cells and its proofs.  ValueError for k
+        above used_trees; k at or below dropped_trees does nothing."""
+        k = int(k)
+        if not 0 <= k <= self.used_trees:
+            raise ValueError(f"drop_front: {k} trees to drop, {self.used_trees} in use")
+        if k <= self.dropped_trees:
+            return
+        self.dev.forest_drop_front_enqueue(self.offsets, self.ntrees, k, self.roots_buf, None, stream=stream)
+        self.dropped_leaves += int(self.counts[:k].sum())
+        self.counts[:k] = 0
+        self.dropped_trees = k
+
+    def drop_front(self, k):
+        """Drop the oldest trees, all below number k: a window that slides (a chain keeps the last N blocks, an index expires
+        files, a log is pruned).  Nothing moves and nothing is hashed; the dropped trees stay in the numbering as empty trees
+        (roots zero, counts 0), find() no longer answers with their leaves, an update naming one is refused.  Their cells are
+        not free again -- dropped_leaves counts them, used_leaves and free_leaves are where append() goes on -- until
+        repacked() copies the live trees into a forest with fresh room.  ValueError for k above used_trees."""
+        self.drop_front_async(k)
+        self.dev.sync()
+
+    def append_from_async(self, src, sel_buf, m, n_leaves, new_offsets_buf, status_buf, src_mutated_buf=None, mutated_buf=None, stream=None):
+        """The next m free trees become trees sel_buf[0 .. m) (uint32) of the stored forest `src`, another MerkleForest of this
+        device: copied cell by cell, never hashed.  new_offsets_buf: m + 1 uint64 from 0 to n_leaves, the prefix sums of their
+        counts; status_buf: one uint32, 0 when copied (forest_copy_status_text names the bits; nonzero: nothing changed);
+        src_mutated_buf / mutated_buf: the masks of `src` and of this forest (uint64 per tree) or None.  All in device
+        memory; ordered on `stream`.  Only enqueues: the caller who has seen status 0 tells the handle with appended(counts)."""
+        self.dev.forest_copy_trees_enqueue(src.digests, src.forest, src.total, src.offsets, src.ntrees, src.max_count, src.roots_buf,
+                                           src_mutated_buf, sel_buf, m, n_leaves, new_offsets_buf, self.digests, self.forest, self.total,
+                                           self.offsets, self.ntrees, self.max_count, self.used_trees, self.used_leaves, self.roots_buf,
+                                           mutated_buf, status_buf, stream=stream)
+
+    def _chosen(self, src, trees, what):
+        """(sel uint32 [m], the new offsets, the counts) of trees `trees` of `src`, with append's host refusals."""
+        if not isinstance(src, MerkleForest):
+            raise ValueError(f"{what}: the source is no MerkleForest")
+        if src is self:
+            raise ValueError(f"{what}: a copy inside one forest is not offered")
+        sel = _as_uint64(trees, what, "tree", "trees", below=src.ntrees).astype(np.uint32)
+        counts = src.counts[sel.astype(np.int64)]
+        offsets, new = self._append_counts(counts, int(counts.sum()), what, "leaves")
+        return sel, offsets, new
+
+    def append_from(self, src, trees, mutated=False):
+        """New trees behind the last one in use, copied from the stored forest `src` (same device): its trees `trees`, in
+        any order, with repeats and empty trees.  Every level is copied from src's, nothing is hashed and no leaf goes through
+        the host: two forests merged, one split, trees moved.  The numbers of the new trees; mutated=True: (numbers, their
+        mutation masks, from a scan of src).  append()'s ValueErrors for room and max_count, taken from src.counts, before
+        any device call; IndexError for a tree src does not have; RuntimeError when the device refuses."""
+        sel, offsets, new = self._chosen(src, trees, "append_from")
+        first, m = self.used_trees, int(sel.shape[0])
+        numbers = np.arange(first, first + m, dtype=np.uint32)
+        masks = np.zeros(m, dtype=np.uint64)
+        if m:
+            with self.dev.scope() as tmp:
+                d_status, d_src_mut, d_mut = tmp.alloc(4), None, None
+                if mutated:
+                    d_src_mut, d_mut = tmp.alloc(8 * src.ntrees), tmp.alloc(8 * self.ntrees)
+                    src.mutated_async(d_src_mut)
+                self.append_from_async(src, tmp.upload(sel), m, int(offsets[-1]), tmp.upload(offsets), d_status, d_src_mut, d_mut)
+                status = int(self.dev.download(d_status, 4)[0])
+                if status:
+                    raise RuntimeError(f"MerkleForest.append_from: the device refused the trees (status {status}: {forest_copy_status_text(status)})")
+                if mutated:
+                    masks = self.dev.download(d_mut, 8 * m, dtype=np.uint64, offset=8 * first)
+                self.appended(new)
+        return (numbers, masks) if mutated else numbers
+
+    def repacked(self, trees=None, max_count=None, reserve_trees=0, reserve_leaves=0, mutated=False):
+        """A new MerkleForest, owning all its buffers, that holds trees `trees` of this one -- by default the trees in use that
+        were not dropped, in order -- as its trees 0 .. m - 1, with reserve_trees empty trees and reserve_leaves free cells
+        behind them: the room in front that drop_front() left is reclaimed, a used-up reserve renewed, trees deleted from the
+        middle.  Allocation plus one copy call: no leaf goes through the host and nothing is hashed.  max_count: that of the
+        new forest (this forest's when None).  mutated=True keeps the copied trees' masks in built_mutated.  This forest is
+        left as it is.  ValueError for no tree at all or a chosen tree above max_count, IndexError for a tree not there."""
+        what = "repacked"
+        reserve_trees, reserve_leaves = _reserve(what, reserve_trees, reserve_leaves, self.max_count)
+        if trees is None:
+            trees = np.arange(self.dropped_trees, self.used_trees, dtype=np.uint32)
+        sel = _as_uint64(trees, what, "tree", "trees", below=self.ntrees).astype(np.uint32)
+        counts = self.counts[sel.astype(np.int64)]
+        m, n = int(sel.shape[0]), int(counts.sum())
+        max_count = self.max_count if max_count is None else int(max_count)
+        if m + reserve_trees == 0:
+            raise ValueError(f"{what}: no tree")
+        if max_count < 1 or (m and int(counts.max()) > max_count):
+            raise ValueError(f"{what}: a tree of {int(counts.max()) if m else 0} leaves, max_count is {max_count}")
+        ntrees, total = m + reserve_trees, n + reserve_leaves
+        dev = self.dev
+        with dev.scope() as tmp:
+            d_leaves = tmp.alloc(32 * total) if total else None
+            d_forest = tmp.alloc(dev.forest_tree_bytes(total, ntrees, max_count))
+            d_off, d_roots = tmp.upload(np.zeros(ntrees + 1, dtype=np.uint64)), tmp.upload(np.zeros((ntrees, 8), dtype=np.uint32))
+            new = MerkleForest(dev, d_leaves, total, np.zeros(ntrees, dtype=np.uint64), d_off, max_count, d_forest, d_roots, used_trees=0)
+            got = new.append_from(self, sel, mutated=mutated)
+            if mutated:
+                new.built_mutated = np.concatenate([got[1], np.zeros(reserve_trees, dtype=np.uint64)])
+            new._owned = [d_leaves] if d_leaves else []
+            tmp.release(d_leaves, d_forest, d_off, d_roots)      # the new forest's from here on
+        return new
 
     # -- the open tree: the last tree in use takes more leaves, or drops its last, at its right edge ------------------------
     @property
@@ -1673,7 +1802,7 @@ class MerkleForest(_Stored):
     def _entry_cells(self, trees, indices):
         """(each entry's cell in the leaves buffer, the leaf count of its tree)."""
         t = trees.astype(np.int64)
-        offsets = np.concatenate([[0], np.cumsum(self.counts)]).astype(np.uint64)
+        offsets = np.concatenate([[0], np.cumsum(self.counts)]).astype(np.uint64) + np.uint64(self.dropped_leaves)
         return offsets[t] + indices, self.counts[t]
 
     def update_with_witness(self, trees, indices, leaves):
@@ -1931,6 +2060,16 @@ def forest_append_status_text(status):
     if status & 4:
         names.append("bit 2: the forest's free trees do not begin where the caller says")
     if status & ~7:
+        names.append("unknown bits")
+    return "; ".join(names) if names else "ok"
+
+
+def forest_copy_status_text(status):
+    """The bits of vkmr_hip_forest_copy_trees_async's status word, named: append's three and bit 3."""
+    names = [] if not status & 7 else [forest_append_status_text(status & 7)]
+    if status & 8:
+        names.append("bit 3: a chosen tree is not in the source forest, or a new count is not that tree's count")
+    if status & ~15:
         names.append("unknown bits")
     return "; ".join(names) if names else "ok"
 
