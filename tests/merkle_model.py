@@ -13,10 +13,26 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+def digest_of(b):
+    """SHA-256d of the bytes `b` as 8 words: the leaf digest of a string."""
+    return np.frombuffer(hashlib.sha256(hashlib.sha256(b).digest()).digest(), dtype=">u4").astype(np.uint32)
+
+
 def node(l, r):
     """SHA-256d(l || r) of word-valued digests."""
-    b = np.concatenate([l, r]).astype(">u4").tobytes()
-    return np.frombuffer(hashlib.sha256(hashlib.sha256(b).digest()).digest(), dtype=">u4").astype(np.uint32)
+    return digest_of(np.concatenate([l, r]).astype(">u4").tobytes())
+
+
+def stored_level_base(total, ntrees, l):
+    """The cell of a stored forest's level buffers at which level l >= 1 begins: level j has (total >> j) + ntrees cells
+    (include/vkmr_hip.h, STORED FOREST)."""
+    return sum((int(total) >> j) + int(ntrees) for j in range(1, l))
+
+
+def stored_node_cell(total, ntrees, offset, t, l, j):
+    """The cell of the level buffers that holds node j of level l (1 <= l < h_t) of tree t, a tree whose leaves begin at cell
+    `offset` of level 0."""
+    return stored_level_base(total, ntrees, l) + (int(offset) >> l) + int(t) + int(j)
 
 
 def tree_height(count):

@@ -1155,7 +1155,7 @@ class _Stored:
         """The leaves in which this tree or forest and `other` differ, in increasing order: a tree gives indices uint64 [n],
         a forest (trees uint32 [n], indices uint64 [n]).  capacity None: room for min(cells, 65536) answers first, 16 times
         more while more differ; an integer: DiffOverflow when more differ.  ValueError for another device or another shape
-        (a tree's count and height; a forest's counts and max_count), before any device call."""
+        (a tree's count and height; a forest's counts, dropped front and max_count), before any device call."""
         with self.dev.scope() as tmp:
             n, d_entries, _ = self._diff(tmp, other, capacity, False, "diff")
             return _bare(self._read(d_entries, self._columns, n) if n else _empty(self._columns))
@@ -1501,7 +1501,9 @@ class MerkleForest(_Stored):
         files, a log is pruned).  Nothing moves and nothing is hashed; the dropped trees stay in the numbering as empty trees
         (roots zero, counts 0), find() no longer answers with their leaves, an update naming one is refused.  Their cells are
         not free again -- dropped_leaves counts them, used_leaves and free_leaves are where append() goes on -- until
-        repacked() copies the live trees into a forest with fresh room.  ValueError for k above used_trees."""
+        repacked() copies the live trees into a forest with fresh room.  A dropped tree is never the open tree: after
+        drop_front(used_trees) extend() and shrink() find no tree in use, and the next leaves come by append().  ValueError
+        for k above used_trees."""
         self.drop_front_async(k)
         self.dev.sync()
 
@@ -1588,8 +1590,10 @@ class MerkleForest(_Stored):
     # -- the open tree: the last tree in use takes more leaves, or drops its last, at its right edge ------------------------
     @property
     def open_tree(self):
-        """The number of the last tree in use, the one extend() and shrink() work on; None when no tree is in use."""
-        return self.used_trees - 1 if self.used_trees else None
+        """The number of the last tree in use, the one extend() and shrink() work on; None when no tree is in use.  A tree
+        dropped from the front is never the open tree: after drop_front(used_trees) -- or a truncate() down to the dropped
+        trees -- there is none until append() brings the next."""
+        return self.used_trees - 1 if self.used_trees > self.dropped_trees else None
 
     def _open(self, what, more=0, fewer=0):
         """(the open tree, its count, the leaves in use); ValueError -- before any device call -- when no tree is in use, when
@@ -1659,7 +1663,8 @@ class MerkleForest(_Stored):
         `digests` [n, 8] (a host array) go behind its last leaf and only the nodes of its right edge are hashed, at most
         (n >> l) + 2 at level l; the forest is afterwards what a build over the new counts gives.  The open tree's count;
         mutated=True: (count, its mutation mask, what forest_roots_mutated gives for it).  ValueError, before any device call,
-        when no tree is in use, when there is no room for the leaves or the tree would pass max_count."""
+        when no tree is in use -- none at all, or every one dropped from the front: a dropped tree takes no leaf, growth goes
+        on by append() -- when there is no room for the leaves or the tree would pass max_count."""
         digests = _host(digests, np.uint32, -1, 8)
         n = int(digests.shape[0])
         self._open("extend", more=n)
@@ -1684,7 +1689,8 @@ class MerkleForest(_Stored):
     def shrink(self, r, mutated=False):
         """The open tree drops its last r leaves: the inverse of extend(); their cells are free again.  Only the nodes of the
         new right edge are hashed.  The open tree's count (it may reach 0: the tree stays in use, empty); mutated=True:
-        (count, its mask).  ValueError, before any device call, when no tree is in use or r is above the open tree's count."""
+        (count, its mask).  ValueError, before any device call, when no tree is in use (a tree dropped from the front is not:
+        open_tree) or r is above the open tree's count."""
         r = int(r)
         self._open("shrink", fewer=r)
         if r == 0 and not mutated:
@@ -1832,13 +1838,16 @@ class MerkleForest(_Stored):
 
     def _same_shape(self, other, what):
         """ValueError unless `other` is a MerkleForest of this forest's device, counts, capacity (cells and trees, room to grow
-        included) and max_count; no device call."""
+        included), front and max_count; no device call.  With equal counts, equal dropped_leaves put every tree of the two at
+        the same offset: one forest's offsets then serve for both."""
         if not isinstance(other, MerkleForest):
             raise ValueError(f"{what}: the other side is no MerkleForest")
         if other.dev.index != self.dev.index:
             raise ValueError(f"{what}: the forests live on devices {self.dev.index} and {other.dev.index}")
         if other.ntrees != self.ntrees or other.total != self.total or not np.array_equal(other.counts, self.counts):
             raise ValueError(f"{what}: the forests do not have the same counts")
+        if other.dropped_leaves != self.dropped_leaves:
+            raise ValueError(f"{what}: {self.dropped_leaves} cells dropped in front against {other.dropped_leaves}: the trees lie at other offsets")
         if other.max_count != self.max_count:
             raise ValueError(f"{what}: max_count {self.max_count} against {other.max_count}")
 
