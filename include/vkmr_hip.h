@@ -1058,6 +1058,59 @@ VKMR_API vkmr_status vkmr_hip_frontier_extend_async(int dev, vkmr_stream s, cons
                                                     uint32_t* status_dev);
 
 /*
+ * CONSISTENCY PROOFS: A HOLDER OF TWO ROOTS CHECKS THAT A TREE ONLY GREW.  A monitor, a light client or an auditor of a log
+ * holds the root a tree had at c leaves, is handed the root it has at c2 >= c leaves, and must decide whether the first c leaves
+ * are still the ones it trusted -- without the c2 - c leaves between.  The proof is two rows of `stride` digests (1 <= stride
+ * <= 64), read from the stored levels of the NEW tree without a hash.  With l0 the lowest set bit of c >= 1 and the notation of
+ * the block above:
+ *   peaks    cell l = P_l of the OLD count for every set bit l of c (a complete node never changes): a frontier of count c
+ *   rights   for l0 <= l < H(c2) the walk from P_l0 to the new root stands on node j = (c >> l0) - 1 of level l0 and on
+ *            j = c >> l above it.  Where l == l0 or bit l of c is clear j is a left child, and cell l holds node j + 1 of the
+ *            new tree's level l when that node exists (j + 1 < ceil(c2 / 2^l)); where bit l of c is set above l0, j is a right
+ *            child whose left sibling is P_l, so no cell is needed
+ * Every other cell of both rows is zero and is never read, so that two proofs of one claim compare byte for byte.
+ * THE CHECK.  The root of the frontier (c, peaks), by the rule above, must be the old root.  Then acc = P_l0 and for
+ * l = l0 .. H(c2) - 1: a left child gives acc = node_hash(acc, rights[l] if node j + 1 exists, else acc), a right child
+ * acc = node_hash(P_l, acc); acc must be the new root.  Both must hold: the SAME peaks serve both walks, which is what binds
+ * the old tree into the new one.  c == c2 runs through the same rule.  c == 0: ok exactly when the old root is all zero (any
+ * tree extends one not yet begun), nothing else is read.  ok = 0 without reading a cell: c > c2, c2 > 2^58, c2 of more bits
+ * than stride.  At most H(c) + H(c2) node hashes a query.
+ *
+ * vkmr_hip_forest_consistency_async: the proofs of Q queries out of a stored forest, taken as vkmr_hip_forest_frontier_async
+ * takes it (digests_dev .. max_count: those of the build, trusted in the same way; roots_dev holds every level of a single node).
+ *   trees_dev, old_counts_dev  Q queries (tree, old count) in device memory, CHECKED there; a tree in any order and as often as
+ *                              wanted: a log serves many followers at different counts
+ *   new_counts_out_dev         Q counts: the count the tree of query q has now
+ *   peaks_out_dev, rights_out_dev   Q x stride digests each; EVERY cell is written, zeros included
+ *   status_dev                 one uint32_t, always written: 0 when done; bit 0 (1) a tree index >= ntrees; bit 1 (2) an old
+ *                              count above the tree's count (so a tree dropped from the front, count 0, proves nothing but
+ *                              c == 0, and a tree that shrank below c is refused); bit 2 (4) a current count of more bits than
+ *                              stride.  When it is nonzero NOTHING of the caller's is written: no count, no cell.
+ * Level 0 is the leaves; level l >= 1 of two nodes at least is cell (offsets[t] >> l) + t + node of stored level l; a level of a
+ * single node is roots_dev[t] (only the seed P_l0 when c == c2 == 2^l0 lies there).  Launches, all on the caller's stream: the
+ * status word zeroed, one check (a lane per query), one gather (a lane per (query, cell), at most two loads, no hash); never a
+ * launch per tree or per query, no allocation, no host read of device data.  Refused on the host (VKMR_ERR_INVALID), before
+ * any HIP call: a NULL pointer, and what vkmr_hip_forest_frontier_async refuses.  Q == 0 does nothing.
+ *
+ * vkmr_hip_verify_consistency_async: the check above, a lane per query in one launch; ok_dev[q] (uint32_t) = 1 when proof q
+ * (old_counts_dev[q], new_counts_dev[q], the stride cells of peaks_dev and rights_dev behind q * stride) holds under
+ * old_roots_dev[q] and new_roots_dev[q], else 0.  No stored level, no scratch: what a monitor runs.  The roots are per query;
+ * the caller indexes its own tables by tree.  Refused: a NULL pointer, stride outside 1..64.  Q == 0 does nothing.
+ * The peaks row with the old counts IS a frontier: vkmr_hip_frontier_roots_async over it names every tree's root as of its old
+ * count again, and a follower that fell behind adopts it under the old root it trusts and goes on with
+ * vkmr_hip_frontier_extend_async.  vkmr_host_cpu_forest_consistency and vkmr_host_cpu_verify_consistency (libvkmr_host.so)
+ * apply the same rules on the CPU.  Not offered: inclusion proofs as of an earlier count.
+ */
+VKMR_API vkmr_status vkmr_hip_forest_consistency_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* forest_dev,
+                                                       uint64_t total, const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count,
+                                                       const vkmr_digest* roots_dev, const uint32_t* trees_dev, const uint64_t* old_counts_dev,
+                                                       uint32_t Q, uint32_t stride, uint64_t* new_counts_out_dev, vkmr_digest* peaks_out_dev,
+                                                       vkmr_digest* rights_out_dev, uint32_t* status_dev);
+VKMR_API vkmr_status vkmr_hip_verify_consistency_async(int dev, vkmr_stream s, const uint64_t* old_counts_dev, const uint64_t* new_counts_dev,
+                                                       const vkmr_digest* peaks_dev, const vkmr_digest* rights_dev, uint32_t stride, uint32_t Q,
+                                                       const vkmr_digest* old_roots_dev, const vkmr_digest* new_roots_dev, uint32_t* ok_dev);
+
+/*
  * COMBINE: duplicate-last Merkle root over n >= 1 slice roots given in slice order, always
  * at least one level -- the rule of CpuSha256D::Root that the reference applies to the slice
  * roots on the CPU (CpuSha256DforReductions, src/vkmr/Reductions.cpp:56-69, :703-712).  Here

@@ -27,6 +27,8 @@
 #                          trees) beside truncate + append of the whole tree and the stored build (one JSON line)
 #   frontier_extend [args] tools/frontier_extend_timing.py: a holder of the frontier alone following the same growth, beside the primary's
 #                          extend and the reduction of all the leaves (one JSON line)
+#   consistency [args]     tools/consistency_timing.py: consistency proofs gathered from a stored forest and checked by a holder of two roots
+#                          (2^15 trees of 2 048; one tree of 2^26 at Q = 1 and 2^16), beside verify_frontier and the follower's extend (one JSON line)
 #   forest_repack [args]   tools/forest_repack_timing.py: the oldest trees of a stored forest dropped and the rest (or all) copied into an
 #                          empty forest, beside the stored build over the same leaves (one JSON line)
 #   cumask                 tools/cu_mask_probe.py: where CU-mask bits land, map/reduce on half the CUs with and without neighbours
@@ -203,6 +205,11 @@ frontier_extend)
   timeout -k 10 500 python3 tools/frontier_extend_timing.py "$@" --out $OUT/frontier_extend_timing.json > /dev/null 2> $OUT/frontier_extend_timing.err && echo "frontier_extend_timing ok" &&
   cat $OUT/frontier_extend_timing.json
   echo "frontier_extend rc=$?"
+  ;;
+consistency)
+  timeout -k 10 500 python3 tools/consistency_timing.py "$@" --out $OUT/consistency_timing.json > /dev/null 2> $OUT/consistency_timing.err && echo "consistency_timing ok" &&
+  cat $OUT/consistency_timing.json
+  echo "consistency rc=$?"
   ;;
 forest_repack)
   timeout -k 10 500 python3 tools/forest_repack_timing.py "$@" --out $OUT/forest_repack_timing.json > /dev/null 2> $OUT/forest_repack_timing.err && echo "forest_repack_timing ok" &&

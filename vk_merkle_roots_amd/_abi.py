@@ -109,6 +109,10 @@ SIGNATURES = {
     "vkmr_hip_frontier_extend_scratch_bytes": (C.c_size_t, [C.c_uint64, C.c_uint32]),
     "vkmr_hip_frontier_extend_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p,
                                                  C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vkmr_hip_forest_consistency_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "vkmr_hip_verify_consistency_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                    C.c_void_p, C.c_void_p]),
     "vkmr_hip_forest_multiproof_max_nodes":(C.c_size_t, [C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32]),
     "vkmr_hip_forest_multiproof_scratch_bytes": (C.c_size_t, [C.c_uint32, C.c_uint32]),
     "vkmr_hip_forest_multiproof_async": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_uint64, C.c_void_p,
@@ -177,6 +181,9 @@ HOST_SIGNATURES = {
     "vkmr_host_cpu_frontier_extend": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                                 C.c_void_p, C.c_void_p, C.c_void_p]),
     "vkmr_host_cpu_forest_frontier": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    "vkmr_host_cpu_forest_consistency": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p]),
+    "vkmr_host_cpu_verify_consistency": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "vkmr_host_cpu_forest_find": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "vkmr_host_cpu_tree_find": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p]),
     "vkmr_host_cpu_forest_sort_entries": (C.c_int, [C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p,

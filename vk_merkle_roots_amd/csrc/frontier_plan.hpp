@@ -116,16 +116,21 @@ VKMR_FRONTIER_FN PeakSource peak_source(uint64_t c, uint64_t c2, uint32_t l)
 // The one tree no launch forms a root for: no new leaf and a power of two of at least 2 old ones; the root is P_H(c).
 VKMR_FRONTIER_FN bool root_is_old_peak(uint64_t c, uint64_t c2) { return c2 == c && c >= 2ull && (c & (c - 1ull)) == 0ull; }
 
-// ---- the frontier of a tree of a stored forest (vkmr_hip_forest_frontier_async): peak l of tree t with offset o and c leaves
-// is the leaf o + c - 1 for l == 0, roots[t] where c == 2^l (the build keeps a tree's last level in the roots alone), else
-// cell (o >> l) + t + (c >> l) - 1 of stored level l.
+// ---- a node of a tree of a stored forest, read where the build left it: node j of level l of tree t with offset o and `count`
+// leaves now (j < level_count(count, l)) is the leaf o + j for l == 0, roots[t] where level l has a single node (the build keeps
+// a tree's last level in the roots alone), else cell (o >> l) + t + j of stored level l.  consistency_plan.hpp reads the peaks
+// of an EARLIER count and their right neighbours by the same two functions.
 enum GatherSource { GATHER_NONE = 0, GATHER_LEAF = 1, GATHER_ROOT = 2, GATHER_LEVEL = 3 };
-VKMR_FRONTIER_FN GatherSource gather_source(uint64_t c, uint32_t l)
+VKMR_FRONTIER_FN GatherSource node_source(uint64_t count, uint32_t l)
 {
-    if (!has_peak(c, l)) return GATHER_NONE;
     if (l == 0u) return GATHER_LEAF;
-    return c == (1ull << l) ? GATHER_ROOT : GATHER_LEVEL;
+    return level_count(count, l) == 1ull ? GATHER_ROOT : GATHER_LEVEL;
 }
-VKMR_FRONTIER_FN uint64_t gather_cell(uint64_t o, uint32_t t, uint64_t c, uint32_t l) { return l == 0u ? o + c - 1ull : (o >> l) + t + (c >> l) - 1ull; }
+VKMR_FRONTIER_FN uint64_t node_cell(uint64_t o, uint32_t t, uint32_t l, uint64_t j) { return l == 0u ? o + j : (o >> l) + t + j; }
+
+// The frontier of such a tree (vkmr_hip_forest_frontier_async): peak l is node (c >> l) - 1 of level l, for c the count now:
+// the last leaf for l == 0, roots[t] where c == 2^l, else a cell of stored level l.
+VKMR_FRONTIER_FN GatherSource gather_source(uint64_t c, uint32_t l) { return has_peak(c, l) ? node_source(c, l) : GATHER_NONE; }
+VKMR_FRONTIER_FN uint64_t gather_cell(uint64_t o, uint32_t t, uint64_t c, uint32_t l) { return node_cell(o, t, l, (c >> l) - 1ull); }
 
 }  // namespace vkmr_frontier

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../audit_plan.hpp"   // forest_plan.hpp, tree_plan.hpp: where the stored levels lie
+#include "../consistency_plan.hpp"
 #include "../frontier_plan.hpp"
 #include "../merkle_math.hpp"
 #include "cpu_sha256d.hpp"
@@ -813,6 +814,97 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_forest_frontier(const v
         for (uint64_t i = offsets[t]; i < offsets[t + 1]; ++i) frontier_push(c, mine, digests[i]);
         counts_out[t] = c;
         std::memcpy(peaks_out + (size_t)t * stride, mine, sizeof(vkmr_digest) * stride);
+    }
+    return 0;
+}
+
+// ---- consistency proofs (consistency_plan.hpp; vkmr_hip_forest_consistency_async, vkmr_hip_verify_consistency_async) for a
+// primary or a monitor without a GPU.  The gather here has no stored forest: it builds every level of a queried tree from its
+// leaves and takes the nodes the plan names out of them.
+
+// The proofs of Q queries (trees[q], old_counts[q]) over the trees of a forest given by its leaves, tree t is
+// digests[offsets[t] .. offsets[t+1]): new_counts_out[q], and the stride cells of peaks_out and rights_out behind q * stride,
+// every cell written.  Returns the status word of vkmr_hip_forest_consistency_async (0: done; nonzero: nothing written), or -1
+// for a missing pointer, a stride outside 1..64 or offsets that decrease.
+__attribute__((visibility("default"))) int vkmr_host_cpu_forest_consistency(const vkmr_digest* digests, const uint64_t* offsets, uint32_t ntrees,
+                                                                             const uint32_t* trees, const uint64_t* old_counts, uint32_t Q,
+                                                                             uint32_t stride, uint64_t* new_counts_out, vkmr_digest* peaks_out,
+                                                                             vkmr_digest* rights_out)
+{
+    if (Q == 0) return 0;
+    if (!offsets || !trees || !old_counts || !new_counts_out || !peaks_out || !rights_out || stride == 0 || stride > VKMR_FRONTIER_MAX_STRIDE) return -1;
+    for (uint32_t t = 0; t < ntrees; ++t)
+        if (offsets[t + 1] < offsets[t]) return -1;
+    if (!digests && ntrees > 0 && offsets[ntrees] > offsets[0]) return -1;
+    uint32_t status = 0;
+    for (uint32_t q = 0; q < Q; ++q) status |= vkmr_consistency::refusal(trees[q], ntrees, offsets, old_counts[q], stride);
+    if (status) return (int)status;
+    std::vector<uint32_t> order(Q);
+    for (uint32_t q = 0; q < Q; ++q) order[q] = q;
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return trees[a] < trees[b]; });   // a tree's levels are built once
+    std::vector<std::vector<vkmr_digest>> levels;
+    uint32_t built = UINT32_MAX;
+    for (uint32_t q : order) {
+        const uint32_t t = trees[q];
+        const uint64_t c = old_counts[q], c2 = offsets[t + 1] - offsets[t];
+        new_counts_out[q] = c2;
+        vkmr_digest* peaks = peaks_out + (size_t)q * stride;
+        vkmr_digest* rights = rights_out + (size_t)q * stride;
+        std::memset(peaks, 0, sizeof(vkmr_digest) * stride);
+        std::memset(rights, 0, sizeof(vkmr_digest) * stride);
+        if (c == 0) continue;
+        if (built != t) {
+            levels.assign(1, std::vector<vkmr_digest>(digests + offsets[t], digests + offsets[t + 1]));
+            for (uint32_t l = 0; l < vkmr_math::height(c2); ++l) {
+                const std::vector<vkmr_digest>& in = levels[l];
+                std::vector<vkmr_digest> out((in.size() + 1) / 2);
+                for (uint64_t j = 0; j < out.size(); ++j) vkmr::cpu_sha256d_pair(in[2 * j].data, in[vkmr_math::right_child(j, in.size())].data, out[j].data);
+                levels.push_back(std::move(out));
+            }
+            built = t;
+        }
+        for (uint32_t l = 0; l < stride; ++l) {
+            if (vkmr_consistency::has_peak(c, l)) peaks[l] = levels[l][vkmr_consistency::peak_node(c, l)];
+            if (vkmr_consistency::has_right(c, c2, l)) rights[l] = levels[l][vkmr_consistency::right_node(c, l)];
+        }
+    }
+    return 0;
+}
+
+// ok[q] = 1 when proof q holds under old_roots[q] and new_roots[q], else 0: vkmr_hip_verify_consistency_async's check, the two
+// walks written out one behind the other.  -1 for a missing pointer or a stride outside 1..64.
+__attribute__((visibility("default"))) int vkmr_host_cpu_verify_consistency(const uint64_t* old_counts, const uint64_t* new_counts,
+                                                                             const vkmr_digest* peaks, const vkmr_digest* rights, uint32_t stride,
+                                                                             uint32_t Q, const vkmr_digest* old_roots, const vkmr_digest* new_roots,
+                                                                             uint32_t* ok)
+{
+    if (Q == 0) return 0;
+    if (!old_counts || !new_counts || !peaks || !rights || !old_roots || !new_roots || !ok || stride == 0 || stride > VKMR_FRONTIER_MAX_STRIDE) return -1;
+    for (uint32_t q = 0; q < Q; ++q) {
+        const uint64_t c = old_counts[q], c2 = new_counts[q];
+        const vkmr_digest* P = peaks + (size_t)q * stride;
+        const vkmr_digest* R = rights + (size_t)q * stride;
+        ok[q] = 0u;
+        if (!vkmr_consistency::checkable(c, c2, stride)) continue;
+        vkmr_digest acc;
+        if (c == 0) {
+            std::memset(acc.data, 0, 32);
+            ok[q] = std::memcmp(acc.data, old_roots[q].data, 32) == 0 ? 1u : 0u;
+            continue;
+        }
+        frontier_root(c, P, &acc);
+        if (std::memcmp(acc.data, old_roots[q].data, 32) != 0) continue;
+        const uint32_t l0 = vkmr_consistency::low_level(c);
+        acc = P[l0];
+        for (uint32_t l = l0; l < vkmr_math::height(c2); ++l) {
+            vkmr_digest next;
+            if (!vkmr_consistency::walk_is_left(c, l))
+                vkmr::cpu_sha256d_pair(P[l].data, acc.data, next.data);
+            else
+                vkmr::cpu_sha256d_pair(acc.data, vkmr_consistency::has_right(c, c2, l) ? R[l].data : acc.data, next.data);
+            acc = next;
+        }
+        ok[q] = std::memcmp(acc.data, new_roots[q].data, 32) == 0 ? 1u : 0u;
     }
     return 0;
 }

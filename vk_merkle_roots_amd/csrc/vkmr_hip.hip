@@ -26,6 +26,9 @@
 //   frontier_kernels.hpp  frontier_*_kernel     trees followed by their frontiers alone (a count and one peak per set bit): the
 //                                              new roots and frontiers from the new leaves, the root of a frontier, the frontier
 //                                              of a stored tree
+//   consistency_kernels.hpp  consistency_*_kernel   consistency proofs: the peaks of an earlier count and the right neighbours of
+//                                              the walk from them to the root gathered from a stored forest (no hash), and the
+//                                              verifier's two root walks, one lane per query (rules: consistency_plan.hpp)
 //   forest_tree_kernels.hpp  forest_proofs_kernel          proofs gathered from the stored forest, one lane per (query, level)
 //                            verify_forest_proofs_kernel   batch verification of proofs of unequal height, one lane per proof
 //                            forest_update_*_kernel        leaf updates of the stored forest: tree_update_*'s bodies, a tree per entry
@@ -92,6 +95,7 @@ using vkmr_dev::Node;
 #include "diff_kernels.hpp"
 #include "audit_kernels.hpp"
 #include "frontier_kernels.hpp"
+#include "consistency_kernels.hpp"
 
 // ============================================================================
 // C ABI
@@ -1422,6 +1426,40 @@ vkmr_status vkmr_hip_frontier_extend_async(int dev, vkmr_stream s, const uint64_
     // a wavefront per tree: four trees a workgroup
     return launch(frontier_commit_kernel, dim3((uint32_t)(((uint64_t)T + 3) / 4)), dim3(256), S(s), counts_dev, nodes(peaks_dev), stride, offsets_dev, T,
                   nodes(leaves_dev), staging, new_counts_dev, nodes(new_peaks_dev), nodes(roots_dev), status_dev);
+}
+
+// ---- consistency proofs (consistency_kernels.hpp, consistency_plan.hpp) ----------------------------------------------------------
+
+vkmr_status vkmr_hip_forest_consistency_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* forest_dev, uint64_t total,
+                                              const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count, const vkmr_digest* roots_dev,
+                                              const uint32_t* trees_dev, const uint64_t* old_counts_dev, uint32_t Q, uint32_t stride,
+                                              uint64_t* new_counts_out_dev, vkmr_digest* peaks_out_dev, vkmr_digest* rights_out_dev, uint32_t* status_dev)
+{
+    if (Q == 0) return VKMR_OK;
+    if ((!digests_dev && total > 0) || !forest_dev || !offsets_dev || !roots_dev || !trees_dev || !old_counts_dev || !new_counts_out_dev ||
+        !peaks_out_dev || !rights_out_dev || !status_dev)
+        return refuse(__func__, "null pointer");
+    VKMR_CHECK(forest_args_check(__func__, total, ntrees, max_count, 0, nullptr, nullptr));
+    VKMR_CHECK(frontier_args_check(__func__, stride, Q));
+    if (vkmr_frontier::bit_length(max_count < total ? max_count : total) > stride) return refuse(__func__, "a tree of max_count leaves has more bits than stride");
+    const ForestLevels lv = forest_levels(total, ntrees, vkmr_forest::launches(total, max_count));
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_TRY(hipMemsetAsync(status_dev, 0, sizeof(uint32_t), S(s)));
+    VKMR_CHECK(launch(consistency_check_kernel, grid_of(Q), dim3(256), S(s), offsets_dev, ntrees, trees_dev, old_counts_dev, Q, stride, status_dev));
+    return launch(consistency_gather_kernel, grid_of((uint64_t)Q * stride), dim3(256), S(s), nodes(digests_dev), nodes(forest_dev), lv, offsets_dev,
+                  nodes(roots_dev), trees_dev, old_counts_dev, Q, stride, new_counts_out_dev, nodes(peaks_out_dev), nodes(rights_out_dev), status_dev);
+}
+
+vkmr_status vkmr_hip_verify_consistency_async(int dev, vkmr_stream s, const uint64_t* old_counts_dev, const uint64_t* new_counts_dev,
+                                              const vkmr_digest* peaks_dev, const vkmr_digest* rights_dev, uint32_t stride, uint32_t Q,
+                                              const vkmr_digest* old_roots_dev, const vkmr_digest* new_roots_dev, uint32_t* ok_dev)
+{
+    if (Q == 0) return VKMR_OK;
+    if (!old_counts_dev || !new_counts_dev || !peaks_dev || !rights_dev || !old_roots_dev || !new_roots_dev || !ok_dev) return refuse(__func__, "null pointer");
+    VKMR_CHECK(frontier_args_check(__func__, stride, Q));
+    VKMR_TRY(hipSetDevice(dev));
+    return launch(consistency_fold_kernel, grid_of(Q), dim3(256), S(s), old_counts_dev, new_counts_dev, nodes(peaks_dev), nodes(rights_dev), stride, Q,
+                  nodes(old_roots_dev), nodes(new_roots_dev), ok_dev);
 }
 
 // ---- multiproofs inside the stored forest (forest_tree_kernels.hpp) ---------------------------------------------------------

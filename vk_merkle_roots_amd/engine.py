@@ -763,6 +763,22 @@ class HipDevice:
     def frontier_extend_scratch(self, total_new, T):
         return self.alloc(self.lib.vkmr_hip_frontier_extend_scratch_bytes(total_new, T))
 
+    def forest_consistency_enqueue(self, digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, roots_buf, trees_buf, old_counts_buf, Q, stride,
+                                   new_counts_out_buf, peaks_out_buf, rights_out_buf, status_buf, stream=None):
+        """The consistency proofs of Q queries (trees_buf uint32, old_counts_buf uint64) out of a stored forest (total, ntrees,
+        max_count: the build's; roots_buf its roots): Q uint64 counts as they are now and two rows of Q x stride digests, every
+        cell written.  status_buf: one uint32, consistency_status_text names its bits; nonzero: nothing written.  All in device
+        memory.  include/vkmr_hip.h."""
+        self._call("vkmr_hip_forest_consistency_async", digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, roots_buf, trees_buf,
+                   old_counts_buf, Q, stride, new_counts_out_buf, peaks_out_buf, rights_out_buf, status_buf, stream=stream)
+
+    def verify_consistency_enqueue(self, old_counts_buf, new_counts_buf, peaks_buf, rights_buf, stride, Q, old_roots_buf, new_roots_buf, ok_buf,
+                                   stream=None):
+        """ok_buf[q] (uint32) = 1 when proof q shows that the tree of new_counts_buf[q] leaves under new_roots_buf[q] extends the
+        one of old_counts_buf[q] leaves under old_roots_buf[q], else 0."""
+        self._call("vkmr_hip_verify_consistency_async", old_counts_buf, new_counts_buf, peaks_buf, rights_buf, stride, Q, old_roots_buf, new_roots_buf,
+                   ok_buf, stream=stream)
+
     def reduce_scratch(self, count, levels_variant=False):
         fn = self.lib.vkmr_hip_reduce_levels_scratch_bytes if levels_variant else self.lib.vkmr_hip_reduce_scratch_bytes
         return self.alloc(fn(count))
@@ -1713,6 +1729,31 @@ class MerkleForest(_Stored):
             return Frontier(self.dev.download(d_counts, 8 * self.ntrees, dtype=np.uint64),
                             self.dev.download(d_peaks, 32 * self.ntrees * stride).reshape(self.ntrees, stride, 8))
 
+    def consistency(self, old_counts, trees=None, stride=None):
+        """The ConsistencyProof that tree trees[q] as it is now extends what it was at old_counts[q] leaves, read out of the
+        stored levels (no hash): what a holder of the old root and of the root now checks (ConsistencyProof.verify) without the
+        leaves between.  trees None: one query per tree, old_counts one per tree; else any trees in any order, as often as
+        wanted.  stride: cells per row, by default that of frontier().  RuntimeError, with consistency_status_text, when the
+        device refuses: a tree outside the forest, an old count above the tree's count (a tree that shrank or was dropped)."""
+        stride = max(1, min(self.max_count, self.total).bit_length()) if stride is None else int(stride)
+        old_counts = np.array(old_counts, dtype=np.uint64).reshape(-1)
+        trees = np.arange(self.ntrees, dtype=np.uint32) if trees is None else np.array(trees, dtype=np.uint32).reshape(-1)
+        Q = int(trees.shape[0])
+        if int(old_counts.shape[0]) != Q:
+            raise ValueError(f"consistency: {int(old_counts.shape[0])} old counts for {Q} queries")
+        if Q == 0:
+            return ConsistencyProof(trees, old_counts, np.zeros(0, np.uint64), np.zeros((0, stride, 8), np.uint32), np.zeros((0, stride, 8), np.uint32))
+        with self.dev.scope() as tmp:
+            d_counts, d_peaks, d_rights, d_status = tmp.alloc(8 * Q), tmp.alloc(32 * Q * stride), tmp.alloc(32 * Q * stride), tmp.alloc(4)
+            self.dev.forest_consistency_enqueue(self.digests, self.forest, self.total, self.offsets, self.ntrees, self.max_count, self.roots_buf,
+                                                tmp.upload(trees), tmp.upload(old_counts), Q, stride, d_counts, d_peaks, d_rights, d_status)
+            status = int(self.dev.download(d_status, 4)[0])
+            if status:
+                raise RuntimeError(f"MerkleForest.consistency: the device refused (status {status}: {consistency_status_text(status)})")
+            return ConsistencyProof(trees, old_counts, self.dev.download(d_counts, 8 * Q, dtype=np.uint64),
+                                    self.dev.download(d_peaks, 32 * Q * stride).reshape(Q, stride, 8),
+                                    self.dev.download(d_rights, 32 * Q * stride).reshape(Q, stride, 8))
+
     def roots(self):
         """[ntrees, 8] uint32: what forest_roots gives for the same leaves (an all-zero root for an empty tree)."""
         return self.dev.download(self.roots_buf, 32 * self.ntrees).reshape(self.ntrees, 8)
@@ -2041,6 +2082,62 @@ class Frontier:
         offsets = self._new_offsets(counts, int(batch.count), "extend_packed")
         with dev.scope() as tmp:
             return self._extend(dev, tmp, dev.map_packed(tmp, batch) if batch.count else None, offsets, "extend_packed")
+
+
+class ConsistencyProof:
+    """Q proofs that a tree only grew (include/vkmr_hip.h, CONSISTENCY PROOFS): query q says that tree `trees[q]`, which has
+    `new_counts[q]` leaves, extends what it was at `old_counts[q]` leaves.  `peaks` (uint32 [Q, stride, 8]) are the peaks of the
+    OLD count, `rights` the right neighbours of the walk from them to the root now; cells the check does not read are zero.
+    Host arrays, as Frontier's; MerkleForest.consistency gathers one, a holder of the two roots verifies it."""
+
+    def __init__(self, trees, old_counts, new_counts, peaks, rights):
+        self.trees = np.array(trees, dtype=np.uint32).reshape(-1)
+        self.old_counts = np.array(old_counts, dtype=np.uint64).reshape(-1)
+        self.new_counts = np.array(new_counts, dtype=np.uint64).reshape(-1)
+        Q = int(self.trees.shape[0])
+        self.peaks, self.rights = (np.array(x, dtype=np.uint32) for x in (peaks, rights))
+        if (self.old_counts.shape[0] != Q or self.new_counts.shape[0] != Q or self.peaks.ndim != 3 or self.peaks.shape != self.rights.shape
+                or self.peaks.shape[0] != Q or self.peaks.shape[2] != 8 or not 1 <= self.stride <= 64):
+            raise ValueError("ConsistencyProof: one tree, old count and new count per query; peaks and rights [Q, stride, 8] with stride in 1..64")
+
+    Q = property(lambda self: int(self.trees.shape[0]))
+    stride = property(lambda self: int(self.peaks.shape[1]))
+
+    def same_as(self, other):
+        """Byte for byte: equal queries, counts and cells, the zero ones included."""
+        mine, theirs = ((p.trees, p.old_counts, p.new_counts, p.peaks, p.rights) for p in (self, other))
+        return all(a.shape == b.shape and bool((a == b).all()) for a, b in zip(mine, theirs))
+
+    def frontier(self):
+        """Frontier(old_counts, peaks): frontier().roots(dev) is the root every queried tree had at its old count, and a
+        follower that fell behind adopts it under the old root it trusts and goes on with Frontier.extend."""
+        return Frontier(self.old_counts, self.peaks)
+
+    def verify(self, dev, old_roots, new_roots):
+        """uint32 [Q]: 1 where proof q holds under old_roots[q] and new_roots[q] ([Q, 8] each, per QUERY: the caller indexes
+        its own root tables by `trees`), else 0."""
+        Q = self.Q
+        if Q == 0:
+            return np.zeros(0, np.uint32)
+        with dev.scope() as tmp:
+            d_ok = tmp.alloc(4 * Q)
+            dev.verify_consistency_enqueue(tmp.upload(self.old_counts), tmp.upload(self.new_counts), tmp.upload(self.peaks), tmp.upload(self.rights),
+                                           self.stride, Q, tmp.upload(_host(old_roots, np.uint32, Q, 8)), tmp.upload(_host(new_roots, np.uint32, Q, 8)), d_ok)
+            return dev.download(d_ok, 4 * Q)
+
+
+def consistency_status_text(status):
+    """The bits of vkmr_hip_forest_consistency_async's status word, named."""
+    names = []
+    if status & 1:
+        names.append("bit 0: a tree index outside the forest")
+    if status & 2:
+        names.append("bit 1: an old count above the count the tree has now")
+    if status & 4:
+        names.append("bit 2: a tree's count has more bits than a row has cells")
+    if status & ~7:
+        names.append("unknown bits")
+    return "; ".join(names) if names else "ok"
 
 
 def frontier_status_text(status):
