@@ -1099,7 +1099,7 @@ VKMR_API vkmr_status vkmr_hip_frontier_extend_async(int dev, vkmr_stream s, cons
  * The peaks row with the old counts IS a frontier: vkmr_hip_frontier_roots_async over it names every tree's root as of its old
  * count again, and a follower that fell behind adopts it under the old root it trusts and goes on with
  * vkmr_hip_frontier_extend_async.  vkmr_host_cpu_forest_consistency and vkmr_host_cpu_verify_consistency (libvkmr_host.so)
- * apply the same rules on the CPU.  Not offered: inclusion proofs as of an earlier count.
+ * apply the same rules on the CPU.  Inclusion proofs as of an earlier count: vkmr_hip_forest_proofs_at_async, below.
  */
 VKMR_API vkmr_status vkmr_hip_forest_consistency_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* forest_dev,
                                                        uint64_t total, const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count,
@@ -1109,6 +1109,53 @@ VKMR_API vkmr_status vkmr_hip_forest_consistency_async(int dev, vkmr_stream s, c
 VKMR_API vkmr_status vkmr_hip_verify_consistency_async(int dev, vkmr_stream s, const uint64_t* old_counts_dev, const uint64_t* new_counts_dev,
                                                        const vkmr_digest* peaks_dev, const vkmr_digest* rights_dev, uint32_t stride, uint32_t Q,
                                                        const vkmr_digest* old_roots_dev, const vkmr_digest* new_roots_dev, uint32_t* ok_dev);
+
+/*
+ * INCLUSION PROOFS AS OF AN EARLIER COUNT: "LEAF i WAS IN THE TREE I TRUSTED".  The other half of the append-only pair for a log
+ * that serves checkpoints: a client holds the root tree t had at c leaves and asks for the proof of leaf i < c under THAT root,
+ * while the tree has grown to c2 >= c leaves.  An EPOCH is (tree, old count); a log serves many queries at few epochs.  With the
+ * notation of the two blocks above, l0 the lowest set bit of c >= 1:
+ *   a node s of level l of the old tree with (s + 1) << l <= c is COMPLETE: no later leaf changes it, so it is node s of level l
+ *   of the new tree -- a leaf, cell (offsets[t] >> l) + t + s of stored level l, or roots_dev[t] where the level has one node;
+ *   a level l0 < l <= H(c) of the old tree has one other node, its last: E_l = node_hash(P_(l-1), E_(l-1)) where bit l - 1 of c
+ *   is set (E_(l-1) replaced by P_(l-1) itself for l - 1 == l0), else node_hash(E_(l-1), E_(l-1)) -- the carry of the frontier's
+ *   root walk, the peaks P_l read from the new tree as the consistency gather reads them;
+ *   the old root is E_H(c); for c a power of two of at least 2 it is node 0 of level H(c) of the new tree, without a hash; for
+ *   c == 1 it is node_hash(leaf, leaf).  H(c) - l0 node hashes an epoch (none for a power of two), NONE per query.
+ * The proof of leaf i < c has H(c) cells: cell l is node s = j ^ 1 of the old tree's level l for j = i >> l, or j itself where
+ * j ^ 1 >= ceil(c / 2^l) -- the stored node when complete, else E_l.
+ *
+ * vkmr_hip_forest_proofs_at_async: the stored forest as vkmr_hip_forest_consistency_async takes it (digests_dev .. roots_dev).
+ *   epoch_trees_dev, epoch_counts_dev   E epochs (uint32 tree, uint64 old count) in device memory, CHECKED there
+ *   epochs_dev, indices_dev    k queries: leaf indices_dev[q] (uint64) as of epoch epochs_dev[q] (uint32)
+ *   edges_out_dev              E x stride digests: cell l of epoch e is E_l for l0 < l < H(c) when the epoch hashes, every other
+ *                              cell zero; EVERY cell is written
+ *   old_roots_out_dev          E digests: the root of epoch e's tree as of its count; all zero for c == 0
+ *   siblings_dev, heights_dev  k x stride digests and k uint32: heights_dev[q] = H(c), cells l < H(c) as above, cells above zero.
+ *                              A query with epochs_dev[q] >= E or indices_dev[q] >= c -- every query into an epoch of c == 0 --
+ *                              gets height 0 and zero cells: vkmr_hip_forest_proofs_async's rule for a bad index, not a status bit
+ *   status_dev                 one uint32_t, always written: 0 when done, else the bits of vkmr_hip_forest_consistency_async
+ *                              over the epochs: bit 0 (1) a tree index >= ntrees; bit 1 (2) an old count above the tree's count
+ *                              now; bit 2 (4) a current count of more bits than stride.  When it is nonzero NOTHING of the
+ *                              caller's is written: no edge, no root, no proof, no height.
+ * VERIFYING.  There is no new verifier: the output is exactly what vkmr_hip_verify_forest_proofs_async takes with
+ * trees_dev := epochs_dev, roots_dev := old_roots_out_dev (or the roots the client trusts, in the order of the epochs) and
+ * ntrees := E; on the CPU every proof folds with vkmr_host_cpu_fold_proof.
+ * Launches, all on the caller's stream: the status word zeroed, one check (a lane per epoch), one edge launch (a lane per epoch,
+ * the hashes of its right edge through one node hash), one gather (a lane per (query, level): one load, from the stored forest
+ * or from the edge row, and one store; no hash); never a launch per tree, epoch or query, no allocation, no scratch to size, no
+ * host read of device data.  Refused on the host (VKMR_ERR_INVALID), before any HIP call: a NULL pointer (the four query buffers
+ * may be NULL when k == 0), stride outside 1..63 (the verifier's range), and what vkmr_hip_forest_consistency_async refuses of
+ * the forest.  E == 0 does nothing.  k == 0 with E > 0 is valid: the edges and the old roots alone, "the root of tree t as of
+ * count c".  vkmr_host_cpu_forest_proofs_at (libvkmr_host.so) applies the same rules on the CPU.  Not offered: multiproofs as of
+ * an earlier count.
+ */
+VKMR_API vkmr_status vkmr_hip_forest_proofs_at_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* forest_dev,
+                                                     uint64_t total, const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count,
+                                                     const vkmr_digest* roots_dev, const uint32_t* epoch_trees_dev, const uint64_t* epoch_counts_dev,
+                                                     uint32_t E, const uint32_t* epochs_dev, const uint64_t* indices_dev, uint32_t k, uint32_t stride,
+                                                     vkmr_digest* edges_out_dev, vkmr_digest* old_roots_out_dev, vkmr_digest* siblings_dev,
+                                                     uint32_t* heights_dev, uint32_t* status_dev);
 
 /*
  * COMBINE: duplicate-last Merkle root over n >= 1 slice roots given in slice order, always

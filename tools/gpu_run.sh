@@ -29,6 +29,9 @@
 #                          extend and the reduction of all the leaves (one JSON line)
 #   consistency [args]     tools/consistency_timing.py: consistency proofs gathered from a stored forest and checked by a holder of two roots
 #                          (2^15 trees of 2 048; one tree of 2^26 at Q = 1 and 2^16), beside verify_frontier and the follower's extend (one JSON line)
+#   proofs_at [args]       tools/proofs_at_timing.py: inclusion proofs as of an earlier count out of a stored forest (2^15 trees of 2 048 with 32
+#                          queries an epoch; one tree of 2^26 - 2^16 at E = 1, k = 2^20 and at E = k = 2^16), beside what they replace: a second
+#                          stored forest built from the prefix leaves plus its proof gather (one JSON line)
 #   forest_repack [args]   tools/forest_repack_timing.py: the oldest trees of a stored forest dropped and the rest (or all) copied into an
 #                          empty forest, beside the stored build over the same leaves (one JSON line)
 #   cumask                 tools/cu_mask_probe.py: where CU-mask bits land, map/reduce on half the CUs with and without neighbours
@@ -210,6 +213,11 @@ consistency)
   timeout -k 10 500 python3 tools/consistency_timing.py "$@" --out $OUT/consistency_timing.json > /dev/null 2> $OUT/consistency_timing.err && echo "consistency_timing ok" &&
   cat $OUT/consistency_timing.json
   echo "consistency rc=$?"
+  ;;
+proofs_at)
+  timeout -k 10 500 python3 tools/proofs_at_timing.py "$@" --out $OUT/proofs_at_timing.json > /dev/null 2> $OUT/proofs_at_timing.err && echo "proofs_at_timing ok" &&
+  cat $OUT/proofs_at_timing.json
+  echo "proofs_at rc=$?"
   ;;
 forest_repack)
   timeout -k 10 500 python3 tools/forest_repack_timing.py "$@" --out $OUT/forest_repack_timing.json > /dev/null 2> $OUT/forest_repack_timing.err && echo "forest_repack_timing ok" &&

@@ -10,6 +10,7 @@
 #include "../consistency_plan.hpp"
 #include "../frontier_plan.hpp"
 #include "../merkle_math.hpp"
+#include "../proofs_at_plan.hpp"
 #include "cpu_sha256d.hpp"
 #include "vkmr_hip.h"
 
@@ -905,6 +906,77 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_verify_consistency(cons
             acc = next;
         }
         ok[q] = std::memcmp(acc.data, new_roots[q].data, 32) == 0 ? 1u : 0u;
+    }
+    return 0;
+}
+
+// ---- inclusion proofs as of an earlier count (proofs_at_plan.hpp; vkmr_hip_forest_proofs_at_async) for a log without a GPU.
+// As the consistency gather above, there is no stored forest: every level of a tree that has an epoch is built from its leaves
+// as they are NOW, the complete nodes are taken out of them and the old tree's right edge is hashed by the plan's edge_step().
+
+// E epochs (epoch_trees[e], epoch_counts[e]) over the trees of a forest given by its leaves, and k queries (epochs[q],
+// indices[q]): edges_out (E x stride), old_roots_out (E), siblings (k x stride) and heights (k), every cell written.  Returns
+// the status word of vkmr_hip_forest_proofs_at_async (0: done; nonzero: nothing written), or -1 for a missing pointer, a stride
+// outside 1..63 or offsets that decrease.
+__attribute__((visibility("default"))) int vkmr_host_cpu_forest_proofs_at(const vkmr_digest* digests, const uint64_t* offsets, uint32_t ntrees,
+                                                                           const uint32_t* epoch_trees, const uint64_t* epoch_counts, uint32_t E,
+                                                                           const uint32_t* epochs, const uint64_t* indices, uint32_t k, uint32_t stride,
+                                                                           vkmr_digest* edges_out, vkmr_digest* old_roots_out, vkmr_digest* siblings,
+                                                                           uint32_t* heights)
+{
+    if (E == 0) return 0;
+    if (!offsets || !epoch_trees || !epoch_counts || !edges_out || !old_roots_out || stride == 0 || stride > 63) return -1;
+    if (k > 0 && (!epochs || !indices || !siblings || !heights)) return -1;
+    for (uint32_t t = 0; t < ntrees; ++t)
+        if (offsets[t + 1] < offsets[t]) return -1;
+    if (!digests && ntrees > 0 && offsets[ntrees] > offsets[0]) return -1;
+    uint32_t status = 0;
+    for (uint32_t e = 0; e < E; ++e) status |= vkmr_proofs_at::refusal(epoch_trees[e], ntrees, offsets, epoch_counts[e], stride);
+    if (status) return (int)status;
+    // the levels of every tree that has an epoch, built once
+    std::vector<std::vector<std::vector<vkmr_digest>>> levels(ntrees);
+    for (uint32_t e = 0; e < E; ++e) {
+        const uint32_t t = epoch_trees[e];
+        const uint64_t c2 = offsets[t + 1] - offsets[t];
+        if (epoch_counts[e] == 0 || !levels[t].empty()) continue;
+        levels[t].assign(1, std::vector<vkmr_digest>(digests + offsets[t], digests + offsets[t + 1]));
+        for (uint32_t l = 0; l < vkmr_math::height(c2); ++l) {
+            const std::vector<vkmr_digest>& in = levels[t][l];
+            std::vector<vkmr_digest> out((in.size() + 1) / 2);
+            for (uint64_t j = 0; j < out.size(); ++j) vkmr::cpu_sha256d_pair(in[2 * j].data, in[vkmr_math::right_child(j, in.size())].data, out[j].data);
+            levels[t].push_back(std::move(out));
+        }
+    }
+    std::memset(edges_out, 0, sizeof(vkmr_digest) * (size_t)E * stride);
+    std::memset(old_roots_out, 0, sizeof(vkmr_digest) * (size_t)E);
+    for (uint32_t e = 0; e < E; ++e) {
+        const uint32_t t = epoch_trees[e];
+        const uint64_t c = epoch_counts[e];
+        vkmr_digest carry = {};
+        bool have = false;
+        for (uint32_t l = 0; l < vkmr_proofs_at::levels(c); ++l) {
+            const vkmr_proofs_at::EdgeStep s = vkmr_proofs_at::edge_step(c, l, have);
+            vkmr_digest* dst = s.to_root ? old_roots_out + e : edges_out + (size_t)e * stride + (l + 1);
+            if (s.stored) *dst = levels[t][l + 1][0];
+            if (!s.hash) continue;
+            const vkmr_digest a = s.peak ? levels[t][l][vkmr_proofs_at::peak_node(c, l)] : carry;
+            const vkmr_digest b = s.twice ? a : carry;
+            vkmr::cpu_sha256d_pair(a.data, b.data, carry.data);
+            have = true;
+            *dst = carry;
+        }
+    }
+    for (uint32_t q = 0; q < k; ++q) {
+        vkmr_digest* mine = siblings + (size_t)q * stride;
+        std::memset(mine, 0, sizeof(vkmr_digest) * stride);
+        heights[q] = 0;
+        const uint32_t e = epochs[q];
+        if (e >= E || indices[q] >= epoch_counts[e]) continue;
+        const uint64_t c = epoch_counts[e], i = indices[q];
+        heights[q] = vkmr_proofs_at::height(c);
+        for (uint32_t l = 0; l < heights[q]; ++l)
+            mine[l] = vkmr_proofs_at::cell_source(c, l, i) == vkmr_proofs_at::CELL_STORED ? levels[epoch_trees[e]][l][vkmr_proofs_at::sibling(c, l, i)]
+                                                                                          : edges_out[(size_t)e * stride + l];
     }
     return 0;
 }

@@ -29,6 +29,9 @@
 //   consistency_kernels.hpp  consistency_*_kernel   consistency proofs: the peaks of an earlier count and the right neighbours of
 //                                              the walk from them to the root gathered from a stored forest (no hash), and the
 //                                              verifier's two root walks, one lane per query (rules: consistency_plan.hpp)
+//   proofs_at_kernels.hpp  proofs_at_*_kernel   inclusion proofs as of an earlier count: the old tree's right edge hashed once per
+//                                              epoch (one lane each, one hash_pair), then a gather without a hash, one lane per
+//                                              (query, level) (rules: proofs_at_plan.hpp)
 //   forest_tree_kernels.hpp  forest_proofs_kernel          proofs gathered from the stored forest, one lane per (query, level)
 //                            verify_forest_proofs_kernel   batch verification of proofs of unequal height, one lane per proof
 //                            forest_update_*_kernel        leaf updates of the stored forest: tree_update_*'s bodies, a tree per entry
@@ -96,6 +99,7 @@ using vkmr_dev::Node;
 #include "audit_kernels.hpp"
 #include "frontier_kernels.hpp"
 #include "consistency_kernels.hpp"
+#include "proofs_at_kernels.hpp"
 
 // ============================================================================
 // C ABI
@@ -1460,6 +1464,35 @@ vkmr_status vkmr_hip_verify_consistency_async(int dev, vkmr_stream s, const uint
     VKMR_TRY(hipSetDevice(dev));
     return launch(consistency_fold_kernel, grid_of(Q), dim3(256), S(s), old_counts_dev, new_counts_dev, nodes(peaks_dev), nodes(rights_dev), stride, Q,
                   nodes(old_roots_dev), nodes(new_roots_dev), ok_dev);
+}
+
+// ---- inclusion proofs as of an earlier count (proofs_at_kernels.hpp, proofs_at_plan.hpp) ---------------------------------------
+
+vkmr_status vkmr_hip_forest_proofs_at_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* forest_dev, uint64_t total,
+                                            const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count, const vkmr_digest* roots_dev,
+                                            const uint32_t* epoch_trees_dev, const uint64_t* epoch_counts_dev, uint32_t E, const uint32_t* epochs_dev,
+                                            const uint64_t* indices_dev, uint32_t k, uint32_t stride, vkmr_digest* edges_out_dev,
+                                            vkmr_digest* old_roots_out_dev, vkmr_digest* siblings_dev, uint32_t* heights_dev, uint32_t* status_dev)
+{
+    if (E == 0) return VKMR_OK;
+    if ((!digests_dev && total > 0) || !forest_dev || !offsets_dev || !roots_dev || !epoch_trees_dev || !epoch_counts_dev || !edges_out_dev ||
+        !old_roots_out_dev || !status_dev || (k > 0 && (!epochs_dev || !indices_dev || !siblings_dev || !heights_dev)))
+        return refuse(__func__, "null pointer");
+    VKMR_CHECK(forest_args_check(__func__, total, ntrees, max_count, 0, nullptr, nullptr));
+    if (stride == 0 || stride > 63) return refuse(__func__, "stride must be 1..63");
+    VKMR_CHECK(frontier_args_check(__func__, stride, E));
+    if (grid_too_large(groups_of((uint64_t)k * stride))) return refuse(__func__, "too many proofs in one call");
+    if (vkmr_frontier::bit_length(max_count < total ? max_count : total) > stride) return refuse(__func__, "a tree of max_count leaves has more bits than stride");
+    const ForestLevels lv = forest_levels(total, ntrees, vkmr_forest::launches(total, max_count));
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_TRY(hipMemsetAsync(status_dev, 0, sizeof(uint32_t), S(s)));
+    VKMR_CHECK(launch(proofs_at_check_kernel, grid_of(E), dim3(256), S(s), offsets_dev, ntrees, epoch_trees_dev, epoch_counts_dev, E, stride, status_dev));
+    VKMR_CHECK(launch(proofs_at_edge_kernel, grid_of(E), dim3(256), S(s), nodes(digests_dev), nodes(forest_dev), lv, offsets_dev, nodes(roots_dev),
+                      epoch_trees_dev, epoch_counts_dev, E, stride, nodes(edges_out_dev), nodes(old_roots_out_dev), status_dev));
+    if (k == 0) return VKMR_OK;                  // the edges and the old roots alone: the root of tree t as of count c
+    return launch(proofs_at_gather_kernel, grid_of((uint64_t)k * stride), dim3(256), S(s), nodes(digests_dev), nodes(forest_dev), lv, offsets_dev,
+                  nodes(roots_dev), epoch_trees_dev, epoch_counts_dev, E, epochs_dev, indices_dev, k, stride, nodes(edges_out_dev), nodes(siblings_dev),
+                  heights_dev, status_dev);
 }
 
 // ---- multiproofs inside the stored forest (forest_tree_kernels.hpp) ---------------------------------------------------------

@@ -779,6 +779,18 @@ class HipDevice:
         self._call("vkmr_hip_verify_consistency_async", old_counts_buf, new_counts_buf, peaks_buf, rights_buf, stride, Q, old_roots_buf, new_roots_buf,
                    ok_buf, stream=stream)
 
+    def forest_proofs_at_enqueue(self, digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, roots_buf, epoch_trees_buf, epoch_counts_buf, E,
+                                 epochs_buf, indices_buf, k, stride, edges_out_buf, old_roots_out_buf, siblings_buf, heights_buf, status_buf, stream=None):
+        """Inclusion proofs as of an earlier count out of a stored forest (total, ntrees, max_count: the build's; roots_buf its
+        roots): E epochs (epoch_trees_buf uint32, epoch_counts_buf uint64) and k queries (epochs_buf uint32, indices_buf
+        uint64) give E x stride edge cells, E old roots, k x stride sibling cells and k heights, every cell written; k == 0 (the
+        four query buffers may be None): the edges and the old roots alone.  status_buf: one uint32,
+        consistency_status_text names its bits; nonzero: nothing written.  What comes out is what verify_forest_proofs_async
+        takes with the epochs as trees and the old roots as roots.  All in device memory.  include/vkmr_hip.h."""
+        self._call("vkmr_hip_forest_proofs_at_async", digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, roots_buf, epoch_trees_buf,
+                   epoch_counts_buf, E, epochs_buf, indices_buf, k, stride, edges_out_buf, old_roots_out_buf, siblings_buf, heights_buf, status_buf,
+                   stream=stream)
+
     def reduce_scratch(self, count, levels_variant=False):
         fn = self.lib.vkmr_hip_reduce_levels_scratch_bytes if levels_variant else self.lib.vkmr_hip_reduce_scratch_bytes
         return self.alloc(fn(count))
@@ -1753,6 +1765,46 @@ class MerkleForest(_Stored):
             return ConsistencyProof(trees, old_counts, self.dev.download(d_counts, 8 * Q, dtype=np.uint64),
                                     self.dev.download(d_peaks, 32 * Q * stride).reshape(Q, stride, 8),
                                     self.dev.download(d_rights, 32 * Q * stride).reshape(Q, stride, 8))
+
+    def proofs_at(self, old_counts, epochs, indices, trees=None, stride=None):
+        """(siblings [k, stride, 8], heights [k], old_roots [E, 8]): the proof of leaf indices[q] of epoch epochs[q] under the
+        root that epoch's tree had at old_counts[epoch] leaves, out of the levels stored now; the right edge of every old tree
+        is hashed once per epoch, a query hashes nothing.  trees None: one epoch per tree, so an epoch's number is its tree's,
+        as in consistency(); else epoch e is tree trees[e] as of old_counts[e], any trees as often as wanted.  heights[q] is
+        the old tree's height; a query into an epoch outside the list or with an index at or above its old count gets height 0
+        and zero cells.  stride: cells per proof, by default that of frontier().  Verified by
+        HipDevice.verify_forest_proofs(leaves, epochs, indices, siblings, heights, old_roots) -- or under the roots the asker
+        holds in place of old_roots.  RuntimeError, with consistency_status_text, when the device refuses: a tree outside the
+        forest, an old count above the tree's count (a tree that shrank or was dropped)."""
+        stride = max(1, min(self.max_count, self.total).bit_length()) if stride is None else int(stride)
+        old_counts = np.array(old_counts, dtype=np.uint64).reshape(-1)
+        trees = np.arange(self.ntrees, dtype=np.uint32) if trees is None else np.array(trees, dtype=np.uint32).reshape(-1)
+        epochs, indices = np.array(epochs, dtype=np.uint32).reshape(-1), np.array(indices, dtype=np.uint64).reshape(-1)
+        E, k = int(trees.shape[0]), int(epochs.shape[0])
+        if int(old_counts.shape[0]) != E:
+            raise ValueError(f"proofs_at: {int(old_counts.shape[0])} old counts for {E} epochs")
+        if int(indices.shape[0]) != k:
+            raise ValueError("proofs_at: one epoch per index")
+        if E == 0:
+            return np.zeros((k, stride, 8), np.uint32), np.zeros(k, np.uint32), np.zeros((0, 8), np.uint32)
+        with self.dev.scope() as tmp:
+            d_edges, d_roots, d_status = tmp.alloc(32 * E * stride), tmp.alloc(32 * E), tmp.alloc(4)
+            d_sib, d_heights = (tmp.alloc(32 * k * stride), tmp.alloc(4 * k)) if k else (None, None)
+            self.dev.forest_proofs_at_enqueue(self.digests, self.forest, self.total, self.offsets, self.ntrees, self.max_count, self.roots_buf,
+                                              tmp.upload(trees), tmp.upload(old_counts), E, tmp.upload(epochs) if k else None,
+                                              tmp.upload(indices) if k else None, k, stride, d_edges, d_roots, d_sib, d_heights, d_status)
+            status = int(self.dev.download(d_status, 4)[0])
+            if status:
+                raise RuntimeError(f"MerkleForest.proofs_at: the device refused (status {status}: {consistency_status_text(status)})")
+            old_roots = self.dev.download(d_roots, 32 * E).reshape(E, 8)
+            if k == 0:
+                return np.zeros((0, stride, 8), np.uint32), np.zeros(0, np.uint32), old_roots
+            return self.dev.download(d_sib, 32 * k * stride).reshape(k, stride, 8), self.dev.download(d_heights, 4 * k), old_roots
+
+    def roots_at(self, old_counts, trees=None):
+        """[E, 8] uint32: the root tree trees[e] had at old_counts[e] leaves (all zero for a count of 0), from the levels stored
+        now: proofs_at without a query.  trees None: one count per tree."""
+        return self.proofs_at(old_counts, [], [], trees=trees)[2]
 
     def roots(self):
         """[ntrees, 8] uint32: what forest_roots gives for the same leaves (an all-zero root for an empty tree)."""
