@@ -16,6 +16,7 @@ import forest_multiproof_cases as fm
 import forest_mutation_cases as fmu
 import forest_proof_cases as fp
 import frontier_cases as fr
+import high_cases as hc
 from merkle_model import fold, stored_level_base
 from no_device import NoDevice, NoDeviceAt
 
@@ -199,3 +200,72 @@ def test_a_dropped_tree_is_never_the_open_tree(native):
     model = fl.ModelForest(4, 20, 9, [np.ones((3, 8), np.uint32), np.ones((4, 8), np.uint32)])
     model.drop_front(2)
     assert model.open_tree is None and model.books()["dropped_leaves"] == 7 and model.offsets().tolist() == [7, 7, 7, 7, 7]
+
+
+# ---- the walks above 4 GiB (tests/high_cases.py): the placements do what they are for ---------------------------------------------
+
+def test_the_walks_are_the_four_of_the_issue():
+    assert hc.HIGH_WALKS == [(0, "roomy", 7), (0, "tight", 1), (1, "roomy", 7), (3, "roomy", 4)]
+
+
+@pytest.mark.parametrize("level,name,seed", hc.HIGH_WALKS)
+def test_the_high_walks_straddle_the_line_in_most_steps_and_in_every_kind(level, name, seed):
+    steps, kinds = hc.straddling_steps(name, seed, level)
+    print("straddling steps", (level, name, seed), steps)
+    assert steps >= 60 and [k for k in fl.KINDS if k not in kinds] == []
+
+
+def test_a_shift_is_the_smallest_that_puts_the_line_at_a_quarter_of_the_window():
+    for name, config in fl.CONFIGS.items():
+        total, ntrees = config.cells, config.trees
+        assert hc.shift_for(0, total, ntrees) == 2**27 - total // 4
+        for level in (1, 2, 3):
+            D = hc.shift_for(level, total, ntrees)
+            at = lambda d: stored_level_base(total + d, ntrees, level) + ((d + total // 4) >> level) + ntrees // 2
+            assert at(D) >= 2**27 > at(D - 1), (name, level, D)
+            assert D % (1 << (level + 4)), (name, level, D)          # not rounded to the levels above: (offset >> l) does not commute with it
+            # the whole forest fits 72 GiB four times over: level 0 and the level buffers, 32 bytes a cell
+            assert 4 * 32 * (D + total + stored_level_base(D + total, ntrees, 8)) <= 72 * 2**30
+
+
+def test_a_view_at_shift_0_is_the_model_and_a_shifted_one_moves_the_cells_alone():
+    life = fl.Life(7, fl.CONFIGS["roomy"])
+    for number, kind, p in life.steps():
+        life.apply(kind, p)
+        m, same, high = life.a, hc.Shifted(life.a), hc.Shifted(life.a, 1)
+        assert same.D == 0 and same.books() == m.books() and (same.offsets() == m.offsets()).all() and same.levels == m.levels
+        assert all((x == y).all() for x, y in zip(same.nodes(), m.nodes())) and (same.live_cells() == m.live_cells()).all()
+        D = high.D
+        assert D == hc.shift_for(1, m.total, m.ntrees) and high.total == m.total + D and high.levels == 7
+        books = high.books()
+        assert (books["dropped_leaves"], books["used_leaves"], books["free_leaves"]) == (m.dropped_leaves + D, m.used_leaves + D, m.free_leaves)
+        assert (high.offsets() == m.offsets() + np.uint64(D)).all() and (high.live_cells() == m.live_cells() + D).all()
+        cells, digests, levels = high.nodes(with_levels=True)
+        assert (digests == m.nodes()[1]).all() and cells.shape[0] == m.nodes()[0].shape[0]
+        assert cells.shape[0] == 0 or cells.max() < stored_level_base(high.total, m.ntrees, high.levels + 1)
+        if number % 16 == 0:
+            trees, indices = life.entry_set()
+            sib, heights = high.proofs(trees, indices)
+            want = m.proofs(trees, indices)
+            assert sib.shape[1] == high.levels and (sib[:, : m.levels] == want[0]).all() and not sib[:, m.levels:].any() and (heights == want[1]).all()
+
+
+def test_a_handle_laid_into_a_larger_buffer_keeps_its_books_from_the_front(native):
+    import vk_merkle_roots_amd as vk
+    D = 2**27 - 15
+    f = vk.MerkleForest(NoDevice(), None, D + 60, [4, 0, 9, 0, 0], None, 9, None, None, used_trees=3, front=D)
+    assert (f.dropped_trees, f.dropped_leaves, f.used_leaves, f.live_leaves, f.free_leaves, f.free_trees) == (0, D, D + 13, 13, 47, 2)
+    assert f.open_tree == 2 and f.levels == 4 and f.total == D + 60
+    cells, counts = f._entry_cells(np.array([0, 2, 2], dtype=np.uint32), np.array([3, 0, 8], dtype=np.uint64))
+    assert cells.tolist() == [D + 3, D + 4, D + 12] and counts.tolist() == [4, 9, 9]
+    model = fl.ModelForest(5, 60, 9, [np.ones((4, 8), np.uint32), np.zeros((0, 8), np.uint32), np.ones((9, 8), np.uint32)])
+    view = hc.Shifted(model, 0)
+    assert view.D == D and all((getattr(f, k).tolist() if k == "counts" else getattr(f, k)) == v for k, v in view.books().items())
+    high, low = (vk.MerkleForest(NoDeviceAt(0), None, D + 60, [4, 0, 9, 0, 0], None, 9, None, None, used_trees=3, front=d) for d in (D, 0))
+    assert low.dropped_leaves == 0 and low.free_leaves == D + 47
+    for call in (lambda: high.diff(low), lambda: low.sync_from(high)):   # the same counts at another place are another shape
+        with pytest.raises(ValueError, match="dropped in front"):
+            call()
+    for front in (-1, D + 61):
+        with pytest.raises(ValueError, match="in front of the first tree"):
+            vk.MerkleForest(NoDevice(), None, D + 60, [4, 0, 9, 0, 0], None, 9, None, None, used_trees=3, front=front)

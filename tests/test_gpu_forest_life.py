@@ -4,12 +4,19 @@ result with another: the handle's books, the offsets, the roots, every live cell
 and its count, the masks, the proofs of every live leaf, find, a multiproof, the frontier.  Beside the forest under test (A) walk
 its twin (B: the structural steps alone, so that diff and sync_from always have the same shape in front of them), a follower that
 holds only the roots and one that holds only a Frontier.  Every fourth step one call that must be refused, and is, without a
-trace.  A failure prints (config, seed, step, kind, parameters): the walk can be replayed on the model alone."""
+trace.  A failure prints (config, seed, step, kind, parameters): the walk can be replayed on the model alone.
+
+The same walks above 4 GiB (test_the_walk_above_4_gib): the forests laid into large, mostly untouched buffers so that the live
+cells of one level straddle cell 2^27 -- byte 2^32 -- of that level's buffer (tests/high_cases.py).  Every helper here takes the
+model as a high_cases.Shifted view (level None: the forest where it is) and reads cells through high_cases.read_cells, so the
+low and the high walks make the same checks against the same model; the high ones also find their canaries intact after every
+step, looked at before anything else so that a store that lost its upper bits is named by where it landed."""
 import numpy as np
 import pytest
 
 import forest_life_cases as fl
 import forest_multiproof_cases as fm
+import high_cases as hc
 from merkle_model import stored_level_base
 
 pytestmark = pytest.mark.gpu
@@ -29,37 +36,30 @@ def batch_of(vk, strings):
     return vk.pack_lines(b"".join(s + b"\n" for s in strings))
 
 
-def built(gpu, model):
-    """build_forest of a model that has dropped nothing yet."""
+def built(gpu, model, level=None):
+    """build_forest of a model that has dropped nothing yet; with a level, the same forest built at that placement's shift."""
     assert model.dropped_trees == 0
+    if level is not None:
+        return hc.build(gpu, hc.Shifted(model, level))
     leaves = np.concatenate(model.trees + [np.zeros((0, 8), dtype=np.uint32)])
     return gpu.build_forest(leaves, model.counts[: model.used_trees], max_count=model.max_count, reserve_trees=model.free_trees,
                             reserve_leaves=model.free_leaves)
 
 
-def level_0(gpu, forest):
-    return gpu.download(forest.digests, 32 * forest.total).reshape(-1, 8)
-
-
-def level_buffers(gpu, forest):
-    nbytes = gpu.forest_tree_bytes(forest.total, forest.ntrees, forest.max_count)
-    return gpu.download(forest.forest, nbytes).reshape(-1, 8)
-
-
 def state_equals_model(gpu, forest, m):
-    """Checks 2 - 4: the offsets, the roots, every live leaf and every live node at the model's cell."""
+    """Checks 2 - 4: the offsets, the roots, every live leaf and every live node at the model's cell (m: a Shifted view).  A
+    forest with canaries has them looked at first: a store that lost its upper bits is then named by where it landed."""
+    assert hc.canaries_intact(gpu, getattr(forest, "canaries", ()))
     assert (gpu.download(forest.offsets, 8 * (m.ntrees + 1), dtype=np.uint64) == m.offsets()).all(), "offsets"
     assert (forest.roots() == m.roots()).all(), "roots"
-    live = m.live_cells()
-    assert (level_0(gpu, forest)[live] == m.image[live]).all(), "level 0"
-    buffers = level_buffers(gpu, forest)
-    assert buffers.shape[0] == stored_level_base(m.total, m.ntrees, m.levels + 1)
+    assert (hc.read_cells(gpu, forest.digests, m.live_cells()) == m.image[m.local_live_cells()]).all(), "level 0"
+    assert gpu.forest_tree_bytes(forest.total, forest.ntrees, forest.max_count) == 32 * stored_level_base(m.total, m.ntrees, m.levels + 1)
     cells, digests = m.nodes()
-    assert (buffers[cells] == digests).all(), "the level buffers"
+    assert (hc.read_cells(gpu, forest.forest, cells) == digests).all(), "the level buffers"
 
 
-def everything_equals_model(gpu, vk, forest, life):
-    m = life.a
+def everything_equals_model(gpu, vk, forest, life, level=None):
+    m = hc.Shifted(life.a, level)
     roots = m.roots()
     # 1: the books
     for name, want in m.books().items():
@@ -109,30 +109,35 @@ def everything_equals_model(gpu, vk, forest, life):
     return frontier
 
 
-def refused_call(gpu, forest, life, number):
+def refused_call(gpu, forest, life, number, level=None):
     """One call that must be refused, in turn: an update of a leaf that is none through the handle, the same entry through the
     raw call, a raw extend with a wrong count, a diff against a fresh build of the same counts that has no dropped front (its
-    trees lie at other offsets).  Each is a refusal the device or the handle documents; none touches anything."""
-    m = life.a
+    trees lie at other offsets; above the line it is built at the forest's own shift).  Each is a refusal the device or the
+    handle documents; none touches anything."""
+    m = hc.Shifted(life.a, level)
     tree, index = (0, 0) if m.dropped_trees else (0, m.counts[0])        # a dropped tree, or index == count
     leaf = life.ask.integers(0, 2**32, size=(1, 8), dtype=np.uint32)
     which = (number // 4) % 4
-    if which == 3 and m.dropped_leaves == 0:
+    if which == 3 and m.local.dropped_leaves == 0:
         which = 0                                                        # nothing dropped in front: a fresh build lies where the forest lies
     last = m.used_trees - 1
-    if which == 2 and (last < 0 or m.free_leaves == 0 or (m.counts[last] == 0 and m.used_leaves == 0)):
+    if which == 2 and (last < 0 or m.free_leaves == 0 or (m.counts[last] == 0 and m.local.used_leaves == 0)):
         which = 1                                                        # no argument set the host lets through: the raw update instead
     if which == 0:
         with pytest.raises(IndexError):
             forest.update([tree], [index], leaf)
         return
     if which == 3:
-        fresh = gpu.build_forest(m.image[m.live_cells()], m.counts[: m.used_trees], max_count=m.max_count, reserve_trees=m.free_trees,
-                                 reserve_leaves=m.total - m.live_leaves)
+        if level is None:
+            fresh = gpu.build_forest(m.image[m.live_cells()], m.counts[: m.used_trees], max_count=m.max_count, reserve_trees=m.free_trees,
+                                     reserve_leaves=m.total - m.live_leaves)
+        else:
+            fresh = built(gpu, fl.ModelForest(m.ntrees, m.local.total, m.max_count, m.trees), level)
         assert fresh.counts.tolist() == forest.counts.tolist() and (fresh.total, fresh.ntrees) == (forest.total, forest.ntrees)
         for call in (lambda: forest.diff(fresh), lambda: fresh.diff(forest)):
             with pytest.raises(ValueError, match="dropped in front"):
                 call()
+        assert hc.canaries_intact(gpu, getattr(fresh, "canaries", ()))
         fresh.free()
         return
     with gpu.scope() as tmp:
@@ -149,7 +154,7 @@ def refused_call(gpu, forest, life, number):
         assert status not in (0, 0xDEADBEEF), (which, status)
 
 
-def perform(gpu, vk, kind, p, a, b, src, life):
+def perform(gpu, vk, kind, p, a, b, src, life, level=None):
     """The step on the device: on A, and on B where it is structural.  (A, B, what the calls returned)."""
     got = {}
     if kind == "update":
@@ -205,9 +210,19 @@ def perform(gpu, vk, kind, p, a, b, src, life):
         b.drop_front(p["k"])
     elif kind == "repack":
         old_roots = (life.a.roots(), life.b.roots())
-        new = [f.repacked(trees=p["trees"], reserve_trees=p["reserve_trees"], reserve_leaves=p["reserve_leaves"], mutated=p["mutated"]) for f in (a, b)]
-        for f, roots in zip((a, b), old_roots):                          # the old handle is left as it is, until it is freed
-            assert f.audit().clean and (f.roots() == roots).all(), "the forest repacked() was called on"
+        room = dict(trees=p["trees"], reserve_trees=p["reserve_trees"], reserve_leaves=p["reserve_leaves"], mutated=p["mutated"])
+        new = []
+        try:
+            for f in (a, b):
+                new.append(f.repacked(**room) if level is None else hc.repacked_at(gpu, f, level, **room))
+            for f, roots in zip((a, b), old_roots):                      # the old handle is left as it is, until it is freed
+                assert f.audit().clean and (f.roots() == roots).all(), "the forest repacked() was called on"
+                assert hc.canaries_intact(gpu, getattr(f, "canaries", ()))
+        except BaseException:
+            for f in new:
+                f.free()
+            raise
+        for f in (a, b):
             f.free()
         a, b = new
         got["built_mutated"] = a.built_mutated
@@ -221,8 +236,8 @@ def perform(gpu, vk, kind, p, a, b, src, life):
     return a, b, got
 
 
-def returns_equal_model(gpu, kind, p, a, b, got, want, life):
-    m = life.a
+def returns_equal_model(gpu, kind, p, a, b, got, want, life, level=None):
+    m, mb = hc.Shifted(life.a, level), hc.Shifted(life.b, level)
     masks = want["masks"]
     if "counted" in got:
         assert tuple(got["counted"]) == tuple(want["counted"]), "the counters returned"
@@ -246,14 +261,14 @@ def returns_equal_model(gpu, kind, p, a, b, got, want, life):
         again = a.diff(b)
         assert again[0].shape == (0,) and again[1].shape == (0,), "a second diff"
     if kind in fl.STRUCTURAL or kind == "sync":                          # the twin: its books and its cells are its model's
-        assert b.counts.tolist() == life.b.counts and b.dropped_leaves == life.b.dropped_leaves and b.used_trees == life.b.used_trees
-        state_equals_model(gpu, b, life.b)
+        assert b.counts.tolist() == mb.counts and b.dropped_leaves == mb.dropped_leaves and b.used_trees == mb.used_trees
+        state_equals_model(gpu, b, mb)
 
 
-def follow(gpu, vk, follower, frontier, kind, p, life):
+def follow(gpu, vk, follower, frontier, kind, p, life, level=None):
     """The Frontier-only follower: advanced by the new leaves on append and extend steps, adopted again -- the forest's frontier
     verified under the model's roots -- after any other step; then the model's, byte for byte."""
-    m = life.a
+    m = hc.Shifted(life.a, level)
     if kind in ("append", "extend") and not p["degenerate"] and p["leaves"].shape[0]:
         new = np.zeros(m.ntrees, dtype=np.int64)
         if kind == "append":
@@ -268,29 +283,58 @@ def follow(gpu, vk, follower, frontier, kind, p, life):
     return follower
 
 
-@pytest.mark.parametrize("name,seed", WALKS)
-def test_every_operation_after_every_other_against_the_model(gpu, name, seed):
+def the_walk(gpu, name, seed, level=None):
+    """One walk, the forests where build_forest puts them (level None) or at the shift of that placement level: every step
+    performed, every check made after it, every fourth step a refused call; at the end every pair of kinds has been performed
+    and the canaries of the forests that have them are intact."""
     import vk_merkle_roots_amd as vk
     life = fl.Life(seed, fl.CONFIGS[name])
-    a, b, src = built(gpu, life.a), built(gpu, life.b), built(gpu, life.src)
-    follower = everything_equals_model(gpu, vk, a, life)
-    assert (follower.verify(gpu, life.a.roots()) == 1).all()
-    for number, kind, p in life.steps():
+    forests = []
+    try:
+        for model, low in ((life.a, False), (life.b, False), (life.src, True)):       # src may stay low
+            forests.append(built(gpu, model, None if low else level))
+        a, b, src = forests
         try:
-            a, b, got = perform(gpu, vk, kind, p, a, b, src, life)
-            want = life.apply(kind, p)
-            returns_equal_model(gpu, kind, p, a, b, got, want, life)
-            frontier = everything_equals_model(gpu, vk, a, life)
-            follower = follow(gpu, vk, follower, frontier, kind, p, life)
-            if number % 4 == 3:
-                refused_call(gpu, a, life, number)
-                state_equals_model(gpu, a, life.a)
+            follower = everything_equals_model(gpu, vk, a, life, level)
+            state_equals_model(gpu, b, hc.Shifted(life.b, level))
+            assert (follower.verify(gpu, life.a.roots()) == 1).all()
         except BaseException:
-            print("failed at", (name, seed, number, kind, p))
+            print("failed at", (level, name, seed, "the build, before step 0"))
             raise
-    assert life.pairs == {(x, y) for x in fl.KINDS for y in fl.KINDS}
-    for f in (a, b, src):
-        f.free()
+        for number, kind, p in life.steps():
+            try:
+                a, b, got = perform(gpu, vk, kind, p, a, b, src, life, level)
+                forests[:2] = [a, b]
+                want = life.apply(kind, p)
+                returns_equal_model(gpu, kind, p, a, b, got, want, life, level)
+                frontier = everything_equals_model(gpu, vk, a, life, level)
+                follower = follow(gpu, vk, follower, frontier, kind, p, life, level)
+                if number % 4 == 3:
+                    refused_call(gpu, a, life, number, level)
+                    state_equals_model(gpu, a, hc.Shifted(life.a, level))
+            except BaseException:
+                print("failed at", (level, name, seed, number, kind, p))
+                raise
+        assert life.pairs == {(x, y) for x in fl.KINDS for y in fl.KINDS}
+        for f in (a, b):
+            assert hc.canaries_intact(gpu, getattr(f, "canaries", ()))
+    finally:
+        for f in forests:
+            f.free()
+
+
+@pytest.mark.parametrize("name,seed", WALKS)
+def test_every_operation_after_every_other_against_the_model(gpu, name, seed):
+    the_walk(gpu, name, seed)
+
+
+@pytest.mark.parametrize("level,name,seed", hc.HIGH_WALKS)
+def test_the_walk_above_4_gib(gpu, level, name, seed):
+    """The walk with A, B and both followers, the live cells of `level` on both sides of cell 2^27 of that level's buffer in
+    most steps: level 0, the leaves straddle byte 2^32 of the digests buffer; level 1, the level-1 nodes straddle byte 2^32 of
+    the level buffers while level 0 straddles byte 2^33; level 3 likewise.  The tight walks reach level 3 in two or three
+    steps only, so none is placed there.  Peak device memory: four forests of about 16 GiB in a repack step of level 1."""
+    the_walk(gpu, name, seed, level)
 
 
 def test_a_twin_that_kept_its_front_is_refused_then_diffed_after_it_dropped_it_too(gpu):

@@ -1391,13 +1391,15 @@ class MerkleForest(_Stored):
     """Every level of every tree of a forest, resident on the device (vkmr_hip_reduce_forest_tree_async): level 0 is the
     leaves buffer it was built from, levels 1..`levels` one buffer laid out as include/vkmr_hip.h describes, the roots a
     buffer of their own.  `levels` is also the stride of its proofs.  `built_mutated`: the mutation masks of the build
-    (uint64 [ntrees]) when it was a flagged one, else None; mutated() gives those of the forest as it is now."""
+    (uint64 [ntrees]) when it was a flagged one, else None; mutated() gives those of the forest as it is now.  `front`: the
+    cells of level 0 in front of the first tree that are no tree's (offsets_buf[0]), for a forest laid into a larger buffer."""
 
     _columns, _proof_columns, _Proof = (np.uint32, np.uint64), (np.uint32,), ForestMultiproof
     cells = property(lambda self: self.total)
     stride = property(lambda self: self.levels)
 
-    def __init__(self, dev, digests_buf, total, counts, offsets_buf, max_count, forest_buf, roots_buf, owned=(), built_mutated=None, used_trees=None):
+    def __init__(self, dev, digests_buf, total, counts, offsets_buf, max_count, forest_buf, roots_buf, owned=(), built_mutated=None, used_trees=None,
+                 front=0):
         self.built_mutated = built_mutated
         self.dev, self.digests, self.total, self.offsets, self.max_count = dev, digests_buf, int(total), offsets_buf, int(max_count)
         self.counts = np.array(counts, dtype=np.uint64)      # one entry per tree of the capacity; a copy, append() writes into it
@@ -1406,12 +1408,17 @@ class MerkleForest(_Stored):
         self.forest, self.roots_buf = forest_buf, roots_buf
         self._owned = list(owned)
         self.used_trees = self.ntrees if used_trees is None else int(used_trees)
-        self.dropped_trees = self.dropped_leaves = 0         # drop_front(): trees emptied at the front, cells in front that are no tree's
+        self.dropped_trees = 0                               # drop_front(): trees emptied at the front
+        self.dropped_leaves = int(front)                     # cells in front that are no tree's: dropped ones, behind the `front` it was laid at
+        if not 0 <= self.dropped_leaves <= self.total:
+            raise ValueError(f"MerkleForest: {front} cells in front of the first tree, {self.total} cells in all")
 
     # -- room to grow: `total` and `ntrees` are the capacity the level buffers are laid out for; the trees in use are the first
     # used_trees, their leaves end at cell used_leaves; the trees behind them are empty and the cells behind them free.  After
     # drop_front() the first dropped_leaves cells belong to no tree: used_leaves still is the cell behind the last leaf in
-    # use, where append and extend go on, and live_leaves counts the leaves that trees hold
+    # use, where append and extend go on, and live_leaves counts the leaves that trees hold.  A forest laid into a larger
+    # buffer (offsets_buf[0] > 0: a handle made with front=offsets_buf[0]) starts with dropped_leaves == front, the cells in
+    # front of its first tree that are no tree's, and `total` counts them: everything above holds as after a drop_front()
     used_leaves = property(lambda self: self.dropped_leaves + int(self.counts.sum()))
     live_leaves = property(lambda self: int(self.counts.sum()))
     free_trees = property(lambda self: self.ntrees - self.used_trees)
