@@ -4,12 +4,8 @@ import ctypes as C
 import os
 import re
 
+from abi_support import assert_bound, assert_exported, declared_symbols
 from conftest import ROOT
-
-
-def declared_symbols():
-    text = open(os.path.join(ROOT, "include", "vkmr_hip.h")).read()
-    return sorted(set(re.findall(r"VKMR_API\s+[\w\s\*]+?\b(vkmr_hip_\w+)\s*\(", text)))
 
 
 def test_header_declares_the_hot_path():
@@ -20,15 +16,30 @@ def test_header_declares_the_hot_path():
 
 
 def test_library_exports_every_declared_symbol(native):
-    lib = C.CDLL(native.HIP_LIB)
-    for name in declared_symbols():
-        assert hasattr(lib, name), name
+    assert_exported(native.HIP_LIB, declared_symbols())
 
 
 def test_python_stub_covers_the_header(native):
     from vk_merkle_roots_amd import _abi
     assert sorted(_abi.SIGNATURES) == declared_symbols()
     _abi.lib()   # binds every signature; raises if one is missing
+
+
+def test_the_stub_binds_every_declaration_argument_by_argument():
+    """Every entry of _abi.SIGNATURES against its declaration in include/vkmr_hip.h: arity, every scalar's type, pointer for
+    pointer, the return type.  (HOST_SIGNATURES has no header to be read against.)"""
+    from vk_merkle_roots_amd import _abi
+    assert sorted(_abi.SIGNATURES) == declared_symbols() and len(_abi.SIGNATURES) >= 98
+    for name in declared_symbols():
+        assert_bound(name)
+
+
+def test_the_experiments_stub_binds_every_declaration_argument_by_argument():
+    from vk_merkle_roots_amd import _abi
+    header = "vkmr_hip_experiments.h"
+    assert sorted(_abi.EXPERIMENT_SIGNATURES) == declared_symbols(header) != []
+    for name in declared_symbols(header):
+        assert_bound(name, table=_abi.EXPERIMENT_SIGNATURES, header=header)
 
 
 def test_header_is_plain_c(tmp_path):
@@ -98,7 +109,7 @@ def test_docs_name_only_entry_points_that_exist():
     helpers, `vkmr_host_*`): stale names in the binding guide would send a maintainer looking for functions that are gone."""
     declared = set(declared_symbols())
     # the experiments build's entry points (include/vkmr_hip_experiments.h) may be named too -- as what they are
-    declared |= set(re.findall(r"VKMR_API\s+[\w\s\*]+?\b(vkmr_hip_[a-z0-9_]+)\s*\(", open(os.path.join(ROOT, "include", "vkmr_hip_experiments.h")).read()))
+    declared |= set(declared_symbols("vkmr_hip_experiments.h"))
     for doc in ("INTEGRATION.md", "DESIGN.md", "README.md"):
         text = open(os.path.join(ROOT, doc)).read()
         for name in set(re.findall(r"\b(vkmr_hip_[a-z0-9_]+)\b", text)):

@@ -16,6 +16,7 @@ import pytest
 import apply_cases as ac
 import forest_cases as fc
 import forest_multiproof_cases as fm
+from abi_support import Refusals, assert_bound, assert_exported, assert_key_resolves, assert_no_spills, isa_record
 from conftest import ROOT
 from merkle_model import build_plan_exe, cpu_levels, random_leaves, tree_height
 
@@ -29,23 +30,13 @@ VERIFIER_HASH_BLOCK = {"valu": 3746, "complex": 1959, "simple": 1787, "rotates":
 
 def test_header_library_and_stub_agree_on_the_new_symbols(native):
     from vk_merkle_roots_amd import _abi
-    text = open(os.path.join(ROOT, "include", "vkmr_hip.h")).read()
-    declared = set(re.findall(r"VKMR_API\s+[\w\s\*]+?\b(vkmr_hip_\w+)\s*\(", text))
-    lib = C.CDLL(native.HIP_LIB)
-    for name in ENTRY_POINTS:
-        assert name in declared, name
-        assert hasattr(lib, name), name
-        params = re.search(r"\b" + name + r"\s*\(([^)]*)\)", text).group(1).split(",")
-        assert len(_abi.SIGNATURES[name][1]) == len(params), name
+    assert_exported(native.HIP_LIB, ENTRY_POINTS)
     # scratch_bytes(k, levels); the tree: dev, s, old, new, indices, k, count, height, nodes, m, root, scratch, ok, new_root; the
     # forest: dev, s, old, new, trees, indices, counts, k, stride, nodes, m, roots, ntrees, scratch, ok, new_roots
-    assert [len(_abi.SIGNATURES[n][1]) for n in ENTRY_POINTS] == [2, 14, 16]
-    assert _abi.SIGNATURES[ENTRY_POINTS[0]][0] is C.c_size_t
-    assert [a for a in _abi.SIGNATURES[ENTRY_POINTS[1]][1] if a is not C.c_void_p] == [C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64]
-    assert [a for a in _abi.SIGNATURES[ENTRY_POINTS[2]][1] if a is not C.c_void_p] == [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32]
-    host = C.CDLL(native.HOST_LIB)
-    for name in HOST_ENTRY_POINTS:
-        assert hasattr(host, name) and name in _abi.HOST_SIGNATURES, name
+    assert_bound(ENTRY_POINTS[0], nparams=2, restype=C.c_size_t)
+    assert_bound(ENTRY_POINTS[1], nparams=14, scalars=[C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64])
+    assert_bound(ENTRY_POINTS[2], nparams=16, scalars=[C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32])
+    assert_exported(native.HOST_LIB, HOST_ENTRY_POINTS)
     assert [len(_abi.HOST_SIGNATURES[n][1]) for n in HOST_ENTRY_POINTS] == [10, 12]
 
 
@@ -61,46 +52,19 @@ def test_the_python_wrappers_are_there_and_none_is_named_async(native):
 def test_bad_arguments_are_refused_before_any_hip_call(native):
     from vk_merkle_roots_amd import _abi
     lib = _abi.lib()
-    bad = _abi.ERR_INVALID
     d = C.c_void_p(0x1000)                 # never dereferenced: every call below returns before launching anything
-    name = b"vkmr_hip_apply_forest_multiproof_async"
     # old, new, trees, indices, counts, k, stride, nodes, m, roots, ntrees, scratch, ok, new_roots
-    good = [d, d, d, d, d, 8, 12, d, 30, d, 4, d, d, d]
-    for i in (0, 1, 2, 3, 4, 7, 9, 11, 12, 13):   # each pointer NULL with k > 0 (the nodes with m > 0)
-        args = list(good)
-        args[i] = None
-        assert lib.vkmr_hip_apply_forest_multiproof_async(0, None, *args) == bad, i
-        assert name in lib.vkmr_hip_last_error()
-    for stride in (0, 64, 100):
-        args = list(good)
-        args[6] = stride
-        assert lib.vkmr_hip_apply_forest_multiproof_async(0, None, *args) == bad, stride
-        assert name in lib.vkmr_hip_last_error()
-    args = list(good)
-    args[11] = C.c_void_p(0x1004)
-    assert lib.vkmr_hip_apply_forest_multiproof_async(0, None, *args) == bad
-    assert name in lib.vkmr_hip_last_error()
-    assert lib.vkmr_hip_apply_forest_multiproof_async(0, None, None, None, None, None, None, 0, 12, None, 0, None, 4, None, None, None) == _abi.OK   # k == 0
-    assert lib.vkmr_hip_apply_forest_multiproof_async(0, None, None, None, None, None, None, 0, 0, None, 9, None, 0, None, None, None) == _abi.OK
+    forest = Refusals(lib.vkmr_hip_apply_forest_multiproof_async, "vkmr_hip_apply_forest_multiproof_async", good=[d, d, d, d, d, 8, 12, d, 30, d, 4, d, d, d])
+    forest.null(0, 1, 2, 3, 4, 7, 9, 11, 12, 13)   # each pointer NULL with k > 0 (the nodes with m > 0)
+    forest.changed({6: 0}, {6: 64}, {6: 100}, {11: C.c_void_p(0x1004)})        # the stride; the scratch's alignment
+    forest.ok((None, None, None, None, None, 0, 12, None, 0, None, 4, None, None, None),      # k == 0
+              (None, None, None, None, None, 0, 0, None, 9, None, 0, None, None, None))
 
-    name = b"vkmr_hip_apply_multiproof_async"
     # old, new, indices, k, count, height, nodes, m, root, scratch, ok, new_root
-    good = [d, d, d, 8, 1000, 10, d, 30, d, d, d, d]
-    for i in (0, 1, 2, 6, 8, 9, 10, 11):
-        args = list(good)
-        args[i] = None
-        assert lib.vkmr_hip_apply_multiproof_async(0, None, *args) == bad, i
-        assert name in lib.vkmr_hip_last_error()
-    for height in (0, 64, 100):
-        args = list(good)
-        args[5] = height
-        assert lib.vkmr_hip_apply_multiproof_async(0, None, *args) == bad, height
-        assert name in lib.vkmr_hip_last_error()
-    args = list(good)
-    args[9] = C.c_void_p(0x1008)
-    assert lib.vkmr_hip_apply_multiproof_async(0, None, *args) == bad
-    assert lib.vkmr_hip_apply_multiproof_async(0, None, None, None, None, 0, 1000, 10, None, 0, None, None, None, None) == _abi.OK   # k == 0
-    assert lib.vkmr_hip_apply_multiproof_async(0, None, None, None, None, 0, 0, 0, None, 5, None, None, None, None) == _abi.OK
+    tree = Refusals(lib.vkmr_hip_apply_multiproof_async, "vkmr_hip_apply_multiproof_async", good=[d, d, d, 8, 1000, 10, d, 30, d, d, d, d])
+    tree.null(0, 1, 2, 6, 8, 9, 10, 11)
+    tree.changed({5: 0}, {5: 64}, {5: 100}, {9: C.c_void_p(0x1008)})           # the height; the scratch's alignment
+    tree.ok((None, None, None, 0, 1000, 10, None, 0, None, None, None, None), (None, None, None, 0, 0, 0, None, 5, None, None, None, None))   # k == 0
 
 
 def test_scratch_bytes_is_its_closed_form_and_the_pinned_sizes_did_not_move(native):
@@ -282,29 +246,18 @@ def test_a_tree_taller_than_its_count_needs(native):
 def test_both_level_kernels_hold_one_hash_block_and_the_verifiers_kept_theirs(native):
     from vk_merkle_roots_amd import isa_prio_pass
     expected = isa_prio_pass.EXPECTED_HASH_BLOCKS
-    for mine, mangled in zip(LEVEL_KERNELS, ("_Z23tree_apply_level_kernelPK", "_Z25forest_apply_level_kernelPK")):
+    for mine in LEVEL_KERNELS:
         assert expected[mine] == 1
-        # the pass matches by substring, first match wins: the name must resolve to its own key and shadow nobody's
-        assert next(k for k in expected if k in mangled) == mine
-        for other in expected:
-            assert other == mine or (other not in mine and mine not in other), other
-    path = os.path.splitext(native.HIP_LIB)[0] + ".isa.json"
-    if os.path.exists(path):               # written by a build that ran the issue pass (tests/test_isa_prio_pass.py covers its absence)
-        rec = json.load(open(path))
+        assert_key_resolves(mine)
+    rec = isa_record(native)
+    if rec is not None:                    # written by a build that ran the issue pass (tests/test_isa_prio_pass.py covers its absence)
         assert rec["audit"]["block_count_errors"] == [] and rec["audit"]["unclassified"] == []
         blocks = {k: v for k, v in rec["audit"]["blocks"].items() if "apply_" in k}
         assert sorted(blocks.values()) == [1, 1] and all(any(m in k for k in blocks) for m in LEVEL_KERNELS)   # the heights and the commits hold none
         for kernel in ("verify_multiproof_level_kernel", "verify_forest_multiproof_level_kernel") + LEVEL_KERNELS:
             mine = [v for k, v in rec["hash_blocks"].items() if re.match(r"_Z\d+" + kernel + "PK", k)]
             assert mine == [[VERIFIER_HASH_BLOCK]], (kernel, mine)
-    listing = os.path.join(ROOT, "build", "obj", os.path.basename(native.HIP_LIB), "device.s")
-    if os.path.exists(listing):            # the device assembly that build left behind: the code object's own metadata of the kernels
-        text = open(listing).read()
-        for mine in LEVEL_KERNELS:
-            meta = re.search(r"\.name:\s+_Z\d+" + mine + r"\w*\n((?:    \..*\n)+)", text).group(1)
-            fields = dict(re.findall(r"\.(\w+):\s+(\S+)", meta))
-            assert fields["private_segment_fixed_size"] == "0" and fields["sgpr_spill_count"] == "0" and fields["vgpr_spill_count"] == "0"
-            assert int(fields["vgpr_count"]) <= 64          # 512 registers a lane, 8 wavefronts per SIMD
+    assert_no_spills(native, LEVEL_KERNELS, max_vgprs=64, prefix=True)         # 512 registers a lane, 8 wavefronts per SIMD
 
 
 def test_both_host_functions_under_address_and_undefined_behaviour_sanitizers(native, tmp_path):

@@ -3,7 +3,6 @@ scratch layout replayed by tests/c/audit_plan_test.cpp, the CPU counterparts (vk
 against the rule restated with hashlib in tests/audit_cases.py, and the theorem the rule stands on: no bad node <=> the stored
 cells are those of a rebuild."""
 import ctypes as C
-import json
 import os
 import subprocess
 
@@ -13,6 +12,7 @@ import pytest
 import audit_cases as ac
 import forest_cases
 import merkle_model
+from abi_support import Refusals, assert_bound, assert_exported, assert_key_resolves, isa_record
 from no_device import NoDeviceAt as NoDevice
 
 NEW = {"vkmr_hip_audit_scratch_bytes": 3, "vkmr_hip_forest_audit_async": 16, "vkmr_hip_tree_audit_async": 11}
@@ -23,12 +23,11 @@ FULL_SCAN_LEAVES = 3000                    # above this the hashlib model looks 
 
 def test_libraries_export_the_symbols_and_the_stub_binds_them(native):
     from vk_merkle_roots_amd import _abi
-    lib, host = C.CDLL(native.HIP_LIB), C.CDLL(native.HOST_LIB)
+    assert_exported(native.HIP_LIB, NEW)
+    assert_exported(native.HOST_LIB, HOST_NEW)
     for name, nargs in NEW.items():
-        assert hasattr(lib, name), name
-        assert len(_abi.SIGNATURES[name][1]) == nargs
+        assert_bound(name, nparams=nargs)
     for name, nargs in HOST_NEW.items():
-        assert hasattr(host, name), name
         assert len(_abi.HOST_SIGNATURES[name][1]) == nargs
     _abi.host_lib()
 
@@ -190,15 +189,13 @@ def test_the_cpu_counterparts_report_bad_offsets_and_refuse_missing_arguments(na
     d = f.leaves.ctypes.data
     good = [d, d, d, 14, f.offsets.ctypes.data, 3, 9, d, d, d, d, 4, d]
     for i in (0, 1, 2, 4, 7, 8, 9, 10, 12):
-        args = list(good)
-        args[i] = None
+        args = good[:i] + [None] + good[i + 1:]
         assert host.vkmr_host_cpu_forest_audit(*args) == -1, i
     assert host.vkmr_host_cpu_forest_audit(*(good[:6] + [0] + good[7:])) == -1                  # no max_count
     assert host.vkmr_host_cpu_forest_audit(None, None, None, 0, None, 0, 0, None, None, None, None, 0, None) == 0     # no tree: nothing to do
     tgood = [d, d, 5, 3, d, d, 4, d]
     for i in (0, 1, 4, 5, 7):
-        args = list(tgood)
-        args[i] = None
+        args = tgood[:i] + [None] + tgood[i + 1:]
         assert host.vkmr_host_cpu_tree_audit(*args) == -1, i
     assert host.vkmr_host_cpu_tree_audit(d, d, 5, 2, d, d, 4, d) == -1 and host.vkmr_host_cpu_tree_audit(d, d, 5, 64, d, d, 4, d) == -1
     assert host.vkmr_host_cpu_tree_audit(None, None, 0, 3, None, None, 4, None) == 0
@@ -312,60 +309,34 @@ def test_the_scratch_layout_replayed(tmp_path, sanitize):
 def test_the_forest_call_refuses_bad_arguments_before_any_hip_call(native):
     from vk_merkle_roots_amd import _abi
     lib = _abi.lib()
-    fn = lib.vkmr_hip_forest_audit_async
     d = C.c_void_p(0x1000)                     # never dereferenced: every call below returns before launching anything
     # digests, forest, roots, total, offsets, ntrees, max_count, scratch, masks, bad_trees, bad_levels, bad_nodes, capacity, info
-    good = [d, d, d, 100, d, 4, 50, d, d, d, d, d, 8, d]
-    for i in (0, 1, 2, 4, 7, 8, 9, 10, 11, 13):
-        args = list(good)
-        args[i] = None
-        assert fn(0, None, *args) == _abi.ERR_INVALID, i
-        assert b"vkmr_hip_forest_audit_async" in lib.vkmr_hip_last_error()
-    for i, bad in ((6, 0), (3, (1 << 58) + 1), (7, C.c_void_p(0x1008))):      # no max_count, too many leaves, scratch off the 16-byte grid
-        args = list(good)
-        args[i] = bad
-        assert fn(0, None, *args) == _abi.ERR_INVALID, i
+    audit = Refusals(lib.vkmr_hip_forest_audit_async, "vkmr_hip_forest_audit_async", good=[d, d, d, 100, d, 4, 50, d, d, d, d, d, 8, d])
+    audit.null(0, 1, 2, 4, 7, 8, 9, 10, 11, 13)
+    audit.changed({6: 0}, {3: (1 << 58) + 1}, {7: C.c_void_p(0x1008)})        # no max_count, too many leaves, scratch off the 16-byte grid
     # a level of more than 2^32 - 1 cells cannot be listed; the refusal names the way out
-    args = list(good)
-    args[3] = 1 << 34
-    assert fn(0, None, *args) == _abi.ERR_INVALID and b"capacity must be 0" in lib.vkmr_hip_last_error()
+    audit.changed({3: 1 << 34})
+    assert b"capacity must be 0" in lib.vkmr_hip_last_error()
     # capacity 0: the lists and the scratch may be missing -- the masks and the counters may not
-    none = [d, d, d, 100, d, 4, 50, None, d, None, None, None, 0, d]
-    for i in (8, 13):
-        bad = list(none)
-        bad[i] = None
-        assert fn(0, None, *bad) == _abi.ERR_INVALID, i
+    audit.changed(*({7: None, 9: None, 10: None, 11: None, 12: 0, i: None} for i in (8, 13)))
     # no tree: nothing to do, whatever the rest
-    assert fn(0, None, None, None, None, 1 << 60, None, 0, 0, None, None, None, None, None, 7, None) == _abi.OK
+    audit.ok((None, None, None, 1 << 60, None, 0, 0, None, None, None, None, None, 7, None))
 
 
 def test_the_tree_call_refuses_bad_arguments_before_any_hip_call(native):
     from vk_merkle_roots_amd import _abi
     lib = _abi.lib()
-    fn = lib.vkmr_hip_tree_audit_async
     d = C.c_void_p(0x1000)
     # digests, tree, count, height, scratch, bad_levels, bad_nodes, capacity, info
-    good = [d, d, 100, 7, d, d, d, 8, d]
-    for i in (0, 1, 4, 5, 6, 8):
-        args = list(good)
-        args[i] = None
-        assert fn(0, None, *args) == _abi.ERR_INVALID, i
-        assert b"vkmr_hip_tree_audit_async" in lib.vkmr_hip_last_error()
-    for count, height in ((100, 6), (100, 64), (1 << 59, 59)):
-        args = list(good)
-        args[2], args[3] = count, height
-        assert fn(0, None, *args) == _abi.ERR_INVALID, (count, height)
-    args = list(good)
-    args[4] = C.c_void_p(0x1004)
-    assert fn(0, None, *args) == _abi.ERR_INVALID
-    args = list(good)
-    args[2], args[3] = 1 << 34, 34
-    assert fn(0, None, *args) == _abi.ERR_INVALID and b"capacity must be 0" in lib.vkmr_hip_last_error()
-    for i in (0, 1, 8):                        # capacity 0: the digests, the tree and the counters are still needed
-        bad = [d, d, 100, 7, None, None, None, 0, d]
-        bad[i] = None
-        assert fn(0, None, *bad) == _abi.ERR_INVALID, i
-    assert fn(0, None, None, None, 0, 99, None, None, None, 7, None) == _abi.OK           # no leaf: nothing to do
+    audit = Refusals(lib.vkmr_hip_tree_audit_async, "vkmr_hip_tree_audit_async", good=[d, d, 100, 7, d, d, d, 8, d])
+    audit.null(0, 1, 4, 5, 6, 8)
+    audit.changed(*({2: count, 3: height} for count, height in ((100, 6), (100, 64), (1 << 59, 59))))
+    audit.changed({4: C.c_void_p(0x1004)})
+    audit.changed({2: 1 << 34, 3: 34})
+    assert b"capacity must be 0" in lib.vkmr_hip_last_error()
+    # capacity 0: the digests, the tree and the counters are still needed
+    audit.changed(*({4: None, 5: None, 6: None, 7: 0, i: None} for i in (0, 1, 8)))
+    audit.ok((None, None, 0, 99, None, None, None, 7, None))                              # no leaf: nothing to do
 
 
 def test_the_python_layer_checks_the_capacity_before_any_device_call():
@@ -450,16 +421,12 @@ def test_the_raw_wrappers_pass_every_argument_in_the_headers_order():
 def test_the_level_kernels_hold_one_hash_block_each_and_the_build_lists_them(native):
     from vk_merkle_roots_amd import isa_prio_pass
     keys = isa_prio_pass.EXPECTED_HASH_BLOCKS
-    for mine, mangled in (("forest_audit_level_kernel", "_Z25forest_audit_level_kernelPK"), ("tree_audit_level_kernel", "_Z23tree_audit_level_kernelPK")):
+    for mine in ("forest_audit_level_kernel", "tree_audit_level_kernel"):
         assert keys[mine] == 1
-        # the pass matches by substring, first match wins: the name must resolve to its own key and shadow nobody's
-        assert next(k for k in keys if k in mangled) == mine
-        for other in keys:
-            assert other == mine or (other not in mine and mine not in other), other
-    path = os.path.splitext(native.HIP_LIB)[0] + ".isa.json"
-    if not os.path.exists(path):           # as tests/test_isa_prio_pass.py: only a build without the llvm tools leaves no record
+        assert_key_resolves(mine)
+    rec = isa_record(native)
+    if rec is None:                        # as tests/test_isa_prio_pass.py: only a build without the llvm tools leaves no record
         pytest.skip("the library in the tree was built without the issue pass (llvm tools absent)")
-    rec = json.load(open(path))
     assert rec["audit"]["block_count_errors"] == [] and rec["audit"]["unclassified"] == []
     blocks = {k: v for k, v in rec["audit"]["blocks"].items() if "_audit_" in k}
     assert sorted(blocks.values()) == [1, 1] and all("audit_level_kernel" in k for k in blocks)       # the emit kernels hold none

@@ -4,7 +4,6 @@ its own program under AddressSanitizer and UBSan), the CPU twins (vkmr_host_cpu_
 the hashlib model of tests/consistency_cases.py -- the read set cell by cell --, and the host side of vk.ConsistencyProof.  No
 compute call on a device here."""
 import ctypes as C
-import json
 import os
 import re
 
@@ -12,6 +11,7 @@ import numpy as np
 import pytest
 
 import consistency_cases as cc
+from abi_support import Refusals, assert_bound, assert_exported, assert_key_resolves, assert_no_spills, isa_record
 from conftest import ROOT
 from merkle_model import random_counts, random_leaves
 from no_device import NoDevice
@@ -25,56 +25,34 @@ NAMES_OTHER_TESTS_COUNT = ("frontier", "mutated", "apply_", "_audit_", "forest_m
 
 
 def test_header_declares_them_and_the_stub_binds_every_argument():
-    text = open(os.path.join(ROOT, "include", "vkmr_hip.h")).read()
     from vk_merkle_roots_amd import _abi
     for name, nparams in ENTRY_POINTS.items():
-        params = re.search(r"VKMR_API\s+[\w\s\*]+?\b" + name + r"\s*\(([^)]*)\)", text).group(1).split(",")
-        assert len(params) == nparams, name
-        res, args = _abi.SIGNATURES[name]
-        assert len(args) == nparams and res is C.c_int, name
+        assert_bound(name, nparams=nparams, restype=C.c_int)
     for name, nparams in HOST_ENTRY_POINTS.items():
         res, args = _abi.HOST_SIGNATURES[name]
         assert len(args) == nparams and res is C.c_int, name
 
 
 def test_libraries_export_them(native):
-    lib, host = C.CDLL(native.HIP_LIB), C.CDLL(native.HOST_LIB)
-    assert all(hasattr(lib, name) for name in ENTRY_POINTS) and all(hasattr(host, name) for name in HOST_ENTRY_POINTS)
+    assert_exported(native.HIP_LIB, ENTRY_POINTS)
+    assert_exported(native.HOST_LIB, HOST_ENTRY_POINTS)
 
 
 def test_bad_arguments_are_refused_before_any_hip_call(native):
     from vk_merkle_roots_amd import _abi
     lib = _abi.lib()
-    bad = _abi.ERR_INVALID
     d = C.c_void_p(0x1000)                 # never dereferenced: every call below returns before launching anything
     # digests, forest, total, offsets, ntrees, max_count, roots, trees, old_counts, Q, stride, new_counts, peaks, rights, status
-    good = [d, d, 100, d, 8, 50, d, d, d, 5, 6, d, d, d, d]
-    gather = "vkmr_hip_forest_consistency_async"
-    for i in (0, 1, 3, 6, 7, 8, 11, 12, 13, 14):
-        args = list(good)
-        args[i] = None
-        assert lib.vkmr_hip_forest_consistency_async(0, None, *args) == bad, i
-        assert gather.encode() in lib.vkmr_hip_last_error()
+    gather = Refusals(lib.vkmr_hip_forest_consistency_async, "vkmr_hip_forest_consistency_async", good=[d, d, 100, d, 8, 50, d, d, d, 5, 6, d, d, d, d])
+    gather.null(0, 1, 3, 6, 7, 8, 11, 12, 13, 14)
     # what vkmr_hip_forest_frontier_async refuses: stride 5 -- a tree of 50 leaves has six bits
-    for changes in ({10: 0}, {10: 65}, {10: 5}, {5: 0}, {2: (1 << 58) + 1}):
-        args = list(good)
-        for i, value in changes.items():
-            args[i] = value
-        assert lib.vkmr_hip_forest_consistency_async(0, None, *args) == bad, changes
-        assert gather.encode() in lib.vkmr_hip_last_error()
-    assert lib.vkmr_hip_forest_consistency_async(0, None, None, None, 0, None, 0, 0, None, None, None, 0, 0, None, None, None, None) == _abi.OK   # no query
+    gather.changed({10: 0}, {10: 65}, {10: 5}, {5: 0}, {2: (1 << 58) + 1})
+    gather.ok((None, None, 0, None, 0, 0, None, None, None, 0, 0, None, None, None, None))      # no query
     # the verifier: old counts, new counts, peaks, rights, stride, Q, old roots, new roots, ok
-    good = [d, d, d, d, 8, 3, d, d, d]
-    for i in (0, 1, 2, 3, 6, 7, 8):
-        args = list(good)
-        args[i] = None
-        assert lib.vkmr_hip_verify_consistency_async(0, None, *args) == bad, i
-        assert b"vkmr_hip_verify_consistency_async" in lib.vkmr_hip_last_error()
-    for stride in (0, 65):
-        args = list(good)
-        args[4] = stride
-        assert lib.vkmr_hip_verify_consistency_async(0, None, *args) == bad, stride
-    assert lib.vkmr_hip_verify_consistency_async(0, None, None, None, None, None, 0, 0, None, None, None) == _abi.OK
+    verify = Refusals(lib.vkmr_hip_verify_consistency_async, "vkmr_hip_verify_consistency_async", good=[d, d, d, d, 8, 3, d, d, d])
+    verify.null(0, 1, 2, 3, 6, 7, 8)
+    verify.changed({4: 0}, {4: 65})        # the stride
+    verify.ok((None, None, None, None, 0, 0, None, None, None))
     # and the twins
     import vk_merkle_roots_amd as vk
     host = vk.host_lib()
@@ -300,25 +278,15 @@ def test_the_kernel_key_resolves_to_itself_and_the_build_lists_it(native):
     from vk_merkle_roots_amd import isa_prio_pass
     keys = isa_prio_pass.EXPECTED_HASH_BLOCKS
     assert keys[FOLD] == 1
-    # the pass matches by substring, first match wins: the name must resolve to its own key and shadow nobody's
-    assert next(k for k in keys if k in f"_Z23{FOLD}PK") == FOLD
-    for other in keys:
-        assert other == FOLD or (other not in FOLD and FOLD not in other), other
+    assert_key_resolves(FOLD)
     for name in KERNELS:
         assert name == FOLD or not any(k in name for k in keys), name                            # no hash expected in the others
         assert not any(s in name for s in NAMES_OTHER_TESTS_COUNT), name
     text = open(os.path.join(ROOT, "vk_merkle_roots_amd", "csrc", "consistency_kernels.hpp")).read()
     assert len(re.findall(r"\bhash_pair\(", text)) == 1 and sorted(re.findall(r"void (\w+_kernel)\(", text)) == sorted(KERNELS)
-    path = os.path.splitext(native.HIP_LIB)[0] + ".isa.json"
-    if os.path.exists(path):               # written by a build that ran the issue pass (tests/test_isa_prio_pass.py covers its absence)
-        rec = json.load(open(path))
+    rec = isa_record(native)
+    if rec is not None:                    # written by a build that ran the issue pass (tests/test_isa_prio_pass.py covers its absence)
         assert rec["audit"]["block_count_errors"] == [] and rec["audit"]["unclassified"] == []
         mine = {k: v for k, v in rec["audit"]["blocks"].items() if "consistency" in k}
         assert list(mine.values()) == [1] and FOLD in next(iter(mine))
-    listing = os.path.join(ROOT, "build", "obj", os.path.basename(native.HIP_LIB), "device.s")
-    if os.path.exists(listing):            # the device assembly that build left behind: the code object's own metadata of the kernels
-        text = open(listing).read()
-        for name in KERNELS:
-            meta = re.search(r"\.name:\s+_Z\d+" + name + r"P\w*\n((?:    \..*\n)+)", text).group(1)
-            fields = dict(re.findall(r"\.(\w+):\s+(\S+)", meta))
-            assert fields["private_segment_fixed_size"] == "0" and fields["sgpr_spill_count"] == "0" and fields["vgpr_spill_count"] == "0"
+    assert_no_spills(native, KERNELS)

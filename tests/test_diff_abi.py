@@ -8,17 +8,16 @@ import pytest
 
 import diff_cases as dc
 import merkle_model
+from abi_support import Refusals, assert_bound, assert_exported
 from no_device import NoDeviceAt as NoDevice
 
 NEW = {"vkmr_hip_diff_scratch_bytes": 1, "vkmr_hip_forest_diff_async": 18, "vkmr_hip_tree_diff_async": 13}
 
 
 def test_library_exports_the_symbols_and_the_stub_binds_them(native):
-    from vk_merkle_roots_amd import _abi
-    lib = C.CDLL(native.HIP_LIB)
+    assert_exported(native.HIP_LIB, NEW)
     for name, nargs in NEW.items():
-        assert hasattr(lib, name), name
-        assert len(_abi.SIGNATURES[name][1]) == nargs
+        assert_bound(name, nparams=nargs)
 
 
 def test_the_model_itself():
@@ -70,56 +69,32 @@ def test_scratch_bytes_is_the_layout(native, capacity):
 def test_the_forest_call_refuses_bad_arguments_before_any_hip_call(native):
     from vk_merkle_roots_amd import _abi
     lib = _abi.lib()
-    fn = lib.vkmr_hip_forest_diff_async
     d = C.c_void_p(0x1000)                     # never dereferenced: every call below returns before launching anything
     # digests_a, forest_a, roots_a, digests_b, forest_b, roots_b, total, offsets, ntrees, max_count, scratch, trees_out, indices_out, leaves_b_out, capacity, info
-    good = [d, d, d, d, d, d, 100, d, 4, 50, d, d, d, None, 8, d]
-    for i in (0, 1, 2, 3, 4, 5, 7, 10, 11, 12, 15):     # each pointer NULL where it is needed; B's leaves are optional
-        args = list(good)
-        args[i] = None
-        assert fn(0, None, *args) == _abi.ERR_INVALID, i
-        assert b"vkmr_hip_forest_diff_async" in lib.vkmr_hip_last_error()
-    for i, bad in ((9, 0), (6, (1 << 58) + 1), (10, C.c_void_p(0x1008))):      # no max_count, too many leaves, scratch off the 16-byte grid
-        args = list(good)
-        args[i] = bad
-        assert fn(0, None, *args) == _abi.ERR_INVALID, i
-    args = list(good)
-    args[11] = args[12] = None                 # capacity 0: the outputs may be missing -- the scratch and the counters may not
-    args[14] = 0
-    for i in (10, 15):
-        bad = list(args)
-        bad[i] = None
-        assert fn(0, None, *bad) == _abi.ERR_INVALID, i
+    diff = Refusals(lib.vkmr_hip_forest_diff_async, "vkmr_hip_forest_diff_async", good=[d, d, d, d, d, d, 100, d, 4, 50, d, d, d, None, 8, d])
+    diff.null(0, 1, 2, 3, 4, 5, 7, 10, 11, 12, 15)      # each pointer NULL where it is needed; B's leaves are optional
+    diff.changed({9: 0}, {6: (1 << 58) + 1}, {10: C.c_void_p(0x1008)})         # no max_count, too many leaves, scratch off the 16-byte grid
+    # capacity 0: the outputs may be missing -- the scratch and the counters may not
+    diff.changed(*({11: None, 12: None, 14: 0, i: None} for i in (10, 15)))
     # no tree: nothing to do, whatever the rest
-    assert fn(0, None, None, None, None, None, None, None, 1 << 60, None, 0, 0, None, None, None, None, 7, None) == _abi.OK
+    diff.ok((None, None, None, None, None, None, 1 << 60, None, 0, 0, None, None, None, None, 7, None))
 
 
 def test_the_tree_call_refuses_bad_arguments_before_any_hip_call(native):
     from vk_merkle_roots_amd import _abi
     lib = _abi.lib()
-    fn = lib.vkmr_hip_tree_diff_async
     d = C.c_void_p(0x1000)
     # digests_a, tree_a, digests_b, tree_b, count, height, scratch, indices_out, leaves_b_out, capacity, info
-    good = [d, d, d, d, 100, 7, d, d, None, 8, d]
-    for i in (0, 1, 2, 3, 6, 7, 10):
-        args = list(good)
-        args[i] = None
-        assert fn(0, None, *args) == _abi.ERR_INVALID, i
-        assert b"vkmr_hip_tree_diff_async" in lib.vkmr_hip_last_error()
+    diff = Refusals(lib.vkmr_hip_tree_diff_async, "vkmr_hip_tree_diff_async", good=[d, d, d, d, 100, 7, d, d, None, 8, d])
+    diff.null(0, 1, 2, 3, 6, 7, 10)
     for count, height in ((100, 6), (100, 64), (1 << 59, 59)):                 # as vkmr_hip_tree_proofs_async refuses a height; too many leaves
-        args = list(good)
-        args[4], args[5] = count, height
-        assert fn(0, None, *args) == _abi.ERR_INVALID, (count, height)
+        diff.changed({4: count, 5: height})
         assert lib.vkmr_hip_tree_proofs_async(0, None, d, d, count, height, d, 1, d) == _abi.ERR_INVALID or count > (1 << 58)
-    args = list(good)
-    args[6] = C.c_void_p(0x1004)
-    assert fn(0, None, *args) == _abi.ERR_INVALID
-    for i in (0, 2, 6, 10):                    # one leaf and no level: the tree buffers may be missing, the rest may not
-        args = [d, None, d, None, 1, 0, d, d, None, 8, d]
-        args[i] = None
-        assert fn(0, None, *args) == _abi.ERR_INVALID, i
+    diff.changed({6: C.c_void_p(0x1004)})
+    # one leaf and no level: the tree buffers may be missing, the rest may not
+    diff.changed(*({1: None, 3: None, 4: 1, 5: 0, i: None} for i in (0, 2, 6, 10)))
     # no leaf: nothing to do, whatever the rest
-    assert fn(0, None, None, None, None, None, 0, 99, None, None, None, 7, None) == _abi.OK
+    diff.ok((None, None, None, None, 0, 99, None, None, None, 7, None))
 
 
 def test_the_python_layer_refuses_other_shapes_before_any_device_call():

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import find_cases as fd
+from abi_support import Refusals, assert_bound, assert_exported
 
 NEW = {"vkmr_hip_find_scratch_bytes": 1, "vkmr_hip_forest_find_async": 11, "vkmr_hip_tree_find_async": 8}
 
@@ -18,13 +19,11 @@ def assert_equals_the_model(case, trees, indices, what):
 
 def test_library_exports_the_symbols_and_the_stub_binds_them(native):
     from vk_merkle_roots_amd import _abi
-    lib = C.CDLL(native.HIP_LIB)
+    assert_exported(native.HIP_LIB, NEW)
     for name, nargs in NEW.items():
-        assert hasattr(lib, name), name
-        assert len(_abi.SIGNATURES[name][1]) == nargs
-    host = C.CDLL(native.HOST_LIB)
-    assert hasattr(host, "vkmr_host_cpu_forest_find") and len(_abi.HOST_SIGNATURES["vkmr_host_cpu_forest_find"][1]) == 8
-    assert hasattr(host, "vkmr_host_cpu_tree_find") and len(_abi.HOST_SIGNATURES["vkmr_host_cpu_tree_find"][1]) == 5
+        assert_bound(name, nparams=nargs)
+    assert_exported(native.HOST_LIB, ["vkmr_host_cpu_forest_find", "vkmr_host_cpu_tree_find"])
+    assert len(_abi.HOST_SIGNATURES["vkmr_host_cpu_forest_find"][1]) == 8 and len(_abi.HOST_SIGNATURES["vkmr_host_cpu_tree_find"][1]) == 5
 
 
 def test_the_model_itself():
@@ -63,48 +62,26 @@ def test_the_plan_constants_can_be_read():
 
 def test_the_forest_call_refuses_bad_arguments_before_any_hip_call(native):
     from vk_merkle_roots_amd import _abi
-    fn = _abi.lib().vkmr_hip_forest_find_async
     d = C.c_void_p(0x1000)                     # never dereferenced: every call below returns before launching anything
-    good = [d, 100, d, 4, d, 5, d, d, d]       # digests, total, offsets, ntrees, queries, k, scratch, trees, indices
-    for i in (0, 2, 4, 6, 7, 8):               # each pointer NULL where it is needed
-        args = list(good)
-        args[i] = None
-        assert fn(0, None, *args) == _abi.ERR_INVALID, i
-        assert _abi.lib().vkmr_hip_last_error()
-    args = list(good)
-    args[1] = (1 << 58) + 1                    # more leaves than a forest takes
-    assert fn(0, None, *args) == _abi.ERR_INVALID
-    args = list(good)
-    args[6] = C.c_void_p(0x1004)               # the slots are 8-byte words
-    assert fn(0, None, *args) == _abi.ERR_INVALID
+    # digests, total, offsets, ntrees, queries, k, scratch, trees, indices
+    find = Refusals(_abi.lib().vkmr_hip_forest_find_async, "vkmr_hip_forest_find_async", good=[d, 100, d, 4, d, 5, d, d, d])
+    find.null(0, 2, 4, 6, 7, 8)                # each pointer NULL where it is needed
+    find.changed({1: (1 << 58) + 1}, {6: C.c_void_p(0x1004)})      # more leaves than a forest takes; the slots are 8-byte words
     for total, ntrees in ((0, 4), (100, 0)):   # without a leaf the queries, the scratch and the outputs are still needed
-        for i in (4, 6, 7, 8):
-            args = [None, total, d if ntrees else None, ntrees, d, 5, d, d, d]
-            args[i] = None
-            assert fn(0, None, *args) == _abi.ERR_INVALID, (total, ntrees, i)
+        find.changed(*({0: None, 1: total, 2: d if ntrees else None, 3: ntrees, i: None} for i in (4, 6, 7, 8)))
     # k == 0 does nothing whatever the rest
-    assert fn(0, None, None, 0, None, 0, None, 0, None, None, None) == _abi.OK
-    assert fn(0, None, None, (1 << 60), None, 7, None, 0, None, None, None) == _abi.OK
+    find.ok((None, 0, None, 0, None, 0, None, None, None), (None, (1 << 60), None, 7, None, 0, None, None, None))
 
 
 def test_the_tree_call_refuses_bad_arguments_before_any_hip_call(native):
     from vk_merkle_roots_amd import _abi
-    fn = _abi.lib().vkmr_hip_tree_find_async
     d = C.c_void_p(0x1000)
-    good = [d, 100, d, 5, d, d]                # digests, count, queries, k, scratch, indices
-    for i in (0, 2, 4, 5):
-        args = list(good)
-        args[i] = None
-        assert fn(0, None, *args) == _abi.ERR_INVALID, i
-    args = list(good)
-    args[1] = (1 << 58) + 1
-    assert fn(0, None, *args) == _abi.ERR_INVALID
-    for i in (2, 4, 5):                        # count == 0: the leaves alone may be missing
-        args = [None, 0, d, 5, d, d]
-        args[i] = None
-        assert fn(0, None, *args) == _abi.ERR_INVALID, i
-    assert fn(0, None, None, 0, None, 0, None, None) == _abi.OK
-    assert fn(0, None, None, (1 << 60), None, 0, None, None) == _abi.OK
+    # digests, count, queries, k, scratch, indices
+    find = Refusals(_abi.lib().vkmr_hip_tree_find_async, "vkmr_hip_tree_find_async", good=[d, 100, d, 5, d, d])
+    find.null(0, 2, 4, 5)
+    find.changed({1: (1 << 58) + 1})
+    find.changed(*({0: None, 1: 0, i: None} for i in (2, 4, 5)))   # count == 0: the leaves alone may be missing
+    find.ok((None, 0, None, 0, None, None), (None, (1 << 60), None, 0, None, None))
 
 
 @pytest.mark.parametrize("variant", fd.VARIANTS)

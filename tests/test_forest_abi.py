@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import forest_cases as fc
+from abi_support import Refusals, assert_bound, assert_exported
 
 
 @pytest.fixture(scope="module")
@@ -15,34 +16,22 @@ def plan_exe(tmp_path_factory):
 
 
 def test_library_exports_the_forest_symbols_and_the_stub_binds_them(native):
-    from vk_merkle_roots_amd import _abi
-    lib = C.CDLL(native.HIP_LIB)
-    for name in ("vkmr_hip_forest_scratch_bytes", "vkmr_hip_reduce_forest_async"):
-        assert hasattr(lib, name), name
-        assert name in _abi.SIGNATURES
-    assert len(_abi.SIGNATURES["vkmr_hip_reduce_forest_async"][1]) == 10
-    assert hasattr(C.CDLL(native.HOST_LIB), "vkmr_host_cpu_forest_roots")
+    assert_exported(native.HIP_LIB, ("vkmr_hip_forest_scratch_bytes", "vkmr_hip_reduce_forest_async"))
+    assert_bound("vkmr_hip_forest_scratch_bytes")
+    assert_bound("vkmr_hip_reduce_forest_async", nparams=10)
+    assert_exported(native.HOST_LIB, ["vkmr_host_cpu_forest_roots"])
 
 
 def test_bad_arguments_are_refused_before_any_hip_call(native):
     from vk_merkle_roots_amd import _abi
     lib = _abi.lib()
     d = C.c_void_p(0x1000)                 # never dereferenced: every call below returns before launching anything
-    good = [d, 100, d, 4, 50, d, d, d]     # digests, total, offsets, ntrees, max_count, scratch, roots, status
-    for i in (0, 2, 5, 6, 7):              # each pointer NULL with ntrees > 0
-        args = list(good)
-        args[i] = None
-        assert lib.vkmr_hip_reduce_forest_async(0, None, *args) == _abi.ERR_INVALID, i
-    args = list(good)
-    args[4] = 0                            # max_count == 0
-    assert lib.vkmr_hip_reduce_forest_async(0, None, *args) == _abi.ERR_INVALID
-    assert lib.vkmr_hip_last_error()
-    args = list(good)
-    args[5] = C.c_void_p(0x1008)           # scratch not 16-byte aligned
-    assert lib.vkmr_hip_reduce_forest_async(0, None, *args) == _abi.ERR_INVALID
+    # digests, total, offsets, ntrees, max_count, scratch, roots, status
+    reduce = Refusals(lib.vkmr_hip_reduce_forest_async, "vkmr_hip_reduce_forest_async", good=[d, 100, d, 4, 50, d, d, d])
+    reduce.null(0, 2, 5, 6, 7)             # each pointer NULL with ntrees > 0
+    reduce.changed({4: 0}, {5: C.c_void_p(0x1008)})        # max_count == 0; scratch not 16-byte aligned
     # ntrees == 0 does nothing whatever the rest
-    assert lib.vkmr_hip_reduce_forest_async(0, None, None, 0, None, 0, 0, None, None, None) == _abi.OK
-    assert lib.vkmr_hip_reduce_forest_async(0, None, None, 100, None, 0, 7, None, None, None) == _abi.OK
+    reduce.ok((None, 0, None, 0, 0, None, None, None), (None, 100, None, 0, 7, None, None, None))
 
 
 def test_scratch_bytes_is_zero_for_no_tree_and_monotone(native):

@@ -4,16 +4,13 @@ that reserve room, and the range rule of csrc/forest_plan.hpp replayed on the CP
 (tests/c/forest_append_plan_test.cpp).  No compute calls here: every case returns before the library or the Python layer
 touches HIP."""
 import ctypes as C
-import json
-import os
-import re
 
 import numpy as np
 import pytest
 
 import forest_append_cases as fa
 import forest_cases as fc
-from conftest import ROOT
+from abi_support import Refusals, assert_bound, assert_exported, assert_key_resolves, assert_no_spills, isa_record
 from merkle_model import random_counts
 from no_device import NoDevice
 
@@ -22,56 +19,35 @@ LEVEL_KERNELS = ("forest_append_level_kernel", "forest_append_level_flagged_kern
 
 
 def test_header_declares_both_and_the_stub_binds_every_argument():
-    text = open(os.path.join(ROOT, "include", "vkmr_hip.h")).read()
-    declared = set(re.findall(r"VKMR_API\s+[\w\s\*]+?\b(vkmr_hip_\w+)\s*\(", text))
-    from vk_merkle_roots_amd import _abi
     # dev, stream, digests, forest, total, offsets, ntrees, max_count, first_tree, used, leaves, n_leaves, new_offsets, m, roots,
     # mutated, status: seventeen; dev, stream, offsets, ntrees, keep_trees, roots: six
     for name, nparams, scalars in ((APPEND, 17, [C.c_int, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32]),
                                    (TRUNCATE, 6, [C.c_int, C.c_uint32, C.c_uint32])):
-        assert name in declared
-        params = re.search(r"\b" + name + r"\s*\(([^)]*)\)", text).group(1).split(",")
-        assert len(params) == nparams
-        res, args = _abi.SIGNATURES[name]
-        assert res is C.c_int and len(args) == len(params)
-        assert [a for a in args if a is not C.c_void_p] == scalars
+        assert_bound(name, nparams=nparams, scalars=scalars, restype=C.c_int)
 
 
 def test_library_exports_both(native):
-    lib = C.CDLL(native.HIP_LIB)
-    assert hasattr(lib, APPEND) and hasattr(lib, TRUNCATE)
+    assert_exported(native.HIP_LIB, [APPEND, TRUNCATE])
 
 
 def test_bad_arguments_are_refused_before_any_hip_call(native):
     from vk_merkle_roots_amd import _abi
     lib = _abi.lib()
-    bad = _abi.ERR_INVALID
     d = C.c_void_p(0x1000)                 # never dereferenced: every call below returns before launching anything
     # digests, forest, total, offsets, ntrees, max_count, first_tree, used, leaves, n_leaves, new_offsets, m, roots, mutated, status
-    good = [d, d, 100, d, 8, 50, 4, 60, d, 30, d, 3, d, None, d]
-    for i in (0, 1, 3, 8, 10, 12, 14):     # each needed pointer NULL with m > 0 (mutated, 13, is NULL in `good` already)
-        args = list(good)
-        args[i] = None
-        assert lib.vkmr_hip_forest_append_async(0, None, *args) == bad, i
-        assert APPEND.encode() in lib.vkmr_hip_last_error()
+    append = Refusals(lib.vkmr_hip_forest_append_async, APPEND, good=[d, d, 100, d, 8, 50, 4, 60, d, 30, d, 3, d, None, d])
+    append.null(0, 1, 3, 8, 10, 12, 14)    # each needed pointer NULL with m > 0 (mutated, 13, is NULL in `good` already)
     # first_tree + m > ntrees (also past 2^32), used + n_leaves > total (also past 2^64), max_count == 0, too many leaves
-    for changes in ({6: 6}, {11: 5}, {6: 9}, {6: 2**32 - 1, 11: 2}, {9: 41}, {7: 71}, {7: 101, 9: 0}, {7: 2**64 - 1, 9: 2}, {5: 0},
-                    {2: (1 << 58) + 1}):
-        args = list(good)
-        for i, value in changes.items():
-            args[i] = value
-        assert lib.vkmr_hip_forest_append_async(0, None, *args) == bad, changes
-        assert APPEND.encode() in lib.vkmr_hip_last_error()
+    append.changed({6: 6}, {11: 5}, {6: 9}, {6: 2**32 - 1, 11: 2}, {9: 41}, {7: 71}, {7: 101, 9: 0}, {7: 2**64 - 1, 9: 2}, {5: 0},
+                   {2: (1 << 58) + 1})
     # m == 0 is a no-op whatever the rest
-    assert lib.vkmr_hip_forest_append_async(0, None, None, None, 100, None, 8, 50, 4, 60, None, 0, None, 0, None, None, None) == _abi.OK
-    assert lib.vkmr_hip_forest_append_async(0, None, None, None, 0, None, 0, 0, 9, 9, None, 9, None, 0, None, None, None) == _abi.OK
-    assert lib.vkmr_hip_forest_append_async(0, None, d, d, (1 << 58) + 1, d, 4, 0, 9, 0, d, 5, d, 0, d, d, d) == _abi.OK
+    append.ok((None, None, 100, None, 8, 50, 4, 60, None, 0, None, 0, None, None, None), (None, None, 0, None, 0, 0, 9, 9, None, 9, None, 0, None, None, None),
+              (d, d, (1 << 58) + 1, d, 4, 0, 9, 0, d, 5, d, 0, d, d, d))
 
-    for args in ((None, 8, 3, d), (d, 8, 3, None), (d, 8, 9, d), (None, 8, 9, None), (d, 0, 1, d)):   # a NULL pointer; keep_trees > ntrees
-        assert lib.vkmr_hip_forest_truncate_async(0, None, *args) == bad, args
-        assert TRUNCATE.encode() in lib.vkmr_hip_last_error()
-    assert lib.vkmr_hip_forest_truncate_async(0, None, None, 8, 8, None) == _abi.OK                   # keep_trees == ntrees: nothing to do
-    assert lib.vkmr_hip_forest_truncate_async(0, None, None, 0, 0, None) == _abi.OK
+    truncate = Refusals(lib.vkmr_hip_forest_truncate_async, TRUNCATE, good=[d, 8, 3, d])              # offsets, ntrees, keep_trees, roots
+    truncate.null(0, 3)
+    truncate.changed({2: 9}, {0: None, 2: 9, 3: None}, {1: 0, 2: 1})                                  # keep_trees > ntrees
+    truncate.ok((None, 8, 8, None), (None, 0, 0, None))                                               # keep_trees == ntrees: nothing to do
 
 
 def host_forest(counts=(4, 0, 7, 0, 0, 0), total=20, max_count=8, used_trees=3):
@@ -212,23 +188,12 @@ def test_the_level_ranges_replayed_over_a_thousand_random_forests(native, plan_e
 def test_the_append_level_kernels_hold_one_hash_block_and_the_build_lists_them(native):
     from vk_merkle_roots_amd import isa_prio_pass
     keys = isa_prio_pass.EXPECTED_HASH_BLOCKS
-    for mine, mangled in zip(LEVEL_KERNELS, ("_Z26forest_append_level_kernelPK", "_Z34forest_append_level_flagged_kernelPK")):
+    for mine in LEVEL_KERNELS:
         assert keys[mine] == 1
-        # the pass matches by substring, first match wins: the name must resolve to its own key and shadow nobody's
-        assert next(k for k in keys if k in mangled) == mine
-        for other in keys:
-            assert other == mine or (other not in mine and mine not in other), other
-    path = os.path.splitext(native.HIP_LIB)[0] + ".isa.json"
-    if os.path.exists(path):               # written by a build that ran the issue pass (tests/test_isa_prio_pass.py covers its absence)
-        rec = json.load(open(path))
+        assert_key_resolves(mine)
+    rec = isa_record(native)
+    if rec is not None:                    # written by a build that ran the issue pass (tests/test_isa_prio_pass.py covers its absence)
         assert rec["audit"]["block_count_errors"] == [] and rec["audit"]["unclassified"] == []
         mine = {k: v for k, v in rec["audit"]["blocks"].items() if "forest_append" in k or "forest_truncate" in k}
         assert sorted(mine.values()) == [1, 1] and all(any(n in k for n in LEVEL_KERNELS) for k in mine)   # the check, leaves, offsets, truncate: none
-    listing = os.path.join(ROOT, "build", "obj", os.path.basename(native.HIP_LIB), "device.s")
-    if os.path.exists(listing):            # the device assembly that build left behind: the code object's own metadata of the kernels
-        text = open(listing).read()
-        for name in LEVEL_KERNELS:
-            meta = re.search(r"\.name:\s+_Z\d+" + name + r"P\w*\n((?:    \..*\n)+)", text).group(1)
-            fields = dict(re.findall(r"\.(\w+):\s+(\S+)", meta))
-            assert fields["private_segment_fixed_size"] == "0" and fields["sgpr_spill_count"] == "0" and fields["vgpr_spill_count"] == "0"
-            assert int(fields["vgpr_count"]) <= 64          # 512 registers a lane, 8 wavefronts per SIMD
+    assert_no_spills(native, LEVEL_KERNELS, max_vgprs=64)  # 512 registers a lane, 8 wavefronts per SIMD

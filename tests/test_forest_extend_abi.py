@@ -4,15 +4,12 @@ shrink, and the range rule of csrc/forest_plan.hpp replayed on the CPU with fore
 (tests/c/forest_extend_plan_test.cpp), the lone-node clause pinned by the failure of the rule without it.  No compute calls
 here: every case returns before the library or the Python layer touches HIP."""
 import ctypes as C
-import json
-import os
-import re
 
 import numpy as np
 import pytest
 
 import forest_extend_cases as fe
-from conftest import ROOT
+from abi_support import Refusals, assert_bound, assert_exported, assert_key_resolves, assert_no_spills, isa_record
 from merkle_model import random_counts, tree_height
 from no_device import NoDevice
 
@@ -22,67 +19,37 @@ KERNELS = ("forest_extend_check_kernel", "forest_extend_offsets_kernel", LEVEL_K
 
 
 def test_header_declares_both_and_the_stub_binds_every_argument():
-    text = open(os.path.join(ROOT, "include", "vkmr_hip.h")).read()
-    declared = set(re.findall(r"VKMR_API\s+[\w\s\*]+?\b(vkmr_hip_\w+)\s*\(", text))
-    from vk_merkle_roots_amd import _abi
     # dev, stream, digests, forest, total, offsets, ntrees, max_count, tree, count, used, leaves, n_leaves, roots, mutated, status:
     # sixteen; the shrink has r for leaves and n_leaves: fifteen
     for name, nparams, scalars in ((EXTEND, 16, [C.c_int, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64]),
                                    (SHRINK, 15, [C.c_int, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint64])):
-        assert name in declared
-        params = re.search(r"\b" + name + r"\s*\(([^)]*)\)", text).group(1).split(",")
-        assert len(params) == nparams
-        res, args = _abi.SIGNATURES[name]
-        assert res is C.c_int and len(args) == len(params)
-        assert [a for a in args if a is not C.c_void_p] == scalars
+        assert_bound(name, nparams=nparams, scalars=scalars, restype=C.c_int)
 
 
 def test_library_exports_both(native):
-    lib = C.CDLL(native.HIP_LIB)
-    assert hasattr(lib, EXTEND) and hasattr(lib, SHRINK)
+    assert_exported(native.HIP_LIB, [EXTEND, SHRINK])
 
 
 def test_bad_arguments_are_refused_before_any_hip_call(native):
     from vk_merkle_roots_amd import _abi
     lib = _abi.lib()
-    bad = _abi.ERR_INVALID
     d = C.c_void_p(0x1000)                 # never dereferenced: every call below returns before launching anything
     # digests, forest, total, offsets, ntrees, max_count, tree, count, used, leaves, n_leaves, roots, mutated, status
-    good = [d, d, 100, d, 8, 50, 4, 20, 60, d, 30, d, None, d]
-    for i in (0, 1, 3, 9, 11, 13):         # each needed pointer NULL (mutated, 12, is NULL in `good` already)
-        args = list(good)
-        args[i] = None
-        assert lib.vkmr_hip_forest_extend_async(0, None, *args) == bad, i
-        assert EXTEND.encode() in lib.vkmr_hip_last_error()
+    extend = Refusals(lib.vkmr_hip_forest_extend_async, EXTEND, good=[d, d, 100, d, 8, 50, 4, 20, 60, d, 30, d, None, d])
+    extend.null(0, 1, 3, 9, 11, 13)        # each needed pointer NULL (mutated, 12, is NULL in `good` already)
     # tree >= ntrees (also the last 32-bit number), count + n_leaves > max_count (also past 2^64), used + n_leaves > total (also
     # past 2^64), more leaves in the tree than in use, max_count == 0, total > 2^58
-    for changes in ({6: 8}, {6: 9}, {6: 2**32 - 1}, {10: 31}, {7: 21}, {7: 51, 10: 1}, {7: 2**64 - 1, 10: 2}, {10: 41, 5: 100}, {8: 71}, {8: 101, 10: 1},
-                    {8: 2**64 - 1, 10: 2}, {7: 20, 8: 19, 10: 1}, {5: 0}, {2: (1 << 58) + 1}):
-        args = list(good)
-        for i, value in changes.items():
-            args[i] = value
-        assert lib.vkmr_hip_forest_extend_async(0, None, *args) == bad, changes
-        assert EXTEND.encode() in lib.vkmr_hip_last_error()
+    extend.changed({6: 8}, {6: 9}, {6: 2**32 - 1}, {10: 31}, {7: 21}, {7: 51, 10: 1}, {7: 2**64 - 1, 10: 2}, {10: 41, 5: 100}, {8: 71}, {8: 101, 10: 1},
+                   {8: 2**64 - 1, 10: 2}, {7: 20, 8: 19, 10: 1}, {5: 0}, {2: (1 << 58) + 1})
     # n_leaves == 0 is a no-op whatever the rest
-    assert lib.vkmr_hip_forest_extend_async(0, None, None, None, 100, None, 8, 50, 4, 20, 60, None, 0, None, None, None) == _abi.OK
-    assert lib.vkmr_hip_forest_extend_async(0, None, None, None, 0, None, 0, 0, 9, 9, 3, None, 0, None, None, None) == _abi.OK
-    assert lib.vkmr_hip_forest_extend_async(0, None, d, d, (1 << 58) + 1, d, 4, 0, 9, 0, 0, d, 0, d, d, d) == _abi.OK
+    extend.ok((None, None, 100, None, 8, 50, 4, 20, 60, None, 0, None, None, None), (None, None, 0, None, 0, 0, 9, 9, 3, None, 0, None, None, None),
+              (d, d, (1 << 58) + 1, d, 4, 0, 9, 0, 0, d, 0, d, d, d))
 
     # digests, forest, total, offsets, ntrees, max_count, tree, count, used, r, roots, mutated, status
-    good = [d, d, 100, d, 8, 50, 4, 20, 60, 7, d, None, d]
-    for i in (0, 1, 3, 10, 12):
-        args = list(good)
-        args[i] = None
-        assert lib.vkmr_hip_forest_shrink_async(0, None, *args) == bad, i
-        assert SHRINK.encode() in lib.vkmr_hip_last_error()
-    for changes in ({6: 8}, {6: 2**32 - 1}, {9: 21}, {9: 2**64 - 1}, {7: 0}, {8: 19}, {8: 101}, {5: 0}, {2: (1 << 58) + 1}):
-        args = list(good)
-        for i, value in changes.items():
-            args[i] = value
-        assert lib.vkmr_hip_forest_shrink_async(0, None, *args) == bad, changes
-        assert SHRINK.encode() in lib.vkmr_hip_last_error()
-    assert lib.vkmr_hip_forest_shrink_async(0, None, None, None, 100, None, 8, 50, 4, 20, 60, 0, None, None, None) == _abi.OK
-    assert lib.vkmr_hip_forest_shrink_async(0, None, d, d, (1 << 58) + 1, d, 0, 0, 9, 0, 0, 0, d, d, d) == _abi.OK
+    shrink = Refusals(lib.vkmr_hip_forest_shrink_async, SHRINK, good=[d, d, 100, d, 8, 50, 4, 20, 60, 7, d, None, d])
+    shrink.null(0, 1, 3, 10, 12)
+    shrink.changed({6: 8}, {6: 2**32 - 1}, {9: 21}, {9: 2**64 - 1}, {7: 0}, {8: 19}, {8: 101}, {5: 0}, {2: (1 << 58) + 1})
+    shrink.ok((None, None, 100, None, 8, 50, 4, 20, 60, 0, None, None, None), (d, d, (1 << 58) + 1, d, 0, 0, 9, 0, 0, 0, d, d, d))
 
 
 def host_forest(counts=(4, 0, 7, 0, 0, 0), total=20, max_count=8, used_trees=3):
@@ -210,24 +177,13 @@ def test_the_kernel_keys_resolve_to_themselves_and_the_build_lists_them(native):
     from vk_merkle_roots_amd import isa_prio_pass
     keys = isa_prio_pass.EXPECTED_HASH_BLOCKS
     assert keys[LEVEL_KERNEL] == 1
-    # the pass matches by substring, first match wins: the name must resolve to its own key and shadow nobody's
-    assert next(k for k in keys if k in "_Z26forest_extend_level_kernelPK") == LEVEL_KERNEL
-    for other in keys:
-        assert other == LEVEL_KERNEL or (other not in LEVEL_KERNEL and LEVEL_KERNEL not in other), other
+    assert_key_resolves(LEVEL_KERNEL)
     for name in KERNELS:                   # existing tests pick their kernels out of the build's record by these substrings
         assert not any(s in name for s in ("forest_append", "forest_truncate", "mutated"))
         assert name == LEVEL_KERNEL or not any(k in name for k in keys), name      # no hash expected in the others
-    path = os.path.splitext(native.HIP_LIB)[0] + ".isa.json"
-    if os.path.exists(path):               # written by a build that ran the issue pass (tests/test_isa_prio_pass.py covers its absence)
-        rec = json.load(open(path))
+    rec = isa_record(native)
+    if rec is not None:                    # written by a build that ran the issue pass (tests/test_isa_prio_pass.py covers its absence)
         assert rec["audit"]["block_count_errors"] == [] and rec["audit"]["unclassified"] == []
         mine = {k: v for k, v in rec["audit"]["blocks"].items() if "forest_extend" in k}
         assert list(mine.values()) == [1] and LEVEL_KERNEL in next(iter(mine))     # the check, the offsets, the scan: none
-    listing = os.path.join(ROOT, "build", "obj", os.path.basename(native.HIP_LIB), "device.s")
-    if os.path.exists(listing):            # the device assembly that build left behind: the code object's own metadata of the kernels
-        text = open(listing).read()
-        for name in KERNELS:
-            meta = re.search(r"\.name:\s+_Z\d+" + name + r"P\w*\n((?:    \..*\n)+)", text).group(1)
-            fields = dict(re.findall(r"\.(\w+):\s+(\S+)", meta))
-            assert fields["private_segment_fixed_size"] == "0" and fields["sgpr_spill_count"] == "0" and fields["vgpr_spill_count"] == "0"
-            assert int(fields["vgpr_count"]) <= 64          # 512 registers a lane, 8 wavefronts per SIMD
+    assert_no_spills(native, KERNELS, max_vgprs=64)        # 512 registers a lane, 8 wavefronts per SIMD

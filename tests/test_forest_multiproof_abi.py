@@ -4,9 +4,7 @@ the host counterparts vkmr_host_cpu_forest_multiproof and vkmr_host_cpu_verify_f
 against the single tree's multiproof, and one run of both host functions under AddressSanitizer and UBSan in a stand-alone
 program (tests/c/forest_multiproof_host_test.cpp).  No compute calls on a device here."""
 import ctypes as C
-import json
 import os
-import re
 import subprocess
 
 import numpy as np
@@ -15,6 +13,7 @@ import pytest
 import forest_cases as fc
 import forest_multiproof_cases as fm
 import multiproof_cases as mc
+from abi_support import Refusals, assert_bound, assert_exported, assert_key_resolves, assert_no_spills, isa_record
 from conftest import ROOT
 from merkle_model import random_counts
 from no_device import NoDevice
@@ -32,66 +31,34 @@ def case_leaves(name):
 
 def test_header_library_and_stub_agree_on_the_new_symbols(native):
     from vk_merkle_roots_amd import _abi
-    text = open(os.path.join(ROOT, "include", "vkmr_hip.h")).read()
-    declared = set(re.findall(r"VKMR_API\s+[\w\s\*]+?\b(vkmr_hip_\w+)\s*\(", text))
-    lib = C.CDLL(native.HIP_LIB)
-    for name in ENTRY_POINTS:
-        assert name in declared, name
-        assert hasattr(lib, name), name
-        params = re.search(r"\b" + name + r"\s*\(([^)]*)\)", text).group(1).split(",")
-        assert len(_abi.SIGNATURES[name][1]) == len(params), name
+    assert_exported(native.HIP_LIB, ENTRY_POINTS)
     # max_nodes(total, ntrees, max_count, k); scratch_bytes(k, stride); the gather: dev, s, digests, forest, total, offsets, ntrees,
     # max_count, trees, indices, k, scratch, nodes, nodes_capacity, heights, info; the verifier: dev, s, leaves, trees, indices,
     # heights, k, stride, nodes, m, roots, ntrees, scratch, ok
-    assert [len(_abi.SIGNATURES[n][1]) for n in ENTRY_POINTS] == [4, 2, 16, 14]
-    assert _abi.SIGNATURES[ENTRY_POINTS[0]][0] is C.c_size_t and _abi.SIGNATURES[ENTRY_POINTS[1]][0] is C.c_size_t
-    assert [a for a in _abi.SIGNATURES[ENTRY_POINTS[2]][1] if a is not C.c_void_p] == [C.c_int, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64]
-    assert [a for a in _abi.SIGNATURES[ENTRY_POINTS[3]][1] if a is not C.c_void_p] == [C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32]
-    host = C.CDLL(native.HOST_LIB)
-    for name in HOST_ENTRY_POINTS:
-        assert hasattr(host, name) and name in _abi.HOST_SIGNATURES, name
+    assert_bound(ENTRY_POINTS[0], nparams=4, restype=C.c_size_t)
+    assert_bound(ENTRY_POINTS[1], nparams=2, restype=C.c_size_t)
+    assert_bound(ENTRY_POINTS[2], nparams=16, scalars=[C.c_int, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64])
+    assert_bound(ENTRY_POINTS[3], nparams=14, scalars=[C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32])
+    assert_exported(native.HOST_LIB, HOST_ENTRY_POINTS)
+    assert all(name in _abi.HOST_SIGNATURES for name in HOST_ENTRY_POINTS)
 
 
 def test_bad_arguments_are_refused_before_any_hip_call(native):
     from vk_merkle_roots_amd import _abi
     lib = _abi.lib()
-    bad = _abi.ERR_INVALID
     d = C.c_void_p(0x1000)                 # never dereferenced: every call below returns before launching anything
-    name = b"vkmr_hip_forest_multiproof_async"
     # digests, forest, total, offsets, ntrees, max_count, trees, indices, k, scratch, nodes, nodes_capacity, heights, info
-    good = [d, d, 100, d, 4, 50, d, d, 8, d, d, 64, d, d]
-    for i in (0, 1, 3, 6, 7, 9, 10, 12, 13):   # each pointer NULL with k > 0 (the nodes with a capacity above 0)
-        args = list(good)
-        args[i] = None
-        assert lib.vkmr_hip_forest_multiproof_async(0, None, *args) == bad, i
-        assert name in lib.vkmr_hip_last_error()
-    for i, value in ((4, 0), (2, 0), (5, 0), (2, (1 << 58) + 1), (9, C.c_void_p(0x1008))):   # ntrees, total, max_count == 0; too many leaves; alignment
-        args = list(good)
-        args[i] = value
-        assert lib.vkmr_hip_forest_multiproof_async(0, None, *args) == bad, (i, value)
-        assert name in lib.vkmr_hip_last_error()
+    gather = Refusals(lib.vkmr_hip_forest_multiproof_async, "vkmr_hip_forest_multiproof_async", good=[d, d, 100, d, 4, 50, d, d, 8, d, d, 64, d, d])
+    gather.null(0, 1, 3, 6, 7, 9, 10, 12, 13)  # each pointer NULL with k > 0 (the nodes with a capacity above 0)
+    gather.changed({4: 0}, {2: 0}, {5: 0}, {2: (1 << 58) + 1}, {9: C.c_void_p(0x1008)})      # ntrees, total, max_count == 0; too many leaves; alignment
     # k == 0 is a no-op whatever the rest
-    assert lib.vkmr_hip_forest_multiproof_async(0, None, None, None, 100, None, 4, 50, None, None, 0, None, None, 0, None, None) == _abi.OK
-    assert lib.vkmr_hip_forest_multiproof_async(0, None, None, None, 0, None, 0, 0, None, None, 0, None, None, 7, None, None) == _abi.OK
+    gather.ok((None, None, 100, None, 4, 50, None, None, 0, None, None, 0, None, None), (None, None, 0, None, 0, 0, None, None, 0, None, None, 7, None, None))
 
-    name = b"vkmr_hip_verify_forest_multiproof_async"
     # leaves, trees, indices, heights, k, stride, nodes, m, roots, ntrees, scratch, ok
-    good = [d, d, d, d, 8, 12, d, 30, d, 4, d, d]
-    for i in (0, 1, 2, 3, 6, 8, 10, 11):   # each pointer NULL with k > 0 (the nodes with m > 0)
-        args = list(good)
-        args[i] = None
-        assert lib.vkmr_hip_verify_forest_multiproof_async(0, None, *args) == bad, i
-        assert name in lib.vkmr_hip_last_error()
-    for stride in (0, 64, 100):
-        args = list(good)
-        args[5] = stride
-        assert lib.vkmr_hip_verify_forest_multiproof_async(0, None, *args) == bad, stride
-        assert name in lib.vkmr_hip_last_error()
-    args = list(good)
-    args[10] = C.c_void_p(0x1004)
-    assert lib.vkmr_hip_verify_forest_multiproof_async(0, None, *args) == bad
-    assert lib.vkmr_hip_verify_forest_multiproof_async(0, None, None, None, None, None, 0, 12, None, 0, None, 4, None, None) == _abi.OK   # k == 0
-    assert lib.vkmr_hip_verify_forest_multiproof_async(0, None, None, None, None, None, 0, 0, None, 9, None, 0, None, None) == _abi.OK
+    verify = Refusals(lib.vkmr_hip_verify_forest_multiproof_async, "vkmr_hip_verify_forest_multiproof_async", good=[d, d, d, d, 8, 12, d, 30, d, 4, d, d])
+    verify.null(0, 1, 2, 3, 6, 8, 10, 11)  # each pointer NULL with k > 0 (the nodes with m > 0)
+    verify.changed({5: 0}, {5: 64}, {5: 100}, {10: C.c_void_p(0x1004)})                      # the stride; the scratch's alignment
+    verify.ok((None, None, None, None, 0, 12, None, 0, None, 4, None, None), (None, None, None, None, 0, 0, None, 9, None, 0, None, None))   # k == 0
 
 
 def test_scratch_bytes_is_one_aligned_size_for_gather_and_verifier(native):
@@ -363,23 +330,13 @@ def test_the_level_kernel_holds_one_hash_block_and_the_build_lists_it(native):
     from vk_merkle_roots_amd import isa_prio_pass
     mine = "verify_forest_multiproof_level_kernel"
     assert isa_prio_pass.EXPECTED_HASH_BLOCKS[mine] == 1
-    # the pass matches by substring, first match wins: the name must resolve to its own key and shadow nobody's
-    assert next(k for k in isa_prio_pass.EXPECTED_HASH_BLOCKS if k in "_Z37verify_forest_multiproof_level_kernelPK") == mine
-    for other in isa_prio_pass.EXPECTED_HASH_BLOCKS:
-        assert other == mine or (other not in mine and mine not in other), other
-    path = os.path.splitext(native.HIP_LIB)[0] + ".isa.json"
-    if os.path.exists(path):               # written by a build that ran the issue pass (tests/test_isa_prio_pass.py covers its absence)
-        rec = json.load(open(path))
+    assert_key_resolves(mine)
+    rec = isa_record(native)
+    if rec is not None:                    # written by a build that ran the issue pass (tests/test_isa_prio_pass.py covers its absence)
         assert rec["audit"]["block_count_errors"] == [] and rec["audit"]["unclassified"] == []
         blocks = {k: v for k, v in rec["audit"]["blocks"].items() if "forest_multiproof" in k}
         assert list(blocks.values()) == [1] and mine in next(iter(blocks))      # the check, the heights, the masks, the gather and the finish hold none
-    listing = os.path.join(ROOT, "build", "obj", os.path.basename(native.HIP_LIB), "device.s")
-    if os.path.exists(listing):            # the device assembly that build left behind: the code object's own metadata of the kernel
-        text = open(listing).read()
-        meta = re.search(r"\.name:\s+_Z\d+" + mine + r"\w*\n((?:    \..*\n)+)", text).group(1)
-        fields = dict(re.findall(r"\.(\w+):\s+(\S+)", meta))
-        assert fields["private_segment_fixed_size"] == "0" and fields["sgpr_spill_count"] == "0" and fields["vgpr_spill_count"] == "0"
-        assert int(fields["vgpr_count"]) <= 64          # 512 registers a lane, 8 wavefronts per SIMD
+    assert_no_spills(native, [mine], max_vgprs=64, prefix=True)        # 512 registers a lane, 8 wavefronts per SIMD
 
 
 def test_both_host_functions_under_address_and_undefined_behaviour_sanitizers(native, tmp_path):

@@ -2,70 +2,49 @@
 vkmr_host_cpu_forest_mutated against the rule restated in tests/forest_mutation_cases.py, and the build's record of the new
 kernels."""
 import ctypes as C
-import json
-import os
 
 import numpy as np
 import pytest
 
 import forest_cases as fc
 import forest_mutation_cases as fm
+from abi_support import Refusals, assert_bound, assert_exported, assert_key_resolves, isa_record
 
 NEW = {"vkmr_hip_reduce_forest_mutated_async": 11, "vkmr_hip_reduce_forest_tree_mutated_async": 11, "vkmr_hip_forest_tree_mutated_async": 9}
 
 
 def test_library_exports_the_symbols_and_the_stub_binds_them(native):
     from vk_merkle_roots_amd import _abi
-    lib = C.CDLL(native.HIP_LIB)
+    assert_exported(native.HIP_LIB, NEW)
     for name, nargs in NEW.items():
-        assert hasattr(lib, name), name
-        assert len(_abi.SIGNATURES[name][1]) == nargs
+        assert_bound(name, nparams=nargs)
     # the calls beside them keep their arguments
-    assert len(_abi.SIGNATURES["vkmr_hip_reduce_forest_async"][1]) == 10
-    assert len(_abi.SIGNATURES["vkmr_hip_reduce_forest_tree_async"][1]) == 10
-    assert hasattr(C.CDLL(native.HOST_LIB), "vkmr_host_cpu_forest_mutated")
+    assert_bound("vkmr_hip_reduce_forest_async", nparams=10)
+    assert_bound("vkmr_hip_reduce_forest_tree_async", nparams=10)
+    assert_exported(native.HOST_LIB, ["vkmr_host_cpu_forest_mutated"])
     assert len(_abi.HOST_SIGNATURES["vkmr_host_cpu_forest_mutated"][1]) == 5
 
 
 @pytest.mark.parametrize("name", ["vkmr_hip_reduce_forest_mutated_async", "vkmr_hip_reduce_forest_tree_mutated_async"])
 def test_the_builds_refuse_bad_arguments_before_any_hip_call(native, name):
     from vk_merkle_roots_amd import _abi
-    fn = getattr(_abi.lib(), name)
     d = C.c_void_p(0x1000)                    # never dereferenced: every call below returns before launching anything
-    good = [d, 100, d, 4, 50, d, d, d, d]     # digests, total, offsets, ntrees, max_count, scratch / forest, roots, mutated, status
-    for i in (0, 2, 5, 6, 7, 8):              # each pointer NULL with ntrees > 0; 7 is the new one
-        args = list(good)
-        args[i] = None
-        assert fn(0, None, *args) == _abi.ERR_INVALID, i
-        assert _abi.lib().vkmr_hip_last_error()
-    args = list(good)
-    args[4] = 0                               # max_count == 0
-    assert fn(0, None, *args) == _abi.ERR_INVALID
-    args = list(good)
-    args[5] = C.c_void_p(0x1008)              # the level buffer not 16-byte aligned
-    assert fn(0, None, *args) == _abi.ERR_INVALID
+    # digests, total, offsets, ntrees, max_count, scratch / forest, roots, mutated, status
+    build = Refusals(getattr(_abi.lib(), name), name, good=[d, 100, d, 4, 50, d, d, d, d])
+    build.null(0, 2, 5, 6, 7, 8)              # each pointer NULL with ntrees > 0; 7 is the new one
+    build.changed({4: 0}, {5: C.c_void_p(0x1008)})         # max_count == 0; the level buffer not 16-byte aligned
     # ntrees == 0 does nothing whatever the rest
-    assert fn(0, None, None, 0, None, 0, 0, None, None, None, None) == _abi.OK
-    assert fn(0, None, None, 100, None, 0, 7, None, None, None, None) == _abi.OK
+    build.ok((None, 0, None, 0, 0, None, None, None, None), (None, 100, None, 0, 7, None, None, None, None))
 
 
 def test_the_scan_refuses_bad_arguments_before_any_hip_call(native):
     from vk_merkle_roots_amd import _abi
-    fn = _abi.lib().vkmr_hip_forest_tree_mutated_async
     d = C.c_void_p(0x1000)
-    good = [d, d, 100, d, 4, 50, d]           # digests, forest, total, offsets, ntrees, max_count, mutated
-    for i in (0, 1, 3, 6):
-        args = list(good)
-        args[i] = None
-        assert fn(0, None, *args) == _abi.ERR_INVALID, i
-    args = list(good)
-    args[5] = 0                               # max_count == 0
-    assert fn(0, None, *args) == _abi.ERR_INVALID
-    args = list(good)
-    args[2] = (1 << 58) + 1                   # more leaves than a forest takes
-    assert fn(0, None, *args) == _abi.ERR_INVALID
-    assert fn(0, None, None, None, 0, None, 0, 0, None) == _abi.OK
-    assert fn(0, None, None, None, 100, None, 0, 7, None) == _abi.OK
+    # digests, forest, total, offsets, ntrees, max_count, mutated
+    scan = Refusals(_abi.lib().vkmr_hip_forest_tree_mutated_async, "vkmr_hip_forest_tree_mutated_async", good=[d, d, 100, d, 4, 50, d])
+    scan.null(0, 1, 3, 6)
+    scan.changed({5: 0}, {2: (1 << 58) + 1})  # max_count == 0; more leaves than a forest takes
+    scan.ok((None, None, 0, None, 0, 0, None), (None, None, 100, None, 0, 7, None))
 
 
 @pytest.mark.parametrize("name", sorted(fm.CASES))
@@ -157,21 +136,18 @@ def test_the_new_kernel_holds_one_hash_block_and_shadows_no_key(native):
     keys = isa_prio_pass.EXPECTED_HASH_BLOCKS
     mine = "forest_level_mutated_kernel"
     assert keys[mine] == 1
-    assert next(k for k in keys if k in "_Z27forest_level_mutated_kernelPK") == mine
-    for other in keys:
-        assert other == mine or (other not in mine and mine not in other), other
+    assert_key_resolves(mine)
     # the pass matches by substring, first match wins: every other kernel resolves to the key it resolved to without the new one
     before = [k for k in keys if k != mine]
     for k in before:
         for name in (f"_Z{len(k)}{k}PK4Node", f"_Z10{k}ILi64ELi5ELb1EEvPK"):
             assert next(x for x in keys if x in name) == next(x for x in before if x in name), name
-    path = os.path.splitext(native.HIP_LIB)[0] + ".isa.json"
-    if not os.path.exists(path):           # a build without the llvm tools ran no issue pass and wrote no counts: the nm check stands alone
+    rec = isa_record(native)
+    if rec is None:                        # a build without the llvm tools ran no issue pass and wrote no counts: the nm check stands alone
         import subprocess
         syms = subprocess.run(["nm", "-C", native.HIP_LIB], stdout=subprocess.PIPE).stdout.decode()
         assert "forest_level_mutated_kernel" in syms and "forest_scan_mutated_kernel" in syms
         return
-    rec = json.load(open(path))
     assert rec["audit"]["block_count_errors"] == [] and rec["audit"]["unclassified"] == []
     blocks = {k: v for k, v in rec["audit"]["blocks"].items() if "mutated" in k}
     assert list(blocks.values()) == [1] and mine in next(iter(blocks))      # the scan holds none

@@ -3,9 +3,6 @@ csrc/forest_plan.hpp replayed on the CPU (tests/c/forest_store_plan_test.cpp), a
 vkmr_host_cpu_forest_proofs against a hashlib restatement (tests/forest_proof_cases.py), the oracle's roots and what the
 reference's own CPU path returned."""
 import ctypes as C
-import json
-import os
-import re
 import subprocess
 
 import numpy as np
@@ -13,7 +10,7 @@ import pytest
 
 import forest_cases as fc
 import forest_proof_cases as fp
-from conftest import ROOT
+from abi_support import Refusals, assert_bound, assert_exported, isa_record
 
 ENTRY_POINTS = ("vkmr_hip_forest_tree_bytes", "vkmr_hip_reduce_forest_tree_async", "vkmr_hip_forest_proofs_async",
                 "vkmr_hip_verify_forest_proofs_async")
@@ -26,72 +23,38 @@ def plan_exe(tmp_path_factory):
 
 def test_header_declares_and_library_exports_the_stored_forest_entry_points(native):
     from vk_merkle_roots_amd import _abi
-    text = open(os.path.join(ROOT, "include", "vkmr_hip.h")).read()
-    declared = set(re.findall(r"VKMR_API\s+[\w\s\*]+?\b(vkmr_hip_\w+)\s*\(", text))
-    lib = C.CDLL(native.HIP_LIB)
-    for name in ENTRY_POINTS:
-        assert name in declared, name
-        assert hasattr(lib, name), name
-        assert name in _abi.SIGNATURES, name
-    assert [len(_abi.SIGNATURES[n][1]) for n in ENTRY_POINTS] == [3, 10, 13, 12]
-    assert hasattr(C.CDLL(native.HOST_LIB), "vkmr_host_cpu_forest_proofs")
+    assert_exported(native.HIP_LIB, ENTRY_POINTS)
+    for name, nparams in zip(ENTRY_POINTS, [3, 10, 13, 12]):
+        assert_bound(name, nparams=nparams)
+    assert_exported(native.HOST_LIB, ["vkmr_host_cpu_forest_proofs"])
     assert "vkmr_host_cpu_forest_proofs" in _abi.HOST_SIGNATURES
 
 
 def test_bad_arguments_are_refused_before_any_hip_call(native):
     from vk_merkle_roots_amd import _abi
     lib = _abi.lib()
-    bad = _abi.ERR_INVALID
     d = C.c_void_p(0x1000)                 # never dereferenced: every call below returns before launching anything
     # build: digests, total, offsets, ntrees, max_count, forest, roots, status
-    good = [d, 100, d, 4, 50, d, d, d]
-    for i in (0, 2, 5, 6, 7):              # each pointer NULL with ntrees > 0
-        args = list(good)
-        args[i] = None
-        assert lib.vkmr_hip_reduce_forest_tree_async(0, None, *args) == bad, i
-    args = list(good)
-    args[4] = 0                            # max_count == 0
-    assert lib.vkmr_hip_reduce_forest_tree_async(0, None, *args) == bad
-    assert b"vkmr_hip_reduce_forest_tree_async" in lib.vkmr_hip_last_error()
-    args = list(good)
-    args[5] = C.c_void_p(0x1008)           # forest not 16-byte aligned
-    assert lib.vkmr_hip_reduce_forest_tree_async(0, None, *args) == bad
-    args = list(good)
-    args[1] = (1 << 58) + 1                # more leaves than the plan's shifts allow
-    assert lib.vkmr_hip_reduce_forest_tree_async(0, None, *args) == bad
-    assert lib.vkmr_hip_reduce_forest_tree_async(0, None, None, 0, None, 0, 0, None, None, None) == _abi.OK      # ntrees == 0: nothing to do
-    assert lib.vkmr_hip_reduce_forest_tree_async(0, None, None, 100, None, 0, 7, None, None, None) == _abi.OK
+    build = Refusals(lib.vkmr_hip_reduce_forest_tree_async, "vkmr_hip_reduce_forest_tree_async", good=[d, 100, d, 4, 50, d, d, d])
+    build.null(0, 2, 5, 6, 7)              # each pointer NULL with ntrees > 0
+    # max_count == 0; forest not 16-byte aligned; more leaves than the plan's shifts allow
+    build.changed({4: 0}, {5: C.c_void_p(0x1008)}, {1: (1 << 58) + 1})
+    build.ok((None, 0, None, 0, 0, None, None, None), (None, 100, None, 0, 7, None, None, None))      # ntrees == 0: nothing to do
     # the roots-only call still names itself in its refusals
-    assert lib.vkmr_hip_reduce_forest_async(0, None, d, 100, d, 4, 0, d, d, d) == bad
-    assert b"vkmr_hip_reduce_forest_async" in lib.vkmr_hip_last_error()
+    Refusals(lib.vkmr_hip_reduce_forest_async, "vkmr_hip_reduce_forest_async", good=[d, 100, d, 4, 50, d, d, d]).changed({4: 0})
 
     # gather: digests, forest, total, offsets, ntrees, max_count, trees, indices, k, siblings, heights
-    good = [d, d, 100, d, 4, 50, d, d, 8, d, d]
-    for i in (0, 1, 3, 6, 7, 9, 10):
-        args = list(good)
-        args[i] = None
-        assert lib.vkmr_hip_forest_proofs_async(0, None, *args) == bad, i
-    args = list(good)
-    args[5] = 0                            # max_count == 0
-    assert lib.vkmr_hip_forest_proofs_async(0, None, *args) == bad
-    args = list(good)
-    args[2] = (1 << 58) + 1
-    assert lib.vkmr_hip_forest_proofs_async(0, None, *args) == bad
+    gather = Refusals(lib.vkmr_hip_forest_proofs_async, "vkmr_hip_forest_proofs_async", good=[d, d, 100, d, 4, 50, d, d, 8, d, d])
+    gather.null(0, 1, 3, 6, 7, 9, 10)
+    gather.changed({5: 0}, {2: (1 << 58) + 1})             # max_count == 0; too many leaves
     # (k * H cells past the launch limit cannot be reached: k < 2^32 and H <= 58 stay below 2^31 workgroups of 256 lanes)
-    assert lib.vkmr_hip_forest_proofs_async(0, None, None, None, 100, None, 4, 50, None, None, 0, None, None) == _abi.OK   # k == 0
+    gather.ok((None, None, 100, None, 4, 50, None, None, 0, None, None))       # k == 0
 
     # verify: leaves, trees, indices, siblings, heights, k, stride, roots, ntrees, ok
-    good = [d, d, d, d, d, 8, 12, d, 4, d]
-    for i in (0, 1, 2, 3, 4, 7, 9):
-        args = list(good)
-        args[i] = None
-        assert lib.vkmr_hip_verify_forest_proofs_async(0, None, *args) == bad, i
-    for stride in (0, 64, 100):
-        args = list(good)
-        args[6] = stride
-        assert lib.vkmr_hip_verify_forest_proofs_async(0, None, *args) == bad, stride
-    assert lib.vkmr_hip_verify_forest_proofs_async(0, None, None, None, None, None, None, 0, 12, None, 4, None) == _abi.OK  # k == 0
-    assert lib.vkmr_hip_last_error()
+    verify = Refusals(lib.vkmr_hip_verify_forest_proofs_async, "vkmr_hip_verify_forest_proofs_async", good=[d, d, d, d, d, 8, 12, d, 4, d])
+    verify.null(0, 1, 2, 3, 4, 7, 9)
+    verify.changed({6: 0}, {6: 64}, {6: 100})              # the stride
+    verify.ok((None, None, None, None, None, 0, 12, None, 4, None))            # k == 0
 
 
 def test_forest_tree_bytes_is_its_closed_form(native):
@@ -245,9 +208,8 @@ def test_python_layer_refuses_bad_counts_before_any_device_call(native):
 def test_the_forest_verifier_holds_one_hash_block_and_the_build_lists_it(native):
     from vk_merkle_roots_amd import isa_prio_pass
     assert isa_prio_pass.EXPECTED_HASH_BLOCKS["verify_forest_proofs_kernel"] == 1
-    path = os.path.splitext(native.HIP_LIB)[0] + ".isa.json"
-    if os.path.exists(path):               # written by a build that ran the issue pass (tests/test_isa_prio_pass.py covers its absence)
-        rec = json.load(open(path))
+    rec = isa_record(native)
+    if rec is not None:                    # written by a build that ran the issue pass (tests/test_isa_prio_pass.py covers its absence)
         assert rec["audit"]["block_count_errors"] == [] and rec["audit"]["unclassified"] == []
         mine = {k: v for k, v in rec["audit"]["blocks"].items() if "forest_proofs_kernel" in k}
         assert list(mine.values()) == [1] and "verify_forest_proofs_kernel" in next(iter(mine))      # the gather holds none

@@ -11,6 +11,7 @@ import pytest
 
 import forest_cases as fc
 import forest_repack_cases as fr
+from abi_support import Refusals, assert_bound, assert_exported, isa_record
 from conftest import ROOT
 from no_device import NoDevice
 
@@ -19,28 +20,15 @@ KERNELS = ("forest_drop_front_kernel", "forest_copy_check_kernel", "forest_copy_
 
 
 def test_header_declares_both_and_the_stub_binds_every_argument():
-    text = open(os.path.join(ROOT, "include", "vkmr_hip.h")).read()
-    declared = set(re.findall(r"VKMR_API\s+[\w\s\*]+?\b(vkmr_hip_\w+)\s*\(", text))
-    from vk_merkle_roots_amd import _abi
     u32, u64 = C.c_uint32, C.c_uint64
     # dev, stream, offsets, ntrees, drop_trees, roots, mutated: seven; the copy: dev, stream, eight of the source, sel, m, n_leaves,
     # new_offsets, ten of the destination, status: twenty-five
     for name, nparams, scalars in ((DROP, 7, [C.c_int, u32, u32]), (COPY, 25, [C.c_int, u64, u32, u64, u32, u64, u64, u32, u64, u32, u64])):
-        assert name in declared
-        params = re.search(r"VKMR_API vkmr_status " + name + r"\s*\(([^)]*)\)", text).group(1).split(",")
-        assert len(params) == nparams
-        res, args = _abi.SIGNATURES[name]
-        assert res is C.c_int and len(args) == len(params)
-        assert [a for a in args if a is not C.c_void_p] == scalars
-        for param, arg in zip(params, args):                 # pointer for pointer, scalar for scalar, in the header's order
-            assert ("*" in param or "vkmr_stream" in param) == (arg is C.c_void_p), (name, param)
-            if arg is not C.c_void_p:
-                assert {C.c_int: "int ", u32: "uint32_t ", u64: "uint64_t "}[arg] in param, (name, param)
+        assert_bound(name, nparams=nparams, scalars=scalars, restype=C.c_int)      # pointer for pointer, scalar for scalar, in the header's order
 
 
 def test_library_exports_both(native):
-    lib = C.CDLL(native.HIP_LIB)
-    assert hasattr(lib, DROP) and hasattr(lib, COPY)
+    assert_exported(native.HIP_LIB, [DROP, COPY])
 
 
 def good_copy():
@@ -55,39 +43,26 @@ def good_copy():
 def test_bad_copy_arguments_are_refused_before_any_hip_call(native):
     from vk_merkle_roots_amd import _abi
     lib = _abi.lib()
-    bad = _abi.ERR_INVALID
-    for i in (0, 1, 3, 6, 8, 11, 12, 13, 15, 20, 22):       # each needed pointer NULL with m > 0 (the masks, 7 and 21, are NULL already)
-        args = good_copy()
-        args[i] = None
-        assert lib.vkmr_hip_forest_copy_trees_async(0, None, *args) == bad, i
-        assert COPY.encode() in lib.vkmr_hip_last_error()
     g = good_copy()
+    copy = Refusals(lib.vkmr_hip_forest_copy_trees_async, COPY, good=g)
+    copy.null(0, 1, 3, 6, 8, 11, 12, 13, 15, 20, 22)        # each needed pointer NULL with m > 0 (the masks, 7 and 21, are NULL already)
     # first_tree + m > dst_ntrees (also past 2^32), used + n_leaves > dst_total (also past 2^64), either max_count == 0, either
     # total above 2^58, and the four pairs of buffers that may not be the same
-    for changes in ({18: 6}, {9: 5}, {18: 9}, {18: 2**32 - 1, 9: 2}, {10: 41}, {19: 71}, {19: 101, 10: 0}, {19: 2**64 - 1, 10: 2}, {5: 0}, {17: 0},
-                    {2: (1 << 58) + 1}, {14: (1 << 58) + 1}, {12: g[0]}, {13: g[1]}, {15: g[3]}, {20: g[6]}):
-        args = good_copy()
-        for i, value in changes.items():
-            args[i] = value
-        assert lib.vkmr_hip_forest_copy_trees_async(0, None, *args) == bad, changes
-        assert COPY.encode() in lib.vkmr_hip_last_error()
+    copy.changed({18: 6}, {9: 5}, {18: 9}, {18: 2**32 - 1, 9: 2}, {10: 41}, {19: 71}, {19: 101, 10: 0}, {19: 2**64 - 1, 10: 2}, {5: 0}, {17: 0},
+                 {2: (1 << 58) + 1}, {14: (1 << 58) + 1}, {12: g[0]}, {13: g[1]}, {15: g[3]}, {20: g[6]})
     # m == 0 is a no-op whatever the rest
-    for changes in ({9: 0}, {9: 0, 0: None, 12: None, 22: None}, {9: 0, 14: (1 << 58) + 1, 5: 0, 18: 99}, {9: 0, 12: g[0], 13: g[1]}):
-        args = good_copy()
-        for i, value in changes.items():
-            args[i] = value
-        assert lib.vkmr_hip_forest_copy_trees_async(0, None, *args) == _abi.OK, changes
+    copy.ok(*([changes.get(i, a) for i, a in enumerate(g)]
+              for changes in ({9: 0}, {9: 0, 0: None, 12: None, 22: None}, {9: 0, 14: (1 << 58) + 1, 5: 0, 18: 99}, {9: 0, 12: g[0], 13: g[1]})))
 
 
 def test_bad_drop_arguments_are_refused_before_any_hip_call(native):
     from vk_merkle_roots_amd import _abi
     lib = _abi.lib()
     d = C.c_void_p(0x1000)
-    for args in ((None, 8, 3, d, None), (d, 8, 3, None, None), (d, 8, 9, d, d), (None, 8, 9, None, None), (d, 0, 1, d, None)):
-        assert lib.vkmr_hip_forest_drop_front_async(0, None, *args) == _abi.ERR_INVALID, args
-        assert DROP.encode() in lib.vkmr_hip_last_error()
-    assert lib.vkmr_hip_forest_drop_front_async(0, None, None, 8, 0, None, None) == _abi.OK      # drop_trees == 0: nothing to do
-    assert lib.vkmr_hip_forest_drop_front_async(0, None, None, 0, 0, None, None) == _abi.OK
+    drop = Refusals(lib.vkmr_hip_forest_drop_front_async, DROP, good=[d, 8, 3, d, None])         # offsets, ntrees, drop_trees, roots, mutated
+    drop.null(0, 3)
+    drop.changed({2: 9, 4: d}, {0: None, 2: 9, 3: None}, {1: 0, 2: 1})                           # drop_trees > ntrees
+    drop.ok((None, 8, 0, None, None), (None, 0, 0, None, None))                                  # drop_trees == 0: nothing to do
 
 
 def host_forest(counts=(4, 0, 7, 0, 0, 0), total=20, max_count=8, used_trees=3):
@@ -192,10 +167,8 @@ def test_the_kernel_names_match_no_hash_block_key(native):
     text = open(os.path.join(ROOT, "vk_merkle_roots_amd", "csrc", "forest_copy_kernels.hpp")).read()
     assert set(re.findall(r"__global__ __launch_bounds__\(\d+\) void (\w+)\(", text)) == set(KERNELS)
     assert "hash_pair" not in text and "sha256" not in text.lower()
-    path = os.path.splitext(native.HIP_LIB)[0] + ".isa.json"
-    if os.path.exists(path):               # written by a build that ran the issue pass
-        import json
-        rec = json.load(open(path))
+    rec = isa_record(native)
+    if rec is not None:                    # written by a build that ran the issue pass
         assert rec["audit"]["block_count_errors"] == [] and rec["audit"]["unclassified"] == []
         assert not [k for k in rec["audit"]["blocks"] if "forest_copy" in k or "forest_drop_front" in k]
 

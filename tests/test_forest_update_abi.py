@@ -3,16 +3,13 @@ MerkleForest.update and update_packed, the ordering rule, and the addressing of 
 the CPU with the run-head rule of forest_update_level_kernel (tests/c/forest_update_plan_test.cpp).  No compute calls here:
 every case returns before the library or the Python layer touches HIP."""
 import ctypes as C
-import json
-import os
-import re
 
 import numpy as np
 import pytest
 
 import forest_cases as fc
 import forest_update_cases as fu
-from conftest import ROOT
+from abi_support import Refusals, assert_bound, assert_exported, assert_key_resolves, assert_no_spills, isa_record
 from merkle_model import random_counts
 from no_device import NoDevice
 
@@ -20,45 +17,27 @@ NAME = "vkmr_hip_forest_update_async"
 
 
 def test_header_declares_the_update_and_the_stub_binds_every_argument_of_it():
-    text = open(os.path.join(ROOT, "include", "vkmr_hip.h")).read()
-    declared = set(re.findall(r"VKMR_API\s+[\w\s\*]+?\b(vkmr_hip_\w+)\s*\(", text))
-    assert NAME in declared
-    params = re.search(r"\b" + NAME + r"\s*\(([^)]*)\)", text).group(1).split(",")
     # dev, stream, digests, forest, total, offsets, ntrees, max_count, trees, indices, leaves, k, roots, status: the prototype the
     # feature was specified with has these fourteen
-    assert len(params) == 14
-    from vk_merkle_roots_amd import _abi
-    res, args = _abi.SIGNATURES[NAME]
-    assert res is C.c_int and len(args) == len(params)
-    assert [a for a in args if a is not C.c_void_p] == [C.c_int, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32]
+    assert_bound(NAME, nparams=14, scalars=[C.c_int, C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32], restype=C.c_int)
 
 
 def test_library_exports_the_update(native):
-    assert hasattr(C.CDLL(native.HIP_LIB), NAME)
+    assert_exported(native.HIP_LIB, [NAME])
 
 
 def test_bad_arguments_are_refused_before_any_hip_call(native):
     from vk_merkle_roots_amd import _abi
     lib = _abi.lib()
-    bad = _abi.ERR_INVALID
     d = C.c_void_p(0x1000)                 # never dereferenced: every call below returns before launching anything
     # digests, forest, total, offsets, ntrees, max_count, trees, indices, leaves, k, roots, status
-    good = [d, d, 100, d, 4, 50, d, d, d, 8, d, d]
-    for i in (0, 1, 3, 6, 7, 8, 10, 11):   # each pointer NULL with k > 0
-        args = list(good)
-        args[i] = None
-        assert lib.vkmr_hip_forest_update_async(0, None, *args) == bad, i
-        assert b"vkmr_hip_forest_update_async" in lib.vkmr_hip_last_error()
-    for i, value in ((4, 0), (2, 0), (5, 0), (2, (1 << 58) + 1)):   # ntrees == 0, total == 0, max_count == 0, too many leaves
-        args = list(good)
-        args[i] = value
-        assert lib.vkmr_hip_forest_update_async(0, None, *args) == bad, (i, value)
-        assert b"vkmr_hip_forest_update_async" in lib.vkmr_hip_last_error()
+    update = Refusals(lib.vkmr_hip_forest_update_async, NAME, good=[d, d, 100, d, 4, 50, d, d, d, 8, d, d])
+    update.null(0, 1, 3, 6, 7, 8, 10, 11)  # each pointer NULL with k > 0
+    update.changed({4: 0}, {2: 0}, {5: 0}, {2: (1 << 58) + 1})       # ntrees == 0, total == 0, max_count == 0, too many leaves
     # (a grid that is too large cannot be reached: k < 2^32 entries are fewer than 2^31 workgroups of 256 lanes)
     # k == 0 is a no-op whatever the rest
-    assert lib.vkmr_hip_forest_update_async(0, None, None, None, 100, None, 4, 50, None, None, None, 0, None, None) == _abi.OK
-    assert lib.vkmr_hip_forest_update_async(0, None, None, None, 0, None, 0, 0, None, None, None, 0, None, None) == _abi.OK
-    assert lib.vkmr_hip_forest_update_async(0, None, d, d, (1 << 58) + 1, d, 4, 0, d, d, d, 0, d, d) == _abi.OK
+    update.ok((None, None, 100, None, 4, 50, None, None, None, 0, None, None), (None, None, 0, None, 0, 0, None, None, None, 0, None, None),
+              (d, d, (1 << 58) + 1, d, 4, 0, d, d, d, 0, d, d))
 
 
 COUNTS = [4, 0, 0, 7, 0, 0, 0, 1]          # fc.CASES["empty_adjacent"]
@@ -194,18 +173,10 @@ def test_the_update_step_replayed_over_a_thousand_random_forests(native, plan_ex
 def test_the_update_level_kernel_holds_one_hash_block_and_the_build_lists_it(native):
     from vk_merkle_roots_amd import isa_prio_pass
     assert isa_prio_pass.EXPECTED_HASH_BLOCKS["forest_update_level_kernel"] == 1
-    # the pass matches by substring, first match wins: the name must not be taken for the single tree's kernel
-    assert next(k for k in isa_prio_pass.EXPECTED_HASH_BLOCKS if k in "_Z26forest_update_level_kernelPK") == "forest_update_level_kernel"
-    path = os.path.splitext(native.HIP_LIB)[0] + ".isa.json"
-    if os.path.exists(path):               # written by a build that ran the issue pass (tests/test_isa_prio_pass.py covers its absence)
-        rec = json.load(open(path))
+    assert_key_resolves("forest_update_level_kernel")      # the name must not be taken for the single tree's kernel
+    rec = isa_record(native)
+    if rec is not None:                    # written by a build that ran the issue pass (tests/test_isa_prio_pass.py covers its absence)
         assert rec["audit"]["block_count_errors"] == [] and rec["audit"]["unclassified"] == []
         mine = {k: v for k, v in rec["audit"]["blocks"].items() if "forest_update" in k}
         assert list(mine.values()) == [1] and "forest_update_level_kernel" in next(iter(mine))   # the check and the leaves hold none
-    listing = os.path.join(ROOT, "build", "obj", os.path.basename(native.HIP_LIB), "device.s")
-    if os.path.exists(listing):            # the device assembly that build left behind: the code object's own metadata of the kernel
-        text = open(listing).read()
-        meta = re.search(r"\.name:\s+_Z\d+forest_update_level_kernel\w*\n((?:    \..*\n)+)", text).group(1)
-        fields = dict(re.findall(r"\.(\w+):\s+(\S+)", meta))
-        assert fields["private_segment_fixed_size"] == "0" and fields["sgpr_spill_count"] == "0" and fields["vgpr_spill_count"] == "0"
-        assert int(fields["vgpr_count"]) <= 64          # 512 registers a lane, 8 wavefronts per SIMD
+    assert_no_spills(native, ["forest_update_level_kernel"], max_vgprs=64, prefix=True)      # 512 registers a lane, 8 wavefronts per SIMD

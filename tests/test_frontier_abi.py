@@ -3,15 +3,12 @@ rules of csrc/frontier_plan.hpp replayed on the CPU with frontier_level_kernel's
 CPU twins (vkmr_host_cpu_frontier_extend, _frontier_roots, _forest_frontier) against the hashlib model of tests/frontier_cases.py,
 and the host-side checks of vk.Frontier.  No compute call on a device here."""
 import ctypes as C
-import json
-import os
-import re
 
 import numpy as np
 import pytest
 
 import frontier_cases as fr
-from conftest import ROOT
+from abi_support import Refusals, assert_bound, assert_exported, assert_key_resolves, assert_no_spills, isa_record
 from merkle_model import random_leaves
 from no_device import NoDevice
 
@@ -24,65 +21,38 @@ EXTEND = "vkmr_hip_frontier_extend_async"
 
 
 def test_header_declares_them_and_the_stub_binds_every_argument():
-    text = open(os.path.join(ROOT, "include", "vkmr_hip.h")).read()
-    from vk_merkle_roots_amd import _abi
     for name, nparams in ENTRY_POINTS.items():
-        params = re.search(r"VKMR_API\s+[\w\s\*]+?\b" + name + r"\s*\(([^)]*)\)", text).group(1).split(",")
-        assert len(params) == nparams, name
-        res, args = _abi.SIGNATURES[name]
-        assert len(args) == nparams and res is (C.c_size_t if name.endswith("_bytes") else C.c_int), name
+        assert_bound(name, nparams=nparams, restype=C.c_size_t if name.endswith("_bytes") else C.c_int)
 
 
 def test_libraries_export_them(native):
-    lib, host = C.CDLL(native.HIP_LIB), C.CDLL(native.HOST_LIB)
-    assert all(hasattr(lib, name) for name in ENTRY_POINTS) and all(hasattr(host, name) for name in HOST_ENTRY_POINTS)
+    assert_exported(native.HIP_LIB, ENTRY_POINTS)
+    assert_exported(native.HOST_LIB, HOST_ENTRY_POINTS)
 
 
 def test_bad_arguments_are_refused_before_any_hip_call(native):
     from vk_merkle_roots_amd import _abi
     lib = _abi.lib()
-    bad = _abi.ERR_INVALID
     d = C.c_void_p(0x1000)                 # never dereferenced: every call below returns before launching anything
     # counts, peaks, stride, T, leaves, total_new, offsets, max_new, scratch, new_counts, new_peaks, roots, status
-    good = [d, d, 8, 3, d, 6, d, 4, d, d, d, d, d]
-    for i in (0, 1, 4, 6, 8, 9, 10, 11, 12):
-        args = list(good)
-        args[i] = None
-        assert lib.vkmr_hip_frontier_extend_async(0, None, *args) == bad, i
-        assert EXTEND.encode() in lib.vkmr_hip_last_error()
-    for changes in ({2: 0}, {2: 65}, {5: (1 << 58) + 1}, {8: C.c_void_p(0x1008)}):
-        args = list(good)
-        for i, value in changes.items():
-            args[i] = value
-        assert lib.vkmr_hip_frontier_extend_async(0, None, *args) == bad, changes
-        assert EXTEND.encode() in lib.vkmr_hip_last_error()
-    assert lib.vkmr_hip_frontier_extend_async(0, None, None, None, 0, 0, None, 0, None, 0, None, None, None, None, None) == _abi.OK   # no tree
+    extend = Refusals(lib.vkmr_hip_frontier_extend_async, EXTEND, good=[d, d, 8, 3, d, 6, d, 4, d, d, d, d, d])
+    extend.null(0, 1, 4, 6, 8, 9, 10, 11, 12)
+    extend.changed({2: 0}, {2: 65}, {5: (1 << 58) + 1}, {8: C.c_void_p(0x1008)})
+    extend.ok((None, None, 0, 0, None, 0, None, 0, None, None, None, None, None))       # no tree
     # the root walk and the verifier: counts, peaks, stride, T, roots (, ok)
-    for i in (0, 1, 4):
-        args = [d, d, 8, 3, d]
-        args[i] = None
-        assert lib.vkmr_hip_frontier_roots_async(0, None, *args) == bad, i
-    for i in (0, 1, 4, 5):
-        args = [d, d, 8, 3, d, d]
-        args[i] = None
-        assert lib.vkmr_hip_verify_frontier_async(0, None, *args) == bad, i
-    for stride in (0, 65):
-        assert lib.vkmr_hip_frontier_roots_async(0, None, d, d, stride, 3, d) == bad
-        assert lib.vkmr_hip_verify_frontier_async(0, None, d, d, stride, 3, d, d) == bad
-    assert lib.vkmr_hip_frontier_roots_async(0, None, None, None, 0, 0, None) == _abi.OK
-    assert lib.vkmr_hip_verify_frontier_async(0, None, None, None, 0, 0, None, None) == _abi.OK
+    roots = Refusals(lib.vkmr_hip_frontier_roots_async, "vkmr_hip_frontier_roots_async", good=[d, d, 8, 3, d])
+    verify = Refusals(lib.vkmr_hip_verify_frontier_async, "vkmr_hip_verify_frontier_async", good=[d, d, 8, 3, d, d])
+    roots.null(0, 1, 4)
+    verify.null(0, 1, 4, 5)
+    roots.changed({2: 0}, {2: 65})
+    verify.changed({2: 0}, {2: 65})
+    roots.ok((None, None, 0, 0, None))
+    verify.ok((None, None, 0, 0, None, None))
     # the gather: digests, forest, total, offsets, ntrees, max_count, roots, stride, counts_out, peaks_out
-    good = [d, d, 100, d, 8, 50, d, 6, d, d]
-    for i in (0, 1, 3, 6, 8, 9):
-        args = list(good)
-        args[i] = None
-        assert lib.vkmr_hip_forest_frontier_async(0, None, *args) == bad, i
-    for changes in ({7: 0}, {7: 65}, {7: 5}, {5: 0}, {2: (1 << 58) + 1}):       # stride 5: a tree of 50 leaves has six bits
-        args = list(good)
-        for i, value in changes.items():
-            args[i] = value
-        assert lib.vkmr_hip_forest_frontier_async(0, None, *args) == bad, changes
-    assert lib.vkmr_hip_forest_frontier_async(0, None, None, None, 0, None, 0, 0, None, 0, None, None) == _abi.OK
+    gather = Refusals(lib.vkmr_hip_forest_frontier_async, "vkmr_hip_forest_frontier_async", good=[d, d, 100, d, 8, 50, d, 6, d, d])
+    gather.null(0, 1, 3, 6, 8, 9)
+    gather.changed({7: 0}, {7: 65}, {7: 5}, {5: 0}, {2: (1 << 58) + 1})           # stride 5: a tree of 50 leaves has six bits
+    gather.ok((None, None, 0, None, 0, 0, None, 0, None, None))
 
 
 def test_the_scratch_budget(native):
@@ -232,23 +202,12 @@ def test_the_kernel_keys_resolve_to_themselves_and_the_build_lists_them(native):
     keys = isa_prio_pass.EXPECTED_HASH_BLOCKS
     for mine in HASHING:
         assert keys[mine] == 1
-        # the pass matches by substring, first match wins: the name must resolve to its own key and shadow nobody's
-        assert next(k for k in keys if k in f"_Z21{mine}PK") == mine
-        for other in keys:
-            assert other == mine or (other not in mine and mine not in other), other
+        assert_key_resolves(mine)
     for name in KERNELS:
         assert name in HASHING or not any(k in name for k in keys), name      # no hash expected in the others
-    path = os.path.splitext(native.HIP_LIB)[0] + ".isa.json"
-    if os.path.exists(path):               # written by a build that ran the issue pass (tests/test_isa_prio_pass.py covers its absence)
-        rec = json.load(open(path))
+    rec = isa_record(native)
+    if rec is not None:                    # written by a build that ran the issue pass (tests/test_isa_prio_pass.py covers its absence)
         assert rec["audit"]["block_count_errors"] == [] and rec["audit"]["unclassified"] == []
         mine = {k: v for k, v in rec["audit"]["blocks"].items() if "frontier" in k}
         assert sorted(mine.values()) == [1, 1] and all(any(h in k for h in HASHING) for k in mine)
-    listing = os.path.join(ROOT, "build", "obj", os.path.basename(native.HIP_LIB), "device.s")
-    if os.path.exists(listing):            # the device assembly that build left behind: the code object's own metadata of the kernels
-        text = open(listing).read()
-        for name in KERNELS:
-            meta = re.search(r"\.name:\s+_Z\d+" + name + r"P\w*\n((?:    \..*\n)+)", text).group(1)
-            fields = dict(re.findall(r"\.(\w+):\s+(\S+)", meta))
-            assert fields["private_segment_fixed_size"] == "0" and fields["sgpr_spill_count"] == "0" and fields["vgpr_spill_count"] == "0"
-            assert int(fields["vgpr_count"]) <= 64          # 512 registers a lane, 8 wavefronts per SIMD
+    assert_no_spills(native, KERNELS, max_vgprs=64)        # 512 registers a lane, 8 wavefronts per SIMD

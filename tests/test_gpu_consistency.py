@@ -2,15 +2,12 @@
 MerkleForest.consistency and vk.ConsistencyProof): byte for byte what the CPU twin gives, between guard words, for the shapes of
 tests/consistency_cases.py; the verifier against the roots of the trees built from the first c leaves; the read set flip by
 flip; a primary that forks; forests that grew, slid and were repacked; the refusals; and the code object."""
-import json
-import os
-import re
-
 import numpy as np
 import pytest
 
 import consistency_cases as cc
 import forest_update_cases as fu
+from abi_support import assert_no_spills, isa_record
 from merkle_model import At, random_leaves
 
 pytestmark = pytest.mark.gpu
@@ -191,18 +188,12 @@ def test_a_refused_gather_writes_nothing(gpu, what, status, trees, old, stride, 
 
 
 def test_the_code_object(native):
-    from conftest import ROOT
     from vk_merkle_roots_amd import isa_prio_pass
-    rec = json.load(open(os.path.splitext(native.HIP_LIB)[0] + ".isa.json"))                    # the record the build writes beside the library
+    rec = isa_record(native)                                                                     # the record the build writes beside the library
+    assert rec is not None
     mine = {k: len(v) for k, v in rec["hash_blocks"].items() if "consistency_fold_kernel" in k}
     assert list(mine.values()) == [isa_prio_pass.EXPECTED_HASH_BLOCKS["consistency_fold_kernel"]] == [1]
     assert rec["audit"]["block_count_errors"] == [] and {v for k, v in rec["audit"]["blocks"].items() if "consistency" in k} == {1}
     assert not any("consistency_check" in k or "consistency_gather" in k for k in rec["hash_blocks"])
-    listing = os.path.join(ROOT, "build", "obj", os.path.basename(native.HIP_LIB), "device.s")
-    if not os.path.exists(listing):                                                              # the library came built, without the assembly it was made from
-        return
-    text = open(listing).read()
-    for name in ("consistency_check_kernel", "consistency_gather_kernel", "consistency_fold_kernel"):
-        meta = re.search(r"\.name:\s+_Z\d+" + name + r"P\w*\n((?:    \..*\n)+)", text).group(1)
-        fields = dict(re.findall(r"\.(\w+):\s+(\S+)", meta))
-        assert fields["private_segment_fixed_size"] == "0" and fields["sgpr_spill_count"] == "0" and fields["vgpr_spill_count"] == "0", name
+    # returns where the library came built, without the assembly it was made from
+    assert_no_spills(native, ("consistency_check_kernel", "consistency_gather_kernel", "consistency_fold_kernel"))

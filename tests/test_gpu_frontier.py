@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import frontier_cases as fr
+from abi_support import assert_no_spills, isa_record
 from merkle_model import random_leaves
 
 pytestmark = pytest.mark.gpu
@@ -173,18 +174,9 @@ def test_the_handle_reports_the_devices_refusal(gpu):
 
 
 def test_the_level_kernels_listing(native):
-    import json
-    import os
-    import re
-    from conftest import ROOT
-    rec = json.load(open(os.path.splitext(native.HIP_LIB)[0] + ".isa.json"))          # the record the build writes beside the library
+    rec = isa_record(native)                                                          # the record the build writes beside the library
+    assert rec is not None
     mine = {k: len(v) for k, v in rec["hash_blocks"].items() if "frontier_level_kernel" in k}
     assert list(mine.values()) == [1]
     assert rec["audit"]["block_count_errors"] == [] and {v for k, v in rec["audit"]["blocks"].items() if "frontier" in k} == {1}
-    listing = os.path.join(ROOT, "build", "obj", os.path.basename(native.HIP_LIB), "device.s")
-    if not os.path.exists(listing):                                                   # the library came built, without the assembly it was made from
-        return
-    text = open(listing).read()
-    meta =re.search(r"\.name:\s+_Z\d+frontier_level_kernelP\w*\n((?:    \..*\n)+)", text).group(1)
-    fields = dict(re.findall(r"\.(\w+):\s+(\S+)", meta))
-    assert fields["private_segment_fixed_size"] == "0" and fields["sgpr_spill_count"] == "0" and fields["vgpr_spill_count"] == "0"
+    assert_no_spills(native, ["frontier_level_kernel"])                               # returns where the library came built, without its assembly

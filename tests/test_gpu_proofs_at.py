@@ -3,15 +3,12 @@ MerkleForest.proofs_at / roots_at): byte for byte what the CPU twin gives, betwe
 tests/proofs_at_cases.py; the same batch verified by the existing vkmr_hip_verify_forest_proofs_async under the old roots; the old
 roots and the proofs by independent device paths (the consistency proof's frontier; a forest built from the prefix leaves); one
 large tree; the shapes of the call; forests that grew, slid, were repacked, shrank and forked; the refusals; the code object."""
-import json
-import os
-import re
-
 import numpy as np
 import pytest
 
 import forest_update_cases as fu
 import proofs_at_cases as pc
+from abi_support import assert_no_spills, isa_record
 from merkle_model import At, random_leaves
 
 pytestmark = pytest.mark.gpu
@@ -236,18 +233,12 @@ def test_a_refused_call_writes_nothing(gpu, what, status, trees, old, stride, ma
 
 
 def test_the_code_object(native):
-    from conftest import ROOT
     from vk_merkle_roots_amd import isa_prio_pass
-    rec = json.load(open(os.path.splitext(native.HIP_LIB)[0] + ".isa.json"))                    # the record the build writes beside the library
+    rec = isa_record(native)                                                                     # the record the build writes beside the library
+    assert rec is not None
     mine = {k: len(v) for k, v in rec["hash_blocks"].items() if "proofs_at_edge_kernel" in k}
     assert list(mine.values()) == [isa_prio_pass.EXPECTED_HASH_BLOCKS["proofs_at_edge_kernel"]] == [1]
     assert rec["audit"]["block_count_errors"] == [] and {v for k, v in rec["audit"]["blocks"].items() if "proofs_at" in k} == {1}
     assert not any("proofs_at_check" in k or "proofs_at_gather" in k for k in rec["hash_blocks"])
-    listing = os.path.join(ROOT, "build", "obj", os.path.basename(native.HIP_LIB), "device.s")
-    if not os.path.exists(listing):                                                              # the library came built, without the assembly it was made from
-        return
-    text = open(listing).read()
-    for name in ("proofs_at_check_kernel", "proofs_at_edge_kernel", "proofs_at_gather_kernel"):
-        meta = re.search(r"\.name:\s+_Z\d+" + name + r"P\w*\n((?:    \..*\n)+)", text).group(1)
-        fields = dict(re.findall(r"\.(\w+):\s+(\S+)", meta))
-        assert fields["private_segment_fixed_size"] == "0" and fields["sgpr_spill_count"] == "0" and fields["vgpr_spill_count"] == "0", name
+    # returns where the library came built, without the assembly it was made from
+    assert_no_spills(native, ("proofs_at_check_kernel", "proofs_at_edge_kernel", "proofs_at_gather_kernel"))

@@ -6,8 +6,6 @@ import re
 
 import pytest
 
-from conftest import ROOT
-
 LISTING = """\t.text
 \t.amdgcn_target "amdgcn-amd-amdhsa--gfx950"
 _Z6kernelPj:                            ; @_Z6kernelPj
@@ -111,8 +109,8 @@ def _semantics(lines):
 
 
 def test_the_assembly_of_the_library_in_the_tree_differs_only_by_what_the_pass_may_insert(native):
-    work = os.path.join(ROOT, "build", "obj", "libvkmr_hip.so")
-    before, after = os.path.join(work, "device.s"), os.path.join(work, "device_prio.s")
+    from abi_support import listing_path
+    before, after = listing_path(native), listing_path(native, "device_prio.s")
     if not (os.path.exists(before) and os.path.exists(after)):
         pytest.skip("no build/obj in this checkout (the library was built elsewhere)")
     from vk_merkle_roots_amd import build, isa_prio_pass as P
@@ -197,11 +195,10 @@ def test_verify_accepts_what_the_pass_does_and_nothing_else():
 def test_the_shipped_library_is_covered_by_the_issue_model(native):
     """The record the build writes beside the product library: every VALU opcode in its hash blocks is one the issue
     measurements covered, every kernel shows the hash blocks the static counts assume, and the pass's output was verified."""
-    import json
-    path = os.path.splitext(native.HIP_LIB)[0] + ".isa.json"
-    if not os.path.exists(path):
+    from abi_support import isa_record
+    rec = isa_record(native)
+    if rec is None:
         pytest.skip("the library in the tree was built without the issue pass (llvm tools absent)")
-    rec = json.load(open(path))
     assert rec["audit"]["unclassified"] == [], rec["audit"]["unclassified"]
     assert rec["audit"]["block_count_errors"] == [], rec["audit"]["block_count_errors"]
     assert "verify" in rec["verified"]

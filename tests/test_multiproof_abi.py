@@ -2,14 +2,12 @@
 (vkmr_host_cpu_verify_multiproof) against the hashlib restatement in tests/multiproof_cases.py, and the host-side checks of
 MerkleTree.multiproof.  No compute calls: every case returns before the library touches HIP, so this runs without a GPU."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
 import multiproof_cases as mc
-from conftest import ROOT
+from abi_support import Refusals, assert_bound, assert_exported
 from no_device import NoDevice
 
 ENTRY_POINTS = ("vkmr_hip_multiproof_max_nodes", "vkmr_hip_multiproof_scratch_bytes", "vkmr_hip_tree_multiproof_async",
@@ -17,18 +15,13 @@ ENTRY_POINTS = ("vkmr_hip_multiproof_max_nodes", "vkmr_hip_multiproof_scratch_by
 
 
 def test_header_declares_library_exports_and_stub_binds(native):
-    text = open(os.path.join(ROOT, "include", "vkmr_hip.h")).read()
-    declared = set(re.findall(r"VKMR_API\s+[\w\s\*]+?\b(vkmr_hip_\w+)\s*\(", text))
     from vk_merkle_roots_amd import _abi
-    raw = C.CDLL(native.HIP_LIB)
+    assert_exported(native.HIP_LIB, ENTRY_POINTS)
     lib = _abi.lib()
     for name in ENTRY_POINTS:
-        assert name in declared, name
-        assert hasattr(raw, name), name
-        assert name in _abi.SIGNATURES and list(getattr(lib, name).argtypes) == _abi.SIGNATURES[name][1], name
-    assert len(_abi.SIGNATURES["vkmr_hip_tree_multiproof_async"][1]) == 12
-    assert len(_abi.SIGNATURES["vkmr_hip_verify_multiproof_async"][1]) == 11
-    assert hasattr(C.CDLL(native.HOST_LIB), "vkmr_host_cpu_verify_multiproof")
+        assert_bound(name, nparams={"vkmr_hip_tree_multiproof_async": 12, "vkmr_hip_verify_multiproof_async": 11}.get(name))
+        assert list(getattr(lib, name).argtypes) == _abi.SIGNATURES[name][1], name
+    assert_exported(native.HOST_LIB, ["vkmr_host_cpu_verify_multiproof"])
     assert _abi.host_lib().vkmr_host_cpu_verify_multiproof.restype is C.c_int
 
 
@@ -61,30 +54,17 @@ def test_scratch_bytes(native):
 def test_bad_arguments_are_refused_before_any_hip_call(native):
     from vk_merkle_roots_amd import _abi
     lib = _abi.lib()
-    bad = _abi.ERR_INVALID
     d = C.c_void_p(0x1000)           # never dereferenced: every call below returns before launching anything
-    good = [d, d, 8, 3, d, 4, d, d, 7, d]   # digests, tree, count, height, indices, k, scratch, nodes, capacity, info
-    for i in (0, 1, 4, 6, 7, 9):             # each pointer NULL with k > 0
-        args = list(good)
-        args[i] = None
-        assert lib.vkmr_hip_tree_multiproof_async(0, None, *args) == bad, i
-    for count, height in ((8, 2), (9, 3), (8, 64), (0, 3), (0, 0), (2, 0)):
-        args = list(good)
-        args[2], args[3] = count, height
-        assert lib.vkmr_hip_tree_multiproof_async(0, None, *args) == bad, (count, height)
-    assert lib.vkmr_hip_last_error()
-    assert lib.vkmr_hip_tree_multiproof_async(0, None, None, None, 8, 3, None, 0, None, None, 0, None) == _abi.OK
-    assert lib.vkmr_hip_tree_multiproof_async(0, None, None, None, 0, 64, None, 0, None, None, 0, None) == _abi.OK
-    good = [d, d, 4, 3, d, 5, d, d, d]       # leaves, indices, k, height, nodes, m, root, scratch, ok
-    for i in (0, 1, 4, 6, 7, 8):
-        args = list(good)
-        args[i] = None
-        assert lib.vkmr_hip_verify_multiproof_async(0, None, *args) == bad, i
-    for height in (0, 64, 100):
-        args = list(good)
-        args[3] = height
-        assert lib.vkmr_hip_verify_multiproof_async(0, None, *args) == bad, height
-    assert lib.vkmr_hip_verify_multiproof_async(0, None, None, None, 0, 3, None, 0, None, None, None) == _abi.OK
+    # digests, tree, count, height, indices, k, scratch, nodes, capacity, info
+    gather = Refusals(lib.vkmr_hip_tree_multiproof_async, "vkmr_hip_tree_multiproof_async", good=[d, d, 8, 3, d, 4, d, d, 7, d])
+    gather.null(0, 1, 4, 6, 7, 9)    # each pointer NULL with k > 0
+    gather.changed(*({2: count, 3: height} for count, height in ((8, 2), (9, 3), (8, 64), (0, 3), (0, 0), (2, 0))))
+    gather.ok((None, None, 8, 3, None, 0, None, None, 0, None), (None, None, 0, 64, None, 0, None, None, 0, None))
+    # leaves, indices, k, height, nodes, m, root, scratch, ok
+    verify = Refusals(lib.vkmr_hip_verify_multiproof_async, "vkmr_hip_verify_multiproof_async", good=[d, d, 4, 3, d, 5, d, d, d])
+    verify.null(0, 1, 4, 6, 7, 8)
+    verify.changed({3: 0}, {3: 64}, {3: 100})              # the height
+    verify.ok((None, None, 0, 3, None, 0, None, None, None))
 
 
 def test_known_sizes_of_the_restatement():

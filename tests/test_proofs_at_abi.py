@@ -4,7 +4,6 @@ own program under AddressSanitizer and UBSan), the CPU twin (vkmr_host_cpu_fores
 tests/proofs_at_cases.py byte for byte, against vkmr_host_cpu_fold_proof and against the consistency twin's peaks, and the host
 side of MerkleForest.proofs_at / roots_at.  No compute call on a device here."""
 import ctypes as C
-import json
 import os
 import re
 
@@ -14,6 +13,7 @@ import pytest
 import consistency_cases as cc
 import frontier_cases as fr
 import proofs_at_cases as pc
+from abi_support import Refusals, assert_bound, assert_exported, assert_key_resolves, assert_no_spills, isa_record
 from conftest import ROOT
 from merkle_model import host_fold, random_counts
 from no_device import NoDevice
@@ -29,9 +29,7 @@ NAMES_OTHER_TESTS_COUNT = ("frontier", "consistency", "mutated", "apply_", "_aud
 def test_header_declares_it_and_the_stub_binds_every_argument():
     text = open(os.path.join(ROOT, "include", "vkmr_hip.h")).read()
     from vk_merkle_roots_amd import _abi
-    params = re.search(r"VKMR_API\s+[\w\s\*]+?\b" + ENTRY_POINT + r"\s*\(([^)]*)\)", text).group(1).split(",")
-    res, args = _abi.SIGNATURES[ENTRY_POINT]
-    assert len(params) == NPARAMS == len(args) and res is C.c_int
+    assert_bound(ENTRY_POINT, nparams=NPARAMS, restype=C.c_int)
     res, args = _abi.HOST_SIGNATURES[HOST_ENTRY_POINT]
     assert len(args) == HOST_NPARAMS and res is C.c_int
     # the header says how the proofs are verified, and no longer says that they are not offered
@@ -42,38 +40,25 @@ def test_header_declares_it_and_the_stub_binds_every_argument():
 
 
 def test_libraries_export_them(native):
-    assert hasattr(C.CDLL(native.HIP_LIB), ENTRY_POINT) and hasattr(C.CDLL(native.HOST_LIB), HOST_ENTRY_POINT)
+    assert_exported(native.HIP_LIB, [ENTRY_POINT])
+    assert_exported(native.HOST_LIB, [HOST_ENTRY_POINT])
 
 
 def test_bad_arguments_are_refused_before_any_hip_call(native):
     from vk_merkle_roots_amd import _abi
     lib = _abi.lib()
-    bad = _abi.ERR_INVALID
     d = C.c_void_p(0x1000)                 # never dereferenced: every call below returns before launching anything
     # 0 digests, 1 forest, 2 total, 3 offsets, 4 ntrees, 5 max_count, 6 roots, 7 epoch trees, 8 epoch counts, 9 E, 10 epochs, 11 indices, 12 k, 13 stride,
     # 14 edges, 15 old roots, 16 siblings, 17 heights, 18 status
-    good = [d, d, 100, d, 8, 50, d, d, d, 5, d, d, 9, 6, d, d, d, d, d]
-    for i in (0, 1, 3, 6, 7, 8, 10, 11, 14, 15, 16, 17, 18):
-        args = list(good)
-        args[i] = None
-        assert lib.vkmr_hip_forest_proofs_at_async(0, None, *args) == bad, i
-        assert ENTRY_POINT.encode() in lib.vkmr_hip_last_error()
+    proofs = Refusals(lib.vkmr_hip_forest_proofs_at_async, ENTRY_POINT, good=[d, d, 100, d, 8, 50, d, d, d, 5, d, d, 9, 6, d, d, d, d, d])
+    proofs.null(0, 1, 3, 6, 7, 8, 10, 11, 14, 15, 16, 17, 18)
     # stride outside 1..63 (the verifier's range), and what vkmr_hip_forest_consistency_async refuses of the forest: stride 5 -- a
     # tree of 50 leaves has six bits --, no max_count, too many leaves
-    for changes in ({13: 0}, {13: 64}, {13: 65}, {13: 5}, {5: 0}, {2: (1 << 58) + 1}):
-        args = list(good)
-        for i, value in changes.items():
-            args[i] = value
-        assert lib.vkmr_hip_forest_proofs_at_async(0, None, *args) == bad, changes
-        assert ENTRY_POINT.encode() in lib.vkmr_hip_last_error()
-    for i in (7, 8, 14, 15, 18):           # k == 0 is a call like any other: the epochs' buffers are still needed
-        args = list(good)
-        args[10], args[11], args[12], args[16], args[17], args[i] = None, None, 0, None, None, None
-        assert lib.vkmr_hip_forest_proofs_at_async(0, None, *args) == bad, i
-    none = [None, None, 0, None, 0, 0, None, None, None, 0, None, None, 0, 0, None, None, None, None, None]
-    assert lib.vkmr_hip_forest_proofs_at_async(0, None, *none) == _abi.OK                        # no epoch: nothing to do
-    none[12] = 7
-    assert lib.vkmr_hip_forest_proofs_at_async(0, None, *none) == _abi.OK
+    proofs.changed({13: 0}, {13: 64}, {13: 65}, {13: 5}, {5: 0}, {2: (1 << 58) + 1})
+    # k == 0 is a call like any other: the epochs' buffers are still needed
+    proofs.changed(*({10: None, 11: None, 12: 0, 16: None, 17: None, i: None} for i in (7, 8, 14, 15, 18)))
+    proofs.ok((None, None, 0, None, 0, 0, None, None, None, 0, None, None, 0, 0, None, None, None, None, None),        # no epoch: nothing to do
+              (None, None, 0, None, 0, 0, None, None, None, 0, None, None, 7, 0, None, None, None, None, None))
     # and the twin
     import vk_merkle_roots_amd as vk
     host = vk.host_lib()
@@ -263,10 +248,7 @@ def test_the_kernel_key_resolves_to_itself_and_the_build_lists_it(native):
     from vk_merkle_roots_amd import isa_prio_pass
     keys = isa_prio_pass.EXPECTED_HASH_BLOCKS
     assert keys[EDGE] == 1
-    # the pass matches by substring, first match wins: the name must resolve to its own key and shadow nobody's
-    assert next(k for k in keys if k in f"_Z21{EDGE}PK") == EDGE
-    for other in keys:
-        assert other == EDGE or (other not in EDGE and EDGE not in other), other
+    assert_key_resolves(EDGE)
     for name in KERNELS:
         assert name == EDGE or not any(k in name for k in keys), name                              # no hash expected in the others
         assert not any(s in name for s in NAMES_OTHER_TESTS_COUNT), name
@@ -274,16 +256,9 @@ def test_the_kernel_key_resolves_to_itself_and_the_build_lists_it(native):
     assert len(re.findall(r"\bhash_pair\(", text)) == 1 and sorted(re.findall(r"void (\w+_kernel)\(", text)) == sorted(KERNELS)
     from vk_merkle_roots_amd import build
     assert "proofs_at_plan.hpp" in open(build.__file__).read()
-    path = os.path.splitext(native.HIP_LIB)[0] + ".isa.json"
-    if os.path.exists(path):               # written by a build that ran the issue pass (tests/test_isa_prio_pass.py covers its absence)
-        rec = json.load(open(path))
+    rec = isa_record(native)
+    if rec is not None:                    # written by a build that ran the issue pass (tests/test_isa_prio_pass.py covers its absence)
         assert rec["audit"]["block_count_errors"] == [] and rec["audit"]["unclassified"] == []
         mine = {k: v for k, v in rec["audit"]["blocks"].items() if "proofs_at" in k}
         assert list(mine.values()) == [1] and EDGE in next(iter(mine))
-    listing = os.path.join(ROOT, "build", "obj", os.path.basename(native.HIP_LIB), "device.s")
-    if os.path.exists(listing):            # the device assembly that build left behind: the code object's own metadata of the kernels
-        text = open(listing).read()
-        for name in KERNELS:
-            meta = re.search(r"\.name:\s+_Z\d+" + name + r"P\w*\n((?:    \..*\n)+)", text).group(1)
-            fields = dict(re.findall(r"\.(\w+):\s+(\S+)", meta))
-            assert fields["private_segment_fixed_size"] == "0" and fields["sgpr_spill_count"] == "0" and fields["vgpr_spill_count"] == "0"
+    assert_no_spills(native, KERNELS)

@@ -1,7 +1,6 @@
 """`roofline.traffic` is only ever quoted for the kernels that produced it: the counter record carries the
 identity of the kernel sources and the kernel instantiation it was measured on; a library built from edited sources, or
 one that launched another instantiation, gets `traffic: null` with the reason.  No GPU."""
-import os
 import shutil
 
 from conftest import ROOT
@@ -47,7 +46,8 @@ def test_the_loaded_library_reports_the_id_of_the_sources_in_the_tree(native):
     info = vk.lib().vkmr_hip_kernel_info().decode()
     assert provenance.build_id_of(info) == build.source_id()
     assert build.source_id(split_every=build.SPLIT_ADD3_EVERY + 1) != build.source_id()
-    assert os.path.exists(os.path.splitext(build.HIP_LIB)[0] + ".isa.json")
+    from abi_support import isa_record
+    assert isa_record(build) is not None
 
 
 def test_experiment_only_sources_do_not_change_the_product_id(native, tmp_path, monkeypatch):

@@ -10,6 +10,7 @@ import pytest
 
 import merkle_model
 import sort_cases as sc
+from abi_support import Refusals, assert_bound, assert_exported
 
 NEW = {"vkmr_hip_sort_entries_scratch_bytes": 2, "vkmr_hip_forest_sort_entries_async": 13, "vkmr_hip_tree_sort_entries_async": 9,
        "vkmr_hip_gather_digests_async": 6}
@@ -17,13 +18,11 @@ NEW = {"vkmr_hip_sort_entries_scratch_bytes": 2, "vkmr_hip_forest_sort_entries_a
 
 def test_library_exports_the_symbols_and_the_stub_binds_them(native):
     from vk_merkle_roots_amd import _abi
-    lib = C.CDLL(native.HIP_LIB)
+    assert_exported(native.HIP_LIB, NEW)
     for name, nargs in NEW.items():
-        assert hasattr(lib, name), name
-        assert len(_abi.SIGNATURES[name][1]) == nargs
-    host = C.CDLL(native.HOST_LIB)
-    assert hasattr(host, "vkmr_host_cpu_forest_sort_entries") and len(_abi.HOST_SIGNATURES["vkmr_host_cpu_forest_sort_entries"][1]) == 10
-    assert hasattr(host, "vkmr_host_cpu_tree_sort_entries") and len(_abi.HOST_SIGNATURES["vkmr_host_cpu_tree_sort_entries"][1]) == 6
+        assert_bound(name, nparams=nargs)
+    assert_exported(native.HOST_LIB, ["vkmr_host_cpu_forest_sort_entries", "vkmr_host_cpu_tree_sort_entries"])
+    assert len(_abi.HOST_SIGNATURES["vkmr_host_cpu_forest_sort_entries"][1]) == 10 and len(_abi.HOST_SIGNATURES["vkmr_host_cpu_tree_sort_entries"][1]) == 6
 
 
 def test_the_model_itself():
@@ -64,60 +63,35 @@ def test_scratch_bytes_is_the_layout(native, k):
 
 def test_the_forest_call_refuses_bad_arguments_before_any_hip_call(native):
     from vk_merkle_roots_amd import _abi
-    fn = _abi.lib().vkmr_hip_forest_sort_entries_async
     d = C.c_void_p(0x1000)                     # never dereferenced: every call below returns before launching anything
-    good = [100, d, 4, d, d, 5, d, d, d, d, d]     # total, offsets, ntrees, trees, indices, k, scratch, trees_out, indices_out, order_out, info
-    for i in (1, 3, 4, 6, 7, 8, 9, 10):        # each pointer NULL
-        args = list(good)
-        args[i] = None
-        assert fn(0, None, *args) == _abi.ERR_INVALID, i
-        assert _abi.lib().vkmr_hip_last_error()
-    args = list(good)
-    args[0] = (1 << 58) + 1                    # more leaves than a forest takes
-    assert fn(0, None, *args) == _abi.ERR_INVALID
+    # total, offsets, ntrees, trees, indices, k, scratch, trees_out, indices_out, order_out, info
+    sort = Refusals(_abi.lib().vkmr_hip_forest_sort_entries_async, "vkmr_hip_forest_sort_entries_async", good=[100, d, 4, d, d, 5, d, d, d, d, d])
+    sort.null(1, 3, 4, 6, 7, 8, 9, 10)         # each pointer NULL
+    sort.changed({0: (1 << 58) + 1})           # more leaves than a forest takes
     for bad in (0x1004, 0x1008):               # the scratch is laid out in 16-byte units
-        args = list(good)
-        args[6] = C.c_void_p(bad)
-        assert fn(0, None, *args) == _abi.ERR_INVALID
+        sort.changed({6: C.c_void_p(bad)})
         assert b"16-byte" in _abi.lib().vkmr_hip_last_error()
-    for i in (3, 4, 6, 7, 8, 9, 10):           # no tree: the offsets alone may be missing
-        args = [100, None, 0, d, d, 5, d, d, d, d, d]
-        args[i] = None
-        assert fn(0, None, *args) == _abi.ERR_INVALID, i
+    sort.changed(*({1: None, 2: 0, i: None} for i in (3, 4, 6, 7, 8, 9, 10)))      # no tree: the offsets alone may be missing
     # k == 0 does nothing whatever the rest
-    assert fn(0, None, 0, None, 0, None, None, 0, None, None, None, None, None) == _abi.OK
-    assert fn(0, None, 1 << 60, None, 7, None, None, 0, C.c_void_p(0x1004), None, None, None, None) == _abi.OK
+    sort.ok((0, None, 0, None, None, 0, None, None, None, None, None), (1 << 60, None, 7, None, None, 0, C.c_void_p(0x1004), None, None, None, None))
 
 
 def test_the_tree_call_refuses_bad_arguments_before_any_hip_call(native):
     from vk_merkle_roots_amd import _abi
-    fn = _abi.lib().vkmr_hip_tree_sort_entries_async
     d = C.c_void_p(0x1000)
-    good = [100, d, 5, d, d, d, d]             # count, indices, k, scratch, indices_out, order_out, info
-    for i in (1, 3, 4, 5, 6):
-        args = list(good)
-        args[i] = None
-        assert fn(0, None, *args) == _abi.ERR_INVALID, i
-    args = list(good)
-    args[0] = (1 << 58) + 1
-    assert fn(0, None, *args) == _abi.ERR_INVALID
-    args = list(good)
-    args[3] = C.c_void_p(0x1008)
-    assert fn(0, None, *args) == _abi.ERR_INVALID
-    assert fn(0, None, 0, None, 0, None, None, None, None) == _abi.OK
-    assert fn(0, None, 1 << 60, None, 0, None, None, None, None) == _abi.OK
+    # count, indices, k, scratch, indices_out, order_out, info
+    sort = Refusals(_abi.lib().vkmr_hip_tree_sort_entries_async, "vkmr_hip_tree_sort_entries_async", good=[100, d, 5, d, d, d, d])
+    sort.null(1, 3, 4, 5, 6)
+    sort.changed({0: (1 << 58) + 1}, {3: C.c_void_p(0x1008)})
+    sort.ok((0, None, 0, None, None, None, None), (1 << 60, None, 0, None, None, None, None))
 
 
 def test_the_gather_refuses_bad_arguments_before_any_hip_call(native):
     from vk_merkle_roots_amd import _abi
-    fn = _abi.lib().vkmr_hip_gather_digests_async
     d = C.c_void_p(0x1000)
-    good = [d, d, 5, d]                        # src, order, n, dst
-    for i in (0, 1, 3):
-        args = list(good)
-        args[i] = None
-        assert fn(0, None, *args) == _abi.ERR_INVALID, i
-    assert fn(0, None, None, None, 0, None) == _abi.OK
+    gather = Refusals(_abi.lib().vkmr_hip_gather_digests_async, "vkmr_hip_gather_digests_async", good=[d, d, 5, d])      # src, order, n, dst
+    gather.null(0, 1, 3)
+    gather.ok((None, None, 0, None))
 
 
 @pytest.mark.parametrize("shape", sc.SHAPES)
@@ -207,8 +181,7 @@ def test_host_cpu_twins_refuse_bad_offsets_and_missing_pointers(native):
     good = [65, o.ctypes.data, 1, trees.ctypes.data, idx.ctypes.data, 5, *outs]
     assert f(*good) == 0 and list(info) == [1, 0, 0, 4]
     for i in (1, 3, 4, 6, 7, 8, 9):
-        args = list(good)
-        args[i] = None
+        args = good[:i] + [None] + good[i + 1:]
         assert f(*args) != 0, i
     assert f(0, None, 0, None, None, 0, None, None, None, None) == 0       # no entry: nothing to do
     g = vk.host_lib().vkmr_host_cpu_tree_sort_entries

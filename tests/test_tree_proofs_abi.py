@@ -1,17 +1,14 @@
 """Stored tree, proofs from it, batch verification: the C ABI's declarations, the tree layout and the argument checks.
 No compute calls here: every case returns before the library touches HIP, so this runs without a GPU."""
 import ctypes as C
-import os
-import re
 
-from conftest import ROOT
+from abi_support import Refusals, declared_symbols
 
 ENTRY_POINTS = ("vkmr_hip_tree_bytes", "vkmr_hip_reduce_tree_async", "vkmr_hip_tree_proofs_async", "vkmr_hip_verify_proofs_async")
 
 
 def test_header_declares_the_tree_entry_points():
-    text = open(os.path.join(ROOT, "include", "vkmr_hip.h")).read()
-    declared = set(re.findall(r"VKMR_API\s+[\w\s\*]+?\b(vkmr_hip_\w+)\s*\(", text))
+    declared = declared_symbols()
     for name in ENTRY_POINTS:
         assert name in declared, name
 
@@ -60,14 +57,8 @@ def test_bad_arguments_are_refused_before_any_hip_call(native):
     assert lib.vkmr_hip_tree_proofs_async(0, None, d, d, 8, 3, d, 0, d) == _abi.OK
     assert lib.vkmr_hip_tree_proofs_async(0, None, None, None, 8, 3, None, 0, None) == _abi.OK
     # verify: null pointers, height 0 or above 63, nroots not in {1, k}
-    good = (d, d, d, 4, 3, d, 1, d)
-    for i in (0, 1, 2, 5, 7):
-        args = list(good)
-        args[i] = None
-        assert lib.vkmr_hip_verify_proofs_async(0, None, *args) == bad, i
-    for height in (0, 64, 100):
-        assert lib.vkmr_hip_verify_proofs_async(0, None, d, d, d, 4, height, d, 1, d) == bad, height
-    for nroots in (0, 2, 3, 5):
-        assert lib.vkmr_hip_verify_proofs_async(0, None, d, d, d, 4, 3, d, nroots, d) == bad, nroots
-    assert lib.vkmr_hip_verify_proofs_async(0, None, None, None, None, 0, 3, None, 1, None) == _abi.OK
-    assert lib.vkmr_hip_last_error()
+    verify = Refusals(lib.vkmr_hip_verify_proofs_async, "vkmr_hip_verify_proofs_async", good=(d, d, d, 4, 3, d, 1, d))
+    verify.null(0, 1, 2, 5, 7)
+    verify.changed({4: 0}, {4: 64}, {4: 100})                  # the height
+    verify.changed({6: 0}, {6: 2}, {6: 3}, {6: 5})             # nroots
+    verify.ok((None, None, None, 0, 3, None, 1, None))

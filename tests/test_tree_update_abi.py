@@ -1,43 +1,27 @@
 """Leaf updates of a stored tree: the C ABI's declaration, the argument checks and the host-side checks of MerkleTree.update.
 No compute calls here: every case returns before the library or the Python layer touches HIP, so this runs without a GPU."""
 import ctypes as C
-import os
-import re
 
 import numpy as np
 import pytest
 
-from conftest import ROOT
+from abi_support import Refusals, assert_bound
 from no_device import NoDevice
 
 
 def test_header_declares_the_update_and_the_stub_binds_it():
-    text = open(os.path.join(ROOT, "include", "vkmr_hip.h")).read()
-    declared = set(re.findall(r"VKMR_API\s+[\w\s\*]+?\b(vkmr_hip_\w+)\s*\(", text))
-    assert "vkmr_hip_tree_update_async" in declared
-    from vk_merkle_roots_amd import _abi
-    res, args = _abi.SIGNATURES["vkmr_hip_tree_update_async"]
-    assert res is C.c_int and len(args) == 10
+    assert_bound("vkmr_hip_tree_update_async", nparams=10, restype=C.c_int)
 
 
 def test_bad_arguments_are_refused_before_any_hip_call(native):
     from vk_merkle_roots_amd import _abi
     lib = _abi.lib()
-    bad = _abi.ERR_INVALID
     d = C.c_void_p(0x1000)           # never dereferenced: every call below returns before launching anything
-    good = [d, d, 8, 3, d, d, 4, d]  # digests, tree, count, height, indices, leaves, k, status
-    for i in (0, 1, 4, 5, 7):        # each pointer NULL with k > 0
-        args = list(good)
-        args[i] = None
-        assert lib.vkmr_hip_tree_update_async(0, None, *args) == bad, i
-    for count, height in ((8, 2), (9, 3), (8, 64), (0, 3), (0, 0), (2, 0)):
-        args = list(good)
-        args[2], args[3] = count, height
-        assert lib.vkmr_hip_tree_update_async(0, None, *args) == bad, (count, height)
-    assert lib.vkmr_hip_last_error()
+    update = Refusals(lib.vkmr_hip_tree_update_async, "vkmr_hip_tree_update_async", good=[d, d, 8, 3, d, d, 4, d])  # digests, tree, count, height, indices, leaves, k, status
+    update.null(0, 1, 4, 5, 7)       # each pointer NULL with k > 0
+    update.changed(*({2: count, 3: height} for count, height in ((8, 2), (9, 3), (8, 64), (0, 3), (0, 0), (2, 0))))
     # k == 0 is a no-op whatever the rest
-    assert lib.vkmr_hip_tree_update_async(0, None, None, None, 8, 3, None, None, 0, None) == _abi.OK
-    assert lib.vkmr_hip_tree_update_async(0, None, None, None, 0, 64, None, None, 0, None) == _abi.OK
+    update.ok((None, None, 8, 3, None, None, 0, None), (None, None, 0, 64, None, None, 0, None))
 
 
 def host_tree(count=10, height=4):
