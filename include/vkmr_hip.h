@@ -1158,6 +1158,64 @@ VKMR_API vkmr_status vkmr_hip_forest_proofs_at_async(int dev, vkmr_stream s, con
                                                      uint32_t* heights_dev, uint32_t* status_dev);
 
 /*
+ * PARTIAL MERKLE TREES IN BIP37 ORDER: the form Bitcoin software reads for "these transactions are in this block" -- the partial
+ * Merkle tree of a `merkleblock` message, Bitcoin Core's CPartialMerkleTree -- ONE per named tree of a stored forest, built on the
+ * device in one call: a wallet rescan or a filter match over many blocks.  digests_dev, forest_dev, total, offsets_dev, ntrees,
+ * max_count and the k entries (trees_dev[q], indices_dev[q]) are those of vkmr_hip_forest_multiproof_async: device memory, the
+ * pairs strictly increasing, tree < ntrees, index < c_t, checked on the device into the same status bits 0 and 1.
+ * THE RULE, for a tree of c >= 1 leaves: h = max(1, ceil(log2 c)), w(l) = ceil(c / 2^l) the nodes of level l, A_0 the tree's
+ * matched indices, A_{l+1} = unique(A_l >> 1).  visit(h, 0) starts the walk; visit(l, p) appends the flag f = (p in A_l); if
+ * l == 0 or !f it appends the hash of stored node (l, p); otherwise visit(l - 1, 2p), then visit(l - 1, 2p + 1) only if
+ * 2p + 1 < w(l - 1).  Flag number i is bit i & 7 of byte i >> 3; padding bits are 0.  For c >= 2 the flags and hashes are byte
+ * for byte what Bitcoin Core's TraverseAndBuild writes.  THE LONE LEAF: for c == 1 the rule gives two flags and one hash, and the
+ * root is hash_pair(leaf, leaf); Bitcoin has one flag and the txid as the root.  It is not special-cased: this engine's root of
+ * such a tree is not Bitcoin's anyway.  Against the multiproof: the matched leaves themselves are carried, and nothing is where
+ * the multiproof puts a node in as its own sibling (the duplicate-last edge): hashes = k_t + the tree's multiproof nodes - those
+ * emitted at such an edge.
+ * Outputs, B the number of distinct trees named, b over them in ascending order (the per-block arrays have room for k entries,
+ * the two starts for k + 1):
+ *   block_trees_dev[b]   uint32: the tree of block b          block_counts_dev[b]  uint64: c_t
+ *   bit_counts_dev[b]    uint64: the flags of block b
+ *   hash_starts_dev[b]   uint64: the first hash of block b in hashes_dev; [B] their number
+ *   byte_starts_dev[b]   uint64: the first flag byte of block b in flags_dev (every block starts on a byte); [B] their number
+ *   hashes_dev           hash_capacity vkmr_digest cells, tree-major, each block in the visit order above
+ *   flags_dev            flag_capacity bytes, 4-byte aligned; every byte in [0, byte_starts_dev[B]) is written whole
+ *   info_dev             4 uint64: [0] status, [1] B, [2] the hashes, [3] the flag bytes
+ * Status: bits 0 and 1 as above -- then nothing else of the caller's is written; bit 2 when the hashes exceed hash_capacity or the
+ * flag bytes flag_capacity -- then the per-block arrays and info_dev are written and valid, no hash and no flag is, and the caller
+ * can allocate and call again.  Nothing behind the used hashes and bytes is touched.  vkmr_hip_forest_merkleblocks_max_hashes
+ * (<= k + vkmr_hip_forest_multiproof_max_nodes) and _max_flag_bytes (per tree flags <= 2 * hashes + h, a byte of padding a
+ * block) bound them from the forest's shape; scratch_dev is vkmr_hip_forest_merkleblocks_scratch_bytes(k, H) bytes, 16-byte
+ * aligned, H the forest's stride (the tree's height for the twin).
+ * No walk on the device: what the walk appends between one matched leaf and the next is a closed form of the two indices
+ * (csrc/merkleblock_plan.hpp), so a prefix sum over the entries places everything.  Launches, all on the caller's stream: the
+ * status zeroed, the check, then nine kernels whatever k, B and H are (sums, starts, places; byte sums, starts, places; the flag
+ * words zeroed, the emit of H x k lanes, the flag bytes out); never a launch per tree or per level, no allocation, no host read
+ * of device data; every kernel behind the check reads the status first; flags of neighbouring small trees share 32-bit words and
+ * are set with atomicOr.  No kernel hashes.  Refused on the host (VKMR_ERR_INVALID) with k > 0: what
+ * vkmr_hip_forest_multiproof_async refuses, and a flags_dev off the 4-byte grid.  k == 0 does nothing.  Stream-ordered behind
+ * updates.  vkmr_hip_tree_merkleblock_async is the same for ONE stored tree (vkmr_hip_reduce_tree_async) with
+ * height == max(1, ceil(log2 count)) -- any other height is refused: B is 1 and block_trees_dev[0] is 0.
+ * vkmr_host_cpu_forest_merkleblocks (libvkmr_host.so) applies the same rule on the CPU; vkmr_host_cpu_merkleblock_extract is the
+ * receiver's side, Bitcoin Core's TraverseAndExtract under this height, with its CVE-2012-2459 check.  Not offered: a batched
+ * verifier on the device -- the receiver of a merkleblock is a light client.
+ */
+VKMR_API size_t vkmr_hip_forest_merkleblocks_max_hashes(uint64_t total, uint32_t ntrees, uint64_t max_count, uint32_t k);
+VKMR_API size_t vkmr_hip_forest_merkleblocks_max_flag_bytes(uint64_t total, uint32_t ntrees, uint64_t max_count, uint32_t k);
+VKMR_API size_t vkmr_hip_forest_merkleblocks_scratch_bytes(uint32_t k, uint32_t stride);
+VKMR_API vkmr_status vkmr_hip_forest_merkleblocks_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* forest_dev,
+                                                        uint64_t total, const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count,
+                                                        const uint32_t* trees_dev, const uint64_t* indices_dev, uint32_t k, void* scratch_dev,
+                                                        uint32_t* block_trees_dev, uint64_t* block_counts_dev, uint64_t* bit_counts_dev,
+                                                        uint64_t* hash_starts_dev, uint64_t* byte_starts_dev, vkmr_digest* hashes_dev,
+                                                        uint64_t hash_capacity, uint8_t* flags_dev, uint64_t flag_capacity, uint64_t* info_dev);
+VKMR_API vkmr_status vkmr_hip_tree_merkleblock_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* tree_dev,
+                                                     uint64_t count, uint32_t height, const uint64_t* indices_dev, uint32_t k, void* scratch_dev,
+                                                     uint32_t* block_trees_dev, uint64_t* block_counts_dev, uint64_t* bit_counts_dev,
+                                                     uint64_t* hash_starts_dev, uint64_t* byte_starts_dev, vkmr_digest* hashes_dev,
+                                                     uint64_t hash_capacity, uint8_t* flags_dev, uint64_t flag_capacity, uint64_t* info_dev);
+
+/*
  * COMBINE: duplicate-last Merkle root over n >= 1 slice roots given in slice order, always
  * at least one level -- the rule of CpuSha256D::Root that the reference applies to the slice
  * roots on the CPU (CpuSha256DforReductions, src/vkmr/Reductions.cpp:56-69, :703-712).  Here

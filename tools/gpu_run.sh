@@ -32,6 +32,9 @@
 #   proofs_at [args]       tools/proofs_at_timing.py: inclusion proofs as of an earlier count out of a stored forest (2^15 trees of 2 048 with 32
 #                          queries an epoch; one tree of 2^26 - 2^16 at E = 1, k = 2^20 and at E = k = 2^16), beside what they replace: a second
 #                          stored forest built from the prefix leaves plus its proof gather (one JSON line)
+#   merkleblocks [args]    tools/merkleblocks_timing.py: partial Merkle trees in BIP37 order out of a stored forest (2^15 trees of 2 048; 2^10, 2^16,
+#                          2^20 random entries, 2^16 filling whole trees) beside the multiproof gather, its downloads and the gather of a host reordering
+#                          (one JSON line)
 #   forest_repack [args]   tools/forest_repack_timing.py: the oldest trees of a stored forest dropped and the rest (or all) copied into an
 #                          empty forest, beside the stored build over the same leaves (one JSON line)
 #   cumask                 tools/cu_mask_probe.py: where CU-mask bits land, map/reduce on half the CUs with and without neighbours
@@ -213,6 +216,11 @@ consistency)
   timeout -k 10 500 python3 tools/consistency_timing.py "$@" --out $OUT/consistency_timing.json > /dev/null 2> $OUT/consistency_timing.err && echo "consistency_timing ok" &&
   cat $OUT/consistency_timing.json
   echo "consistency rc=$?"
+  ;;
+merkleblocks)
+  timeout -k 10 500 python3 tools/merkleblocks_timing.py "$@" --out $OUT/merkleblocks_timing.json > /dev/null 2> $OUT/merkleblocks_timing.err && echo "merkleblocks_timing ok" &&
+  cat $OUT/merkleblocks_timing.json
+  echo "merkleblocks rc=$?"
   ;;
 proofs_at)
   timeout -k 10 500 python3 tools/proofs_at_timing.py "$@" --out $OUT/proofs_at_timing.json > /dev/null 2> $OUT/proofs_at_timing.err && echo "proofs_at_timing ok" &&

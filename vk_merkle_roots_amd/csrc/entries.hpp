@@ -45,6 +45,8 @@ struct TreeCells {
         const uint64_t s = vkmr_math::sibling(index >> l, n);
         return (l == 0) ? digests + s : tree + lv.off[l] + s;
     }
+    // node_cell(t, l, p): the cell of node p of level l itself; the caller knows that l is below the height and p < n_l.
+    __device__ __forceinline__ const Node* node_cell(uint32_t, uint32_t l, uint64_t p) const { return (l == 0) ? digests + p : tree + lv.off[l] + p; }
 };
 
 struct ForestCells {
@@ -54,6 +56,11 @@ struct ForestCells {
         const uint64_t off = offsets[t], c = offsets[t + 1u] - off;
         const uint64_t s = vkmr_math::sibling(index >> l, vkmr_forest::level_count(c, l));
         return (l == 0) ? digests + off + s : forest + lv.base[l] + vkmr_forest::pos(off, t, l) + s;
+    }
+    __device__ __forceinline__ const Node* node_cell(uint32_t t, uint32_t l, uint64_t p) const
+    {
+        const uint64_t off = offsets[t];
+        return (l == 0) ? digests + off + p : forest + lv.base[l] + vkmr_forest::pos(off, t, l) + p;
     }
 };
 

@@ -981,4 +981,149 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_forest_proofs_at(const 
     return 0;
 }
 
+// Partial Merkle trees in BIP37 order on the CPU, by the rule of vkmr_hip_forest_merkleblocks_async, walked as the rule is
+// written (the device places everything by csrc/merkleblock_plan.hpp's closed form instead): the same entries, the same eight
+// outputs, info[0..4) = status, B, hashes, flag bytes.  Returns the status: 0 done; bit 0 a tree >= ntrees or an index >= c_t,
+// bit 1 pairs not strictly increasing (then only info[0] is written); bit 2 the hashes exceed hash_capacity or the flag bytes
+// flag_capacity (the per-block arrays and info are written, no hash and no flag is).  -1 for a missing pointer or k == 0, -2
+// when the offsets decrease somewhere (nothing written).  A touched tree's levels are formed once, tree by tree.
+__attribute__((visibility("default"))) int vkmr_host_cpu_forest_merkleblocks(const vkmr_digest* digests, const uint64_t* offsets, uint32_t ntrees,
+                                                                              const uint32_t* trees, const uint64_t* indices, uint32_t k,
+                                                                              uint32_t* block_trees, uint64_t* block_counts, uint64_t* bit_counts,
+                                                                              uint64_t* hash_starts, uint64_t* byte_starts, vkmr_digest* hashes,
+                                                                              uint64_t hash_capacity, uint8_t* flags, uint64_t flag_capacity, uint64_t* info)
+{
+    if (k == 0 || !digests || !offsets || !trees || !indices || !block_trees || !block_counts || !bit_counts || !hash_starts || !byte_starts || !info ||
+        (!hashes && hash_capacity > 0) || (!flags && flag_capacity > 0))
+        return -1;
+    for (uint32_t t = 0; t < ntrees; ++t)
+        if (offsets[t + 1] < offsets[t]) return -2;
+    int status = 0;
+    for (uint32_t q = 0; q < k; ++q) {
+        if (trees[q] >= ntrees || indices[q] >= offsets[trees[q] + 1] - offsets[trees[q]]) status |= 1;
+        if (q > 0 && (trees[q - 1] > trees[q] || (trees[q - 1] == trees[q] && indices[q - 1] >= indices[q]))) status |= 2;
+    }
+    info[0] = (uint64_t)status;
+    if (status) return status;
+    // the walk of one tree over the sorted indices [a, b): in(l, p) says whether node p of level l has a matched leaf below it
+    struct Walk {
+        const uint64_t* idx; uint32_t a, b; uint64_t c;
+        std::vector<uint8_t> bits;
+        std::vector<std::pair<uint32_t, uint64_t>> cells;
+        bool in(uint32_t l, uint64_t p) const
+        {
+            const uint64_t* lo = std::lower_bound(idx + a, idx + b, p << l);
+            return lo != idx + b && (*lo >> l) == p;
+        }
+        void visit(uint32_t l, uint64_t p)
+        {
+            const bool f = in(l, p);
+            bits.push_back(f ? 1 : 0);
+            if (l == 0 || !f) {
+                cells.push_back({l, p});
+                return;
+            }
+            visit(l - 1, 2 * p);
+            if (2 * p + 1 < vkmr_forest::level_count(c, l - 1)) visit(l - 1, 2 * p + 1);
+        }
+    };
+    std::vector<Walk> walks;
+    uint64_t nhashes = 0, nbytes = 0;
+    for (uint32_t a = 0; a < k;) {
+        const uint32_t b = forest_run_end(trees, a, k), t = trees[a];
+        Walk w{indices, a, b, offsets[t + 1] - offsets[t], {}, {}};
+        w.visit(vkmr_math::height(w.c), 0);
+        const size_t n = walks.size();
+        block_trees[n] = t;
+        block_counts[n] = w.c;
+        bit_counts[n] = w.bits.size();
+        hash_starts[n] = nhashes;
+        byte_starts[n] = nbytes;
+        nhashes += w.cells.size();
+        nbytes += (w.bits.size() + 7) / 8;
+        walks.push_back(std::move(w));
+        a = b;
+    }
+    hash_starts[walks.size()] = nhashes;
+    byte_starts[walks.size()] = nbytes;
+    info[1] = walks.size();
+    info[2] = nhashes;
+    info[3] = nbytes;
+    if (nhashes > hash_capacity || nbytes > flag_capacity) {
+        info[0] = 4;
+        return 4;
+    }
+    std::vector<std::vector<vkmr_digest>> levels;
+    for (size_t n = 0; n < walks.size(); ++n) {
+        const Walk& w = walks[n];
+        const uint32_t t = block_trees[n];
+        tree_levels(digests + offsets[t], digests + offsets[t + 1], vkmr_math::height(w.c), levels);
+        for (size_t j = 0; j < w.cells.size(); ++j) hashes[hash_starts[n] + j] = levels[w.cells[j].first][w.cells[j].second];
+        uint8_t* out = flags + byte_starts[n];
+        std::memset(out, 0, (w.bits.size() + 7) / 8);
+        for (size_t i = 0; i < w.bits.size(); ++i) out[i >> 3] |= (uint8_t)(w.bits[i] << (i & 7));
+    }
+    return 0;
+}
+
+// The receiver's side of one partial Merkle tree: Bitcoin Core's CPartialMerkleTree::ExtractMatches (TraverseAndExtract) under
+// this project's height h = max(1, ceil(log2 count)).  `hashes` [nhashes] and the flag bytes [nbytes] are one block of
+// vkmr_hip_forest_merkleblocks_async; on 0 root_out is the root they fold to, matched_idx_out / matched_hash_out (room for
+// nhashes entries each) the matched leaves in ascending order and *nmatched_out their number.  The caller compares the root
+// with the one it trusts.  Refusals, nothing written: -1 a missing pointer, -2 count == 0, -3 more hashes than leaves, -4 fewer
+// flag bits than hashes, -5 a flag or a hash read past the end, -6 not all hashes used, -7 the flags used do not end in the last
+// byte, -8 a right child that exists and equals its left (CVE-2012-2459: [a, b, c, c] has the root of [a, b, c]).  Padding bits
+// are not inspected, as in Core.
+__attribute__((visibility("default"))) int vkmr_host_cpu_merkleblock_extract(uint64_t count, const vkmr_digest* hashes, uint64_t nhashes,
+                                                                              const uint8_t* flag_bytes, uint64_t nbytes, vkmr_digest* root_out,
+                                                                              uint64_t* matched_idx_out, vkmr_digest* matched_hash_out, uint64_t* nmatched_out)
+{
+    if (!root_out || !matched_idx_out || !matched_hash_out || !nmatched_out || (!hashes && nhashes > 0) || (!flag_bytes && nbytes > 0)) return -1;
+    if (count == 0) return -2;
+    if (nhashes > count) return -3;
+    if (nbytes < (nhashes + 7) / 8) return -4;       // fewer flag bits than hashes
+    struct Extract {
+        uint64_t count; const vkmr_digest* hashes; uint64_t nhashes; const uint8_t* bytes; uint64_t nbits;
+        uint64_t bit = 0, hash = 0;
+        int bad = 0;
+        std::vector<uint64_t> idx;
+        std::vector<vkmr_digest> leaves;
+        vkmr_digest visit(uint32_t l, uint64_t p)
+        {
+            vkmr_digest x{};
+            if (bad) return x;
+            if (bit >= nbits) { bad = -5; return x; }
+            const bool f = (bytes[bit >> 3] >> (bit & 7)) & 1;
+            ++bit;
+            if (l == 0 || !f) {
+                if (hash >= nhashes) { bad = -5; return x; }
+                x = hashes[hash++];
+                if (l == 0 && f) { idx.push_back(p); leaves.push_back(x); }
+                return x;
+            }
+            const vkmr_digest left = visit(l - 1, 2 * p);
+            vkmr_digest right = left;
+            if (2 * p + 1 < vkmr_forest::level_count(count, l - 1)) {
+                right = visit(l - 1, 2 * p + 1);
+                if (!bad && std::memcmp(left.data, right.data, sizeof(left.data)) == 0) bad = -8;
+            }
+            if (bad) return x;
+            vkmr::cpu_sha256d_pair(left.data, right.data, x.data);
+            return x;
+        }
+    };
+    Extract e{count, hashes, nhashes, flag_bytes, nbytes * 8};
+    const vkmr_digest root = e.visit(vkmr_math::height(count), 0);
+    if (e.bad) return e.bad;
+    if (e.hash != nhashes) return -6;
+    if ((e.bit + 7) / 8 != nbytes) return -7;
+    *root_out = root;
+    for (size_t j = 0; j < e.idx.size(); ++j) {
+        matched_idx_out[j] = e.idx[j];
+        matched_hash_out[j] = e.leaves[j];
+    }
+    *nmatched_out = e.idx.size();
+    return 0;
+}
+
 }  // extern "C"

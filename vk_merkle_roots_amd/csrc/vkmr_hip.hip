@@ -32,6 +32,10 @@
 //   proofs_at_kernels.hpp  proofs_at_*_kernel   inclusion proofs as of an earlier count: the old tree's right edge hashed once per
 //                                              epoch (one lane each, one hash_pair), then a gather without a hash, one lane per
 //                                              (query, level) (rules: proofs_at_plan.hpp)
+//   merkleblock_kernels.hpp  merkleblock_*_kernel   partial Merkle trees in BIP37 order, one per named tree: the groups of the
+//                                              entries summed, placed by two prefix sums (entries, blocks), then one lane per
+//                                              (entry, level) copies at most three nodes and sets one flag; no hash, no walk
+//                                              (the closed form and the sizes: merkleblock_plan.hpp)
 //   forest_tree_kernels.hpp  forest_proofs_kernel          proofs gathered from the stored forest, one lane per (query, level)
 //                            verify_forest_proofs_kernel   batch verification of proofs of unequal height, one lane per proof
 //                            forest_update_*_kernel        leaf updates of the stored forest: tree_update_*'s bodies, a tree per entry
@@ -63,6 +67,7 @@
 //   sort_plan.hpp       the entry sort's passes, tiles, histogram words and scratch layout
 //   diff_plan.hpp       one step of a diff's descent, the bound on every step's frontier and the scratch layout
 //   audit_plan.hpp      the ballot words of an audit's levels, the nodes it checks and the scratch layout
+//   merkleblock_plan.hpp  what a BIP37 walk appends between two matched leaves, in closed form; the three size bounds, the scratch layout
 //
 // Host side: plain launches on the caller's stream, each through launch() and so each checked; every argument refusal
 // through refuse(__func__, why); no allocation, no sync inside the *_async entry points.
@@ -100,6 +105,7 @@ using vkmr_dev::Node;
 #include "frontier_kernels.hpp"
 #include "consistency_kernels.hpp"
 #include "proofs_at_kernels.hpp"
+#include "merkleblock_kernels.hpp"
 
 // ============================================================================
 // C ABI
@@ -1493,6 +1499,158 @@ vkmr_status vkmr_hip_forest_proofs_at_async(int dev, vkmr_stream s, const vkmr_d
     return launch(proofs_at_gather_kernel, grid_of((uint64_t)k * stride), dim3(256), S(s), nodes(digests_dev), nodes(forest_dev), lv, offsets_dev,
                   nodes(roots_dev), epoch_trees_dev, epoch_counts_dev, E, epochs_dev, indices_dev, k, stride, nodes(edges_out_dev), nodes(siblings_dev),
                   heights_dev, status_dev);
+}
+
+// ---- partial Merkle trees in BIP37 order (merkleblock_kernels.hpp, merkleblock_plan.hpp) ----------------------------------------
+
+size_t vkmr_hip_forest_merkleblocks_max_hashes(uint64_t total, uint32_t ntrees, uint64_t max_count, uint32_t k)
+{
+    if (total == 0 || ntrees == 0 || max_count == 0 || k == 0) return 0;
+    return (size_t)vkmr_mb::max_hashes(total, ntrees, max_count, k);
+}
+
+size_t vkmr_hip_forest_merkleblocks_max_flag_bytes(uint64_t total, uint32_t ntrees, uint64_t max_count, uint32_t k)
+{
+    if (total == 0 || ntrees == 0 || max_count == 0 || k == 0) return 0;
+    return (size_t)vkmr_mb::max_flag_bytes(total, ntrees, max_count, k);
+}
+
+size_t vkmr_hip_forest_merkleblocks_scratch_bytes(uint32_t k, uint32_t stride)
+{
+    if (k == 0 || stride == 0 || stride > 63) return 0;
+    return vkmr_mb::layout(k, stride).bytes;
+}
+
+namespace {
+// The parts of a merkleblock call's scratch_dev as the kernels take them.
+struct MerkleblockScratch {
+    uint64_t *flag_at, *hash_at, *sums, *bit_start, *byte_sums;
+    uint32_t *block_of, *flag_words;
+    MerkleblockScratch(void* scratch_dev, const vkmr_mb::Layout& L)
+    {
+        const uintptr_t at = reinterpret_cast<uintptr_t>(scratch_dev);
+        flag_at = reinterpret_cast<uint64_t*>(at + L.flag_at);
+        hash_at = reinterpret_cast<uint64_t*>(at + L.hash_at);
+        block_of = reinterpret_cast<uint32_t*>(at + L.block_of);
+        sums = reinterpret_cast<uint64_t*>(at + L.sums);
+        bit_start = reinterpret_cast<uint64_t*>(at + L.bit_start);
+        byte_sums = reinterpret_cast<uint64_t*>(at + L.byte_sums);
+        flag_words = reinterpret_cast<uint32_t*>(at + L.flag_words);
+    }
+};
+
+struct MerkleblockOutputs {
+    uint32_t* block_trees;
+    uint64_t *block_counts, *bit_counts, *hash_starts, *byte_starts;
+    vkmr_digest* hashes;
+    uint64_t hash_capacity;
+    uint8_t* flags;
+    uint64_t flag_capacity;
+    uint64_t* info;
+};
+
+vkmr_status merkleblock_outputs_check(const char* who, const MerkleblockOutputs& o, const void* scratch_dev)
+{
+    if (!o.block_trees || !o.block_counts || !o.bit_counts || !o.hash_starts || !o.byte_starts || !o.info || !scratch_dev ||
+        (!o.hashes && o.hash_capacity > 0) || (!o.flags && o.flag_capacity > 0))
+        return refuse(who, "null pointer");
+    if (reinterpret_cast<uintptr_t>(scratch_dev) & 15u) return refuse(who, "scratch must be 16-byte aligned");
+    if (reinterpret_cast<uintptr_t>(o.flags) & 3u) return refuse(who, "flags_dev must be 4-byte aligned");
+    return VKMR_OK;
+}
+
+// The launches behind the index check, the same for one tree and for a forest but for the three kernels that read entries:
+// `sums`, `places` and `emit` launch those with the caller's own arguments in front.
+extern "C++" {
+template <class Sums, class Places, class Emit>
+vkmr_status merkleblock_launch(hipStream_t stream, uint32_t k, uint32_t stride, const vkmr_mb::Layout& L, const MerkleblockScratch& sc,
+                               const MerkleblockOutputs& o, Sums sums, Places places, Emit emit)
+{
+    const dim3 egrid((uint32_t)L.groups), eblock(VKMR_MB_THREADS);
+    VKMR_CHECK(sums(egrid, eblock));
+    VKMR_CHECK(launch(merkleblock_starts_kernel, dim3(1), eblock, stream, sc.sums, L.groups, o.info, sc.bit_start, o.hash_starts));
+    VKMR_CHECK(places(egrid, eblock));
+    VKMR_CHECK(launch(merkleblock_byte_sums_kernel, egrid, eblock, stream, o.info, sc.bit_start, o.bit_counts, sc.byte_sums));
+    VKMR_CHECK(launch(merkleblock_byte_starts_kernel, dim3(1), eblock, stream, sc.byte_sums, L.groups, o.hash_capacity, o.flag_capacity, o.info));
+    VKMR_CHECK(launch(merkleblock_byte_places_kernel, dim3((uint32_t)(((uint64_t)k + 1 + VKMR_MB_THREADS - 1) / VKMR_MB_THREADS)), eblock, stream, o.info,
+                      sc.bit_start, sc.byte_sums, o.byte_starts));
+    // the flag words in use never exceed the scratch's (the plan's bound) nor, with status 0, the caller's capacity
+    uint64_t words = (o.flag_capacity + 3) / 4;
+    if (words > L.words) words = L.words;
+    if (words == 0) words = 1;                   // no byte fits: the status is bit 2 and both kernels return at once
+    VKMR_CHECK(launch(merkleblock_zero_kernel, grid_of(words), dim3(256), stream, o.info, sc.flag_words));
+    VKMR_CHECK(emit(grid_of(k, stride), dim3(256)));
+    return launch(merkleblock_flags_kernel, grid_of(words), dim3(256), stream, o.info, sc.flag_words, o.flags);
+}
+}  // extern "C++"
+}  // namespace
+
+vkmr_status vkmr_hip_forest_merkleblocks_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* forest_dev, uint64_t total,
+                                               const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count, const uint32_t* trees_dev,
+                                               const uint64_t* indices_dev, uint32_t k, void* scratch_dev, uint32_t* block_trees_dev,
+                                               uint64_t* block_counts_dev, uint64_t* bit_counts_dev, uint64_t* hash_starts_dev, uint64_t* byte_starts_dev,
+                                               vkmr_digest* hashes_dev, uint64_t hash_capacity, uint8_t* flags_dev, uint64_t flag_capacity,
+                                               uint64_t* info_dev)
+{
+    if (k == 0) return VKMR_OK;
+    const MerkleblockOutputs o{block_trees_dev, block_counts_dev, bit_counts_dev, hash_starts_dev, byte_starts_dev, hashes_dev, hash_capacity, flags_dev,
+                               flag_capacity, info_dev};
+    if (!digests_dev || !forest_dev || !offsets_dev || !trees_dev || !indices_dev) return refuse(__func__, "null pointer");
+    VKMR_CHECK(merkleblock_outputs_check(__func__, o, scratch_dev));
+    VKMR_CHECK(forest_args_check(__func__, total, ntrees, max_count, k, "a forest without a leaf has none to match", scratch_dev));
+    const uint32_t H = vkmr_forest::launches(total, max_count);   // <= 58
+    const ForestLevels lv = forest_levels(total, ntrees, H);
+    const vkmr_mb::Layout L = vkmr_mb::layout(k, H);
+    const MerkleblockScratch sc(scratch_dev, L);
+    hipStream_t stream = S(s);
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_TRY(hipMemsetAsync(info_dev, 0, sizeof(uint64_t), stream));
+    VKMR_CHECK(launch(forest_update_check_kernel, grid_of(k), dim3(256), stream, offsets_dev, ntrees, trees_dev, indices_dev, k,
+                      reinterpret_cast<uint32_t*>(info_dev)));
+    return merkleblock_launch(
+        stream, k, H, L, sc, o,
+        [&](dim3 g, dim3 b) { return launch(merkleblock_forest_sums_kernel, g, b, stream, offsets_dev, trees_dev, indices_dev, k, L.groups, info_dev, sc.sums); },
+        [&](dim3 g, dim3 b) {
+            return launch(merkleblock_forest_places_kernel, g, b, stream, offsets_dev, trees_dev, indices_dev, k, L.groups, info_dev, sc.sums, sc.flag_at,
+                          sc.hash_at, sc.block_of, sc.bit_start, block_trees_dev, block_counts_dev, hash_starts_dev);
+        },
+        [&](dim3 g, dim3 b) {
+            return launch(merkleblock_forest_emit_kernel, g, b, stream, nodes(digests_dev), nodes(forest_dev), lv, offsets_dev, trees_dev, indices_dev, k,
+                          info_dev, sc.flag_at, sc.hash_at, sc.block_of, sc.bit_start, byte_starts_dev, nodes(hashes_dev), sc.flag_words);
+        });
+}
+
+vkmr_status vkmr_hip_tree_merkleblock_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* tree_dev, uint64_t count,
+                                            uint32_t height, const uint64_t* indices_dev, uint32_t k, void* scratch_dev, uint32_t* block_trees_dev,
+                                            uint64_t* block_counts_dev, uint64_t* bit_counts_dev, uint64_t* hash_starts_dev, uint64_t* byte_starts_dev,
+                                            vkmr_digest* hashes_dev, uint64_t hash_capacity, uint8_t* flags_dev, uint64_t flag_capacity, uint64_t* info_dev)
+{
+    if (k == 0) return VKMR_OK;
+    const MerkleblockOutputs o{block_trees_dev, block_counts_dev, bit_counts_dev, hash_starts_dev, byte_starts_dev, hashes_dev, hash_capacity, flags_dev,
+                               flag_capacity, info_dev};
+    if (!digests_dev || !tree_dev || !indices_dev) return refuse(__func__, "null pointer");
+    VKMR_CHECK(merkleblock_outputs_check(__func__, o, scratch_dev));
+    if (count == 0 || height == 0 || height > 63 || height != vkmr_math::height(count))
+        return refuse(__func__, "height must be max(1, ceil(log2 count)): the walk starts at the tree's root");
+    if (grid_too_large(groups_of(k))) return refuse(__func__, "too many entries in one call");
+    const TreeLevels lv = tree_levels(count, height);
+    const vkmr_mb::Layout L = vkmr_mb::layout(k, height);
+    const MerkleblockScratch sc(scratch_dev, L);
+    hipStream_t stream = S(s);
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_TRY(hipMemsetAsync(info_dev, 0, sizeof(uint64_t), stream));
+    VKMR_CHECK(launch(tree_update_check_kernel, grid_of(k), dim3(256), stream, indices_dev, k, count, reinterpret_cast<uint32_t*>(info_dev)));
+    return merkleblock_launch(
+        stream, k, height, L, sc, o,
+        [&](dim3 g, dim3 b) { return launch(merkleblock_tree_sums_kernel, g, b, stream, indices_dev, count, k, L.groups, info_dev, sc.sums); },
+        [&](dim3 g, dim3 b) {
+            return launch(merkleblock_tree_places_kernel, g, b, stream, indices_dev, count, k, L.groups, info_dev, sc.sums, sc.flag_at, sc.hash_at, sc.block_of,
+                          sc.bit_start, block_trees_dev, block_counts_dev, hash_starts_dev);
+        },
+        [&](dim3 g, dim3 b) {
+            return launch(merkleblock_tree_emit_kernel, g, b, stream, nodes(digests_dev), nodes(tree_dev), lv, count, indices_dev, k, info_dev, sc.flag_at,
+                          sc.hash_at, sc.block_of, sc.bit_start, byte_starts_dev, nodes(hashes_dev), sc.flag_words);
+        });
 }
 
 // ---- multiproofs inside the stored forest (forest_tree_kernels.hpp) ---------------------------------------------------------

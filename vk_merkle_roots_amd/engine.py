@@ -791,6 +791,30 @@ class HipDevice:
                    epoch_counts_buf, E, epochs_buf, indices_buf, k, stride, edges_out_buf, old_roots_out_buf, siblings_buf, heights_buf, status_buf,
                    stream=stream)
 
+    def forest_merkleblocks_enqueue(self, digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, trees_buf, indices_buf, k, scratch_buf,
+                                    block_trees_buf, block_counts_buf, bit_counts_buf, hash_starts_buf, byte_starts_buf, hashes_buf, hash_capacity,
+                                    flags_buf, flag_capacity, info_buf, stream=None):
+        """One partial Merkle tree in BIP37 order per tree named by the k sorted (tree, index) entries in device memory
+        (vkmr_hip_forest_merkleblocks_async): the per-block arrays (room for k entries, the two starts for k + 1), the hashes
+        (hash_capacity cells), the flag bytes (flag_capacity bytes) and info_buf (4 uint64: status, blocks, hashes, flag
+        bytes; merkleblocks_status_text names the status bits).  scratch_buf: merkleblocks_scratch_bytes(k, the forest's
+        stride).  All in device memory.  include/vkmr_hip.h."""
+        self._call("vkmr_hip_forest_merkleblocks_async", digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, trees_buf, indices_buf, k,
+                   scratch_buf, block_trees_buf, block_counts_buf, bit_counts_buf, hash_starts_buf, byte_starts_buf, hashes_buf, hash_capacity, flags_buf,
+                   flag_capacity, info_buf, stream=stream)
+
+    def tree_merkleblock_enqueue(self, digests_buf, tree_buf, count, height, indices_buf, k, scratch_buf, block_trees_buf, block_counts_buf,
+                                 bit_counts_buf, hash_starts_buf, byte_starts_buf, hashes_buf, hash_capacity, flags_buf, flag_capacity, info_buf,
+                                 stream=None):
+        """forest_merkleblocks_enqueue for ONE stored tree of height max(1, ceil(log2 count)) and k strictly increasing indices
+        (vkmr_hip_tree_merkleblock_async): one block, tree 0."""
+        self._call("vkmr_hip_tree_merkleblock_async", digests_buf, tree_buf, count, height, indices_buf, k, scratch_buf, block_trees_buf,
+                   block_counts_buf, bit_counts_buf, hash_starts_buf, byte_starts_buf, hashes_buf, hash_capacity, flags_buf, flag_capacity, info_buf,
+                   stream=stream)
+
+    def merkleblocks_scratch_bytes(self, k, stride):
+        return self.lib.vkmr_hip_forest_merkleblocks_scratch_bytes(k, stride)
+
     def reduce_scratch(self, count, levels_variant=False):
         fn = self.lib.vkmr_hip_reduce_levels_scratch_bytes if levels_variant else self.lib.vkmr_hip_reduce_scratch_bytes
         return self.alloc(fn(count))
@@ -893,6 +917,106 @@ class ForestMultiproof:
             raise ValueError(f"ForestMultiproof.split: the entries imply {at} nodes, the proof holds {self.nodes.shape[0]}")
         return {t: Multiproof(idx, np.concatenate(parts[r]).reshape(-1, 8), np.array(counts[r], dtype=np.uint64), h)
                 for r, (t, idx, h) in enumerate(runs)}
+
+
+def _compact_size(n):
+    """Bitcoin's CompactSize of n < 2^64."""
+    if n < 253:
+        return bytes([n])
+    for tag, width in ((253, 2), (254, 4), (255, 8)):
+        if n < 1 << (8 * width):
+            return bytes([tag]) + int(n).to_bytes(width, "little")
+    raise ValueError("CompactSize: a length of 2^64 or more")
+
+
+def _read_compact_size(data, at, what):
+    """(n, the position behind it); any encoding of a length is read, the shortest is not insisted on."""
+    if at >= len(data):
+        raise ValueError(f"PartialMerkleTree.parse: the bytes end in front of {what}")
+    tag = data[at]
+    if tag < 253:
+        return tag, at + 1
+    width = {253: 2, 254: 4, 255: 8}[tag]
+    if at + 1 + width > len(data):
+        raise ValueError(f"PartialMerkleTree.parse: the bytes end inside {what}")
+    return int.from_bytes(data[at + 1: at + 1 + width], "little"), at + 1 + width
+
+
+class PartialMerkleTree:
+    """One tree's partial Merkle tree in BIP37 order: `count`, the tree's leaves; `hashes` uint32 [n, 8], word-valued digests in
+    the walk's order; `flags`, the flag bytes (uint8 [m], flag i in bit i & 7 of byte i >> 3).  One block of
+    vkmr_hip_forest_merkleblocks_async."""
+
+    def __init__(self, count, hashes, flags):
+        self.count = int(count)
+        self.hashes = _host(hashes, np.uint32, -1, 8)
+        self.flags = np.frombuffer(bytes(flags), dtype=np.uint8) if isinstance(flags, (bytes, bytearray)) else _host(flags, np.uint8, -1)
+
+    def serialize(self):
+        """Bitcoin's CPartialMerkleTree bytes: uint32 LE count, CompactSize, the hashes -- each as the big-endian bytes of its
+        eight words, the byte order of vkmr_hip_digest_hex --, CompactSize, the flag bytes.  ValueError for a count above
+        2^32 - 1, which the wire form cannot say."""
+        if not 0 <= self.count <= 0xFFFFFFFF:
+            raise ValueError(f"PartialMerkleTree.serialize: a count of {self.count} does not fit the wire form's 32 bits")
+        return (self.count.to_bytes(4, "little") + _compact_size(self.hashes.shape[0]) + self.hashes.astype(">u4").tobytes() +
+                _compact_size(self.flags.shape[0]) + self.flags.tobytes())
+
+    @classmethod
+    def parse(cls, data):
+        """The inverse of serialize().  ValueError for bytes that end early or go on behind the flags."""
+        data = bytes(data)
+        if len(data) < 4:
+            raise ValueError("PartialMerkleTree.parse: the bytes end inside the count")
+        count = int.from_bytes(data[:4], "little")
+        n, at = _read_compact_size(data, 4, "the number of hashes")
+        if at + 32 * n > len(data):
+            raise ValueError("PartialMerkleTree.parse: the bytes end inside the hashes")
+        hashes = np.frombuffer(data[at: at + 32 * n], dtype=">u4").astype(np.uint32).reshape(n, 8)
+        m, at = _read_compact_size(data, at + 32 * n, "the number of flag bytes")
+        if at + m != len(data):
+            raise ValueError("PartialMerkleTree.parse: " + ("the bytes end inside the flags" if at + m > len(data) else "bytes behind the flags"))
+        return cls(count, hashes, np.frombuffer(data[at:], dtype=np.uint8))
+
+    def extract(self):
+        """(root [8] uint32, indices uint64 [n], leaves uint32 [n, 8]): the root the hashes fold to and the matched leaves, by
+        vkmr_host_cpu_merkleblock_extract -- Bitcoin Core's TraverseAndExtract under this project's height.  The caller compares
+        the root with the one it trusts.  ValueError, naming the reason, when the tree is refused."""
+        n = int(self.hashes.shape[0])
+        hashes, flags = np.ascontiguousarray(self.hashes), np.ascontiguousarray(self.flags)
+        root, idx, leaves, found = np.zeros(8, np.uint32), np.zeros(max(n, 1), np.uint64), np.zeros((max(n, 1), 8), np.uint32), np.zeros(1, np.uint64)
+        rc = _abi.host_lib().vkmr_host_cpu_merkleblock_extract(self.count, hashes.ctypes.data if n else None, n, flags.ctypes.data if flags.size else None,
+                                                               int(flags.shape[0]), root.ctypes.data, idx.ctypes.data, leaves.ctypes.data, found.ctypes.data)
+        if rc != 0:
+            raise ValueError(f"PartialMerkleTree.extract: refused ({rc}: {MERKLEBLOCK_EXTRACT_REFUSALS.get(rc, 'unknown')})")
+        m = int(found[0])
+        return root, idx[:m].copy(), leaves[:m].copy()
+
+
+MERKLEBLOCK_EXTRACT_REFUSALS = {-1: "a missing pointer", -2: "a count of 0", -3: "more hashes than leaves", -4: "fewer flag bits than hashes",
+                                -5: "a flag or a hash read past the end", -6: "not all hashes used", -7: "the flags used do not end in the last byte",
+                                -8: "a right child equal to its left (CVE-2012-2459)"}
+
+
+class PartialMerkleTrees:
+    """What merkleblocks() gives: one partial Merkle tree per named tree, side by side as the device wrote them.  `trees` uint32
+    [B] ascending, `counts` uint64 [B], `bit_counts` uint64 [B] (flags per block), `hash_starts` and `byte_starts` uint64 [B + 1],
+    `hashes` uint32 [N, 8] tree-major, `flags` uint8 [bytes] (every block starts on a byte).  len() is B; [b] is block b as a
+    PartialMerkleTree."""
+
+    def __init__(self, trees, counts, bit_counts, hash_starts, byte_starts, hashes, flags):
+        self.trees, self.counts, self.bit_counts, self.hash_starts, self.byte_starts = trees, counts, bit_counts, hash_starts, byte_starts
+        self.hashes, self.flags = hashes, flags
+
+    def __len__(self):
+        return int(self.trees.shape[0])
+
+    def __getitem__(self, b):
+        b = int(b)
+        if not -len(self) <= b < len(self):
+            raise IndexError(f"block {b} of {len(self)}")
+        b %= len(self)
+        return PartialMerkleTree(int(self.counts[b]), self.hashes[int(self.hash_starts[b]): int(self.hash_starts[b + 1])],
+                                 self.flags[int(self.byte_starts[b]): int(self.byte_starts[b + 1])])
 
 
 class UpdateWitness:
@@ -1053,6 +1177,43 @@ class _Stored:
             nodes, extra, counts = self._gather_multiproof(tmp, d_sorted, n, "multiproof_of", "its own sorted entries")
             cols, order = self._read(d_sorted, self._columns, n), self.dev.download(d_order, 4 * n)
         return self._Proof(*cols, *extra, nodes, counts, self.stride), order
+
+    def _gather_merkleblocks(self, tmp, d_entries, k, method, whose):
+        """merkleblocks_async over the k sorted entries in d_entries with buffers of the bounds' sizes, read back as far as they
+        are used: a PartialMerkleTrees."""
+        cap_h, cap_b, scratch_bytes = self._merkleblocks_sizes(k)
+        cols = (np.uint32, np.uint64, np.uint64)
+        d_rows, d_hs, d_bs = self._alloc(tmp, cols, k), tmp.alloc(8 * (k + 1)), tmp.alloc(8 * (k + 1))
+        d_hashes, d_flags, d_info = tmp.alloc(32 * cap_h), tmp.alloc(cap_b), tmp.alloc(32)
+        self.merkleblocks_async(*d_entries, k, tmp.alloc(scratch_bytes), *d_rows, d_hs, d_bs, d_hashes, cap_h, d_flags, cap_b, d_info)
+        status, B, n, m = (int(x) for x in self.dev.download(d_info, 32, dtype=np.uint64))
+        if status:
+            text = merkleblocks_status_text(status)
+            raise RuntimeError(f"{type(self).__name__}.{method}: the device refused {whose} (status {status}{': ' + text if text else ''})")
+        trees, counts, bits = self._read(d_rows, cols, B)
+        return PartialMerkleTrees(trees, counts, bits, self.dev.download(d_hs, 8 * (B + 1), dtype=np.uint64), self.dev.download(d_bs, 8 * (B + 1), dtype=np.uint64),
+                                  self.dev.download(d_hashes, 32 * n).reshape(n, 8), self.dev.download(d_flags, m, dtype=np.uint8))
+
+    def _merkleblocks(self, entries, what):
+        self._merkleblock_height(what)
+        *cols, _ = self._update_order(*entries, what)
+        k = int(cols[-1].shape[0])
+        if k == 0:
+            raise ValueError(f"{what}: no entry")
+        with self.dev.scope() as tmp:
+            return self._gather_merkleblocks(tmp, [tmp.upload(c) for c in cols], k, what, "sorted in-range entries")
+
+    def _merkleblocks_of(self, digests, what):
+        self._merkleblock_height(what)
+        q = _host(digests, np.uint32, -1, 8)
+        k = int(q.shape[0])
+        if k == 0:
+            raise ValueError(f"{what}: no digest")
+        with self.dev.scope() as tmp:
+            d_sorted, d_order, (n, _, _, _) = self._sort(tmp, self._find(tmp, q, k), k)
+            if n == 0:
+                raise ValueError(f"{what}: none of the digests is a leaf")
+            return self._gather_merkleblocks(tmp, d_sorted, n, what, "its own sorted entries"), self.dev.download(d_order, 4 * n)
 
     def _apply(self, tmp, method, whose, d_entries, d_leaves, n):
         """update_async of the n sorted entries in d_entries to the digests in d_leaves, and its status word read back."""
@@ -1296,6 +1457,37 @@ class MerkleTree(_Stored):
         """A Multiproof of leaves `indices` (a host array; sorted and deduplicated here).  IndexError for an index < 0 or
         >= count, ValueError for indices that are not integers or for none at all, before any device call."""
         return self._multiproof((indices,))
+
+    def merkleblocks_async(self, indices_buf, k, scratch_buf, block_trees_buf, block_counts_buf, bit_counts_buf, hash_starts_buf, byte_starts_buf,
+                           hashes_buf, hash_capacity, flags_buf, flag_capacity, info_buf, stream=None):
+        """The tree's partial Merkle tree in BIP37 order for the k strictly increasing indices in device memory: one block.
+        HipDevice.tree_merkleblock_enqueue; include/vkmr_hip.h."""
+        self.dev.tree_merkleblock_enqueue(self.digests, self.tree, self.count, self.height, indices_buf, k, scratch_buf, block_trees_buf, block_counts_buf,
+                                          bit_counts_buf, hash_starts_buf, byte_starts_buf, hashes_buf, hash_capacity, flags_buf, flag_capacity, info_buf,
+                                          stream=stream)
+
+    def _merkleblocks_sizes(self, k):
+        """(the most hashes, the most flag bytes, the bytes of the scratch) of k entries: the forest's bounds for one tree."""
+        lib = self.dev.lib
+        return (lib.vkmr_hip_forest_merkleblocks_max_hashes(self.count, 1, self.count, k),
+                lib.vkmr_hip_forest_merkleblocks_max_flag_bytes(self.count, 1, self.count, k), lib.vkmr_hip_forest_merkleblocks_scratch_bytes(k, self.height))
+
+    def _merkleblock_height(self, what):
+        if self.height != tree_height(self.count):
+            raise ValueError(f"{what}: a tree of {self.count} leaves stored with height {self.height}; the walk needs height {tree_height(self.count)}")
+
+    def merkleblock(self, indices):
+        """The PartialMerkleTree (BIP37 order, Bitcoin's CPartialMerkleTree) that shows leaves `indices` (a host array; sorted
+        and deduplicated here) to be in this tree.  IndexError for an index < 0 or >= count, ValueError for none at all or for
+        a tree stored with another height than max(1, ceil(log2 count)), before any device call."""
+        return self._merkleblocks((indices,), "merkleblock")[0]
+
+    def merkleblock_of(self, digests):
+        """(PartialMerkleTree, order): find -> sort -> merkleblock on the device for the leaves that hold `digests` ([k, 8], any
+        order); digests[order[j]] is the j-th matched leaf, digests that are no leaf are left out, repeats count once.
+        ValueError when none is found."""
+        blocks, order = self._merkleblocks_of(digests, "merkleblock_of")
+        return blocks[0], order
 
     def update_async(self, indices_buf, leaves_buf, k, status_buf, stream=None):
         """Leaves indices[q] = leaves[q], q < k, and every ancestor rehashed, on the device: indices [k] uint64 strictly
@@ -1871,6 +2063,37 @@ class MerkleForest(_Stored):
         index outside [0, counts[tree]), all before any device call."""
         return self._multiproof((trees, indices))
 
+    def merkleblocks_async(self, trees_buf, indices_buf, k, scratch_buf, block_trees_buf, block_counts_buf, bit_counts_buf, hash_starts_buf,
+                           byte_starts_buf, hashes_buf, hash_capacity, flags_buf, flag_capacity, info_buf, stream=None):
+        """One partial Merkle tree in BIP37 order per tree named by the k (tree, index) entries in device memory (strictly
+        increasing pairs).  HipDevice.forest_merkleblocks_enqueue; include/vkmr_hip.h."""
+        self.dev.forest_merkleblocks_enqueue(self.digests, self.forest, self.total, self.offsets, self.ntrees, self.max_count, trees_buf, indices_buf, k,
+                                             scratch_buf, block_trees_buf, block_counts_buf, bit_counts_buf, hash_starts_buf, byte_starts_buf, hashes_buf,
+                                             hash_capacity, flags_buf, flag_capacity, info_buf, stream=stream)
+
+    def _merkleblocks_sizes(self, k):
+        """(the most hashes, the most flag bytes, the bytes of the scratch) of k entries."""
+        lib = self.dev.lib
+        return (lib.vkmr_hip_forest_merkleblocks_max_hashes(self.total, self.ntrees, self.max_count, k),
+                lib.vkmr_hip_forest_merkleblocks_max_flag_bytes(self.total, self.ntrees, self.max_count, k),
+                lib.vkmr_hip_forest_merkleblocks_scratch_bytes(k, self.levels))
+
+    def _merkleblock_height(self, what):
+        pass                                   # a forest's trees have the height the walk needs
+
+    def merkleblocks(self, trees, indices):
+        """PartialMerkleTrees: one partial Merkle tree in BIP37 order (Bitcoin's CPartialMerkleTree) per tree named, showing
+        leaves `indices` of trees `trees` (host arrays; the pairs sorted and deduplicated here) -- the `merkleblock` answers of
+        a rescan over many blocks, one device call.  ValueError when there is not one tree per index or for no entry at all,
+        IndexError for a tree outside [0, ntrees) or an index outside [0, counts[tree]), all before any device call."""
+        return self._merkleblocks((trees, indices), "merkleblocks")
+
+    def merkleblocks_of(self, digests):
+        """(PartialMerkleTrees, order): find -> sort -> merkleblocks on the device for the leaves that hold `digests` ([k, 8],
+        txids in any order); digests[order[j]] is the leaf of the j-th sorted entry, digests that are no leaf are left out,
+        repeats count once.  ValueError when none is found."""
+        return self._merkleblocks_of(digests, "merkleblocks_of")
+
     def update_async(self, trees_buf, indices_buf, leaves_buf, k, status_buf, stream=None):
         """Leaf indices[q] of tree trees[q] = leaves[q], q < k, and every ancestor rehashed, on the device: trees [k] uint32 and
         indices [k] uint64 strictly increasing as (tree, index) pairs with index < counts[tree], leaves [k, 8], status one
@@ -2237,6 +2460,13 @@ def forest_copy_status_text(status):
     if status & ~15:
         names.append("unknown bits")
     return "; ".join(names) if names else "ok"
+
+
+def merkleblocks_status_text(status):
+    """The bits of vkmr_hip_forest_merkleblocks_async's status word (info[0]), named."""
+    names = ["bit 0: a tree outside the forest or an index outside its tree", "bit 1: the entries are not strictly increasing",
+             "bit 2: more hashes or flag bytes than the buffers hold"]
+    return "; ".join(n for b, n in enumerate(names) if status >> b & 1)
 
 
 def forest_multiproof_status_text(status):
