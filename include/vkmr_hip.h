@@ -1216,6 +1216,107 @@ VKMR_API vkmr_status vkmr_hip_tree_merkleblock_async(int dev, vkmr_stream s, con
                                                      uint64_t hash_capacity, uint8_t* flags_dev, uint64_t flag_capacity, uint64_t* info_dev);
 
 /*
+ * SORTED TREES (the reference has no counterpart): "this digest is NO leaf", proved to a holder of the roots and the counts.  Every
+ * proof above says that something IS in a tree; the one "no", vkmr_hip_forest_find_async's not-found pair, is visible only to who
+ * holds every leaf.  A tree whose leaves are strictly increasing gives the provable one: x is absent exactly when two ADJACENT
+ * leaves straddle it, or it lies below leaf 0 or above the last leaf, and the inclusion proofs of those neighbours prove it under
+ * the root.  The rules, csrc/absence_plan.hpp:
+ *   order        a < b compares data[0], then data[1], .. data[7] as UNSIGNED 32-bit values: the byte order of the canonical digest
+ *   sorted       leaf[i-1] < leaf[i] for every 1 <= i < c; equal neighbours offend as well
+ *   lower bound  lo = 0, hi = c; while lo < hi: mid = lo + (hi - lo) / 2; leaf[mid] < x ? lo = mid + 1 : hi = mid.  The answer is
+ *                lo, on a sorted tree the number of leaves below x; fixed as a loop, so an unsorted tree still has one answer
+ * digests_dev, total, offsets_dev, ntrees as in vkmr_hip_reduce_forest_async, TRUSTED as vkmr_hip_forest_find_async trusts them; no
+ * leaf load leaves [offsets[0], min(offsets[ntrees], total)).  All four calls are stream-ordered on the caller's stream, allocate
+ * nothing, need no scratch and read no device data on the host; every index and offset is 64-bit.  Refused on the host
+ * (VKMR_ERR_INVALID), before any HIP call: a NULL pointer that is needed, a count above 2^58, a buffer off its grid (16 bytes for
+ * digests, 8 for uint64_t, 4 for uint32_t) and what each call names below.
+ *
+ * IS IT SORTED: one read-only pass over level 0, 32 bytes a leaf, no stored level needed.
+ *   first_bad_dev[t]  ntrees uint64_t: the lowest i in [1, c_t) with !(leaf[i-1] < leaf[i]), or UINT64_MAX.  A descent across the
+ *                     boundary of two trees is no offence.
+ *   info_dev          four uint64_t: [0] status (bit 0: the offsets decrease somewhere or end behind total; the rest is then
+ *                     not to be used), [1] trees not sorted, [2] those whose first offence is an EQUAL pair, [3] pairs compared
+ * Launches: two memsets, the scan (a lane per cell; none below two cells) and a lane per tree.  ntrees == 0 does nothing.  The
+ * one-tree twin takes the leaves as cells [0, count) of digests_dev; first_bad_dev is then one uint64_t; count == 0 is fine.
+ * This pass is what will test a sort of the leaves on the device; there is none yet.
+ */
+VKMR_API vkmr_status vkmr_hip_forest_sorted_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t total,
+                                                  const uint64_t* offsets_dev, uint32_t ntrees, uint64_t* first_bad_dev, uint64_t* info_dev);
+VKMR_API vkmr_status vkmr_hip_tree_sorted_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t count,
+                                                uint64_t* first_bad_dev, uint64_t* info_dev);
+/*
+ * LOWER BOUND: Q queries (trees_dev[q], queries_dev[q]) in DEVICE memory, one lane a query running the loop above:
+ *   indices_out_dev[q] = i, found_out_dev[q] = 1 when leaf i exists and equals the query, else 0
+ * and UINT64_MAX, 0 for a tree >= ntrees.  The tree need not be sorted for the call to answer; the answer then means what the
+ * loop makes of it.  On a sorted tree the number of leaves in [x, y) is the difference of two queries: range counts come free.
+ * No stored level is needed.  Q == 0 does nothing.
+ */
+VKMR_API vkmr_status vkmr_hip_forest_lower_bound_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t total,
+                                                       const uint64_t* offsets_dev, uint32_t ntrees, const uint32_t* trees_dev,
+                                                       const vkmr_digest* queries_dev, uint32_t Q, uint64_t* indices_out_dev,
+                                                       uint32_t* found_out_dev);
+VKMR_API vkmr_status vkmr_hip_tree_lower_bound_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t count,
+                                                     const vkmr_digest* queries_dev, uint32_t Q, uint64_t* indices_out_dev,
+                                                     uint32_t* found_out_dev);
+/*
+ * ABSENCE PROOFS out of a stored forest (digests_dev, forest_dev, total, offsets_dev, ntrees, max_count: those of the build,
+ * trusted as vkmr_hip_forest_proofs_async trusts them): the lower bound, then a gather.  No hash.  For query q, i its lower bound
+ * in tree t of c leaves and H(c) = max(1, ceil(log2 c)), 0 for c == 0:
+ *   indices_out_dev[q]         i
+ *   neighbours_out_dev[2q]     pred = leaf i - 1, a zero cell when i == 0;   [2q + 1]  succ = leaf i, a zero cell when i == c
+ *   heights_out_dev[q]         H(c)
+ *   main_out_dev[q * stride + l]  the plain inclusion proof (vkmr_hip_forest_proofs_async's cells) of the ANCHOR: leaf i when
+ *                              i < c, else leaf c - 1; zero for l >= H(c)
+ *   low_out_dev[q * stride + l]   only when 0 < i < c, with top = ctz(i): the sibling of leaf i - 1 at the levels l < top; zero
+ *                              from top up.  The bits of i - 1 below top are ones, so these are left siblings and all exist.
+ * This is the compact form: above top the two paths are one, and the node of leaf i - 1 at level top IS main[top].  A tree
+ * >= ntrees gets height 0, index UINT64_MAX and zero cells; a tree without a leaf index 0, height 0 and zero cells.  Every cell
+ * of every output is written.  Launches: a lane per query, then a lane per (query, level).  Refused: stride 0, above 63 or below
+ * the forest's H = max(1, ceil(log2 min(max_count, total))).  Q == 0 does nothing.  The one-tree twin reads a tree stored by
+ * vkmr_hip_reduce_tree_async with height == max(1, ceil(log2 count)) -- any other is refused --; its stride is that height, and it
+ * writes no heights.  A query that IS a leaf gets the same cells: succ is then the query, and the check below says "present".
+ */
+VKMR_API vkmr_status vkmr_hip_forest_absence_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* forest_dev,
+                                                   uint64_t total, const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count,
+                                                   const uint32_t* trees_dev, const vkmr_digest* queries_dev, uint32_t Q, uint32_t stride,
+                                                   uint64_t* indices_out_dev, vkmr_digest* neighbours_out_dev, vkmr_digest* main_out_dev,
+                                                   vkmr_digest* low_out_dev, uint32_t* heights_out_dev);
+VKMR_API vkmr_status vkmr_hip_tree_absence_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* tree_dev,
+                                                 uint64_t count, uint32_t height, const vkmr_digest* queries_dev, uint32_t Q,
+                                                 uint64_t* indices_out_dev, vkmr_digest* neighbours_out_dev, vkmr_digest* main_out_dev,
+                                                 vkmr_digest* low_out_dev);
+/*
+ * THE CHECK of Q absence proofs against roots_dev[ntrees] and counts_dev[ntrees], one lane a proof.  verdict_dev[q] is
+ *   0 not proven, 1 absent, proven, 2 present, proven
+ * by these steps, with t, i, pred, succ, the rows and height as above and c = counts_dev[t]:
+ *   1. 0 when t >= ntrees;  2. 0 when height != H(c) (or above stride, or c above 2^58);  3. 0 when i > c
+ *   4. c == 0: 1 exactly when the root is all zero
+ *   5. i < c and x == succ: succ folded through the main row (vkmr_host_cpu_fold_proof, index i); 2 when that is the root.  pred
+ *      and the low row are not looked at
+ *   6. else pred < x is required when i > 0, and x < succ when i < c
+ *   7. the anchor (succ when i < c, else pred, at index min(i, c - 1)) folded through the main row must be the root
+ *   8. when 0 < i < c: pred folded through low[0 .. top) as a right child at every level must equal main[top]
+ *   9. 1 when all of it holds
+ * Cells of the low row at or above top, and of either row at or above the height, are never read.  The cost is H + top node
+ * hashes a proof where two plain proofs take 2 H; over random gaps the mean top is about 1.  SOUNDNESS: the verdict binds under a
+ * root COMMITTED OVER A SORTED TREE -- two adjacent leaves of an unsorted tree may straddle a digest that is a leaf elsewhere.
+ * Who holds the leaves checks that with vkmr_hip_forest_sorted_async; a light client trusts whoever signed the root for it.
+ * Refused: stride 0 or above 63.  Q == 0 does nothing.  The one-tree twin checks against one root and one count, the same for
+ * every proof; its stride is `height`, refused unless height == H(count) (0 for count == 0, when the rows may be NULL).
+ * vkmr_host_cpu_forest_sorted, vkmr_host_cpu_forest_lower_bound, vkmr_host_cpu_forest_absence and vkmr_host_cpu_verify_absence
+ * (libvkmr_host.so) apply the same rules on the CPU, for a party without a GPU.
+ */
+VKMR_API vkmr_status vkmr_hip_verify_forest_absence_async(int dev, vkmr_stream s, const vkmr_digest* queries_dev, const uint32_t* trees_dev,
+                                                          const uint64_t* indices_dev, const vkmr_digest* neighbours_dev,
+                                                          const vkmr_digest* main_dev, const vkmr_digest* low_dev, const uint32_t* heights_dev,
+                                                          uint32_t Q, uint32_t stride, const vkmr_digest* roots_dev, const uint64_t* counts_dev,
+                                                          uint32_t ntrees, uint32_t* verdict_dev);
+VKMR_API vkmr_status vkmr_hip_verify_absence_async(int dev, vkmr_stream s, const vkmr_digest* queries_dev, const uint64_t* indices_dev,
+                                                   const vkmr_digest* neighbours_dev, const vkmr_digest* main_dev, const vkmr_digest* low_dev,
+                                                   uint32_t Q, uint32_t height, const vkmr_digest* root_dev, uint64_t count,
+                                                   uint32_t* verdict_dev);
+
+/*
  * COMBINE: duplicate-last Merkle root over n >= 1 slice roots given in slice order, always
  * at least one level -- the rule of CpuSha256D::Root that the reference applies to the slice
  * roots on the CPU (CpuSha256DforReductions, src/vkmr/Reductions.cpp:56-69, :703-712).  Here

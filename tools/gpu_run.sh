@@ -35,6 +35,9 @@
 #   merkleblocks [args]    tools/merkleblocks_timing.py: partial Merkle trees in BIP37 order out of a stored forest (2^15 trees of 2 048; 2^10, 2^16,
 #                          2^20 random entries, 2^16 filling whole trees) beside the multiproof gather, its downloads and the gather of a host reordering
 #                          (one JSON line)
+#   absence [args]         tools/absence_timing.py: sorted trees (2^26 sorted leaves as 2^15 trees of 2 048 and as one tree; Q = 2^10, 2^16, 2^20, half
+#                          present): the sorted pass beside torch's sum over as many bytes, the lower bound, the gather, and the verifier beside
+#                          vkmr_hip_verify_forest_proofs_async over 2 Q plain proofs (one JSON line)
 #   forest_repack [args]   tools/forest_repack_timing.py: the oldest trees of a stored forest dropped and the rest (or all) copied into an
 #                          empty forest, beside the stored build over the same leaves (one JSON line)
 #   cumask                 tools/cu_mask_probe.py: where CU-mask bits land, map/reduce on half the CUs with and without neighbours
@@ -226,6 +229,11 @@ proofs_at)
   timeout -k 10 500 python3 tools/proofs_at_timing.py "$@" --out $OUT/proofs_at_timing.json > /dev/null 2> $OUT/proofs_at_timing.err && echo "proofs_at_timing ok" &&
   cat $OUT/proofs_at_timing.json
   echo "proofs_at rc=$?"
+  ;;
+absence)
+  timeout -k 10 500 python3 tools/absence_timing.py "$@" --out $OUT/absence_timing.json > /dev/null 2> $OUT/absence_timing.err && echo "absence_timing ok" &&
+  cat $OUT/absence_timing.json
+  echo "absence rc=$?"
   ;;
 forest_repack)
   timeout -k 10 500 python3 tools/forest_repack_timing.py "$@" --out $OUT/forest_repack_timing.json > /dev/null 2> $OUT/forest_repack_timing.err && echo "forest_repack_timing ok" &&

@@ -186,7 +186,7 @@ def build_host(force=False):
     """Host-side C++ (g++): helper library, front end, tools."""
     os.makedirs(BIN, exist_ok=True)
     hdrs = _tree(HOST, (".hpp", ".h")) + [os.path.join(ROOT, "include", "vkmr_hip.h")] + [
-        os.path.join(CSRC, h) for h in ("merkle_math.hpp", "forest_plan.hpp", "tree_plan.hpp", "audit_plan.hpp", "frontier_plan.hpp", "consistency_plan.hpp", "proofs_at_plan.hpp", "merkleblock_plan.hpp")]
+        os.path.join(CSRC, h) for h in ("merkle_math.hpp", "forest_plan.hpp", "tree_plan.hpp", "audit_plan.hpp", "frontier_plan.hpp", "consistency_plan.hpp", "proofs_at_plan.hpp", "merkleblock_plan.hpp", "absence_plan.hpp")]
     cxx = os.environ.get("CXX", "g++")
     flags = ["-O2", "-std=c++17", "-Wall", "-pthread", "-I", os.path.join(ROOT, "include"), "-I", HOST]
     built = []

@@ -6,6 +6,7 @@
 #include <utility>
 #include <vector>
 
+#include "../absence_plan.hpp"
 #include "../audit_plan.hpp"   // forest_plan.hpp, tree_plan.hpp: where the stored levels lie
 #include "../consistency_plan.hpp"
 #include "../frontier_plan.hpp"
@@ -1123,6 +1124,135 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_merkleblock_extract(uin
         matched_hash_out[j] = e.leaves[j];
     }
     *nmatched_out = e.idx.size();
+    return 0;
+}
+
+// ---- sorted trees: order, lower bound, absence proofs (absence_plan.hpp; vkmr_hip_forest_sorted_async and its neighbours) for a
+// party without a GPU.  A forest is its leaves and offsets; one tree is a forest of one (offsets {0, count}).  Each returns -1 for
+// a missing pointer and 1 when the offsets decrease somewhere or end behind `total`; nothing is written then.
+
+static int absence_offsets_bad(const uint64_t* offsets, uint32_t ntrees, uint64_t total)
+{
+    for (uint32_t t = 0; t < ntrees; ++t)
+        if (offsets[t + 1] < offsets[t]) return 1;
+    return ntrees > 0 && offsets[ntrees] > total ? 1 : 0;
+}
+
+// first_bad[t] = the lowest i in [1, c_t) with !(leaf[i-1] < leaf[i]), or UINT64_MAX; info: status 0, trees not sorted, trees whose
+// first offence is an equal pair, pairs compared.
+__attribute__((visibility("default"))) int vkmr_host_cpu_forest_sorted(const vkmr_digest* digests, uint64_t total, const uint64_t* offsets,
+                                                                        uint32_t ntrees, uint64_t* first_bad, uint64_t* info)
+{
+    if (ntrees == 0) return 0;
+    if (!offsets || !first_bad || !info) return -1;
+    if (absence_offsets_bad(offsets, ntrees, total)) return 1;
+    if (!digests && offsets[ntrees] > offsets[0]) return -1;
+    info[0] = info[1] = info[2] = info[3] = 0;
+    for (uint32_t t = 0; t < ntrees; ++t) {
+        const vkmr_digest* leaf = digests + offsets[t];
+        const uint64_t c = offsets[t + 1] - offsets[t];
+        first_bad[t] = vkmr_absence::NONE;
+        if (c >= 2) info[3] += c - 1;
+        for (uint64_t i = 1; i < c; ++i) {
+            if (vkmr_absence::less(leaf[i - 1].data, leaf[i].data)) continue;
+            first_bad[t] = i;
+            ++info[1];
+            if (vkmr_absence::equal(leaf[i - 1].data, leaf[i].data)) ++info[2];
+            break;
+        }
+    }
+    return 0;
+}
+
+// indices[q] = the lower bound of queries[q] in tree trees[q] by the plan's loop, found[q] = 1 when the leaf there is the query;
+// UINT64_MAX and 0 for a tree >= ntrees.
+__attribute__((visibility("default"))) int vkmr_host_cpu_forest_lower_bound(const vkmr_digest* digests, uint64_t total, const uint64_t* offsets,
+                                                                             uint32_t ntrees, const uint32_t* trees, const vkmr_digest* queries,
+                                                                             uint32_t Q, uint64_t* indices, uint32_t* found)
+{
+    if (Q == 0) return 0;
+    if (!trees || !queries || !indices || !found || (ntrees > 0 && !offsets)) return -1;
+    if (absence_offsets_bad(offsets, ntrees, total)) return 1;
+    if (ntrees > 0 && !digests && offsets[ntrees] > offsets[0]) return -1;
+    for (uint32_t q = 0; q < Q; ++q) {
+        indices[q] = vkmr_absence::NONE;
+        found[q] = 0;
+        if (trees[q] >= ntrees) continue;
+        const vkmr_digest* leaf = digests + offsets[trees[q]];
+        const uint64_t c = offsets[trees[q] + 1] - offsets[trees[q]];
+        const uint64_t i = vkmr_absence::lower_bound(c, [&](uint64_t mid) { return vkmr_absence::less(leaf[mid].data, queries[q].data); });
+        indices[q] = i;
+        found[q] = i < c && vkmr_absence::equal(leaf[i].data, queries[q].data) ? 1u : 0u;
+    }
+    return 0;
+}
+
+// The absence proofs of vkmr_hip_forest_absence_async, with no stored forest: the levels of a tree are built from its leaves, once
+// per tree however many queries name it.  2, and nothing written, when `stride` is below the height of a tree that a query names.
+__attribute__((visibility("default"))) int vkmr_host_cpu_forest_absence(const vkmr_digest* digests, uint64_t total, const uint64_t* offsets,
+                                                                         uint32_t ntrees, const uint32_t* trees, const vkmr_digest* queries, uint32_t Q,
+                                                                         uint32_t stride, uint64_t* indices, vkmr_digest* neighbours,
+                                                                         vkmr_digest* main_row, vkmr_digest* low_row, uint32_t* heights)
+{
+    if (Q == 0) return 0;
+    if (!trees || !queries || !indices || !neighbours || !heights || (stride > 0 && (!main_row || !low_row)) || (ntrees > 0 && !offsets)) return -1;
+    if (absence_offsets_bad(offsets, ntrees, total)) return 1;
+    if (ntrees > 0 && !digests && offsets[ntrees] > offsets[0]) return -1;
+    std::vector<uint32_t> order;
+    for (uint32_t q = 0; q < Q; ++q) {
+        if (trees[q] >= ntrees) continue;
+        if (vkmr_absence::height(offsets[trees[q] + 1] - offsets[trees[q]]) > stride) return 2;
+        order.push_back(q);
+    }
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return trees[x] < trees[y]; });
+    for (uint32_t q = 0; q < Q; ++q) indices[q] = vkmr_absence::NONE;
+    std::memset(heights, 0, sizeof(uint32_t) * (size_t)Q);
+    std::memset(neighbours, 0, sizeof(vkmr_digest) * 2 * (size_t)Q);
+    if (stride > 0) {
+        std::memset(main_row, 0, sizeof(vkmr_digest) * (size_t)Q * stride);
+        std::memset(low_row, 0, sizeof(vkmr_digest) * (size_t)Q * stride);
+    }
+    std::vector<std::vector<vkmr_digest>> levels;
+    for (size_t n = 0; n < order.size(); ++n) {
+        const uint32_t q = order[n], t = trees[q];
+        const vkmr_digest* leaf = digests + offsets[t];
+        const uint64_t c = offsets[t + 1] - offsets[t];
+        const uint32_t h = vkmr_absence::height(c);
+        const uint64_t i = vkmr_absence::lower_bound(c, [&](uint64_t mid) { return vkmr_absence::less(leaf[mid].data, queries[q].data); });
+        indices[q] = i;
+        heights[q] = h;
+        if (c == 0) continue;
+        if (n == 0 || trees[order[n - 1]] != t) tree_levels(leaf, leaf + c, h, levels);
+        if (vkmr_absence::has_pred(i)) neighbours[2 * (size_t)q] = leaf[i - 1];
+        if (vkmr_absence::has_succ(i, c)) neighbours[2 * (size_t)q + 1] = leaf[i];
+        const uint64_t a = vkmr_absence::anchor(i, c);
+        for (uint32_t l = 0; l < h; ++l) {
+            main_row[(size_t)q * stride + l] = levels[l][vkmr_math::sibling(a >> l, levels[l].size())];
+            if (vkmr_absence::low_cell(i, c, l)) low_row[(size_t)q * stride + l] = levels[l][vkmr_math::sibling((i - 1) >> l, levels[l].size())];
+        }
+    }
+    return 0;
+}
+
+// verdict[q] of vkmr_hip_verify_forest_absence_async: the plan's verdict() over the CPU's node hash.
+__attribute__((visibility("default"))) int vkmr_host_cpu_verify_absence(const vkmr_digest* queries, const uint32_t* trees, const uint64_t* indices,
+                                                                         const vkmr_digest* neighbours, const vkmr_digest* main_row,
+                                                                         const vkmr_digest* low_row, const uint32_t* heights, uint32_t Q, uint32_t stride,
+                                                                         const vkmr_digest* roots, const uint64_t* counts, uint32_t ntrees,
+                                                                         uint32_t* verdict)
+{
+    if (Q == 0) return 0;
+    if (!queries || !trees || !indices || !neighbours || !heights || !verdict || (stride > 0 && (!main_row || !low_row)) ||
+        (ntrees > 0 && (!roots || !counts)) || stride > 63)
+        return -1;
+    for (uint32_t q = 0; q < Q; ++q) {
+        const uint32_t t = trees[q];
+        const bool known = t < ntrees;
+        verdict[q] = vkmr_absence::verdict(queries[q].data, t, ntrees, indices[q], neighbours[2 * (size_t)q].data, neighbours[2 * (size_t)q + 1].data,
+                                           stride ? main_row[(size_t)q * stride].data : nullptr, stride ? low_row[(size_t)q * stride].data : nullptr,
+                                           heights[q], stride, known ? roots[t].data : nullptr, known ? counts[t] : 0ull,
+                                           [](const uint32_t* a, const uint32_t* b, uint32_t* out) { vkmr::cpu_sha256d_pair(a, b, out); });
+    }
     return 0;
 }
 

@@ -36,6 +36,10 @@
 //                                              entries summed, placed by two prefix sums (entries, blocks), then one lane per
 //                                              (entry, level) copies at most three nodes and sets one flag; no hash, no walk
 //                                              (the closed form and the sizes: merkleblock_plan.hpp)
+//   absence_kernels.hpp  *_sorted_*_kernel, *_lower_bound_kernel, *_absence_*_kernel   sorted trees: one pass over level 0 for the first
+//                                              pair out of order per tree, the lower bound of a digest, the two neighbours and their
+//                                              compact pair of proofs gathered (no hash), and the verdict absent / present, one lane
+//                                              per proof through one hash_pair (rules: absence_plan.hpp)
 //   forest_tree_kernels.hpp  forest_proofs_kernel          proofs gathered from the stored forest, one lane per (query, level)
 //                            verify_forest_proofs_kernel   batch verification of proofs of unequal height, one lane per proof
 //                            forest_update_*_kernel        leaf updates of the stored forest: tree_update_*'s bodies, a tree per entry
@@ -68,6 +72,7 @@
 //   diff_plan.hpp       one step of a diff's descent, the bound on every step's frontier and the scratch layout
 //   audit_plan.hpp      the ballot words of an audit's levels, the nodes it checks and the scratch layout
 //   merkleblock_plan.hpp  what a BIP37 walk appends between two matched leaves, in closed form; the three size bounds, the scratch layout
+//   absence_plan.hpp    the order on digests, the lower bound's loop, the cells of an absence proof and the verdict of its check
 //
 // Host side: plain launches on the caller's stream, each through launch() and so each checked; every argument refusal
 // through refuse(__func__, why); no allocation, no sync inside the *_async entry points.
@@ -106,6 +111,7 @@ using vkmr_dev::Node;
 #include "consistency_kernels.hpp"
 #include "proofs_at_kernels.hpp"
 #include "merkleblock_kernels.hpp"
+#include "absence_kernels.hpp"
 
 // ============================================================================
 // C ABI
@@ -1499,6 +1505,156 @@ vkmr_status vkmr_hip_forest_proofs_at_async(int dev, vkmr_stream s, const vkmr_d
     return launch(proofs_at_gather_kernel, grid_of((uint64_t)k * stride), dim3(256), S(s), nodes(digests_dev), nodes(forest_dev), lv, offsets_dev,
                   nodes(roots_dev), epoch_trees_dev, epoch_counts_dev, E, epochs_dev, indices_dev, k, stride, nodes(edges_out_dev), nodes(siblings_dev),
                   heights_dev, status_dev);
+}
+
+// ---- sorted trees: order, lower bound, absence proofs (absence_kernels.hpp, absence_plan.hpp) -----------------------------------
+
+static inline bool off_grid(const void* p, uintptr_t grid) { return (reinterpret_cast<uintptr_t>(p) & (grid - 1u)) != 0; }
+
+// Both sortedness passes, on the caller's stream: first_bad set to "none", the counters zeroed, the scan (no launch below two
+// cells), the finish.  offsets_dev null: one tree over [0, cells).
+static vkmr_status sorted_launch(const char* who, int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t cells, const uint64_t* offsets_dev,
+                                 uint32_t ntrees, uint64_t* first_bad_dev, uint64_t* info_dev)
+{
+    if (cells > (1ull << 58)) return refuse(who, "too many leaves");
+    if (off_grid(digests_dev, 16) || off_grid(first_bad_dev, 8) || off_grid(info_dev, 8) || off_grid(offsets_dev, 8)) return refuse(who, "misaligned buffer");
+    if (grid_too_large(groups_of(cells)) || grid_too_large(groups_of(ntrees))) return refuse(who, "too many leaves for one call");
+    unsigned long long* first_bad = reinterpret_cast<unsigned long long*>(first_bad_dev);
+    unsigned long long* info = reinterpret_cast<unsigned long long*>(info_dev);
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_TRY(hipMemsetAsync(first_bad_dev, 0xFF, sizeof(uint64_t) * (size_t)ntrees, S(s)));
+    VKMR_TRY(hipMemsetAsync(info_dev, 0, 4 * sizeof(uint64_t), S(s)));
+    if (cells >= 2) {
+        VKMR_CHECK(offsets_dev ? launch(forest_sorted_scan_kernel, grid_of(cells - 1), dim3(256), S(s), nodes(digests_dev), offsets_dev, ntrees, cells, first_bad)
+                               : launch(tree_sorted_scan_kernel, grid_of(cells - 1), dim3(256), S(s), nodes(digests_dev), cells, first_bad));
+    }
+    if (offsets_dev) return launch(forest_sorted_finish_kernel, grid_of(ntrees), dim3(256), S(s), nodes(digests_dev), offsets_dev, ntrees, cells, first_bad, info);
+    return launch(tree_sorted_finish_kernel, dim3(1), dim3(64), S(s), nodes(digests_dev), cells, first_bad, info);
+}
+
+vkmr_status vkmr_hip_forest_sorted_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t total, const uint64_t* offsets_dev,
+                                         uint32_t ntrees, uint64_t* first_bad_dev, uint64_t* info_dev)
+{
+    if (ntrees == 0) return VKMR_OK;
+    if ((!digests_dev && total > 0) || !offsets_dev || !first_bad_dev || !info_dev) return refuse(__func__, "null pointer");
+    return sorted_launch(__func__, dev, s, digests_dev, total, offsets_dev, ntrees, first_bad_dev, info_dev);
+}
+
+vkmr_status vkmr_hip_tree_sorted_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t count, uint64_t* first_bad_dev,
+                                       uint64_t* info_dev)
+{
+    if ((!digests_dev && count > 0) || !first_bad_dev || !info_dev) return refuse(__func__, "null pointer");
+    return sorted_launch(__func__, dev, s, digests_dev, count, nullptr, 1, first_bad_dev, info_dev);
+}
+
+vkmr_status vkmr_hip_forest_lower_bound_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t total, const uint64_t* offsets_dev,
+                                              uint32_t ntrees, const uint32_t* trees_dev, const vkmr_digest* queries_dev, uint32_t Q,
+                                              uint64_t* indices_out_dev, uint32_t* found_out_dev)
+{
+    if (Q == 0) return VKMR_OK;
+    if (!trees_dev || !queries_dev || !indices_out_dev || !found_out_dev || (ntrees > 0 && !offsets_dev) || (ntrees > 0 && total > 0 && !digests_dev))
+        return refuse(__func__, "null pointer");
+    if (total > (1ull << 58)) return refuse(__func__, "too many leaves");
+    if (off_grid(digests_dev, 16) || off_grid(queries_dev, 16) || off_grid(offsets_dev, 8) || off_grid(indices_out_dev, 8) || off_grid(trees_dev, 4) ||
+        off_grid(found_out_dev, 4))
+        return refuse(__func__, "misaligned buffer");
+    if (grid_too_large(groups_of(Q))) return refuse(__func__, "too many queries in one call");
+    VKMR_TRY(hipSetDevice(dev));
+    return launch(forest_lower_bound_kernel, grid_of(Q), dim3(256), S(s), nodes(digests_dev), offsets_dev, ntrees, total, trees_dev, nodes(queries_dev), Q,
+                  indices_out_dev, found_out_dev);
+}
+
+vkmr_status vkmr_hip_tree_lower_bound_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t count, const vkmr_digest* queries_dev,
+                                            uint32_t Q, uint64_t* indices_out_dev, uint32_t* found_out_dev)
+{
+    if (Q == 0) return VKMR_OK;
+    if (!queries_dev || !indices_out_dev || !found_out_dev || (count > 0 && !digests_dev)) return refuse(__func__, "null pointer");
+    if (count > (1ull << 58)) return refuse(__func__, "too many leaves");
+    if (off_grid(digests_dev, 16) || off_grid(queries_dev, 16) || off_grid(indices_out_dev, 8) || off_grid(found_out_dev, 4))
+        return refuse(__func__, "misaligned buffer");
+    if (grid_too_large(groups_of(Q))) return refuse(__func__, "too many queries in one call");
+    VKMR_TRY(hipSetDevice(dev));
+    return launch(tree_lower_bound_kernel, grid_of(Q), dim3(256), S(s), nodes(digests_dev), count, nodes(queries_dev), Q, indices_out_dev, found_out_dev);
+}
+
+// What the two gathers and the two checks refuse of their proof buffers alike: a missing one, one off its grid, too many cells.
+static vkmr_status absence_buffers_check(const char* who, const void* queries, const void* indices, const void* neighbours, const void* main_row,
+                                         const void* low_row, uint32_t Q, uint32_t stride)
+{
+    if (!queries || !indices || !neighbours || (stride > 0 && (!main_row || !low_row))) return refuse(who, "null pointer");
+    if (off_grid(queries, 16) || off_grid(neighbours, 16) || off_grid(main_row, 16) || off_grid(low_row, 16) || off_grid(indices, 8))
+        return refuse(who, "misaligned buffer");
+    if (grid_too_large(groups_of((uint64_t)Q * (stride ? stride : 1u)))) return refuse(who, "too many proofs in one call");
+    return VKMR_OK;
+}
+
+vkmr_status vkmr_hip_forest_absence_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* forest_dev, uint64_t total,
+                                          const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count, const uint32_t* trees_dev,
+                                          const vkmr_digest* queries_dev, uint32_t Q, uint32_t stride, uint64_t* indices_out_dev,
+                                          vkmr_digest* neighbours_out_dev, vkmr_digest* main_out_dev, vkmr_digest* low_out_dev, uint32_t* heights_out_dev)
+{
+    if (Q == 0) return VKMR_OK;
+    if ((!digests_dev && total > 0) || !forest_dev || !offsets_dev || !trees_dev || !heights_out_dev) return refuse(__func__, "null pointer");
+    if (stride == 0 || stride > 63) return refuse(__func__, "stride must be 1..63");
+    VKMR_CHECK(absence_buffers_check(__func__, queries_dev, indices_out_dev, neighbours_out_dev, main_out_dev, low_out_dev, Q, stride));
+    VKMR_CHECK(forest_args_check(__func__, total, ntrees, max_count, Q, nullptr, nullptr));
+    if (off_grid(digests_dev, 16) || off_grid(forest_dev, 16) || off_grid(offsets_dev, 8) || off_grid(trees_dev, 4) || off_grid(heights_out_dev, 4))
+        return refuse(__func__, "misaligned buffer");
+    const uint32_t H = vkmr_forest::launches(total, max_count);   // <= 58
+    if (stride < H) return refuse(__func__, "stride is below the forest's levels");
+    const ForestLevels lv = forest_levels(total, ntrees, H);
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_CHECK(launch(forest_absence_entries_kernel, grid_of(Q), dim3(256), S(s), nodes(digests_dev), offsets_dev, ntrees, total, trees_dev,
+                      nodes(queries_dev), Q, indices_out_dev, nodes(neighbours_out_dev), heights_out_dev));
+    return launch(forest_absence_rows_kernel, grid_of((uint64_t)Q * stride), dim3(256), S(s), nodes(digests_dev), nodes(forest_dev), lv, offsets_dev, ntrees,
+                  total, trees_dev, indices_out_dev, Q, stride, nodes(main_out_dev), nodes(low_out_dev));
+}
+
+vkmr_status vkmr_hip_tree_absence_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* tree_dev, uint64_t count,
+                                        uint32_t height, const vkmr_digest* queries_dev, uint32_t Q, uint64_t* indices_out_dev,
+                                        vkmr_digest* neighbours_out_dev, vkmr_digest* main_out_dev, vkmr_digest* low_out_dev)
+{
+    if (Q == 0) return VKMR_OK;
+    if (!digests_dev || !tree_dev) return refuse(__func__, "null pointer");
+    if (count == 0 || count > (1ull << 58) || height != vkmr_math::height(count)) return refuse(__func__, "height must be max(1, ceil(log2 count))");
+    VKMR_CHECK(absence_buffers_check(__func__, queries_dev, indices_out_dev, neighbours_out_dev, main_out_dev, low_out_dev, Q, height));
+    if (off_grid(digests_dev, 16) || off_grid(tree_dev, 16)) return refuse(__func__, "misaligned buffer");
+    const TreeLevels lv = tree_levels(count, height);
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_CHECK(launch(tree_absence_entries_kernel, grid_of(Q), dim3(256), S(s), nodes(digests_dev), count, nodes(queries_dev), Q, indices_out_dev,
+                      nodes(neighbours_out_dev)));
+    return launch(tree_absence_rows_kernel, grid_of((uint64_t)Q * height), dim3(256), S(s), nodes(digests_dev), nodes(tree_dev), lv, count, indices_out_dev, Q,
+                  height, nodes(main_out_dev), nodes(low_out_dev));
+}
+
+vkmr_status vkmr_hip_verify_forest_absence_async(int dev, vkmr_stream s, const vkmr_digest* queries_dev, const uint32_t* trees_dev,
+                                                 const uint64_t* indices_dev, const vkmr_digest* neighbours_dev, const vkmr_digest* main_dev,
+                                                 const vkmr_digest* low_dev, const uint32_t* heights_dev, uint32_t Q, uint32_t stride,
+                                                 const vkmr_digest* roots_dev, const uint64_t* counts_dev, uint32_t ntrees, uint32_t* verdict_dev)
+{
+    if (Q == 0) return VKMR_OK;
+    if (!trees_dev || !heights_dev || !verdict_dev || (ntrees > 0 && (!roots_dev || !counts_dev))) return refuse(__func__, "null pointer");
+    if (stride == 0 || stride > 63) return refuse(__func__, "stride must be 1..63");
+    VKMR_CHECK(absence_buffers_check(__func__, queries_dev, indices_dev, neighbours_dev, main_dev, low_dev, Q, stride));
+    if (off_grid(roots_dev, 16) || off_grid(counts_dev, 8) || off_grid(trees_dev, 4) || off_grid(heights_dev, 4) || off_grid(verdict_dev, 4))
+        return refuse(__func__, "misaligned buffer");
+    VKMR_TRY(hipSetDevice(dev));
+    return launch(forest_absence_fold_kernel, grid_of(Q), dim3(256), S(s), nodes(queries_dev), trees_dev, indices_dev, nodes(neighbours_dev), nodes(main_dev),
+                  nodes(low_dev), heights_dev, Q, stride, nodes(roots_dev), counts_dev, ntrees, verdict_dev);
+}
+
+vkmr_status vkmr_hip_verify_absence_async(int dev, vkmr_stream s, const vkmr_digest* queries_dev, const uint64_t* indices_dev,
+                                          const vkmr_digest* neighbours_dev, const vkmr_digest* main_dev, const vkmr_digest* low_dev, uint32_t Q,
+                                          uint32_t height, const vkmr_digest* root_dev, uint64_t count, uint32_t* verdict_dev)
+{
+    if (Q == 0) return VKMR_OK;
+    if (!root_dev || !verdict_dev) return refuse(__func__, "null pointer");
+    if (height > 63 || height != vkmr_absence::height(count)) return refuse(__func__, "height must be max(1, ceil(log2 count)), 0 for no leaf");
+    VKMR_CHECK(absence_buffers_check(__func__, queries_dev, indices_dev, neighbours_dev, main_dev, low_dev, Q, height));
+    if (off_grid(root_dev, 16) || off_grid(verdict_dev, 4)) return refuse(__func__, "misaligned buffer");
+    VKMR_TRY(hipSetDevice(dev));
+    return launch(tree_absence_fold_kernel, grid_of(Q), dim3(256), S(s), nodes(queries_dev), indices_dev, nodes(neighbours_dev), nodes(main_dev),
+                  nodes(low_dev), Q, height, nodes(root_dev), count, verdict_dev);
 }
 
 // ---- partial Merkle trees in BIP37 order (merkleblock_kernels.hpp, merkleblock_plan.hpp) ----------------------------------------

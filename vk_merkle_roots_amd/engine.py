@@ -815,6 +815,57 @@ class HipDevice:
     def merkleblocks_scratch_bytes(self, k, stride):
         return self.lib.vkmr_hip_forest_merkleblocks_scratch_bytes(k, stride)
 
+    # -- sorted trees: is a tree strictly increasing, where would a digest stand, the proof that it is no leaf ----------------
+    def forest_sorted_enqueue(self, digests_buf, total, offsets_buf, ntrees, first_bad_buf, info_buf, stream=None):
+        """first_bad_buf[t] (ntrees uint64) = the lowest index of tree t whose leaf is not above the one in front, or 2^64 - 1;
+        info_buf: 4 uint64 (status, trees not sorted, of those the ones whose first offence is an equal pair, pairs compared).
+        One pass over level 0; all in device memory.  include/vkmr_hip.h."""
+        self._call("vkmr_hip_forest_sorted_async", digests_buf, total, offsets_buf, ntrees, first_bad_buf, info_buf, stream=stream)
+
+    def tree_sorted_enqueue(self, digests_buf, count, first_bad_buf, info_buf, stream=None):
+        """forest_sorted_enqueue for ONE tree over digests_buf[0 .. count): first_bad_buf is one uint64."""
+        self._call("vkmr_hip_tree_sorted_async", digests_buf, count, first_bad_buf, info_buf, stream=stream)
+
+    def forest_lower_bound_enqueue(self, digests_buf, total, offsets_buf, ntrees, trees_buf, queries_buf, Q, indices_buf, found_buf, stream=None):
+        """indices_buf[q] (uint64) = the lower bound of the digest queries_buf[q] among the leaves of tree trees_buf[q], found_buf[q]
+        (uint32) = 1 when the leaf there is the digest; 2^64 - 1 and 0 for a tree outside the forest.  All in device memory."""
+        self._call("vkmr_hip_forest_lower_bound_async", digests_buf, total, offsets_buf, ntrees, trees_buf, queries_buf, Q, indices_buf, found_buf,
+                   stream=stream)
+
+    def tree_lower_bound_enqueue(self, digests_buf, count, queries_buf, Q, indices_buf, found_buf, stream=None):
+        """forest_lower_bound_enqueue for ONE tree over digests_buf[0 .. count)."""
+        self._call("vkmr_hip_tree_lower_bound_async", digests_buf, count, queries_buf, Q, indices_buf, found_buf, stream=stream)
+
+    def forest_absence_enqueue(self, digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, trees_buf, queries_buf, Q, stride, indices_buf,
+                               neighbours_buf, main_buf, low_buf, heights_buf, stream=None):
+        """The absence proofs of Q queries (trees_buf uint32, queries_buf digests) out of a stored forest (total, ntrees,
+        max_count: the build's): Q uint64 indices, 2 Q neighbour cells (pred, succ), two rows of Q x stride cells and Q uint32
+        heights, every cell written.  No hash.  All in device memory.  include/vkmr_hip.h."""
+        self._call("vkmr_hip_forest_absence_async", digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, trees_buf, queries_buf, Q, stride,
+                   indices_buf, neighbours_buf, main_buf, low_buf, heights_buf, stream=stream)
+
+    def tree_absence_enqueue(self, digests_buf, tree_buf, count, height, queries_buf, Q, indices_buf, neighbours_buf, main_buf, low_buf, stream=None):
+        """forest_absence_enqueue for ONE stored tree of height max(1, ceil(log2 count)): rows of Q x height cells, no heights."""
+        self._call("vkmr_hip_tree_absence_async", digests_buf, tree_buf, count, height, queries_buf, Q, indices_buf, neighbours_buf, main_buf, low_buf,
+                   stream=stream)
+
+    def verify_forest_absence_enqueue(self, queries_buf, trees_buf, indices_buf, neighbours_buf, main_buf, low_buf, heights_buf, Q, stride, roots_buf,
+                                      counts_buf, ntrees, verdict_buf, stream=None):
+        """verdict_buf[q] (uint32) = 0 not proven, 1 the digest queries_buf[q] is no leaf of tree trees_buf[q], 2 it is one: proof
+        q checked against roots_buf[ntrees] and counts_buf[ntrees] (uint64).  All in device memory.  include/vkmr_hip.h."""
+        self._call("vkmr_hip_verify_forest_absence_async", queries_buf, trees_buf, indices_buf, neighbours_buf, main_buf, low_buf, heights_buf, Q, stride,
+                   roots_buf, counts_buf, ntrees, verdict_buf, stream=stream)
+
+    def verify_absence_enqueue(self, queries_buf, indices_buf, neighbours_buf, main_buf, low_buf, Q, height, root_buf, count, verdict_buf, stream=None):
+        """verify_forest_absence_enqueue against ONE root (root_buf, one cell) and one count: rows of Q x height cells."""
+        self._call("vkmr_hip_verify_absence_async", queries_buf, indices_buf, neighbours_buf, main_buf, low_buf, Q, height, root_buf, count, verdict_buf,
+                   stream=stream)
+
+    def verify_forest_absence(self, queries, trees, indices, pred, succ, main, low, heights, roots, counts):
+        """uint32 [Q] verdicts (0 not proven, 1 absent, 2 present) of Q absence proofs given as host arrays -- the fields of an
+        AbsenceProofs -- against roots [ntrees, 8] and counts [ntrees]; verified on the device."""
+        return AbsenceProofs(trees, queries, indices, pred, succ, main, low, heights).verify(self, roots, counts)
+
     def reduce_scratch(self, count, levels_variant=False):
         fn = self.lib.vkmr_hip_reduce_levels_scratch_bytes if levels_variant else self.lib.vkmr_hip_reduce_scratch_bytes
         return self.alloc(fn(count))
@@ -1074,6 +1125,7 @@ class _Stored:
       _Proof           the class of its multiproofs: _Proof(*entry columns, *proof columns, nodes, level counts, stride)
       ntrees, cells, stride            its trees, its leaf cells, the cells of one proof
       _multiproof_sizes, _status_text, _same_shape, _update_order
+      _lower_bound_of, _absence_of     its lower_bound_async / absence_async over host trees and a device buffer of digests
     the thin *_async methods, and the public methods whose signature names the entry columns."""
 
     @staticmethod
@@ -1118,6 +1170,60 @@ class _Stored:
         with self.dev.scope() as tmp:
             d_entries = self._find(tmp, q, k)
             return (*self._gather_proofs(tmp, d_entries, k), *self._read(d_entries, self._columns, k))
+
+    def first_unsorted(self):
+        """uint64 [ntrees]: per tree the lowest index whose leaf is not above the leaf in front of it (an equal one offends as
+        well), NOT_FOUND (2^64 - 1) for a tree that is strictly increasing -- the order being that of the digests' bytes.  One
+        pass over the leaves on the device; a descent from one tree into the next is no offence."""
+        return self._sorted()[0]
+
+    def is_sorted(self):
+        """Every tree strictly increasing: what an absence proof's verdict rests on."""
+        return int(self._sorted()[1][1]) == 0
+
+    def _sorted(self):
+        """(first_bad uint64 [ntrees], info uint64 [4]) of sorted_async; RuntimeError when the device found the offsets broken."""
+        if self.ntrees == 0:
+            return np.zeros(0, np.uint64), np.zeros(4, np.uint64)
+        with self.dev.scope() as tmp:
+            d_bad, d_info = tmp.alloc(8 * self.ntrees), tmp.alloc(32)
+            self.sorted_async(d_bad, d_info)
+            bad, info = self.dev.download(d_bad, 8 * self.ntrees, dtype=np.uint64), self.dev.download(d_info, 32, dtype=np.uint64)
+        if int(info[0]):
+            raise RuntimeError(f"{type(self).__name__}.first_unsorted: the offsets are not a forest's (status {int(info[0])})")
+        return bad, info
+
+    def _queries(self, trees, digests, what):
+        """(trees uint32 [Q], digests uint32 [Q, 8]) of a call that names a tree per digest."""
+        q = _host(digests, np.uint32, -1, 8)
+        t = np.zeros(q.shape[0], np.uint32) if trees is None else _host(trees, np.uint32, -1)
+        if t.shape[0] != q.shape[0]:
+            raise ValueError(f"{what}: one tree per digest")
+        return t, q
+
+    def _lower_bound(self, trees, digests):
+        t, q = self._queries(trees, digests, "lower_bound")
+        Q = int(q.shape[0])
+        if Q == 0:
+            return np.zeros(0, np.uint64), np.zeros(0, bool)
+        with self.dev.scope() as tmp:
+            d_idx, d_found = tmp.alloc(8 * Q), tmp.alloc(4 * Q)
+            self._lower_bound_of(tmp, t, tmp.upload(q), Q, d_idx, d_found)
+            return self.dev.download(d_idx, 8 * Q, dtype=np.uint64), self.dev.download(d_found, 4 * Q) == 1
+
+    def _absence(self, trees, digests, stride):
+        t, q = self._queries(trees, digests, "absence")
+        Q = int(q.shape[0])
+        if Q == 0:
+            return AbsenceProofs(t, q, np.zeros(0, np.uint64), *(np.zeros((0, 8), np.uint32),) * 2, *(np.zeros((0, stride, 8), np.uint32),) * 2,
+                                 np.zeros(0, np.uint32))
+        with self.dev.scope() as tmp:
+            d_idx, d_nb, d_main, d_low = tmp.alloc(8 * Q), tmp.alloc(64 * Q), tmp.alloc(32 * Q * stride), tmp.alloc(32 * Q * stride)
+            heights = self._absence_of(tmp, t, tmp.upload(q), Q, stride, d_idx, d_nb, d_main, d_low)
+            nb = self.dev.download(d_nb, 64 * Q).reshape(Q, 2, 8)
+            return AbsenceProofs(t, q, self.dev.download(d_idx, 8 * Q, dtype=np.uint64), nb[:, 0], nb[:, 1],
+                                 self.dev.download(d_main, 32 * Q * stride).reshape(Q, stride, 8),
+                                 self.dev.download(d_low, 32 * Q * stride).reshape(Q, stride, 8), heights)
 
     def _no_proofs(self, k):
         """What k proofs without a cell are: (siblings [k, stride, 8], *the proof columns), all zero."""
@@ -1441,6 +1547,46 @@ class MerkleTree(_Stored):
         """indices_buf[q] = the lowest index whose leaf equals the digest queries_buf[q], or 2^64 - 1 (NOT_FOUND): device
         memory throughout, scratch_buf of dev.find_scratch_bytes(k) bytes; ordered on `stream` behind earlier updates."""
         self.dev.tree_find_async(self.digests, self.count, queries_buf, k, scratch_buf, indices_buf, stream=stream)
+
+    def sorted_async(self, first_bad_buf, info_buf, stream=None):
+        """first_bad_buf (one uint64) = the lowest index whose leaf is not above the one in front, or 2^64 - 1; info_buf: 4 uint64.
+        Device memory; ordered on `stream` behind earlier updates.  HipDevice.tree_sorted_enqueue."""
+        self.dev.tree_sorted_enqueue(self.digests, self.count, first_bad_buf, info_buf, stream=stream)
+
+    def lower_bound_async(self, queries_buf, Q, indices_buf, found_buf, stream=None):
+        """indices_buf[q] = the lower bound of the digest queries_buf[q] among the leaves, found_buf[q] = 1 when it is a leaf."""
+        self.dev.tree_lower_bound_enqueue(self.digests, self.count, queries_buf, Q, indices_buf, found_buf, stream=stream)
+
+    def lower_bound(self, digests):
+        """(indices uint64 [Q], found bool [Q]): where each digest ([Q, 8], a host array) would stand among the leaves -- on a
+        sorted tree the number of leaves below it -- and whether it is the leaf there.  The number of leaves in [x, y) is the
+        difference of two answers."""
+        return self._lower_bound(None, digests)
+
+    def _lower_bound_of(self, tmp, trees, d_queries, Q, d_idx, d_found):
+        self.lower_bound_async(d_queries, Q, d_idx, d_found)
+
+    def _absence_of(self, tmp, trees, d_queries, Q, stride, d_idx, d_nb, d_main, d_low):
+        """absence_async enqueued; the heights of the Q proofs: the tree's, it writes none."""
+        self.absence_async(d_queries, Q, d_idx, d_nb, d_main, d_low)
+        return np.full(Q, stride, np.uint32)
+
+    def _absence_height(self):
+        if self.height != tree_height(self.count):
+            raise ValueError(f"absence: a tree of {self.count} leaves stored with height {self.height}; the proofs need height {tree_height(self.count)}")
+
+    def absence_async(self, queries_buf, Q, indices_buf, neighbours_buf, main_buf, low_buf, stream=None):
+        """The absence proofs of the Q digests in queries_buf: Q indices, 2 Q neighbour cells and two rows of Q x height cells, all
+        in device memory.  HipDevice.tree_absence_enqueue; a tree stored with height max(1, ceil(log2 count)) only."""
+        self._absence_height()
+        self.dev.tree_absence_enqueue(self.digests, self.tree, self.count, self.height, queries_buf, Q, indices_buf, neighbours_buf, main_buf, low_buf,
+                                      stream=stream)
+
+    def absence(self, digests):
+        """The AbsenceProofs (tree 0 throughout) that show, to a holder of the root and the count, that each digest ([Q, 8]) is no
+        leaf of this tree -- or that it is one.  The verdict binds when the tree is sorted: is_sorted()."""
+        self._absence_height()
+        return self._absence(None, digests, self.height)
 
     def multiproof_async(self, indices_buf, k, scratch_buf, nodes_buf, nodes_capacity, info_buf, stream=None):
         """ONE proof for the k leaves whose strictly increasing indices are in device memory, written to nodes_buf
@@ -2044,6 +2190,45 @@ class MerkleForest(_Stored):
         self.dev.forest_find_async(self.digests, self.total, self.offsets, self.ntrees, queries_buf, k, scratch_buf, trees_buf, indices_buf,
                                    stream=stream)
 
+    def sorted_async(self, first_bad_buf, info_buf, stream=None):
+        """first_bad_buf[t] (ntrees uint64) = the lowest index of tree t whose leaf is not above the one in front, or 2^64 - 1;
+        info_buf: 4 uint64.  Device memory; ordered on `stream` behind earlier updates.  HipDevice.forest_sorted_enqueue."""
+        self.dev.forest_sorted_enqueue(self.digests, self.total, self.offsets, self.ntrees, first_bad_buf, info_buf, stream=stream)
+
+    def lower_bound_async(self, trees_buf, queries_buf, Q, indices_buf, found_buf, stream=None):
+        """indices_buf[q] = the lower bound of the digest queries_buf[q] among the leaves of tree trees_buf[q], found_buf[q] = 1
+        when it is a leaf of it; 2^64 - 1 and 0 for a tree outside the forest."""
+        self.dev.forest_lower_bound_enqueue(self.digests, self.total, self.offsets, self.ntrees, trees_buf, queries_buf, Q, indices_buf, found_buf,
+                                            stream=stream)
+
+    def lower_bound(self, trees, digests):
+        """(indices uint64 [Q], found bool [Q]): where digest q ([Q, 8], host arrays) would stand among the leaves of tree
+        trees[q] -- on a sorted tree the number of leaves below it -- and whether it is the leaf there; NOT_FOUND and False for
+        a tree outside the forest.  The number of leaves in [x, y) is the difference of two answers."""
+        return self._lower_bound(trees, digests)
+
+    def absence_async(self, trees_buf, queries_buf, Q, stride, indices_buf, neighbours_buf, main_buf, low_buf, heights_buf, stream=None):
+        """The absence proofs of Q (tree, digest) queries in device memory: Q indices, 2 Q neighbour cells, two rows of Q x stride
+        cells and Q heights.  HipDevice.forest_absence_enqueue."""
+        self.dev.forest_absence_enqueue(self.digests, self.forest, self.total, self.offsets, self.ntrees, self.max_count, trees_buf, queries_buf, Q,
+                                        stride, indices_buf, neighbours_buf, main_buf, low_buf, heights_buf, stream=stream)
+
+    def _lower_bound_of(self, tmp, trees, d_queries, Q, d_idx, d_found):
+        self.lower_bound_async(tmp.upload(trees), d_queries, Q, d_idx, d_found)
+
+    def _absence_of(self, tmp, trees, d_queries, Q, stride, d_idx, d_nb, d_main, d_low):
+        """absence_async enqueued; the heights it wrote, read back."""
+        d_h = tmp.alloc(4 * Q)
+        self.absence_async(tmp.upload(trees), d_queries, Q, stride, d_idx, d_nb, d_main, d_low, d_h)
+        return self.dev.download(d_h, 4 * Q)
+
+    def absence(self, trees, digests, stride=None):
+        """The AbsenceProofs that show, to a holder of the roots and the counts, that digest q ([Q, 8]) is no leaf of tree
+        trees[q] -- or that it is one: the two leaves that straddle it and their proofs in the compact form, read out of the
+        stored levels (no hash).  stride: cells per row, by default the forest's.  The verdict binds when the trees are
+        sorted: is_sorted()."""
+        return self._absence(trees, digests, self.levels if stride is None else int(stride))
+
     def multiproof_async(self, trees_buf, indices_buf, k, scratch_buf, nodes_buf, nodes_capacity, heights_buf, info_buf, stream=None):
         """ONE proof for the k (tree, index) entries in device memory (strictly increasing pairs), written to nodes_buf
         (nodes_capacity cells) and heights_buf [k]; info_buf: 2 + levels uint64 (status, M, the per-level counts).
@@ -2406,6 +2591,65 @@ class ConsistencyProof:
             dev.verify_consistency_enqueue(tmp.upload(self.old_counts), tmp.upload(self.new_counts), tmp.upload(self.peaks), tmp.upload(self.rights),
                                            self.stride, Q, tmp.upload(_host(old_roots, np.uint32, Q, 8)), tmp.upload(_host(new_roots, np.uint32, Q, 8)), d_ok)
             return dev.download(d_ok, 4 * Q)
+
+
+class AbsenceProofs:
+    """Q proofs that a digest is no leaf of a sorted tree (include/vkmr_hip.h, SORTED TREES): `queries[q]` ([Q, 8]) would stand at
+    index `indices[q]` of tree `trees[q]`, between `pred[q]` and `succ[q]` (zero cells where there is none); `main` ([Q, stride, 8])
+    is the inclusion proof of the anchor -- succ, or the last leaf behind which the digest lies -- and `low` the siblings of pred
+    below the level at which the two paths meet.  `heights[q]` is the tree's.  Host arrays; MerkleForest.absence gathers one, a
+    holder of the roots and the counts verifies it."""
+
+    def __init__(self, trees, queries, indices, pred, succ, main, low, heights):
+        self.trees, self.heights = (np.array(x, dtype=np.uint32).reshape(-1) for x in (trees, heights))
+        self.indices = np.array(indices, dtype=np.uint64).reshape(-1)
+        Q = int(self.trees.shape[0])
+        self.queries, self.pred, self.succ = (np.array(x, dtype=np.uint32).reshape(-1, 8) for x in (queries, pred, succ))
+        self.main, self.low = (np.array(x, dtype=np.uint32) for x in (main, low))
+        if (any(a.shape[0] != Q for a in (self.heights, self.indices, self.queries, self.pred, self.succ)) or self.main.ndim != 3
+                or self.main.shape != self.low.shape or self.main.shape[0] != Q or self.main.shape[2] != 8 or not 1 <= self.stride <= 63):
+            raise ValueError("AbsenceProofs: one tree, digest, index, pred, succ and height per query; main and low [Q, stride, 8] with stride in 1..63")
+
+    Q = property(lambda self: int(self.trees.shape[0]))
+    stride = property(lambda self: int(self.main.shape[1]))
+    neighbours = property(lambda self: np.ascontiguousarray(np.stack([self.pred, self.succ], axis=1)))   # [Q, 2, 8]: as the ABI takes them
+
+    def same_as(self, other):
+        """Byte for byte: equal queries, indices, neighbours, heights and cells, the zero ones included."""
+        names = ("trees", "queries", "indices", "pred", "succ", "main", "low", "heights")
+        return all(getattr(self, n).shape == getattr(other, n).shape and bool((getattr(self, n) == getattr(other, n)).all()) for n in names)
+
+    def verify(self, dev, roots, counts):
+        """uint32 [Q]: 0 not proven, 1 absent, 2 present -- proof q under roots[trees[q]] and counts[trees[q]] (roots [ntrees, 8],
+        counts [ntrees]: the verifier's own tables)."""
+        Q = self.Q
+        if Q == 0:
+            return np.zeros(0, np.uint32)
+        roots, counts = _host(roots, np.uint32, -1, 8), _host(counts, np.uint64, -1)
+        if roots.shape[0] != counts.shape[0]:
+            raise ValueError("AbsenceProofs.verify: one count per root")
+        with dev.scope() as tmp:
+            d_verdict = tmp.alloc(4 * Q)
+            dev.verify_forest_absence_enqueue(tmp.upload(self.queries), tmp.upload(self.trees), tmp.upload(self.indices), tmp.upload(self.neighbours),
+                                              tmp.upload(self.main), tmp.upload(self.low), tmp.upload(self.heights), Q, self.stride,
+                                              tmp.upload(roots) if roots.shape[0] else None, tmp.upload(counts) if roots.shape[0] else None,
+                                              int(roots.shape[0]), d_verdict)
+            return dev.download(d_verdict, 4 * Q)
+
+
+def sort_digests(digests, counts):
+    """A HOST helper, numpy on the CPU, for tests and small callers: the digests ([n, 8] uint32) with every tree's leaves
+    (counts[t] of them, in order) sorted by the order an absence proof rests on -- word 0 first, every word unsigned.  The device
+    does not sort leaves; MerkleForest.first_unsorted checks an order made elsewhere."""
+    d = _host(digests, np.uint32, -1, 8).copy()
+    at = 0
+    for c in (int(c) for c in counts):
+        part = d[at: at + c]
+        d[at: at + c] = part[np.lexsort(tuple(part[:, w] for w in range(7, -1, -1)))]
+        at += c
+    if at != d.shape[0]:
+        raise ValueError(f"sort_digests: the counts sum to {at}, {d.shape[0]} digests given")
+    return d
 
 
 def consistency_status_text(status):

@@ -54,6 +54,7 @@ EXPECTED_HASH_BLOCKS = {"ELi64ELi5ELb1": 3,   # map_kernel MODE 5 (two blocks pe
                         "frontier_level_kernel": 1, "frontier_roots_kernel": 1,   # one hash_pair each: operands chosen by pointer; the walk's loop body
                         "consistency_fold_kernel": 1,   # both root walks of a consistency check through one hash_pair: one loop, operands selected
                         "proofs_at_edge_kernel": 1,   # the old tree's right edge, a lane per epoch: one loop over the levels, operands selected
+                        "forest_absence_fold_kernel": 1, "tree_absence_fold_kernel": 1,   # an absence proof's two folds, a lane per proof: one ballot-driven loop, operands selected
                         "map_persist_kernel": 4, "map_hash_sorted_kernel": 2}   # the last two: experiments build (staged + per-lane loop; block + digest)
 
 _INSTR = re.compile(r"^\s+([a-z_0-9]+)\s*(.*)$")
