@@ -8,6 +8,7 @@ A new operation's ABI file starts from a table of arguments:
     from abi_support import Refusals, assert_bound, assert_exported, assert_key_resolves, assert_no_spills, isa_record
 
     assert_bound("vkmr_hip_thing_async", nparams=9, scalars=[C.c_int, C.c_uint64, C.c_uint32])   # the literals pin the header
+    assert_bound("vkmr_host_cpu_thing", nparams=7, table=_abi.HOST_SIGNATURES, header="vkmr_host.h")   # the CPU twin, against its own
     assert_exported(native.HIP_LIB, ["vkmr_hip_thing_async"])
     r = Refusals(lib.vkmr_hip_thing_async, "vkmr_hip_thing_async", good=[d, d, 100, d, 8, d, d])
     r.null(0, 1, 3, 5, 6)                          # each pointer set to NULL alone
@@ -26,7 +27,8 @@ from typing import NamedTuple
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INCLUDE = os.path.join(ROOT, "include")
 POINTER = "a pointer"          # what ctypes_of says of a parameter the stub may bind as c_void_p, c_char_p or a POINTER(...) type
-SCALARS = {"int": C.c_int, "vkmr_status": C.c_int, "unsigned": C.c_uint, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "size_t": C.c_size_t}
+SCALARS = {"int": C.c_int, "vkmr_status": C.c_int, "unsigned": C.c_uint, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64, "size_t": C.c_size_t,
+           "int32_t": C.c_int32, "int64_t": C.c_int64}     # vkmr_host.h's; its uint8_t, char, double and void stand behind a `*` only
 
 
 class Declaration(NamedTuple):
@@ -53,12 +55,13 @@ def _handles(text):
 
 @functools.lru_cache(maxsize=None)
 def declarations(header="vkmr_hip.h"):
-    """{name: Declaration} of every `VKMR_API <type> vkmr_hip_<name>(<parameters>);` of the header."""
+    """{name: Declaration} of every `VKMR_API <type> vkmr_hip_<name>(<parameters>);` or `... vkmr_host_<name>(...)` of the header
+    itself; what it includes declares its own."""
     text = _source(header)
     handles = frozenset(_handles(text))
     text = re.sub(r"^\s*#.*$", " ", text, flags=re.M)                                   # `#define VKMR_API ...` declares nothing
     found = {}
-    for restype, name, params in re.findall(r"\bVKMR_API\s+([^;()]+?)\b(vkmr_hip_\w+)\s*\(([^()]*)\)\s*;", text):
+    for restype, name, params in re.findall(r"\bVKMR_API\s+([^;()]+?)\b(vkmr_(?:hip|host)_\w+)\s*\(([^()]*)\)\s*;", text):
         assert name not in found, name
         params = " ".join(params.split())
         pairs = []

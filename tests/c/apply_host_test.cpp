@@ -17,19 +17,7 @@
 #include <string>
 #include <vector>
 
-#include "vkmr_hip.h"
-
-extern "C" {
-int vkmr_host_cpu_forest_multiproof(const vkmr_digest* digests, const uint64_t* offsets, uint32_t ntrees, const uint32_t* trees,
-                                    const uint64_t* indices, uint32_t k, uint32_t stride, vkmr_digest* nodes, uint64_t nodes_capacity,
-                                    uint32_t* heights, uint64_t* info);
-int vkmr_host_cpu_forest_roots(const vkmr_digest* digests, const uint64_t* offsets, uint32_t ntrees, vkmr_digest* roots);
-int vkmr_host_cpu_apply_multiproof(const vkmr_digest* old_leaves, const vkmr_digest* new_leaves, const uint64_t* indices, uint32_t k, uint64_t count,
-                                   uint32_t height, const vkmr_digest* nodes, uint64_t m, const vkmr_digest* root, vkmr_digest* new_root);
-int vkmr_host_cpu_apply_forest_multiproof(const vkmr_digest* old_leaves, const vkmr_digest* new_leaves, const uint32_t* trees, const uint64_t* indices,
-                                          const uint64_t* counts, uint32_t k, uint32_t stride, const vkmr_digest* nodes, uint64_t m,
-                                          const vkmr_digest* roots, uint32_t ntrees, vkmr_digest* new_roots);
-}
+#include "vkmr_host.h"
 
 static int fail(size_t line, const char* what)
 {

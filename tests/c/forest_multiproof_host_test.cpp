@@ -15,17 +15,7 @@
 #include <string>
 #include <vector>
 
-#include "vkmr_hip.h"
-
-extern "C" {
-int vkmr_host_cpu_forest_multiproof(const vkmr_digest* digests, const uint64_t* offsets, uint32_t ntrees, const uint32_t* trees,
-                                    const uint64_t* indices, uint32_t k, uint32_t stride, vkmr_digest* nodes, uint64_t nodes_capacity,
-                                    uint32_t* heights, uint64_t* info);
-int vkmr_host_cpu_verify_forest_multiproof(const vkmr_digest* leaves, const uint32_t* trees, const uint64_t* indices, const uint32_t* heights,
-                                           uint32_t k, uint32_t stride, const vkmr_digest* nodes, uint64_t m, const vkmr_digest* roots,
-                                           uint32_t ntrees);
-int vkmr_host_cpu_forest_roots(const vkmr_digest* digests, const uint64_t* offsets, uint32_t ntrees, vkmr_digest* roots);
-}
+#include "vkmr_host.h"
 
 static int fail(size_t line, const char* what)
 {

@@ -53,10 +53,10 @@ def device():
     return dev
 
 
-def methods():
-    """The public `*_async` methods of HipDevice, by name."""
+def methods(suffix="_async"):
+    """The public `*_async` methods of HipDevice, by name (or those of another suffix: the record holds only these)."""
     from vk_merkle_roots_amd import engine
-    return sorted(n for n, f in vars(engine.HipDevice).items() if n.endswith("_async") and not n.startswith("_") and inspect.isfunction(f))
+    return sorted(n for n, f in vars(engine.HipDevice).items() if n.endswith(suffix) and not n.startswith("_") and inspect.isfunction(f))
 
 
 def cases(method):

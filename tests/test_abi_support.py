@@ -67,6 +67,55 @@ def test_a_header_that_differs_from_the_stub_is_caught(what, old, new):
         bound(header=HEADER.replace(old, new))
 
 
+HOST_HEADER = """
+#include "vkmr_hip.h"
+/* VKMR_API int vkmr_host_in_a_comment(int n); */
+VKMR_API int64_t vkmr_host_thing(const uint8_t* buf, uint64_t len, uint32_t maxlen, int which, const vkmr_digest* roots, char* root_hex,
+                                 double* seconds);
+VKMR_API void* vkmr_host_thing_open(uint32_t seed);
+VKMR_API void vkmr_host_thing_rand(uint32_t seed, int32_t* out, uint64_t n);
+"""
+HOST_TABLE = {"vkmr_host_thing": (C.c_int64, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_void_p, C.c_char_p, C.POINTER(C.c_double)]),
+              "vkmr_host_thing_open": (C.c_void_p, [C.c_uint32]),
+              "vkmr_host_thing_rand": (None, [C.c_uint32, C.c_void_p, C.c_uint64])}
+HOST_THING = "vkmr_host_thing"
+
+
+def test_a_host_header_is_read_as_written():
+    d = A.declarations(HOST_HEADER)
+    assert sorted(d) == sorted(HOST_TABLE) == A.declared_symbols(HOST_HEADER)
+    assert A.ctypes_of(d[HOST_THING]) == (C.c_int64, [A.POINTER, C.c_uint64, C.c_uint32, C.c_int, A.POINTER, A.POINTER, A.POINTER])
+    assert A.ctypes_of(d["vkmr_host_thing_open"]) == (A.POINTER, [C.c_uint32])
+    assert A.ctypes_of(d["vkmr_host_thing_rand"]) == (None, [C.c_uint32, A.POINTER, C.c_uint64])       # an int32_t* is a pointer
+    for name in HOST_TABLE:
+        bound(header=HOST_HEADER, table=HOST_TABLE, name=name)
+    bound(header=HOST_HEADER, table=HOST_TABLE, name=HOST_THING, nparams=7, scalars=[C.c_uint64, C.c_uint32, C.c_int], restype=C.c_int64)
+
+
+@pytest.mark.parametrize("what,old,new", [
+    ("a parameter is dropped", "uint32_t maxlen, ", ""),
+    ("uint32_t has become uint64_t", "uint32_t maxlen", "uint64_t maxlen"),
+    ("uint64_t has become uint32_t", "uint64_t len", "uint32_t len"),
+    ("a pointer has become a scalar", "const uint8_t* buf", "uint64_t buf"),
+    ("a scalar has become a pointer", "int which", "int* which"),
+    ("the return type differs", "VKMR_API int64_t vkmr_host_thing(", "VKMR_API int vkmr_host_thing("),
+    ("the return type has become a pointer", "VKMR_API int64_t vkmr_host_thing(", "VKMR_API void* vkmr_host_thing("),
+    ("the name is not declared", "vkmr_host_thing(", "vkmr_host_other("),
+])
+def test_a_host_header_that_differs_from_the_stub_is_caught(what, old, new):
+    assert HOST_HEADER.count(old) == 1
+    with pytest.raises(AssertionError):
+        bound(header=HOST_HEADER.replace(old, new), table=HOST_TABLE, name=HOST_THING)
+
+
+def test_a_host_stub_that_differs_from_the_header_is_caught():
+    res, args = HOST_TABLE[HOST_THING]
+    for entry in ((res, args[:-1]), (C.c_int, args), (res, args[:1] + [C.c_uint32] + args[2:]), (res, args[:2] + [C.c_uint64] + args[3:]),
+                  (res, [C.c_uint64] + args[1:])):
+        with pytest.raises(AssertionError):
+            bound(header=HOST_HEADER, table={HOST_THING: entry}, name=HOST_THING)
+
+
 def test_a_stub_that_differs_from_the_header_is_caught():
     res, args = TABLE[THING]
     for entry in ((res, args[:-1]), (res, args + [C.c_void_p]), (C.c_size_t, args), (None, args), (res, [C.c_uint32] + args[1:]),

@@ -1,5 +1,5 @@
-"""The C-ABI library loads and exports every symbol include/vkmr_hip.h declares.
-No compute calls here: this runs without a GPU."""
+"""The C-ABI library loads and exports every symbol include/vkmr_hip.h declares, and the two host libraries those of
+include/vkmr_host.h.  No compute calls here: this runs without a GPU."""
 import ctypes as C
 import os
 import re
@@ -27,7 +27,7 @@ def test_python_stub_covers_the_header(native):
 
 def test_the_stub_binds_every_declaration_argument_by_argument():
     """Every entry of _abi.SIGNATURES against its declaration in include/vkmr_hip.h: arity, every scalar's type, pointer for
-    pointer, the return type.  (HOST_SIGNATURES has no header to be read against.)"""
+    pointer, the return type."""
     from vk_merkle_roots_amd import _abi
     assert sorted(_abi.SIGNATURES) == declared_symbols() and len(_abi.SIGNATURES) >= 98
     for name in declared_symbols():
@@ -40,6 +40,59 @@ def test_the_experiments_stub_binds_every_declaration_argument_by_argument():
     assert sorted(_abi.EXPERIMENT_SIGNATURES) == declared_symbols(header) != []
     for name in declared_symbols(header):
         assert_bound(name, table=_abi.EXPERIMENT_SIGNATURES, header=header)
+
+
+HOST_HEADER = "vkmr_host.h"
+PIPELINE_ONLY = ["vkmr_host_pipeline_packed", "vkmr_host_pipeline_text"]   # libvkmr_pipeline.so's own: bench.py binds them for itself
+
+
+def test_the_host_stub_binds_every_declaration_argument_by_argument():
+    """Every entry of _abi.HOST_SIGNATURES against its declaration in include/vkmr_host.h, as above."""
+    from vk_merkle_roots_amd import _abi
+    declared = declared_symbols(HOST_HEADER)
+    assert set(PIPELINE_ONLY) <= set(declared)
+    assert sorted(_abi.HOST_SIGNATURES) == [n for n in declared if n not in PIPELINE_ONLY] and len(_abi.HOST_SIGNATURES) >= 41
+    for name in _abi.HOST_SIGNATURES:
+        assert_bound(name, table=_abi.HOST_SIGNATURES, header=HOST_HEADER)
+
+
+def exported_host_symbols(path):
+    import subprocess
+    out = subprocess.run(["nm", "-D", "--defined-only", path], stdout=subprocess.PIPE, check=True).stdout.decode()
+    return {line.split()[-1] for line in out.splitlines() if re.search(r"\bvkmr_host_\w+$", line)}
+
+
+def test_the_host_libraries_export_what_the_host_header_declares_and_nothing_else(native):
+    declared = set(declared_symbols(HOST_HEADER))
+    host, pipeline = exported_host_symbols(native.HOST_LIB), exported_host_symbols(native.PIPELINE_LIB)
+    assert declared <= host | pipeline, sorted(declared - host - pipeline)
+    assert host | pipeline <= declared, sorted((host | pipeline) - declared)
+    assert host == declared - set(PIPELINE_ONLY) and set(PIPELINE_ONLY) <= pipeline
+    assert_exported(native.HOST_LIB, sorted(host))                 # and the loader finds them
+
+
+def test_the_host_header_is_plain_c(tmp_path):
+    src = tmp_path / "t.c"
+    src.write_text('#include "vkmr_host.h"\nint main(void){ int (*f)(const vkmr_digest*, uint32_t, vkmr_digest*) = vkmr_host_cpu_combine; '
+                   'int64_t (*g)(void*, uint64_t, uint32_t, uint32_t*, uint64_t, vkmr_metadata*, uint64_t*) = vkmr_host_rndm_next; (void)f; (void)g; return 0; }\n')
+    import subprocess
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), "-c", str(src), "-o", str(tmp_path / "t.o")])
+
+
+def test_a_definition_that_differs_from_the_host_header_stops_the_compile(tmp_path):
+    """The definitions take their linkage from include/vkmr_host.h; with one parameter's type edited in a copy of the header that
+    stands first on the include path, the build's own flags refuse host_api.cpp (and take it with the header as it is)."""
+    import subprocess
+    from vk_merkle_roots_amd import build
+    text = open(os.path.join(ROOT, "include", HOST_HEADER)).read()
+    old = "vkmr_host_cpu_fold_proof(const vkmr_digest* leaf, uint64_t index,"
+    assert text.count(old) == 1
+    for edited, stops in ((text, False), (text.replace(old, old.replace("uint64_t index", "uint32_t index")), True)):
+        (tmp_path / HOST_HEADER).write_text(edited)
+        r = subprocess.run([os.environ.get("CXX", "g++"), "-fsyntax-only", "-I", str(tmp_path)] + build.HOST_CXXFLAGS + [os.path.join(build.HOST, "host_api.cpp")],
+                           stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+        assert (r.returncode != 0) == stops, r.stdout.decode()[-2000:]
+        assert not stops or b"vkmr_host_cpu_fold_proof" in r.stdout
 
 
 def test_header_is_plain_c(tmp_path):

@@ -37,7 +37,8 @@ def test_header_library_and_stub_agree_on_the_new_symbols(native):
     assert_bound(ENTRY_POINTS[1], nparams=14, scalars=[C.c_int, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint64])
     assert_bound(ENTRY_POINTS[2], nparams=16, scalars=[C.c_int, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32])
     assert_exported(native.HOST_LIB, HOST_ENTRY_POINTS)
-    assert [len(_abi.HOST_SIGNATURES[n][1]) for n in HOST_ENTRY_POINTS] == [10, 12]
+    for name, nparams in zip(HOST_ENTRY_POINTS, [10, 12]):
+        assert_bound(name, nparams=nparams, table=_abi.HOST_SIGNATURES, header="vkmr_host.h")
 
 
 def test_the_python_wrappers_are_there_and_none_is_named_async(native):

@@ -28,7 +28,7 @@ def test_libraries_export_the_symbols_and_the_stub_binds_them(native):
     for name, nargs in NEW.items():
         assert_bound(name, nparams=nargs)
     for name, nargs in HOST_NEW.items():
-        assert len(_abi.HOST_SIGNATURES[name][1]) == nargs
+        assert_bound(name, nparams=nargs, table=_abi.HOST_SIGNATURES, header="vkmr_host.h")
     _abi.host_lib()
 
 
@@ -395,25 +395,6 @@ def test_audit_async_hands_the_abi_its_arguments_in_the_headers_order():
         ("vkmr_hip_tree_audit_async", [3, 0x6000, leaves.ptr, tree.ptr, 14, 5, None, None, None, 0, info.ptr])]
     for name, args in dev.lib.calls:
         assert len(args) == len(_abi.SIGNATURES[name][1])
-
-
-def test_the_raw_wrappers_pass_every_argument_in_the_headers_order():
-    """HipDevice.forest_audit_enqueue / tree_audit_enqueue over the recording library of tests/golden/make_engine_calls.py and its
-    synthesised cases (default, another stream, every buffer as None): the wrapper's parameters are the ABI's, in its order."""
-    import importlib.util
-    from vk_merkle_roots_amd import _abi
-    spec = importlib.util.spec_from_file_location("make_engine_calls", os.path.join(merkle_model.ROOT, "tests", "golden", "make_engine_calls.py"))
-    calls = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(calls)
-    for method, c_name in (("forest_audit_enqueue", "vkmr_hip_forest_audit_async"), ("tree_audit_enqueue", "vkmr_hip_tree_audit_async")):
-        cases = calls.cases(method)
-        assert {"default", "stream", "scratch_buf=None", "info_buf=None"} <= set(cases)
-        for case, kwargs in cases.items():
-            kw = dict(kwargs)
-            stream = kw.pop("stream", calls.DEVICE_STREAM)
-            want = [calls.DEVICE_INDEX, stream] + [getattr(v, "ptr", v) for v in kw.values()]      # the parameters in declaration order
-            assert calls.record(method, kwargs) == [c_name, want], (method, case)
-            assert len(want) == len(_abi.SIGNATURES[c_name][1])
 
 
 # ---- the build ------------------------------------------------------------------------------------------------------------------

@@ -29,8 +29,7 @@ def test_header_declares_them_and_the_stub_binds_every_argument():
     for name, nparams in ENTRY_POINTS.items():
         assert_bound(name, nparams=nparams, restype=C.c_int)
     for name, nparams in HOST_ENTRY_POINTS.items():
-        res, args = _abi.HOST_SIGNATURES[name]
-        assert len(args) == nparams and res is C.c_int, name
+        assert_bound(name, nparams=nparams, restype=C.c_int, table=_abi.HOST_SIGNATURES, header="vkmr_host.h")
 
 
 def test_libraries_export_them(native):

@@ -23,7 +23,8 @@ def test_library_exports_the_symbols_and_the_stub_binds_them(native):
     for name, nargs in NEW.items():
         assert_bound(name, nparams=nargs)
     assert_exported(native.HOST_LIB, ["vkmr_host_cpu_forest_find", "vkmr_host_cpu_tree_find"])
-    assert len(_abi.HOST_SIGNATURES["vkmr_host_cpu_forest_find"][1]) == 8 and len(_abi.HOST_SIGNATURES["vkmr_host_cpu_tree_find"][1]) == 5
+    assert_bound("vkmr_host_cpu_forest_find", nparams=8, table=_abi.HOST_SIGNATURES, header="vkmr_host.h")
+    assert_bound("vkmr_host_cpu_tree_find", nparams=5, table=_abi.HOST_SIGNATURES, header="vkmr_host.h")
 
 
 def test_the_model_itself():

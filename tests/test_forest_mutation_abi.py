@@ -22,7 +22,7 @@ def test_library_exports_the_symbols_and_the_stub_binds_them(native):
     assert_bound("vkmr_hip_reduce_forest_async", nparams=10)
     assert_bound("vkmr_hip_reduce_forest_tree_async", nparams=10)
     assert_exported(native.HOST_LIB, ["vkmr_host_cpu_forest_mutated"])
-    assert len(_abi.HOST_SIGNATURES["vkmr_host_cpu_forest_mutated"][1]) == 5
+    assert_bound("vkmr_host_cpu_forest_mutated", nparams=5, table=_abi.HOST_SIGNATURES, header="vkmr_host.h")
 
 
 @pytest.mark.parametrize("name", ["vkmr_hip_reduce_forest_mutated_async", "vkmr_hip_reduce_forest_tree_mutated_async"])

@@ -38,8 +38,7 @@ def test_header_declares_them_and_the_stub_binds_every_argument():
     assert_bound(SIZES[1], nparams=4, scalars=[C.c_uint64, C.c_uint32, C.c_uint64, C.c_uint32], restype=C.c_size_t)
     assert_bound(SIZES[2], nparams=2, scalars=[C.c_uint32, C.c_uint32], restype=C.c_size_t)
     for name, n in HOST.items():
-        res, args = _abi.HOST_SIGNATURES[name]
-        assert len(args) == n and res is C.c_int
+        assert_bound(name, nparams=n, restype=C.c_int, table=_abi.HOST_SIGNATURES, header="vkmr_host.h")
     text = open(os.path.join(ROOT, "include", "vkmr_hip.h")).read()
     block = text[text.index("PARTIAL MERKLE TREES IN BIP37 ORDER"): text.index(SIZES[0] + "(")]
     for said in ("THE LONE LEAF", "TraverseAndBuild", "bit i & 7 of byte i >> 3", "bit 2", "atomicOr", "never a launch per tree", "Not offered: a batched"):
@@ -404,7 +403,7 @@ def test_the_kernels_hash_nothing_shadow_no_key_and_spill_nothing(native):
         assert not any(s in name for s in NAMES_OTHER_TESTS_COUNT), name
     text = open(os.path.join(ROOT, "vk_merkle_roots_amd", "csrc", "merkleblock_kernels.hpp")).read()
     assert not re.search(r"\bhash_(pair|parent)\(", text) and sorted(re.findall(r"void (\w+_kernel)\(", text)) == sorted(KERNELS)
-    assert "merkleblock_plan.hpp" in open(build.__file__).read()
+    assert os.path.join(build.CSRC, "merkleblock_plan.hpp") in build.host_headers()
     rec = isa_record(native)
     if rec is not None:
         assert rec["audit"]["block_count_errors"] == [] and rec["audit"]["unclassified"] == []

@@ -30,8 +30,7 @@ def test_header_declares_it_and_the_stub_binds_every_argument():
     text = open(os.path.join(ROOT, "include", "vkmr_hip.h")).read()
     from vk_merkle_roots_amd import _abi
     assert_bound(ENTRY_POINT, nparams=NPARAMS, restype=C.c_int)
-    res, args = _abi.HOST_SIGNATURES[HOST_ENTRY_POINT]
-    assert len(args) == HOST_NPARAMS and res is C.c_int
+    assert_bound(HOST_ENTRY_POINT, nparams=HOST_NPARAMS, restype=C.c_int, table=_abi.HOST_SIGNATURES, header="vkmr_host.h")
     # the header says how the proofs are verified, and no longer says that they are not offered
     assert "Not offered: inclusion proofs as of an earlier count" not in text
     block = text[text.index("INCLUSION PROOFS AS OF AN EARLIER COUNT"): text.index(ENTRY_POINT + "(")]
@@ -255,7 +254,7 @@ def test_the_kernel_key_resolves_to_itself_and_the_build_lists_it(native):
     text = open(os.path.join(ROOT, "vk_merkle_roots_amd", "csrc", "proofs_at_kernels.hpp")).read()
     assert len(re.findall(r"\bhash_pair\(", text)) == 1 and sorted(re.findall(r"void (\w+_kernel)\(", text)) == sorted(KERNELS)
     from vk_merkle_roots_amd import build
-    assert "proofs_at_plan.hpp" in open(build.__file__).read()
+    assert os.path.join(build.CSRC, "proofs_at_plan.hpp") in build.host_headers()
     rec = isa_record(native)
     if rec is not None:                    # written by a build that ran the issue pass (tests/test_isa_prio_pass.py covers its absence)
         assert rec["audit"]["block_count_errors"] == [] and rec["audit"]["unclassified"] == []

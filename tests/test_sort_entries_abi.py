@@ -22,7 +22,8 @@ def test_library_exports_the_symbols_and_the_stub_binds_them(native):
     for name, nargs in NEW.items():
         assert_bound(name, nparams=nargs)
     assert_exported(native.HOST_LIB, ["vkmr_host_cpu_forest_sort_entries", "vkmr_host_cpu_tree_sort_entries"])
-    assert len(_abi.HOST_SIGNATURES["vkmr_host_cpu_forest_sort_entries"][1]) == 10 and len(_abi.HOST_SIGNATURES["vkmr_host_cpu_tree_sort_entries"][1]) == 6
+    assert_bound("vkmr_host_cpu_forest_sort_entries", nparams=10, table=_abi.HOST_SIGNATURES, header="vkmr_host.h")
+    assert_bound("vkmr_host_cpu_tree_sort_entries", nparams=6, table=_abi.HOST_SIGNATURES, header="vkmr_host.h")
 
 
 def test_the_model_itself():

@@ -31,6 +31,9 @@ SPLIT_ADD3_EVERY = 4   # isa_prio_pass: every 4th v_add3_u32 becomes two v_add_u
 LATENCY_BOUND_KERNELS = ("reduce_collapse_kernel", "reduce_tail_kernel", "reduce_collapse_proofs_kernel", "reduce_tail_proofs_kernel")   # one wavefront per SIMD: left as hipcc emits them (collapse: 113 vs 140 us with the pass, profiles/r03_reduce_top_kernels.txt)
 ROTATE_LEVEL = None    # isa_prio_pass: priority of v_alignbit_b32 when it differs from the other complex instructions' (1)
 PRIO_GAP = 0    # isa_prio_pass: complex-instruction runs separated by at most this many simple instructions are merged
+# missing-declarations: a vkmr_host_* definition whose parameters have drifted from include/vkmr_host.h is no longer the declared
+# function but an overload nobody declared (hidden, C++ linkage); this stops the compile there
+HOST_CXXFLAGS = ["-O2", "-std=c++17", "-Wall", "-Werror=missing-declarations", "-pthread", "-I", os.path.join(ROOT, "include"), "-I", HOST]
 
 
 def _hipcc():
@@ -182,13 +185,20 @@ def build_experiments_stamps(force=False):
     return _build_hip_variant(os.path.join(ROOT, "build", "ab", "libexp_stamps.so"), ["-DVKMR_EXPERIMENTS", "-DVKMR_STAMPS"], force)
 
 
+def host_headers():
+    """What the host-side C++ is rebuilt for: its own headers, the two C headers, merkle_math.hpp and every plan header --
+    host_api.cpp includes only some of them, at the cost of a few needless rebuilds and with no list to keep."""
+    import glob
+    return (_tree(HOST, (".hpp", ".h")) + [os.path.join(ROOT, "include", h) for h in ("vkmr_hip.h", "vkmr_host.h")] +
+            sorted(glob.glob(os.path.join(CSRC, "*_plan.hpp"))) + [os.path.join(CSRC, "merkle_math.hpp")])
+
+
 def build_host(force=False):
     """Host-side C++ (g++): helper library, front end, tools."""
     os.makedirs(BIN, exist_ok=True)
-    hdrs = _tree(HOST, (".hpp", ".h")) + [os.path.join(ROOT, "include", "vkmr_hip.h")] + [
-        os.path.join(CSRC, h) for h in ("merkle_math.hpp", "forest_plan.hpp", "tree_plan.hpp", "audit_plan.hpp", "frontier_plan.hpp", "consistency_plan.hpp", "proofs_at_plan.hpp", "merkleblock_plan.hpp", "absence_plan.hpp")]
+    hdrs = host_headers()
     cxx = os.environ.get("CXX", "g++")
-    flags = ["-O2", "-std=c++17", "-Wall", "-pthread", "-I", os.path.join(ROOT, "include"), "-I", HOST]
+    flags = HOST_CXXFLAGS
     built = []
 
     def need(target, srcs):

@@ -1,5 +1,6 @@
-// host_api.cpp -- C entry points over the host-side C++ for bindings and tests
-// (libvkmr_host.so): the "CPU" backend on packed batches and on slice roots.
+// host_api.cpp -- the vkmr_host_cpu_* entry points of libvkmr_host.so: the "CPU" backend on packed batches and slice roots and
+// the CPU twins of the stored-structure operations.  include/vkmr_host.h declares every one and holds its contract; linkage
+// and visibility come from there, and the definitions below stand in the header's order.
 #include <algorithm>
 #include <cstdint>
 #include <cstring>
@@ -13,7 +14,7 @@
 #include "../merkle_math.hpp"
 #include "../proofs_at_plan.hpp"
 #include "cpu_sha256d.hpp"
-#include "vkmr_hip.h"
+#include "vkmr_host.h"
 
 namespace {
 
@@ -80,20 +81,13 @@ void tree_levels(const vkmr_digest* first, const vkmr_digest* last, uint32_t h, 
 
 }  // namespace
 
-extern "C" {
-
-// Leaf digests of a packed batch with the CPU backend (CpuSha256D::Add per string).
-__attribute__((visibility("default"))) void vkmr_host_cpu_leaves(const uint32_t* data, const vkmr_metadata* meta, uint64_t count,
-                                                                  vkmr_digest* out)
+void vkmr_host_cpu_leaves(const uint32_t* data, const vkmr_metadata* meta, uint64_t count, vkmr_digest* out)
 {
     for (uint64_t i = 0; i < count; ++i)
         vkmr::cpu_sha256d_words(reinterpret_cast<const unsigned char*>(data + meta[i].start), meta[i].size, out[i].data);
 }
 
-// Sub-tree root of `count` digests through exactly `height` levels (the per-slice
-// contract of vkmr_hip_reduce_async), on the CPU backend's node function.
-__attribute__((visibility("default"))) int vkmr_host_cpu_reduce(const vkmr_digest* digests, uint64_t count, uint32_t height,
-                                                                 vkmr_digest* root)
+int vkmr_host_cpu_reduce(const vkmr_digest* digests, uint64_t count, uint32_t height, vkmr_digest* root)
 {
     if (!digests || !root || count == 0) return -1;
     std::vector<uint32_t> nodes(8 * count);
@@ -113,10 +107,7 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_reduce(const vkmr_diges
     return 0;
 }
 
-// Combine of slice roots in slice order: duplicate-last tree, at least one level
-// (CpuSha256D::Root over already-hashed nodes; reference CpuSha256DforReductions,
-// src/vkmr/Reductions.cpp:56-69, :703-712).
-__attribute__((visibility("default"))) int vkmr_host_cpu_combine(const vkmr_digest* roots, uint32_t n, vkmr_digest* out)
+int vkmr_host_cpu_combine(const vkmr_digest* roots, uint32_t n, vkmr_digest* out)
 {
     if (!roots || !out || n == 0) return -1;
     std::vector<uint32_t> nodes(8 * (size_t)n);
@@ -126,10 +117,7 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_combine(const vkmr_dige
     return 0;
 }
 
-// Folds a leaf digest with the siblings of its authentication path (vkmr_hip_proof_async):
-// bit l of `index` tells whether the path node is the right (1) or left (0) operand at level l.
-__attribute__((visibility("default"))) void vkmr_host_cpu_fold_proof(const vkmr_digest* leaf, uint64_t index, const vkmr_digest* siblings,
-                                                                      uint32_t height, vkmr_digest* root)
+void vkmr_host_cpu_fold_proof(const vkmr_digest* leaf, uint64_t index, const vkmr_digest* siblings, uint32_t height, vkmr_digest* root)
 {
     vkmr_digest cur = *leaf;
     for (uint32_t l = 0; l < height; ++l) {
@@ -140,11 +128,8 @@ __attribute__((visibility("default"))) void vkmr_host_cpu_fold_proof(const vkmr_
     *root = cur;
 }
 
-// Multiproof verification on the CPU, by the rule of vkmr_hip_verify_multiproof_async: 1 when the indices are strictly
-// increasing and < 2^height, the fold of leaves and nodes consumes exactly m nodes and ends in `root`; else 0.
-__attribute__((visibility("default"))) int vkmr_host_cpu_verify_multiproof(const vkmr_digest* leaves, const uint64_t* indices, uint32_t k,
-                                                                            uint32_t height, const vkmr_digest* nodes, uint64_t m,
-                                                                            const vkmr_digest* root)
+int vkmr_host_cpu_verify_multiproof(const vkmr_digest* leaves, const uint64_t* indices, uint32_t k, uint32_t height, const vkmr_digest* nodes,
+                                    uint64_t m, const vkmr_digest* root)
 {
     if (!leaves || !indices || !root || k == 0 || height > 63 || (!nodes && m > 0)) return 0;
     for (uint32_t q = 0; q < k; ++q)
@@ -166,11 +151,7 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_verify_multiproof(const
     return used == m && pos.size() == 1 && pos[0] == 0 && std::memcmp(cur[0].data, root->data, 32) == 0 ? 1 : 0;
 }
 
-// Roots of a forest on the CPU, by the rule of vkmr_hip_reduce_forest_async: tree t is digests[offsets[t] .. offsets[t+1]),
-// reduced through max(1, ceil(log2 c_t)) levels (vkmr_host_cpu_reduce); an empty tree gets an all-zero root.  Nonzero when
-// the offsets decrease somewhere (nothing is written then) or a pointer is missing.
-__attribute__((visibility("default"))) int vkmr_host_cpu_forest_roots(const vkmr_digest* digests, const uint64_t* offsets, uint32_t ntrees,
-                                                                       vkmr_digest* roots)
+int vkmr_host_cpu_forest_roots(const vkmr_digest* digests, const uint64_t* offsets, uint32_t ntrees, vkmr_digest* roots)
 {
     if (ntrees == 0) return 0;
     if (!offsets || !roots) return -1;
@@ -188,13 +169,7 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_forest_roots(const vkmr
     return 0;
 }
 
-// Roots and mutation masks of a forest on the CPU, by the rule of vkmr_hip_reduce_forest_mutated_async: bit l of mutated[t] is
-// set iff level l of tree t (n_l nodes) holds a j with 2j + 1 < n_l and node 2j equal to node 2j + 1 -- Bitcoin Core's
-// ComputeMerkleRoot(hashes, &mutated) with the level kept; the last node of an odd level, hashed with itself, is no pair.  An
-// empty tree gets an all-zero root and mask 0.  `roots` may be null (the masks alone).  Nonzero, and nothing written, when the
-// offsets decrease somewhere (1) or a pointer is missing (-1).
-__attribute__((visibility("default"))) int vkmr_host_cpu_forest_mutated(const vkmr_digest* digests, const uint64_t* offsets, uint32_t ntrees,
-                                                                         vkmr_digest* roots, uint64_t* mutated)
+int vkmr_host_cpu_forest_mutated(const vkmr_digest* digests, const uint64_t* offsets, uint32_t ntrees, vkmr_digest* roots, uint64_t* mutated)
 {
     if (ntrees == 0) return 0;
     if (!offsets || !mutated) return -1;
@@ -230,15 +205,8 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_forest_mutated(const vk
     return 0;
 }
 
-// Proofs from a forest on the CPU, by the rule of vkmr_hip_forest_proofs_async: query q is leaf indices[q] of tree trees[q]
-// (tree t: digests[offsets[t] .. offsets[t+1])); heights[q] = h_t = max(1, ceil(log2 c_t)) and siblings[q * stride + l] is
-// L_t[l][p ^ 1] with p = index >> l, or L_t[l][p] where p ^ 1 is past the level's end, for l < h_t and all-zero behind.  A
-// tree >= ntrees or an index >= c_t gets height 0 and `stride` zero cells.  Nonzero, and nothing written, when the offsets
-// decrease somewhere (1), when `stride` is below the largest h_t a query needs (2) or a pointer is missing (-1).  A tree's
-// levels are formed once, however many queries ask for it.  The proofs verify through vkmr_host_cpu_fold_proof.
-__attribute__((visibility("default"))) int vkmr_host_cpu_forest_proofs(const vkmr_digest* digests, const uint64_t* offsets, uint32_t ntrees,
-                                                                        const uint32_t* trees, const uint64_t* indices, uint32_t k, uint32_t stride,
-                                                                        vkmr_digest* siblings, uint32_t* heights)
+int vkmr_host_cpu_forest_proofs(const vkmr_digest* digests, const uint64_t* offsets, uint32_t ntrees, const uint32_t* trees, const uint64_t* indices,
+                                uint32_t k, uint32_t stride, vkmr_digest* siblings, uint32_t* heights)
 {
     if (k == 0) return 0;
     if (!trees || !indices || !heights || (!siblings && stride > 0) || (!offsets && ntrees > 0)) return -1;
@@ -274,17 +242,9 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_forest_proofs(const vkm
     return 0;
 }
 
-// Multiproof for leaves of many trees on the CPU, by the rule of vkmr_hip_forest_multiproof_async: entry q is leaf indices[q]
-// of tree trees[q] (tree t: digests[offsets[t] .. offsets[t+1])), the pairs strictly increasing; nodes[] receives the M nodes
-// in level-major order over the whole forest, heights[q] = h of entry q's tree, info[0] = status, info[1] = M,
-// info[2 + l] = m_l for l < stride.  Returns the status: 0 done; bit 0 a tree >= ntrees or an index >= c_t, bit 1 pairs not
-// strictly increasing (then only info[0] is written); bit 2 M > nodes_capacity (the heights, M and the counts are written, no
-// node is).  -1 for a missing pointer or k == 0, -2 when the offsets decrease somewhere, -3 when `stride` is above 63 or below
-// the height of a tree some entry names (nothing written).  A touched tree's levels are formed once, tree by tree.
-__attribute__((visibility("default"))) int vkmr_host_cpu_forest_multiproof(const vkmr_digest* digests, const uint64_t* offsets, uint32_t ntrees,
-                                                                            const uint32_t* trees, const uint64_t* indices, uint32_t k,
-                                                                            uint32_t stride, vkmr_digest* nodes, uint64_t nodes_capacity,
-                                                                            uint32_t* heights, uint64_t* info)
+int vkmr_host_cpu_forest_multiproof(const vkmr_digest* digests, const uint64_t* offsets, uint32_t ntrees, const uint32_t* trees,
+                                    const uint64_t* indices, uint32_t k, uint32_t stride, vkmr_digest* nodes, uint64_t nodes_capacity,
+                                    uint32_t* heights, uint64_t* info)
 {
     if (k == 0 || !digests || !offsets || !trees || !indices || !heights || !info || (!nodes && nodes_capacity > 0)) return -1;
     if (stride > 63) return -3;
@@ -336,14 +296,9 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_forest_multiproof(const
     return 0;
 }
 
-// Forest multiproof verification on the CPU, by the rule of vkmr_hip_verify_forest_multiproof_async: 1 when the (tree, index)
-// pairs are strictly increasing, every tree < ntrees, 1 <= heights[q] <= stride <= 63, indices[q] < 2^heights[q], the entries
-// of one tree carry one height, the indices and heights imply exactly m nodes, and every named tree's fold -- a missing child
-// being the next unread node of its level in forest order -- ends in roots[t]; else 0.
-__attribute__((visibility("default"))) int vkmr_host_cpu_verify_forest_multiproof(const vkmr_digest* leaves, const uint32_t* trees,
-                                                                                   const uint64_t* indices, const uint32_t* heights, uint32_t k,
-                                                                                   uint32_t stride, const vkmr_digest* nodes, uint64_t m,
-                                                                                   const vkmr_digest* roots, uint32_t ntrees)
+int vkmr_host_cpu_verify_forest_multiproof(const vkmr_digest* leaves, const uint32_t* trees, const uint64_t* indices, const uint32_t* heights,
+                                           uint32_t k, uint32_t stride, const vkmr_digest* nodes, uint64_t m, const vkmr_digest* roots,
+                                           uint32_t ntrees)
 {
     if (!leaves || !trees || !indices || !heights || !roots || k == 0 || stride == 0 || stride > 63 || (!nodes && m > 0)) return 0;
     for (uint32_t q = 0; q < k; ++q) {
@@ -384,8 +339,6 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_verify_forest_multiproo
     return 1;
 }
 
-}  // extern "C"
-
 namespace {
 
 // One tree's fold on both sides at once, by the rule of vkmr_hip_apply_multiproof_async: the entries [a, b) of a tree of
@@ -418,15 +371,8 @@ bool apply_fold(const uint64_t* indices, uint32_t a, uint32_t b, uint64_t count,
 
 }  // namespace
 
-extern "C" {
-
-// Applying a multiproof on the CPU, by the rule of vkmr_hip_apply_multiproof_async: 1, and *new_root written, when
-// 1 <= count <= 2^height, height is 1..63, the indices are strictly increasing and < count, the fold of the old leaves
-// consumes exactly m nodes and ends in `root`; else 0 and nothing written.  new_root may be root.
-__attribute__((visibility("default"))) int vkmr_host_cpu_apply_multiproof(const vkmr_digest* old_leaves, const vkmr_digest* new_leaves,
-                                                                           const uint64_t* indices, uint32_t k, uint64_t count, uint32_t height,
-                                                                           const vkmr_digest* nodes, uint64_t m, const vkmr_digest* root,
-                                                                           vkmr_digest* new_root)
+int vkmr_host_cpu_apply_multiproof(const vkmr_digest* old_leaves, const vkmr_digest* new_leaves, const uint64_t* indices, uint32_t k, uint64_t count,
+                                   uint32_t height, const vkmr_digest* nodes, uint64_t m, const vkmr_digest* root, vkmr_digest* new_root)
 {
     if (!old_leaves || !new_leaves || !indices || !root || !new_root || k == 0 || height == 0 || height > 63 || (!nodes && m > 0)) return 0;
     if (count == 0 || count > (1ull << height)) return 0;
@@ -449,15 +395,9 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_apply_multiproof(const 
     return 1;
 }
 
-// Applying a forest multiproof on the CPU, by the rule of vkmr_hip_apply_forest_multiproof_async: 1 when every count is
-// >= 1, indices[q] < counts[q], the entries of one tree carry one count and vkmr_host_cpu_verify_forest_multiproof answers 1
-// for the old leaves with the heights max(1, ceil(log2 count)); then new_roots[t] of every named tree is written (new_roots
-// may be roots; the cells of other trees are not touched).  Else 0 and nothing written.
-__attribute__((visibility("default"))) int vkmr_host_cpu_apply_forest_multiproof(const vkmr_digest* old_leaves, const vkmr_digest* new_leaves,
-                                                                                  const uint32_t* trees, const uint64_t* indices,
-                                                                                  const uint64_t* counts, uint32_t k, uint32_t stride,
-                                                                                  const vkmr_digest* nodes, uint64_t m, const vkmr_digest* roots,
-                                                                                  uint32_t ntrees, vkmr_digest* new_roots)
+int vkmr_host_cpu_apply_forest_multiproof(const vkmr_digest* old_leaves, const vkmr_digest* new_leaves, const uint32_t* trees,
+                                          const uint64_t* indices, const uint64_t* counts, uint32_t k, uint32_t stride, const vkmr_digest* nodes,
+                                          uint64_t m, const vkmr_digest* roots, uint32_t ntrees, vkmr_digest* new_roots)
 {
     if (!old_leaves || !new_leaves || !trees || !indices || !counts || !roots || !new_roots || k == 0 || stride == 0 || stride > 63 ||
         (!nodes && m > 0))
@@ -497,14 +437,8 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_apply_forest_multiproof
     return 1;
 }
 
-// Leaves by digest on the CPU, by the rule of vkmr_hip_forest_find_async: query q's answer is the lowest flat position p in
-// [offsets[0], offsets[ntrees]) with digests[p] == queries[q] on all 32 bytes, as trees[q] = the tree that holds p and
-// indices[q] = p - offsets[trees[q]]; no such p: 0xFFFFFFFF and UINT64_MAX.  The queries are sorted once and every leaf is
-// looked up among them: O((total + k) log k).  Nonzero, and nothing written, when the offsets decrease somewhere or end past
-// `total` (1) or a needed pointer is missing (-1).  k == 0 does nothing.
-__attribute__((visibility("default"))) int vkmr_host_cpu_forest_find(const vkmr_digest* digests, uint64_t total, const uint64_t* offsets,
-                                                                      uint32_t ntrees, const vkmr_digest* queries, uint32_t k, uint32_t* trees,
-                                                                      uint64_t* indices)
+int vkmr_host_cpu_forest_find(const vkmr_digest* digests, uint64_t total, const uint64_t* offsets, uint32_t ntrees, const vkmr_digest* queries,
+                              uint32_t k, uint32_t* trees, uint64_t* indices)
 {
     if (k == 0) return 0;
     if (!queries || !trees || !indices || (ntrees > 0 && !offsets)) return -1;
@@ -540,9 +474,7 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_forest_find(const vkmr_
     return 0;
 }
 
-// The same for one tree over digests[0 .. count): indices[q] = the lowest index whose leaf equals queries[q], or UINT64_MAX.
-__attribute__((visibility("default"))) int vkmr_host_cpu_tree_find(const vkmr_digest* digests, uint64_t count, const vkmr_digest* queries,
-                                                                    uint32_t k, uint64_t* indices)
+int vkmr_host_cpu_tree_find(const vkmr_digest* digests, uint64_t count, const vkmr_digest* queries, uint32_t k, uint64_t* indices)
 {
     if (k == 0) return 0;
     if (!indices) return -1;
@@ -551,12 +483,8 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_tree_find(const vkmr_di
     return vkmr_host_cpu_forest_find(digests, count, offsets, 1, queries, k, trees.data(), indices);
 }
 
-// Leaf entries sorted and deduplicated on the CPU, by the rule of vkmr_hip_forest_sort_entries_async: cells [0, n) of the
-// outputs are the distinct valid (tree, index) pairs, strictly increasing, order_out[j] the largest q whose pair is output
-// pair j; info[0..4) = survivors n, "not found" markers (trees[q] == 0xFFFFFFFF), entries out of range, earlier repeats.
-// trees == NULL: one tree (offsets {0, total}), the marker being indices[q] == UINT64_MAX, and trees_out is not written.
-// A stable sort of q by flat position.  Nonzero, and nothing written, when the offsets decrease somewhere or end past
-// `total` (1) or a needed pointer is missing (-1).  k == 0 does nothing (the two entry points below see to that).
+// Both sort entry points (vkmr_host.h has the contract).  trees == NULL: one tree (offsets {0, total}), the marker being
+// indices[q] == UINT64_MAX, and trees_out is not written.  k == 0 is the callers' to see to.
 static int sort_entries_cpu(uint64_t total, const uint64_t* offsets, uint32_t ntrees, const uint32_t* trees, const uint64_t* indices, uint32_t k,
                            uint32_t* trees_out, uint64_t* indices_out, uint32_t* order_out, uint64_t* info)
 {
@@ -598,35 +526,24 @@ static int sort_entries_cpu(uint64_t total, const uint64_t* offsets, uint32_t nt
     return 0;
 }
 
-__attribute__((visibility("default"))) int vkmr_host_cpu_forest_sort_entries(uint64_t total, const uint64_t* offsets, uint32_t ntrees,
-                                                                              const uint32_t* trees, const uint64_t* indices, uint32_t k,
-                                                                              uint32_t* trees_out, uint64_t* indices_out, uint32_t* order_out,
-                                                                              uint64_t* info)
+int vkmr_host_cpu_forest_sort_entries(uint64_t total, const uint64_t* offsets, uint32_t ntrees, const uint32_t* trees, const uint64_t* indices,
+                                      uint32_t k, uint32_t* trees_out, uint64_t* indices_out, uint32_t* order_out, uint64_t* info)
 {
     if (k == 0) return 0;
     if (!trees || !trees_out) return -1;
     return sort_entries_cpu(total, offsets, ntrees, trees, indices, k, trees_out, indices_out, order_out, info);
 }
 
-// The same for one tree of `count` leaves: every entry in tree 0.
-__attribute__((visibility("default"))) int vkmr_host_cpu_tree_sort_entries(uint64_t count, const uint64_t* indices, uint32_t k, uint64_t* indices_out,
-                                                                            uint32_t* order_out, uint64_t* info)
+int vkmr_host_cpu_tree_sort_entries(uint64_t count, const uint64_t* indices, uint32_t k, uint64_t* indices_out, uint32_t* order_out, uint64_t* info)
 {
     if (k == 0) return 0;
     const uint64_t offsets[2] = {0, count};
     return sort_entries_cpu(count, offsets, 1, nullptr, indices, k, nullptr, indices_out, order_out, info);
 }
 
-// A stored forest audited on the CPU, by the rule of vkmr_hip_forest_audit_async and with its outputs: node (t, l, j) is bad when
-// its stored cell -- roots[t] for the tree's last level, else cell stored_level_base(l) + pos_l(t) + j of `forest` -- is not
-// hash_pair of the two stored cells beneath it; an empty tree's root must be all zero.  masks[t] bit l - 1, the first
-// `capacity` bad nodes in (level, tree, node) order, info[0..4) = status (bits 0, 1: the offsets and max_count check, and then
-// nothing is audited; bit 2: more than `capacity` > 0 bad nodes), bad nodes, trees with a nonzero mask, nodes checked.  Reads
-// only.  -1, and nothing written, when a needed pointer is missing, max_count is 0 or total is above 2^58.
-__attribute__((visibility("default"))) int vkmr_host_cpu_forest_audit(const vkmr_digest* digests, const vkmr_digest* forest, const vkmr_digest* roots,
-                                                                       uint64_t total, const uint64_t* offsets, uint32_t ntrees, uint64_t max_count,
-                                                                       uint64_t* masks, uint32_t* bad_trees, uint32_t* bad_levels, uint64_t* bad_nodes,
-                                                                       uint32_t capacity, uint64_t* info)
+int vkmr_host_cpu_forest_audit(const vkmr_digest* digests, const vkmr_digest* forest, const vkmr_digest* roots, uint64_t total,
+                               const uint64_t* offsets, uint32_t ntrees, uint64_t max_count, uint64_t* masks, uint32_t* bad_trees,
+                               uint32_t* bad_levels, uint64_t* bad_nodes, uint32_t capacity, uint64_t* info)
 {
     if (ntrees == 0) return 0;
     if ((!digests && total > 0) || !forest || !roots || !offsets || !masks || !info || (capacity > 0 && (!bad_trees || !bad_levels || !bad_nodes)))
@@ -674,11 +591,8 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_forest_audit(const vkmr
     return 0;
 }
 
-// The same for one stored tree (vkmr_hip_tree_audit_async): levels 1 .. height in `tree` as tree_plan.hpp lays them out, a
-// lone-node level above ceil(log2 count) being hash(a, a) of the node below; info[2] is the tree's own level mask.  -1 when a
-// needed pointer is missing or `height` does not reduce `count` to one node.
-__attribute__((visibility("default"))) int vkmr_host_cpu_tree_audit(const vkmr_digest* digests, const vkmr_digest* tree, uint64_t count, uint32_t height,
-                                                                     uint32_t* bad_levels, uint64_t* bad_nodes, uint32_t capacity, uint64_t* info)
+int vkmr_host_cpu_tree_audit(const vkmr_digest* digests, const vkmr_digest* tree, uint64_t count, uint32_t height, uint32_t* bad_levels,
+                             uint64_t* bad_nodes, uint32_t capacity, uint64_t* info)
 {
     if (count == 0) return 0;
     if (!digests || (height > 0 && !tree) || !info || (capacity > 0 && (!bad_levels || !bad_nodes))) return -1;
@@ -706,8 +620,7 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_tree_audit(const vkmr_d
     return 0;
 }
 
-// ---- frontiers (frontier_plan.hpp; vkmr_hip_frontier_roots_async, vkmr_hip_frontier_extend_async, vkmr_hip_forest_frontier_async)
-// for a follower without a GPU.  The extension here is NOT the device's level rule: a leaf at a time, the carry chain of a
+// ---- frontiers (frontier_plan.hpp).  The extension here is NOT the device's level rule: a leaf at a time, the carry chain of a
 // binary counter (the node climbs while the count's bit is set, merging with the peak it meets), so the two check each other.
 
 // The root of one frontier by the rule of vkmr_hip_frontier_roots_async; `peaks` are its stride cells, c fits them.
@@ -748,10 +661,7 @@ static void frontier_push(uint64_t& c, vkmr_digest* peaks, const vkmr_digest& le
     ++c;
 }
 
-// roots[q] = the root of frontier q (counts[q], the stride cells behind peaks + q * stride), T of them.  A count above 2^58 or
-// of more bits than stride gives the zero root and makes the call return 1; -1 for a missing pointer or a stride outside 1..64.
-__attribute__((visibility("default"))) int vkmr_host_cpu_frontier_roots(const uint64_t* counts, const vkmr_digest* peaks, uint32_t stride, uint32_t T,
-                                                                         vkmr_digest* roots)
+int vkmr_host_cpu_frontier_roots(const uint64_t* counts, const vkmr_digest* peaks, uint32_t stride, uint32_t T, vkmr_digest* roots)
 {
     if (T == 0) return 0;
     if (!counts || !peaks || !roots || stride == 0 || stride > VKMR_FRONTIER_MAX_STRIDE) return -1;
@@ -767,13 +677,9 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_frontier_roots(const ui
     return rc;
 }
 
-// T frontiers each take leaves[offsets[q] .. offsets[q+1]): the new counts, the new peaks (cells of clear bits zero) and the
-// roots, by the contract of vkmr_hip_frontier_extend_async; new_counts / new_peaks may be counts / peaks.  Returns the status
-// word of that call (0: done; nonzero: nothing written), or -1 for a missing pointer or a stride outside 1..64.
-__attribute__((visibility("default"))) int vkmr_host_cpu_frontier_extend(const uint64_t* counts, const vkmr_digest* peaks, uint32_t stride, uint32_t T,
-                                                                          const vkmr_digest* leaves, uint64_t total_new, const uint64_t* offsets,
-                                                                          uint64_t max_new, uint64_t* new_counts, vkmr_digest* new_peaks,
-                                                                          vkmr_digest* roots)
+int vkmr_host_cpu_frontier_extend(const uint64_t* counts, const vkmr_digest* peaks, uint32_t stride, uint32_t T, const vkmr_digest* leaves,
+                                  uint64_t total_new, const uint64_t* offsets, uint64_t max_new, uint64_t* new_counts, vkmr_digest* new_peaks,
+                                  vkmr_digest* roots)
 {
     if (T == 0) return 0;
     if (!counts || !peaks || (!leaves && total_new > 0) || !offsets || !new_counts || !new_peaks || !roots) return -1;
@@ -795,11 +701,8 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_frontier_extend(const u
     return 0;
 }
 
-// The frontiers of the trees of a forest from its leaves: tree t is digests[offsets[t] .. offsets[t+1]).  What
-// vkmr_hip_forest_frontier_async reads out of a stored forest.  1, and nothing written, when the offsets decrease or a tree has
-// more leaves than 2^58 or than stride bits hold; -1 for a missing pointer or a stride outside 1..64.
-__attribute__((visibility("default"))) int vkmr_host_cpu_forest_frontier(const vkmr_digest* digests, const uint64_t* offsets, uint32_t ntrees,
-                                                                          uint32_t stride, uint64_t* counts_out, vkmr_digest* peaks_out)
+int vkmr_host_cpu_forest_frontier(const vkmr_digest* digests, const uint64_t* offsets, uint32_t ntrees, uint32_t stride, uint64_t* counts_out,
+                                  vkmr_digest* peaks_out)
 {
     if (ntrees == 0) return 0;
     if (!offsets || !counts_out || !peaks_out || stride == 0 || stride > VKMR_FRONTIER_MAX_STRIDE) return -1;
@@ -820,18 +723,12 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_forest_frontier(const v
     return 0;
 }
 
-// ---- consistency proofs (consistency_plan.hpp; vkmr_hip_forest_consistency_async, vkmr_hip_verify_consistency_async) for a
-// primary or a monitor without a GPU.  The gather here has no stored forest: it builds every level of a queried tree from its
-// leaves and takes the nodes the plan names out of them.
+// ---- consistency proofs (consistency_plan.hpp).  The gather here has no stored forest: it builds every level of a queried tree
+// from its leaves and takes the nodes the plan names out of them.
 
-// The proofs of Q queries (trees[q], old_counts[q]) over the trees of a forest given by its leaves, tree t is
-// digests[offsets[t] .. offsets[t+1]): new_counts_out[q], and the stride cells of peaks_out and rights_out behind q * stride,
-// every cell written.  Returns the status word of vkmr_hip_forest_consistency_async (0: done; nonzero: nothing written), or -1
-// for a missing pointer, a stride outside 1..64 or offsets that decrease.
-__attribute__((visibility("default"))) int vkmr_host_cpu_forest_consistency(const vkmr_digest* digests, const uint64_t* offsets, uint32_t ntrees,
-                                                                             const uint32_t* trees, const uint64_t* old_counts, uint32_t Q,
-                                                                             uint32_t stride, uint64_t* new_counts_out, vkmr_digest* peaks_out,
-                                                                             vkmr_digest* rights_out)
+int vkmr_host_cpu_forest_consistency(const vkmr_digest* digests, const uint64_t* offsets, uint32_t ntrees, const uint32_t* trees,
+                                     const uint64_t* old_counts, uint32_t Q, uint32_t stride, uint64_t* new_counts_out, vkmr_digest* peaks_out,
+                                     vkmr_digest* rights_out)
 {
     if (Q == 0) return 0;
     if (!offsets || !trees || !old_counts || !new_counts_out || !peaks_out || !rights_out || stride == 0 || stride > VKMR_FRONTIER_MAX_STRIDE) return -1;
@@ -873,12 +770,8 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_forest_consistency(cons
     return 0;
 }
 
-// ok[q] = 1 when proof q holds under old_roots[q] and new_roots[q], else 0: vkmr_hip_verify_consistency_async's check, the two
-// walks written out one behind the other.  -1 for a missing pointer or a stride outside 1..64.
-__attribute__((visibility("default"))) int vkmr_host_cpu_verify_consistency(const uint64_t* old_counts, const uint64_t* new_counts,
-                                                                             const vkmr_digest* peaks, const vkmr_digest* rights, uint32_t stride,
-                                                                             uint32_t Q, const vkmr_digest* old_roots, const vkmr_digest* new_roots,
-                                                                             uint32_t* ok)
+int vkmr_host_cpu_verify_consistency(const uint64_t* old_counts, const uint64_t* new_counts, const vkmr_digest* peaks, const vkmr_digest* rights,
+                                     uint32_t stride, uint32_t Q, const vkmr_digest* old_roots, const vkmr_digest* new_roots, uint32_t* ok)
 {
     if (Q == 0) return 0;
     if (!old_counts || !new_counts || !peaks || !rights || !old_roots || !new_roots || !ok || stride == 0 || stride > VKMR_FRONTIER_MAX_STRIDE) return -1;
@@ -911,19 +804,13 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_verify_consistency(cons
     return 0;
 }
 
-// ---- inclusion proofs as of an earlier count (proofs_at_plan.hpp; vkmr_hip_forest_proofs_at_async) for a log without a GPU.
-// As the consistency gather above, there is no stored forest: every level of a tree that has an epoch is built from its leaves
-// as they are NOW, the complete nodes are taken out of them and the old tree's right edge is hashed by the plan's edge_step().
+// ---- inclusion proofs as of an earlier count (proofs_at_plan.hpp).  As the consistency gather above, there is no stored forest:
+// every level of a tree that has an epoch is built from its leaves as they are NOW, the complete nodes are taken out of them and
+// the old tree's right edge is hashed by the plan's edge_step().
 
-// E epochs (epoch_trees[e], epoch_counts[e]) over the trees of a forest given by its leaves, and k queries (epochs[q],
-// indices[q]): edges_out (E x stride), old_roots_out (E), siblings (k x stride) and heights (k), every cell written.  Returns
-// the status word of vkmr_hip_forest_proofs_at_async (0: done; nonzero: nothing written), or -1 for a missing pointer, a stride
-// outside 1..63 or offsets that decrease.
-__attribute__((visibility("default"))) int vkmr_host_cpu_forest_proofs_at(const vkmr_digest* digests, const uint64_t* offsets, uint32_t ntrees,
-                                                                           const uint32_t* epoch_trees, const uint64_t* epoch_counts, uint32_t E,
-                                                                           const uint32_t* epochs, const uint64_t* indices, uint32_t k, uint32_t stride,
-                                                                           vkmr_digest* edges_out, vkmr_digest* old_roots_out, vkmr_digest* siblings,
-                                                                           uint32_t* heights)
+int vkmr_host_cpu_forest_proofs_at(const vkmr_digest* digests, const uint64_t* offsets, uint32_t ntrees, const uint32_t* epoch_trees,
+                                   const uint64_t* epoch_counts, uint32_t E, const uint32_t* epochs, const uint64_t* indices, uint32_t k,
+                                   uint32_t stride, vkmr_digest* edges_out, vkmr_digest* old_roots_out, vkmr_digest* siblings, uint32_t* heights)
 {
     if (E == 0) return 0;
     if (!offsets || !epoch_trees || !epoch_counts || !edges_out || !old_roots_out || stride == 0 || stride > 63) return -1;
@@ -982,17 +869,10 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_forest_proofs_at(const 
     return 0;
 }
 
-// Partial Merkle trees in BIP37 order on the CPU, by the rule of vkmr_hip_forest_merkleblocks_async, walked as the rule is
-// written (the device places everything by csrc/merkleblock_plan.hpp's closed form instead): the same entries, the same eight
-// outputs, info[0..4) = status, B, hashes, flag bytes.  Returns the status: 0 done; bit 0 a tree >= ntrees or an index >= c_t,
-// bit 1 pairs not strictly increasing (then only info[0] is written); bit 2 the hashes exceed hash_capacity or the flag bytes
-// flag_capacity (the per-block arrays and info are written, no hash and no flag is).  -1 for a missing pointer or k == 0, -2
-// when the offsets decrease somewhere (nothing written).  A touched tree's levels are formed once, tree by tree.
-__attribute__((visibility("default"))) int vkmr_host_cpu_forest_merkleblocks(const vkmr_digest* digests, const uint64_t* offsets, uint32_t ntrees,
-                                                                              const uint32_t* trees, const uint64_t* indices, uint32_t k,
-                                                                              uint32_t* block_trees, uint64_t* block_counts, uint64_t* bit_counts,
-                                                                              uint64_t* hash_starts, uint64_t* byte_starts, vkmr_digest* hashes,
-                                                                              uint64_t hash_capacity, uint8_t* flags, uint64_t flag_capacity, uint64_t* info)
+int vkmr_host_cpu_forest_merkleblocks(const vkmr_digest* digests, const uint64_t* offsets, uint32_t ntrees, const uint32_t* trees,
+                                      const uint64_t* indices, uint32_t k, uint32_t* block_trees, uint64_t* block_counts, uint64_t* bit_counts,
+                                      uint64_t* hash_starts, uint64_t* byte_starts, vkmr_digest* hashes, uint64_t hash_capacity, uint8_t* flags,
+                                      uint64_t flag_capacity, uint64_t* info)
 {
     if (k == 0 || !digests || !offsets || !trees || !indices || !block_trees || !block_counts || !bit_counts || !hash_starts || !byte_starts || !info ||
         (!hashes && hash_capacity > 0) || (!flags && flag_capacity > 0))
@@ -1067,17 +947,8 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_forest_merkleblocks(con
     return 0;
 }
 
-// The receiver's side of one partial Merkle tree: Bitcoin Core's CPartialMerkleTree::ExtractMatches (TraverseAndExtract) under
-// this project's height h = max(1, ceil(log2 count)).  `hashes` [nhashes] and the flag bytes [nbytes] are one block of
-// vkmr_hip_forest_merkleblocks_async; on 0 root_out is the root they fold to, matched_idx_out / matched_hash_out (room for
-// nhashes entries each) the matched leaves in ascending order and *nmatched_out their number.  The caller compares the root
-// with the one it trusts.  Refusals, nothing written: -1 a missing pointer, -2 count == 0, -3 more hashes than leaves, -4 fewer
-// flag bits than hashes, -5 a flag or a hash read past the end, -6 not all hashes used, -7 the flags used do not end in the last
-// byte, -8 a right child that exists and equals its left (CVE-2012-2459: [a, b, c, c] has the root of [a, b, c]).  Padding bits
-// are not inspected, as in Core.
-__attribute__((visibility("default"))) int vkmr_host_cpu_merkleblock_extract(uint64_t count, const vkmr_digest* hashes, uint64_t nhashes,
-                                                                              const uint8_t* flag_bytes, uint64_t nbytes, vkmr_digest* root_out,
-                                                                              uint64_t* matched_idx_out, vkmr_digest* matched_hash_out, uint64_t* nmatched_out)
+int vkmr_host_cpu_merkleblock_extract(uint64_t count, const vkmr_digest* hashes, uint64_t nhashes, const uint8_t* flag_bytes, uint64_t nbytes,
+                                      vkmr_digest* root_out, uint64_t* matched_idx_out, vkmr_digest* matched_hash_out, uint64_t* nmatched_out)
 {
     if (!root_out || !matched_idx_out || !matched_hash_out || !nmatched_out || (!hashes && nhashes > 0) || (!flag_bytes && nbytes > 0)) return -1;
     if (count == 0) return -2;
@@ -1127,9 +998,7 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_merkleblock_extract(uin
     return 0;
 }
 
-// ---- sorted trees: order, lower bound, absence proofs (absence_plan.hpp; vkmr_hip_forest_sorted_async and its neighbours) for a
-// party without a GPU.  A forest is its leaves and offsets; one tree is a forest of one (offsets {0, count}).  Each returns -1 for
-// a missing pointer and 1 when the offsets decrease somewhere or end behind `total`; nothing is written then.
+// ---- sorted trees: order, lower bound, absence proofs (absence_plan.hpp)
 
 static int absence_offsets_bad(const uint64_t* offsets, uint32_t ntrees, uint64_t total)
 {
@@ -1138,10 +1007,8 @@ static int absence_offsets_bad(const uint64_t* offsets, uint32_t ntrees, uint64_
     return ntrees > 0 && offsets[ntrees] > total ? 1 : 0;
 }
 
-// first_bad[t] = the lowest i in [1, c_t) with !(leaf[i-1] < leaf[i]), or UINT64_MAX; info: status 0, trees not sorted, trees whose
-// first offence is an equal pair, pairs compared.
-__attribute__((visibility("default"))) int vkmr_host_cpu_forest_sorted(const vkmr_digest* digests, uint64_t total, const uint64_t* offsets,
-                                                                        uint32_t ntrees, uint64_t* first_bad, uint64_t* info)
+int vkmr_host_cpu_forest_sorted(const vkmr_digest* digests, uint64_t total, const uint64_t* offsets, uint32_t ntrees, uint64_t* first_bad,
+                                uint64_t* info)
 {
     if (ntrees == 0) return 0;
     if (!offsets || !first_bad || !info) return -1;
@@ -1164,11 +1031,8 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_forest_sorted(const vkm
     return 0;
 }
 
-// indices[q] = the lower bound of queries[q] in tree trees[q] by the plan's loop, found[q] = 1 when the leaf there is the query;
-// UINT64_MAX and 0 for a tree >= ntrees.
-__attribute__((visibility("default"))) int vkmr_host_cpu_forest_lower_bound(const vkmr_digest* digests, uint64_t total, const uint64_t* offsets,
-                                                                             uint32_t ntrees, const uint32_t* trees, const vkmr_digest* queries,
-                                                                             uint32_t Q, uint64_t* indices, uint32_t* found)
+int vkmr_host_cpu_forest_lower_bound(const vkmr_digest* digests, uint64_t total, const uint64_t* offsets, uint32_t ntrees, const uint32_t* trees,
+                                     const vkmr_digest* queries, uint32_t Q, uint64_t* indices, uint32_t* found)
 {
     if (Q == 0) return 0;
     if (!trees || !queries || !indices || !found || (ntrees > 0 && !offsets)) return -1;
@@ -1187,12 +1051,9 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_forest_lower_bound(cons
     return 0;
 }
 
-// The absence proofs of vkmr_hip_forest_absence_async, with no stored forest: the levels of a tree are built from its leaves, once
-// per tree however many queries name it.  2, and nothing written, when `stride` is below the height of a tree that a query names.
-__attribute__((visibility("default"))) int vkmr_host_cpu_forest_absence(const vkmr_digest* digests, uint64_t total, const uint64_t* offsets,
-                                                                         uint32_t ntrees, const uint32_t* trees, const vkmr_digest* queries, uint32_t Q,
-                                                                         uint32_t stride, uint64_t* indices, vkmr_digest* neighbours,
-                                                                         vkmr_digest* main_row, vkmr_digest* low_row, uint32_t* heights)
+int vkmr_host_cpu_forest_absence(const vkmr_digest* digests, uint64_t total, const uint64_t* offsets, uint32_t ntrees, const uint32_t* trees,
+                                 const vkmr_digest* queries, uint32_t Q, uint32_t stride, uint64_t* indices, vkmr_digest* neighbours,
+                                 vkmr_digest* main_row, vkmr_digest* low_row, uint32_t* heights)
 {
     if (Q == 0) return 0;
     if (!trees || !queries || !indices || !neighbours || !heights || (stride > 0 && (!main_row || !low_row)) || (ntrees > 0 && !offsets)) return -1;
@@ -1234,12 +1095,9 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_forest_absence(const vk
     return 0;
 }
 
-// verdict[q] of vkmr_hip_verify_forest_absence_async: the plan's verdict() over the CPU's node hash.
-__attribute__((visibility("default"))) int vkmr_host_cpu_verify_absence(const vkmr_digest* queries, const uint32_t* trees, const uint64_t* indices,
-                                                                         const vkmr_digest* neighbours, const vkmr_digest* main_row,
-                                                                         const vkmr_digest* low_row, const uint32_t* heights, uint32_t Q, uint32_t stride,
-                                                                         const vkmr_digest* roots, const uint64_t* counts, uint32_t ntrees,
-                                                                         uint32_t* verdict)
+int vkmr_host_cpu_verify_absence(const vkmr_digest* queries, const uint32_t* trees, const uint64_t* indices, const vkmr_digest* neighbours,
+                                 const vkmr_digest* main_row, const vkmr_digest* low_row, const uint32_t* heights, uint32_t Q, uint32_t stride,
+                                 const vkmr_digest* roots, const uint64_t* counts, uint32_t ntrees, uint32_t* verdict)
 {
     if (Q == 0) return 0;
     if (!queries || !trees || !indices || !neighbours || !heights || !verdict || (stride > 0 && (!main_row || !low_row)) ||
@@ -1255,5 +1113,3 @@ __attribute__((visibility("default"))) int vkmr_host_cpu_verify_absence(const vk
     }
     return 0;
 }
-
-}  // extern "C"

@@ -14,15 +14,11 @@
 #include <vector>
 
 #include "hip_sha256d.hpp"
+#include "vkmr_host.h"
 
-extern "C" {
-
-// device: a HIP device index, or -1 for every device ("hip:all").  strings_per_batch: how many strings one map launch
-// takes (the batch pool is sized for it); slice_log2: digests per slice, 0 = chosen from the devices.
-// root_hex: 65 bytes.  seconds: the timed part (first Map to the root on the host).  Returns 0, or -1 on failure.
-__attribute__((visibility("default"))) int vkmr_host_pipeline_packed(int device, const uint32_t* data, uint64_t words, const vkmr_metadata* meta,
-                                                                      uint64_t count, uint64_t strings_per_batch, uint32_t slice_log2,
-                                                                      char* root_hex, double* seconds)
+// The C entry points: include/vkmr_host.h declares them and holds their contracts.
+int vkmr_host_pipeline_packed(int device, const uint32_t* data, uint64_t words, const vkmr_metadata* meta, uint64_t count, uint64_t strings_per_batch,
+                              uint32_t slice_log2, char* root_hex, double* seconds)
 {
     if (!data || !meta || !root_hex || count == 0 || strings_per_batch == 0) return -1;
     vkmr::HipSha256D gpus;
@@ -59,14 +55,8 @@ __attribute__((visibility("default"))) int vkmr_host_pipeline_packed(int device,
     return 0;
 }
 
-// The front end on text in memory: the non-empty lines of text[0,len) -- a line ends at '\n' or at len; '\r' is kept
-// (Input::Get, reference src/vkmr/Inputs.cpp:75-101) -- through the parallel packer, pinned batches, Mappings, Reductions and
-// the combine, exactly as `vkmr hip:<n> < file` runs them, span by span (span_bytes at a time; 0 = the 32 MiB of vkmr_main).
-// device: a HIP device index, or -1 for every device ("hip:all").  root_hex: 65 bytes; all zero-length when the text holds no
-// string (the reference prints no root then).  items / bytes: strings added and their payload bytes.  seconds: from the
-// first span to the root on the host (the reference's stopwatch).  Returns 0, or -1 on failure.
-__attribute__((visibility("default"))) int vkmr_host_pipeline_text(int device, const char* text, uint64_t len, uint64_t span_bytes, char* root_hex,
-                                                                    uint64_t* items, uint64_t* bytes, double* seconds)
+int vkmr_host_pipeline_text(int device, const char* text, uint64_t len, uint64_t span_bytes, char* root_hex, uint64_t* items, uint64_t* bytes,
+                            double* seconds)
 {
     if ((!text && len != 0) || !root_hex) return -1;
     vkmr::HipSha256D gpus;
@@ -103,5 +93,3 @@ __attribute__((visibility("default"))) int vkmr_host_pipeline_text(int device, c
     if (bytes) *bytes = n_bytes;
     return 0;
 }
-
-}  // extern "C"

@@ -3,7 +3,7 @@
 
 #include <cstring>
 
-#include "vkmr_hip.h"
+#include "vkmr_host.h"
 
 namespace vkmr {
 
@@ -29,23 +29,18 @@ GlibcRand::GlibcRand(uint32_t seed)
 
 }  // namespace vkmr
 
-extern "C" {
-
-// First n values of rand() after srand(seed) (test hook).
-__attribute__((visibility("default"))) void vkmr_host_rndm_rand(uint32_t seed, int32_t* out, uint64_t n)
+// The C entry points: include/vkmr_host.h declares them and holds their contracts.
+void vkmr_host_rndm_rand(uint32_t seed, int32_t* out, uint64_t n)
 {
     vkmr::GlibcRand g(seed);
     for (uint64_t i = 0; i < n; ++i) out[i] = (int32_t)g.Next();
 }
 
-// Stateful form: the stream of `rndm seed * maxlen` produced batch after batch (a packed batch
-// addresses at most 2^32 words, so long-string workloads need several).
-__attribute__((visibility("default"))) void* vkmr_host_rndm_open(uint32_t seed) { return new vkmr::GlibcRand(seed); }
-__attribute__((visibility("default"))) void vkmr_host_rndm_close(void* h) { delete static_cast<vkmr::GlibcRand*>(h); }
+void* vkmr_host_rndm_open(uint32_t seed) { return new vkmr::GlibcRand(seed); }
+void vkmr_host_rndm_close(void* h) { delete static_cast<vkmr::GlibcRand*>(h); }
 
-// Next `count` strings of the stream into a fresh packed batch (metadata starts at word 0).
-__attribute__((visibility("default"))) int64_t vkmr_host_rndm_next(void* h, uint64_t count, uint32_t maxlen, uint32_t* data,
-                                                                    uint64_t data_capacity_words, vkmr_metadata* meta, uint64_t* words_used)
+int64_t vkmr_host_rndm_next(void* h, uint64_t count, uint32_t maxlen, uint32_t* data, uint64_t data_capacity_words, vkmr_metadata* meta,
+                            uint64_t* words_used)
 {
     if (!h || maxlen < 2 || !data || !meta) return -1;
     vkmr::GlibcRand& g = *static_cast<vkmr::GlibcRand*>(h);
@@ -65,14 +60,8 @@ __attribute__((visibility("default"))) int64_t vkmr_host_rndm_next(void* h, uint
     return (int64_t)count;
 }
 
-// Generates the strings of `rndm seed count maxlen` directly in the packed batch
-// layout (Batch::Push, reference src/vkmr/Batches.cpp:64-121): string i starts at the
-// word after string i-1, `start` is a word index, bytes past `size` in the last word
-// are zero.  Returns the number of strings written (== count) or -1 when the data
-// buffer is too small; *words_used receives the packed length in words.
-__attribute__((visibility("default"))) int64_t vkmr_host_rndm_pack(uint32_t seed, uint64_t count, uint32_t maxlen,
-                                                                    uint32_t* data, uint64_t data_capacity_words,
-                                                                    vkmr_metadata* meta, uint64_t* words_used)
+int64_t vkmr_host_rndm_pack(uint32_t seed, uint64_t count, uint32_t maxlen, uint32_t* data, uint64_t data_capacity_words, vkmr_metadata* meta,
+                            uint64_t* words_used)
 {
     if (maxlen < 2 || !data || !meta) return -1;
     vkmr::GlibcRand g(seed);
@@ -91,5 +80,3 @@ __attribute__((visibility("default"))) int64_t vkmr_host_rndm_pack(uint32_t seed
     if (words_used) *words_used = w;
     return (int64_t)count;
 }
-
-}  // extern "C"

@@ -1,5 +1,6 @@
 // stream_pack.cpp -- see stream_pack.hpp.
 #include "stream_pack.hpp"
+#include "vkmr_host.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -503,14 +504,9 @@ void PackIndexed(const uint8_t* buf, size_t len, const LineIndex& ix, uint32_t* 
 
 }  // namespace vkmr
 
-extern "C" {
-
-// One-shot form for bindings: packs the whole buffer (final = true).  Returns the
-// number of strings, or -1 when a buffer was too small.
-__attribute__((visibility("default"))) int64_t vkmr_host_pack_lines(const uint8_t* buf, uint64_t len, uint32_t* data,
-                                                                     uint64_t data_capacity_words, vkmr_metadata* meta,
-                                                                     uint64_t meta_capacity, uint64_t* words_used,
-                                                                     uint64_t* bytes_total)
+// The C entry points: include/vkmr_host.h declares them and holds their contracts.
+int64_t vkmr_host_pack_lines(const uint8_t* buf, uint64_t len, uint32_t* data, uint64_t data_capacity_words, vkmr_metadata* meta,
+                             uint64_t meta_capacity, uint64_t* words_used, uint64_t* bytes_total)
 {
     const vkmr::PackResult r = vkmr::PackLines(buf, len, true, data, 0, data_capacity_words, meta, meta_capacity);
     if (r.consumed != len) return -1;
@@ -519,12 +515,8 @@ __attribute__((visibility("default"))) int64_t vkmr_host_pack_lines(const uint8_
     return (int64_t)r.strings;
 }
 
-// The same with the portable (memchr per line) splitter forced, and the line counter of the parallel packer's first
-// pass in both forms: lets the tests hold the AVX2 forms against the portable ones on the same input.
-__attribute__((visibility("default"))) int64_t vkmr_host_pack_lines_portable(const uint8_t* buf, uint64_t len, uint32_t* data,
-                                                                              uint64_t data_capacity_words, vkmr_metadata* meta,
-                                                                              uint64_t meta_capacity, uint64_t* words_used,
-                                                                              uint64_t* bytes_total)
+int64_t vkmr_host_pack_lines_portable(const uint8_t* buf, uint64_t len, uint32_t* data, uint64_t data_capacity_words, vkmr_metadata* meta,
+                                      uint64_t meta_capacity, uint64_t* words_used, uint64_t* bytes_total)
 {
     const vkmr::PackResult r = vkmr::PackLinesPortable(buf, len, true, data, 0, data_capacity_words, meta, meta_capacity);
     if (r.consumed != len) return -1;
@@ -533,19 +525,14 @@ __attribute__((visibility("default"))) int64_t vkmr_host_pack_lines_portable(con
     return (int64_t)r.strings;
 }
 
-// out[0..4] = strings, words, bytes, empties, too_long; which: 0 = the form the packer uses on this CPU, 1 = portable
-__attribute__((visibility("default"))) void vkmr_host_count_lines(const uint8_t* buf, uint64_t len, int which, uint64_t* out)
+void vkmr_host_count_lines(const uint8_t* buf, uint64_t len, int which, uint64_t* out)
 {
     const vkmr::LineCount c = which ? vkmr::CountLinesPortable(buf, len) : vkmr::CountLines(buf, len);
     out[0] = c.strings; out[1] = c.words; out[2] = c.bytes; out[3] = c.empties; out[4] = c.too_long ? 1 : 0;
 }
 
-// The indexed two-pass form on one buffer (every line, the last one terminated or not), placed at data[first_word ...):
-// which as above.  Returns the number of strings, or -1 when a buffer was too small; out[0..3] = words, bytes, empties,
-// lines indexed.
-__attribute__((visibility("default"))) int64_t vkmr_host_pack_indexed(const uint8_t* buf, uint64_t len, uint32_t* data, uint64_t first_word,
-                                                                       uint64_t data_capacity_words, vkmr_metadata* meta, uint64_t meta_capacity,
-                                                                       int which, uint64_t* out)
+int64_t vkmr_host_pack_indexed(const uint8_t* buf, uint64_t len, uint32_t* data, uint64_t first_word, uint64_t data_capacity_words,
+                               vkmr_metadata* meta, uint64_t meta_capacity, int which, uint64_t* out)
 {
     if (len >= 0xFFFFFF00ull) return -1;
     vkmr::LineIndex ix;
@@ -557,23 +544,17 @@ __attribute__((visibility("default"))) int64_t vkmr_host_pack_indexed(const uint
     return (int64_t)c.strings;
 }
 
-// CopyAndCountLines on one buffer: out[0..1] = newlines, empties; which as above.
-__attribute__((visibility("default"))) void vkmr_host_copy_and_count(const uint8_t* buf, uint64_t len, uint8_t* dst, int after_newline, int which, uint64_t* out)
+void vkmr_host_copy_and_count(const uint8_t* buf, uint64_t len, uint8_t* dst, int after_newline, int which, uint64_t* out)
 {
     const vkmr::TextCount c = which ? vkmr::CopyAndCountLinesPortable(buf, len, dst, after_newline != 0) : vkmr::CopyAndCountLines(buf, len, dst, after_newline != 0);
     out[0] = c.newlines;
     out[1] = c.empties;
 }
 
-// A prefix split with capacity limits and `final` unset, as the stream processor calls it: out[0..4] = consumed, strings,
-// words, bytes, empties; which as above.
-__attribute__((visibility("default"))) void vkmr_host_pack_prefix(const uint8_t* buf, uint64_t len, int final, uint32_t* data, uint64_t first_word,
-                                                                  uint64_t data_capacity_words, vkmr_metadata* meta, uint64_t meta_capacity,
-                                                                  int which, uint64_t* out)
+void vkmr_host_pack_prefix(const uint8_t* buf, uint64_t len, int final, uint32_t* data, uint64_t first_word, uint64_t data_capacity_words,
+                           vkmr_metadata* meta, uint64_t meta_capacity, int which, uint64_t* out)
 {
     const vkmr::PackResult r = which ? vkmr::PackLinesPortable(buf, len, final != 0, data, first_word, data_capacity_words, meta, meta_capacity)
                                      : vkmr::PackLines(buf, len, final != 0, data, first_word, data_capacity_words, meta, meta_capacity);
     out[0] = r.consumed; out[1] = r.strings; out[2] = r.words; out[3] = r.bytes; out[4] = r.empties;
 }
-
-}  // extern "C"

@@ -666,9 +666,9 @@ class HipDevice:
         """Scratch of an audit with room for `capacity` listed nodes: 0 for capacity 0; a tree: (count, 1, capacity)."""
         return self.lib.vkmr_hip_audit_scratch_bytes(total, ntrees, capacity)
 
-    # The two wrappers below are asynchronous like every *_async wrapper above.  They do not carry that suffix because the
-    # *_async wrappers of this class are a closed list, recorded call by call in tests/golden/engine_calls.json
-    # (tests/test_engine_calls.py); tests/test_audit_abi.py pins what these two hand to the ABI in the same way.
+    # The *_enqueue wrappers, from here on, are asynchronous like every *_async wrapper above.  They do not carry that suffix
+    # because the *_async wrappers of this class are a closed list, recorded call by call in tests/golden/engine_calls.json.
+    # tests/test_engine_calls.py pins both families: those against the record, these against include/vkmr_hip.h.
     def forest_audit_enqueue(self, digests_buf, forest_buf, roots_buf, total, offsets_buf, ntrees, max_count, scratch_buf, masks_buf, trees_buf,
                              levels_buf, nodes_buf, capacity, info_buf, stream=None):
         """masks_buf[t] (uint64) bit l - 1 = level l of tree t holds a node that is not hash_pair of its two stored children;
