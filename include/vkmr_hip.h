@@ -1238,7 +1238,7 @@ VKMR_API vkmr_status vkmr_hip_tree_merkleblock_async(int dev, vkmr_stream s, con
  *                     not to be used), [1] trees not sorted, [2] those whose first offence is an EQUAL pair, [3] pairs compared
  * Launches: two memsets, the scan (a lane per cell; none below two cells) and a lane per tree.  ntrees == 0 does nothing.  The
  * one-tree twin takes the leaves as cells [0, count) of digests_dev; first_bad_dev is then one uint64_t; count == 0 is fine.
- * This pass is what will test a sort of the leaves on the device; there is none yet.
+ * This pass is what tests vkmr_hip_forest_sort_leaves_async below.
  */
 VKMR_API vkmr_status vkmr_hip_forest_sorted_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, uint64_t total,
                                                   const uint64_t* offsets_dev, uint32_t ntrees, uint64_t* first_bad_dev, uint64_t* info_dev);
@@ -1315,6 +1315,48 @@ VKMR_API vkmr_status vkmr_hip_verify_absence_async(int dev, vkmr_stream s, const
                                                    const vkmr_digest* neighbours_dev, const vkmr_digest* main_dev, const vkmr_digest* low_dev,
                                                    uint32_t Q, uint32_t height, const vkmr_digest* root_dev, uint64_t count,
                                                    uint32_t* verdict_dev);
+
+/*
+ * SORT THE LEAVES of a forest, tree by tree, on the device: what makes a sorted tree out of a set of digests without a trip
+ * through the host.  A stable segmented sort of 32-byte digests: for every tree t the leaves at cells [offsets[t], offsets[t+1])
+ * of digests_in_dev are written to the SAME cells of digests_out_dev in increasing order -- the order above (word 0 first, every
+ * word unsigned) --, equal digests in their input order.  total, offsets_dev, ntrees, max_count as in vkmr_hip_reduce_forest_async.
+ *   order_out_dev[j]  for offsets[0] <= j < offsets[ntrees]: the flat cell of digests_in_dev that now lies at cell j of
+ *                     digests_out_dev (uint32; `total` cells; may be NULL).  order_out_dev + offsets[0] is what
+ *                     vkmr_hip_gather_digests_async takes, so that a payload (values, string numbers) follows the leaves.
+ *   info_dev          4 uint64_t, always written when ntrees > 0: [0] status, [1] n, the leaves sorted (0 with status bit 0),
+ *                     [2] m, the leaves that tie with a neighbour on the sort key, [3] the leaves equal in all 32 bytes to an
+ *                     earlier leaf of their tree (0 with a nonzero status).  A tree with [3] > 0 cannot be strictly increasing;
+ *                     the call sorts it all the same and says so.
+ * Cells outside [offsets[0], offsets[ntrees]) of both outputs are never touched.  Status bits, checked on the device before
+ * anything is written, as the forest build does: bit 0 the offsets decrease somewhere or offsets[ntrees] > total; bit 1 some
+ * tree holds more than max_count leaves; bit 2 m > VKMR_LEAFSORT_MAX_TIES (csrc/leafsort_plan.hpp; [2] still holds m).  With a
+ * nonzero status no cell of digests_out_dev or order_out_dev is written.
+ * HOW (csrc/leafsort_plan.hpp): one stable LSD radix sort, csrc/sort_plan.hpp's passes of 8 bits, of the 64-bit keys
+ *   (tree << P) | (the digest's first 64 bits >> (64 - P)),  P = min(64 - bit_length(ntrees - 1), 2 * bit_length(max_count) + 8)
+ * over `total` elements -- element i is cell offsets[0] + i, the elements behind the last leaf carry an all-ones sentinel --, so
+ * ceil((bit_length(ntrees - 1) + P) / 8) <= 8 passes; then the few leaves whose key equals a neighbour's are placed inside their
+ * run of equal keys by all 256 bits.  That last step costs at most MAX_TIES^2 compares whatever the input: a crafted batch with
+ * more ties is refused (bit 2) and goes through vkmr_host_cpu_forest_sort_leaves, which has no limit.  Among hashed leaves about
+ * n / (512 * max_count) tie.
+ *   scratch_dev  vkmr_hip_sort_leaves_scratch_bytes(total) bytes of device memory, 16-byte aligned: about 29.3 bytes a cell (24 for
+ *                the ping-pong keys and positions, 4 for dest, the rest histograms); 0 for total == 0, when it may be NULL
+ * Launches, all on the caller's stream: two memsets, the check, the keys, three per pass, the ties, the place, the emit.  They
+ * depend on (total, ntrees, max_count) alone; no allocation, no host synchronisation, no host read of device data; no kernel
+ * waits for another workgroup; atomics only count.  ntrees == 0 does nothing.  total == 0 with ntrees > 0 writes n = 0 (and the
+ * status of the offsets).  Refused on the host (VKMR_ERR_INVALID), before any HIP call: a NULL pointer that is needed, total >=
+ * 2^32 (positions are uint32), scratch_dev not 16-byte aligned, the `total` cells of digests_out_dev overlapping those of
+ * digests_in_dev or the scratch.
+ * The one-tree twin sorts cells [0, count): total = max_count = count, no offsets, status bit 2 alone; order_out_dev may be NULL.
+ * vkmr_host_cpu_forest_sort_leaves / vkmr_host_cpu_tree_sort_leaves (libvkmr_host.so) are the CPU's, without the tie limit.
+ */
+VKMR_API size_t vkmr_hip_sort_leaves_scratch_bytes(uint64_t total);
+VKMR_API vkmr_status vkmr_hip_forest_sort_leaves_async(int dev, vkmr_stream s, const vkmr_digest* digests_in_dev, uint64_t total,
+                                                       const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count, void* scratch_dev,
+                                                       vkmr_digest* digests_out_dev, uint32_t* order_out_dev, uint64_t* info_dev);
+VKMR_API vkmr_status vkmr_hip_tree_sort_leaves_async(int dev, vkmr_stream s, const vkmr_digest* digests_in_dev, uint64_t count,
+                                                     void* scratch_dev, vkmr_digest* digests_out_dev, uint32_t* order_out_dev,
+                                                     uint64_t* info_dev);
 
 /*
  * COMBINE: duplicate-last Merkle root over n >= 1 slice roots given in slice order, always

@@ -247,6 +247,21 @@ VKMR_API int vkmr_host_cpu_verify_absence(const vkmr_digest* queries, const uint
                                           const vkmr_digest* main_row, const vkmr_digest* low_row, const uint32_t* heights, uint32_t Q,
                                           uint32_t stride, const vkmr_digest* roots, const uint64_t* counts, uint32_t ntrees, uint32_t* verdict);
 
+/* ---- the leaves of a forest sorted tree by tree, by the rule of vkmr_hip_forest_sort_leaves_async ---- */
+
+/* For every tree t the leaves at cells [offsets[t], offsets[t+1]) of digests_in, in increasing digest order (equal digests in input
+ * order: std::stable_sort under absence_plan.hpp's less), at the same cells of digests_out; order_out[j] (may be NULL) the flat cell
+ * of digests_in that lies at cell j.  info[0..4) as the device writes it: status (bit 0 the offsets, bit 1 a tree above max_count;
+ * nothing else is written then), n, m counted with leafsort_plan.hpp's key, the leaves equal to an earlier leaf of their tree.  The
+ * one difference: there is no tie limit, bit 2 is never set and the leaves are always sorted.  -1 for a missing pointer or total >=
+ * 2^32; ntrees == 0 does nothing. */
+VKMR_API int vkmr_host_cpu_forest_sort_leaves(const vkmr_digest* digests_in, uint64_t total, const uint64_t* offsets, uint32_t ntrees,
+                                              uint64_t max_count, vkmr_digest* digests_out, uint32_t* order_out, uint64_t* info);
+
+/* The same for one tree over digests_in[0 .. count): total = max_count = count. */
+VKMR_API int vkmr_host_cpu_tree_sort_leaves(const vkmr_digest* digests_in, uint64_t count, vkmr_digest* digests_out, uint32_t* order_out,
+                                            uint64_t* info);
+
 /* ---- packing (stream_pack.cpp; in libvkmr_host.so and libvkmr_pipeline.so) ---- */
 
 /* One-shot form for bindings: packs the whole buffer (final = true).  Returns the

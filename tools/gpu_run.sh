@@ -38,6 +38,9 @@
 #   absence [args]         tools/absence_timing.py: sorted trees (2^26 sorted leaves as 2^15 trees of 2 048 and as one tree; Q = 2^10, 2^16, 2^20, half
 #                          present): the sorted pass beside torch's sum over as many bytes, the lower bound, the gather, and the verifier beside
 #                          vkmr_hip_verify_forest_proofs_async over 2 Q plain proofs (one JSON line)
+#   leafsort [args]        tools/leafsort_timing.py: the leaves sorted on the device (2^26 random leaves as 2^15 trees of 2 048 and as one tree): the
+#                          sort alone, the sort and the stored build, the build alone, the worst case of the tie step, beside the host route
+#                          (download, vk.sort_digests, upload) and torch.sort of as many int64 keys (one JSON line)
 #   forest_repack [args]   tools/forest_repack_timing.py: the oldest trees of a stored forest dropped and the rest (or all) copied into an
 #                          empty forest, beside the stored build over the same leaves (one JSON line)
 #   cumask                 tools/cu_mask_probe.py: where CU-mask bits land, map/reduce on half the CUs with and without neighbours
@@ -234,6 +237,11 @@ absence)
   timeout -k 10 500 python3 tools/absence_timing.py "$@" --out $OUT/absence_timing.json > /dev/null 2> $OUT/absence_timing.err && echo "absence_timing ok" &&
   cat $OUT/absence_timing.json
   echo "absence rc=$?"
+  ;;
+leafsort)
+  timeout -k 10 900 python3 tools/leafsort_timing.py "$@" --out $OUT/leafsort_timing.json > /dev/null 2> $OUT/leafsort_timing.err && echo "leafsort_timing ok" &&
+  cat $OUT/leafsort_timing.json
+  echo "leafsort rc=$?"
   ;;
 forest_repack)
   timeout -k 10 500 python3 tools/forest_repack_timing.py "$@" --out $OUT/forest_repack_timing.json > /dev/null 2> $OUT/forest_repack_timing.err && echo "forest_repack_timing ok" &&

@@ -11,6 +11,7 @@
 #include "../audit_plan.hpp"   // forest_plan.hpp, tree_plan.hpp: where the stored levels lie
 #include "../consistency_plan.hpp"
 #include "../frontier_plan.hpp"
+#include "../leafsort_plan.hpp"
 #include "../merkle_math.hpp"
 #include "../proofs_at_plan.hpp"
 #include "cpu_sha256d.hpp"
@@ -1112,4 +1113,47 @@ int vkmr_host_cpu_verify_absence(const vkmr_digest* queries, const uint32_t* tre
                                            [](const uint32_t* a, const uint32_t* b, uint32_t* out) { vkmr::cpu_sha256d_pair(a, b, out); });
     }
     return 0;
+}
+
+// ---- the leaves of a forest sorted tree by tree (leafsort_plan.hpp)
+
+int vkmr_host_cpu_forest_sort_leaves(const vkmr_digest* digests_in, uint64_t total, const uint64_t* offsets, uint32_t ntrees, uint64_t max_count,
+                                     vkmr_digest* digests_out, uint32_t* order_out, uint64_t* info)
+{
+    if (ntrees == 0) return 0;
+    if (!offsets || !info || total >= vkmr_leafsort::MAX_TOTAL) return -1;
+    uint64_t status = absence_offsets_bad(offsets, ntrees, total) ? VKMR_LEAFSORT_BAD_OFFSETS : 0ull;
+    for (uint32_t t = 0; t < ntrees; ++t)
+        if (offsets[t + 1] >= offsets[t] && offsets[t + 1] - offsets[t] > max_count) status |= VKMR_LEAFSORT_ABOVE_MAX_COUNT;
+    const uint64_t lo = offsets[0], n = (status & VKMR_LEAFSORT_BAD_OFFSETS) ? 0ull : offsets[ntrees] - lo;
+    if (!status && n > 0 && (!digests_in || !digests_out)) return -1;
+    info[0] = status;
+    info[1] = n;
+    info[2] = info[3] = 0;
+    if (status) return 0;
+    const vkmr_leafsort::Shape shape = vkmr_leafsort::shape(ntrees, max_count);
+    std::vector<uint32_t> order((size_t)n);
+    for (uint64_t i = 0; i < n; ++i) order[(size_t)i] = (uint32_t)(lo + i);
+    std::vector<uint64_t> keys((size_t)n);
+    for (uint32_t t = 0; t < ntrees; ++t) {
+        const auto first = order.begin() + (ptrdiff_t)(offsets[t] - lo), last = order.begin() + (ptrdiff_t)(offsets[t + 1] - lo);
+        std::stable_sort(first, last, [&](uint32_t x, uint32_t y) { return vkmr_absence::less(digests_in[x].data, digests_in[y].data); });
+        for (auto it = first; it != last; ++it) {
+            const uint32_t* w = digests_in[*it].data;
+            keys[(size_t)(it - order.begin())] = vkmr_leafsort::key(t, w[0], w[1], shape.P);
+            if (it != first && vkmr_absence::equal(w, digests_in[*(it - 1)].data)) ++info[3];
+        }
+    }
+    for (uint64_t j = 0; j < n; ++j) {
+        if ((j > 0 && keys[(size_t)j - 1] == keys[(size_t)j]) || (j + 1 < n && keys[(size_t)j + 1] == keys[(size_t)j])) ++info[2];
+        digests_out[lo + j] = digests_in[order[(size_t)j]];
+        if (order_out) order_out[lo + j] = order[(size_t)j];
+    }
+    return 0;
+}
+
+int vkmr_host_cpu_tree_sort_leaves(const vkmr_digest* digests_in, uint64_t count, vkmr_digest* digests_out, uint32_t* order_out, uint64_t* info)
+{
+    const uint64_t offsets[2] = {0, count};
+    return vkmr_host_cpu_forest_sort_leaves(digests_in, count, offsets, 1, count, digests_out, order_out, info);
 }

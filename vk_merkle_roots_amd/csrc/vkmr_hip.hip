@@ -40,6 +40,10 @@
 //                                              pair out of order per tree, the lower bound of a digest, the two neighbours and their
 //                                              compact pair of proofs gathered (no hash), and the verdict absent / present, one lane
 //                                              per proof through one hash_pair (rules: absence_plan.hpp)
+//   leafsort_kernels.hpp  *_leafsort_keys_kernel, *_leafsort_ties_kernel, *_leafsort_place_kernel, *_leafsort_emit_kernel   the leaves of a
+//                                              forest sorted tree by tree in digest order: sort_kernels.hpp's radix passes over
+//                                              (tree, digest prefix) keys, then the few ties placed by all 256 bits; no hash
+//                                              (the key, the sentinel and the tie limit: leafsort_plan.hpp)
 //   forest_tree_kernels.hpp  forest_proofs_kernel          proofs gathered from the stored forest, one lane per (query, level)
 //                            verify_forest_proofs_kernel   batch verification of proofs of unequal height, one lane per proof
 //                            forest_update_*_kernel        leaf updates of the stored forest: tree_update_*'s bodies, a tree per entry
@@ -73,6 +77,7 @@
 //   audit_plan.hpp      the ballot words of an audit's levels, the nodes it checks and the scratch layout
 //   merkleblock_plan.hpp  what a BIP37 walk appends between two matched leaves, in closed form; the three size bounds, the scratch layout
 //   absence_plan.hpp    the order on digests, the lower bound's loop, the cells of an absence proof and the verdict of its check
+//   leafsort_plan.hpp   the leaf sort's key and passes, its elements and sentinel, what a tie is, the tie limit and the scratch layout
 //
 // Host side: plain launches on the caller's stream, each through launch() and so each checked; every argument refusal
 // through refuse(__func__, why); no allocation, no sync inside the *_async entry points.
@@ -112,6 +117,7 @@ using vkmr_dev::Node;
 #include "proofs_at_kernels.hpp"
 #include "merkleblock_kernels.hpp"
 #include "absence_kernels.hpp"
+#include "leafsort_kernels.hpp"
 
 // ============================================================================
 // C ABI
@@ -2075,6 +2081,89 @@ vkmr_status vkmr_hip_gather_digests_async(int dev, vkmr_stream s, const vkmr_dig
     if (!src_dev || !order_dev || !dst_dev) return refuse(__func__, "null pointer");
     VKMR_TRY(hipSetDevice(dev));
     return launch(gather_digests_kernel, grid_of(n), dim3(256), S(s), nodes(src_dev), order_dev, n, nodes(dst_dev));
+}
+
+// ---- the leaves of a forest sorted tree by tree (leafsort_kernels.hpp, leafsort_plan.hpp) ------------------------------------
+
+static_assert(VKMR_LEAFSORT_HEADER_WORDS == 4u, "status, m, repeats, the tie refusal");
+
+size_t vkmr_hip_sort_leaves_scratch_bytes(uint64_t total) { return vkmr_leafsort::scratch_bytes(total); }
+
+// [a, a + na) and [b, b + nb) share a byte.
+static inline bool bytes_overlap(const void* a, uint64_t na, const void* b, uint64_t nb)
+{
+    const uintptr_t pa = reinterpret_cast<uintptr_t>(a), pb = reinterpret_cast<uintptr_t>(b);
+    return na && nb && pa < pb + nb && pb < pa + na;
+}
+
+// The launches of both leaf sorts, all on the caller's stream: two memsets, the check (a forest's), the keys, three launches per
+// pass, the ties, the place, the emit.  They depend on (total, ntrees, max_count) alone.  offsets_dev null: one tree over
+// [0, total), nothing to check.
+static vkmr_status leafsort_launch(const char* who, int dev, vkmr_stream s, const vkmr_digest* in_dev, uint64_t total, const uint64_t* offsets_dev,
+                                   uint32_t ntrees, uint64_t max_count, void* scratch_dev, vkmr_digest* out_dev, uint32_t* order_out_dev,
+                                   uint64_t* info_dev)
+{
+    if (total >= vkmr_leafsort::MAX_TOTAL) return refuse(who, "2^32 leaves or more: positions are 32-bit");
+    if (total == 0) {   // no cell: nothing to sort, and the offsets are still checked
+        VKMR_TRY(hipSetDevice(dev));
+        VKMR_TRY(hipMemsetAsync(info_dev, 0, 4 * sizeof(uint64_t), S(s)));
+        if (!offsets_dev) return VKMR_OK;
+        return launch(forest_check_kernel, grid_of(ntrees), dim3(256), S(s), offsets_dev, ntrees, total, max_count, reinterpret_cast<uint32_t*>(info_dev));
+    }
+    if (!in_dev || !scratch_dev || !out_dev) return refuse(who, "null pointer");
+    if (reinterpret_cast<uintptr_t>(scratch_dev) & 15u) return refuse(who, "scratch must be 16-byte aligned");
+    const vkmr_leafsort::Layout L = vkmr_leafsort::layout(total);
+    if (bytes_overlap(out_dev, 32u * total, in_dev, 32u * total) || bytes_overlap(out_dev, 32u * total, scratch_dev, L.bytes))
+        return refuse(who, "the sorted leaves must not overlap the input or the scratch");
+    const SortScratch sc(scratch_dev, L.sort);
+    char* at = static_cast<char*>(scratch_dev);
+    uint32_t* dest = reinterpret_cast<uint32_t*>(at + L.dest);
+    uint64_t* hdr = reinterpret_cast<uint64_t*>(at + L.hdr);
+    unsigned long long* counters = reinterpret_cast<unsigned long long*>(hdr);   // the same words, as atomicAdd takes them
+    const vkmr_leafsort::Shape shape = vkmr_leafsort::shape(ntrees, max_count);
+    const uint32_t passes = vkmr_leafsort::passes(shape), k = (uint32_t)total;
+    const dim3 lanes = grid_of(k), tiles((uint32_t)L.sort.G), block(VKMR_SORT_THREADS);
+    const Node *in = nodes(in_dev);
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_TRY(hipMemsetAsync(info_dev, 0, 4 * sizeof(uint64_t), S(s)));
+    VKMR_TRY(hipMemsetAsync(hdr, 0, VKMR_LEAFSORT_HEADER_WORDS * sizeof(uint64_t), S(s)));
+    if (offsets_dev) {
+        VKMR_CHECK(launch(forest_check_kernel, grid_of(ntrees), dim3(256), S(s), offsets_dev, ntrees, total, max_count, reinterpret_cast<uint32_t*>(hdr)));
+        VKMR_CHECK(launch(forest_leafsort_keys_kernel, lanes, dim3(256), S(s), offsets_dev, ntrees, in, k, shape.P, hdr, sc.key[0], sc.val[0]));
+    } else {
+        VKMR_CHECK(launch(tree_leafsort_keys_kernel, lanes, dim3(256), S(s), total, in, k, shape.P, hdr, sc.key[0], sc.val[0]));
+    }
+    for (uint32_t p = 0; p < passes; ++p) {   // pass p from buffer p & 1 into the other, which the previous launches are done with
+        const uint32_t from = vkmr_sort::pass_input(p), to = from ^ 1u;
+        VKMR_CHECK(launch(sort_histogram_kernel, tiles, block, S(s), sc.key[from], k, p, L.sort.G, sc.hist));
+        VKMR_CHECK(launch(sort_scan_kernel, dim3(VKMR_SORT_BINS), block, S(s), sc.hist, L.sort.G, sc.totals));
+        VKMR_CHECK(launch(sort_scatter_kernel, tiles, block, S(s), sc.key[from], sc.val[from], k, p, L.sort.G, sc.hist, sc.totals, sc.key[to], sc.val[to]));
+    }
+    const uint32_t r = vkmr_leafsort::result_buffer(shape);
+    if (offsets_dev) {
+        VKMR_CHECK(launch(forest_leafsort_ties_kernel, lanes, dim3(256), S(s), offsets_dev, ntrees, sc.key[r], counters));
+        VKMR_CHECK(launch(forest_leafsort_place_kernel, lanes, dim3(256), S(s), offsets_dev, ntrees, in, sc.key[r], sc.val[r], counters, dest));
+        return launch(forest_leafsort_emit_kernel, lanes, dim3(256), S(s), offsets_dev, ntrees, in, sc.val[r], dest, hdr, nodes(out_dev), order_out_dev, info_dev);
+    }
+    VKMR_CHECK(launch(tree_leafsort_ties_kernel, lanes, dim3(256), S(s), total, sc.key[r], counters));
+    VKMR_CHECK(launch(tree_leafsort_place_kernel, lanes, dim3(256), S(s), total, in, sc.key[r], sc.val[r], counters, dest));
+    return launch(tree_leafsort_emit_kernel, lanes, dim3(256), S(s), total, in, sc.val[r], dest, hdr, nodes(out_dev), order_out_dev, info_dev);
+}
+
+vkmr_status vkmr_hip_forest_sort_leaves_async(int dev, vkmr_stream s, const vkmr_digest* digests_in_dev, uint64_t total, const uint64_t* offsets_dev,
+                                              uint32_t ntrees, uint64_t max_count, void* scratch_dev, vkmr_digest* digests_out_dev,
+                                              uint32_t* order_out_dev, uint64_t* info_dev)
+{
+    if (ntrees == 0) return VKMR_OK;
+    if (!offsets_dev || !info_dev) return refuse(__func__, "null pointer");
+    return leafsort_launch(__func__, dev, s, digests_in_dev, total, offsets_dev, ntrees, max_count, scratch_dev, digests_out_dev, order_out_dev, info_dev);
+}
+
+vkmr_status vkmr_hip_tree_sort_leaves_async(int dev, vkmr_stream s, const vkmr_digest* digests_in_dev, uint64_t count, void* scratch_dev,
+                                            vkmr_digest* digests_out_dev, uint32_t* order_out_dev, uint64_t* info_dev)
+{
+    if (!info_dev) return refuse(__func__, "null pointer");
+    return leafsort_launch(__func__, dev, s, digests_in_dev, count, nullptr, 1u, count, scratch_dev, digests_out_dev, order_out_dev, info_dev);
 }
 
 // ---- the leaves that differ between two stored forests or trees (diff_kernels.hpp, diff_plan.hpp) ----------------------------

@@ -866,6 +866,98 @@ class HipDevice:
         AbsenceProofs -- against roots [ntrees, 8] and counts [ntrees]; verified on the device."""
         return AbsenceProofs(trees, queries, indices, pred, succ, main, low, heights).verify(self, roots, counts)
 
+    # -- the leaves of a forest sorted on the device, tree by tree, in the order an absence proof rests on -------------------------
+    def sort_leaves_scratch_bytes(self, total):
+        return self.lib.vkmr_hip_sort_leaves_scratch_bytes(total)
+
+    def forest_sort_leaves_enqueue(self, digests_in_buf, total, offsets_buf, ntrees, max_count, scratch_buf, digests_out_buf, order_out_buf, info_buf,
+                                   stream=None):
+        """For every tree t the leaves at cells [offsets[t], offsets[t+1]) of digests_in_buf, in increasing digest order (word 0
+        first, unsigned; equal digests in input order), at the same cells of digests_out_buf; order_out_buf[j] (uint32, may be
+        None) the flat cell of digests_in_buf that lies at cell j; info_buf: 4 uint64 (status, leaves sorted, leaves tying on the
+        sort key, leaves equal to an earlier one).  All in device memory; scratch_buf: sort_leaves_scratch_bytes(total), 16-byte
+        aligned.  A nonzero status writes no cell.  include/vkmr_hip.h."""
+        self._call("vkmr_hip_forest_sort_leaves_async", digests_in_buf, total, offsets_buf, ntrees, max_count, scratch_buf, digests_out_buf,
+                   order_out_buf, info_buf, stream=stream)
+
+    def tree_sort_leaves_enqueue(self, digests_in_buf, count, scratch_buf, digests_out_buf, order_out_buf, info_buf, stream=None):
+        """forest_sort_leaves_enqueue for ONE tree over digests_in_buf[0 .. count)."""
+        self._call("vkmr_hip_tree_sort_leaves_async", digests_in_buf, count, scratch_buf, digests_out_buf, order_out_buf, info_buf, stream=stream)
+
+    def _sort_leaves_of_buffer(self, tmp, d_in, total, offsets, ntrees, max_count, what):
+        """The leaves of the trees at `offsets` (ntrees >= 1) over the `total` cells of d_in, sorted into a new buffer of as many
+        cells in the scope `tmp`: (sorted buffer, order buffer, info [4] uint64).  RuntimeError when the device refuses; nothing
+        falls back to the host."""
+        d_out, d_order, d_info = tmp.alloc(32 * total), tmp.alloc(4 * total), tmp.alloc(32)
+        d_scratch = tmp.alloc(self.sort_leaves_scratch_bytes(total))
+        self.forest_sort_leaves_enqueue(d_in, total, tmp.upload(offsets), ntrees, max_count, d_scratch, d_out, d_order, d_info)
+        info = self.download(d_info, 32, dtype=np.uint64)
+        tmp.release(d_scratch)
+        d_scratch.free()
+        status = int(info[0])
+        if status & 4:
+            raise RuntimeError(f"{what}: {int(info[2])} leaves tie on the sort key, above the limit of {LEAFSORT_MAX_TIES} "
+                               f"(status {status}: {leafsort_status_text(status)}); such a batch is sorted on the host: vk.sort_digests")
+        if status:
+            raise RuntimeError(f"{what}: the device refused the forest (status {status}: {leafsort_status_text(status)})")
+        return d_out, d_order, info
+
+    def sort_leaves(self, digests, counts, max_count=None):
+        """(sorted [n, 8] uint32, order [n] uint32, info [4] uint64): every tree's leaves (`digests` [n, 8], tree t the next
+        counts[t] of them) sorted on the device in the order an absence proof rests on -- word 0 first, every word unsigned,
+        equal digests in input order -- (vkmr_hip_forest_sort_leaves_async); sorted[j] = digests[order[j]].  info: status 0, n,
+        the leaves that tied on the sort key, the leaves equal to an earlier leaf of their tree (a tree with one of those cannot
+        be strictly increasing).  max_count: an upper bound on every count (the largest count when None).  ValueError when the
+        counts do not add up; RuntimeError when the device refuses -- a count above max_count, or more ties than the sort takes,
+        which names vk.sort_digests; it never falls back to the host by itself."""
+        digests = _host(digests, np.uint32, -1, 8)
+        total = int(digests.shape[0])
+        offsets, ntrees = _checked_offsets(counts, total, "sort_leaves")
+        if ntrees == 0 or total == 0:
+            return np.zeros((0, 8), dtype=np.uint32), np.zeros(0, dtype=np.uint32), np.array([0, 0, 0, 0], dtype=np.uint64)
+        if max_count is None:
+            max_count = max(1, int(np.diff(offsets).max()))
+        with self.scope() as tmp:
+            d_out, d_order, info = self._sort_leaves_of_buffer(tmp, tmp.upload(digests), total, offsets, ntrees, max_count, "sort_leaves")
+            return self.download(d_out, 32 * total).reshape(total, 8), self.download(d_order, 4 * total), info
+
+    def _build_sorted_forest_of_buffer(self, tmp, d_in, total, counts, max_count, what, **build):
+        """(MerkleForest, order [n] uint32) over the leaves in the first cells of d_in, sorted on the device: the sorted buffer
+        is the forest's level 0."""
+        reserve_leaves = int(build.get("reserve_leaves", 0))
+        offsets, ntrees = _checked_offsets(counts, total, what, slack=reserve_leaves)
+        if ntrees == 0:
+            raise ValueError(f"{what}: no tree")
+        if max_count is None:
+            max_count = max(1, int(np.diff(offsets).max()))
+        n = int(offsets[-1])
+        if total == 0:
+            d_out, order = None, np.zeros(0, dtype=np.uint32)
+        else:
+            d_out, d_order, _ = self._sort_leaves_of_buffer(tmp, d_in, total, offsets, ntrees, max_count, what)
+            order = self.download(d_order, 4 * n)
+        forest = self._build_forest_of_buffer(d_out, total, counts, max_count, what, owned=[d_out] if d_out else [], **build)
+        if d_out:
+            tmp.release(d_out)
+        return forest, order
+
+    def build_sorted_forest(self, digests, counts, max_count=None, mutated=False, reserve_trees=0, reserve_leaves=0):
+        """(MerkleForest, order): build_forest over every tree's leaves SORTED on the device (sort_leaves' order), so that
+        MerkleForest.is_sorted holds when no tree has a repeated leaf and MerkleForest.absence proves under its roots.  The
+        leaves are uploaded once, sorted into the buffer that becomes the forest's level 0 and never come back; order [n] uint32
+        says which input digest lies at each cell (leaf j of the forest is digests[order[j]]), for a payload to follow.  Same
+        keywords and ValueErrors as build_forest; RuntimeError as sort_leaves."""
+        digests = _host(digests, np.uint32, -1, 8)
+        reserve_trees, reserve_leaves = _reserve("build_sorted_forest", reserve_trees, reserve_leaves, max_count)
+        used, total = int(digests.shape[0]), int(digests.shape[0]) + reserve_leaves
+        with self.scope() as tmp:
+            d_in = tmp.alloc(32 * total) if total else None
+            if used:
+                self._call("vkmr_hip_memcpy_h2d_async", d_in, digests.ctypes.data, digests.nbytes)
+                self.sync()
+            return self._build_sorted_forest_of_buffer(tmp, d_in, total, counts, max_count, "build_sorted_forest", mutated=mutated,
+                                                       reserve_trees=reserve_trees, reserve_leaves=reserve_leaves)
+
     def reduce_scratch(self, count, levels_variant=False):
         fn = self.lib.vkmr_hip_reduce_levels_scratch_bytes if levels_variant else self.lib.vkmr_hip_reduce_scratch_bytes
         return self.alloc(fn(count))
@@ -2639,8 +2731,8 @@ class AbsenceProofs:
 
 def sort_digests(digests, counts):
     """A HOST helper, numpy on the CPU, for tests and small callers: the digests ([n, 8] uint32) with every tree's leaves
-    (counts[t] of them, in order) sorted by the order an absence proof rests on -- word 0 first, every word unsigned.  The device
-    does not sort leaves; MerkleForest.first_unsorted checks an order made elsewhere."""
+    (counts[t] of them, in order) sorted by the order an absence proof rests on -- word 0 first, every word unsigned.  The device's
+    sort is HipDevice.sort_leaves / build_sorted_forest; this one has no tie limit and takes the batches that one refuses."""
     d = _host(digests, np.uint32, -1, 8).copy()
     at = 0
     for c in (int(c) for c in counts):
@@ -2650,6 +2742,38 @@ def sort_digests(digests, counts):
     if at != d.shape[0]:
         raise ValueError(f"sort_digests: the counts sum to {at}, {d.shape[0]} digests given")
     return d
+
+
+LEAFSORT_MAX_TIES = 1 << 14     # VKMR_LEAFSORT_MAX_TIES of csrc/leafsort_plan.hpp (tests/test_leafsort_abi.py holds the two together)
+
+
+def leafsort_status_text(status):
+    """The bits of vkmr_hip_forest_sort_leaves_async's status word (info[0]), named."""
+    names = []
+    if status & 3:
+        names.append(forest_status_text(status & 3))
+    if status & 4:
+        names.append("bit 2: more leaves tie on the sort key than one sort places")
+    if status & ~7:
+        names.append("unknown bits")
+    return "; ".join(names) if names else "ok"
+
+
+def sorted_forest_packed(dev, batch, counts, max_count=None, reserve_trees=0, reserve_leaves=0):
+    """(MerkleForest, order): merkle_forest_packed over SORTED leaves -- the strings of `batch` mapped to leaf digests once, every
+    tree's digests (tree t the next counts[t] of them) sorted on the device and the stored forest built over the sorted buffer,
+    with no trip through the host.  order [n] uint32: leaf j of the forest is the digest of string order[j].  Keywords and
+    errors as HipDevice.build_sorted_forest."""
+    what = "sorted_forest_packed"
+    _checked_offsets(counts, batch.count, what, "strings")
+    reserve_trees, reserve_leaves = _reserve(what, reserve_trees, reserve_leaves, max_count)
+    total = batch.count + reserve_leaves
+    with dev.scope() as tmp:
+        d_leaves = tmp.alloc(32 * total) if total else None
+        if batch.count:
+            dev.map_packed(tmp, batch, out_buf=d_leaves)
+        return dev._build_sorted_forest_of_buffer(tmp, d_leaves, total, counts, max_count, what, reserve_trees=reserve_trees,
+                                                  reserve_leaves=reserve_leaves)
 
 
 def consistency_status_text(status):
