@@ -1359,7 +1359,58 @@ VKMR_API vkmr_status vkmr_hip_tree_sort_leaves_async(int dev, vkmr_stream s, con
                                                      uint64_t* info_dev);
 
 /*
- * COMBINE: duplicate-last Merkle root over n >= 1 slice roots given in slice order, always
+ * MERGE two sorted forests over the same ntrees, tree by tree, on the device: what inserts leaves into sorted trees, removes them
+ * and says which are held in common, in one streaming pass and with equal digests kept once.  A is a_digests_dev, a_total,
+ * a_offsets_dev[ntrees + 1] and B is b_digests_dev, b_total, b_offsets_dev[ntrees + 1], both laid out as
+ * vkmr_hip_reduce_forest_async takes them; the order is the one above (word 0 first, every word unsigned).  Every tree of A must
+ * be strictly increasing; every tree of B non-decreasing -- equal neighbours, which vkmr_hip_forest_sort_leaves_async leaves
+ * behind, count once.  Tree t of the output, by op:
+ *   0 union          the distinct digests of A_t and B_t, increasing; a digest in both is A's cell
+ *   1 difference     the leaves of A_t that equal no leaf of B_t
+ *   2 intersection   the leaves of A_t that equal some leaf of B_t
+ *   out_offsets_dev   ntrees + 1 uint64_t, out_offsets[0] = 0: what the forest builds take as it is
+ *   out_digests_dev   the output trees back to back at cells [0, out_offsets[ntrees]); out_capacity cells; the cells at or behind
+ *                     out_offsets[ntrees] are never touched
+ *   origin_out_dev    (may be NULL) out_capacity uint64_t: the flat input cell that lies at output cell j, bit 63 set when it is a
+ *                     cell of B, so that a payload can follow
+ *   info_dev          4 uint64_t, always written when ntrees > 0: [0] status, [1] n_out, [2] matches, the distinct digests of B
+ *                     that equal a leaf of A in their tree, [3] repeats, the leaves of B equal to their predecessor in their tree.
+ *                     [2] and [3] do not depend on op; n_out = nA + nB - matches - repeats (union), nA - matches (difference),
+ *                     matches (intersection).  [1..3] are 0 when one of the status bits 0 to 3 is set.
+ * Status bits, all formed on the device before any cell of out_digests_dev, origin_out_dev or out_offsets_dev is written; with a
+ * nonzero status none of those is written: bit 0 A's offsets decrease somewhere or end behind a_total; bit 1 the same for B; bit 2
+ * some tree of A is not strictly increasing; bit 3 some tree of B decreases somewhere; bit 4 n_out > out_capacity ([1] still holds
+ * n_out, so that the caller can call again).  out_capacity = nA + nB for union, nA for the other two, never sees bit 4.
+ * HOW (csrc/merge_plan.hpp): a lane per leaf of B runs the lower bound's loop in A_t and compares with its predecessor; a kept
+ * leaf counts at A's slot "in front of element lb" (an atomic add that only counts), a match marks it; one exclusive prefix over
+ * the slots and B's keep flags (sort_scan_kernel as it is, two launches) makes every destination a closed form; then a lane per leaf
+ * of A and, for union, of B does one 32-byte load and one 32-byte store.  The elements are numbered from offsets[0]: the work
+ * follows (a_total, b_total, ntrees), never where the forests lie in their buffers.
+ *   scratch_dev  vkmr_hip_merge_leaves_scratch_bytes(a_total, b_total, ntrees) bytes, 16-byte aligned: about 4 bytes a cell of A
+ *                and 8 a cell of B (ntrees does not enter today's layout); 0 when the call would be refused for its size
+ * Launches, all on the caller's stream: two memsets, the two offsets checks, the order of A, the marks of B, two scans, the emit;
+ * no allocation, no host synchronisation, no host read of device data; no kernel waits for another workgroup.  ntrees == 0 does
+ * nothing.  Empty trees on either side, an empty A and an empty B are fine and still write the offsets and info.  Refused on the
+ * host (VKMR_ERR_INVALID), before any HIP call: a NULL pointer that is needed (the digests of a side with no cell and
+ * out_digests_dev with out_capacity == 0 are not), op > 2, a_total + b_total + 2 >= 2^32 (the scan carries uint32 sums), a
+ * digest buffer or the scratch off its 16-byte grid, a uint64_t buffer off its 8-byte grid, the out_capacity cells of
+ * out_digests_dev overlapping either input or the scratch.
+ * The one-tree twin merges cells [0, a_count) with cells [0, b_count): no offsets, n_out in info[1] alone, status bits 2, 3 and 4.
+ * vkmr_host_cpu_forest_merge_leaves / vkmr_host_cpu_tree_merge_leaves (libvkmr_host.so) are the CPU's.
+ */
+VKMR_API size_t vkmr_hip_merge_leaves_scratch_bytes(uint64_t a_total, uint64_t b_total, uint32_t ntrees);
+VKMR_API vkmr_status vkmr_hip_forest_merge_leaves_async(int dev, vkmr_stream s, const vkmr_digest* a_digests_dev, uint64_t a_total,
+                                                        const uint64_t* a_offsets_dev, const vkmr_digest* b_digests_dev, uint64_t b_total,
+                                                        const uint64_t* b_offsets_dev, uint32_t ntrees, uint32_t op, void* scratch_dev,
+                                                        vkmr_digest* out_digests_dev, uint64_t out_capacity, uint64_t* out_offsets_dev,
+                                                        uint64_t* origin_out_dev, uint64_t* info_dev);
+VKMR_API vkmr_status vkmr_hip_tree_merge_leaves_async(int dev, vkmr_stream s, const vkmr_digest* a_digests_dev, uint64_t a_count,
+                                                      const vkmr_digest* b_digests_dev, uint64_t b_count, uint32_t op, void* scratch_dev,
+                                                      vkmr_digest* out_digests_dev, uint64_t out_capacity, uint64_t* origin_out_dev,
+                                                      uint64_t* info_dev);
+
+/*
+ * COMBINE:duplicate-last Merkle root over n >= 1 slice roots given in slice order, always
  * at least one level -- the rule of CpuSha256D::Root that the reference applies to the slice
  * roots on the CPU (CpuSha256DforReductions, src/vkmr/Reductions.cpp:56-69, :703-712).  Here
  * the roots stay in HBM (where the reductions or the gather below left them) and the combine is

@@ -262,6 +262,22 @@ VKMR_API int vkmr_host_cpu_forest_sort_leaves(const vkmr_digest* digests_in, uin
 VKMR_API int vkmr_host_cpu_tree_sort_leaves(const vkmr_digest* digests_in, uint64_t count, vkmr_digest* digests_out, uint32_t* order_out,
                                             uint64_t* info);
 
+/* ---- two sorted forests merged tree by tree, by the rule of vkmr_hip_forest_merge_leaves_async ---- */
+
+/* A two-pointer merge per tree under absence_plan.hpp's less: op 0 union, 1 difference, 2 intersection of the strictly increasing
+ * trees of A (a_digests, a_total, a_offsets) with the non-decreasing trees of B.  out_offsets[ntrees + 1], out_digests (out_capacity
+ * cells), origin_out (may be NULL; bit 63: a cell of B) and info[0..4) = status, n_out, matches, repeats as the device writes them,
+ * with the same status bits 0 to 4; with a nonzero status only info is written.  -1 for a missing pointer or op > 2; ntrees == 0
+ * does nothing. */
+VKMR_API int vkmr_host_cpu_forest_merge_leaves(const vkmr_digest* a_digests, uint64_t a_total, const uint64_t* a_offsets,
+                                               const vkmr_digest* b_digests, uint64_t b_total, const uint64_t* b_offsets, uint32_t ntrees,
+                                               uint32_t op, vkmr_digest* out_digests, uint64_t out_capacity, uint64_t* out_offsets,
+                                               uint64_t* origin_out, uint64_t* info);
+
+/* The same for one tree a side, a_digests[0 .. a_count) and b_digests[0 .. b_count): no offsets, n_out in info[1]. */
+VKMR_API int vkmr_host_cpu_tree_merge_leaves(const vkmr_digest* a_digests, uint64_t a_count, const vkmr_digest* b_digests, uint64_t b_count,
+                                             uint32_t op, vkmr_digest* out_digests, uint64_t out_capacity, uint64_t* origin_out, uint64_t* info);
+
 /* ---- packing (stream_pack.cpp; in libvkmr_host.so and libvkmr_pipeline.so) ---- */
 
 /* One-shot form for bindings: packs the whole buffer (final = true).  Returns the

@@ -41,6 +41,9 @@
 #   leafsort [args]        tools/leafsort_timing.py: the leaves sorted on the device (2^26 random leaves as 2^15 trees of 2 048 and as one tree): the
 #                          sort alone, the sort and the stored build, the build alone, the worst case of the tie step, beside the host route
 #                          (download, vk.sort_digests, upload) and torch.sort of as many int64 keys (one JSON line)
+#   merge [args]           tools/merge_timing.py: a batch merged into sorted trees (2^26 leaves as 2^15 trees of 2 048 and as one tree): the union with
+#                          2^10, 2^16, 2^20 and 2^24 new digests, the difference at 2^16, the union and the stored build, beside the parent's route
+#                          (the concatenation sorted again by vkmr_hip_forest_sort_leaves_async) and vkmr_hip_forest_copy_trees_async (one JSON line)
 #   forest_repack [args]   tools/forest_repack_timing.py: the oldest trees of a stored forest dropped and the rest (or all) copied into an
 #                          empty forest, beside the stored build over the same leaves (one JSON line)
 #   cumask                 tools/cu_mask_probe.py: where CU-mask bits land, map/reduce on half the CUs with and without neighbours
@@ -242,6 +245,11 @@ leafsort)
   timeout -k 10 900 python3 tools/leafsort_timing.py "$@" --out $OUT/leafsort_timing.json > /dev/null 2> $OUT/leafsort_timing.err && echo "leafsort_timing ok" &&
   cat $OUT/leafsort_timing.json
   echo "leafsort rc=$?"
+  ;;
+merge)
+  timeout -k 10 900 python3 tools/merge_timing.py "$@" --out $OUT/merge_timing.json > /dev/null 2> $OUT/merge_timing.err && echo "merge_timing ok" &&
+  cat $OUT/merge_timing.json
+  echo "merge rc=$?"
   ;;
 forest_repack)
   timeout -k 10 500 python3 tools/forest_repack_timing.py "$@" --out $OUT/forest_repack_timing.json > /dev/null 2> $OUT/forest_repack_timing.err && echo "forest_repack_timing ok" &&

@@ -12,6 +12,7 @@
 #include "../consistency_plan.hpp"
 #include "../frontier_plan.hpp"
 #include "../leafsort_plan.hpp"
+#include "../merge_plan.hpp"
 #include "../merkle_math.hpp"
 #include "../proofs_at_plan.hpp"
 #include "cpu_sha256d.hpp"
@@ -1156,4 +1157,78 @@ int vkmr_host_cpu_tree_sort_leaves(const vkmr_digest* digests_in, uint64_t count
 {
     const uint64_t offsets[2] = {0, count};
     return vkmr_host_cpu_forest_sort_leaves(digests_in, count, offsets, 1, count, digests_out, order_out, info);
+}
+
+// ---- two sorted forests merged tree by tree (merge_plan.hpp)
+
+// offsets == nullptr: one tree a side at cell 0.
+static int merge_leaves_cpu(const vkmr_digest* a, uint64_t a_total, const uint64_t* a_offsets, const vkmr_digest* b, uint64_t b_total,
+                            const uint64_t* b_offsets, uint32_t ntrees, uint32_t op, vkmr_digest* out, uint64_t out_capacity, uint64_t* out_offsets,
+                            uint64_t* origin_out, uint64_t* info)
+{
+    if (!info || op > VKMR_MERGE_INTERSECTION || (a_total && !a) || (b_total && !b) || (out_capacity && !out)) return -1;
+    const uint64_t one_a[2] = {0, a_total}, one_b[2] = {0, b_total};
+    const uint64_t *ao = a_offsets ? a_offsets : one_a, *bo = b_offsets ? b_offsets : one_b;
+    uint64_t status = 0;
+    if (a_offsets && absence_offsets_bad(ao, ntrees, a_total)) status |= VKMR_MERGE_BAD_A_OFFSETS;
+    if (b_offsets && absence_offsets_bad(bo, ntrees, b_total)) status |= VKMR_MERGE_BAD_B_OFFSETS;
+    info[0] = status;
+    info[1] = info[2] = info[3] = 0;
+    if (status) return 0;
+    for (uint32_t t = 0; t < ntrees; ++t) {
+        for (uint64_t i = ao[t] + 1; i < ao[t + 1]; ++i)
+            if (!vkmr_absence::less(a[i - 1].data, a[i].data)) status |= VKMR_MERGE_A_NOT_INCREASING;
+        for (uint64_t j = bo[t] + 1; j < bo[t + 1]; ++j)
+            if (vkmr_absence::less(b[j].data, b[j - 1].data)) status |= VKMR_MERGE_B_DECREASES;
+    }
+    info[0] = status;
+    if (status) return 0;
+    // every output cell as the input cell it comes from; the counts
+    std::vector<uint64_t> from, starts(ntrees + 1u, 0);
+    uint64_t matches = 0, repeats = 0;
+    for (uint32_t t = 0; t < ntrees; ++t) {
+        starts[t] = from.size();
+        uint64_t i = ao[t], j = bo[t];
+        const uint64_t ie = ao[t + 1], je = bo[t + 1];
+        while (i < ie || j < je) {
+            if (j < je && j > bo[t] && vkmr_absence::equal(b[j].data, b[j - 1].data)) { ++repeats; ++j; continue; }
+            if (j == je || (i < ie && vkmr_absence::less(a[i].data, b[j].data))) {          // A's leaf alone
+                if (op != VKMR_MERGE_INTERSECTION) from.push_back(i);
+                ++i;
+            } else if (i == ie || vkmr_absence::less(b[j].data, a[i].data)) {               // B's leaf alone
+                if (op == VKMR_MERGE_UNION) from.push_back(j | VKMR_MERGE_ORIGIN_B);
+                ++j;
+            } else {                                                                        // in both: A's cell
+                ++matches;
+                if (op != VKMR_MERGE_DIFFERENCE) from.push_back(i);
+                ++i; ++j;
+            }
+        }
+    }
+    starts[ntrees] = from.size();
+    info[1] = from.size();
+    info[2] = matches;
+    info[3] = repeats;
+    if (from.size() > out_capacity) { info[0] = VKMR_MERGE_SHORT_OUTPUT; return 0; }
+    if (out_offsets) std::copy(starts.begin(), starts.end(), out_offsets);
+    for (size_t k = 0; k < from.size(); ++k) {
+        out[k] = (from[k] & VKMR_MERGE_ORIGIN_B) ? b[from[k] & ~VKMR_MERGE_ORIGIN_B] : a[from[k]];
+        if (origin_out) origin_out[k] = from[k];
+    }
+    return 0;
+}
+
+int vkmr_host_cpu_forest_merge_leaves(const vkmr_digest* a_digests, uint64_t a_total, const uint64_t* a_offsets, const vkmr_digest* b_digests,
+                                      uint64_t b_total, const uint64_t* b_offsets, uint32_t ntrees, uint32_t op, vkmr_digest* out_digests,
+                                      uint64_t out_capacity, uint64_t* out_offsets, uint64_t* origin_out, uint64_t* info)
+{
+    if (ntrees == 0) return 0;
+    if (!a_offsets || !b_offsets || !out_offsets) return -1;
+    return merge_leaves_cpu(a_digests, a_total, a_offsets, b_digests, b_total, b_offsets, ntrees, op, out_digests, out_capacity, out_offsets, origin_out, info);
+}
+
+int vkmr_host_cpu_tree_merge_leaves(const vkmr_digest* a_digests, uint64_t a_count, const vkmr_digest* b_digests, uint64_t b_count, uint32_t op,
+                                    vkmr_digest* out_digests, uint64_t out_capacity, uint64_t* origin_out, uint64_t* info)
+{
+    return merge_leaves_cpu(a_digests, a_count, nullptr, b_digests, b_count, nullptr, 1u, op, out_digests, out_capacity, nullptr, origin_out, info);
 }

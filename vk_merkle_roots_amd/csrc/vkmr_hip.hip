@@ -44,6 +44,10 @@
 //                                              forest sorted tree by tree in digest order: sort_kernels.hpp's radix passes over
 //                                              (tree, digest prefix) keys, then the few ties placed by all 256 bits; no hash
 //                                              (the key, the sentinel and the tie limit: leafsort_plan.hpp)
+//   merge_kernels.hpp  *_merge_order_kernel, *_merge_mark_kernel, *_merge_emit_kernel   two sorted forests merged tree by tree (union,
+//                                              difference, intersection): a lower bound per leaf of B, counts and marks at A's
+//                                              slots, sort_scan_kernel over them, every leaf copied to a closed-form cell; no hash
+//                                              (the slots and the placement: merge_plan.hpp)
 //   forest_tree_kernels.hpp  forest_proofs_kernel          proofs gathered from the stored forest, one lane per (query, level)
 //                            verify_forest_proofs_kernel   batch verification of proofs of unequal height, one lane per proof
 //                            forest_update_*_kernel        leaf updates of the stored forest: tree_update_*'s bodies, a tree per entry
@@ -78,6 +82,7 @@
 //   merkleblock_plan.hpp  what a BIP37 walk appends between two matched leaves, in closed form; the three size bounds, the scratch layout
 //   absence_plan.hpp    the order on digests, the lower bound's loop, the cells of an absence proof and the verdict of its check
 //   leafsort_plan.hpp   the leaf sort's key and passes, its elements and sentinel, what a tie is, the tie limit and the scratch layout
+//   merge_plan.hpp      the merge's slots, what a leaf of B does at its slot, where every leaf goes, the counts and the scratch layout
 //
 // Host side: plain launches on the caller's stream, each through launch() and so each checked; every argument refusal
 // through refuse(__func__, why); no allocation, no sync inside the *_async entry points.
@@ -118,6 +123,7 @@ using vkmr_dev::Node;
 #include "merkleblock_kernels.hpp"
 #include "absence_kernels.hpp"
 #include "leafsort_kernels.hpp"
+#include "merge_kernels.hpp"
 
 // ============================================================================
 // C ABI
@@ -2164,6 +2170,85 @@ vkmr_status vkmr_hip_tree_sort_leaves_async(int dev, vkmr_stream s, const vkmr_d
 {
     if (!info_dev) return refuse(__func__, "null pointer");
     return leafsort_launch(__func__, dev, s, digests_in_dev, count, nullptr, 1u, count, scratch_dev, digests_out_dev, order_out_dev, info_dev);
+}
+
+// ---- two sorted forests merged tree by tree (merge_kernels.hpp, merge_plan.hpp) ---------------------------------------------
+
+static_assert(VKMR_MERGE_HEADER_WORDS >= 5u, "status bits 2 and 3, matches, repeats, the two offsets checks");
+static_assert(VKMR_MERGE_SCAN_ROW % VKMR_SORT_SCAN_SPAN == 0u, "a row is whole trips of sort_scan_kernel");
+
+size_t vkmr_hip_merge_leaves_scratch_bytes(uint64_t a_total, uint64_t b_total, uint32_t) { return vkmr_merge::scratch_bytes(a_total, b_total); }
+
+// The launches of both merges, all on the caller's stream: two memsets, the two offsets checks (a forest's), the order of A, the
+// marks of B, the scan's two launches, the emit.  They depend on (a_total, b_total, ntrees, op) alone.  a_offsets_dev null: one
+// tree a side at cell 0, nothing to check.
+static vkmr_status merge_launch(const char* who, int dev, vkmr_stream s, const vkmr_digest* a_dev, uint64_t a_total, const uint64_t* a_offsets_dev,
+                                const vkmr_digest* b_dev, uint64_t b_total, const uint64_t* b_offsets_dev, uint32_t ntrees, uint32_t op,
+                                void* scratch_dev, vkmr_digest* out_dev, uint64_t out_capacity, uint64_t* out_offsets_dev, uint64_t* origin_out_dev,
+                                uint64_t* info_dev)
+{
+    if (op > VKMR_MERGE_INTERSECTION) return refuse(who, "op is 0 (union), 1 (difference) or 2 (intersection)");
+    if (!vkmr_merge::fits(a_total, b_total)) return refuse(who, "a_total + b_total + 2 must stay below 2^32: the scan's sums are 32-bit");
+    if (!info_dev || !scratch_dev || (a_total && !a_dev) || (b_total && !b_dev) || (out_capacity && !out_dev)) return refuse(who, "null pointer");
+    if ((reinterpret_cast<uintptr_t>(scratch_dev) | reinterpret_cast<uintptr_t>(a_dev) | reinterpret_cast<uintptr_t>(b_dev) |
+         reinterpret_cast<uintptr_t>(out_dev)) & 15u)
+        return refuse(who, "digests and scratch must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(a_offsets_dev) | reinterpret_cast<uintptr_t>(b_offsets_dev) | reinterpret_cast<uintptr_t>(out_offsets_dev) |
+         reinterpret_cast<uintptr_t>(origin_out_dev) | reinterpret_cast<uintptr_t>(info_dev)) & 7u)
+        return refuse(who, "uint64_t buffers must be 8-byte aligned");
+    if (out_capacity > (~0ull >> 6)) return refuse(who, "out_capacity too large");
+    const vkmr_merge::Layout L = vkmr_merge::layout(a_total, b_total);
+    if (bytes_overlap(out_dev, 32u * out_capacity, a_dev, 32u * a_total) || bytes_overlap(out_dev, 32u * out_capacity, b_dev, 32u * b_total) ||
+        bytes_overlap(out_dev, 32u * out_capacity, scratch_dev, L.bytes))
+        return refuse(who, "the output cells must not overlap an input or the scratch");
+    char* at = static_cast<char*>(scratch_dev);
+    uint32_t* scan = reinterpret_cast<uint32_t*>(at + L.scan);
+    uint32_t* tot = reinterpret_cast<uint32_t*>(at + L.tot);
+    uint32_t* grand = reinterpret_cast<uint32_t*>(at + L.grand);
+    uint32_t* pos0 = reinterpret_cast<uint32_t*>(at + L.pos0);
+    unsigned long long* hdr = reinterpret_cast<unsigned long long*>(at + L.hdr);
+    const Node *a = nodes(a_dev), *b = nodes(b_dev);
+    const uint64_t emit_lanes = std::max<uint64_t>(a_total + (op == VKMR_MERGE_UNION ? b_total : 0ull), a_offsets_dev ? (uint64_t)ntrees + 1u : 1u);
+    const dim3 block(256), scan_block(VKMR_SORT_THREADS);
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_TRY(hipMemsetAsync(at + L.scan, 0, L.tot - L.scan, S(s)));
+    VKMR_TRY(hipMemsetAsync(hdr, 0, VKMR_MERGE_HEADER_WORDS * sizeof(uint64_t), S(s)));
+    if (a_offsets_dev) {
+        VKMR_CHECK(launch(forest_check_kernel, grid_of(ntrees), block, S(s), a_offsets_dev, ntrees, a_total, ~0ull, reinterpret_cast<uint32_t*>(hdr + 3)));
+        VKMR_CHECK(launch(forest_check_kernel, grid_of(ntrees), block, S(s), b_offsets_dev, ntrees, b_total, ~0ull, reinterpret_cast<uint32_t*>(hdr + 4)));
+        if (a_total > 1) VKMR_CHECK(launch(forest_merge_order_kernel, grid_of(a_total), block, S(s), a_offsets_dev, b_offsets_dev, ntrees, a, hdr));
+        if (b_total) VKMR_CHECK(launch(forest_merge_mark_kernel, grid_of(b_total), block, S(s), a_offsets_dev, b_offsets_dev, ntrees, a, b, op, L.S, hdr, scan, pos0));
+    } else {
+        if (a_total > 1) VKMR_CHECK(launch(tree_merge_order_kernel, grid_of(a_total), block, S(s), a_total, b_total, a, hdr));
+        if (b_total) VKMR_CHECK(launch(tree_merge_mark_kernel, grid_of(b_total), block, S(s), a_total, b_total, a, b, op, L.S, hdr, scan, pos0));
+    }
+    VKMR_CHECK(launch(sort_scan_kernel, dim3((uint32_t)L.rows), scan_block, S(s), scan, (uint64_t)VKMR_MERGE_SCAN_ROW, tot));
+    VKMR_CHECK(launch(sort_scan_kernel, dim3(1), scan_block, S(s), tot, L.rows, grand));
+    if (a_offsets_dev)
+        return launch(forest_merge_emit_kernel, grid_of(emit_lanes), block, S(s), a_offsets_dev, b_offsets_dev, ntrees, a, b, op, a_total, b_total,
+                      (const unsigned long long*)hdr, (const uint32_t*)scan, (const uint32_t*)tot, (const uint32_t*)pos0, out_capacity, nodes(out_dev),
+                      out_offsets_dev, origin_out_dev, info_dev);
+    return launch(tree_merge_emit_kernel, grid_of(emit_lanes), block, S(s), a_total, b_total, a, b, op, (const unsigned long long*)hdr, (const uint32_t*)scan,
+                  (const uint32_t*)tot, (const uint32_t*)pos0, out_capacity, nodes(out_dev), origin_out_dev, info_dev);
+}
+
+vkmr_status vkmr_hip_forest_merge_leaves_async(int dev, vkmr_stream s, const vkmr_digest* a_digests_dev, uint64_t a_total, const uint64_t* a_offsets_dev,
+                                               const vkmr_digest* b_digests_dev, uint64_t b_total, const uint64_t* b_offsets_dev, uint32_t ntrees,
+                                               uint32_t op, void* scratch_dev, vkmr_digest* out_digests_dev, uint64_t out_capacity,
+                                               uint64_t* out_offsets_dev, uint64_t* origin_out_dev, uint64_t* info_dev)
+{
+    if (ntrees == 0) return VKMR_OK;
+    if (!a_offsets_dev || !b_offsets_dev || !out_offsets_dev) return refuse(__func__, "null pointer");
+    return merge_launch(__func__, dev, s, a_digests_dev, a_total, a_offsets_dev, b_digests_dev, b_total, b_offsets_dev, ntrees, op, scratch_dev,
+                        out_digests_dev, out_capacity, out_offsets_dev, origin_out_dev, info_dev);
+}
+
+vkmr_status vkmr_hip_tree_merge_leaves_async(int dev, vkmr_stream s, const vkmr_digest* a_digests_dev, uint64_t a_count, const vkmr_digest* b_digests_dev,
+                                             uint64_t b_count, uint32_t op, void* scratch_dev, vkmr_digest* out_digests_dev, uint64_t out_capacity,
+                                             uint64_t* origin_out_dev, uint64_t* info_dev)
+{
+    return merge_launch(__func__, dev, s, a_digests_dev, a_count, nullptr, b_digests_dev, b_count, nullptr, 1u, op, scratch_dev, out_digests_dev,
+                        out_capacity, nullptr, origin_out_dev, info_dev);
 }
 
 // ---- the leaves that differ between two stored forests or trees (diff_kernels.hpp, diff_plan.hpp) ----------------------------

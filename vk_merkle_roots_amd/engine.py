@@ -958,6 +958,82 @@ class HipDevice:
             return self._build_sorted_forest_of_buffer(tmp, d_in, total, counts, max_count, "build_sorted_forest", mutated=mutated,
                                                        reserve_trees=reserve_trees, reserve_leaves=reserve_leaves)
 
+    # -- two sorted forests merged tree by tree on the device: insert, remove and intersect leaves ---------------------------------
+    def merge_leaves_scratch_bytes(self, a_total, b_total, ntrees):
+        return self.lib.vkmr_hip_merge_leaves_scratch_bytes(a_total, b_total, ntrees)
+
+    def forest_merge_leaves_enqueue(self, a_buf, a_total, a_offsets_buf, b_buf, b_total, b_offsets_buf, ntrees, op, scratch_buf, out_buf, out_capacity,
+                                    out_offsets_buf, origin_out_buf, info_buf, stream=None):
+        """Tree t of the output = op (0 union, 1 difference, 2 intersection) of tree t of A (strictly increasing) and tree t of B
+        (non-decreasing; equal neighbours count once): out_offsets_buf (ntrees + 1 uint64 from 0), the trees back to back in the
+        first cells of out_buf (out_capacity cells), origin_out_buf (uint64 per output cell, bit 63: a cell of B; may be None),
+        info_buf: 4 uint64 (status, n_out, matches, repeats).  All in device memory; scratch_buf:
+        merge_leaves_scratch_bytes(a_total, b_total, ntrees), 16-byte aligned.  A nonzero status writes no cell and no offset.
+        include/vkmr_hip.h."""
+        self._call("vkmr_hip_forest_merge_leaves_async", a_buf, a_total, a_offsets_buf, b_buf, b_total, b_offsets_buf, ntrees, op, scratch_buf, out_buf,
+                   out_capacity, out_offsets_buf, origin_out_buf, info_buf, stream=stream)
+
+    def tree_merge_leaves_enqueue(self, a_buf, a_count, b_buf, b_count, op, scratch_buf, out_buf, out_capacity, origin_out_buf, info_buf, stream=None):
+        """forest_merge_leaves_enqueue for ONE tree a side, a_buf[0 .. a_count) and b_buf[0 .. b_count): no offsets, n_out in
+        info_buf[1]."""
+        self._call("vkmr_hip_tree_merge_leaves_async", a_buf, a_count, b_buf, b_count, op, scratch_buf, out_buf, out_capacity, origin_out_buf, info_buf,
+                   stream=stream)
+
+    def _sorted_batch(self, tmp, rows, offsets, ntrees, what, stream=None):
+        """The batch `rows` ([n, 8], n >= 1) uploaded and every tree's leaves sorted by forest_sort_leaves_enqueue on `stream`; the
+        sort's info is NOT read here: (sorted buffer, info buffer).  The caller looks at the info once its own call is done."""
+        n = int(rows.shape[0])
+        d_in, d_sorted, d_info = tmp.upload(rows), tmp.alloc(32 * n), tmp.alloc(32)
+        self.forest_sort_leaves_enqueue(d_in, n, tmp.upload(offsets), ntrees, max(1, int(np.diff(offsets).max())),
+                                        tmp.alloc(self.sort_leaves_scratch_bytes(n)), d_sorted, None, d_info, stream=stream)
+        return d_sorted, d_info
+
+    def _raise_unless_sorted_batch(self, d_sort_info, what):
+        if d_sort_info is not None:
+            status = int(self.download(d_sort_info, 32, dtype=np.uint64)[0])
+            if status:
+                raise RuntimeError(f"{what}: the batch was not sorted (status {status}: {leafsort_status_text(status)}); sort it with vk.sort_digests "
+                                   f"and pass sort_b=False")
+
+    def merge_leaves(self, a, a_counts, b, b_counts, op="union", sort_b=True):
+        """(digests [n_out, 8] uint32, counts [ntrees] uint64, origin [n_out] uint64, info [4] uint64): tree t of the result is
+        the union, "difference" or "intersection" of tree t of `a` (the next a_counts[t] rows of it, strictly increasing in
+        sort_leaves' order) and tree t of `b`, merged on the device (vkmr_hip_forest_merge_leaves_async).  With sort_b the
+        batch `b` comes in any order and goes through forest_sort_leaves_enqueue first, on the same stream; without, every tree of
+        it must not decrease.  A digest that `b` holds twice counts once; a digest in both is a's.  origin[j]: the row of `a`
+        that lies at output row j, or (1 << 63) | the row of the batch as it was merged (sorted, with sort_b).  info: status 0,
+        n_out, the distinct digests of b found in a, the repeats in b.  ValueError when the counts do not add up or name
+        different numbers of trees, or for an unknown op; RuntimeError, carrying merge_status_text, when the device refuses --
+        `a` not strictly increasing, `b` decreasing; nothing falls back to the host."""
+        what = "merge_leaves"
+        code = _merge_op(op, what)
+        a, b = _host(a, np.uint32, -1, 8), _host(b, np.uint32, -1, 8)
+        na, nb = int(a.shape[0]), int(b.shape[0])
+        a_off, ntrees = _checked_offsets(a_counts, na, what)
+        b_off, b_trees = _checked_offsets(b_counts, nb, what)
+        if b_trees != ntrees:
+            raise ValueError(f"{what}: {ntrees} trees of a, {b_trees} of b")
+        if ntrees == 0:
+            return np.zeros((0, 8), dtype=np.uint32), np.zeros(0, dtype=np.uint64), np.zeros(0, dtype=np.uint64), np.zeros(4, dtype=np.uint64)
+        cap = na + nb if code == 0 else na
+        with self.scope() as tmp:
+            d_a = tmp.upload(a) if na else None
+            d_b, d_sort_info = None, None
+            if nb and sort_b:
+                d_b, d_sort_info = self._sorted_batch(tmp, b, b_off, ntrees, what)
+            elif nb:
+                d_b = tmp.upload(b)
+            d_out, d_origin, d_off, d_info = (tmp.alloc(32 * cap) if cap else None), (tmp.alloc(8 * cap) if cap else None), tmp.alloc(8 * (ntrees + 1)), tmp.alloc(32)
+            self.forest_merge_leaves_enqueue(d_a, na, tmp.upload(a_off), d_b, nb, tmp.upload(b_off), ntrees, code,
+                                             tmp.alloc(self.merge_leaves_scratch_bytes(na, nb, ntrees)), d_out, cap, d_off, d_origin, d_info)
+            info = self.download(d_info, 32, dtype=np.uint64)
+            self._raise_unless_sorted_batch(d_sort_info, what)
+            _raise_merge_status(info, what)
+            n = int(info[1])
+            out = self.download(d_out, 32 * n).reshape(n, 8) if n else np.zeros((0, 8), dtype=np.uint32)
+            origin = self.download(d_origin, 8 * n, dtype=np.uint64) if n else np.zeros(0, dtype=np.uint64)
+            return out, np.diff(self.download(d_off, 8 * (ntrees + 1), dtype=np.uint64)), origin, info
+
     def reduce_scratch(self, count, levels_variant=False):
         fn = self.lib.vkmr_hip_reduce_levels_scratch_bytes if levels_variant else self.lib.vkmr_hip_reduce_scratch_bytes
         return self.alloc(fn(count))
@@ -1808,6 +1884,51 @@ class MerkleTree(_Stored):
         self.dev.tree_audit_enqueue(self.digests, self.tree, self.count, self.height, scratch_buf, levels_buf, nodes_buf, capacity, info_buf,
                                     stream=stream)
 
+    # -- a sorted tree that changes: a NEW tree whose level 0 is the output of vkmr_hip_tree_merge_leaves_async ---------------------
+    def _merged(self, what, op, digests):
+        """(MerkleTree, info): this tree's leaves merged with the batch (`digests` [n, 8] in any order: sorted on the device
+        first) into a new stored tree that owns its leaves; this one is only read."""
+        dev = self.dev
+        what = f"MerkleTree.{what}"
+        rows = _host(digests, np.uint32, -1, 8)
+        nb = int(rows.shape[0])
+        cap = self.count + nb if op == 0 else self.count
+        d_out = dev.alloc(32 * cap)
+        try:
+            with dev.scope() as tmp:
+                d_b, d_sort_info = dev._sorted_batch(tmp, rows, np.array([0, nb], dtype=np.uint64), 1, what) if nb else (None, None)
+                d_info = tmp.alloc(32)
+                dev.tree_merge_leaves_enqueue(self.digests, self.count, d_b, nb, op, tmp.alloc(dev.merge_leaves_scratch_bytes(self.count, nb, 1)), d_out, cap,
+                                              None, d_info)
+                info = dev.download(d_info, 32, dtype=np.uint64)
+                dev._raise_unless_sorted_batch(d_sort_info, what)
+                _raise_merge_status(info, what)
+            n = int(info[1])
+            if n == 0:
+                raise ValueError(f"{what}: no leaf is left, and a stored tree has at least one")
+            tree = dev.build_tree(d_out, n)
+            dev.sync()
+            tree._owned.append(d_out)
+            return tree, info
+        except BaseException:
+            d_out.free()
+            raise
+
+    def inserted(self, digests):
+        """(MerkleTree, info): a NEW stored tree over this tree's leaves and `digests` ([n, 8], in any order), increasing and
+        each once (vkmr_hip_tree_merge_leaves_async, union); it owns its leaves, this tree is not touched and must be sorted:
+        one that is not is refused (status bit 2).  info: 0, the leaves of the result, the distinct digests of the batch that
+        were leaves already, the repeats in the batch.  RuntimeError with merge_status_text when the device refuses."""
+        return self._merged("inserted", 0, digests)
+
+    def removed(self, digests):
+        """(MerkleTree, info) as inserted(): without the leaves that equal a digest of the batch.  ValueError when none is left."""
+        return self._merged("removed", 1, digests)
+
+    def common(self, digests):
+        """(MerkleTree, info) as inserted(): the leaves that equal a digest of the batch.  ValueError when there is none."""
+        return self._merged("common", 2, digests)
+
     def free(self):
         if self.tree:
             self.tree.free()
@@ -2473,6 +2594,87 @@ class MerkleForest(_Stored):
         self.dev.forest_audit_enqueue(self.digests, self.forest, self.roots_buf, self.total, self.offsets, self.ntrees, self.max_count, scratch_buf,
                                       masks_buf, trees_buf, levels_buf, nodes_buf, capacity, info_buf, stream=stream)
 
+    # -- a sorted forest that changes: a NEW forest whose level 0 is the output of vkmr_hip_forest_merge_leaves_async ---------------
+    def _merged(self, what, op, digests, counts, max_count=None, mutated=False, reserve_trees=0, reserve_leaves=0):
+        """(MerkleForest, info): the trees in use merged with the batch (`digests` [n, 8], tree t the next counts[t] of them, in
+        any order: sorted on the device first) into a new stored forest; this one is only read."""
+        dev = self.dev
+        what = f"MerkleForest.{what}"
+        rows = _host(digests, np.uint32, -1, 8)
+        nb, used = int(rows.shape[0]), self.used_trees
+        b_off, b_trees = _checked_offsets(counts, nb, what)
+        if b_trees != used:
+            raise ValueError(f"{what}: {b_trees} counts for the {used} trees in use")
+        if used == 0:
+            raise ValueError(f"{what}: no tree")
+        reserve_trees, reserve_leaves = _reserve(what, reserve_trees, reserve_leaves, max_count)
+        a_counts = self.counts[:used]
+        if max_count is None:
+            max_count = max(1, int((a_counts + np.diff(b_off)).max())) if op == 0 else self.max_count
+        na = self.live_leaves
+        cap, ntrees = (na + nb if op == 0 else na), used + reserve_trees
+        total = cap + reserve_leaves
+        d_out = d_off = d_forest = d_roots = None
+        try:
+            with dev.scope() as tmp:
+                d_b, d_sort_info = dev._sorted_batch(tmp, rows, b_off, used, what) if nb else (None, None)
+                d_out, d_off = (dev.alloc(32 * total) if total else None), dev.alloc(8 * (ntrees + 1))
+                d_forest, d_roots = dev.alloc(dev.forest_tree_bytes(total, ntrees, max_count)), dev.alloc(32 * ntrees)
+                d_info, d_status, d_mut = tmp.alloc(32), tmp.alloc(4), (tmp.alloc(8 * ntrees) if mutated else None)
+                dev._call("vkmr_hip_memset_async", d_off, 0xFF, 8 * (ntrees + 1))     # offsets no build accepts, should the merge refuse
+                dev.forest_merge_leaves_enqueue(self.digests, self.total, self.offsets, d_b, nb, tmp.upload(b_off), used, op,
+                                                tmp.alloc(dev.merge_leaves_scratch_bytes(self.total, nb, used)), d_out, cap, d_off, None, d_info)
+
+                def build():
+                    if mutated:
+                        dev.reduce_forest_tree_mutated_async(d_out, total, d_off, ntrees, max_count, d_forest, d_roots, d_mut, d_status)
+                    else:
+                        dev.reduce_forest_tree_async(d_out, total, d_off, ntrees, max_count, d_forest, d_roots, d_status)
+                if not reserve_trees:
+                    build()                                  # from out_offsets on the same stream: nothing was read in between
+                info = dev.download(d_info, 32, dtype=np.uint64)
+                dev._raise_unless_sorted_batch(d_sort_info, what)
+                _raise_merge_status(info, what)
+                offsets = dev.download(d_off, 8 * (used + 1), dtype=np.uint64)
+                if reserve_trees:                            # the empty trees behind: their offsets are the host's to write
+                    tail = np.full(reserve_trees, offsets[-1], dtype=np.uint64)
+                    dev._call("vkmr_hip_memcpy_h2d_async", d_off.at(8 * (used + 1)), tail.ctypes.data, tail.nbytes)
+                    dev.sync()
+                    build()
+                status = int(dev.download(d_status, 4)[0])
+                if status:
+                    raise ValueError(f"{what}: the device refused the forest (status {status}: {forest_status_text(status)})")
+                masks = dev.download(d_mut, 8 * ntrees, dtype=np.uint64) if mutated else None
+            new_counts = np.concatenate([np.diff(offsets), np.zeros(reserve_trees, dtype=np.uint64)])
+            return MerkleForest(dev, d_out, total, new_counts, d_off, max_count, d_forest, d_roots, owned=[d_out] if d_out else [],
+                                built_mutated=masks, used_trees=used), info
+        except BaseException:
+            for b in (d_out, d_off, d_forest, d_roots):
+                if b:
+                    b.free()
+            raise
+
+    def inserted(self, digests, counts, **build):
+        """(MerkleForest, info): a NEW stored forest whose tree t holds this forest's leaves and the next counts[t] rows of
+        `digests` ([n, 8], in any order: they are sorted on the device first), increasing and each once -- the union by
+        vkmr_hip_forest_merge_leaves_async; its level 0 IS the merge's output buffer, and it is built from the merge's
+        offsets on the same stream.  This forest must be sorted (is_sorted()) and is not touched: one that is not is refused
+        (status bit 2), not trusted.  info: 0, the leaves of the result, the distinct digests of the batch that were leaves
+        already, the repeats in the batch.  Keywords as build_forest's (max_count, mutated, reserve_trees, reserve_leaves);
+        max_count None: the largest count the result can have.  ValueError for counts that do not add up or are not one per
+        tree in use; RuntimeError with merge_status_text when the device refuses."""
+        return self._merged("inserted", 0, digests, counts, **build)
+
+    def removed(self, digests, counts, **build):
+        """(MerkleForest, info) as inserted(): tree t without the leaves that equal one of its rows of the batch (the
+        difference); info[2] says how many were there to remove."""
+        return self._merged("removed", 1, digests, counts, **build)
+
+    def common(self, digests, counts, **build):
+        """(MerkleForest, info) as inserted(): tree t holds the leaves that equal one of its rows of the batch (the
+        intersection)."""
+        return self._merged("common", 2, digests, counts, **build)
+
     def free(self):
         for b in [self.forest, self.roots_buf, self.offsets] + self._owned:
             if b:
@@ -2757,6 +2959,33 @@ def leafsort_status_text(status):
     if status & ~7:
         names.append("unknown bits")
     return "; ".join(names) if names else "ok"
+
+
+MERGE_OPS = {"union": 0, "difference": 1, "intersection": 2}     # VKMR_MERGE_* of csrc/merge_plan.hpp
+
+
+def _merge_op(op, what):
+    if op in MERGE_OPS:
+        return MERGE_OPS[op]
+    if isinstance(op, (int, np.integer)) and not isinstance(op, bool) and int(op) in MERGE_OPS.values():
+        return int(op)
+    raise ValueError(f"{what}: op is one of {', '.join(MERGE_OPS)}, not {op!r}")
+
+
+def merge_status_text(status):
+    """The bits of vkmr_hip_forest_merge_leaves_async's status word (info[0]), named."""
+    names = [text for bit, text in ((1, "bit 0: the offsets of A decrease or end past its cells"), (2, "bit 1: the offsets of B decrease or end past its cells"),
+                                    (4, "bit 2: a tree of A is not strictly increasing"), (8, "bit 3: a tree of B decreases"),
+                                    (16, "bit 4: the output has more leaves than cells")) if status & bit]
+    if status & ~31:
+        names.append("unknown bits")
+    return "; ".join(names) if names else "ok"
+
+
+def _raise_merge_status(info, what):
+    status = int(info[0])
+    if status:
+        raise RuntimeError(f"{what}: the device refused the merge (status {status}: {merge_status_text(status)})")
 
 
 def sorted_forest_packed(dev, batch, counts, max_count=None, reserve_trees=0, reserve_leaves=0):
