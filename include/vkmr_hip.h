@@ -1317,6 +1317,78 @@ VKMR_API vkmr_status vkmr_hip_verify_absence_async(int dev, vkmr_stream s, const
                                                    uint32_t* verdict_dev);
 
 /*
+ * RANGE PROOFS: "here is EVERY leaf of tree t between lo and hi, and none was left out", for a holder of the roots and counts of
+ * sorted trees.  The rules, csrc/range_plan.hpp.  A query is (trees_dev[q], lo_dev[q], hi_dev[q]): a tree and a CLOSED interval of
+ * digests in the order above; the all-zero and the all-ones digest say "from the start" and "to the end".  For tree t of c leaves,
+ * H = H(c):
+ *   i0 = the lower bound of lo;  i1 = the upper bound of hi (the lower bound, + 1 when the leaf there is hi)
+ *   the RUN is leaves [a, b]: a = i0 > 0 ? i0 - 1 : 0, b = i1 < c ? i1 : c - 1, m = b - a + 1 >= 1 -- the leaves in the range and the
+ *   neighbour on either side that fences them, where there is one; an empty range carries its fence alone (one or two leaves)
+ *   c == 0: first 0, m 0.  t >= ntrees or hi < lo: the query is REFUSED, first UINT64_MAX, m 0, height 0; the check answers 0
+ * THE GATHER (no hash; four small launches, a lane per carried leaf, a lane per (query, level)) writes
+ *   firsts_out_dev[q]       a
+ *   leaf_starts_out_dev     Q + 1 words: the exclusive prefix over m, formed in 64 bits; [Q] is the leaves carried
+ *   leaves_out_dev          the runs back to back: cells [leaf_starts[q], leaf_starts[q + 1]) are leaves a .. b of the tree
+ *   left_out_dev, right_out_dev   Q x stride cells each: left[l] = node (a >> l) - 1 of level l when (a >> l) is odd, right[l] = node
+ *                           (b >> l) + 1 when (b >> l) is even and that node exists (< ceil(c / 2^l)); zero cells otherwise and from H
+ *                           up.  The duplicate of a level's last node is NOT carried: the check duplicates by the count, as BIP37
+ *                           does, so that the count binds the right edge.  Every cell of both rows is written
+ *   heights_out_dev[q]      H (the forest call only)
+ *   info_dev[0..4)          status, leaves carried, queries refused, leaves in range
+ * Status bit 0: the leaves carried exceed leaves_capacity.  firsts, leaf_starts, the heights, the rows and info are valid then,
+ * info[1] is the true total, NO leaf is written; the caller allocates and calls again (leaves_capacity 0, leaves_out_dev NULL, is
+ * the counting call).  Nothing at or behind cell leaf_starts[Q] of leaves_out_dev is touched.  scratch_dev:
+ * vkmr_hip_range_scratch_bytes(0, Q) bytes, 16-byte aligned.  Refused as vkmr_hip_forest_absence_async refuses: a NULL pointer, a
+ * buffer off its grid, stride 0, above 63 or below the forest's H.  Q == 0 does nothing.  The one-tree twin reads one stored tree
+ * (vkmr_hip_reduce_tree_async; count >= 1, height == H(count), which is its stride) and writes no heights.
+ */
+VKMR_API size_t vkmr_hip_range_scratch_bytes(uint64_t nleaves, uint32_t Q);
+VKMR_API vkmr_status vkmr_hip_forest_range_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* forest_dev, uint64_t total,
+                                                 const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count, const uint32_t* trees_dev,
+                                                 const vkmr_digest* lo_dev, const vkmr_digest* hi_dev, uint32_t Q, uint32_t stride, void* scratch_dev,
+                                                 uint64_t* firsts_out_dev, uint64_t* leaf_starts_out_dev, vkmr_digest* leaves_out_dev,
+                                                 uint64_t leaves_capacity, vkmr_digest* left_out_dev, vkmr_digest* right_out_dev,
+                                                 uint32_t* heights_out_dev, uint64_t* info_dev);
+VKMR_API vkmr_status vkmr_hip_tree_range_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* tree_dev, uint64_t count,
+                                               uint32_t height, const vkmr_digest* lo_dev, const vkmr_digest* hi_dev, uint32_t Q, void* scratch_dev,
+                                               uint64_t* firsts_out_dev, uint64_t* leaf_starts_out_dev, vkmr_digest* leaves_out_dev,
+                                               uint64_t leaves_capacity, vkmr_digest* left_out_dev, vkmr_digest* right_out_dev, uint64_t* info_dev);
+/*
+ * THE CHECK of Q range proofs against roots_dev[ntrees] and counts_dev[ntrees]; nleaves is the cells of leaves_dev, at least
+ * leaf_starts[Q].  With t, a, the rows and the height as above, m = leaf_starts[q + 1] - leaf_starts[q] and c = counts_dev[t],
+ * verdict_dev[q] is 0 when
+ *   t >= ntrees;  height != H(c), or above stride;  c > 2^58;  a + m > c;  hi < lo;  m == 0 with c > 0
+ * and c == 0 is proven empty exactly when m == 0 and the root is all zero.  Otherwise it is 1 when all of this holds:
+ *   1. the carried leaves are strictly increasing
+ *   2. leaf[a] < lo, or a == 0;   3. leaf[b] > hi, or b == c - 1          (the fences)
+ *   4. leaf[a + 1] >= lo when m >= 2 and leaf[a] < lo; leaf[b - 1] <= hi when m >= 2 and leaf[b] > hi   (the canonical shape)
+ *   5. THE FOLD: the nodes of level l are [a >> l, b >> l]; parent p takes its left child 2p from left[l] when 2p < (a >> l), its
+ *      right child 2p + 1 from right[l] when 2p + 1 > (b >> l) and 2p + 1 < ceil(c / 2^l), and the left child again when 2p + 1 does
+ *      not exist.  After H levels the one node left must be the root.
+ * in_first_dev[q], in_count_dev[q]: the leaves of the run that lie in [lo, hi], as an index into the tree and a number; both 0 when
+ * the verdict is 0.  The position is bound: every left / right decision is taken from a, m and c, and no row cell is read that the
+ * rule does not name (the zero cells, and the cells at or above H, never).  leaf_starts that is no non-decreasing sequence ending at
+ * or below nleaves proves nothing: every verdict is 0.  SOUNDNESS: as with absence, the verdict binds under a root COMMITTED OVER A
+ * SORTED TREE.  The launches: a lane per query and a lane per leaf for the refusals, then ONE LAUNCH PER LEVEL (`stride` of them)
+ * with a lane per node of all ranges, then a lane per query.  scratch_dev: vkmr_hip_range_scratch_bytes(nleaves, Q) bytes, 16-byte
+ * aligned (0 for Q == 0 or nleaves above 2^58).  Refused: stride 0 or above 63, a NULL pointer, a buffer off its grid.  Q == 0 does
+ * nothing.  The one-tree twin checks against one root and one count; its stride is `height`, refused unless height == H(count) (0 for
+ * count == 0, when the rows may be NULL).  vkmr_host_cpu_forest_range, vkmr_host_cpu_tree_range and vkmr_host_cpu_verify_range
+ * (libvkmr_host.so) apply the same rules on the CPU.
+ */
+VKMR_API vkmr_status vkmr_hip_verify_forest_range_async(int dev, vkmr_stream s, const uint32_t* trees_dev, const vkmr_digest* lo_dev,
+                                                        const vkmr_digest* hi_dev, const uint64_t* firsts_dev, const uint64_t* leaf_starts_dev,
+                                                        const vkmr_digest* leaves_dev, uint64_t nleaves, const vkmr_digest* left_dev,
+                                                        const vkmr_digest* right_dev, const uint32_t* heights_dev, uint32_t Q, uint32_t stride,
+                                                        const vkmr_digest* roots_dev, const uint64_t* counts_dev, uint32_t ntrees, void* scratch_dev,
+                                                        uint32_t* verdict_dev, uint64_t* in_first_dev, uint64_t* in_count_dev);
+VKMR_API vkmr_status vkmr_hip_verify_range_async(int dev, vkmr_stream s, const vkmr_digest* lo_dev, const vkmr_digest* hi_dev,
+                                                 const uint64_t* firsts_dev, const uint64_t* leaf_starts_dev, const vkmr_digest* leaves_dev,
+                                                 uint64_t nleaves, const vkmr_digest* left_dev, const vkmr_digest* right_dev, uint32_t Q,
+                                                 uint32_t height, const vkmr_digest* root_dev, uint64_t count, void* scratch_dev,
+                                                 uint32_t* verdict_dev, uint64_t* in_first_dev, uint64_t* in_count_dev);
+
+/*
  * SORT THE LEAVES of a forest, tree by tree, on the device: what makes a sorted tree out of a set of digests without a trip
  * through the host.  A stable segmented sort of 32-byte digests: for every tree t the leaves at cells [offsets[t], offsets[t+1])
  * of digests_in_dev are written to the SAME cells of digests_out_dev in increasing order -- the order above (word 0 first, every

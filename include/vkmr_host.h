@@ -247,6 +247,30 @@ VKMR_API int vkmr_host_cpu_verify_absence(const vkmr_digest* queries, const uint
                                           const vkmr_digest* main_row, const vkmr_digest* low_row, const uint32_t* heights, uint32_t Q,
                                           uint32_t stride, const vkmr_digest* roots, const uint64_t* counts, uint32_t ntrees, uint32_t* verdict);
 
+/* ---- sorted trees: every leaf between two digests, proved complete (vkmr_hip_forest_range_async and its neighbours) ---- */
+
+/* The range proofs of vkmr_hip_forest_range_async, with no stored forest: the levels of a tree are built from its leaves, once per tree.
+ * firsts[Q], leaf_starts[Q + 1], leaves (leaves_capacity cells), the two rows of Q x stride cells, heights[Q] and info[0..4) = status,
+ * leaves carried, queries refused, leaves in range, as the device writes them; status bit 0 (no leaf written) when the leaves carried
+ * exceed leaves_capacity, the only limit.  -1 for a missing pointer, 1 for offsets that are no forest's, 2 when `stride` is below the
+ * height of a tree that a query names; nothing is written then. */
+VKMR_API int vkmr_host_cpu_forest_range(const vkmr_digest* digests, uint64_t total, const uint64_t* offsets, uint32_t ntrees, const uint32_t* trees,
+                                        const vkmr_digest* lo, const vkmr_digest* hi, uint32_t Q, uint32_t stride, uint64_t* firsts,
+                                        uint64_t* leaf_starts, vkmr_digest* leaves, uint64_t leaves_capacity, vkmr_digest* left_row,
+                                        vkmr_digest* right_row, uint32_t* heights, uint64_t* info);
+
+/* The same for one tree over digests[0 .. count): every query names it, no heights. */
+VKMR_API int vkmr_host_cpu_tree_range(const vkmr_digest* digests, uint64_t count, const vkmr_digest* lo, const vkmr_digest* hi, uint32_t Q,
+                                      uint32_t stride, uint64_t* firsts, uint64_t* leaf_starts, vkmr_digest* leaves, uint64_t leaves_capacity,
+                                      vkmr_digest* left_row, vkmr_digest* right_row, uint64_t* info);
+
+/* verdict[q], in_first[q], in_count[q] of vkmr_hip_verify_forest_range_async: range_plan.hpp's verdict() over the CPU's node hash. */
+VKMR_API int vkmr_host_cpu_verify_range(const uint32_t* trees, const vkmr_digest* lo, const vkmr_digest* hi, const uint64_t* firsts,
+                                        const uint64_t* leaf_starts, const vkmr_digest* leaves, uint64_t nleaves, const vkmr_digest* left_row,
+                                        const vkmr_digest* right_row, const uint32_t* heights, uint32_t Q, uint32_t stride,
+                                        const vkmr_digest* roots, const uint64_t* counts, uint32_t ntrees, uint32_t* verdict, uint64_t* in_first,
+                                        uint64_t* in_count);
+
 /* ---- the leaves of a forest sorted tree by tree, by the rule of vkmr_hip_forest_sort_leaves_async ---- */
 
 /* For every tree t the leaves at cells [offsets[t], offsets[t+1]) of digests_in, in increasing digest order (equal digests in input

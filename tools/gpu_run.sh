@@ -44,6 +44,9 @@
 #   merge [args]           tools/merge_timing.py: a batch merged into sorted trees (2^26 leaves as 2^15 trees of 2 048 and as one tree): the union with
 #                          2^10, 2^16, 2^20 and 2^24 new digests, the difference at 2^16, the union and the stored build, beside the parent's route
 #                          (the concatenation sorted again by vkmr_hip_forest_sort_leaves_async) and vkmr_hip_forest_copy_trees_async (one JSON line)
+#   range [args]           tools/range_timing.py: range proofs over sorted trees (2^26 leaves as 2^15 trees of 2 048 and as one tree): gather, check and
+#                          counting call for 2^10, 2^16 and 2^20 ranges of 16 leaves, 2^10 ranges of 2^16, every tree whole, beside the parent's route
+#                          (vkmr_hip_forest_multiproof_async over explicit entries and its check) and vkmr_hip_reduce_forest_async (one JSON line)
 #   forest_repack [args]   tools/forest_repack_timing.py: the oldest trees of a stored forest dropped and the rest (or all) copied into an
 #                          empty forest, beside the stored build over the same leaves (one JSON line)
 #   cumask                 tools/cu_mask_probe.py: where CU-mask bits land, map/reduce on half the CUs with and without neighbours
@@ -250,6 +253,11 @@ merge)
   timeout -k 10 900 python3 tools/merge_timing.py "$@" --out $OUT/merge_timing.json > /dev/null 2> $OUT/merge_timing.err && echo "merge_timing ok" &&
   cat $OUT/merge_timing.json
   echo "merge rc=$?"
+  ;;
+range)
+  timeout -k 10 900 python3 tools/range_timing.py "$@" --out $OUT/range_timing.json > /dev/null 2> $OUT/range_timing.err && echo "range_timing ok" &&
+  cat $OUT/range_timing.json
+  echo "range rc=$?"
   ;;
 forest_repack)
   timeout -k 10 500 python3 tools/forest_repack_timing.py "$@" --out $OUT/forest_repack_timing.json > /dev/null 2> $OUT/forest_repack_timing.err && echo "forest_repack_timing ok" &&

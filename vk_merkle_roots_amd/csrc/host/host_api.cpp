@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "../absence_plan.hpp"
+#include "../range_plan.hpp"
 #include "../audit_plan.hpp"   // forest_plan.hpp, tree_plan.hpp: where the stored levels lie
 #include "../consistency_plan.hpp"
 #include "../frontier_plan.hpp"
@@ -1112,6 +1113,105 @@ int vkmr_host_cpu_verify_absence(const vkmr_digest* queries, const uint32_t* tre
                                            stride ? main_row[(size_t)q * stride].data : nullptr, stride ? low_row[(size_t)q * stride].data : nullptr,
                                            heights[q], stride, known ? roots[t].data : nullptr, known ? counts[t] : 0ull,
                                            [](const uint32_t* a, const uint32_t* b, uint32_t* out) { vkmr::cpu_sha256d_pair(a, b, out); });
+    }
+    return 0;
+}
+
+// ---- sorted trees: every leaf between two digests, proved complete (range_plan.hpp)
+
+int vkmr_host_cpu_forest_range(const vkmr_digest* digests, uint64_t total, const uint64_t* offsets, uint32_t ntrees, const uint32_t* trees,
+                               const vkmr_digest* lo, const vkmr_digest* hi, uint32_t Q, uint32_t stride, uint64_t* firsts, uint64_t* leaf_starts,
+                               vkmr_digest* leaves, uint64_t leaves_capacity, vkmr_digest* left_row, vkmr_digest* right_row, uint32_t* heights,
+                               uint64_t* info)
+{
+    if (Q == 0) return 0;
+    if (!trees || !lo || !hi || !firsts || !leaf_starts || !heights || !info || (leaves_capacity > 0 && !leaves) ||
+        (stride > 0 && (!left_row || !right_row)) || (ntrees > 0 && !offsets))
+        return -1;
+    if (absence_offsets_bad(offsets, ntrees, total)) return 1;
+    if (ntrees > 0 && !digests && offsets[ntrees] > offsets[0]) return -1;
+    for (uint32_t q = 0; q < Q; ++q)
+        if (trees[q] < ntrees && vkmr_absence::height(offsets[trees[q] + 1] - offsets[trees[q]]) > stride) return 2;
+    info[0] = info[1] = info[2] = info[3] = 0;
+    for (uint32_t q = 0; q < Q; ++q) {
+        const bool known = trees[q] < ntrees;
+        const vkmr_digest* leaf = known ? digests + offsets[trees[q]] : nullptr;
+        const uint64_t c = known ? offsets[trees[q] + 1] - offsets[trees[q]] : 0;
+        const vkmr_range::Run r = vkmr_range::run(
+            known, c, lo[q].data, hi[q].data, [&](uint64_t i, const uint32_t* x) { return vkmr_absence::less(leaf[i].data, x); },
+            [&](uint64_t i, const uint32_t* x) { return vkmr_absence::equal(leaf[i].data, x); });
+        firsts[q] = r.first;
+        heights[q] = r.height;
+        leaf_starts[q] = info[1];
+        info[1] += r.m;
+        info[2] += r.first == vkmr_range::NONE ? 1 : 0;
+        info[3] += r.inside;
+    }
+    leaf_starts[Q] = info[1];
+    if (stride > 0) {
+        std::memset(left_row, 0, sizeof(vkmr_digest) * (size_t)Q * stride);
+        std::memset(right_row, 0, sizeof(vkmr_digest) * (size_t)Q * stride);
+    }
+    if (info[1] > leaves_capacity) info[0] = VKMR_RANGE_LEAVES_CAPACITY;
+    std::vector<uint32_t> order;
+    for (uint32_t q = 0; q < Q; ++q)
+        if (leaf_starts[q + 1] > leaf_starts[q]) order.push_back(q);
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) { return trees[x] < trees[y]; });
+    std::vector<std::vector<vkmr_digest>> levels;
+    for (size_t n = 0; n < order.size(); ++n) {
+        const uint32_t q = order[n], t = trees[q];
+        const vkmr_digest* leaf = digests + offsets[t];
+        const uint64_t c = offsets[t + 1] - offsets[t], a = firsts[q], m = leaf_starts[q + 1] - leaf_starts[q], b = a + m - 1;
+        const uint32_t h = heights[q];
+        if (n == 0 || trees[order[n - 1]] != t) tree_levels(leaf, leaf + c, h, levels);
+        if (info[0] == 0)
+            for (uint64_t j = 0; j < m; ++j) leaves[leaf_starts[q] + j] = leaf[a + j];
+        for (uint32_t l = 0; l < h; ++l) {
+            if (vkmr_range::left_cell(a, l, h)) left_row[(size_t)q * stride + l] = levels[l][(a >> l) - 1];
+            if (vkmr_range::right_cell(b, c, l, h)) right_row[(size_t)q * stride + l] = levels[l][(b >> l) + 1];
+        }
+    }
+    return 0;
+}
+
+int vkmr_host_cpu_tree_range(const vkmr_digest* digests, uint64_t count, const vkmr_digest* lo, const vkmr_digest* hi, uint32_t Q, uint32_t stride,
+                             uint64_t* firsts, uint64_t* leaf_starts, vkmr_digest* leaves, uint64_t leaves_capacity, vkmr_digest* left_row,
+                             vkmr_digest* right_row, uint64_t* info)
+{
+    if (Q == 0) return 0;
+    const uint64_t offsets[2] = {0, count};
+    std::vector<uint32_t> trees(Q, 0u), heights(Q);
+    return vkmr_host_cpu_forest_range(digests, count, offsets, 1, trees.data(), lo, hi, Q, stride, firsts, leaf_starts, leaves, leaves_capacity, left_row,
+                                      right_row, heights.data(), info);
+}
+
+int vkmr_host_cpu_verify_range(const uint32_t* trees, const vkmr_digest* lo, const vkmr_digest* hi, const uint64_t* firsts, const uint64_t* leaf_starts,
+                               const vkmr_digest* leaves, uint64_t nleaves, const vkmr_digest* left_row, const vkmr_digest* right_row,
+                               const uint32_t* heights, uint32_t Q, uint32_t stride, const vkmr_digest* roots, const uint64_t* counts, uint32_t ntrees,
+                               uint32_t* verdict, uint64_t* in_first, uint64_t* in_count)
+{
+    if (Q == 0) return 0;
+    if (!trees || !lo || !hi || !firsts || !leaf_starts || !heights || !verdict || !in_first || !in_count || (nleaves > 0 && !leaves) ||
+        (stride > 0 && (!left_row || !right_row)) || (ntrees > 0 && (!roots || !counts)) || stride > 63)
+        return -1;
+    bool prefix = true;                          // leaf_starts is no prefix over [0, nleaves]: nothing is proven
+    for (uint32_t q = 0; q < Q; ++q) prefix = prefix && leaf_starts[q] <= leaf_starts[q + 1] && leaf_starts[q + 1] <= nleaves;
+    std::vector<uint32_t> work;
+    for (uint32_t q = 0; q < Q; ++q) {
+        const uint32_t t = trees[q];
+        const bool known = t < ntrees;
+        vkmr_range::Verdict v{0u, 0ull, 0ull};
+        if (prefix) {
+            const uint64_t m = leaf_starts[q + 1] - leaf_starts[q];
+            work.resize(8 * (size_t)m + 8);
+            v = vkmr_range::verdict(t, ntrees, lo[q].data, hi[q].data, firsts[q], m, m ? leaves[leaf_starts[q]].data : nullptr,
+                                    stride ? left_row[(size_t)q * stride].data : nullptr, stride ? right_row[(size_t)q * stride].data : nullptr, heights[q],
+                                    stride, known ? roots[t].data : nullptr, known ? counts[t] : 0ull, work.data(),
+                                    [](const uint32_t* a, const uint32_t* b, uint32_t* out) { vkmr::cpu_sha256d_pair(a, b, out); });
+        }
+        verdict[q] = v.verdict;
+        in_first[q] = v.in_first;
+        in_count[q] = v.in_count;
     }
     return 0;
 }

@@ -40,6 +40,9 @@
 //                                              pair out of order per tree, the lower bound of a digest, the two neighbours and their
 //                                              compact pair of proofs gathered (no hash), and the verdict absent / present, one lane
 //                                              per proof through one hash_pair (rules: absence_plan.hpp)
+//   range_kernels.hpp  *_range_runs_kernel .. *_range_rows_kernel, *_range_heads_kernel .. *_range_verdict_kernel   sorted trees: every leaf
+//                                              between two digests with the two rows that close its run (no hash), and the check that
+//                                              none was left out: one launch per level, a lane per node of all ranges (rules: range_plan.hpp)
 //   leafsort_kernels.hpp  *_leafsort_keys_kernel, *_leafsort_ties_kernel, *_leafsort_place_kernel, *_leafsort_emit_kernel   the leaves of a
 //                                              forest sorted tree by tree in digest order: sort_kernels.hpp's radix passes over
 //                                              (tree, digest prefix) keys, then the few ties placed by all 256 bits; no hash
@@ -80,6 +83,7 @@
 //   diff_plan.hpp       one step of a diff's descent, the bound on every step's frontier and the scratch layout
 //   audit_plan.hpp      the ballot words of an audit's levels, the nodes it checks and the scratch layout
 //   merkleblock_plan.hpp  what a BIP37 walk appends between two matched leaves, in closed form; the three size bounds, the scratch layout
+//   range_plan.hpp      the run a closed interval of digests carries, the cells of its two rows, the check's steps and level layout
 //   absence_plan.hpp    the order on digests, the lower bound's loop, the cells of an absence proof and the verdict of its check
 //   leafsort_plan.hpp   the leaf sort's key and passes, its elements and sentinel, what a tie is, the tie limit and the scratch layout
 //   merge_plan.hpp      the merge's slots, what a leaf of B does at its slot, where every leaf goes, the counts and the scratch layout
@@ -122,6 +126,7 @@ using vkmr_dev::Node;
 #include "proofs_at_kernels.hpp"
 #include "merkleblock_kernels.hpp"
 #include "absence_kernels.hpp"
+#include "range_kernels.hpp"
 #include "leafsort_kernels.hpp"
 #include "merge_kernels.hpp"
 
@@ -1667,6 +1672,171 @@ vkmr_status vkmr_hip_verify_absence_async(int dev, vkmr_stream s, const vkmr_dig
     VKMR_TRY(hipSetDevice(dev));
     return launch(tree_absence_fold_kernel, grid_of(Q), dim3(256), S(s), nodes(queries_dev), indices_dev, nodes(neighbours_dev), nodes(main_dev),
                   nodes(low_dev), Q, height, nodes(root_dev), count, verdict_dev);
+}
+
+// ---- sorted trees: every leaf between two digests, proved complete (range_kernels.hpp, range_plan.hpp) ----------------------------
+
+size_t vkmr_hip_range_scratch_bytes(uint64_t nleaves, uint32_t Q)
+{
+    if (Q == 0 || nleaves > (1ull << 58)) return 0;
+    return (size_t)vkmr_range::layout(nleaves, Q).bytes;
+}
+
+namespace {
+// The parts of a range call's scratch_dev as the kernels take them.
+struct RangeScratch {
+    uint32_t *bad, *ok;
+    uint64_t* sums;
+    Node *tops, *odd, *even;
+    RangeScratch(void* scratch_dev, const vkmr_range::Layout& L)
+    {
+        const uintptr_t at = reinterpret_cast<uintptr_t>(scratch_dev);
+        bad = reinterpret_cast<uint32_t*>(at);
+        sums = reinterpret_cast<uint64_t*>(at + L.sums);
+        ok = reinterpret_cast<uint32_t*>(at + L.ok);
+        tops = reinterpret_cast<Node*>(at + L.tops);
+        odd = reinterpret_cast<Node*>(at + L.odd);
+        even = reinterpret_cast<Node*>(at + L.even);
+    }
+};
+
+// What the two gathers and the two checks refuse of their proof buffers alike: a missing one, one off its grid, too many cells.
+vkmr_status range_buffers_check(const char* who, const void* lo, const void* hi, const void* firsts, const void* leaf_starts, const void* leaves,
+                                uint64_t nleaves, const void* left_row, const void* right_row, const void* scratch, uint32_t Q, uint32_t stride)
+{
+    if (!lo || !hi || !firsts || !leaf_starts || !scratch || (nleaves > 0 && !leaves) || (stride > 0 && (!left_row || !right_row)))
+        return refuse(who, "null pointer");
+    if (off_grid(lo, 16) || off_grid(hi, 16) || off_grid(leaves, 16) || off_grid(left_row, 16) || off_grid(right_row, 16) || off_grid(firsts, 8) ||
+        off_grid(leaf_starts, 8))
+        return refuse(who, "misaligned buffer");
+    if (off_grid(scratch, 16)) return refuse(who, "scratch must be 16-byte aligned");
+    if (nleaves > (1ull << 58)) return refuse(who, "too many leaves");
+    if (grid_too_large(groups_of((uint64_t)Q + 1)) || grid_too_large(groups_of(vkmr_range::level_cells(nleaves, Q, 0))))
+        return refuse(who, "too many leaves or queries in one call");
+    return VKMR_OK;
+}
+}  // namespace
+
+vkmr_status vkmr_hip_forest_range_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* forest_dev, uint64_t total,
+                                        const uint64_t* offsets_dev, uint32_t ntrees, uint64_t max_count, const uint32_t* trees_dev,
+                                        const vkmr_digest* lo_dev, const vkmr_digest* hi_dev, uint32_t Q, uint32_t stride, void* scratch_dev,
+                                        uint64_t* firsts_out_dev, uint64_t* leaf_starts_out_dev, vkmr_digest* leaves_out_dev, uint64_t leaves_capacity,
+                                        vkmr_digest* left_out_dev, vkmr_digest* right_out_dev, uint32_t* heights_out_dev, uint64_t* info_dev)
+{
+    if (Q == 0) return VKMR_OK;
+    if ((!digests_dev && total > 0) || !forest_dev || !offsets_dev || !trees_dev || !heights_out_dev || !info_dev) return refuse(__func__, "null pointer");
+    if (stride == 0 || stride > 63) return refuse(__func__, "stride must be 1..63");
+    VKMR_CHECK(range_buffers_check(__func__, lo_dev, hi_dev, firsts_out_dev, leaf_starts_out_dev, leaves_out_dev, leaves_capacity, left_out_dev,
+                                   right_out_dev, scratch_dev, Q, stride));
+    VKMR_CHECK(forest_args_check(__func__, total, ntrees, max_count, Q, nullptr, nullptr));
+    if (off_grid(digests_dev, 16) || off_grid(forest_dev, 16) || off_grid(offsets_dev, 8) || off_grid(trees_dev, 4) || off_grid(heights_out_dev, 4) ||
+        off_grid(info_dev, 8))
+        return refuse(__func__, "misaligned buffer");
+    const uint32_t H = vkmr_forest::launches(total, max_count);   // <= 58
+    if (stride < H) return refuse(__func__, "stride is below the forest's levels");
+    const ForestLevels lv = forest_levels(total, ntrees, H);
+    const vkmr_range::Layout L = vkmr_range::layout(0, Q);
+    const RangeScratch sc(scratch_dev, L);
+    unsigned long long* info = reinterpret_cast<unsigned long long*>(info_dev);
+    const dim3 qgrid((uint32_t)L.groups), qblock(VKMR_RANGE_THREADS);
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_TRY(hipMemsetAsync(info_dev, 0, 4 * sizeof(uint64_t), S(s)));
+    VKMR_CHECK(launch(forest_range_runs_kernel, qgrid, qblock, S(s), nodes(digests_dev), offsets_dev, ntrees, total, trees_dev, nodes(lo_dev), nodes(hi_dev),
+                      Q, firsts_out_dev, leaf_starts_out_dev, heights_out_dev, sc.sums, info));
+    VKMR_CHECK(launch(range_starts_kernel, dim3(1), qblock, S(s), sc.sums, L.groups, leaves_capacity, info));
+    VKMR_CHECK(launch(range_places_kernel, qgrid, qblock, S(s), sc.sums, Q, leaf_starts_out_dev));
+    if (leaves_capacity > 0)
+        VKMR_CHECK(launch(forest_range_leaves_kernel, grid_of(leaves_capacity), dim3(256), S(s), nodes(digests_dev), offsets_dev, ntrees, total, trees_dev, Q,
+                          firsts_out_dev, leaf_starts_out_dev, info, nodes(leaves_out_dev)));
+    return launch(forest_range_rows_kernel, grid_of(Q, stride), dim3(256), S(s), nodes(digests_dev), nodes(forest_dev), lv, offsets_dev, ntrees, total,
+                  trees_dev, firsts_out_dev, leaf_starts_out_dev, Q, stride, nodes(left_out_dev), nodes(right_out_dev));
+}
+
+vkmr_status vkmr_hip_tree_range_async(int dev, vkmr_stream s, const vkmr_digest* digests_dev, const vkmr_digest* tree_dev, uint64_t count,
+                                      uint32_t height, const vkmr_digest* lo_dev, const vkmr_digest* hi_dev, uint32_t Q, void* scratch_dev,
+                                      uint64_t* firsts_out_dev, uint64_t* leaf_starts_out_dev, vkmr_digest* leaves_out_dev, uint64_t leaves_capacity,
+                                      vkmr_digest* left_out_dev, vkmr_digest* right_out_dev, uint64_t* info_dev)
+{
+    if (Q == 0) return VKMR_OK;
+    if (!digests_dev || !tree_dev || !info_dev) return refuse(__func__, "null pointer");
+    if (count == 0 || count > (1ull << 58) || height != vkmr_math::height(count)) return refuse(__func__, "height must be max(1, ceil(log2 count))");
+    VKMR_CHECK(range_buffers_check(__func__, lo_dev, hi_dev, firsts_out_dev, leaf_starts_out_dev, leaves_out_dev, leaves_capacity, left_out_dev,
+                                   right_out_dev, scratch_dev, Q, height));
+    if (off_grid(digests_dev, 16) || off_grid(tree_dev, 16) || off_grid(info_dev, 8)) return refuse(__func__, "misaligned buffer");
+    const TreeLevels lv = tree_levels(count, height);
+    const vkmr_range::Layout L = vkmr_range::layout(0, Q);
+    const RangeScratch sc(scratch_dev, L);
+    unsigned long long* info = reinterpret_cast<unsigned long long*>(info_dev);
+    const dim3 qgrid((uint32_t)L.groups), qblock(VKMR_RANGE_THREADS);
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_TRY(hipMemsetAsync(info_dev, 0, 4 * sizeof(uint64_t), S(s)));
+    VKMR_CHECK(launch(tree_range_runs_kernel, qgrid, qblock, S(s), nodes(digests_dev), count, nodes(lo_dev), nodes(hi_dev), Q, firsts_out_dev,
+                      leaf_starts_out_dev, sc.sums, info));
+    VKMR_CHECK(launch(range_starts_kernel, dim3(1), qblock, S(s), sc.sums, L.groups, leaves_capacity, info));
+    VKMR_CHECK(launch(range_places_kernel, qgrid, qblock, S(s), sc.sums, Q, leaf_starts_out_dev));
+    if (leaves_capacity > 0)
+        VKMR_CHECK(launch(tree_range_leaves_kernel, grid_of(leaves_capacity), dim3(256), S(s), nodes(digests_dev), count, Q, firsts_out_dev,
+                          leaf_starts_out_dev, info, nodes(leaves_out_dev)));
+    return launch(tree_range_rows_kernel, grid_of(Q, height), dim3(256), S(s), nodes(digests_dev), nodes(tree_dev), lv, count, firsts_out_dev,
+                  leaf_starts_out_dev, Q, height, nodes(left_out_dev), nodes(right_out_dev));
+}
+
+vkmr_status vkmr_hip_verify_forest_range_async(int dev, vkmr_stream s, const uint32_t* trees_dev, const vkmr_digest* lo_dev, const vkmr_digest* hi_dev,
+                                               const uint64_t* firsts_dev, const uint64_t* leaf_starts_dev, const vkmr_digest* leaves_dev,
+                                               uint64_t nleaves, const vkmr_digest* left_dev, const vkmr_digest* right_dev, const uint32_t* heights_dev,
+                                               uint32_t Q, uint32_t stride, const vkmr_digest* roots_dev, const uint64_t* counts_dev, uint32_t ntrees,
+                                               void* scratch_dev, uint32_t* verdict_dev, uint64_t* in_first_dev, uint64_t* in_count_dev)
+{
+    if (Q == 0) return VKMR_OK;
+    if (!trees_dev || !heights_dev || !verdict_dev || !in_first_dev || !in_count_dev || (ntrees > 0 && (!roots_dev || !counts_dev)))
+        return refuse(__func__, "null pointer");
+    if (stride == 0 || stride > 63) return refuse(__func__, "stride must be 1..63");
+    VKMR_CHECK(range_buffers_check(__func__, lo_dev, hi_dev, firsts_dev, leaf_starts_dev, leaves_dev, nleaves, left_dev, right_dev, scratch_dev, Q, stride));
+    if (off_grid(roots_dev, 16) || off_grid(counts_dev, 8) || off_grid(trees_dev, 4) || off_grid(heights_dev, 4) || off_grid(verdict_dev, 4) ||
+        off_grid(in_first_dev, 8) || off_grid(in_count_dev, 8))
+        return refuse(__func__, "misaligned buffer");
+    const vkmr_range::Layout L = vkmr_range::layout(nleaves, Q);
+    const RangeScratch sc(scratch_dev, L);
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_TRY(hipMemsetAsync(scratch_dev, 0, 32, S(s)));
+    VKMR_CHECK(launch(forest_range_heads_kernel, grid_of(Q), dim3(256), S(s), trees_dev, heights_dev, nodes(roots_dev), counts_dev, ntrees, nodes(lo_dev),
+                      nodes(hi_dev), firsts_dev, leaf_starts_dev, nodes(leaves_dev), nleaves, Q, stride, sc.bad, sc.ok, in_first_dev, in_count_dev));
+    if (nleaves >= 2) VKMR_CHECK(launch(range_order_kernel, grid_of(nleaves - 1), dim3(256), S(s), leaf_starts_dev, nodes(leaves_dev), nleaves, Q, sc.ok));
+    for (uint32_t l = 0; l < stride; ++l) {      // level l + 1 from level l: odd levels in one buffer, even ones in the other
+        const uint64_t cells = vkmr_range::level_cells(nleaves, Q, l + 1);
+        VKMR_CHECK(launch(forest_range_level_kernel, grid_of(cells), dim3(256), S(s), trees_dev, heights_dev, counts_dev, ntrees, firsts_dev, leaf_starts_dev,
+                          nodes(leaves_dev), nleaves, nodes(left_dev), nodes(right_dev), Q, stride, l, sc.bad, sc.ok, (l & 1u) ? sc.odd : sc.even,
+                          (l & 1u) ? sc.even : sc.odd, sc.tops));
+    }
+    return launch(forest_range_verdict_kernel, grid_of(Q), dim3(256), S(s), trees_dev, heights_dev, nodes(roots_dev), counts_dev, ntrees, Q, sc.bad, sc.ok,
+                  sc.tops, verdict_dev, in_first_dev, in_count_dev);
+}
+
+vkmr_status vkmr_hip_verify_range_async(int dev, vkmr_stream s, const vkmr_digest* lo_dev, const vkmr_digest* hi_dev, const uint64_t* firsts_dev,
+                                        const uint64_t* leaf_starts_dev, const vkmr_digest* leaves_dev, uint64_t nleaves, const vkmr_digest* left_dev,
+                                        const vkmr_digest* right_dev, uint32_t Q, uint32_t height, const vkmr_digest* root_dev, uint64_t count,
+                                        void* scratch_dev, uint32_t* verdict_dev, uint64_t* in_first_dev, uint64_t* in_count_dev)
+{
+    if (Q == 0) return VKMR_OK;
+    if (!root_dev || !verdict_dev || !in_first_dev || !in_count_dev) return refuse(__func__, "null pointer");
+    if (height > 63 || height != vkmr_absence::height(count)) return refuse(__func__, "height must be max(1, ceil(log2 count)), 0 for no leaf");
+    VKMR_CHECK(range_buffers_check(__func__, lo_dev, hi_dev, firsts_dev, leaf_starts_dev, leaves_dev, nleaves, left_dev, right_dev, scratch_dev, Q, height));
+    if (off_grid(root_dev, 16) || off_grid(verdict_dev, 4) || off_grid(in_first_dev, 8) || off_grid(in_count_dev, 8))
+        return refuse(__func__, "misaligned buffer");
+    const vkmr_range::Layout L = vkmr_range::layout(nleaves, Q);
+    const RangeScratch sc(scratch_dev, L);
+    VKMR_TRY(hipSetDevice(dev));
+    VKMR_TRY(hipMemsetAsync(scratch_dev, 0, 32, S(s)));
+    VKMR_CHECK(launch(tree_range_heads_kernel, grid_of(Q), dim3(256), S(s), height, nodes(root_dev), count, nodes(lo_dev), nodes(hi_dev), firsts_dev,
+                      leaf_starts_dev, nodes(leaves_dev), nleaves, Q, sc.bad, sc.ok, in_first_dev, in_count_dev));
+    if (nleaves >= 2) VKMR_CHECK(launch(range_order_kernel, grid_of(nleaves - 1), dim3(256), S(s), leaf_starts_dev, nodes(leaves_dev), nleaves, Q, sc.ok));
+    for (uint32_t l = 0; l < height; ++l) {
+        const uint64_t cells = vkmr_range::level_cells(nleaves, Q, l + 1);
+        VKMR_CHECK(launch(tree_range_level_kernel, grid_of(cells), dim3(256), S(s), height, count, firsts_dev, leaf_starts_dev, nodes(leaves_dev), nleaves,
+                          nodes(left_dev), nodes(right_dev), Q, l, sc.bad, sc.ok, (l & 1u) ? sc.odd : sc.even, (l & 1u) ? sc.even : sc.odd, sc.tops));
+    }
+    return launch(tree_range_verdict_kernel, grid_of(Q), dim3(256), S(s), height, nodes(root_dev), count, Q, sc.bad, sc.ok, sc.tops, verdict_dev,
+                  in_first_dev, in_count_dev);
 }
 
 // ---- partial Merkle trees in BIP37 order (merkleblock_kernels.hpp, merkleblock_plan.hpp) ----------------------------------------

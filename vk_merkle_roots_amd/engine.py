@@ -866,6 +866,40 @@ class HipDevice:
         AbsenceProofs -- against roots [ntrees, 8] and counts [ntrees]; verified on the device."""
         return AbsenceProofs(trees, queries, indices, pred, succ, main, low, heights).verify(self, roots, counts)
 
+    def range_scratch_bytes(self, nleaves, Q):
+        """Bytes of scratch_buf for the range calls on Q queries: the gathers take range_scratch_bytes(0, Q), the checks
+        range_scratch_bytes(nleaves, Q) with nleaves the cells of their leaves."""
+        return self.lib.vkmr_hip_range_scratch_bytes(nleaves, Q)
+
+    def forest_range_enqueue(self, digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, trees_buf, lo_buf, hi_buf, Q, stride, scratch_buf,
+                             firsts_buf, leaf_starts_buf, leaves_buf, leaves_capacity, left_buf, right_buf, heights_buf, info_buf, stream=None):
+        """The range proofs of Q queries (trees_buf uint32, lo_buf and hi_buf digests: closed intervals) out of a stored forest: Q
+        uint64 firsts, Q + 1 uint64 leaf_starts, the carried leaves back to back (leaves_capacity cells; None with 0 only counts),
+        two rows of Q x stride cells, Q uint32 heights and info_buf (4 uint64: status, leaves carried, queries refused, leaves in
+        range; range_status_text names the status bits).  No hash.  All in device memory.  include/vkmr_hip.h."""
+        self._call("vkmr_hip_forest_range_async", digests_buf, forest_buf, total, offsets_buf, ntrees, max_count, trees_buf, lo_buf, hi_buf, Q, stride,
+                   scratch_buf, firsts_buf, leaf_starts_buf, leaves_buf, leaves_capacity, left_buf, right_buf, heights_buf, info_buf, stream=stream)
+
+    def tree_range_enqueue(self, digests_buf, tree_buf, count, height, lo_buf, hi_buf, Q, scratch_buf, firsts_buf, leaf_starts_buf, leaves_buf,
+                           leaves_capacity, left_buf, right_buf, info_buf, stream=None):
+        """forest_range_enqueue for ONE stored tree of height max(1, ceil(log2 count)): rows of Q x height cells, no heights."""
+        self._call("vkmr_hip_tree_range_async", digests_buf, tree_buf, count, height, lo_buf, hi_buf, Q, scratch_buf, firsts_buf, leaf_starts_buf,
+                   leaves_buf, leaves_capacity, left_buf, right_buf, info_buf, stream=stream)
+
+    def verify_forest_range_enqueue(self, trees_buf, lo_buf, hi_buf, firsts_buf, leaf_starts_buf, leaves_buf, nleaves, left_buf, right_buf, heights_buf,
+                                    Q, stride, roots_buf, counts_buf, ntrees, scratch_buf, verdict_buf, in_first_buf, in_count_buf, stream=None):
+        """verdict_buf[q] (uint32) = 1 when the leaves carried for query q are ALL the leaves of tree trees_buf[q] in [lo, hi] (and
+        their fences) under roots_buf[ntrees] and counts_buf[ntrees] (uint64), 0 otherwise; in_first_buf / in_count_buf (uint64): the
+        leaves inside the bounds.  scratch_buf: range_scratch_bytes(nleaves, Q).  All in device memory.  include/vkmr_hip.h."""
+        self._call("vkmr_hip_verify_forest_range_async", trees_buf, lo_buf, hi_buf, firsts_buf, leaf_starts_buf, leaves_buf, nleaves, left_buf, right_buf,
+                   heights_buf, Q, stride, roots_buf, counts_buf, ntrees, scratch_buf, verdict_buf, in_first_buf, in_count_buf, stream=stream)
+
+    def verify_range_enqueue(self, lo_buf, hi_buf, firsts_buf, leaf_starts_buf, leaves_buf, nleaves, left_buf, right_buf, Q, height, root_buf, count,
+                             scratch_buf, verdict_buf, in_first_buf, in_count_buf, stream=None):
+        """verify_forest_range_enqueue against ONE root (root_buf, one cell) and one count: rows of Q x height cells."""
+        self._call("vkmr_hip_verify_range_async", lo_buf, hi_buf, firsts_buf, leaf_starts_buf, leaves_buf, nleaves, left_buf, right_buf, Q, height,
+                   root_buf, count, scratch_buf, verdict_buf, in_first_buf, in_count_buf, stream=stream)
+
     # -- the leaves of a forest sorted on the device, tree by tree, in the order an absence proof rests on -------------------------
     def sort_leaves_scratch_bytes(self, total):
         return self.lib.vkmr_hip_sort_leaves_scratch_bytes(total)
@@ -1393,6 +1427,36 @@ class _Stored:
                                  self.dev.download(d_main, 32 * Q * stride).reshape(Q, stride, 8),
                                  self.dev.download(d_low, 32 * Q * stride).reshape(Q, stride, 8), heights)
 
+    def _ranges(self, trees, lo, hi, stride):
+        t, x = self._queries(trees, lo, "ranges")
+        y = _host(hi, np.uint32, -1, 8)
+        if y.shape[0] != x.shape[0]:
+            raise ValueError("ranges: one upper bound per lower bound")
+        if not 1 <= stride <= 63:
+            raise ValueError("ranges: stride in 1..63")
+        Q = int(x.shape[0])
+        if Q == 0:
+            return RangeProofs(t, x, y, np.zeros(0, np.uint64), np.zeros(1, np.uint64), np.zeros((0, 8), np.uint32),
+                               *(np.zeros((0, stride, 8), np.uint32),) * 2, np.zeros(0, np.uint32), np.zeros(4, np.uint64))
+        dev = self.dev
+        with dev.scope() as tmp:
+            d_first, d_starts, d_left, d_right, d_info = tmp.alloc(8 * Q), tmp.alloc(8 * (Q + 1)), tmp.alloc(32 * Q * stride), tmp.alloc(32 * Q * stride), tmp.alloc(32)
+            call = self._range_call(tmp, t, tmp.upload(x), tmp.upload(y), Q, stride, tmp.alloc(dev.range_scratch_bytes(0, Q)), d_first, d_starts, d_left,
+                                    d_right, d_info)
+            heights = call(None, 0)                  # the counting call: info[1] is what the leaves need
+            n = int(dev.download(d_info, 32, dtype=np.uint64)[1])
+            leaves = np.zeros((0, 8), np.uint32)
+            if n:
+                d_leaves = tmp.alloc(32 * n)
+                heights = call(d_leaves, n)
+                leaves = dev.download(d_leaves, 32 * n).reshape(n, 8)
+            info = dev.download(d_info, 32, dtype=np.uint64)
+            if int(info[0]):
+                raise RuntimeError(f"{type(self).__name__}.ranges: status {int(info[0])}: {range_status_text(int(info[0]))}")
+            return RangeProofs(t, x, y, dev.download(d_first, 8 * Q, dtype=np.uint64), dev.download(d_starts, 8 * (Q + 1), dtype=np.uint64), leaves,
+                               dev.download(d_left, 32 * Q * stride).reshape(Q, stride, 8), dev.download(d_right, 32 * Q * stride).reshape(Q, stride, 8),
+                               heights, info)
+
     def _no_proofs(self, k):
         """What k proofs without a cell are: (siblings [k, stride, 8], *the proof columns), all zero."""
         return (np.zeros((k, self.stride, 8), dtype=np.uint32), *(np.zeros(k, dtype=t) for t in self._proof_columns))
@@ -1755,6 +1819,26 @@ class MerkleTree(_Stored):
         leaf of this tree -- or that it is one.  The verdict binds when the tree is sorted: is_sorted()."""
         self._absence_height()
         return self._absence(None, digests, self.height)
+
+    def range_async(self, lo_buf, hi_buf, Q, scratch_buf, firsts_buf, leaf_starts_buf, leaves_buf, leaves_capacity, left_buf, right_buf, info_buf,
+                    stream=None):
+        """The range proofs of the Q closed intervals [lo_buf[q], hi_buf[q]], all in device memory.  HipDevice.tree_range_enqueue; a
+        tree stored with height max(1, ceil(log2 count)) only."""
+        self._absence_height()
+        self.dev.tree_range_enqueue(self.digests, self.tree, self.count, self.height, lo_buf, hi_buf, Q, scratch_buf, firsts_buf, leaf_starts_buf,
+                                    leaves_buf, leaves_capacity, left_buf, right_buf, info_buf, stream=stream)
+
+    def _range_call(self, tmp, trees, d_lo, d_hi, Q, stride, d_scr, d_first, d_starts, d_left, d_right, d_info):
+        def call(d_leaves, capacity):
+            self.range_async(d_lo, d_hi, Q, d_scr, d_first, d_starts, d_leaves, capacity, d_left, d_right, d_info)
+            return np.full(Q, stride, np.uint32)     # the tree's: the call writes none
+        return call
+
+    def range(self, lo, hi):
+        """The RangeProofs (tree 0 throughout) that show, to a holder of the root and the count, EVERY leaf in each closed interval
+        [lo[q], hi[q]] ([Q, 8] each, or one digest each).  The verdict binds when the tree is sorted: is_sorted()."""
+        self._absence_height()
+        return self._ranges(None, lo, hi, self.height)
 
     def multiproof_async(self, indices_buf, k, scratch_buf, nodes_buf, nodes_capacity, info_buf, stream=None):
         """ONE proof for the k leaves whose strictly increasing indices are in device memory, written to nodes_buf
@@ -2442,6 +2526,28 @@ class MerkleForest(_Stored):
         sorted: is_sorted()."""
         return self._absence(trees, digests, self.levels if stride is None else int(stride))
 
+    def range_async(self, trees_buf, lo_buf, hi_buf, Q, stride, scratch_buf, firsts_buf, leaf_starts_buf, leaves_buf, leaves_capacity, left_buf,
+                    right_buf, heights_buf, info_buf, stream=None):
+        """The range proofs of Q (tree, lo, hi) queries in device memory.  HipDevice.forest_range_enqueue."""
+        self.dev.forest_range_enqueue(self.digests, self.forest, self.total, self.offsets, self.ntrees, self.max_count, trees_buf, lo_buf, hi_buf, Q,
+                                      stride, scratch_buf, firsts_buf, leaf_starts_buf, leaves_buf, leaves_capacity, left_buf, right_buf, heights_buf,
+                                      info_buf, stream=stream)
+
+    def _range_call(self, tmp, trees, d_lo, d_hi, Q, stride, d_scr, d_first, d_starts, d_left, d_right, d_info):
+        d_trees, d_h = tmp.upload(trees), tmp.alloc(4 * Q)
+
+        def call(d_leaves, capacity):
+            self.range_async(d_trees, d_lo, d_hi, Q, stride, d_scr, d_first, d_starts, d_leaves, capacity, d_left, d_right, d_h, d_info)
+            return self.dev.download(d_h, 4 * Q)
+        return call
+
+    def ranges(self, trees, lo, hi, stride=None):
+        """The RangeProofs that show, to a holder of the roots and the counts, EVERY leaf of tree trees[q] in the closed interval
+        [lo[q], hi[q]] ([Q, 8] each): the leaves in range with the neighbour on either side that fences them, and the two rows of
+        nodes that close the run, read out of the stored levels (no hash).  A first call counts the leaves, a second carries them.
+        stride: cells per row, by default the forest's.  The verdict binds when the trees are sorted: is_sorted()."""
+        return self._ranges(trees, lo, hi, self.levels if stride is None else int(stride))
+
     def multiproof_async(self, trees_buf, indices_buf, k, scratch_buf, nodes_buf, nodes_capacity, heights_buf, info_buf, stream=None):
         """ONE proof for the k (tree, index) entries in device memory (strictly increasing pairs), written to nodes_buf
         (nodes_capacity cells) and heights_buf [k]; info_buf: 2 + levels uint64 (status, M, the per-level counts).
@@ -2929,6 +3035,103 @@ class AbsenceProofs:
                                               tmp.upload(roots) if roots.shape[0] else None, tmp.upload(counts) if roots.shape[0] else None,
                                               int(roots.shape[0]), d_verdict)
             return dev.download(d_verdict, 4 * Q)
+
+
+def _digests_below(rows, x):
+    """bool [n]: rows[i] < x in the order of the digests' bytes (word 0 first, every word unsigned); rows [n, 8], x [8]."""
+    differs = rows != x
+    first = np.argmax(differs, axis=1)
+    at = np.arange(rows.shape[0])
+    return differs.any(axis=1) & (rows[at, first] < x[first])
+
+
+def _digests_above(rows, x):
+    """bool [n]: rows[i] > x, as _digests_below."""
+    differs = rows != x
+    first = np.argmax(differs, axis=1)
+    at = np.arange(rows.shape[0])
+    return differs.any(axis=1) & (rows[at, first] > x[first])
+
+
+class RangeProofs:
+    """Q proofs that the leaves carried are ALL the leaves of a sorted tree in a closed interval (include/vkmr_hip.h, RANGE PROOFS):
+    query q is (`trees[q]`, `lo[q]`, `hi[q]`); its run, leaves `firsts[q]` onwards of the tree, lies at `leaves[leaf_starts[q] :
+    leaf_starts[q + 1]]` -- the leaves in range and the neighbour on either side that fences them --, `left` and `right` ([Q, stride,
+    8]) are the nodes that close the run at every level, `heights[q]` is the tree's and `info` the gather's four words.  Host arrays;
+    MerkleForest.ranges gathers one, a holder of the roots and the counts verifies it.  proofs[q] is query q's part as a dict."""
+
+    def __init__(self, trees, lo, hi, firsts, leaf_starts, leaves, left, right, heights, info=None):
+        self.trees, self.heights = (np.array(x, dtype=np.uint32).reshape(-1) for x in (trees, heights))
+        self.firsts, self.leaf_starts = (np.array(x, dtype=np.uint64).reshape(-1) for x in (firsts, leaf_starts))
+        Q = int(self.trees.shape[0])
+        self.lo, self.hi, self.leaves = (np.array(x, dtype=np.uint32).reshape(-1, 8) for x in (lo, hi, leaves))
+        self.left, self.right = (np.array(x, dtype=np.uint32) for x in (left, right))
+        self.info = np.zeros(4, np.uint64) if info is None else np.array(info, dtype=np.uint64).reshape(4)
+        if (any(a.shape[0] != Q for a in (self.heights, self.firsts, self.lo, self.hi)) or self.leaf_starts.shape[0] != Q + 1 or self.left.ndim != 3
+                or self.left.shape != self.right.shape or self.left.shape[0] != Q or self.left.shape[2] != 8 or not 1 <= self.stride <= 63):
+            raise ValueError("RangeProofs: one tree, lo, hi, first and height per query, Q + 1 leaf_starts; left and right [Q, stride, 8] with stride in 1..63")
+
+    Q = property(lambda self: int(self.trees.shape[0]))
+    stride = property(lambda self: int(self.left.shape[1]))
+
+    def __len__(self):
+        return self.Q
+
+    def _run(self, q):
+        q = int(q)
+        if not 0 <= q < self.Q:
+            raise IndexError(f"RangeProofs: query {q} of {self.Q}")
+        a, b = int(self.leaf_starts[q]), int(self.leaf_starts[q + 1])
+        if not a <= b <= self.leaves.shape[0]:
+            raise ValueError(f"RangeProofs: leaf_starts[{q}] and the one behind it do not lie in the leaves")
+        return self.leaves[a:b]
+
+    def __getitem__(self, q):
+        run = self._run(q)
+        q = int(q)
+        return {"tree": int(self.trees[q]), "lo": self.lo[q], "hi": self.hi[q], "first": int(self.firsts[q]), "leaves": run, "left": self.left[q],
+                "right": self.right[q], "height": int(self.heights[q])}
+
+    def in_range(self, q):
+        """The carried leaves of query q that lie in [lo[q], hi[q]] ([n, 8]); what verify() counts in in_count when it proves q."""
+        run = self._run(q)
+        if run.shape[0] == 0:
+            return run
+        keep = ~_digests_below(run, self.lo[int(q)]) & ~_digests_above(run, self.hi[int(q)])
+        return run[keep]
+
+    def same_as(self, other):
+        """Byte for byte: equal queries, firsts, leaf_starts, leaves, heights and cells, the zero ones included."""
+        names = ("trees", "lo", "hi", "firsts", "leaf_starts", "leaves", "left", "right", "heights")
+        return all(getattr(self, n).shape == getattr(other, n).shape and bool((getattr(self, n) == getattr(other, n)).all()) for n in names)
+
+    def verify(self, dev, roots, counts):
+        """(verdict uint32 [Q], in_first uint64 [Q], in_count uint64 [Q]): verdict 1 when the run of query q is proven complete under
+        roots[trees[q]] and counts[trees[q]] (roots [ntrees, 8], counts [ntrees]: the verifier's own tables), and then the leaves
+        inside the bounds as an index into the tree and a number; zeros otherwise."""
+        Q = self.Q
+        if Q == 0:
+            return np.zeros(0, np.uint32), np.zeros(0, np.uint64), np.zeros(0, np.uint64)
+        roots, counts = _host(roots, np.uint32, -1, 8), _host(counts, np.uint64, -1)
+        if roots.shape[0] != counts.shape[0]:
+            raise ValueError("RangeProofs.verify: one count per root")
+        n = int(self.leaves.shape[0])
+        with dev.scope() as tmp:
+            d_verdict, d_first, d_count = tmp.alloc(4 * Q), tmp.alloc(8 * Q), tmp.alloc(8 * Q)
+            dev.verify_forest_range_enqueue(tmp.upload(self.trees), tmp.upload(self.lo), tmp.upload(self.hi), tmp.upload(self.firsts),
+                                            tmp.upload(self.leaf_starts), tmp.upload(self.leaves) if n else None, n, tmp.upload(self.left),
+                                            tmp.upload(self.right), tmp.upload(self.heights), Q, self.stride,
+                                            tmp.upload(roots) if roots.shape[0] else None, tmp.upload(counts) if roots.shape[0] else None,
+                                            int(roots.shape[0]), tmp.alloc(dev.range_scratch_bytes(n, Q)), d_verdict, d_first, d_count)
+            return dev.download(d_verdict, 4 * Q), dev.download(d_first, 8 * Q, dtype=np.uint64), dev.download(d_count, 8 * Q, dtype=np.uint64)
+
+
+def range_status_text(status):
+    """The bits of vkmr_hip_forest_range_async's status word (info[0]), named."""
+    names = ["bit 0: more leaves are carried than the leaves buffer has cells (info[1] is the number)"] if status & 1 else []
+    if status & ~1:
+        names.append("unknown bits")
+    return "; ".join(names) if names else "ok"
 
 
 def sort_digests(digests, counts):

@@ -55,6 +55,7 @@ EXPECTED_HASH_BLOCKS = {"ELi64ELi5ELb1": 3,   # map_kernel MODE 5 (two blocks pe
                         "consistency_fold_kernel": 1,   # both root walks of a consistency check through one hash_pair: one loop, operands selected
                         "proofs_at_edge_kernel": 1,   # the old tree's right edge, a lane per epoch: one loop over the levels, operands selected
                         "forest_absence_fold_kernel": 1, "tree_absence_fold_kernel": 1,   # an absence proof's two folds, a lane per proof: one ballot-driven loop, operands selected
+                        "forest_range_level_kernel": 1, "tree_range_level_kernel": 1,   # a range proof's fold, a launch per level and a lane per node: operands chosen by pointer
                         "map_persist_kernel": 4, "map_hash_sorted_kernel": 2}   # the last two: experiments build (staged + per-lane loop; block + digest)
 
 _INSTR = re.compile(r"^\s+([a-z_0-9]+)\s*(.*)$")
