@@ -47,6 +47,8 @@
 #   range [args]           tools/range_timing.py: range proofs over sorted trees (2^26 leaves as 2^15 trees of 2 048 and as one tree): gather, check and
 #                          counting call for 2^10, 2^16 and 2^20 ranges of 16 leaves, 2^10 ranges of 2^16, every tree whole, beside the parent's route
 #                          (vkmr_hip_forest_multiproof_async over explicit entries and its check) and vkmr_hip_reduce_forest_async (one JSON line)
+#   sorted_set [args]      tests/test_gpu_sorted_set.py: every shape of a sorted tree of up to 40 leaves and the walk of a sorted set, each test with its
+#                          duration (pytest --durations=0; further pytest arguments are passed on)
 #   forest_repack [args]   tools/forest_repack_timing.py: the oldest trees of a stored forest dropped and the rest (or all) copied into an
 #                          empty forest, beside the stored build over the same leaves (one JSON line)
 #   cumask                 tools/cu_mask_probe.py: where CU-mask bits land, map/reduce on half the CUs with and without neighbours
@@ -258,6 +260,11 @@ range)
   timeout -k 10 900 python3 tools/range_timing.py "$@" --out $OUT/range_timing.json > /dev/null 2> $OUT/range_timing.err && echo "range_timing ok" &&
   cat $OUT/range_timing.json
   echo "range rc=$?"
+  ;;
+sorted_set)
+  timeout -k 10 600 python -m pytest tests/test_gpu_sorted_set.py -m gpu -q --durations=0 "$@" > $OUT/pytest_sorted_set.log 2>&1 && echo "sorted_set ok" &&
+  grep -E "passed|call " $OUT/pytest_sorted_set.log || tail -40 $OUT/pytest_sorted_set.log
+  echo "sorted_set rc=$?"
   ;;
 forest_repack)
   timeout -k 10 500 python3 tools/forest_repack_timing.py "$@" --out $OUT/forest_repack_timing.json > /dev/null 2> $OUT/forest_repack_timing.err && echo "forest_repack_timing ok" &&
