@@ -22,6 +22,16 @@
  * completed (reference: a Batch is freed when its Mapping retires,
  * src/vkmr/Mappings.cpp:328-329; a Slice when its Reduction retires,
  * src/vkmr/Reductions.cpp:663).
+ *
+ * Scratch buffers: every entry point with a `scratch_dev` parameter names the size function that sizes it, and all of them
+ * keep one contract, so that a caller may recycle one scratch across calls.  (1) What the scratch holds on entry does not
+ * matter: the call clears or writes whatever it reads, and the result is the same from zeros, from 0xFF or from another call's
+ * leftovers.  (2) The call reads and writes only the bytes the size function named for its arguments, from scratch_dev on.
+ * (3) The next call may take the same scratch on the same stream with no wait in between: the stream orders them.  Calls on
+ * different streams need a scratch each.  scratch_dev must be 16-byte aligned -- 8-byte for vkmr_hip_forest_find_async and
+ * vkmr_hip_tree_find_async -- and no stricter alignment is ever needed; the size functions return whole multiples of that
+ * alignment, except vkmr_hip_multiproof_scratch_bytes and vkmr_hip_sizes_scratch_bytes, which return the bare layout in whole
+ * 4-byte words.  tests/scratch_cases.py holds a row per such entry point.
  */
 #ifndef VKMR_HIP_H
 #define VKMR_HIP_H
@@ -151,7 +161,7 @@ VKMR_API vkmr_status vkmr_hip_map_async(int dev, vkmr_stream s,
  *   digests_dev  count cells, read only (the reference reduces in place)
  *   scratch_dev  vkmr_hip_reduce_scratch_bytes(count) bytes of device memory; the size function is an
  *                upper bound for EVERY run of at most `count` digests, so scratch sized for a slice's
- *                capacity serves any shorter slice (may be NULL for count <= 128)
+ *                capacity serves any shorter slice (may be NULL for count <= 128); 16-byte aligned, see "Scratch buffers"
  *   root_dev     one cell in device memory receiving the root
  * height is at most 63.
  */
@@ -167,7 +177,7 @@ VKMR_API size_t vkmr_hip_reduce_scratch_bytes(uint64_t count);
  * device over PCIe may send the 16-bit sizes (2 bytes per string instead of 8) and have the entries written in device
  * memory, where vkmr_hip_map_async reads them.  Every size must be below 65 536 (send the entries themselves otherwise).
  *   sizes_dev    count sizes, 16-byte aligned
- *   scratch_dev  vkmr_hip_sizes_scratch_bytes(count) bytes
+ *   scratch_dev  vkmr_hip_sizes_scratch_bytes(count) bytes, 16-byte aligned (see "Scratch buffers")
  *   meta_dev     count entries, 16-byte aligned, written
  */
 VKMR_API vkmr_status vkmr_hip_metadata_from_sizes_async(int dev, vkmr_stream s, const uint16_t* sizes_dev, uint32_t count,
@@ -182,7 +192,7 @@ VKMR_API size_t vkmr_hip_sizes_scratch_bytes(uint32_t count);
  * (src/vkmr/SHA-256vk.cpp:301-311) issued as one operation, so that the
  * latency-bound tops of the sub-trees run side by side instead of one after the
  * other.  Same per-slice contract as vkmr_hip_reduce_async.  scratch_dev needs
- * vkmr_hip_reduce_slices_scratch_bytes(capacity, nslices).
+ * vkmr_hip_reduce_slices_scratch_bytes(capacity, nslices) bytes, 16-byte aligned (see "Scratch buffers").
  */
 VKMR_API vkmr_status vkmr_hip_reduce_slices_async(int dev, vkmr_stream s,
                                                   const vkmr_digest* digests_dev, uint32_t nslices,
@@ -202,7 +212,7 @@ VKMR_API size_t vkmr_hip_reduce_slices_scratch_bytes(uint64_t capacity, uint32_t
  * (height = log2 capacity) and one over the slice roots.  Each sibling is the root of
  * the neighbouring sub-tree of 2^l leaves and is computed with the same kernels as the
  * reduction (total work: about one more reduction of the slice).
- * scratch_dev: vkmr_hip_reduce_scratch_bytes(count) bytes.
+ * scratch_dev: vkmr_hip_reduce_scratch_bytes(count) bytes, 16-byte aligned (see "Scratch buffers").
  */
 VKMR_API vkmr_status vkmr_hip_proof_async(int dev, vkmr_stream s,
                                           const vkmr_digest* digests_dev, uint64_t count, uint32_t height,
@@ -217,7 +227,8 @@ VKMR_API vkmr_status vkmr_hip_proof_async(int dev, vkmr_stream s,
  * stores the other node of that pair.  indices[0..k): leaf indices (< count), k <= 16, read on
  * the host at call time.  siblings_dev[q * height + l] = sibling of indices[q]'s path node at
  * level l, as vkmr_hip_proof_async defines it; no extra hash is computed, the reduction's time
- * does not change measurably.  vkmr_hip_proof_async is kept as the independent cross-check.
+ * does not change measurably.  vkmr_hip_proof_async is kept as the independent cross-check.  scratch_dev: as vkmr_hip_reduce_async
+ * takes it, 16-byte aligned (see "Scratch buffers").
  */
 VKMR_API vkmr_status vkmr_hip_reduce_proofs_async(int dev, vkmr_stream s,
                                                   const vkmr_digest* digests_dev, uint64_t count, uint32_t height,
@@ -228,7 +239,7 @@ VKMR_API vkmr_status vkmr_hip_reduce_proofs_async(int dev, vkmr_stream s,
  * One tree level per launch, one lane per pair: the reference's non-subgroup
  * reduction (BasicReduction, src/vkmr/Reductions.cpp:257-409; shader :393-434).
  * Kept as an independent cross-check of vkmr_hip_reduce_async; same contract.
- * scratch_dev needs vkmr_hip_reduce_levels_scratch_bytes(count).
+ * scratch_dev needs vkmr_hip_reduce_levels_scratch_bytes(count) bytes, 16-byte aligned (see "Scratch buffers").
  */
 VKMR_API vkmr_status vkmr_hip_reduce_levels_async(int dev, vkmr_stream s,
                                                   const vkmr_digest* digests_dev, uint64_t count, uint32_t height,
@@ -1489,7 +1500,7 @@ VKMR_API vkmr_status vkmr_hip_tree_merge_leaves_async(int dev, vkmr_stream s, co
  * one more launch on the caller's stream: no allocation, no synchronisation.  For n == 1 the
  * reference prints the slice root itself (src/vkmr/Reductions.cpp:692-701); callers do the same
  * and do not call combine.
- *   scratch_dev  vkmr_hip_reduce_scratch_bytes(n) bytes; may be NULL for n <= 128
+ *   scratch_dev  vkmr_hip_reduce_scratch_bytes(n) bytes, 16-byte aligned (see "Scratch buffers"); may be NULL for n <= 128
  */
 VKMR_API vkmr_status vkmr_hip_combine_async(int dev, vkmr_stream s, const vkmr_digest* roots_dev, uint32_t n,
                                             void* scratch_dev, vkmr_digest* root_dev);

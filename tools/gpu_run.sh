@@ -49,6 +49,9 @@
 #                          (vkmr_hip_forest_multiproof_async over explicit entries and its check) and vkmr_hip_reduce_forest_async (one JSON line)
 #   sorted_set [args]      tests/test_gpu_sorted_set.py: every shape of a sorted tree of up to 40 leaves and the walk of a sorted set, each test with its
 #                          duration (pytest --durations=0; further pytest arguments are passed on)
+#   scratch [args]         tests/test_gpu_scratch.py: every entry point that takes a scratch_dev from dirty scratch of exactly its size (0x00, 0xFF,
+#                          random words, another call's leftovers) and back to back on one stream, each case with its duration (pytest
+#                          --durations=0; further pytest arguments are passed on)
 #   forest_repack [args]   tools/forest_repack_timing.py: the oldest trees of a stored forest dropped and the rest (or all) copied into an
 #                          empty forest, beside the stored build over the same leaves (one JSON line)
 #   cumask                 tools/cu_mask_probe.py: where CU-mask bits land, map/reduce on half the CUs with and without neighbours
@@ -265,6 +268,11 @@ sorted_set)
   timeout -k 10 600 python -m pytest tests/test_gpu_sorted_set.py -m gpu -q --durations=0 "$@" > $OUT/pytest_sorted_set.log 2>&1 && echo "sorted_set ok" &&
   grep -E "passed|call " $OUT/pytest_sorted_set.log || tail -40 $OUT/pytest_sorted_set.log
   echo "sorted_set rc=$?"
+  ;;
+scratch)
+  timeout -k 10 600 python -m pytest tests/test_gpu_scratch.py -m gpu -q --durations=0 "$@" > $OUT/pytest_scratch.log 2>&1 && echo "scratch ok" &&
+  grep -E "passed|call " $OUT/pytest_scratch.log || tail -60 $OUT/pytest_scratch.log
+  echo "scratch rc=$?"
   ;;
 forest_repack)
   timeout -k 10 500 python3 tools/forest_repack_timing.py "$@" --out $OUT/forest_repack_timing.json > /dev/null 2> $OUT/forest_repack_timing.err && echo "forest_repack_timing ok" &&
